@@ -18,6 +18,11 @@ PCM already resident in HBM, outputs left in HBM.  One process per GPU; rank 0 p
 --config shard (alias headline): the per-GPU shard of configs[3] with clips of the configs[1] shape (64 x 3-minute
     clips per GPU).  Weak scaling.
 --config cqt: configs[2] -- 64 x 30 s polyphonic clips through the 84-bin constant-Q filter bank (MFMA path).
+
+A plain run sets up, warms up, times the steps and prints the line (the timed steps' own figures: rate, ms_per_step,
+per-kernel times and roofline).  --full adds everything else the line can carry: the note events and `outputs_check`
+digest of the last step, the sub-records above, the CQT's host-buffer entry and the CPU baseline (--no-extras and
+--no-cpu-baseline drop parts of it again).  --dump-outputs DIR writes the last timed step's outputs as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -99,26 +104,47 @@ def outputs_digest(host, frame_off, clip_ids):
     return total
 
 
-def make_folder_clips(indices, durations):
+def _base_track(kind, k):
+    from tools import signals
+    if kind == "polyphonic":
+        return signals.polyphonic_clip(330.0, SR, seed=700 + k)
+    if kind == "noisy":
+        return signals.guitar_clip(330.0, SR, seed=700 + k, noise_dbfs=-12.0)
+    return signals.guitar_clip(330.0, SR, seed=700 + k)
+
+
+def folder_base_tracks(indices, workers=1):
+    """k -> the 330 s base track of kind k (= i mod 8) for the clips `indices`.  workers > 1 synthesises the tracks in
+    that many fresh processes (spawned, not forked: the caller may hold the GPU runtime); the tracks are the same."""
+    kinds = sorted({i % 8 for i in indices})
+    jobs = [(FOLDER_KINDS[k], k) for k in kinds]
+    if workers <= 1 or len(kinds) <= 1:
+        return {k: _base_track(*j) for k, j in zip(kinds, jobs)}
+    import multiprocessing as mp
+    from concurrent.futures import ProcessPoolExecutor
+    with ProcessPoolExecutor(max_workers=min(workers, len(kinds)), mp_context=mp.get_context("spawn")) as pool:
+        return dict(zip(kinds, pool.map(_base_track, *zip(*jobs))))
+
+
+def folder_cut(i, durations, track_len):
+    """Where clip i of the folder comes from: (first sample in its base track, samples, gain).  The clip is the base
+    track read circularly from that sample on, times the gain in float32."""
+    rng = np.random.default_rng(10_000 + i)
+    n = int(durations[i] * SR)
+    start = int(rng.integers(0, track_len))
+    return start, n, np.float32(rng.uniform(0.5, 1.0))
+
+
+def make_folder_clips(indices, durations, base=None):
     """The clips `indices` of the folder.  Clip i is cut, at a seeded offset and gain, from one of eight 330 s base
     tracks chosen by i mod 8: six monophonic guitar tracks, one three-voice polyphonic track, one guitar track under a
-    -12 dBFS noise floor (where the Viterbi's exact prunes fire least)."""
-    from tools import signals
-    kinds = sorted({i % 8 for i in indices})
-    base = {}
-    for k in kinds:
-        if FOLDER_KINDS[k] == "polyphonic":
-            base[k] = signals.polyphonic_clip(330.0, SR, seed=700 + k)
-        elif FOLDER_KINDS[k] == "noisy":
-            base[k] = signals.guitar_clip(330.0, SR, seed=700 + k, noise_dbfs=-12.0)
-        else:
-            base[k] = signals.guitar_clip(330.0, SR, seed=700 + k)
+    -12 dBFS noise floor (where the Viterbi's exact prunes fire least).  base: folder_base_tracks(indices), if made."""
+    base = folder_base_tracks(indices) if base is None else base
     clips = []
     for i in indices:
-        rng = np.random.default_rng(10_000 + i)
         b = base[i % 8]
-        n = int(durations[i] * SR)
-        y = np.roll(b, -int(rng.integers(0, len(b))))[:n] * np.float32(rng.uniform(0.5, 1.0))
+        start, n, gain = folder_cut(i, durations, len(b))
+        y = np.roll(b, -start)[:n] * gain
         clips.append(np.ascontiguousarray(y, dtype=np.float32))
     return clips
 
@@ -247,6 +273,44 @@ def launch_ranks(n):
 
 
 # --------------------------------------------------------------------------------------------- one rank
+def folder_pcm(indices, durations, base, dev):
+    """The clips `indices` of make_folder_clips, concatenated in one float32 tensor on `dev`.  Only the base tracks
+    cross to the device; each clip is cut and scaled there (the same float32 products)."""
+    import torch
+    d_base = {k: torch.from_numpy(b).to(dev) for k, b in base.items()}
+    cuts = [(d_base[i % 8],) + folder_cut(i, durations, len(base[i % 8])) for i in indices]
+    pcm = torch.empty(max(1, sum(n for _, _, n, _ in cuts)), dtype=torch.float32, device=dev)
+    o = 0
+    for b, start, n, gain in cuts:
+        head = min(n, len(b) - start)
+        torch.mul(b[start:start + head], float(gain), out=pcm[o:o + head])
+        torch.mul(b[:n - head], float(gain), out=pcm[o + head:o + n])
+        o += n
+    return pcm
+
+
+DUMP_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir, arrays, prefix="", budget=DUMP_BYTES):
+    """Write `arrays` (name -> tensor, frames along dim 0, one frame count) as out_dir/<prefix><name>.npy: float64
+    tensors as float64, the rest as float32 (exact for their values).  If they would pass `budget` bytes, the same
+    seeded sample of frames is written in every run, its indices as <prefix>frame_index.npy."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    dtypes = {k: np.float64 if t.dtype == torch.float64 else np.float32 for k, t in arrays.items()}
+    n = len(next(iter(arrays.values())))
+    frame_bytes = sum(np.dtype(dtypes[k]).itemsize * (t[0].numel() if n else 1) for k, t in arrays.items())
+    idx = None
+    if n * frame_bytes > budget:
+        idx = np.sort(np.random.default_rng(0).choice(n, budget // (frame_bytes + 8), replace=False))
+        np.save(os.path.join(out_dir, prefix + "frame_index.npy"), idx.astype(np.float64))
+    for k, t in arrays.items():
+        if idx is not None:
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(out_dir, prefix + k + ".npy"), t.cpu().numpy().astype(dtypes[k]))
+
+
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -260,9 +324,13 @@ def parse_args():
     ap.add_argument("--cpu-sample-seconds", type=float, default=240.0, help="oracle sample (A), about 15 s of CPU work")
     ap.add_argument("--cpu-turbo-seconds", type=float, default=120.0, help="oracle sample (B) Turbo Mode; 0 skips it")
     ap.add_argument("--cpu-turbo-cores", type=int, default=0, help="Turbo pool size; 0 = os.cpu_count() like the reference")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the events and outputs digest, the sub-records and the CPU baseline (off: the timed steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32/float64, at most 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the uniform_shard / host_inclusive / engine_e2e sub-records (profiling runs)")
+                    help="with --full: skip the uniform_shard / host_inclusive / engine_e2e sub-records (profiling runs)")
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
                     help="test hook: every rank uses cuda:0 and the gloo backend (multi-rank path on a 1-GPU box)")
     return ap.parse_args()
@@ -298,15 +366,19 @@ def run_cqt(args, rank, world, dev, fence, reduce_max, reduce_sum):
         kms += handle.kernel_ms("cqt")
     fence()
     wall_dev = time.perf_counter() - t0
-    handle.cqt(clips)
-    fence()
-    t0 = time.perf_counter()
-    handle.cqt(clips)
-    fence()
-    wall = (time.perf_counter() - t0) * args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"cqt": d_out.view(frames, 84)}, prefix="" if world == 1 else f"rank{rank}_",
+                     budget=DUMP_BYTES // world)
+    wall = None
+    if args.full:
+        handle.cqt(clips)
+        fence()
+        t0 = time.perf_counter()
+        handle.cqt(clips)
+        fence()
+        wall = reduce_max((time.perf_counter() - t0) * args.steps)
     wall_dev = reduce_max(wall_dev)
     kernel_s = reduce_max(kms * 1e-3)
-    wall = reduce_max(wall)
     total_audio = reduce_sum(audio_seconds)
     if rank != 0:
         return None
@@ -322,7 +394,7 @@ def run_cqt(args, rank, world, dev, fence, reduce_max, reduce_sum):
     issued = ksteps * 2048.0 * col_tiles
     useful = 4.0 * sum(ilen) * frames
     per_launch_s = kernel_s / args.steps
-    return {
+    line = {
         "metric": "audio-seconds through the 84-bin CQT filter bank/sec (44.1 kHz, hop=512)",
         "value": round(total_audio * args.steps / wall_dev, 2), "unit": "audio-seconds/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(wall_dev / args.steps * 1e3, 3),
@@ -330,14 +402,16 @@ def run_cqt(args, rank, world, dev, fence, reduce_max, reduce_sum):
         "config": {"workload": "configs[2]: 64 x 30 s polyphonic clips (3 Karplus-Strong voices), CQT C1 + 84 bins, 12 per octave",
                    "clips_per_gpu": 64, "clip_seconds": 30.0, "sample_rate": SR, "hop_length": HOP, "frames_per_gpu": frames,
                    "timed": "aegis_cqt_device (PCM and magnitudes resident in HBM), wall clock between the fences; the kernel's "
-                            "own HIP-event time feeds the roofline; the host-buffer entry's wall time beside it"},
+                            "own HIP-event time feeds the roofline; the host-buffer entry's wall time beside it (--full)"},
         "roofline": {"bound": "mfma", "kernel": "cqt_slide", "achieved": round(issued / per_launch_s / 1e12, 2),
                      "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(issued / per_launch_s / 1e12 / MFMA_F32_PEAK_TFLOPS, 4),
                      "frac_useful": round(useful / per_launch_s / 1e12 / MFMA_F32_PEAK_TFLOPS, 4),
                      "issued_flop_per_launch": int(issued), "useful_flop_per_launch": int(useful), "traffic": None},
         "kernel_ms": round(per_launch_s * 1e3, 3),
-        "host_inclusive_ms_per_step": round(wall / args.steps * 1e3, 3),
     }
+    if wall is not None:
+        line["host_inclusive_ms_per_step"] = round(wall / args.steps * 1e3, 3)
+    return line
 
 
 def main():
@@ -407,16 +481,20 @@ def main():
     from spectrogram_midi_amd import _lib, dist as adist, events_native
 
     # ---- this rank's clips ---------------------------------------------------------------------------
+    extras = args.full and not args.no_extras
     if args.config == "folder":
         durations = folder_durations(args.folder_clips)
         shards = adist.shard_clips(durations, world)
         mine = shards[rank]
-        clips = make_folder_clips(mine, durations)
+        cpus = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+        base = folder_base_tracks(mine, workers=max(1, cpus // world))
+        clips = make_folder_clips(mine, durations, base) if extras else None     # host copies for the host-buffer entries
         clip_ids = list(mine)
+        n_samples = np.array([int(durations[i] * SR) for i in mine], dtype=np.int64)
     else:
         clips = make_clips(args.clips, args.clip_seconds, seed0=1000 * rank + 1)
         clip_ids = [rank * args.clips + i for i in range(len(clips))]
-    n_samples = np.array([len(c) for c in clips], dtype=np.int64)
+        n_samples = np.array([len(c) for c in clips], dtype=np.int64)
     offsets = np.concatenate([[0], np.cumsum(n_samples)]).astype(np.int64)
     audio_seconds = float(n_samples.sum()) / SR
     total_frames = int((n_samples // HOP + 1).sum())
@@ -426,9 +504,14 @@ def main():
     frame_counts = [handle.frames_for(int(n)) for n in n_samples]
     frames = int(sum(frame_counts))
 
-    d_pcm = torch.empty(max(1, int(offsets[-1])), dtype=torch.float32, device=dev)
-    for c, o in zip(clips, offsets[:-1]):          # clip by clip: no second host copy of the folder
-        d_pcm[int(o):int(o) + len(c)].copy_(torch.from_numpy(c))
+    # after the Handle: it sizes its passes from the device memory free when it is made
+    if args.config == "folder":
+        d_pcm = folder_pcm(mine, durations, base, dev)
+        del base
+    else:
+        d_pcm = torch.empty(max(1, int(offsets[-1])), dtype=torch.float32, device=dev)
+        for c, o in zip(clips, offsets[:-1]):          # clip by clip: no second host copy of the clips
+            d_pcm[int(o):int(o) + len(c)].copy_(torch.from_numpy(c))
 
     def device_outputs(n_frames):
         t = {"f0": torch.empty(n_frames, dtype=torch.float64, device=dev),
@@ -474,32 +557,38 @@ def main():
     frames_all_ranks = reduce_sum(frames)
     rank_busy_ms = [round(b / args.steps * 1e3, 3) for b in gather_floats(busy)]
     rank_audio = [round(a, 1) for a in gather_floats(audio_seconds)]
+    if args.dump_outputs:
+        # raw_data as AegisEngine hands it out: f0 0 where unvoiced (np.nan_to_num); frames of this rank's clips in batch
+        # order (clip_ids: longest first for the folder)
+        dump_outputs(args.dump_outputs, dict(d_out, f0=torch.nan_to_num(d_out["f0"], nan=0.0)),
+                     prefix="" if world == 1 else f"rank{rank}_", budget=DUMP_BYTES // world)
 
     # ---- note events of this rank's clips, gathered on rank 0 (the only exchange of the job) -----------
-    t0 = time.perf_counter()
-    host = {k: v.cpu().numpy() for k, v in d_out.items()}
-    f_off = np.concatenate([[0], np.cumsum(frame_counts)]).astype(np.int64)
-    ev_packed, _ = events_native.extract_batch(f_off, host["rake_mask"], host["f0"], host["voiced_flag"],
-                                               host["voiced_prob"], host["rms"], SR, HOP, 0.70, packed=True,
-                                               pitch_bin=host["pitch_bin"], freqs=handle.table("freqs"))
-    local_rows = adist.rows_from_packed(ev_packed, clip_ids)
-    events_ms = (time.perf_counter() - t0) * 1e3
-    digest = int(reduce_sum(float(outputs_digest(host, f_off, clip_ids))))    # exact in float64: < 2**41
-    gather_ms, n_events = None, int(local_rows.shape[0])
-    if world > 1:
-        fence()
+    if args.full:
         t0 = time.perf_counter()
-        gathered = adist.gather_events(local_rows, dst=0, device=red_dev)
-        fence()
-        gather_ms = (time.perf_counter() - t0) * 1e3
-        if rank == 0:
-            n_events = int(gathered.shape[0])
-            assert len(set(gathered[:, 0].astype(int))) <= (args.folder_clips if args.config == "folder" else world * args.clips)
-    events_ms = reduce_max(events_ms)
+        host = {k: v.cpu().numpy() for k, v in d_out.items()}
+        f_off = np.concatenate([[0], np.cumsum(frame_counts)]).astype(np.int64)
+        ev_packed, _ = events_native.extract_batch(f_off, host["rake_mask"], host["f0"], host["voiced_flag"],
+                                                   host["voiced_prob"], host["rms"], SR, HOP, 0.70, packed=True,
+                                                   pitch_bin=host["pitch_bin"], freqs=handle.table("freqs"))
+        local_rows = adist.rows_from_packed(ev_packed, clip_ids)
+        events_ms = (time.perf_counter() - t0) * 1e3
+        digest = int(reduce_sum(float(outputs_digest(host, f_off, clip_ids))))    # exact in float64: < 2**41
+        gather_ms, n_events = None, int(local_rows.shape[0])
+        if world > 1:
+            fence()
+            t0 = time.perf_counter()
+            gathered = adist.gather_events(local_rows, dst=0, device=red_dev)
+            fence()
+            gather_ms = (time.perf_counter() - t0) * 1e3
+            if rank == 0:
+                n_events = int(gathered.shape[0])
+                assert len(set(gathered[:, 0].astype(int))) <= (args.folder_clips if args.config == "folder" else world * args.clips)
+        events_ms = reduce_max(events_ms)
 
     # ---- sub-records of the same run ("H2D included and reported separately") ----------------
     host_inclusive = engine_e2e = uniform_shard = single_clip = None
-    if not args.no_extras:
+    if extras:
         import io
         from spectrogram_midi_amd.engine import AegisEngine
         handle.set_profiling(False)
@@ -673,17 +762,18 @@ def main():
                          "kernel_ms": {k: round(v, 3) for k, v in kernel_ms.items()}},
             "roofline_compute": roofline_compute,
             "voiced_fraction": round(voiced, 4),
-            # the outputs of the last timed step (all ranks), held to the digest of the outputs the GPU test verified
-            "outputs_check": {"digest": digest,
-                              "expected": FOLDER_DIGEST_EXPECTED if default_folder else None,
-                              "match": (digest == FOLDER_DIGEST_EXPECTED) if (default_folder and FOLDER_DIGEST_EXPECTED is not None) else None,
-                              "what": "sum over clips of crc32(voiced_flag, rake_mask, rms, voiced_prob, f0) seeded with the clip index; "
-                                      "expected = tests/test_gpu_engine.py::test_folder_512_clips_one_dense_pass"},
             "rank_busy_ms": rank_busy_ms, "rank_audio_seconds": rank_audio,
-            "events": {"count": n_events, "extract_ms": round(events_ms, 2),
-                       "gather_ms": None if gather_ms is None else round(gather_ms, 3),
-                       "backend": None if world == 1 else ("gloo" if args.rehearse_on_one_gpu else "nccl (RCCL)")},
         }
+        if args.full:
+            # the outputs of the last timed step (all ranks), held to the digest of the outputs the GPU test verified
+            line["outputs_check"] = {
+                "digest": digest, "expected": FOLDER_DIGEST_EXPECTED if default_folder else None,
+                "match": (digest == FOLDER_DIGEST_EXPECTED) if (default_folder and FOLDER_DIGEST_EXPECTED is not None) else None,
+                "what": "sum over clips of crc32(voiced_flag, rake_mask, rms, voiced_prob, f0) seeded with the clip index; "
+                        "expected = tests/test_gpu_engine.py::test_folder_512_clips_one_dense_pass"}
+            line["events"] = {"count": n_events, "extract_ms": round(events_ms, 2),
+                              "gather_ms": None if gather_ms is None else round(gather_ms, 3),
+                              "backend": None if world == 1 else ("gloo" if args.rehearse_on_one_gpu else "nccl (RCCL)")}
         line["uniform_shard"], line["host_inclusive"], line["engine_e2e"] = uniform_shard, host_inclusive, engine_e2e
         line["single_clip"] = single_clip
         if vstats is not None and vstats["wave_steps"] > 0:
@@ -693,7 +783,7 @@ def main():
         # calls the library repeated with one Viterbi launch per time chunk because its single launch per pass found no
         # frame stage running beside it (0 unless something serialises kernels, e.g. a counter-collecting profiler)
         line["persistent_fallbacks"] = int(handle.debug_fetch("persistent_fallbacks")[0])
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args.cpu_sample_seconds, args.cpu_turbo_seconds, args.cpu_turbo_cores)
     finish(line)
 

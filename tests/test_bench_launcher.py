@@ -40,6 +40,7 @@ def test_folder_workload_matches_configs3():
     finally:
         sys.argv = argv
     assert a.config == "folder" and a.folder_clips == 512 and a.gpus == 1      # the driver's bare run = configs[3] as written
+    assert not a.full and a.dump_outputs is None                              # ... and times the steps alone
     d = bench.folder_durations(512)
     assert len(d) == 512 and d.min() >= 30 and d.max() <= 330 and abs(d.mean() - 180) < 10
     np.testing.assert_array_equal(d, bench.folder_durations(512))        # seeded
@@ -53,10 +54,86 @@ def test_folder_workload_matches_configs3():
     assert np.std(clips[1]) > np.std(clips[2]) * 0.5
 
 
+@pytest.mark.parametrize("device", ["cpu", pytest.param("cuda", marks=pytest.mark.gpu)])
+def test_folder_pcm_is_the_host_clips(device):
+    """bench.py cuts the folder's clips on the device from base tracks synthesised in worker processes: the same float32
+    samples, in the same order, as make_folder_clips (serial synthesis, host cut).  Clips 6, 8 and 15 wrap round the end
+    of their base track, 0 and 7 do not."""
+    import torch
+    d = bench.folder_durations(512)
+    idx = [0, 6, 7, 8, 15]
+    want = bench.make_folder_clips(idx, d)
+    base = bench.folder_base_tracks(idx, workers=3)
+    pcm = bench.folder_pcm(idx, d, base, torch.device(device)).cpu().numpy()
+    assert pcm.dtype == np.float32
+    np.testing.assert_array_equal(pcm, np.concatenate(want))
+    np.testing.assert_array_equal(np.concatenate(bench.make_folder_clips(idx, d, base)), pcm)
+
+
+def test_dump_outputs_writes_float_arrays_and_a_fixed_sample(tmp_path):
+    """--dump-outputs: float64 stays float64, the integer and float32 outputs are written as float32; past the byte budget
+    the same seeded sample of frames is written in every run, with its frame indices."""
+    import torch
+    n = 5000
+    rng = np.random.default_rng(1)
+    arrays = {"f0": torch.from_numpy(rng.uniform(80, 900, n)), "rms": torch.from_numpy(rng.random(n).astype(np.float32)),
+              "voiced_flag": torch.from_numpy((rng.random(n) < 0.5).astype(np.uint8)),
+              "pitch_bin": torch.from_numpy(rng.integers(-1, 360, n).astype(np.int16))}
+    bench.dump_outputs(str(tmp_path / "all"), arrays)
+    got = {k: np.load(tmp_path / "all" / f"{k}.npy") for k in arrays}
+    assert got["f0"].dtype == np.float64 and all(got[k].dtype == np.float32 for k in ("rms", "voiced_flag", "pitch_bin"))
+    for k, t in arrays.items():
+        np.testing.assert_array_equal(got[k], t.numpy())
+    assert not (tmp_path / "all" / "frame_index.npy").exists()
+    budget = 28_000                                    # 8 + 3 x 4 B per frame + its 8 B index: 1 000 frames
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), arrays, prefix="rank1_", budget=budget)
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == sorted(["rank1_frame_index.npy"] + [f"rank1_{k}.npy" for k in arrays])
+    assert sum((tmp_path / "a" / f).stat().st_size for f in files) <= budget + 128 * len(files)     # + .npy headers
+    idx = np.load(tmp_path / "a" / "rank1_frame_index.npy")
+    assert idx.dtype == np.float64 and len(idx) == 1000 and np.all(np.diff(idx) > 0)
+    for f in files:
+        np.testing.assert_array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "rank1_f0.npy"), arrays["f0"].numpy()[idx.astype(np.int64)])
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_and_dumps_their_outputs(tmp_path):
+    """`bench.py` without --full: the headline fields, nothing measured after the steps; --dump-outputs writes what the
+    timed device entry computed in its last step -- the outputs of the host-buffer entry on the same clips."""
+    out = tmp_path / "out"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--config", "folder",
+           "--folder-clips", "6", "--dump-outputs", str(out)]
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["unit"] == "audio-seconds/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+    assert "cpu_baseline" not in line and "outputs_check" not in line and "events" not in line
+    assert line["host_inclusive"] is None and line["engine_e2e"] is None and line["uniform_shard"] is None
+    from spectrogram_midi_amd import _lib, dist
+    d = bench.folder_durations(6)
+    mine = dist.shard_clips(d, 1)[0]                                   # the rank's batch order: longest first
+    clips = bench.make_folder_clips(mine, d)
+    h = _lib.Handle()
+    res = h.analyze_batch(clips, want_sdb=False)
+    h.close()
+    assert not (out / "frame_index.npy").exists()                      # 6 clips: every frame fits in 64 MB
+    for k in ("f0", "voiced_flag", "voiced_prob", "rms", "rake_mask"):
+        got = np.load(out / f"{k}.npy")
+        want = np.concatenate([np.nan_to_num(x[k]) if k == "f0" else x[k] for x in res])
+        assert got.dtype == (np.float64 if k in ("f0", "voiced_prob") else np.float32)
+        np.testing.assert_array_equal(got, want.astype(got.dtype), err_msg=k)
+
+
 @pytest.mark.gpu
 def test_bare_gpus_2_runs_two_ranks_and_gathers_events():
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--config", "shard",
-           "--clips", "3", "--clip-seconds", "8", "--no-cpu-baseline", "--rehearse-on-one-gpu"]
+           "--clips", "3", "--clip-seconds", "8", "--no-cpu-baseline", "--rehearse-on-one-gpu", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -74,7 +151,7 @@ def test_bare_gpus_2_runs_two_ranks_and_gathers_events():
 @pytest.mark.gpu
 def test_folder_mode_two_ranks():
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--config", "folder",
-           "--folder-clips", "6", "--no-cpu-baseline", "--rehearse-on-one-gpu"]
+           "--folder-clips", "6", "--no-cpu-baseline", "--rehearse-on-one-gpu", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]

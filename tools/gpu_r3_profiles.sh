@@ -6,9 +6,9 @@ cd /root/repo
 O=/root/repo/gpurun_out/r3prof; mkdir -p $O
 export TMPDIR=/tmp
 # the driver's line: bare bench.py = configs[3] as written, with its sub-records and the CPU baseline
-timeout -k 10 600 python bench.py --steps 5 --warmup 2 > $O/bench_default.json 2> $O/bench_default.err; echo "default rc=$?"; cut -c1-300 $O/bench_default.json
-timeout -k 10 300 python bench.py --config shard --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_shard.json 2> $O/bench_shard.err; echo "shard rc=$?"; cut -c1-300 $O/bench_shard.json
-timeout -k 10 300 python bench.py --config cqt --steps 5 --warmup 2 > $O/bench_cqt.json 2> $O/bench_cqt.err; echo "cqt rc=$?"
+timeout -k 10 600 python bench.py --steps 5 --warmup 2 --full > $O/bench_default.json 2> $O/bench_default.err; echo "default rc=$?"; cut -c1-300 $O/bench_default.json
+timeout -k 10 300 python bench.py --config shard --steps 10 --warmup 3 --no-cpu-baseline --full > $O/bench_shard.json 2> $O/bench_shard.err; echo "shard rc=$?"; cut -c1-300 $O/bench_shard.json
+timeout -k 10 300 python bench.py --config cqt --steps 5 --warmup 2 --full > $O/bench_cqt.json 2> $O/bench_cqt.err; echo "cqt rc=$?"
 cd /tmp
 # kernel trace of the default command (1 step): the Viterbi's average duration must agree with the line's kernel_ms
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_folder -o b -- python3 /root/repo/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras > $O/prof_folder.log 2>&1; echo "prof folder rc=$?"
