@@ -345,6 +345,35 @@ int64_t aegis_get_param(const aegis_handle *h, const char *name);
  * section counters read by tools/viterbi_cycles.py, cqt_cycles.py (reading resets them). */
 int64_t aegis_debug_fetch(aegis_handle *h, const char *name, void *dst, int64_t cap);
 
+/* The pass plan an analyze call would make (CPU only: no device work, a device=-1 handle plans too).  Clips of
+ * n_samples[i] samples, every stage, the handle's knobs and max_frames_per_pass, a device of n_cus compute units;
+ * entry: AEGIS_PLAN_DEVICE (aegis_analyze_batch_device on the handle's stream), AEGIS_PLAN_CALLER_STREAM (on a stream of
+ * the caller's) or AEGIS_PLAN_HOST_FED (aegis_analyze_batch, which plans with sync = 2), or-ed with AEGIS_PLAN_COOLING
+ * (the split cool-down holds) and AEGIS_PLAN_NO_PERSIST (after a give-up of the single Viterbi launch).  Writes
+ * min(count, cap) of: the pass count, then per pass n_clips, frames, longest clip's frames, flags (AEGIS_PLAN_F_*),
+ * segment length, hybrid step S, segments, lock-on runs, chunks nk, ramp chunks, stream lanes (4 bits each: frame a,
+ * frame b, Viterbi, hybrid finish, hybrid speculation), a 64-bit hash of the segment tables, sel_off and clip_tb, and the
+ * nk + 1 chunk boundaries.  Returns count. */
+#define AEGIS_PLAN_DEVICE 0
+#define AEGIS_PLAN_CALLER_STREAM 1
+#define AEGIS_PLAN_HOST_FED 2
+#define AEGIS_PLAN_COOLING 4
+#define AEGIS_PLAN_NO_PERSIST 8
+#define AEGIS_PLAN_F_SPLIT 1
+#define AEGIS_PLAN_F_SPLIT_AUTO 2
+#define AEGIS_PLAN_F_WANT_HYBRID 4
+#define AEGIS_PLAN_F_HYBRID 8
+#define AEGIS_PLAN_F_HYBRID_PART 16
+#define AEGIS_PLAN_F_BALANCED 32
+#define AEGIS_PLAN_F_MAY_PERSIST 64
+#define AEGIS_PLAN_F_PERSISTENT 128
+#define AEGIS_PLAN_F_DENSE 256
+#define AEGIS_PLAN_F_PROPORTIONAL 512
+#define AEGIS_PLAN_F_TWO_FRAME_STREAMS 1024
+#define AEGIS_PLAN_F_FRAME_B 2048
+int64_t aegis_debug_plan(aegis_handle *h, const int64_t *n_samples, int32_t n_clips, int32_t entry, int32_t sync,
+                         int32_t n_cus, int64_t *dst, int64_t cap);
+
 /* Kernel timing of the most recent aegis_analyze_batch_device() with sync != 0,
  * measured with hipEvents on the stream the kernels ran on.  name in
  * {"frame","pyin_obs","viterbi","finalize","total"}; milliseconds,

@@ -46,7 +46,7 @@ EXPORTS = ("aegis_abi_version", "aegis_create", "aegis_destroy", "aegis_last_err
            "aegis_analyze_batch", "aegis_analyze_batch_device", "aegis_get_table", "aegis_get_param",
            "aegis_debug_fetch", "aegis_set_profiling", "aegis_last_kernel_ms", "aegis_rake_patterns", "aegis_set_table", "aegis_last_kernel_launches", "aegis_trend", "aegis_ghost_rsi",
            "aegis_stream_open", "aegis_stream_push", "aegis_stream_close", "aegis_stream_free", "aegis_cqt", "aegis_cqt_device", "aegis_chroma_cqt",
-           "aegis_extract_events", "aegis_render_smf", "aegis_events_last_error")
+           "aegis_extract_events", "aegis_render_smf", "aegis_events_last_error", "aegis_debug_plan")
 
 _lib = None
 
@@ -115,6 +115,8 @@ def load():
     lib.aegis_get_param.restype = C.c_int64
     lib.aegis_debug_fetch.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64]
     lib.aegis_debug_fetch.restype = C.c_int64
+    lib.aegis_debug_plan.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64]
+    lib.aegis_debug_plan.restype = C.c_int64
     lib.aegis_set_profiling.argtypes = [C.c_void_p, C.c_int32]
     lib.aegis_set_profiling.restype = C.c_int
     lib.aegis_last_kernel_ms.argtypes = [C.c_void_p, C.c_char_p]
@@ -228,6 +230,34 @@ class Handle:
         if got < 0:
             raise AegisError(got, self.lib.aegis_last_error(self._h).decode())
         return out
+
+    # aegis_debug_plan: entry kinds, option bits and the per-pass flag bits (include/aegis_hip.h AEGIS_PLAN_*)
+    PLAN_ENTRIES = {"device": 0, "caller_stream": 1, "host_fed": 2}
+    PLAN_FLAGS = ("split", "split_auto", "want_hybrid", "hybrid", "hyb_part", "balanced", "may_persist", "persistent",
+                  "dense", "proportional", "two_fs", "use_fb")
+    PLAN_FIELDS = ("n_clips", "fp", "maxF", "flags", "seglen", "hyb_S", "n_seg", "n_lock", "nk", "ramp_k", "lanes", "hash")
+
+    def plan(self, n_samples, entry="device", sync=1, n_cus=256, cooling=False, persistent=True):
+        """The passes an analyze call of clips of n_samples[i] samples would run (aegis_debug_plan; no device work):
+        a list of dicts of PLAN_FIELDS, the flags spelled out as booleans, and the chunk boundaries `cb`."""
+        ns = np.ascontiguousarray(n_samples, dtype=np.int64)
+        kind = self.PLAN_ENTRIES[entry] | (4 if cooling else 0) | (0 if persistent else 8)
+        args = (self._h, ns.ctypes.data_as(C.POINTER(C.c_int64)), len(ns), kind, int(sync), int(n_cus))
+        n = int(self.lib.aegis_debug_plan(*args, None, 0))
+        if n < 0:
+            raise AegisError(n, self.lib.aegis_last_error(self._h).decode())
+        v = np.empty(n, np.int64)
+        self.lib.aegis_debug_plan(*args, v.ctypes.data, n)
+        passes, at = [], 1
+        for _ in range(int(v[0])):
+            d = {k: int(x) for k, x in zip(self.PLAN_FIELDS, v[at:at + len(self.PLAN_FIELDS)])}
+            at += len(self.PLAN_FIELDS)
+            d["hash"] &= (1 << 64) - 1
+            d.update({f: bool(d["flags"] >> i & 1) for i, f in enumerate(self.PLAN_FLAGS)})
+            d["cb"] = [int(x) for x in v[at:at + d["nk"] + 1]]
+            at += d["nk"] + 1
+            passes.append(d)
+        return passes
 
     def set_profiling(self, on=True):
         self._check(self.lib.aegis_set_profiling(self._h, 1 if on else 0))

@@ -1,5 +1,5 @@
 // C ABI of libaegis_hip.so (see include/aegis_hip.h).  Host-side orchestration:
-// table upload, workspace management, ragged-batch pass planning, kernel launches
+// table upload, workspace management, kernel launches of the passes plan.cpp plans
 // on one HIP stream per handle, optional hipEvent timing per kernel.
 #include <hip/hip_runtime.h>
 
@@ -15,7 +15,6 @@
 #include <map>
 #include <mutex>
 #include <new>
-#include <numeric>
 #include <stdexcept>
 #include <string>
 #include <thread>
@@ -23,6 +22,7 @@
 
 #include "../../include/aegis_hip.h"
 #include "kernels.h"
+#include "plan.h"
 #include "cqt.h"
 #include "tables.h"
 #include "trend.h"
@@ -38,13 +38,6 @@ struct DevBuf {
     size_t cap = 0;
 };
 
-struct PassMeta {   // host copies kept alive until the stream has consumed them
-    std::vector<int64_t> sample_off, sample_len, out_off, frame_off, chunk_off, sel_off, chunk_lo, clip_tb;
-    std::vector<int32_t> order;
-    std::vector<int64_t> seg64;     // time-split pass: seg_f0 | seg_ch0
-    std::vector<int32_t> seg32;     // seg_T | seg_store | seg_prev | seg_clip | clip_seg0 | seg_order | lock_order
-};
-
 }  // namespace
 
 struct aegis_handle {
@@ -56,21 +49,11 @@ struct aegis_handle {
     bool troughs_off = false;                 // AEGIS_TROUGHS_IN_FRAME=0 at create
     bool cmnd_off = false;                    // AEGIS_CMND_IN_FRAME=0 at create: pyin_obs_kernel walks the CMND cumsum (tests compare the two paths)
     bool debug_stages = false;                // AEGIS_DEBUG_STAGES=1 at create: pyin_obs also writes the CMND rows ("yin") for the stage tests
-    int64_t chunk_start = 512;                // first time chunk (AEGIS_CHUNK_START), later ones grow by chunk_growth_pct up to time_chunk
-    int chunk_growth_pct = 125, ramp_k = 4;   // AEGIS_CHUNK_GROWTH, AEGIS_RAMP_K (first chunks alternating over two frame streams)
-    int dense_mode = -1;                      // AEGIS_DENSE: -1 (unset) = passes of >= 256 clips, 0 = never, 1 = every unbalanced pass
-    bool proportional_chunks = true;          // ragged unbalanced passes cut every clip into the same number of chunks (AEGIS_PROPORTIONAL_CHUNKS=0: one time axis)
-    int64_t feed_chunk = 1024;                // chunk size of balanced passes fed from host memory (AEGIS_FEED_CHUNK)
-    int64_t balanced_chunk = 384;             // chunk size of balanced passes (AEGIS_BALANCED_CHUNK, 0 = never balanced)
-    int64_t balanced_ends = 64;               // first chunk of a balanced pass with a single Viterbi launch, doubling up to the chunk size and mirrored at the end (AEGIS_BALANCED_ENDS, 0 = off)
-    int balanced_min = 16;                    // fewest clips of a balanced pass (AEGIS_BALANCED_MIN)
-    int64_t time_chunk = 2048;                // Viterbi steps per pipeline chunk (AEGIS_TIME_CHUNK overrides; multiple of 16)
     hipStream_t stream4 = nullptr;            // second frame-stage stream: odd time chunks (their FFTs overlap the even chunks' YIN / observation kernels)
     hipStream_t stream3 = nullptr;            // host->device sample copies of aegis_analyze_batch, chunk by chunk
     // CU-partitioned stream sets of the pipeline (split_streams): [0] Viterbi on 64 CUs / frame stage on 192, [1] 128 / 128
     struct SplitSet { hipStream_t frame_a = nullptr, frame_b = nullptr, viterbi = nullptr; bool tried = false; } split[2];
     int n_cus = 0;                            // compute units of the device (CU masks are built for this count)
-    int split_limit = 64;                     // passes of up to this many clips run partitioned (AEGIS_CU_SPLIT=0 disables)
     hipEvent_t copy_event = nullptr;
     std::vector<hipEvent_t> sync_events;      // cross-stream dependencies (no timing)
     int64_t max_frames_per_pass = 0;
@@ -84,65 +67,34 @@ struct aegis_handle {
         DevBuf sample_off, sample_len, out_off, frame_off, order, sel_off, vstate, chunk_lo, chunk_flag, clip_tb;
         DevBuf seg64, seg32, seg_col, seg_map, seg_i32, colhist, colG, colkg, clip_flag, flag_order, tube_buf, tube_at, tube_count;    // time-split passes
     } work[2];
-    int last_work = 0;
     DevBuf vstats, rk_raw, abort_flag, finite_flag;
     uint32_t chunk_gen = 0;                   // generation of the chunk flags of a persistent Viterbi launch
     int test_drop_signal = -1;
     bool persist_gave_up = false;
     int persist_cooldown = 0;                 // calls left on the one-launch-per-chunk schedule after a give-up; then the single launch is tried again
-    bool persistent_wanted = true;            // what AEGIS_VITERBI_PERSISTENT asked for
     int64_t persistent_fallbacks = 0;         // calls repeated with one launch per chunk (aegis_debug_fetch "persistent_fallbacks")
     bool persist_pending = false;             // a persistent launch ran since the abort flag was last read
-    bool persistent = true;                   // one Viterbi launch per balanced pass (AEGIS_VITERBI_PERSISTENT=0: one per chunk)
+    bool persistent = true;                   // one Viterbi launch per balanced pass now (false for persist_cooldown calls after a give-up)
+    PlanKnobs knobs;                          // scheduling knobs (plan.h), read from the environment at create
     CqtBank cqt_bank;
     DevBuf q_pcm, q_soff, q_foff, q_toff, q_out, q_chroma, q_cls;
     DevBuf t_x, t_off, t_a, t_b, t_c, t_d, t_e, t_i8, t_i64a, t_i64b;   // trend-filter staging
     DevBuf t_pa;                              // scratch of the fused pitch analysis: 12 rows of doubles + 1 of bytes
     DevBuf io_pcm, io_f0, io_voiced, io_vprob, io_rms, io_rake, io_sdb, io_bin, io_colmean;
     int32_t lag_stride = 0, yin_stride = 0, obs_stride = 0;
-    std::vector<PassMeta> metas;
-    // last pass geometry for aegis_debug_fetch
-    int64_t last_frames = 0;
-    // time-split passes (viterbi.hip): AEGIS_TIME_SPLIT=<steps per segment> forces them, 0 turns them off, unset = when a pass
-    // is bound by the recurrence of its longest clip
-    int64_t split_seglen = -1;                // -1: automatic
-    // AEGIS_SPLIT_SEGMENT_ROUNDS: segments per compute unit the automatic rule plans for (whole rounds of workgroups).  The
-    // speculative runs take the same time in one round of long segments or two rounds of segments half as long (+ the second
-    // warm-up), but a lock-on run that never meets its speculative run costs a whole segment and a round of second speculation
-    // another: with two rounds of segments six of the folder's eight rank shards run in 77-79 ms instead of 91-99 (and the
-    // other two in 68-71 instead of 66); with three the slowest shard takes 76.7 ms instead of 79.5, with four 77.6.
-    int split_rounds_of_segments = 3;
-    // AEGIS_SPLIT_SUB_PASSES=2: a split call of >= 16 clips runs as two passes of every second clip, the second half's frame
-    // stage under the first half's Viterbi kernels.  Measured on rank 0's shard of the folder (forced 1 536-step segments):
-    // 86.5 ms against 76.0 as one pass -- the latency-bound parts of a split pass (lock-on tail, rounds of second speculation,
-    // verification, exact walk: ~25 ms) do not shrink with half the clips and now run twice.  Off by default.
-    int split_sub_passes = 1;
-    // Hybrid split passes (AEGIS_SPLIT_HYBRID: unset = automatic split passes of up to split_limit clips, 1 = forced ones as
-    // well, 0 = never).  A split pass ran its whole frame stage in front of its segments (they need every frame's
-    // observations) with the Viterbi's compute units idle; a hybrid pass runs the balanced pipeline instead -- frame stage on
-    // 192 CUs, the SEQUENTIAL kernel chunk by chunk on 64 -- until the frame stage is through, and cuts only what the
-    // sequential kernel has not reached by then (steps behind hybrid step S of every clip) into speculative segments: the
-    // first segment of every clip is the sequential run itself, as before, only now thousands of steps long and free.
-    // AEGIS_HYBRID_PCT: S as a percentage of (frame stage time on 192 CUs) / (time per step).
-    int split_hybrid = -1, hybrid_pct = 100, hybrid_rounds = 3, hybrid_min_seg = 768;      // AEGIS_HYBRID_ROUNDS: rounds of speculative segments behind S
-    int64_t last_hybrid_step = 0;
+    CallPlan plan;                            // the last call's plan: its host arrays stay alive until the stream drained
+    bool plan_in_flight = false;              // the stream may still read them
+    struct SplitCheck { int pass; PassParams p; };
+    hipEvent_t split_ev[2] = {nullptr, nullptr};   // around an automatic split call's Viterbi kernels: the planning rule checks its estimate against them
     hipEvent_t hyb_ev[3] = {nullptr, nullptr, nullptr};
     hipEvent_t fin_ev[2] = {nullptr, nullptr};       // fork / join of a split pass's two finishing streams (launch_viterbi_split)
-    bool call_split_started = false;          // this call's first automatic split pass has recorded split_ev[0]
-    double call_t_seq = 0.0, call_t_front = 0.0;   // the call's sequential estimate; the first split pass's frame stage (not overlapped)
-    int split_bad = 0;                        // automatic split passes in a row that did not pay (two of them start the cool-down)
-    int split_warmup = 256;                   // AEGIS_SPLIT_WARMUP: frames a speculative run starts ahead of its boundary (128: lock-on after a median of 104 steps and one run in twenty never; 256: at the first check)
-    struct SplitCheck { int work; PassParams p; int nc; bool automatic; double t_seq; double t_front; };
-    hipEvent_t split_ev[2] = {nullptr, nullptr};   // around an automatic split pass's Viterbi kernels: the planning rule checks its estimate against them
+    int split_bad = 0;                        // automatic split calls in a row that did not pay (two of them start the cool-down)
     int split_cooldown = 0;                   // automatic mode: calls left without time-split passes after one that did not pay (clips redone sequentially)
-    std::vector<SplitCheck> split_checks;     // split passes of the call in flight: their clip flags are read after the synchronisation
+    std::vector<SplitCheck> split_checks;     // split passes of the call in flight whose clip flags have not been read
     int64_t split_stats[4] = {0, 0, 0, 0};    // since create: split passes, segments, clips flagged for the sequential kernel, lock-on runs that never locked
-    int last_split_segments = 0;              // of the last call (all its passes)
-    int last_pass_segments = 0;               // of its last pass (what the debug fetches of per-segment arrays index)
     double last_split_viterbi_ms = 0.0;      // measured Viterbi time of the call's last automatic split pass
     int64_t last_carried_steps = 0;          // rounds of second speculation (viterbi_band.inc, phases 3 / 4) that had work in the call's last split pass
     std::vector<int64_t> last_split_flags;   // per clip of the call's last split pass (pass order: longest first): the verification's verdict bits
-    int last_passes = 0, last_chunks = 0, last_dense = 0, last_proportional = 0, last_balanced = 0, last_persistent = 0;   // of the last call (its last pass)
     // profiling
     bool profiling = false;
     std::vector<std::pair<std::string, std::pair<hipEvent_t, hipEvent_t>>> events;
@@ -323,6 +275,8 @@ int aegis_create(const aegis_config *cfg, aegis_handle **out) {
     if (!h->tab.set_pyin_init(c.pyin_init)) { g_create_error = "pyin_init must be AEGIS_PYIN_INIT_UNVOICED (0) or AEGIS_PYIN_INIT_UNIFORM (1)"; delete h; return AEGIS_ERR_INVALID; }
     h->device = c.device;
     h->max_frames_per_pass = c.max_frames_per_pass;
+    h->knobs.read_env();                       // (a host-only handle plans with the knobs a device handle would)
+    h->persistent = h->knobs.persistent_wanted;
 
     h->lag_stride = (h->tab.max_period + 1 + 7) & ~7;
     // a dfn row also holds the frame's trough list when the frame kernel finds the troughs (PassParams::troughs)
@@ -346,33 +300,10 @@ int aegis_create(const aegis_config *cfg, aegis_handle **out) {
     CRTHIP(hipStreamCreateWithFlags(&h->stream4, hipStreamNonBlocking));
     CRTHIP(hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking));
     CRTHIP(hipStreamCreateWithFlags(&h->stream3, hipStreamNonBlocking));
-    if (const char *e = std::getenv("AEGIS_TIME_CHUNK")) {
-        const long v = std::strtol(e, nullptr, 10);
-        if (v >= 64 && v % kViterbiChunk == 0) h->time_chunk = v;
-    }
     if (const char *e = std::getenv("AEGIS_DEBUG_STAGES")) h->debug_stages = (e[0] == '1');
     if (const char *e = std::getenv("AEGIS_CMND_IN_FRAME")) h->cmnd_off = (e[0] == '0');
     if (const char *e = std::getenv("AEGIS_TROUGHS_IN_FRAME")) h->troughs_off = (e[0] == '0');
-    if (const char *e = std::getenv("AEGIS_TIME_SPLIT")) { const long v = std::strtol(e, nullptr, 10); if (v >= 0) h->split_seglen = v / kViterbiChunk * kViterbiChunk; }
-    if (const char *e = std::getenv("AEGIS_SPLIT_SUB_PASSES")) { const long v = std::strtol(e, nullptr, 10); if (v >= 1 && v <= 2) h->split_sub_passes = (int)v; }
-    if (const char *e = std::getenv("AEGIS_SPLIT_HYBRID")) h->split_hybrid = e[0] == '0' ? 0 : 1;
-    if (const char *e = std::getenv("AEGIS_HYBRID_ROUNDS")) { const long v = std::strtol(e, nullptr, 10); if (v >= 1 && v <= 8) h->hybrid_rounds = (int)v; }
-    if (const char *e = std::getenv("AEGIS_HYBRID_MIN_SEG")) { const long v = std::strtol(e, nullptr, 10); if (v >= 64 && v <= 65536) h->hybrid_min_seg = (int)(v / kViterbiChunk * kViterbiChunk); }
-    if (const char *e = std::getenv("AEGIS_HYBRID_PCT")) { const long v = std::strtol(e, nullptr, 10); if (v >= 5 && v <= 200) h->hybrid_pct = (int)v; }
-    if (const char *e = std::getenv("AEGIS_SPLIT_SEGMENT_ROUNDS")) { const long v = std::strtol(e, nullptr, 10); if (v >= 1 && v <= 8) h->split_rounds_of_segments = (int)v; }
-    if (const char *e = std::getenv("AEGIS_SPLIT_WARMUP")) { const long v = std::strtol(e, nullptr, 10); if (v >= 0) h->split_warmup = (int)(v / kViterbiChunk * kViterbiChunk); }
-    if (const char *e = std::getenv("AEGIS_CHUNK_START")) { const long v = std::strtol(e, nullptr, 10); if (v >= 16) h->chunk_start = v; }
-    if (const char *e = std::getenv("AEGIS_CHUNK_GROWTH")) { const long v = std::strtol(e, nullptr, 10); if (v >= 100 && v <= 400) h->chunk_growth_pct = (int)v; }
-    if (const char *e = std::getenv("AEGIS_BALANCED_CHUNK")) { const long v = std::strtol(e, nullptr, 10); if (v >= 0 && v % kViterbiChunk == 0) h->balanced_chunk = v; }
-    if (const char *e = std::getenv("AEGIS_DENSE")) h->dense_mode = e[0] == '0' ? 0 : 1;
-    if (const char *e = std::getenv("AEGIS_PROPORTIONAL_CHUNKS")) h->proportional_chunks = e[0] != '0';
-    if (const char *e = std::getenv("AEGIS_FEED_CHUNK")) { const long v = std::strtol(e, nullptr, 10); if (v >= kViterbiChunk && v % kViterbiChunk == 0) h->feed_chunk = v; }
-    if (const char *e = std::getenv("AEGIS_BALANCED_ENDS")) { const long v = std::strtol(e, nullptr, 10); if (v >= 0) h->balanced_ends = v; }
-    if (const char *e = std::getenv("AEGIS_BALANCED_MIN")) { const long v = std::strtol(e, nullptr, 10); if (v >= 1) h->balanced_min = (int)v; }
-    if (const char *e = std::getenv("AEGIS_VITERBI_PERSISTENT")) h->persistent = h->persistent_wanted = std::atoi(e) != 0;
     if (const char *e = std::getenv("AEGIS_TEST_DROP_CHUNK_SIGNAL")) h->test_drop_signal = std::atoi(e);
-    if (const char *e = std::getenv("AEGIS_RAMP_K")) { const long v = std::strtol(e, nullptr, 10); if (v >= 0 && v <= 64) h->ramp_k = (int)v; }
-    if (const char *e = std::getenv("AEGIS_CU_SPLIT")) h->split_limit = std::atoi(e);
     CRTHIP(hipDeviceGetAttribute(&h->n_cus, hipDeviceAttributeMultiprocessorCount, c.device));
     if (auto_pass) {
         // Default workspace bound: as many frames per pass as a third of the free device memory holds (a pass needs
@@ -563,7 +494,7 @@ int aegis_analyze_batch_device(aegis_handle *h, const float *d_pcm, const int64_
     try {
     if (!h) return AEGIS_ERR_INVALID;
     std::lock_guard<std::mutex> lock(h->mu);
-    if (!h->persistent && h->persistent_wanted && h->persist_cooldown > 0 && --h->persist_cooldown == 0)
+    if (!h->persistent && h->knobs.persistent_wanted && h->persist_cooldown > 0 && --h->persist_cooldown == 0)
         h->persistent = true;                 // the give-up is not for good: whatever serialised the kernels may be gone
     int rc = analyze_device_locked(h, d_pcm, sample_offsets, n_clips, rake_sensitivity, stages, dout, stream_v, sync);
     // The default pass size was taken from the device memory free when the handle was created; other handles, the caller's
@@ -589,11 +520,10 @@ int aegis_analyze_batch_device(aegis_handle *h, const float *d_pcm, const int64_
     } catch (...) { return abi_fail(h); }
 }
 
-// The Viterbi workgroups (one CU per clip, latency-bound) lose a fifth of their speed when frame-stage workgroups run on
-// NEIGHBOURING compute units: the kernels' code (19 + 31 + 48 KB) does not fit the instruction cache a CU shares with
-// its neighbour (measured: Viterbi 77.5 ms beside the frame stage, 67.9 ms with the frame stage confined to 192 CUs;
-// keeping frame workgroups off the Viterbi's own CU alone changed nothing).  While a batch leaves CUs free the pipeline
-// therefore runs on CU-masked streams: the Viterbi on the last V CUs of the mask, the frame stage on the others.
+// the last call's plan: its last pass, and the workspace that pass used
+static const PassPlan *last_pass(const aegis_handle *h) { return h->plan.passes.empty() ? nullptr : &h->plan.passes.back(); }
+static int last_work(const aegis_handle *h) { return h->plan.passes.empty() ? 0 : (int)((h->plan.passes.size() - 1) & 1); }
+
 // After a synchronisation: a persistent Viterbi launch that gave up waiting for its chunk flags says so here.
 static int persistent_check(aegis_handle *h) {
     if (!h->persist_pending) return AEGIS_OK;
@@ -622,80 +552,78 @@ static int finite_result(aegis_handle *h, uint32_t opts, const int64_t *sample_o
     return AEGIS_ERR_INVALID;
 }
 
-// After the synchronisation behind time-split passes: the clips whose decode the verification kernel could not certify (or
-// whose lock-on run never met the speculative run) are decoded again by the sequential kernel, and the pass is decoded into
-// the outputs once more.  Rare (a near-tie on the decoded path that involves a voiced state; a boundary inside a long
-// stretch without a voiced note).
-static int split_check(aegis_handle *h, const Tables &t, hipStream_t s) {
-    for (auto &sc : h->split_checks) {
-        std::vector<uint32_t> flags((size_t)sc.nc);
-        HIPCHK(h, hipMemcpy(flags.data(), sc.p.clip_flag, (size_t)sc.nc * 4, hipMemcpyDeviceToHost));
-        std::vector<int32_t> redo;
-        h->last_split_flags.assign(flags.begin(), flags.end());
-        for (int i = 0; i < sc.nc; ++i)
-            if (flags[i]) { redo.push_back(i); if (flags[i] & 1u) ++h->split_stats[3]; }
-        uint32_t counts[2] = {0, 0};
-        HIPCHK(h, hipMemcpy(counts, sc.p.tube_count, 8, hipMemcpyDeviceToHost));
-        h->last_carried_steps = counts[1];
-        // The planning rule's estimate against the clock.  A split pass's Viterbi kernels come behind its frame stage, and their
-        // time depends on the material: a lock-on run that never meets the speculative one runs its whole segment, and the
-        // segments behind it speculate again (one more segment time per round).  When frame stage + measured Viterbi time is
-        // not clearly below what the pass would have taken sequentially twice in a row, the next 32 calls of this handle plan
-        // their passes sequentially.
-        if (sc.automatic && h->split_ev[1] && &sc == &h->split_checks.back()) {      // once per call: from its first split pass's Viterbi kernels to its last's
-            float ms = 0.f;
-            if (hipEventElapsedTime(&ms, h->split_ev[0], h->split_ev[1]) == hipSuccess) {
-                h->last_split_viterbi_ms = ms;
-                if (h->call_t_front + 1e-3 * ms > 0.92 * h->call_t_seq) { if (++h->split_bad >= 2) { h->split_cooldown = 32; h->split_bad = 0; } }
-                else h->split_bad = 0;
-            }
+// After a time-split pass has finished (its done event, or the call's synchronisation): the clips whose decode the
+// verification kernel could not certify (or whose lock-on run never met the speculative run) are decoded again by the
+// sequential kernel, and the pass is decoded into the outputs once more.  Rare (a near-tie on the decoded path that
+// involves a voiced state; a boundary inside a long stretch without a voiced note).
+static int split_check(aegis_handle *h, const aegis_handle::SplitCheck &sc, hipStream_t s) {
+    const Tables &t = h->tab;
+    const PassPlan &m = h->plan.passes[sc.pass];
+    const int nc = m.nc();
+    std::vector<uint32_t> flags((size_t)nc);
+    HIPCHK(h, hipMemcpy(flags.data(), sc.p.clip_flag, (size_t)nc * 4, hipMemcpyDeviceToHost));
+    std::vector<int32_t> redo;
+    h->last_split_flags.assign(flags.begin(), flags.end());
+    for (int i = 0; i < nc; ++i)
+        if (flags[i]) { redo.push_back(i); if (flags[i] & 1u) ++h->split_stats[3]; }
+    uint32_t counts[2] = {0, 0};
+    HIPCHK(h, hipMemcpy(counts, sc.p.tube_count, 8, hipMemcpyDeviceToHost));
+    h->last_carried_steps = counts[1];
+    // The planning rule's estimate against the clock.  A split pass's Viterbi kernels come behind its frame stage, and their
+    // time depends on the material: a lock-on run that never meets the speculative one runs its whole segment, and the
+    // segments behind it speculate again (one more segment time per round).  When frame stage + measured Viterbi time is
+    // not clearly below what the pass would have taken sequentially twice in a row, the next 32 calls of this handle plan
+    // their passes sequentially.  Once per call, at its last split pass: from its first split pass's Viterbi kernels to its
+    // last's.
+    bool last_split = true;
+    for (size_t j = (size_t)sc.pass + 1; j < h->plan.passes.size(); ++j) last_split = last_split && !h->plan.passes[j].tsplit;
+    if (m.split_auto && h->split_ev[1] && last_split) {
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, h->split_ev[0], h->split_ev[1]) == hipSuccess) {
+            h->last_split_viterbi_ms = ms;
+            if (!split_clock_pays(h->plan, ms)) { if (++h->split_bad >= 2) { h->split_cooldown = 32; h->split_bad = 0; } }
+            else h->split_bad = 0;
         }
-        if (redo.empty()) continue;
-        h->split_stats[2] += (int64_t)redo.size();
-        if (sc.automatic) {
-            // the redo is sequential and comes on top of the split pass: when it costs more than a quarter of what the pass
-            // would have taken sequentially (material without voiced notes never locks on and keeps its tubes open: noise,
-            // silence), the next 32 calls of this handle plan their passes sequentially
-            std::vector<int64_t> fo((size_t)sc.nc + 1);
-            HIPCHK(h, hipMemcpy(fo.data(), sc.p.frame_off, ((size_t)sc.nc + 1) * 8, hipMemcpyDeviceToHost));
-            int64_t redoF = 0;
-            for (int i : redo) redoF = std::max(redoF, fo[i + 1] - fo[i]);
-            if ((double)redoF * (t.half_width == 25 ? 3.1e-6 : 7.3e-6) > 0.25 * sc.t_seq) h->split_cooldown = 32;
-        }
-        aegis_handle::Work &w = h->work[sc.work];
-        HIPCHK(h, hipMemcpy(w.flag_order.p, redo.data(), redo.size() * 4, hipMemcpyHostToDevice));
-        PassParams q = sc.p;
-        q.order = static_cast<const int32_t *>(w.flag_order.p);
-        q.n_clips = (int32_t)redo.size();
-        q.vt_begin = 0; q.vt_end = INT64_MAX; q.clip_t0 = nullptr; q.clip_t1 = nullptr; q.chunk_flag = nullptr; q.dense = 0;
-        hipError_t ve = launch_viterbi(q, h->dt, t.log_trans_band.data(), s);
-        if (ve != hipSuccess) { h->err = std::string("viterbi launch: ") + hipGetErrorString(ve); return AEGIS_ERR_DEVICE; }
-        launch_decode(sc.p, h->dt, s);
-        HIPCHK(h, hipStreamSynchronize(s));
     }
-    h->split_checks.clear();
+    if (redo.empty()) return AEGIS_OK;
+    h->split_stats[2] += (int64_t)redo.size();
+    if (m.split_auto) {
+        // the redo is sequential and comes on top of the split pass: when it costs too much of what the pass would have
+        // taken sequentially (material without voiced notes never locks on and keeps its tubes open: noise, silence), the
+        // next 32 calls of this handle plan their passes sequentially
+        int64_t redoF = 0;
+        for (int i : redo) redoF = std::max(redoF, m.frames(i));
+        if (!split_redo_pays(m, redoF, t.half_width)) h->split_cooldown = 32;
+    }
+    aegis_handle::Work &w = h->work[sc.pass & 1];
+    HIPCHK(h, hipMemcpy(w.flag_order.p, redo.data(), redo.size() * 4, hipMemcpyHostToDevice));
+    PassParams q = sc.p;
+    q.order = static_cast<const int32_t *>(w.flag_order.p);
+    q.n_clips = (int32_t)redo.size();
+    q.vt_begin = 0; q.vt_end = INT64_MAX; q.clip_t0 = nullptr; q.clip_t1 = nullptr; q.chunk_flag = nullptr; q.dense = 0;
+    hipError_t ve = launch_viterbi(q, h->dt, t.log_trans_band.data(), s);
+    if (ve != hipSuccess) { h->err = std::string("viterbi launch: ") + hipGetErrorString(ve); return AEGIS_ERR_DEVICE; }
+    launch_decode(sc.p, h->dt, s);
+    HIPCHK(h, hipStreamSynchronize(s));
     return AEGIS_OK;
 }
 
+// The Viterbi workgroups (one CU per clip, latency-bound) lose a fifth of their speed when frame-stage workgroups run on
+// NEIGHBOURING compute units: the kernels' code (19 + 31 + 48 KB) does not fit the instruction cache a CU shares with
+// its neighbour (measured: Viterbi 77.5 ms beside the frame stage, 67.9 ms with the frame stage confined to 192 CUs;
+// keeping frame workgroups off the Viterbi's own CU alone changed nothing).  While a batch leaves CUs free the pipeline
+// therefore runs on CU-masked streams: the Viterbi on the last V CUs of the mask, the frame stage on the others.
 static aegis_handle::SplitSet *split_streams(aegis_handle *h, int n_clips) {
-    if (n_clips > h->split_limit || h->split_limit <= 0) return nullptr;
-    if (h->n_cus != 256) return nullptr;      // the masks below are laid out for the 256 CUs of an un-partitioned MI355X
-    // 65..128 clips: a 128 / 128 partition starves the frame stage (170.8 vs 120.9 ms at 128 clips); only reachable
-    // through AEGIS_CU_SPLIT
+    if (!masked_streams_fit(h->knobs, h->n_cus, n_clips)) return nullptr;
     const int idx = n_clips <= 64 ? 0 : 1;
-    if (n_clips > 128) return nullptr;
     aegis_handle::SplitSet &ss = h->split[idx];
     if (!ss.tried) {
         ss.tried = true;
         const int v = idx == 0 ? 64 : 128;
         uint32_t fm[8], vm[8];
         for (int w = 0; w < 8; ++w) { fm[w] = 0; vm[w] = 0; }
-        // AEGIS_CU_FRAME=<n> (experiment knob): the frame stage's mask covers CUs 0..n-1 instead of the complement of the
-        // Viterbi's (256: the whole device, sharing the Viterbi's CUs)
-        int nf = 256 - v;
-        if (const char *e = std::getenv("AEGIS_CU_FRAME")) nf = std::min(256, std::max(32, std::atoi(e)));
         for (int i = 0; i < 256; ++i) {
-            if (i < nf) fm[i >> 5] |= 1u << (i & 31);
+            if (i < 256 - v) fm[i >> 5] |= 1u << (i & 31);
             if (i >= 256 - v) vm[i >> 5] |= 1u << (i & 31);
         }
         if (hipExtStreamCreateWithCUMask(&ss.frame_a, 8, fm) != hipSuccess || hipExtStreamCreateWithCUMask(&ss.frame_b, 8, fm) != hipSuccess ||
@@ -707,9 +635,176 @@ static aegis_handle::SplitSet *split_streams(aegis_handle *h, int n_clips) {
     return ss.viterbi ? &ss : nullptr;
 }
 
+// What the planner needs to know about a call.  masked: whether a CU-masked stream set exists for n clips (the executor
+// creates them through split_streams; aegis_debug_plan only asks whether they would be laid out).
+static PlanInput plan_input(aegis_handle *h, const int64_t *sample_offsets, int32_t n_clips, uint32_t stages, bool feed,
+                            bool caller_stream, int32_t sync, int n_cus, std::function<bool(int)> masked) {
+    const Tables &t = h->tab;
+    PlanInput in;
+    in.sample_offsets.assign(sample_offsets, sample_offsets + n_clips + 1);
+    in.max_frames_per_pass = h->max_frames_per_pass;
+    in.n_cus = n_cus; in.hop = t.hop; in.half_width = t.half_width;
+    in.py = stages & AEGIS_STAGE_PYIN;
+    in.feed = feed; in.caller_stream = caller_stream; in.sync = sync;
+    DevTables dt = h->dt;      // (a host-only handle: the packed table the device would hold)
+    if (h->device < 0 && !t.log_trans_pack.empty()) dt.lt_pack = t.log_trans_pack.data();
+    in.band_applies = viterbi_band_applies(base_params(t), dt);
+    in.split_applies = viterbi_split_applies(base_params(t), dt);
+    in.masked_streams = std::move(masked);
+    in.knobs = h->knobs;
+    in.persistent = h->persistent;
+    if (split_allowed(in) && in.knobs.split_seglen < 0 && h->split_cooldown > 0) in.cooling = true;
+    return in;
+}
+
+static int ensure_pass(aegis_handle *h, aegis_handle::Work &w, const PassPlan &m, uint32_t stages) {
+    const int64_t nc = m.nc(), nk = m.nk(), fp = m.fp, S = 2 * h->tab.n_bins, nchunks = m.chunk_off[nc];
+    int rc;
+#define ENS(buf, bytes) if ((rc = ensure(h, w.buf, (size_t)(bytes))) != AEGIS_OK) return rc
+    ENS(sample_off, nc * 8); ENS(sample_len, nc * 8); ENS(out_off, nc * 8); ENS(frame_off, (nc + 1) * 8);
+    ENS(order, nc * 4); ENS(chunk_off, (nc + 1) * 8); ENS(sel_off, (size_t)nk * (nc + 1) * 8);
+    if (stages & AEGIS_STAGE_PYIN) {
+        ENS(dfn, fp * h->lag_stride * 8); if (h->debug_stages) ENS(yin, fp * h->yin_stride * 8);
+        ENS(logobs, fp * h->obs_stride * 8); ENS(logunv, fp * 8); ENS(obs_seg, fp * 4);
+        ENS(ptr, fp * S * 2); ENS(cmap, (nchunks + 1) * S * 2); ENS(bnd, (nchunks + 1) * 4);
+        ENS(states, fp * 4); ENS(vstate, (size_t)nc * S * 8);
+        ENS(chunk_lo, (size_t)nk * 8); ENS(chunk_flag, (size_t)nk * 4);
+        if (m.proportional) ENS(clip_tb, (size_t)(nk + 1) * nc * 8);
+        if (m.tsplit) {
+            const int64_t n_seg = m.n_seg;
+            ENS(seg64, m.seg64.size() * 8); ENS(seg32, m.seg32.size() * 4);
+            ENS(seg_col, (size_t)2 * n_seg * S * 8); ENS(seg_map, (size_t)n_seg * S * 2); ENS(seg_i32, ((size_t)n_seg * 3 + 2 * nc) * 4);
+            ENS(colhist, (size_t)fp * S * 8); ENS(colG, (size_t)fp * 8); ENS(colkg, (size_t)fp * 4); ENS(clip_flag, (size_t)nc * 4);
+            ENS(flag_order, (size_t)nc * 4);
+            ENS(tube_buf, (size_t)m.tube_cap * viterbi_tube_record_ints() * 4); ENS(tube_at, (size_t)fp * 4); ENS(tube_count, 8);
+        }
+    }
+    if (stages & AEGIS_STAGE_MEL) { ENS(melpow, fp * h->tab.n_mels * 4); ENS(clipmax, nc * 4); ENS(rake_raw, fp); }
+#undef ENS
+    return AEGIS_OK;
+}
+
+// the plan's host arrays into the workspace, and the device state a pass starts from (on stream fa)
+static int upload_pass(aegis_handle *h, aegis_handle::Work &w, const PassPlan &m, uint32_t stages, hipStream_t fa) {
+    const size_t nc = m.nc(), nk = m.nk();
+    auto up = [&](DevBuf &b, const auto &v) { return hipMemcpyAsync(b.p, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice, fa); };
+    HIPCHK(h, up(w.sample_off, m.sample_off)); HIPCHK(h, up(w.sample_len, m.sample_len)); HIPCHK(h, up(w.out_off, m.out_off));
+    HIPCHK(h, up(w.frame_off, m.frame_off)); HIPCHK(h, up(w.chunk_off, m.chunk_off)); HIPCHK(h, up(w.order, m.order));
+    HIPCHK(h, up(w.sel_off, m.sel_off));
+    if (m.proportional) HIPCHK(h, up(w.clip_tb, m.clip_tb));
+    if (stages & AEGIS_STAGE_MEL) HIPCHK(h, hipMemsetAsync(w.clipmax.p, 0, nc * 4, fa));
+    if (m.tsplit) {
+        HIPCHK(h, up(w.seg64, m.seg64)); HIPCHK(h, up(w.seg32, m.seg32));
+        HIPCHK(h, hipMemsetAsync(w.seg_i32.p, 0, ((size_t)m.n_seg * 3 + 2 * nc) * 4, fa));       // seg_lock = 0 for the segments without a lock-on run
+        HIPCHK(h, hipMemsetAsync(w.clip_flag.p, 0, nc * 4, fa));
+        HIPCHK(h, hipMemsetAsync(w.tube_at.p, 0, (size_t)m.fp * 4, fa));
+        HIPCHK(h, hipMemsetAsync(w.tube_count.p, 0, 8, fa));       // tubes recorded, rounds of second speculation that had work
+    }
+    if (m.persistent) {
+        if (!h->abort_flag.p) {
+            int rc;
+            if ((rc = ensure(h, h->abort_flag, 4)) != AEGIS_OK) return rc;
+            HIPCHK(h, hipMemsetAsync(h->abort_flag.p, 0, 4, fa));
+        }
+        HIPCHK(h, up(w.chunk_lo, m.chunk_lo));
+        HIPCHK(h, hipMemsetAsync(w.chunk_flag.p, 0, nk * 4, fa));       // generations start at 1
+    }
+    return AEGIS_OK;
+}
+
+// The kernels' view of a pass: the workspace's buffers, the call's outputs, the plan's geometry.
+static PassParams bind_pass(const aegis_handle *h, const PassPlan &m, const aegis_handle::Work &w, const float *d_pcm,
+                            uint32_t stages, uint32_t opts, const aegis_outputs *dout, double rake_sensitivity) {
+    const Tables &t = h->tab;
+    const bool py = stages & AEGIS_STAGE_PYIN, mel = stages & AEGIS_STAGE_MEL;
+    const int nc = m.nc(), n_seg = m.n_seg, S = 2 * t.n_bins;
+    PassParams p = base_params(t);
+    p.stages = stages;
+    p.pcm = d_pcm;
+    p.sample_off = static_cast<const int64_t *>(w.sample_off.p);
+    p.sample_len = static_cast<const int64_t *>(w.sample_len.p);
+    p.frame_off = static_cast<const int64_t *>(w.frame_off.p);
+    p.out_off = static_cast<const int64_t *>(w.out_off.p);
+    p.order = static_cast<const int32_t *>(w.order.p);
+    p.n_clips = nc; p.n_frames = m.fp;
+    p.dfn = static_cast<double *>(w.dfn.p); p.lag_stride = h->lag_stride;
+    p.yin = (py && h->debug_stages) ? static_cast<double *>(w.yin.p) : nullptr; p.yin_stride = h->yin_stride;
+    p.cmnd_in_frame = cmnd_in_frame(h); p.troughs = troughs_in_frame(h);
+    p.logobs = static_cast<double *>(w.logobs.p); p.obs_stride = h->obs_stride;
+    p.logunv = static_cast<double *>(w.logunv.p);
+    p.obs_seg = static_cast<int32_t *>(w.obs_seg.p);
+    p.ptr = static_cast<uint16_t *>(w.ptr.p);
+    p.cmap = static_cast<uint16_t *>(w.cmap.p);
+    p.chunk_off = static_cast<int64_t *>(w.chunk_off.p);
+    p.bnd = static_cast<int32_t *>(w.bnd.p);
+    p.states = static_cast<int32_t *>(w.states.p);
+    p.melpow = static_cast<float *>(w.melpow.p);
+    p.clipmax = static_cast<uint32_t *>(w.clipmax.p);
+    p.rake_raw = static_cast<uint8_t *>(w.rake_raw.p);
+    p.vstate = static_cast<double *>(w.vstate.p);
+    p.vstats = static_cast<unsigned long long *>(h->vstats.p);
+    p.out_f0 = py ? dout->f0 : nullptr;
+    p.out_voiced = py ? dout->voiced_flag : nullptr;
+    p.out_vprob = py ? dout->voiced_prob : nullptr;
+    p.out_bin = py ? dout->pitch_bin : nullptr;
+    p.out_rms = (stages & AEGIS_STAGE_RMS) ? dout->rms : nullptr;
+    p.out_rake = (stages & AEGIS_STAGE_RAKE) ? dout->rake_mask : nullptr;
+    p.out_sdb = mel ? dout->S_dB : nullptr;
+    p.out_colmean = mel ? dout->sdb_col_means : nullptr;
+    p.out_total = h->plan.total_frames;
+    p.rake_ratio = rake_sensitivity;
+    const double ms_per_frame = ((double)t.hop / (double)t.sr) * 1000;      // vision.py:23-25
+    p.rake_min_frames = (int)(10 / ms_per_frame); p.rake_max_frames = (int)(30 / ms_per_frame);
+    if (opts & AEGIS_OPT_F0_ZERO) p.f0_unvoiced = 0.0;
+    p.dense = m.dense ? 1 : 0;
+    if (m.tsplit) {
+        const int64_t *g64 = static_cast<const int64_t *>(w.seg64.p);
+        const int32_t *g32 = static_cast<const int32_t *>(w.seg32.p);
+        p.seg_f0 = g64; p.seg_ch0 = g64 + n_seg;
+        p.vf_off = g64 + 2 * n_seg; p.vf_total = m.seg64.back();
+        p.seg_T = g32; p.seg_store = g32 + n_seg; p.seg_prev = g32 + 2 * n_seg; p.seg_clip = g32 + 3 * n_seg;
+        p.clip_seg0 = g32 + 4 * n_seg;
+        p.seg_col = static_cast<double *>(w.seg_col.p); p.seg_col2 = p.seg_col + (size_t)n_seg * S;
+        p.seg_map = static_cast<uint16_t *>(w.seg_map.p);
+        p.seg_kg = static_cast<int32_t *>(w.seg_i32.p); p.seg_lock = p.seg_kg + n_seg; p.seg_end = p.seg_kg + 2 * n_seg; p.clip_first = p.seg_kg + 3 * n_seg; p.clip_dirty = p.clip_first + nc;
+        p.colhist = static_cast<double *>(w.colhist.p); p.colG = static_cast<double *>(w.colG.p); p.colkg = static_cast<int32_t *>(w.colkg.p);
+        p.clip_flag = static_cast<uint32_t *>(w.clip_flag.p);
+        p.tube_buf = static_cast<int32_t *>(w.tube_buf.p); p.tube_cap = m.tube_cap; p.tube_count = static_cast<uint32_t *>(w.tube_count.p);
+        p.tube_at = static_cast<int32_t *>(w.tube_at.p);
+        p.n_seg = n_seg;
+    }
+    if (m.persistent) {
+        p.chunk_flag = static_cast<const uint32_t *>(w.chunk_flag.p);
+        p.chunk_lo = static_cast<const int64_t *>(w.chunk_lo.p);
+        p.n_chunks = m.nk();
+        if (m.hybrid) { int ks = 0; while (ks < m.nk() && m.cb[ks] <= m.hyb_S) ++ks; p.n_chunks = ks; }      // (the launch ends at step S: chunks 0 .. ks - 1)
+        p.abort_flag = static_cast<uint32_t *>(h->abort_flag.p);
+        // bound of one chunk wait: a chunk's frame stage takes well under a millisecond per 10 k frames, so 0.1 s plus
+        // 0.1 s per million frames of the pass is two orders of magnitude of slack, and a pass that cannot overlap
+        // (kernels serialised) costs that much once instead of 1.5 s
+        p.wait_ticks = (uint64_t)std::min<int64_t>(150000000, 10000000 + m.fp * 10);
+    }
+    return p;
+}
+
+static hipStream_t lane_stream(const aegis_handle *h, Lane l, hipStream_t s, const aegis_handle::SplitSet *ss) {
+    switch (l) {
+    case Lane::main: return s;
+    case Lane::frame2: return h->stream4;
+    case Lane::viterbi2: return h->stream2;
+    case Lane::masked_frame_a: return ss->frame_a;
+    case Lane::masked_frame_b: return ss->frame_b;
+    case Lane::masked_viterbi: return ss->viterbi;
+    default: return nullptr;
+    }
+}
+
+#define VCHK(expr) do { hipError_t ve__ = (expr); if (ve__ != hipSuccess) { h->err = std::string("viterbi launch: ") + hipGetErrorString(ve__); return AEGIS_ERR_DEVICE; } } while (0)
+
 static int analyze_device_locked(aegis_handle *h, const float *d_pcm, const int64_t *sample_offsets,
                                  int32_t n_clips, double rake_sensitivity, uint32_t stages,
                                  aegis_outputs *dout, void *stream_v, int32_t sync, HostFeed *feed) {
+    // ---- validate -----------------------------------------------------------------------------------------------------
     if (!h) return AEGIS_ERR_INVALID;
     if (n_clips < 0 || (n_clips > 0 && (!sample_offsets || !dout))) { h->err = "null argument"; return AEGIS_ERR_INVALID; }
     if (n_clips == 0) return AEGIS_OK;
@@ -724,41 +819,28 @@ static int analyze_device_locked(aegis_handle *h, const float *d_pcm, const int6
     if (h->device < 0) { h->err = "handle was created with device=-1 (host tables only)"; return AEGIS_ERR_DEVICE; }
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t s = stream_v ? static_cast<hipStream_t>(stream_v) : h->stream;
-
-    // per-clip frame counts, validation, and each clip's first frame in the output arrays (caller's clip order)
-    std::vector<int64_t> frames(n_clips), out_first(n_clips);
-    int64_t total_frames = 0;
     for (int i = 0; i < n_clips; ++i) {
         const int64_t n = sample_offsets[i + 1] - sample_offsets[i];
         if (n < 0) { h->err = "sample_offsets must be non-decreasing"; return AEGIS_ERR_INVALID; }
         if (n > 0 && !d_pcm) { h->err = "d_pcm == NULL"; return AEGIS_ERR_INVALID; }
-        frames[i] = 1 + n / t.hop;
-        if (frames[i] > h->max_frames_per_pass) {
-            h->err = "clip of " + std::to_string(frames[i]) + " frames exceeds max_frames_per_pass=" +
+        if (1 + n / t.hop > h->max_frames_per_pass) {
+            h->err = "clip of " + std::to_string(1 + n / t.hop) + " frames exceeds max_frames_per_pass=" +
                      std::to_string(h->max_frames_per_pass);
             return AEGIS_ERR_INVALID;
         }
-        out_first[i] = total_frames;
-        total_frames += frames[i];
     }
-    // host metadata from earlier calls is no longer referenced once the stream drained
-    if (!h->metas.empty()) { HIPCHK(h, hipStreamSynchronize(s)); h->metas.clear(); }
+    // host arrays of the previous call's plan are no longer referenced once the stream drained
+    if (h->plan_in_flight) { HIPCHK(h, hipStreamSynchronize(s)); h->plan_in_flight = false; }
     h->split_checks.clear();
     if (h->profiling) { for (auto &ev : h->events) { (void)hipEventDestroy(ev.second.first); (void)hipEventDestroy(ev.second.second); } h->events.clear(); }
 
-    // vision.py:23-25
-    const double ms_per_frame = ((double)t.hop / (double)t.sr) * 1000;
-    const int rake_min = (int)(10 / ms_per_frame), rake_max = (int)(30 / ms_per_frame);
-    const bool py = stages & AEGIS_STAGE_PYIN;
-    const int S = 2 * t.n_bins;
-
-    // Clips go through the passes LONGEST FIRST (outputs keep the caller's order through out_off): a pass lasts as long
-    // as the Viterbi of its longest clip, so clips of similar length share a pass and no compute unit idles behind a
-    // 330 s clip that happens to sit next to 30 s ones.  Passes alternate between two workspaces, so the frame stage of
-    // pass k+1 runs under the Viterbi of pass k.
-    std::vector<int> by_len(n_clips);
-    std::iota(by_len.begin(), by_len.end(), 0);
-    std::stable_sort(by_len.begin(), by_len.end(), [&](int a, int b) { return frames[a] > frames[b]; });
+    // ---- plan ---------------------------------------------------------------------------------------------------------
+    const PlanInput in = plan_input(h, sample_offsets, n_clips, stages, feed != nullptr, stream_v != nullptr, sync, h->n_cus,
+                                    [h](int n) { return split_streams(h, n) != nullptr; });
+    if (in.cooling) --h->split_cooldown;
+    h->plan = plan_call(in);
+    h->plan_in_flight = true;
+    const bool py = in.py;
 
     while (h->sync_events.size() < 8) {
         hipEvent_t e;
@@ -767,556 +849,76 @@ static int analyze_device_locked(aegis_handle *h, const float *d_pcm, const int6
     }
     // fixed slots of sync_events: 0 call start, 1/2 pass done (workspace parity), 3 frame_b joined, 4 frame_a final, 5.. per chunk
     enum { EV_START = 0, EV_DONE0 = 1, EV_DONE1 = 2, EV_FB = 3, EV_FA = 4, EV_META = 5, EV_CHUNK0 = 6 };
-
-    // ---- time-split planning (viterbi.hip "Time-split Viterbi") --------------------------------------------------------
-    // The Viterbi recurrence keeps one compute unit per clip for (frames of the clip) x 3.1 us; the rest of the path costs
-    // ~43 ns per frame of the whole chip.  A pass whose longest clip outlasts the work of the whole pass cuts its clips into
-    // segments that run concurrently (blocking calls on the handle's own stream only: the clips that cannot be certified are
-    // redone after the call's synchronisation).  plan_split: the segment length for a set of clips, 0 = stay sequential.
-    const bool split_ok = py && !stream_v && sync && h->split_seglen != 0 && viterbi_split_applies(base_params(t), h->dt);
-    bool split_cooling = false;
-    if (split_ok && h->split_seglen < 0 && h->split_cooldown > 0) { --h->split_cooldown; split_cooling = true; }
-    const bool feed_pass = feed != nullptr;
-    bool want_hybrid = false;      // set by plan_split: the pass pays only in the hybrid form (no split pass if that cannot be set up)
-    auto plan_split = [&](const int *clips_of_pass, int nc, int64_t fp, int64_t maxF, bool &automatic) -> int64_t {
-        automatic = false; want_hybrid = false;
-        if (!split_ok || nc >= 256) return 0;
-        if (h->split_seglen > 0) return h->split_seglen;
-        if (split_cooling) return 0;
-        // automatic: when the estimate says so.  Sequential pass: the longest clip's recurrence, or the pass's whole work if
-        // that is more (they overlap); split pass: the frame stage first (3/4 of the work, not overlapped), then one segment +
-        // warm-up + a typical lock-on tail, stitch and verification.
-        const double step = t.half_width == 25 ? 3.1e-6 : 7.3e-6, work = (double)fp * 43e-9;
-        const int seg_budget = std::max(1, h->n_cus) * h->split_rounds_of_segments;
-        int64_t sl = std::max<int64_t>(768, ((fp - nc) / seg_budget + kViterbiChunk - 1) / kViterbiChunk * kViterbiChunk);
-        // whole rounds of workgroups: a 257th segment would run alone after the other 256
-        for (int guard = 0; guard < 64; ++guard) {
-            int64_t ns = 0;
-            for (int i = 0; i < nc; ++i) ns += std::max<int64_t>(1, (frames[clips_of_pass[i]] - 1 + sl - 1) / sl);
-            if (ns <= seg_budget) break;
-            sl = (sl + sl / 32 + kViterbiChunk) / kViterbiChunk * kViterbiChunk;
-        }
-        const double t_seq = std::max((double)maxF * step, work);
-        const double t_split = 0.75 * work + (double)(sl + h->split_warmup + 600) * step + 2.5e-3;
-        if (t_split < 0.8 * t_seq) { automatic = true; return sl; }
-        // Passes of 65 .. 255 clips that the rule above leaves alone: too much work for a frame stage IN FRONT of the segments
-        // to pay, but their frame stage is through long before their longest clip (128 ragged clips, a rank of four: frame stage
-        // 71 ms, last Viterbi launch 118 ms -- one in eight compute units busy in between).  The hybrid form costs no front:
-        // the sequential launches run under the frame stage as they do today (5.2 us per step beside it, measured), and what the
-        // longest clip has left when the frame stage ends is cut into segments.  Estimate: frame stage, then one segment +
-        // warm-up per round and 12 ms of lock-on runs, verification and exact walk -- against the frame stage plus the steps
-        // the longest clip still has to walk alone.
-        if (h->split_hybrid != 0 && nc > h->split_limit && !feed_pass) {
-            const double front = 0.8 * work, s_est = front / (1.7 * step);
-            const double t_seq2 = std::max(t_seq, front + std::max(0.0, (double)maxF - s_est) * step);
-            const double t_hyb = front + (double)h->hybrid_rounds * (double)(h->hybrid_min_seg + h->split_warmup) * 1.1 * step + 12e-3;
-            if ((double)maxF > s_est + 4096 && t_hyb < 0.9 * t_seq2) { automatic = true; want_hybrid = true; return h->hybrid_min_seg; }
-        }
-        return 0;
-    };
-    // Sub-passes.  A split pass runs its frame stage IN FRONT of its segments (they need every frame's observations), and
-    // behind the speculative runs the lock-on runs, the verification and the exact walk keep only a few compute units busy.
-    // With AEGIS_SPLIT_SUB_PASSES=2 a call that would be one split pass of >= 16 clips is cut into two passes of every second
-    // clip (longest first in both): the second half's frame stage runs under the first half's Viterbi kernels, on the pass
-    // machinery that already overlaps pass k + 1's frame stage with pass k's Viterbi (two workspaces).  Measured slower (see
-    // split_sub_passes): kept as an experiment knob, off by default.
-    int sub_cut = 0;
-    h->call_split_started = false;
-    if (split_ok && h->split_sub_passes > 1 && n_clips >= 16 && n_clips < 256 && total_frames <= h->max_frames_per_pass) {
-        bool automatic = false;
-        if (plan_split(by_len.data(), n_clips, total_frames, frames[by_len[0]], automatic) > 0) {
-            std::vector<int> re;
-            re.reserve(n_clips);
-            for (int i = 0; i < n_clips; i += 2) re.push_back(by_len[i]);
-            sub_cut = (int)re.size();
-            for (int i = 1; i < n_clips; i += 2) re.push_back(by_len[i]);
-            by_len.swap(re);
-        }
-    }
-    h->call_t_seq = std::max((double)frames[by_len[0]] * (t.half_width == 25 ? 3.1e-6 : 7.3e-6), (double)total_frames * 43e-9);
-
-    int first = 0, pass_index = 0;
-    bool done_recorded[2] = {false, false};
+    bool done_recorded[2] = {false, false}, split_started = false;
     std::vector<hipStream_t> joined;          // streams whose work s must wait for before the call returns
-    while (first < n_clips) {
-        int last = first;
-        int64_t fp = 0;
-        if (sub_cut > 0) {          // the two halves of a split call
-            last = first == 0 ? sub_cut : n_clips;
-            for (int i = first; i < last; ++i) fp += frames[by_len[i]];
-        } else
-        while (last < n_clips && fp + frames[by_len[last]] <= h->max_frames_per_pass) { fp += frames[by_len[last]]; ++last; }
-        const int nc = last - first;
-        const int *pc = by_len.data() + first;            // this pass's clips (indices into the caller's arrays)
-        aegis_handle::Work &w = h->work[pass_index & 1];
-        h->metas.emplace_back();
-        PassMeta &m = h->metas.back();
-        m.sample_off.resize(nc); m.sample_len.resize(nc); m.out_off.resize(nc);
-        m.frame_off.resize(nc + 1); m.chunk_off.resize(nc + 1);
-        m.frame_off[0] = 0; m.chunk_off[0] = 0;
-        int64_t maxF = 0;
-        for (int i = 0; i < nc; ++i) {
-            const int ci = pc[i];
-            m.sample_off[i] = sample_offsets[ci];
-            m.sample_len[i] = sample_offsets[ci + 1] - sample_offsets[ci];
-            m.out_off[i] = out_first[ci];
-            m.frame_off[i + 1] = m.frame_off[i] + frames[ci];
-            m.chunk_off[i + 1] = m.chunk_off[i] + (frames[ci] - 1 + kViterbiChunk - 1) / kViterbiChunk;
-            maxF = std::max(maxF, frames[ci]);
+    for (int pi = 0; pi < (int)h->plan.passes.size(); ++pi) {
+        const PassPlan &m = h->plan.passes[pi];
+        const int nc = m.nc(), nk = m.nk();
+        aegis_handle::Work &w = h->work[pi & 1];
+        int rc;
+        // ---- wait for the workspace: a split verdict of the pass two back is read (and acted on) before anything
+        // overwrites it or ensure() moves its buffers
+        if (!h->split_checks.empty() && h->split_checks.front().pass == pi - 2) {
+            HIPCHK(h, hipEventSynchronize(h->sync_events[EV_DONE0 + (pi & 1)]));
+            const aegis_handle::SplitCheck sc = h->split_checks.front();
+            h->split_checks.erase(h->split_checks.begin());
+            if ((rc = split_check(h, sc, s)) != AEGIS_OK) return rc;
         }
-        m.order.resize(nc);
-        std::iota(m.order.begin(), m.order.end(), 0);     // already longest first
-        const int64_t nchunks = m.chunk_off[nc];
-
-        // ---- time chunks of the pipeline ---------------------------------------------------------------
-        // The Viterbi recurrence is sequential in time and occupies one compute unit per clip; the frame-stage kernels
-        // are wide.  A pass is therefore cut into time chunks: chunk k's frame stage runs on the frame streams while
-        // chunk k-1's Viterbi runs on the Viterbi stream, carrying its column of values exactly (vstate) across
-        // launches.  Boundaries: frame 0, then 1 + (multiple of kViterbiChunk) so that every launch starts on a
-        // back-pointer-map boundary.  Chunks start at a quarter of time_chunk and grow by 1.25x (the frame stage is
-        // faster than the Viterbi per column, so the Viterbi stream never waits after the first chunk).
-        //
-        // Balanced passes: on the CU-partitioned streams (split_streams) a pass of 64 clips keeps the frame stage's 192
-        // CUs as long per column as the Viterbi keeps its 64 (3.1 us each), so neither may wait for the other: chunks
-        // of one small size (growing chunks make the Viterbi wait a quarter of each), alternating over the two frame
-        // streams so that one chunk's FFT kernel overlaps the previous chunk's latency-bound observation kernel, and ONE
-        // Viterbi launch that waits for a flag per chunk (64 clips x 180 s: 59.5 -> 50.8 ms).  With fewer clips the pass is
-        // Viterbi-bound and the gain is the launches and the head (48 clips: 52.0 -> 50.2 ms, 16: 50.2 -> 50.0, 8: 49.5
-        // -> 49.8), hence the lower limit; unpartitioned passes lose with small chunks.
-        bool split_auto = false;
-        int64_t seglen = py ? plan_split(pc, nc, fp, maxF, split_auto) : 0;
-        bool tsplit = seglen > 0;
-        // hybrid (see split_hybrid): S = the step the sequential kernel reaches while the frame stage runs, on a chunk boundary of
-        // the schedule the pass would take anyway -- up to split_limit clips the balanced one on the CU-partitioned streams (ONE
-        // launch of the sequential kernel), above it the ramp of growing chunks on the un-partitioned streams (a launch per
-        // chunk, 5.2 us per step beside the frame stage); worth it when S is at least a couple of segments' worth of steps.
-        // hyb_cb: the pass's chunk boundaries, S + 1 among them; behind S four large chunks (nothing waits for them one by one).
-        int64_t hyb_S = 0, hyb_chunk = 0;
-        bool hyb_part = false;
-        std::vector<int64_t> hyb_cb;
-        if (tsplit && h->split_hybrid != 0 && (split_auto || h->split_hybrid == 1) && h->n_cus == 256) {
-            const double step = t.half_width == 25 ? 3.1e-6 : 7.3e-6;
-            hyb_part = nc <= h->split_limit && h->split_limit > 0 && h->balanced_chunk > 0 && split_streams(h, nc) != nullptr;
-            double front = hyb_part ? 0.75 * (double)fp * 43e-9 * (256.0 / 192.0) : 0.8 * (double)fp * 43e-9;
-            if (feed) {       // a pass fed from host memory: its frame stage cannot outrun the copies (46.7 GB/s pageable, measured)
-                int64_t samples = 0;
-                for (int i = 0; i < nc; ++i) samples += sample_offsets[pc[i] + 1] - sample_offsets[pc[i]];
-                front = std::max(front, (double)samples * 4.0 / 46.7e9);
-            }
-            const int64_t target = (int64_t)((double)h->hybrid_pct / 100.0 * front / (hyb_part ? step : 1.7 * step));
-            std::vector<int64_t> bs{0};
-            if (hyb_part) {
-                // (one launch of the sequential kernel waiting for a flag per chunk, as in balanced passes: half the chunk size)
-                // (fed from host memory: the feed's chunk size and a launch per chunk, as balanced passes of that kind take)
-                hyb_chunk = std::max<int64_t>(kViterbiChunk, (feed ? h->feed_chunk : (h->persistent && sync ? h->balanced_chunk / 2 : h->balanced_chunk)) * 64 / nc / kViterbiChunk * kViterbiChunk);
-                for (int64_t b = 1 + std::max<int64_t>(kViterbiChunk, hyb_chunk - kViterbiChunk); b < maxF; b += hyb_chunk) bs.push_back(b);
-            } else {
-                int64_t stp = std::max<int64_t>(kViterbiChunk, h->chunk_start / kViterbiChunk * kViterbiChunk);
-                for (int64_t b = 1 + stp; b < maxF;) {
-                    bs.push_back(b);
-                    stp = std::min<int64_t>(h->time_chunk, (stp * h->chunk_growth_pct / 100 + kViterbiChunk - 1) / kViterbiChunk * kViterbiChunk);
-                    b += stp;
-                }
-            }
-            if (feed && !hyb_part) bs.resize(1);       // (host-fed passes: the partitioned form only)
-            size_t best = 0;       // the boundary nearest the target
-            for (size_t i = 1; i < bs.size(); ++i)
-                if (std::llabs(bs[i] - 1 - target) < std::llabs(bs[best] - 1 - target)) best = i;
-            const int64_t S0 = best > 0 ? bs[best] - 1 : 0;
-            if (target >= 2048 && S0 >= 1024 && S0 + 4 * kViterbiChunk < maxF - 1) {
-                hyb_S = S0;
-                if (hyb_part) {
-                    hyb_cb.assign(bs.begin(), bs.begin() + (long)best + 1);
-                    const int64_t big = std::max<int64_t>(4 * kViterbiChunk, ((maxF - hyb_S - 1) / 4 + kViterbiChunk - 1) / kViterbiChunk * kViterbiChunk);
-                    for (int64_t b = hyb_S + 1 + big; b + big / 2 < maxF; b += big) hyb_cb.push_back(b);
-                } else {
-                    // (un-partitioned: the sequential launches share the compute units with the frame stage, and four large chunks
-                    // queued in front of them held them back -- at step 7.8 k instead of 13.4 k when the frame stage was through)
-                    hyb_cb = bs;
-                    while (hyb_cb.size() > 1 && hyb_cb.back() + h->time_chunk / 2 >= maxF && hyb_cb.back() > hyb_S + 1) hyb_cb.pop_back();
-                }
-            }
-        }
-        if (want_hybrid && hyb_S == 0) { seglen = 0; split_auto = false; tsplit = false; }      // (planned for the hybrid form only)
-        const bool hybrid = hyb_S > 0;
-        if (hybrid && split_auto) {       // the steps left behind S, one round of segments on the whole chip
-            int64_t left = 0;
-            for (int i = 0; i < nc; ++i) left += std::max<int64_t>(0, frames[pc[i]] - 1 - hyb_S);
-            // (whole rounds of workgroups on the 192 compute units the frame stage leaves: the speculative runs start while the
-            // sequential kernel still holds its 64)
-            const int64_t budget = (int64_t)(hyb_part ? 192 : h->n_cus) * h->hybrid_rounds;
-            seglen = std::max<int64_t>(h->hybrid_min_seg, (left / budget + kViterbiChunk) / kViterbiChunk * kViterbiChunk);
-            for (int guard = 0; guard < 64; ++guard) {       // (ceil per clip: lengthen until the segments fit)
-                int64_t ns = 0;
-                for (int i = 0; i < nc; ++i) { const int64_t rest = frames[pc[i]] - 1 - hyb_S; if (rest > 0) ns += (rest + seglen - 1) / seglen; }
-                if (ns <= budget) break;
-                seglen = (seglen + seglen / 32 + kViterbiChunk) / kViterbiChunk * kViterbiChunk;
-            }
-        }
-        int n_seg = 0, n_lock = 0, tube_cap = 0;
-        if (tsplit) {
-            const int L = h->split_warmup;
-            std::vector<int64_t> sf0, sch0;
-            std::vector<int32_t> sT, sst, sprev, sclip, cseg0(nc + 1, 0);
-            for (int i = 0; i < nc; ++i) {
-                const int64_t Fc = frames[pc[i]], steps = Fc - 1;
-                if (hybrid) {
-                    // first segment = the sequential run to step S (a clip that ends by then: all of it, decoded by that kernel, and a
-                    // one-frame placeholder here), then ceil((steps - S) / seglen) segments of equal length behind S
-                    cseg0[i] = n_seg;
-                    const bool more = steps > hyb_S;
-                    sf0.push_back(m.frame_off[i]); sch0.push_back(m.chunk_off[i]);
-                    sT.push_back(more ? (int32_t)(hyb_S + 1) : 1); sst.push_back(0); sprev.push_back(-1); sclip.push_back(i);
-                    ++n_seg;
-                    if (!more) continue;
-                    const int64_t rest = steps - hyb_S;
-                    const int ns = (int)std::max<int64_t>(1, (rest + seglen - 1) / seglen);
-                    int64_t mprev = hyb_S;
-                    for (int k = 0; k < ns; ++k) {
-                        const int64_t mk = k == 0 ? hyb_S : std::max<int64_t>(mprev + kViterbiChunk, hyb_S + (rest * k / ns) / kViterbiChunk * kViterbiChunk);
-                        const int64_t mnext = k == ns - 1 ? Fc - 1 : std::max<int64_t>(mk + kViterbiChunk, hyb_S + (rest * (k + 1) / ns) / kViterbiChunk * kViterbiChunk);
-                        const int64_t wk = std::max<int64_t>(0, mk - L);
-                        sf0.push_back(m.frame_off[i] + wk);
-                        sch0.push_back(m.chunk_off[i] + wk / kViterbiChunk);
-                        sT.push_back((int32_t)(mnext - wk + 1));
-                        sst.push_back((int32_t)(mk - wk));
-                        sprev.push_back(n_seg - 1);
-                        sclip.push_back(i);
-                        mprev = mk;
-                        ++n_seg;
-                    }
-                    continue;
-                }
-                // (ceil: no segment longer than seglen -- the launch lasts as long as its longest segment; with rounding a clip of
-                // 1.49 segment lengths ran as ONE segment and set the pace of the whole launch)
-                const int ns = (int)std::max<int64_t>(1, (steps + seglen - 1) / seglen);
-                cseg0[i] = n_seg;
-                int64_t mprev = 0;
-                for (int k = 0; k < ns; ++k) {
-                    // boundaries on back-pointer chunk boundaries (multiples of 16); the last segment ends at the last frame
-                    const int64_t mk = k == 0 ? 0 : std::max<int64_t>(mprev + kViterbiChunk, (steps * k / ns) / kViterbiChunk * kViterbiChunk);
-                    const int64_t mnext = k == ns - 1 ? Fc - 1 : std::max<int64_t>(mk + kViterbiChunk, (steps * (k + 1) / ns) / kViterbiChunk * kViterbiChunk);
-                    const int64_t wk = k == 0 ? 0 : std::max<int64_t>(0, mk - L);
-                    sf0.push_back(m.frame_off[i] + wk);
-                    sch0.push_back(m.chunk_off[i] + wk / kViterbiChunk);
-                    sT.push_back((int32_t)(mnext - wk + 1));
-                    sst.push_back((int32_t)(mk - wk));
-                    sprev.push_back(k == 0 ? -1 : n_seg - 1);
-                    sclip.push_back(i);
-                    mprev = mk;
-                    ++n_seg;
-                }
-            }
-            cseg0[nc] = n_seg;
-            m.seg64 = sf0; m.seg64.insert(m.seg64.end(), sch0.begin(), sch0.end());
-            // vf_off: the frames behind every split clip's first boundary (what the verification kernel's grid covers)
-            {
-                int64_t acc = 0;
-                for (int i = 0; i <= nc; ++i) {
-                    m.seg64.push_back(acc);
-                    if (i < nc && cseg0[i + 1] - cseg0[i] >= 2) {
-                        const int k1 = cseg0[i] + 1;
-                        const int64_t fx = sf0[k1] + sst[k1];            // workspace frame of the first boundary
-                        acc += m.frame_off[i] + frames[pc[i]] - 1 - fx;
-                    }
-                }
-            }
-            m.seg32.clear();
-            for (auto *v : {&sT, &sst, &sprev, &sclip, &cseg0}) m.seg32.insert(m.seg32.end(), v->begin(), v->end());
-            // seg_order: the speculative runs (n_seg entries reserved; a hybrid pass lists only the segments behind the first ones)
-            for (int k = 0; k < n_seg; ++k) if (!hybrid || sprev[k] >= 0) m.seg32.push_back(k);
-            if (hybrid) for (int k = 0; k < n_seg; ++k) if (sprev[k] < 0) m.seg32.push_back(k);       // (padding: keeps the layout)
-            for (int k = 0; k < n_seg; ++k) if (sprev[k] >= 0) { m.seg32.push_back(k); ++n_lock; }      // lock_order
-        }
-        const bool balanced = !tsplit && py && !stream_v && h->balanced_chunk > 0 && nc >= h->balanced_min && h->n_cus == 256 &&
-                              h->split_limit > 0 && nc <= h->split_limit && nc <= 128;
-        // (a persistent Viterbi launch pays nothing per chunk: half the chunk size, 54.3 -> 52.0 ms).  The size is stated for
-        // 64 clips and scaled so that a chunk's observation kernel is ONE full round of workgroups on the frame stage's
-        // 192 CUs (2 x 192 workgroups of 32 frames = 12 288 frames = 192 steps x 64 clips) and its frame kernel two:
-        // 224 steps instead of 192 leave a sixth of a second round behind (54.1 instead of 50.6 ms).
-        // A pass fed from host memory (aegis_analyze_batch) copies each chunk's samples from the thread that launches its
-        // kernels, and a pageable copy returns only when the bytes have left the caller's buffer: chunks of 192 steps are
-        // 5 000 copies of 0.4 MB per 64 x 180 s, and the single launch spins on flags that thread is late to set (64 x
-        // 180 s: 108 ms; a launch per chunk: 70).  Such a pass takes 1 024-step chunks (2 MB per clip and copy) and a launch
-        // per chunk: 57 ms, against 63 on the unbalanced schedule it used before and 49.4 device-resident.
-        const bool may_persist = balanced && !feed && h->persistent && sync && viterbi_band_applies(base_params(t), h->dt);
-        int64_t kTimeChunk = h->time_chunk;
-        if (balanced) {
-            const int64_t at64 = feed ? h->feed_chunk : (may_persist ? h->balanced_chunk / 2 : h->balanced_chunk);
-            kTimeChunk = std::max<int64_t>(kViterbiChunk, at64 * 64 / nc / kViterbiChunk * kViterbiChunk);
-        }
-        if (hybrid && hyb_part) kTimeChunk = hyb_chunk;
-        std::vector<int64_t> cb{0};
-        if (hybrid) {
-            // chunks of the schedule's own size while the sequential kernel follows (to step S: the Viterbi sets the pace), then the
-            // rest of the frame stage in a few large ones: a chunk's two kernels take ~0.5 ms however few frames it holds, and
-            // behind S nothing waits for them chunk by chunk (148 chunks of 192 steps: the frame stage alone took 66 ms)
-            cb = hyb_cb;
-        } else if (balanced && maxF > 2 * kTimeChunk) {
-            // (chunk 0 holds frame 0 besides its steps: one back-pointer block less keeps it inside the round too)
-            if (may_persist && h->balanced_ends > 0 && maxF > 8 * kTimeChunk) {
-                // shorter chunks at both ends (the Viterbi starts behind chunk 0 and finishes a chunk after the frame
-                // stage): ends, 2 ends, ... doubling up to the chunk size, mirrored at the end (50.8 -> 50.4 ms)
-                std::vector<int64_t> ramp;
-                for (int64_t sz = std::max<int64_t>(kViterbiChunk, h->balanced_ends / kViterbiChunk * kViterbiChunk); sz < kTimeChunk; sz *= 2) ramp.push_back(sz);
-                int64_t ramp_sum = 0;
-                for (int64_t v : ramp) ramp_sum += v;
-                int64_t b = 1;
-                for (int64_t v : ramp) { b += v; cb.push_back(b); }
-                const int64_t mid_end = maxF - ramp_sum;
-                for (b += kTimeChunk; b + kTimeChunk / 2 < mid_end; b += kTimeChunk) cb.push_back(b);
-                b = cb.back() + ((mid_end - cb.back()) / kViterbiChunk * kViterbiChunk);
-                if (b > cb.back()) cb.push_back(b);
-                for (size_t i = ramp.size(); i-- > 1;) { b += ramp[i]; if (b < maxF) cb.push_back(b); }
-            } else
-            for (int64_t b = 1 + std::max<int64_t>(kViterbiChunk, kTimeChunk - kViterbiChunk); b + kTimeChunk / 2 < maxF; b += kTimeChunk) cb.push_back(b);
-        } else if (py && tsplit && feed) {
-            // a time-split pass fed from host memory: its segments need every frame's observations, but its frame stage need not
-            // wait for the last sample -- chunks of the feed size, each chunk's copy under the frame stage of the chunk before
-            // (64 x 180 s at 22 050 Hz: copy 20 ms + frame stage 12 ms + segments 22 ms in a row before)
-            const int64_t fc = std::max<int64_t>(4 * kViterbiChunk, h->feed_chunk * 64 / nc / kViterbiChunk * kViterbiChunk);
-            for (int64_t b = 1 + fc - kViterbiChunk; b + fc / 2 < maxF; b += fc) cb.push_back(b);
-        } else if (py && !tsplit && maxF > kTimeChunk + kTimeChunk / 2) {      // (a device-resident time-split pass: the whole frame stage, then all segments at once)
-            int64_t step = std::max<int64_t>(kViterbiChunk, h->chunk_start / kViterbiChunk * kViterbiChunk);
-            cb.push_back(1 + step);
-            while (cb.back() + kTimeChunk + kTimeChunk / 2 < maxF) {
-                step = std::min<int64_t>(kTimeChunk, (step * h->chunk_growth_pct / 100 + kViterbiChunk - 1) / kViterbiChunk * kViterbiChunk);
-                cb.push_back(cb.back() + step);
-            }
-        }
-        cb.push_back(maxF);
-        const int nk = (int)cb.size() - 1;
-        auto chunk_lo = [&](int k) { return cb[k]; };
-        auto chunk_hi = [&](int k) { return cb[k + 1]; };
-        // Ragged passes: every clip is cut into the SAME nk chunks, each a share of the clip proportional to the chunk's
-        // share of the longest clip (boundaries stay on 1 + multiples of kViterbiChunk).  With one time axis for all clips
-        // the short clips are done after a few chunks and the last launches hold only the long clips' Viterbi workgroups
-        // on an otherwise idle chip (512-clip folder: the last 36 of 363 ms); with proportional chunks every launch
-        // carries every clip and all of them finish with the last chunk.  The results do not depend on the cut.
-        // Throughput passes (a Viterbi workgroup for every CU and more): the register-capped Viterbi build and four-wave
-        // observation workgroups (viterbi.hip); AEGIS_DENSE=0 turns it off, =1 forces it for every unbalanced pass (tests).
-        const bool dense = py && !balanced && !tsplit && viterbi_band_applies(base_params(t), h->dt) && t.half_width == 25 &&
-                           (h->dense_mode == 1 || (h->dense_mode < 0 && nc >= 256));
-        bool proportional = false;
-        // (not for a pass fed from host memory: it is bound by the pageable copies, and a short clip's proportional chunk is a
-        // copy of a few hundred KB -- 512-clip folder, host-inclusive: 496 ms against 466 on one time axis)
-        if (py && !balanced && !feed && !tsplit && nk > 2 && h->proportional_chunks) {
-            int64_t minF = maxF;
-            for (int i = 0; i < nc; ++i) minF = std::min(minF, frames[pc[i]]);
-            proportional = 4 * minF < 3 * maxF;
-        }
-        // tb[k * nc + i]: first frame of chunk k of the pass's clip i (k = nk: its frame count)
-        m.clip_tb.clear();
-        if (proportional) {
-            m.clip_tb.assign((size_t)(nk + 1) * nc, 0);
-            for (int i = 0; i < nc; ++i) {
-                const int64_t Fc = frames[pc[i]];
-                int64_t prev = 0;
-                for (int k = 1; k <= nk; ++k) {
-                    int64_t b = Fc;
-                    if (k < nk) {
-                        const int64_t want = 1 + (int64_t)((double)(cb[k] - 1) * (double)Fc / (double)maxF) / kViterbiChunk * kViterbiChunk;
-                        b = std::min(Fc, std::max(want, prev == 0 ? 1 + kViterbiChunk : prev + kViterbiChunk));
-                    }
-                    m.clip_tb[(size_t)k * nc + i] = b;
-                    prev = b;
-                }
-            }
-        }
-        auto clip_lo = [&](int k, int i) { return proportional ? m.clip_tb[(size_t)k * nc + i] : std::min(frames[pc[i]], chunk_lo(k)); };
-        auto clip_hi = [&](int k, int i) { return proportional ? m.clip_tb[(size_t)(k + 1) * nc + i] : std::min(frames[pc[i]], chunk_hi(k)); };
-        m.sel_off.assign((size_t)nk * (nc + 1), 0);
-        for (int k = 0; k < nk; ++k)
-            for (int i = 0; i < nc; ++i) {
-                const int64_t cnt = std::max<int64_t>(0, clip_hi(k, i) - clip_lo(k, i));
-                m.sel_off[(size_t)k * (nc + 1) + i + 1] = m.sel_off[(size_t)k * (nc + 1) + i] + cnt;
-            }
-
-        // ---- streams -----------------------------------------------------------------------------------
-        // CU-partitioned streams while the batch leaves compute units free (see split_streams); otherwise the caller's
-        // stream carries the frame stage and the handle's second stream the Viterbi.
-        aegis_handle::SplitSet *ss = (py && nk > 1 && !stream_v && (!tsplit || (hybrid && hyb_part))) ? split_streams(h, nc) : nullptr;      // (segments want every CU)
-        hipStream_t fa = ss ? ss->frame_a : s;
-        hipStream_t fb = ss ? ss->frame_b : h->stream4;
-        hipStream_t sv = ss ? ss->viterbi : ((py && (nk > 1 || tsplit)) ? h->stream2 : fa);      // (a split pass: the next pass's frame stage runs under its Viterbi kernels)
-        // Large batches are frame-stage bound (every CU carries a Viterbi workgroup): alternating the chunks over two
-        // streams lets chunk k+1's FFTs overlap chunk k's latency-bound observation kernel.  Small batches are
-        // Viterbi-bound and want each chunk's frame stage finished as early as possible: one stream, except for the
-        // first four (short) chunks, whose kernels are too small to fill the chip on their own.
-        const bool two_fs = py && nk > 2 && nc >= 128 && (!tsplit || hybrid);      // (a chunked split pass fed from host memory keeps one frame stream: its one Viterbi launch waits for the last chunk's event only)
-        const int ramp_k = (py && nk > 2 && !two_fs && (!tsplit || hybrid)) ? ((balanced || (hybrid && hyb_part)) ? nk : h->ramp_k) : 0;
-        // a hybrid pass ends on an unmasked stream (its segments want every CU, the partitioned pipeline's Viterbi stream has 64);
-        // its speculative runs go behind the frame stage, beside the sequential kernel's last chunks: a stream of their own on
-        // the partitioned set, the frame stream itself otherwise
-        hipStream_t sd = hybrid ? h->stream2 : nullptr;
-        hipStream_t sa = hybrid ? (hyb_part ? h->stream4 : fa) : nullptr;
-        const bool use_fb = two_fs || ramp_k > 0;
+        const aegis_handle::SplitSet *ss = m.fa == Lane::masked_frame_a ? split_streams(h, nc) : nullptr;
+        hipStream_t fa = lane_stream(h, m.fa, s, ss), fb = lane_stream(h, m.fb, s, ss), sv = lane_stream(h, m.sv, s, ss);
+        hipStream_t sd = lane_stream(h, m.sd, s, ss), sa = lane_stream(h, m.sa, s, ss);
         while ((int)h->sync_events.size() < EV_CHUNK0 + nk) {
             hipEvent_t e;
             HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
             h->sync_events.push_back(e);
         }
         auto join_later = [&](hipStream_t q) { if (q != s && std::find(joined.begin(), joined.end(), q) == joined.end()) joined.push_back(q); };
-        if (pass_index == 0) HIPCHK(h, hipEventRecord(h->sync_events[EV_START], s));
+        if (pi == 0) HIPCHK(h, hipEventRecord(h->sync_events[EV_START], s));
         for (hipStream_t q : {fa, fb, sv, sd, sa}) {
             if (q == s || q == nullptr) continue;
             if (std::find(joined.begin(), joined.end(), q) == joined.end())
                 HIPCHK(h, hipStreamWaitEvent(q, h->sync_events[EV_START], 0));      // the caller's earlier work on s comes first
             // this workspace was last used two passes ago: everything of that pass must have finished
-            if (done_recorded[pass_index & 1]) HIPCHK(h, hipStreamWaitEvent(q, h->sync_events[EV_DONE0 + (pass_index & 1)], 0));
+            if (done_recorded[pi & 1]) HIPCHK(h, hipStreamWaitEvent(q, h->sync_events[EV_DONE0 + (pi & 1)], 0));
         }
-        if (fa == s && done_recorded[pass_index & 1]) HIPCHK(h, hipStreamWaitEvent(s, h->sync_events[EV_DONE0 + (pass_index & 1)], 0));
-        join_later(fa); join_later(sv); if (use_fb) join_later(fb); if (sd) { join_later(sd); join_later(sa); }
+        if (fa == s && done_recorded[pi & 1]) HIPCHK(h, hipStreamWaitEvent(s, h->sync_events[EV_DONE0 + (pi & 1)], 0));
+        join_later(fa); join_later(sv); if (m.use_fb) join_later(fb); if (sd) { join_later(sd); join_later(sa); }
 
-        // ---- workspace ---------------------------------------------------------------------------------
-        int rc;
-#define ENS(buf, bytes) if ((rc = ensure(h, w.buf, (size_t)(bytes))) != AEGIS_OK) return rc
-        ENS(sample_off, nc * 8); ENS(sample_len, nc * 8); ENS(out_off, nc * 8); ENS(frame_off, (nc + 1) * 8);
-        ENS(order, nc * 4); ENS(chunk_off, (nc + 1) * 8); ENS(sel_off, (size_t)nk * (nc + 1) * 8);
-        if (py) {
-            ENS(dfn, fp * h->lag_stride * 8); if (h->debug_stages) ENS(yin, fp * h->yin_stride * 8);
-            ENS(logobs, fp * h->obs_stride * 8); ENS(logunv, fp * 8); ENS(obs_seg, fp * 4);
-            ENS(ptr, fp * S * 2); ENS(cmap, (nchunks + 1) * S * 2); ENS(bnd, (nchunks + 1) * 4);
-            ENS(states, fp * 4); ENS(vstate, (size_t)nc * S * 8);
-            ENS(chunk_lo, (size_t)nk * 8); ENS(chunk_flag, (size_t)nk * 4);
-            if (proportional) ENS(clip_tb, (size_t)(nk + 1) * nc * 8);
-            if (tsplit) {
-                ENS(seg64, m.seg64.size() * 8); ENS(seg32, m.seg32.size() * 4);
-                ENS(seg_col, (size_t)2 * n_seg * S * 8); ENS(seg_map, (size_t)n_seg * S * 2); ENS(seg_i32, ((size_t)n_seg * 3 + 2 * nc) * 4);
-                ENS(colhist, (size_t)fp * S * 8); ENS(colG, (size_t)fp * 8); ENS(colkg, (size_t)fp * 4); ENS(clip_flag, (size_t)nc * 4);
-                ENS(flag_order, (size_t)nc * 4);
-                tube_cap = (int)std::max<int64_t>(4096, fp / 128);
-                ENS(tube_buf, (size_t)tube_cap * viterbi_tube_record_ints() * 4); ENS(tube_at, (size_t)fp * 4); ENS(tube_count, 8);
-            }
-        }
-        if (stages & AEGIS_STAGE_MEL) { ENS(melpow, fp * t.n_mels * 4); ENS(clipmax, nc * 4); ENS(rake_raw, fp); }
-#undef ENS
-        HIPCHK(h, hipMemcpyAsync(w.sample_off.p, m.sample_off.data(), nc * 8, hipMemcpyHostToDevice, fa));
-        HIPCHK(h, hipMemcpyAsync(w.sample_len.p, m.sample_len.data(), nc * 8, hipMemcpyHostToDevice, fa));
-        HIPCHK(h, hipMemcpyAsync(w.out_off.p, m.out_off.data(), nc * 8, hipMemcpyHostToDevice, fa));
-        HIPCHK(h, hipMemcpyAsync(w.frame_off.p, m.frame_off.data(), (nc + 1) * 8, hipMemcpyHostToDevice, fa));
-        HIPCHK(h, hipMemcpyAsync(w.chunk_off.p, m.chunk_off.data(), (nc + 1) * 8, hipMemcpyHostToDevice, fa));
-        HIPCHK(h, hipMemcpyAsync(w.order.p, m.order.data(), nc * 4, hipMemcpyHostToDevice, fa));
-        HIPCHK(h, hipMemcpyAsync(w.sel_off.p, m.sel_off.data(), (size_t)nk * (nc + 1) * 8, hipMemcpyHostToDevice, fa));
-        if (proportional) HIPCHK(h, hipMemcpyAsync(w.clip_tb.p, m.clip_tb.data(), (size_t)(nk + 1) * nc * 8, hipMemcpyHostToDevice, fa));
-        if (stages & AEGIS_STAGE_MEL) HIPCHK(h, hipMemsetAsync(w.clipmax.p, 0, nc * 4, fa));
-        if (tsplit) {
-            HIPCHK(h, hipMemcpyAsync(w.seg64.p, m.seg64.data(), m.seg64.size() * 8, hipMemcpyHostToDevice, fa));
-            HIPCHK(h, hipMemcpyAsync(w.seg32.p, m.seg32.data(), m.seg32.size() * 4, hipMemcpyHostToDevice, fa));
-            HIPCHK(h, hipMemsetAsync(w.seg_i32.p, 0, ((size_t)n_seg * 3 + 2 * nc) * 4, fa));       // seg_lock = 0 for the segments without a lock-on run
-            HIPCHK(h, hipMemsetAsync(w.clip_flag.p, 0, (size_t)nc * 4, fa));
-            HIPCHK(h, hipMemsetAsync(w.tube_at.p, 0, (size_t)fp * 4, fa));
-            HIPCHK(h, hipMemsetAsync(w.tube_count.p, 0, 8, fa));       // tubes recorded, rounds of second speculation that had work
-        }
-        PassParams p = base_params(t);
-        // Balanced passes launch the Viterbi ONCE: the kernel waits for a flag per time chunk, stored behind the chunk's
-        // observation kernel, instead of being launched per chunk (40 launches of 45 us each at 64 clips x 180 s, and the
-        // kernel's prologue each time).  It needs the frame stage to run beside it, which the CU partition guarantees.
-        const bool persistent = (may_persist || (hybrid && !feed && h->persistent && sync)) && ss != nullptr && nk > 1;
-        if (persistent) {
-            if (!h->abort_flag.p) {
-                if ((rc = ensure(h, h->abort_flag, 4)) != AEGIS_OK) return rc;
-                HIPCHK(h, hipMemsetAsync(h->abort_flag.p, 0, 4, fa));
-            }
-            m.chunk_lo.assign(cb.begin(), cb.end() - 1);
-            HIPCHK(h, hipMemcpyAsync(w.chunk_lo.p, m.chunk_lo.data(), (size_t)nk * 8, hipMemcpyHostToDevice, fa));
-            HIPCHK(h, hipMemsetAsync(w.chunk_flag.p, 0, (size_t)nk * 4, fa));       // generations start at 1
-        }
-        if (use_fb || persistent) {      // the metadata precedes the second frame stream's kernels and the Viterbi
+        // ---- workspace ----------------------------------------------------------------------------------------------
+        if ((rc = ensure_pass(h, w, m, stages)) != AEGIS_OK) return rc;
+        if ((rc = upload_pass(h, w, m, stages, fa)) != AEGIS_OK) return rc;
+        if (m.use_fb || m.persistent) {      // the metadata precedes the second frame stream's kernels and the Viterbi
             HIPCHK(h, hipEventRecord(h->sync_events[EV_META], fa));
-            if (use_fb) HIPCHK(h, hipStreamWaitEvent(fb, h->sync_events[EV_META], 0));
-            if (persistent) HIPCHK(h, hipStreamWaitEvent(sv, h->sync_events[EV_META], 0));
+            if (m.use_fb) HIPCHK(h, hipStreamWaitEvent(fb, h->sync_events[EV_META], 0));
+            if (m.persistent) HIPCHK(h, hipStreamWaitEvent(sv, h->sync_events[EV_META], 0));
         }
-
-        p.stages = stages;
-        p.pcm = d_pcm;
-        p.sample_off = static_cast<const int64_t *>(w.sample_off.p);
-        p.sample_len = static_cast<const int64_t *>(w.sample_len.p);
-        p.frame_off = static_cast<const int64_t *>(w.frame_off.p);
-        p.out_off = static_cast<const int64_t *>(w.out_off.p);
-        p.order = static_cast<const int32_t *>(w.order.p);
-        p.n_clips = nc; p.n_frames = fp;
-        p.dfn = static_cast<double *>(w.dfn.p); p.lag_stride = h->lag_stride;
-        p.yin = (py && h->debug_stages) ? static_cast<double *>(w.yin.p) : nullptr; p.yin_stride = h->yin_stride;
-        p.cmnd_in_frame = cmnd_in_frame(h); p.troughs = troughs_in_frame(h);
-        p.logobs = static_cast<double *>(w.logobs.p); p.obs_stride = h->obs_stride;
-        p.logunv = static_cast<double *>(w.logunv.p);
-        p.obs_seg = static_cast<int32_t *>(w.obs_seg.p);
-        p.ptr = static_cast<uint16_t *>(w.ptr.p);
-        p.cmap = static_cast<uint16_t *>(w.cmap.p);
-        p.chunk_off = static_cast<int64_t *>(w.chunk_off.p);
-        p.bnd = static_cast<int32_t *>(w.bnd.p);
-        p.states = static_cast<int32_t *>(w.states.p);
-        p.melpow = static_cast<float *>(w.melpow.p);
-        p.clipmax = static_cast<uint32_t *>(w.clipmax.p);
-        p.rake_raw = static_cast<uint8_t *>(w.rake_raw.p);
-        p.vstate = static_cast<double *>(w.vstate.p);
-        p.vstats = static_cast<unsigned long long *>(h->vstats.p);
-        p.out_f0 = py ? dout->f0 : nullptr;
-        p.out_voiced = py ? dout->voiced_flag : nullptr;
-        p.out_vprob = py ? dout->voiced_prob : nullptr;
-        p.out_bin = py ? dout->pitch_bin : nullptr;
-        p.out_rms = (stages & AEGIS_STAGE_RMS) ? dout->rms : nullptr;
-        p.out_rake = (stages & AEGIS_STAGE_RAKE) ? dout->rake_mask : nullptr;
-        p.out_sdb = (stages & AEGIS_STAGE_MEL) ? dout->S_dB : nullptr;
-        p.out_colmean = (stages & AEGIS_STAGE_MEL) ? dout->sdb_col_means : nullptr;
-        p.out_total = total_frames;
-        p.rake_ratio = rake_sensitivity;
-        p.rake_min_frames = rake_min; p.rake_max_frames = rake_max;
-        if (opts & AEGIS_OPT_F0_ZERO) p.f0_unvoiced = 0.0;
-        const int32_t *d_seg_order = nullptr, *d_lock_order = nullptr;
-        if (tsplit) {
-            const int64_t *g64 = static_cast<const int64_t *>(w.seg64.p);
-            const int32_t *g32 = static_cast<const int32_t *>(w.seg32.p);
-            p.seg_f0 = g64; p.seg_ch0 = g64 + n_seg;
-            p.vf_off = g64 + 2 * n_seg; p.vf_total = m.seg64.back();
-            p.seg_T = g32; p.seg_store = g32 + n_seg; p.seg_prev = g32 + 2 * n_seg; p.seg_clip = g32 + 3 * n_seg;
-            p.clip_seg0 = g32 + 4 * n_seg;
-            d_seg_order = g32 + 4 * n_seg + nc + 1; d_lock_order = d_seg_order + n_seg;
-            p.seg_col = static_cast<double *>(w.seg_col.p); p.seg_col2 = p.seg_col + (size_t)n_seg * S;
-            p.seg_map = static_cast<uint16_t *>(w.seg_map.p);
-            p.seg_kg = static_cast<int32_t *>(w.seg_i32.p); p.seg_lock = p.seg_kg + n_seg; p.seg_end = p.seg_kg + 2 * n_seg; p.clip_first = p.seg_kg + 3 * n_seg; p.clip_dirty = p.clip_first + nc;
-            p.colhist = static_cast<double *>(w.colhist.p); p.colG = static_cast<double *>(w.colG.p); p.colkg = static_cast<int32_t *>(w.colkg.p);
-            p.clip_flag = static_cast<uint32_t *>(w.clip_flag.p);
-            p.tube_buf = static_cast<int32_t *>(w.tube_buf.p); p.tube_cap = tube_cap; p.tube_count = static_cast<uint32_t *>(w.tube_count.p);
-            p.tube_at = static_cast<int32_t *>(w.tube_at.p);
-            p.n_seg = n_seg;
-        }
-
-        if (persistent) {
-            p.chunk_flag = static_cast<const uint32_t *>(w.chunk_flag.p);
-            p.chunk_lo = static_cast<const int64_t *>(w.chunk_lo.p);
-            p.n_chunks = nk;
-            if (hybrid) { int ks = 0; while (ks < nk && cb[ks] <= hyb_S) ++ks; p.n_chunks = ks; }      // (the launch ends at step S: chunks 0 .. ks - 1)
+        PassParams p = bind_pass(h, m, w, d_pcm, stages, opts, dout, rake_sensitivity);
+        const int32_t *d_seg_order = m.tsplit ? p.clip_seg0 + nc + 1 : nullptr, *d_lock_order = d_seg_order ? d_seg_order + m.n_seg : nullptr;
+        if (m.persistent) {
             p.chunk_gen = ++h->chunk_gen;
             if (p.chunk_gen == 0) p.chunk_gen = ++h->chunk_gen;
-            p.abort_flag = static_cast<uint32_t *>(h->abort_flag.p);
-            // bound of one chunk wait: a chunk's frame stage takes well under a millisecond per 10 k frames, so 0.1 s plus
-            // 0.1 s per million frames of the pass is two orders of magnitude of slack, and a pass that cannot overlap
-            // (kernels serialised) costs that much once instead of 1.5 s
-            p.wait_ticks = (uint64_t)std::min<int64_t>(150000000, 10000000 + fp * 10);
             h->persist_pending = true;
         }
+
+        // ---- time chunks: frame stage, then the Viterbi behind it -----------------------------------------------------
         for (int k = 0; k < nk; ++k) {
-            hipStream_t fs = ((two_fs || k < ramp_k) && (k & 1)) ? fb : fa;
+            hipStream_t fs = ((m.two_fs || k < m.ramp_k) && (k & 1)) ? fb : fa;
             p.sel_off = static_cast<const int64_t *>(w.sel_off.p) + (size_t)k * (nc + 1);
-            p.t_begin = chunk_lo(k);
+            p.t_begin = m.cb[k];
             p.n_sel = m.sel_off[(size_t)k * (nc + 1) + nc];
-            p.vt_begin = chunk_lo(k);
-            p.vt_end = (k == nk - 1) ? INT64_MAX : chunk_hi(k);
-            p.dense = dense ? 1 : 0;
-            p.clip_t0 = proportional ? static_cast<const int64_t *>(w.clip_tb.p) + (size_t)k * nc : nullptr;
-            p.clip_t1 = proportional ? static_cast<const int64_t *>(w.clip_tb.p) + (size_t)(k + 1) * nc : nullptr;
+            p.vt_begin = m.cb[k];
+            p.vt_end = (k == nk - 1) ? INT64_MAX : m.cb[k + 1];
+            p.clip_t0 = m.proportional ? static_cast<const int64_t *>(w.clip_tb.p) + (size_t)k * nc : nullptr;
+            p.clip_t1 = m.proportional ? static_cast<const int64_t *>(w.clip_tb.p) + (size_t)(k + 1) * nc : nullptr;
             if (feed) {      // frame t reads samples [t*hop - 1024, t*hop + 1024)
                 bool any = false;
                 for (int i = 0; i < nc; ++i) {
-                    const int ci = pc[i];
-                    const int64_t n = sample_offsets[ci + 1] - sample_offsets[ci];
-                    const int64_t fr = clip_hi(k, i);
-                    const int64_t need = (k == nk - 1) ? n : std::min(n, (fr - 1) * (int64_t)t.hop + t.n_fft / 2);
+                    const int ci = m.clips[i];
+                    const int64_t n = m.sample_len[i];
+                    const int64_t need = (k == nk - 1) ? n : std::min(n, (m.clip_hi(k, i) - 1) * (int64_t)t.hop + t.n_fft / 2);
                     int64_t &done = feed->copied[ci];
                     if (need > done) {
-                        HIPCHK(h, hipMemcpyAsync(feed->dst + sample_offsets[ci] + done, feed->pcm[ci] + done,
+                        HIPCHK(h, hipMemcpyAsync(feed->dst + m.sample_off[i] + done, feed->pcm[ci] + done,
                                                  (size_t)(need - done) * 4, hipMemcpyHostToDevice, h->stream3));
                         done = need;
                         any = true;
@@ -1328,59 +930,54 @@ static int analyze_device_locked(aegis_handle *h, const float *d_pcm, const int6
                 }
             }
             begin_event(h, "frame", fs); launch_frame(p, h->dt, fs); end_event(h, fs);
-            if (py) {
-                begin_event(h, "pyin_obs", fs); launch_pyin_obs(p, h->dt, fs); end_event(h, fs);
-                if (persistent) {
-                    if (k != h->test_drop_signal)      // AEGIS_TEST_DROP_CHUNK_SIGNAL=k: the kernel's bounded wait is tested with it
-                        launch_chunk_signal(static_cast<uint32_t *>(w.chunk_flag.p) + k, p.chunk_gen, fs);
-                    if (k == 0) {        // the one launch, ordered behind chunk 0 (its first column reads frame 0)
-                        HIPCHK(h, hipEventRecord(h->sync_events[EV_CHUNK0], fs));
-                        HIPCHK(h, hipStreamWaitEvent(sv, h->sync_events[EV_CHUNK0], 0));
-                        PassParams pv = p;
-                        pv.vt_begin = 0; pv.vt_end = hybrid ? hyb_S + 1 : INT64_MAX;
-                        begin_event(h, "viterbi", sv);
-                        hipError_t ve = launch_viterbi(pv, h->dt, t.log_trans_band.data(), sv);
-                        end_event(h, sv);
-                        if (ve != hipSuccess) { h->err = std::string("viterbi launch: ") + hipGetErrorString(ve); return AEGIS_ERR_DEVICE; }
-                    }
-                    continue;
+            if (!py) continue;
+            begin_event(h, "pyin_obs", fs); launch_pyin_obs(p, h->dt, fs); end_event(h, fs);
+            if (m.persistent) {
+                if (k != h->test_drop_signal)      // AEGIS_TEST_DROP_CHUNK_SIGNAL=k: the kernel's bounded wait is tested with it
+                    launch_chunk_signal(static_cast<uint32_t *>(w.chunk_flag.p) + k, p.chunk_gen, fs);
+                if (k == 0) {        // the one launch, ordered behind chunk 0 (its first column reads frame 0)
+                    HIPCHK(h, hipEventRecord(h->sync_events[EV_CHUNK0], fs));
+                    HIPCHK(h, hipStreamWaitEvent(sv, h->sync_events[EV_CHUNK0], 0));
+                    PassParams pv = p;
+                    pv.vt_begin = 0; pv.vt_end = m.hybrid ? m.hyb_S + 1 : INT64_MAX;
+                    begin_event(h, "viterbi", sv);
+                    hipError_t ve = launch_viterbi(pv, h->dt, t.log_trans_band.data(), sv);
+                    end_event(h, sv);
+                    VCHK(ve);
                 }
-                if (tsplit && !hybrid && k < nk - 1) continue;      // the segments are launched once, behind the last chunk's observations
-                if (hybrid && chunk_lo(k) > hyb_S) continue;        // (hybrid: behind step S the segments take over, launched after the loop)
-                if (sv != fs) {
-                    HIPCHK(h, hipEventRecord(h->sync_events[EV_CHUNK0 + k], fs));
-                    HIPCHK(h, hipStreamWaitEvent(sv, h->sync_events[EV_CHUNK0 + k], 0));
-                }
-                begin_event(h, "viterbi", sv);
-                const bool split_now = tsplit && !hybrid;
-                if (split_now && split_auto) {
-                    for (auto &e : h->split_ev) if (!e) HIPCHK(h, hipEventCreate(&e));
-                    if (!h->call_split_started) { HIPCHK(h, hipEventRecord(h->split_ev[0], sv)); h->call_split_started = true; h->call_t_front = 0.75 * (double)fp * 43e-9; }
-                }
-                if (split_now) for (auto &e : h->fin_ev) if (!e) HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-                hipError_t ve = split_now ? launch_viterbi_split(p, h->dt, t.log_trans_band.data(), d_seg_order, n_seg, d_lock_order, n_lock, sv,
-                                                                 h->stream4 != sv ? h->stream4 : nullptr, h->fin_ev)
-                                          : launch_viterbi(p, h->dt, t.log_trans_band.data(), sv);
-                if (split_now && split_auto) HIPCHK(h, hipEventRecord(h->split_ev[1], sv));
-                end_event(h, sv);
-                if (ve != hipSuccess) { h->err = std::string("viterbi launch: ") + hipGetErrorString(ve); return AEGIS_ERR_DEVICE; }
-                if (split_now) {
-                    h->split_checks.push_back({pass_index & 1, p, nc, split_auto, std::max((double)maxF * (t.half_width == 25 ? 3.1e-6 : 7.3e-6), (double)fp * 43e-9),
-                                               0.75 * (double)fp * 43e-9});
-                    ++h->split_stats[0]; h->split_stats[1] += n_seg;
-                }
+                continue;
             }
+            if (m.tsplit && !m.hybrid && k < nk - 1) continue;      // the segments are launched once, behind the last chunk's observations
+            if (m.hybrid && m.cb[k] > m.hyb_S) continue;            // (hybrid: behind step S the segments take over, launched after the loop)
+            if (sv != fs) {
+                HIPCHK(h, hipEventRecord(h->sync_events[EV_CHUNK0 + k], fs));
+                HIPCHK(h, hipStreamWaitEvent(sv, h->sync_events[EV_CHUNK0 + k], 0));
+            }
+            begin_event(h, "viterbi", sv);
+            const bool split_now = m.tsplit && !m.hybrid;
+            if (split_now && m.split_auto) {
+                for (auto &e : h->split_ev) if (!e) HIPCHK(h, hipEventCreate(&e));
+                if (!split_started) { HIPCHK(h, hipEventRecord(h->split_ev[0], sv)); split_started = true; }
+            }
+            if (split_now) for (auto &e : h->fin_ev) if (!e) HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+            hipError_t ve = split_now ? launch_viterbi_split(p, h->dt, t.log_trans_band.data(), d_seg_order, m.n_seg, d_lock_order, m.n_lock, sv,
+                                                             h->stream4 != sv ? h->stream4 : nullptr, h->fin_ev)
+                                      : launch_viterbi(p, h->dt, t.log_trans_band.data(), sv);
+            if (split_now && m.split_auto) HIPCHK(h, hipEventRecord(h->split_ev[1], sv));
+            end_event(h, sv);
+            VCHK(ve);
+            if (split_now) { h->split_checks.push_back({pi, p}); ++h->split_stats[0]; h->split_stats[1] += m.n_seg; }
         }
-        if (use_fb) {                    // the dB / rake finalisation needs every chunk's mel rows and clip maxima
+        if (m.use_fb) {                    // the dB / rake finalisation needs every chunk's mel rows and clip maxima
             HIPCHK(h, hipEventRecord(h->sync_events[EV_FB], fb));
             HIPCHK(h, hipStreamWaitEvent(fa, h->sync_events[EV_FB], 0));
         }
-        if (hybrid) {
+        if (m.hybrid) {
             // the segments behind step S: after the last chunk's observations (fa; fb has joined it above) and the sequential
             // kernel's last launch (sv), on the unmasked stream
             for (auto &e : h->hyb_ev) if (!e) HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
             PassParams ph = p;
-            ph.split_hybrid = 1; ph.hybrid_step = (int32_t)hyb_S;
+            ph.split_hybrid = 1; ph.hybrid_step = (int32_t)m.hyb_S;
             ph.vt_begin = 0; ph.vt_end = INT64_MAX;
             // the speculative runs need the observations only: they start behind the frame stage, on the compute units it has
             // left, while the sequential kernel walks its last chunks; lock-on runs and everything after wait for both
@@ -1388,8 +985,7 @@ static int analyze_device_locked(aegis_handle *h, const float *d_pcm, const int6
                 HIPCHK(h, hipEventRecord(h->hyb_ev[0], fa));
                 HIPCHK(h, hipStreamWaitEvent(sa, h->hyb_ev[0], 0));
             }
-            hipError_t vs = launch_viterbi_split_spec(ph, h->dt, t.log_trans_band.data(), d_seg_order, n_lock, sa);
-            if (vs != hipSuccess) { h->err = std::string("viterbi launch: ") + hipGetErrorString(vs); return AEGIS_ERR_DEVICE; }
+            VCHK(launch_viterbi_split_spec(ph, h->dt, t.log_trans_band.data(), d_seg_order, m.n_lock, sa));
             HIPCHK(h, hipEventRecord(h->hyb_ev[2], sa));
             if (sd != sv) {
                 HIPCHK(h, hipEventRecord(h->hyb_ev[1], sv));
@@ -1397,29 +993,20 @@ static int analyze_device_locked(aegis_handle *h, const float *d_pcm, const int6
             }
             HIPCHK(h, hipStreamWaitEvent(sd, h->hyb_ev[2], 0));
             begin_event(h, "viterbi", sd);
-            if (split_auto) {
+            if (m.split_auto) {
                 for (auto &e : h->split_ev) if (!e) HIPCHK(h, hipEventCreate(&e));
-                if (!h->call_split_started) {
-                    HIPCHK(h, hipEventRecord(h->split_ev[0], sd)); h->call_split_started = true;
-                    // what precedes the events: the frame stage on 192 CUs / beside 65 .. 255 Viterbi workgroups; and for a pass
-                    // planned in the hybrid form only, the sequential estimate that rule used (frame stage + the longest clip's rest)
-                    h->call_t_front = hyb_part ? (double)fp * 43e-9 : 0.8 * (double)fp * 43e-9;
-                    if (want_hybrid) {
-                        const double step = t.half_width == 25 ? 3.1e-6 : 7.3e-6;
-                        h->call_t_seq = std::max(h->call_t_seq, h->call_t_front + std::max(0.0, (double)maxF - h->call_t_front / (1.7 * step)) * step);
-                    }
-                }
+                if (!split_started) { HIPCHK(h, hipEventRecord(h->split_ev[0], sd)); split_started = true; }
             }
             for (auto &e : h->fin_ev) if (!e) HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            hipError_t ve = launch_viterbi_split(ph, h->dt, t.log_trans_band.data(), d_seg_order, 0, d_lock_order, n_lock, sd, h->stream4, h->fin_ev);
-            if (split_auto) HIPCHK(h, hipEventRecord(h->split_ev[1], sd));
+            hipError_t ve = launch_viterbi_split(ph, h->dt, t.log_trans_band.data(), d_seg_order, 0, d_lock_order, m.n_lock, sd, h->stream4, h->fin_ev);
+            if (m.split_auto) HIPCHK(h, hipEventRecord(h->split_ev[1], sd));
             end_event(h, sd);
-            if (ve != hipSuccess) { h->err = std::string("viterbi launch: ") + hipGetErrorString(ve); return AEGIS_ERR_DEVICE; }
-            h->split_checks.push_back({pass_index & 1, ph, nc, split_auto, std::max((double)maxF * (t.half_width == 25 ? 3.1e-6 : 7.3e-6), (double)fp * 43e-9),
-                                       (double)fp * 43e-9});
-            ++h->split_stats[0]; h->split_stats[1] += n_seg;
+            VCHK(ve);
+            h->split_checks.push_back({pi, ph});
+            ++h->split_stats[0]; h->split_stats[1] += m.n_seg;
         }
-        hipStream_t se = hybrid ? sd : sv;       // the stream the pass ends on
+        // ---- finalize ---------------------------------------------------------------------------------------------------
+        hipStream_t se = m.hybrid ? sd : sv;       // the stream the pass ends on
         begin_event(h, "finalize", fa); launch_finalize_mel(p, h->dt, fa); end_event(h, fa);
         if (py) { begin_event(h, "finalize", se); launch_decode(p, h->dt, se); end_event(h, se); }
         // pass done = its last kernels on the frame stream and on the Viterbi stream
@@ -1427,21 +1014,11 @@ static int analyze_device_locked(aegis_handle *h, const float *d_pcm, const int6
             HIPCHK(h, hipEventRecord(h->sync_events[EV_FA], fa));
             HIPCHK(h, hipStreamWaitEvent(se, h->sync_events[EV_FA], 0));
         }
-        HIPCHK(h, hipEventRecord(h->sync_events[EV_DONE0 + (pass_index & 1)], se));
-        done_recorded[pass_index & 1] = true;
+        HIPCHK(h, hipEventRecord(h->sync_events[EV_DONE0 + (pi & 1)], se));
+        done_recorded[pi & 1] = true;
         HIPCHK(h, hipGetLastError());
-        h->last_frames = fp;
-        h->last_split_segments = (pass_index == 0 ? 0 : h->last_split_segments) + (tsplit ? n_seg : 0);      // of the call: all its passes
-        h->last_pass_segments = tsplit ? n_seg : 0;
-        h->last_chunks = nk; h->last_dense = dense ? 1 : 0; h->last_proportional = proportional ? 1 : 0;
-        h->last_balanced = balanced ? 1 : 0; h->last_persistent = persistent ? 1 : 0;
-        h->last_hybrid_step = hyb_S;
-        h->last_work = pass_index & 1;
-        first = last;
-        ++pass_index;
     }
-    h->last_passes = pass_index;
-    // the caller's stream continues after everything enqueued above
+    // ---- join: the caller's stream continues after everything enqueued above --------------------------------------------
     for (int q = 0; q < 2; ++q)
         if (done_recorded[q]) HIPCHK(h, hipStreamWaitEvent(s, h->sync_events[EV_DONE0 + q], 0));
     if (opts & AEGIS_OPT_CHECK_FINITE) {       // behind the last sample copy of a host feed: every sample is on the device by now
@@ -1453,12 +1030,15 @@ static int analyze_device_locked(aegis_handle *h, const float *d_pcm, const int6
     }
     if (!h->split_checks.empty()) {         // (sync != 0: time-split passes are planned for blocking calls only)
         HIPCHK(h, hipStreamSynchronize(s));
-        int rc = split_check(h, t, s);
-        if (rc != AEGIS_OK) return rc;
+        for (const auto &sc : h->split_checks) {
+            const int rc = split_check(h, sc, s);
+            if (rc != AEGIS_OK) return rc;
+        }
+        h->split_checks.clear();
     }
     if (sync == 1) {
         HIPCHK(h, hipStreamSynchronize(s));
-        h->metas.clear();
+        h->plan_in_flight = false;
         if (h->profiling) collect_events(h);
         int rc = persistent_check(h);
         if (rc != AEGIS_OK) return rc;
@@ -1466,6 +1046,7 @@ static int analyze_device_locked(aegis_handle *h, const float *d_pcm, const int6
     }
     return AEGIS_OK;
 }
+#undef VCHK
 
 int aegis_analyze_batch(aegis_handle *h, const float *const *pcm, const int64_t *n_samples, int32_t n_clips,
                         double rake_sensitivity, uint32_t stages, aegis_outputs *out) {
@@ -1489,7 +1070,7 @@ int aegis_analyze_batch(aegis_handle *h, const float *const *pcm, const int64_t 
     if ((rc = ensure(h, h->io_pcm, (size_t)std::max<int64_t>(off[n_clips], 1) * 4)) != AEGIS_OK) return rc;
     hipStream_t s = h->stream;
     // the previous call's kernels may still read io_pcm only if it returned without a sync -- it never does
-    if (!h->persistent && h->persistent_wanted && h->persist_cooldown > 0 && --h->persist_cooldown == 0)
+    if (!h->persistent && h->knobs.persistent_wanted && h->persist_cooldown > 0 && --h->persist_cooldown == 0)
         h->persistent = true;                 // as in aegis_analyze_batch_device: a give-up is not for good
     aegis_outputs d{};
     const int nm = h->tab.n_mels;
@@ -1533,7 +1114,7 @@ int aegis_analyze_batch(aegis_handle *h, const float *const *pcm, const int64_t 
     if (d.rake_mask) HIPCHK(h, hipMemcpyAsync(out->rake_mask, d.rake_mask, F, hipMemcpyDeviceToHost, s));
     if (d.S_dB) HIPCHK(h, hipMemcpyAsync(out->S_dB, d.S_dB, (size_t)F * nm * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipStreamSynchronize(s));
-    h->metas.clear();
+    h->plan_in_flight = false;
     if ((rc = persistent_check(h)) != AEGIS_OK) return rc;
     if (h->profiling) collect_events(h);
     return finite_result(h, stages, off.data(), n_clips);
@@ -2293,9 +1874,10 @@ int64_t aegis_get_param(const aegis_handle *h, const char *name) {
     if (n == "lag_stride") return h->lag_stride;
     if (n == "yin_stride") return h->yin_stride;
     if (n == "obs_stride") return h->obs_stride;
-    if (n == "last_frames") return h->last_frames;
-    if (n == "last_passes") return h->last_passes;
-    if (n == "last_split_segments") return h->last_split_segments;
+    const PassPlan *lp = last_pass(h);      // the last call's plan (its last pass; the split segments of all its passes)
+    if (n == "last_frames") return lp ? lp->fp : 0;
+    if (n == "last_passes") return (int64_t)h->plan.passes.size();
+    if (n == "last_split_segments") { int64_t v = 0; for (const PassPlan &q : h->plan.passes) v += q.tsplit ? q.n_seg : 0; return v; }
     if (n == "split_passes") return h->split_stats[0];
     if (n == "split_segments") return h->split_stats[1];
     if (n == "split_flagged_clips") return h->split_stats[2];
@@ -2303,12 +1885,12 @@ int64_t aegis_get_param(const aegis_handle *h, const char *name) {
     if (n == "split_rounds") return h->last_carried_steps;
     if (n == "split_viterbi_us") return (int64_t)(h->last_split_viterbi_ms * 1e3);
     if (n == "split_cooldown") return h->split_cooldown;
-    if (n == "last_chunks") return h->last_chunks;
-    if (n == "last_dense") return h->last_dense;
-    if (n == "last_proportional") return h->last_proportional;
-    if (n == "last_balanced") return h->last_balanced;
-    if (n == "last_hybrid_step") return h->last_hybrid_step;
-    if (n == "last_persistent") return h->last_persistent;
+    if (n == "last_chunks") return lp ? lp->nk() : 0;
+    if (n == "last_dense") return lp ? lp->dense : 0;
+    if (n == "last_proportional") return lp ? lp->proportional : 0;
+    if (n == "last_balanced") return lp ? lp->balanced : 0;
+    if (n == "last_hybrid_step") return lp ? lp->hyb_S : 0;
+    if (n == "last_persistent") return lp ? lp->persistent : 0;
     if (n == "pyin_init") return t.pyin_init;
     return AEGIS_ERR_INVALID;
     } catch (...) { return abi_fail(const_cast<aegis_handle *>(h)); }
@@ -2341,6 +1923,45 @@ int64_t aegis_get_table(const aegis_handle *h, const char *name, void *dst, int6
     } catch (...) { return abi_fail(const_cast<aegis_handle *>(h)); }
 }
 
+int64_t aegis_debug_plan(aegis_handle *h, const int64_t *n_samples, int32_t n_clips, int32_t entry, int32_t sync,
+                         int32_t n_cus, int64_t *dst, int64_t cap) {
+    try {
+    if (!h || n_clips < 0 || (n_clips > 0 && !n_samples) || cap < 0 || (cap > 0 && !dst)) return AEGIS_ERR_INVALID;
+    std::lock_guard<std::mutex> lock(h->mu);
+    std::vector<int64_t> off((size_t)n_clips + 1, 0);
+    for (int i = 0; i < n_clips; ++i) {
+        if (n_samples[i] < 0 || 1 + n_samples[i] / h->tab.hop > h->max_frames_per_pass) { h->err = "bad clip " + std::to_string(i); return AEGIS_ERR_INVALID; }
+        off[i + 1] = off[i] + n_samples[i];
+    }
+    const int kind = entry & 3;
+    const PlanKnobs &kn = h->knobs;
+    PlanInput in = plan_input(h, off.data(), n_clips, AEGIS_STAGE_ALL, kind == AEGIS_PLAN_HOST_FED, kind == AEGIS_PLAN_CALLER_STREAM,
+                              sync, n_cus, [&kn, n_cus](int n) { return masked_streams_fit(kn, n_cus, n); });
+    if (entry & AEGIS_PLAN_COOLING) in.cooling = split_allowed(in) && kn.split_seglen < 0;
+    if (entry & AEGIS_PLAN_NO_PERSIST) in.persistent = false;
+    const CallPlan c = plan_call(in);
+    std::vector<int64_t> v{(int64_t)c.passes.size()};
+    for (const PassPlan &m : c.passes) {
+        const int64_t flags = m.tsplit * AEGIS_PLAN_F_SPLIT | m.split_auto * AEGIS_PLAN_F_SPLIT_AUTO | m.want_hybrid * AEGIS_PLAN_F_WANT_HYBRID |
+                              m.hybrid * AEGIS_PLAN_F_HYBRID | m.hyb_part * AEGIS_PLAN_F_HYBRID_PART | m.balanced * AEGIS_PLAN_F_BALANCED |
+                              m.may_persist * AEGIS_PLAN_F_MAY_PERSIST | m.persistent * AEGIS_PLAN_F_PERSISTENT | m.dense * AEGIS_PLAN_F_DENSE |
+                              m.proportional * AEGIS_PLAN_F_PROPORTIONAL | m.two_fs * AEGIS_PLAN_F_TWO_FRAME_STREAMS | m.use_fb * AEGIS_PLAN_F_FRAME_B;
+        const int64_t lanes = (int64_t)m.fa | (int64_t)m.fb << 4 | (int64_t)m.sv << 8 | (int64_t)m.sd << 12 | (int64_t)m.sa << 16;
+        uint64_t hash = 1469598103934665603ull;      // FNV-1a over the tables' bytes, each led by its length
+        auto mix = [&hash](const void *p, size_t n) {
+            for (size_t i = 0; i < n; ++i) { hash ^= static_cast<const unsigned char *>(p)[i]; hash *= 1099511628211ull; }
+        };
+        auto table = [&mix](const auto &t) { const uint64_t n = t.size(); mix(&n, 8); mix(t.data(), n * sizeof(t[0])); };
+        table(m.seg32); table(m.seg64); table(m.sel_off); table(m.clip_tb);
+        for (int64_t x : {(int64_t)m.nc(), m.fp, m.maxF, flags, m.seglen, m.hyb_S, (int64_t)m.n_seg, (int64_t)m.n_lock, (int64_t)m.nk(),
+                          (int64_t)m.ramp_k, lanes, (int64_t)hash}) v.push_back(x);
+        v.insert(v.end(), m.cb.begin(), m.cb.end());
+    }
+    if (cap > 0) std::memcpy(dst, v.data(), (size_t)std::min<int64_t>(cap, (int64_t)v.size()) * 8);
+    return (int64_t)v.size();
+    } catch (...) { return abi_fail(h); }
+}
+
 int64_t aegis_debug_fetch(aegis_handle *h, const char *name, void *dst, int64_t cap) {
     try {
     if (!h || !name) return AEGIS_ERR_INVALID;
@@ -2351,11 +1972,13 @@ int64_t aegis_debug_fetch(aegis_handle *h, const char *name, void *dst, int64_t 
     if (n == "throw_runtime_error") throw std::runtime_error("test hook: runtime_error");
     if (n == "throw_int") throw 42;
     if (n == "fail_allocs") { h->fail_allocs = (int)std::max<int64_t>(0, cap); return 0; }      // (count in `cap`, nothing copied)
-    const int64_t F = h->last_frames;
+    const PassPlan *lp = last_pass(h);
+    const int64_t F = lp ? lp->fp : 0;
+    const int last_pass_segments = lp && lp->tsplit ? lp->n_seg : 0;
     const void *src = nullptr;
     int64_t count = 0;
     size_t esz = 8;
-    const aegis_handle::Work &lw = h->work[h->last_work];      // rows in the order the last pass took its clips: longest first
+    const aegis_handle::Work &lw = h->work[last_work(h)];      // rows in the order the last pass took its clips: longest first
     if (n == "dfn") { src = lw.dfn.p; count = F * h->lag_stride; }
     else if (n == "yin") { src = lw.yin.p; count = F * h->yin_stride; }
     else if (n == "logobs") {            // dense rows: the segments the kernel did not store (obs_seg) are all log(tiny)
@@ -2419,13 +2042,12 @@ int64_t aegis_debug_fetch(aegis_handle *h, const char *name, void *dst, int64_t 
         return 24;
     }
     else if (n == "seg_lock") {           // lock-on run lengths of the last time-split pass, one per segment (0: first of its clip, -1: never met)
-        if (h->device < 0 || h->last_pass_segments <= 0) return 0;
-        const int ns = h->last_pass_segments;
+        if (h->device < 0 || last_pass_segments <= 0) return 0;
+        const int ns = last_pass_segments;
         if (dst && cap > 0) {
             std::vector<int32_t> v((size_t)ns), st((size_t)ns);
             HIPCHK(h, hipSetDevice(h->device));
             HIPCHK(h, hipDeviceSynchronize());
-            const aegis_handle::Work &lw = h->work[h->last_work];
             HIPCHK(h, hipMemcpy(v.data(), static_cast<const int32_t *>(lw.seg_i32.p) + ns, (size_t)ns * 4, hipMemcpyDeviceToHost));
             HIPCHK(h, hipMemcpy(st.data(), static_cast<const int32_t *>(lw.seg32.p) + ns, (size_t)ns * 4, hipMemcpyDeviceToHost));
             int64_t *o = static_cast<int64_t *>(dst);

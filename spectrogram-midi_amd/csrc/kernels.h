@@ -4,6 +4,8 @@
 
 #include <cstdint>
 
+#include "plan.h"      // kViterbiChunk
+
 namespace aegis {
 
 // Constant tables resident in HBM (built by tables.cpp, uploaded once per handle).
@@ -150,8 +152,6 @@ struct PassParams {
     int32_t rake_min_frames, rake_max_frames;
     double f0_unvoiced;                  // what an unvoiced frame's f0 reads: NaN (librosa.pyin fill_na) or 0.0 (np.nan_to_num)
 };
-
-constexpr int kViterbiChunk = 16;   // steps per composed back-pointer map
 
 void launch_frame(const PassParams &p, const DevTables &t, hipStream_t s);
 bool frame_cmnd_supported(int max_period);

@@ -1,0 +1,111 @@
+// Pass planner of the batch entries (aegis_analyze_batch / _device): which clips share a pass, how each pass is cut into
+// time chunks or time-split segments, which kernels run and on which stream.  Plain C++: no HIP, testable on the CPU
+// (aegis_debug_plan, tests/test_plan.py).  aegis_api.hip enqueues what it plans.
+#pragma once
+#include <algorithm>
+#include <cstdint>
+#include <functional>
+#include <vector>
+
+namespace aegis {
+
+constexpr int kViterbiChunk = 16;   // steps per composed back-pointer map
+
+// Scheduling knobs of a handle: defaults, and what the environment overrides when the handle is created (out-of-range
+// values are ignored).
+struct PlanKnobs {
+    int64_t time_chunk = 2048;          // AEGIS_TIME_CHUNK: Viterbi steps per pipeline chunk (>= 64, multiple of 16)
+    int64_t feed_chunk = 1024;          // AEGIS_FEED_CHUNK: chunk size of balanced passes fed from host memory
+    int64_t balanced_chunk = 384;       // AEGIS_BALANCED_CHUNK: chunk size of balanced passes (0 = never balanced)
+    int balanced_min = 16;              // AEGIS_BALANCED_MIN: fewest clips of a balanced pass
+    int dense_mode = -1;                // AEGIS_DENSE: -1 (unset) = passes of >= 256 clips, 0 = never, 1 = every unbalanced pass
+    bool proportional_chunks = true;    // AEGIS_PROPORTIONAL_CHUNKS=0: one time axis for the clips of a ragged pass
+    int split_limit = 64;               // AEGIS_CU_SPLIT: passes of up to this many clips run partitioned (0 disables)
+    bool persistent_wanted = true;      // AEGIS_VITERBI_PERSISTENT: one Viterbi launch per balanced pass (0: one per chunk)
+    // time-split passes (viterbi.hip): AEGIS_TIME_SPLIT=<steps per segment> forces them, 0 turns them off, unset = when a
+    // pass is bound by the recurrence of its longest clip
+    int64_t split_seglen = -1;          // -1: automatic
+    // AEGIS_SPLIT_SEGMENT_ROUNDS: segments per compute unit the automatic rule plans for (whole rounds of workgroups).  The
+    // speculative runs take the same time in one round of long segments or two rounds of segments half as long (+ the second
+    // warm-up), but a lock-on run that never meets its speculative run costs a whole segment and a round of second
+    // speculation another: with two rounds of segments six of the folder's eight rank shards run in 77-79 ms instead of
+    // 91-99 (and the other two in 68-71 instead of 66); with three the slowest shard takes 76.7 ms instead of 79.5, with
+    // four 77.6.
+    int split_rounds_of_segments = 3;
+    int split_warmup = 256;             // AEGIS_SPLIT_WARMUP: frames a speculative run starts ahead of its boundary (128: lock-on after a median of 104 steps and one run in twenty never; 256: at the first check)
+    // Hybrid split passes (AEGIS_SPLIT_HYBRID: unset = automatic split passes, 1 = forced ones as well, 0 = never).  A split
+    // pass ran its whole frame stage in front of its segments (they need every frame's observations) with the Viterbi's
+    // compute units idle; a hybrid pass runs the balanced pipeline instead -- frame stage
+    // on 192 CUs, the SEQUENTIAL kernel chunk by chunk on 64 -- until the frame stage is through, and cuts only what the
+    // sequential kernel has not reached by then (steps behind hybrid step S of every clip) into speculative segments: the
+    // first segment of every clip is the sequential run itself, as before, only now thousands of steps long and free.
+    // AEGIS_HYBRID_PCT: S as a percentage of (frame stage time on 192 CUs) / (time per step); AEGIS_HYBRID_ROUNDS: rounds
+    // of speculative segments behind S; AEGIS_HYBRID_MIN_SEG: their shortest length.
+    int split_hybrid = -1, hybrid_pct = 100, hybrid_rounds = 3, hybrid_min_seg = 768;
+
+    void read_env();
+};
+
+// The streams a pass's kernels go on.  main: the caller's stream, or the handle's own; frame2 / viterbi2: the handle's
+// second frame-stage and Viterbi streams; masked_*: the CU-masked set for the pass's clip count (split_streams).
+enum class Lane : uint8_t { none, main, frame2, viterbi2, masked_frame_a, masked_frame_b, masked_viterbi };
+
+struct PlanInput {
+    std::vector<int64_t> sample_offsets;    // [n_clips + 1], the caller's clip order
+    int64_t max_frames_per_pass = 0;
+    int n_cus = 0, hop = 512, half_width = 25;
+    bool py = true;                         // the pYIN stage runs
+    bool feed = false;                      // host-fed entry (aegis_analyze_batch)
+    bool caller_stream = false;             // the caller gave a stream
+    int sync = 1;
+    bool band_applies = false, split_applies = false;   // viterbi_band_applies / viterbi_split_applies
+    std::function<bool(int)> masked_streams;            // a CU-masked stream set exists for n clips
+    PlanKnobs knobs;
+    // adaptive state of the handle
+    bool cooling = false;                   // the split cool-down holds this call
+    bool persistent = true;                 // single Viterbi launches allowed (false for a while after a give-up)
+};
+
+struct PassPlan {
+    std::vector<int> clips;                 // indices into the caller's arrays, longest first
+    int64_t fp = 0, maxF = 0;               // frames of the pass, of its longest clip
+    bool tsplit = false, split_auto = false, want_hybrid = false, hybrid = false, hyb_part = false;
+    int64_t hyb_S = 0, seglen = 0;
+    int n_seg = 0, n_lock = 0, tube_cap = 0;
+    bool balanced = false, may_persist = false, persistent = false, dense = false, proportional = false;
+    std::vector<int64_t> cb;                // chunk boundaries: cb[k] .. cb[k + 1] is chunk k, cb.back() = maxF
+    bool two_fs = false, use_fb = false;
+    int ramp_k = 0;
+    Lane fa = Lane::none, fb = Lane::none, sv = Lane::none, sd = Lane::none, sa = Lane::none;
+    double t_seq = 0.0;                     // the pass's sequential estimate (split_redo_pays)
+    // host arrays uploaded to the workspace (kept alive until the stream has consumed them)
+    std::vector<int64_t> sample_off, sample_len, out_off, frame_off, chunk_off, sel_off, chunk_lo, clip_tb;
+    std::vector<int32_t> order;
+    std::vector<int64_t> seg64;             // time-split pass: seg_f0 | seg_ch0 | vf_off
+    std::vector<int32_t> seg32;             // seg_T | seg_store | seg_prev | seg_clip | clip_seg0 | seg_order | lock_order
+
+    int nc() const { return (int)clips.size(); }
+    int nk() const { return (int)cb.size() - 1; }
+    int64_t frames(int i) const { return frame_off[i + 1] - frame_off[i]; }
+    // first frame of chunk k of the pass's clip i, and one past its last
+    int64_t clip_lo(int k, int i) const { return proportional ? clip_tb[(size_t)k * nc() + i] : std::min(frames(i), cb[k]); }
+    int64_t clip_hi(int k, int i) const { return proportional ? clip_tb[(size_t)(k + 1) * nc() + i] : std::min(frames(i), cb[k + 1]); }
+};
+
+struct CallPlan {
+    std::vector<PassPlan> passes;
+    int64_t total_frames = 0;
+    // the clock check of an automatic split call (split_clock_pays): its sequential estimate and the frame stage in front
+    // of its first split pass's Viterbi kernels
+    double t_seq = 0.0, t_front = 0.0;
+};
+
+bool split_allowed(const PlanInput &in);              // time-split passes may be planned for this call at all
+bool masked_streams_fit(const PlanKnobs &k, int n_cus, int n_clips);   // split_streams' conditions on the pass
+CallPlan plan_call(const PlanInput &in);
+// after an automatic split call: did frame stage + measured Viterbi time come clearly below the sequential estimate?
+bool split_clock_pays(const CallPlan &c, double viterbi_ms);
+// after a split pass: is the sequential redo of its longest flagged clip (redo_frames) cheap next to the pass?
+bool split_redo_pays(const PassPlan &p, int64_t redo_frames, int half_width);
+
+}  // namespace aegis

@@ -944,6 +944,40 @@ def test_hybrid_split_pass_at_22050_hz(monkeypatch):
         np.testing.assert_array_equal(got[k], ref[k], err_msg=k)
 
 
+def test_split_verdict_read_before_its_workspace_is_reused(monkeypatch):
+    """Passes alternate between two workspaces, so a call of three or more passes reuses pass k's workspace for pass k + 2.
+    A time-split pass leaves its verdicts there (the clips flagged for the sequential redo): they are read, and the flagged
+    clips redone, before the pass two further on overwrites them.  Five forced split passes of 512-step segments (the
+    plan: tests/test_plan.py::test_split_passes_reuse_their_workspace); the two longest clips, alone in passes 0 and 1,
+    silent or silent for 16 s (no voiced note to lock on to: flagged).  Outputs equal to the sequential kernel's."""
+    sr = 44100
+    clips = [np.zeros(int(24.0 * sr), np.float32),
+             np.concatenate([signals.guitar_clip(3.0, seed=21), np.zeros(int(16.0 * sr), np.float32), signals.guitar_clip(3.0, seed=22)])]
+    clips += [signals.guitar_clip(s, seed=30 + i) for i, s in enumerate((11.0, 10.0, 9.0, 8.0, 7.0, 6.0, 5.0))]
+    assert [len(c) for c in clips] == [int(s * sr) for s in (24, 22, 11, 10, 9, 8, 7, 6, 5)]
+    monkeypatch.setenv("AEGIS_TIME_SPLIT", "0")
+    ref_h = _lib.Handle(max_frames_per_pass=2200)
+    ref = ref_h.analyze_batch(clips, stages=_lib.STAGE_PYIN)
+    ref_dev = _analyze_on_device(ref_h, clips)
+    assert ref_h.param("split_passes") == 0 and ref_h.param("last_passes") == 5
+    ref_h.close()
+    monkeypatch.setenv("AEGIS_TIME_SPLIT", "512")
+    monkeypatch.setenv("AEGIS_SPLIT_WARMUP", "64")
+    h = _lib.Handle(max_frames_per_pass=2200)
+    got = h.analyze_batch(clips, stages=_lib.STAGE_PYIN)
+    assert h.param("last_passes") == 5 and h.param("split_passes") == 5
+    print(f"{h.param('split_flagged_clips')} of {len(clips)} clips redone sequentially")
+    assert h.param("split_flagged_clips") >= 1
+    for i in range(len(clips)):
+        for k in ("f0", "voiced_flag", "voiced_prob"):
+            np.testing.assert_array_equal(got[i][k], ref[i][k], err_msg=f"clip {i} {k}")
+    dev = _analyze_on_device(h, clips)
+    assert h.param("split_passes") == 10
+    for k in ref_dev:
+        np.testing.assert_array_equal(dev[k], ref_dev[k], err_msg=k)
+    h.close()
+
+
 def test_out_of_memory_retry_halves_the_passes():
     """An analyze call whose workspace cannot be allocated (another handle or the caller took the memory the pass size was
     derived from) halves max_frames_per_pass -- down to 2^21 frames -- and plans its passes again instead of failing: the first
