@@ -33,6 +33,11 @@ class Config(C.Structure):
                 ("device", C.c_int32), ("pyin_init", C.c_int32), ("max_frames_per_pass", C.c_int64)]
 
 
+class PcmClip(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("n_frames", C.c_int64), ("format", C.c_int32), ("channels", C.c_int32),
+                ("sample_rate", C.c_int32), ("n_taps", C.c_int32), ("taps", C.c_void_p)]
+
+
 class StreamFrames(C.Structure):
     _fields_ = [("rms", C.c_void_p), ("voiced_prob", C.c_void_p), ("live_state", C.c_void_p)]
 
@@ -46,7 +51,8 @@ EXPORTS = ("aegis_abi_version", "aegis_create", "aegis_destroy", "aegis_last_err
            "aegis_analyze_batch", "aegis_analyze_batch_device", "aegis_get_table", "aegis_get_param",
            "aegis_debug_fetch", "aegis_set_profiling", "aegis_last_kernel_ms", "aegis_rake_patterns", "aegis_set_table", "aegis_last_kernel_launches", "aegis_trend", "aegis_ghost_rsi",
            "aegis_stream_open", "aegis_stream_push", "aegis_stream_close", "aegis_stream_free", "aegis_cqt", "aegis_cqt_device", "aegis_chroma_cqt",
-           "aegis_extract_events", "aegis_render_smf", "aegis_events_last_error", "aegis_debug_plan")
+           "aegis_extract_events", "aegis_render_smf", "aegis_events_last_error", "aegis_debug_plan",
+           "aegis_analyze_pcm", "aegis_pcm_samples_for", "aegis_resample_taps")
 
 _lib = None
 
@@ -83,6 +89,13 @@ def load():
     lib.aegis_analyze_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int32,
                                                C.c_double, C.c_uint32, C.POINTER(Outputs), C.c_void_p, C.c_int32]
     lib.aegis_analyze_batch_device.restype = C.c_int
+    lib.aegis_analyze_pcm.argtypes = [C.c_void_p, C.POINTER(PcmClip), C.c_int32, C.c_double, C.c_uint32, C.POINTER(Outputs),
+                                      C.c_void_p]
+    lib.aegis_analyze_pcm.restype = C.c_int
+    lib.aegis_pcm_samples_for.argtypes = [C.c_void_p, C.POINTER(PcmClip)]
+    lib.aegis_pcm_samples_for.restype = C.c_int64
+    lib.aegis_resample_taps.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_int64]
+    lib.aegis_resample_taps.restype = C.c_int64
     lib.aegis_rake_patterns.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.c_void_p]
     lib.aegis_rake_patterns.restype = C.c_int
     lib.aegis_trend.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
@@ -294,6 +307,13 @@ class Handle:
         ptrs = (C.c_void_p * n)(*[c.ctypes.data for c in clips])
         lens = (C.c_int64 * n)(*[len(c) for c in clips])
         frames = [1 + len(c) // self.hop for c in clips]
+        bufs, out, flags = self._outputs(frames, stages, want_sdb, check_finite, f0_zero, concatenated, want_col_means)
+        rc = self.lib.aegis_analyze_batch(self._h, ptrs, lens, n, float(rake_sensitivity), flags, C.byref(out))
+        self._check_analyze(rc, check_finite)
+        return self._split(bufs, frames, views, concatenated)
+
+    def _outputs(self, frames, stages, want_sdb, check_finite, f0_zero, concatenated, want_col_means):
+        """Host buffers of a batch of clips of frames[i] frames, the aegis_outputs that points at them, the flag word."""
         F = sum(frames)
         if stages & STAGE_RAKE:
             stages |= STAGE_MEL
@@ -316,12 +336,17 @@ class Handle:
         for k, v in bufs.items():
             setattr(out, k, v.ctypes.data)
         flags = int(stages) | (OPT_CHECK_FINITE if check_finite else 0) | (OPT_F0_ZERO if f0_zero else 0)
-        rc = self.lib.aegis_analyze_batch(self._h, ptrs, lens, n, float(rake_sensitivity), flags, C.byref(out))
+        return bufs, out, flags
+
+    def _check_analyze(self, rc, check_finite):
         if rc == ERR_INVALID and check_finite:
             msg = self.lib.aegis_last_error(self._h).decode()
             if msg.startswith("Audio buffer is not finite"):
                 raise ValueError(msg)                       # librosa.util.valid_audio's ParameterError
         self._check(rc)
+
+    def _split(self, bufs, frames, views, concatenated):
+        """The batch's buffers -> per-clip dicts (and the batch-level buffers and frame offsets when concatenated)."""
         for k in ("voiced_flag", "rake_mask"):              # 0 / 1 bytes: the same memory read as bool
             if k in bufs:
                 bufs[k] = bufs[k].view(bool)
@@ -341,6 +366,64 @@ class Handle:
         if concatenated:
             return res, bufs, np.concatenate([[0], np.cumsum(frames)]).astype(np.int64)
         return res
+
+    def pcm_clips(self, sources, builtin_taps=False):
+        """aegis_pcm_clip array for sources (audio_io.PcmSource: raw frames as a uint8 array, format, channels, rate);
+        scipy's own taps for every rate pair unless builtin_taps.  Returns (array, objects to keep alive)."""
+        from . import audio_io
+        arr = (PcmClip * max(len(sources), 1))()
+        keep, taps = [], {}
+        for i, src in enumerate(sources):
+            data = np.ascontiguousarray(src.data, dtype=np.uint8)
+            keep.append(data)
+            fb = audio_io.PCM_WIDTH[src.format] * src.channels
+            c = arr[i]
+            c.data, c.n_frames, c.format, c.channels, c.sample_rate = data.ctypes.data, len(data) // fb, src.format, src.channels, src.sample_rate
+            if src.sample_rate != self.sr and not builtin_taps:
+                if src.sample_rate not in taps:
+                    taps[src.sample_rate] = audio_io.resample_taps(src.sample_rate, self.sr)[2]
+                h = taps[src.sample_rate]
+                c.n_taps, c.taps = len(h), h.ctypes.data
+        keep.append(taps)
+        return arr, keep
+
+    def pcm_samples_for(self, source):
+        arr, keep = self.pcm_clips([source], builtin_taps=True)
+        n = int(self.lib.aegis_pcm_samples_for(self._h, arr))
+        if n < 0:
+            raise AegisError(n, "invalid PCM clip")
+        return n
+
+    def analyze_pcm(self, sources, rake_sensitivity=0.6, stages=STAGE_ALL, want_sdb=True, check_finite=False, f0_zero=False,
+                    views=False, concatenated=False, want_col_means=False, want_y=True, builtin_taps=False):
+        """analyze_batch on WAV sample data decoded, mixed down and resampled to the handle's rate on the device
+        (aegis_analyze_pcm).  sources: audio_io.PcmSource tuples.  Each per-clip dict also carries "y", the float32
+        samples the analysis saw (None with want_y=False: then they do not come back from the device).  stages=0 decodes
+        only: the dicts hold "y" alone."""
+        n = len(sources)
+        if n == 0:
+            return ([], {}, np.zeros(1, np.int64)) if concatenated else []
+        arr, keep = self.pcm_clips(sources, builtin_taps)
+        lens = [int(self.lib.aegis_pcm_samples_for(self._h, C.byref(arr[i]))) for i in range(n)]
+        if min(lens) < 0:
+            raise AegisError(ERR_INVALID, "invalid PCM clip")
+        y = np.empty(sum(lens), np.float32) if (want_y or not stages) else None
+        yp = y.ctypes.data if y is not None else None
+        if not stages:
+            flags = OPT_CHECK_FINITE if check_finite else 0
+            self._check_analyze(self.lib.aegis_analyze_pcm(self._h, arr, n, float(rake_sensitivity), flags, None, yp), check_finite)
+            res = [{"y": a} for a in np.split(y, np.cumsum(lens)[:-1])]
+            return (res, {}, np.zeros(1, np.int64)) if concatenated else res
+        frames = [1 + k // self.hop for k in lens]
+        bufs, out, flags = self._outputs(frames, stages, want_sdb, check_finite, f0_zero, concatenated, want_col_means)
+        rc = self.lib.aegis_analyze_pcm(self._h, arr, n, float(rake_sensitivity), flags, C.byref(out), yp)
+        del keep
+        self._check_analyze(rc, check_finite)
+        got = self._split(bufs, frames, views, concatenated)
+        ys = np.split(y, np.cumsum(lens)[:-1]) if y is not None else [None] * n
+        for d, a in zip(got[0] if concatenated else got, ys):
+            d["y"] = a
+        return got
 
     def rake_patterns(self, S_dB, ratio):
         S = np.ascontiguousarray(S_dB, dtype=np.float32)
@@ -444,6 +527,17 @@ class Handle:
         self._check(self.lib.aegis_analyze_batch_device(
             self._h, C.c_void_p(int(d_pcm_ptr)), off.ctypes.data_as(C.POINTER(C.c_int64)), len(off) - 1,
             float(rake_sensitivity), int(stages), C.byref(out), C.c_void_p(stream or 0), 1 if sync else 0))
+
+
+def resample_taps(up, down):
+    """aegis_resample_taps: the library's built-in low-pass for a rate pair (host code, no handle, no GPU)."""
+    lib = load()
+    n = int(lib.aegis_resample_taps(int(up), int(down), None, 0))
+    if n < 0:
+        raise AegisError(n, "bad rate pair")
+    out = np.empty(n, np.float32)
+    lib.aegis_resample_taps(int(up), int(down), out.ctypes.data, n)
+    return out
 
 
 class Stream:

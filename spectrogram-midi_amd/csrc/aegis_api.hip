@@ -15,6 +15,8 @@
 #include <map>
 #include <mutex>
 #include <new>
+#include <numeric>
+#include <functional>
 #include <stdexcept>
 #include <string>
 #include <thread>
@@ -24,6 +26,7 @@
 #include "kernels.h"
 #include "plan.h"
 #include "cqt.h"
+#include "pcm.h"
 #include "tables.h"
 #include "trend.h"
 
@@ -81,6 +84,7 @@ struct aegis_handle {
     DevBuf t_x, t_off, t_a, t_b, t_c, t_d, t_e, t_i8, t_i64a, t_i64b;   // trend-filter staging
     DevBuf t_pa;                              // scratch of the fused pitch analysis: 12 rows of doubles + 1 of bytes
     DevBuf io_pcm, io_f0, io_voiced, io_vprob, io_rms, io_rake, io_sdb, io_bin, io_colmean;
+    DevBuf pcm_raw, pcm_clips, pcm_ranges, pcm_taps;   // aegis_analyze_pcm: raw bytes, clip table, per-chunk range tables, filters
     int32_t lag_stride = 0, yin_stride = 0, obs_stride = 0;
     CallPlan plan;                            // the last call's plan: its host arrays stay alive until the stream drained
     bool plan_in_flight = false;              // the stream may still read them
@@ -434,7 +438,7 @@ static void destroy_now(aegis_handle *h) noexcept {
     T("free staging");
     for (DevBuf *b : {&h->vstats, &h->rk_raw, &h->abort_flag, &h->finite_flag, &h->t_x, &h->t_off, &h->t_a, &h->t_b, &h->t_c, &h->t_d, &h->t_e,
                       &h->t_i8, &h->t_i64a, &h->t_i64b, &h->t_pa, &h->q_pcm, &h->q_soff, &h->q_foff, &h->q_toff, &h->q_out, &h->q_chroma, &h->q_cls, &h->io_pcm, &h->io_f0, &h->io_voiced, &h->io_vprob, &h->io_rms, &h->io_rake,
-                      &h->io_sdb, &h->io_bin, &h->io_colmean})
+                      &h->io_sdb, &h->io_bin, &h->io_colmean, &h->pcm_raw, &h->pcm_clips, &h->pcm_ranges, &h->pcm_taps})
         free_buf(*b);
     T("destroy streams");
     if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -473,13 +477,64 @@ double aegis_last_kernel_ms(const aegis_handle *h, const char *name) {
     return it == h->last_ms.end() ? -1.0 : it->second;
 }
 
+// Raw WAV bytes of aegis_analyze_pcm: per time chunk, the bytes of the input frames the chunk's new output samples read
+// are copied on stream3 and one pcm_decode_resample_kernel writes those samples into the PCM buffer.
+struct PcmFeed {
+    const aegis_pcm_clip *src;            // [n_clips] the caller's clips
+    std::vector<PcmClipDev> clips;        // host copy of the device clip table
+    std::vector<int64_t> done_in;         // input frames of each clip already enqueued
+    std::vector<std::vector<PcmRange>> tables;   // every launch's range table (host memory of in-flight copies)
+    int64_t range_cap = 0, range_used = 0;       // entries of h->pcm_ranges
+    float *y_out = nullptr;               // the decoded samples back to the host, pass after pass (optional)
+};
+
 // Host-resident input of aegis_analyze_batch: the samples each time chunk needs are copied on stream3 right
 // before that chunk's frame stage is enqueued, so the transfer hides behind the pipeline instead of preceding it.
 struct HostFeed {
     const float *const *pcm;      // [n_clips] host pointers
     float *dst;                   // packed device buffer (== d_pcm)
-    std::vector<int64_t> copied;  // samples of each clip already enqueued
+    std::vector<int64_t> copied;  // samples of each clip already enqueued (output samples for a raw-byte feed)
+    PcmFeed *raw = nullptr;       // raw WAV bytes instead of float32 samples
 };
+
+// Enqueues on stream3 the raw bytes and the decode of output samples [copied[ci], need[i]) of the pass's clips i.
+static int pcm_feed(aegis_handle *h, HostFeed &feed, const std::vector<int32_t> &cis, const std::vector<int64_t> &need) {
+    PcmFeed &pf = *feed.raw;
+    std::vector<PcmRange> tab;
+    int64_t tiles = 0;
+    for (size_t i = 0; i < cis.size(); ++i) {
+        const int ci = cis[i];
+        int64_t &done = feed.copied[(size_t)ci];
+        if (need[i] <= done) continue;
+        const PcmClipDev &c = pf.clips[(size_t)ci];
+        const int64_t fb = (int64_t)c.ch * (c.fmt == AEGIS_PCM_U8 ? 1 : c.fmt == AEGIS_PCM_S16 ? 2 : c.fmt == AEGIS_PCM_S24 ? 3 : 4);
+        const int64_t in_hi = pcm_inputs_needed(c, need[i]);
+        int64_t &din = pf.done_in[(size_t)ci];
+        if (in_hi > din) {
+            HIPCHK(h, hipMemcpyAsync(static_cast<uint8_t *>(h->pcm_raw.p) + c.byte_off + din * fb,
+                                     static_cast<const uint8_t *>(pf.src[ci].data) + din * fb, (size_t)((in_hi - din) * fb),
+                                     hipMemcpyHostToDevice, h->stream3));
+            din = in_hi;
+        }
+        tab.push_back(PcmRange{done, need[i], tiles, ci, 0});
+        tiles += (need[i] - done + c.tile - 1) / c.tile;
+        done = need[i];
+    }
+    if (tab.empty()) return AEGIS_OK;
+    if (pf.range_used + (int64_t)tab.size() > pf.range_cap) {      // the slots are reused once the launches reading them are done
+        HIPCHK(h, hipStreamSynchronize(h->stream3));
+        pf.range_used = 0;
+    }
+    PcmRange *d_tab = static_cast<PcmRange *>(h->pcm_ranges.p) + pf.range_used;
+    pf.range_used += (int64_t)tab.size();
+    pf.tables.push_back(std::move(tab));
+    const std::vector<PcmRange> &t = pf.tables.back();
+    HIPCHK(h, hipMemcpyAsync(d_tab, t.data(), t.size() * sizeof(PcmRange), hipMemcpyHostToDevice, h->stream3));
+    launch_pcm_decode(static_cast<const uint8_t *>(h->pcm_raw.p), static_cast<const PcmClipDev *>(h->pcm_clips.p), d_tab,
+                      (int)t.size(), tiles, static_cast<const float *>(h->pcm_taps.p), feed.dst, h->stream3);
+    HIPCHK(h, hipGetLastError());
+    return AEGIS_OK;
+}
 
 // sync: 0 = return with the work enqueued, 1 = synchronise and report (give-up of the single Viterbi launch, non-finite
 // samples), 2 = the caller synchronises and makes those checks itself right away (aegis_analyze_batch: the single Viterbi
@@ -910,7 +965,22 @@ static int analyze_device_locked(aegis_handle *h, const float *d_pcm, const int6
             p.vt_end = (k == nk - 1) ? INT64_MAX : m.cb[k + 1];
             p.clip_t0 = m.proportional ? static_cast<const int64_t *>(w.clip_tb.p) + (size_t)k * nc : nullptr;
             p.clip_t1 = m.proportional ? static_cast<const int64_t *>(w.clip_tb.p) + (size_t)(k + 1) * nc : nullptr;
-            if (feed) {      // frame t reads samples [t*hop - 1024, t*hop + 1024)
+            if (feed && feed->raw) {      // the same samples, decoded on the device from the raw bytes
+                std::vector<int32_t> cis((size_t)nc);
+                std::vector<int64_t> need((size_t)nc);
+                bool any = false;
+                for (int i = 0; i < nc; ++i) {
+                    const int64_t n = m.sample_len[i];
+                    cis[(size_t)i] = m.clips[i];
+                    need[(size_t)i] = (k == nk - 1) ? n : std::min(n, (m.clip_hi(k, i) - 1) * (int64_t)t.hop + t.n_fft / 2);
+                    any = any || need[(size_t)i] > feed->copied[(size_t)m.clips[i]];
+                }
+                if (any) {
+                    if ((rc = pcm_feed(h, *feed, cis, need)) != AEGIS_OK) return rc;
+                    HIPCHK(h, hipEventRecord(h->copy_event, h->stream3));
+                    HIPCHK(h, hipStreamWaitEvent(fs, h->copy_event, 0));
+                }
+            } else if (feed) {      // frame t reads samples [t*hop - 1024, t*hop + 1024)
                 bool any = false;
                 for (int i = 0; i < nc; ++i) {
                     const int ci = m.clips[i];
@@ -1017,6 +1087,12 @@ static int analyze_device_locked(aegis_handle *h, const float *d_pcm, const int6
         HIPCHK(h, hipEventRecord(h->sync_events[EV_DONE0 + (pi & 1)], se));
         done_recorded[pi & 1] = true;
         HIPCHK(h, hipGetLastError());
+        if (feed && feed->raw && feed->raw->y_out) {      // the pass's samples back to the host, behind its last decode
+            for (int i = 0; i < nc; ++i)
+                if (m.sample_len[i] > 0)
+                    HIPCHK(h, hipMemcpyAsync(feed->raw->y_out + m.sample_off[i], feed->dst + m.sample_off[i], (size_t)m.sample_len[i] * 4,
+                                             hipMemcpyDeviceToHost, h->stream3));
+        }
     }
     // ---- join: the caller's stream continues after everything enqueued above --------------------------------------------
     for (int q = 0; q < 2; ++q)
@@ -1048,6 +1124,9 @@ static int analyze_device_locked(aegis_handle *h, const float *d_pcm, const int6
 }
 #undef VCHK
 
+static int host_fed_locked(aegis_handle *h, const std::vector<int64_t> &off, int64_t F, int32_t n_clips, double rake_sensitivity,
+                           uint32_t stages, aegis_outputs *out, const std::function<HostFeed()> &make_feed);
+
 int aegis_analyze_batch(aegis_handle *h, const float *const *pcm, const int64_t *n_samples, int32_t n_clips,
                         double rake_sensitivity, uint32_t stages, aegis_outputs *out) {
     try {
@@ -1068,6 +1147,17 @@ int aegis_analyze_batch(aegis_handle *h, const float *const *pcm, const int64_t 
     }
     int rc;
     if ((rc = ensure(h, h->io_pcm, (size_t)std::max<int64_t>(off[n_clips], 1) * 4)) != AEGIS_OK) return rc;
+    return host_fed_locked(h, off, F, n_clips, rake_sensitivity, stages, out, [&]() {
+        return HostFeed{pcm, static_cast<float *>(h->io_pcm.p), std::vector<int64_t>((size_t)n_clips, 0)};
+    });
+    } catch (...) { return abi_fail(h); }
+}
+
+// The blocking host-fed analysis of aegis_analyze_batch and aegis_analyze_pcm (handle locked, io_pcm sized): the device
+// outputs, the pipeline fed by make_feed() (a fresh feed for every attempt), the outputs back to the host.
+static int host_fed_locked(aegis_handle *h, const std::vector<int64_t> &off, int64_t F, int32_t n_clips, double rake_sensitivity,
+                           uint32_t stages, aegis_outputs *out, const std::function<HostFeed()> &make_feed) {
+    int rc;
     hipStream_t s = h->stream;
     // the previous call's kernels may still read io_pcm only if it returned without a sync -- it never does
     if (!h->persistent && h->knobs.persistent_wanted && h->persist_cooldown > 0 && --h->persist_cooldown == 0)
@@ -1085,7 +1175,7 @@ int aegis_analyze_batch(aegis_handle *h, const float *const *pcm, const int64_t 
     for (int attempt = 0;; ++attempt) {
         // stream_v = NULL (the handle's own stream) and sync = 2: the schedule the device-pointer entry takes with
         // sync = 1, single Viterbi launch included -- this function synchronises below
-        HostFeed feed{pcm, static_cast<float *>(h->io_pcm.p), std::vector<int64_t>((size_t)n_clips, 0)};
+        HostFeed feed = make_feed();
         rc = analyze_device_locked(h, static_cast<const float *>(h->io_pcm.p), off.data(), n_clips,
                                    rake_sensitivity, stages, &d, nullptr, 2, &feed);
         if (rc == AEGIS_ERR_NOMEM && h->max_frames_per_pass > ((int64_t)1 << 21)) {      // as in aegis_analyze_batch_device
@@ -1114,10 +1204,136 @@ int aegis_analyze_batch(aegis_handle *h, const float *const *pcm, const int64_t 
     if (d.rake_mask) HIPCHK(h, hipMemcpyAsync(out->rake_mask, d.rake_mask, F, hipMemcpyDeviceToHost, s));
     if (d.S_dB) HIPCHK(h, hipMemcpyAsync(out->S_dB, d.S_dB, (size_t)F * nm * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipStreamSynchronize(s));
+    HIPCHK(h, hipStreamSynchronize(h->stream3));      // (a raw-byte feed's decoded samples back to the host)
     h->plan_in_flight = false;
     if ((rc = persistent_check(h)) != AEGIS_OK) return rc;
     if (h->profiling) collect_events(h);
     return finite_result(h, stages, off.data(), n_clips);
+}
+
+static int64_t pcm_width(int32_t fmt) {
+    return fmt == AEGIS_PCM_U8 ? 1 : fmt == AEGIS_PCM_S16 ? 2 : fmt == AEGIS_PCM_S24 ? 3 : fmt == AEGIS_PCM_S32 || fmt == AEGIS_PCM_F32 ? 4 : 0;
+}
+
+// samples of a clip at rate sr (audio_io.resampled_length); negative with a message for an invalid clip
+static int64_t pcm_samples(int32_t sr, const aegis_pcm_clip &c, std::string *why) {
+    const char *bad = nullptr;
+    if (!pcm_width(c.format)) bad = "unsupported sample format (AEGIS_PCM_U8 .. AEGIS_PCM_F32)";
+    else if (c.channels < 1 || c.channels > 8) bad = "channels must be 1..8";
+    else if (c.sample_rate <= 0) bad = "sample_rate must be positive";
+    else if (c.n_frames < 0) bad = "n_frames < 0";
+    else if (c.n_frames > 0 && !c.data) bad = "data == NULL";
+    else if (c.taps && (c.n_taps <= 0 || !(c.n_taps & 1))) bad = "n_taps must be odd and positive";
+    if (bad) { if (why) *why = bad; return AEGIS_ERR_INVALID; }
+    if (c.sample_rate == sr) return c.n_frames;
+    return (int64_t)std::ceil((double)c.n_frames * (double)sr / (double)c.sample_rate);
+}
+
+int64_t aegis_pcm_samples_for(const aegis_handle *h, const aegis_pcm_clip *clip) {
+    if (!h || !clip) return AEGIS_ERR_INVALID;
+    return pcm_samples(h->tab.sr, *clip, nullptr);
+}
+
+int64_t aegis_resample_taps(int32_t up, int32_t down, float *dst, int64_t cap) {
+    try {
+    if (up < 1 || down < 1) return AEGIS_ERR_INVALID;
+    const int32_t g = std::gcd(up, down);
+    const std::vector<float> t = pcm_builtin_taps(up / g, down / g);
+    if (dst && cap > 0) std::memcpy(dst, t.data(), (size_t)std::min<int64_t>(cap, (int64_t)t.size()) * 4);
+    return (int64_t)t.size();
+    } catch (...) { return AEGIS_ERR_NOMEM; }
+}
+
+int aegis_analyze_pcm(aegis_handle *h, const aegis_pcm_clip *clips, int32_t n_clips, double rake_sensitivity, uint32_t stages,
+                      aegis_outputs *out, float *y_out) {
+    try {
+    if (!h) return AEGIS_ERR_INVALID;
+    if (stages & AEGIS_STAGE_RAKE) stages |= AEGIS_STAGE_MEL;
+    const bool analyse = (stages & AEGIS_STAGE_ALL) != 0;
+    if (n_clips < 0 || (n_clips > 0 && (!clips || (analyse && !out)))) { h->err = "null argument"; return AEGIS_ERR_INVALID; }
+    if (!analyse && !y_out) { h->err = "stages == 0 decodes only and needs y_out"; return AEGIS_ERR_INVALID; }
+    if (n_clips == 0) return AEGIS_OK;
+    if (h->device < 0) { h->err = "handle was created with device=-1 (host tables only)"; return AEGIS_ERR_DEVICE; }
+    std::lock_guard<std::mutex> lock(h->mu);
+    HIPCHK(h, hipSetDevice(h->device));
+    const int32_t sr = h->tab.sr;
+    PcmFeed pf;
+    pf.src = clips;
+    pf.y_out = y_out;
+    pf.clips.resize((size_t)n_clips);
+    std::vector<int64_t> off((size_t)n_clips + 1, 0);
+    std::vector<float> taps;
+    std::map<std::pair<std::pair<int32_t, int32_t>, const float *>, size_t> filters;   // (up, down, caller's taps) -> first clip using it
+    int64_t F = 0, raw_bytes = 0;
+    for (int i = 0; i < n_clips; ++i) {
+        const aegis_pcm_clip &a = clips[i];
+        std::string why;
+        const int64_t n_out = pcm_samples(sr, a, &why);
+        if (n_out < 0) { h->err = "clip " + std::to_string(i) + ": " + why; return AEGIS_ERR_INVALID; }
+        PcmClipDev &c = pf.clips[(size_t)i];
+        c.byte_off = raw_bytes;
+        raw_bytes += (a.n_frames * pcm_width(a.format) * a.channels + 15) & ~(int64_t)15;
+        c.n_in = a.n_frames; c.out_off = off[(size_t)i];
+        c.fmt = a.format; c.ch = a.channels;
+        c.up = 1; c.down = 1; c.P = 1; c.rm = 0; c.taps_off = 0; c.n_res = a.n_frames;
+        if (a.sample_rate != sr) {
+            const int32_t g = std::gcd(a.sample_rate, sr);
+            c.up = sr / g; c.down = a.sample_rate / g;
+            c.n_res = (a.n_frames * c.up + c.down - 1) / c.down;
+            const auto key = std::make_pair(std::make_pair(c.up, c.down), a.taps);
+            auto it = filters.find(key);
+            if (it != filters.end()) {
+                const PcmClipDev &o = pf.clips[it->second];
+                c.P = o.P; c.rm = o.rm; c.taps_off = o.taps_off;
+            } else {
+                const std::vector<float> own = a.taps ? std::vector<float>(a.taps, a.taps + a.n_taps) : pcm_builtin_taps(c.up, c.down);
+                std::vector<float> htf;
+                c.P = pcm_filter_layout(own.data(), (int)own.size(), c.up, c.down, htf, &c.rm);
+                c.taps_off = (int64_t)taps.size();
+                taps.insert(taps.end(), htf.begin(), htf.end());
+                filters[key] = (size_t)i;
+            }
+        }
+        c.tile = pcm_tile(c);
+        off[(size_t)i + 1] = off[(size_t)i] + n_out;
+        F += 1 + n_out / h->tab.hop;
+    }
+    int rc;
+    if ((rc = ensure(h, h->io_pcm, (size_t)std::max<int64_t>(off[(size_t)n_clips], 1) * 4)) != AEGIS_OK) return rc;
+    if ((rc = ensure(h, h->pcm_raw, (size_t)raw_bytes + 16)) != AEGIS_OK) return rc;
+    if ((rc = ensure(h, h->pcm_clips, (size_t)n_clips * sizeof(PcmClipDev))) != AEGIS_OK) return rc;
+    if ((rc = ensure(h, h->pcm_taps, std::max<size_t>(taps.size(), 1) * 4)) != AEGIS_OK) return rc;
+    pf.range_cap = (int64_t)n_clips * 32;
+    if ((rc = ensure(h, h->pcm_ranges, (size_t)pf.range_cap * sizeof(PcmRange))) != AEGIS_OK) return rc;
+    pf.range_cap = (int64_t)(h->pcm_ranges.cap / sizeof(PcmRange));
+    HIPCHK(h, hipMemcpyAsync(h->pcm_clips.p, pf.clips.data(), (size_t)n_clips * sizeof(PcmClipDev), hipMemcpyHostToDevice, h->stream3));
+    if (!taps.empty()) HIPCHK(h, hipMemcpyAsync(h->pcm_taps.p, taps.data(), taps.size() * 4, hipMemcpyHostToDevice, h->stream3));
+    float *d_pcm = static_cast<float *>(h->io_pcm.p);
+    if (!analyse) {      // decode only: every clip at once
+        HostFeed feed{nullptr, d_pcm, std::vector<int64_t>((size_t)n_clips, 0), &pf};
+        pf.done_in.assign((size_t)n_clips, 0);
+        std::vector<int32_t> cis((size_t)n_clips);
+        std::vector<int64_t> need((size_t)n_clips);
+        for (int i = 0; i < n_clips; ++i) { cis[(size_t)i] = i; need[(size_t)i] = off[(size_t)i + 1] - off[(size_t)i]; }
+        if ((rc = pcm_feed(h, feed, cis, need)) != AEGIS_OK) return rc;
+        if (stages & AEGIS_OPT_CHECK_FINITE) {
+            if ((rc = ensure(h, h->finite_flag, 8)) != AEGIS_OK) return rc;
+            HIPCHK(h, hipMemsetAsync(h->finite_flag.p, 0xff, 8, h->stream3));
+            launch_finite_check(d_pcm, off[(size_t)n_clips], static_cast<unsigned long long *>(h->finite_flag.p), h->stream3);
+        }
+        for (int i = 0; i < n_clips; ++i)
+            if (off[(size_t)i + 1] > off[(size_t)i])
+                HIPCHK(h, hipMemcpyAsync(y_out + off[(size_t)i], d_pcm + off[(size_t)i], (size_t)(off[(size_t)i + 1] - off[(size_t)i]) * 4,
+                                         hipMemcpyDeviceToHost, h->stream3));
+        HIPCHK(h, hipStreamSynchronize(h->stream3));
+        return finite_result(h, stages, off.data(), n_clips);
+    }
+    return host_fed_locked(h, off, F, n_clips, rake_sensitivity, stages, out, [&]() {
+        pf.done_in.assign((size_t)n_clips, 0);
+        pf.tables.clear();
+        pf.range_used = 0;
+        return HostFeed{nullptr, d_pcm, std::vector<int64_t>((size_t)n_clips, 0), &pf};
+    });
     } catch (...) { return abi_fail(h); }
 }
 

@@ -21,14 +21,6 @@ _ENGINE_ONLY_KWARGS = ("confidence_threshold", "start_time", "end_time", "turbo_
                        "vibrato_rate", "vibrato_depth")
 
 
-def _require_finite(y):
-    # librosa.util.valid_audio raises ParameterError on NaN / inf samples.  A BLAS dot product is non-finite whenever
-    # a sample is (NaN and inf propagate) and costs a quarter of np.isfinite(y).all(); only if it is non-finite --
-    # which finite samples beyond 1e19 could also cause -- is the exact test run.
-    if not np.isfinite(np.dot(y, y)) and not np.isfinite(y).all():
-        raise ValueError("Audio buffer is not finite everywhere")
-
-
 class AegisEngine:
     def __init__(self, sample_rate=44100, hop_length=512, n_fft=2048, device=0, verbose=False, pyin_init="unvoiced"):
         # pyin_init (not a reference argument): "unvoiced" = librosa.pyin's own initial distribution (the default, what
@@ -64,10 +56,9 @@ class AegisEngine:
     def load_audio(self, file_path, start_time=0, end_time=None):
         """-> (y float32[N], S_dB float32[128, F])  (aegis_engine.py:22-27)."""
         duration = (end_time - start_time) if end_time else None
-        y = audio_io.read_wav(file_path, self.sr, offset=start_time, duration=duration)
-        _require_finite(y)
-        out = self.handle.analyze_batch([y], stages=_lib.STAGE_MEL)[0]
-        return y, out["S_dB"]
+        src = audio_io.load_pcm_files([file_path], self.sr, start_time, duration)
+        out = self.handle.analyze_pcm(src, stages=_lib.STAGE_MEL, check_finite=True)[0]
+        return out["y"], out["S_dB"]
 
     def detect_rake_patterns(self, S_dB):
         """aegis_engine.py:38-39 (fixed 0.6 ratio)."""
@@ -99,11 +90,9 @@ class AegisEngine:
     def audio_to_midi(self, input_wav, output_mid, **kwargs):
         """Perception phase -> raw_data dict or None for empty audio (aegis_engine.py:41-75).
         `output_mid` is accepted and ignored, as in the reference."""
-        start_time, end_time = kwargs.get("start_time", 0), kwargs.get("end_time", None)
-        duration = (end_time - start_time) if end_time else None
-        y = audio_io.read_wav(input_wav, self.sr, offset=start_time, duration=duration)
-        return self.analyze_array(y, turbo_mode=kwargs.get("turbo_mode", False),
-                                  rake_sensitivity=kwargs.get("rake_sensitivity", 0.6))
+        return self.analyze_files([input_wav], turbo_mode=kwargs.get("turbo_mode", False),
+                                  rake_sensitivity=kwargs.get("rake_sensitivity", 0.6), start_time=kwargs.get("start_time", 0),
+                                  end_time=kwargs.get("end_time", None))[0]
 
     analyze = audio_to_midi      # BASELINE.json's name for the same call
 
@@ -149,14 +138,57 @@ class AegisEngine:
                           "rms": r["rms"], "y": clips[i]}
         return (results, bufs, off, live) if _concatenated else results
 
+    def analyze_files(self, paths, turbo_mode=False, rake_sensitivity=0.6, start_time=0, end_time=None, want_y=True,
+                      _concatenated=False):
+        """A folder of WAV files -> element i is what audio_to_midi(paths[i], None, ...) returns.  The files are read
+        one after the other as raw sample bytes (audio_io.load_pcm); decoding, the channel mean and the resampling to
+        the engine rate run on the GPU, inside the analysis (Handle.analyze_pcm).  want_y=False: "y" is None and the
+        samples never come back from the device."""
+        duration = (end_time - start_time) if end_time else None
+        srcs = audio_io.load_pcm_files(paths, self.sr, start_time, duration)
+        if turbo_mode:          # decode only, then the Turbo-Mode analysis of the decoded clips
+            h = self.handle
+            ys = [r["y"] for r in h.analyze_pcm(srcs, stages=0)] if srcs else []
+            got = self.analyze_arrays(ys, turbo_mode=True, rake_sensitivity=rake_sensitivity, _concatenated=_concatenated)
+            if not want_y:
+                for r in (got[0] if _concatenated else got):
+                    if r is not None:
+                        r["y"] = None
+            return got
+        live = [i for i, s in enumerate(srcs)
+                if audio_io.resampled_length(len(s.data) // (audio_io.PCM_WIDTH[s.format] * s.channels), s.sample_rate, self.sr) > 0]
+        results = [None] * len(srcs)
+        if not live:
+            return (results, None, None, live) if _concatenated else results
+        self._say(f"[Aegis] Starting Perception Phase (Turbo: {turbo_mode})...")
+        self._say("[Aegis] Using Stable Single-core Analysis.")
+        frames, bufs, off = self.handle.analyze_pcm([srcs[i] for i in live], rake_sensitivity=rake_sensitivity,
+                                                    stages=_lib.STAGE_ALL, want_sdb=False, check_finite=True, f0_zero=True,
+                                                    views=True, concatenated=True, want_y=want_y)
+        for i, r in zip(live, frames):
+            results[i] = {"rake_mask": r["rake_mask"], "f0": r["f0"], "voiced_flag": r["voiced_flag"],
+                          "voiced_probs": r["voiced_prob"], "rms": r["rms"], "y": r["y"]}
+        return (results, bufs, off, live) if _concatenated else results
+
+    def audio_to_midi_files(self, paths, want_midi=True, **kwargs):
+        """audio_to_midi_batch for a folder of WAV files decoded on the GPU (analyze_files): the same triple.  kwargs as
+        for audio_to_midi_batch, plus start_time / end_time and want_y."""
+        got = self.analyze_files(paths, turbo_mode=kwargs.get("turbo_mode", False),
+                                 rake_sensitivity=kwargs.get("rake_sensitivity", 0.6), start_time=kwargs.get("start_time", 0),
+                                 end_time=kwargs.get("end_time", None), want_y=kwargs.pop("want_y", True), _concatenated=True)
+        return self._events_batch(len(paths), got, want_midi, kwargs)
+
     def audio_to_midi_batch(self, clips, want_midi=True, **kwargs):
         """A folder of decoded clips -> (raw_data dicts, event lists, SMF bytes per clip): audio_to_midi + extract_events
         for every clip (aegis_engine.py:41-181) as ONE analysis batch and ONE batched event extraction / MIDI rendering
         (C++, clips in parallel).  Empty clips give (None, [], None).  kwargs as for both reference methods."""
         turbo = kwargs.get("turbo_mode", False)
-        raws, bufs, off, live = self.analyze_arrays(clips, turbo_mode=turbo, rake_sensitivity=kwargs.get("rake_sensitivity", 0.6),
-                                                    _concatenated=True)
-        events, blobs = [[] for _ in clips], [None] * len(clips)
+        got = self.analyze_arrays(clips, turbo_mode=turbo, rake_sensitivity=kwargs.get("rake_sensitivity", 0.6), _concatenated=True)
+        return self._events_batch(len(clips), got, want_midi, kwargs)
+
+    def _events_batch(self, n, got, want_midi, kwargs):
+        raws, bufs, off, live = got
+        events, blobs = [[] for _ in range(n)], [None] * n
         if not live:
             return raws, events, blobs
         passthrough = {k: v for k, v in kwargs.items() if k not in _ENGINE_ONLY_KWARGS + ("midi_program",)}

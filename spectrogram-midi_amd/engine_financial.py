@@ -33,8 +33,9 @@ class AegisFinancialEngine:
 
     def load_audio(self, file_path, start_time=0, end_time=None):
         duration = (end_time - start_time) if end_time else None
-        y = audio_io.read_wav(file_path, self.sr, offset=start_time, duration=duration)
-        return y, self.handle.analyze_batch([y], stages=_lib.STAGE_MEL)[0]["S_dB"]
+        src = audio_io.load_pcm_files([file_path], self.sr, start_time, duration)
+        r = self.handle.analyze_pcm(src, stages=_lib.STAGE_MEL)[0]
+        return r["y"], r["S_dB"]
 
     def detect_rake_patterns(self, S_dB, rake_sensitivity=0.6):
         return self.handle.rake_patterns(S_dB, rake_sensitivity)
@@ -47,6 +48,9 @@ class AegisFinancialEngine:
         """Everything of audio_to_midi_financial up to the event list, from decoded PCM (one GPU call)."""
         y = np.ascontiguousarray(y, dtype=np.float32)
         r = self.handle.analyze_batch([y], rake_sensitivity=kwargs.get("rake_sensitivity", 0.6))[0]
+        return self._events_of(r, kwargs)
+
+    def _events_of(self, r, kwargs):
         f0, voiced, rake = r["f0"], r["voiced_flag"], r["rake_mask"]
         if kwargs.get("use_guitar_filters", True):
             g = apply_guitar_filters(f0, voiced, r["S_dB"], self.hop_length, self.sr, rake)
@@ -70,9 +74,24 @@ class AegisFinancialEngine:
         clips = [np.ascontiguousarray(c, dtype=np.float32) for c in clips]
         if not clips:
             return []
+        got = self.handle.analyze_batch(clips, rake_sensitivity=kwargs.get("rake_sensitivity", 0.6), want_sdb=False,
+                                        want_col_means=kwargs.get("use_guitar_filters", True), views=True, concatenated=True)
+        return self._events_batch(got, kwargs)
+
+    def analyze_files(self, paths, **kwargs):
+        """analyze_arrays on a folder of WAV files, decoded, mixed down and resampled to the engine rate on the GPU inside
+        the analysis (Handle.analyze_pcm); the files are read one after the other as raw sample bytes."""
+        srcs = audio_io.load_pcm_files(paths, self.sr)
+        if not srcs:
+            return []
+        got = self.handle.analyze_pcm(srcs, rake_sensitivity=kwargs.get("rake_sensitivity", 0.6), want_sdb=False,
+                                      want_col_means=kwargs.get("use_guitar_filters", True), views=True, concatenated=True,
+                                      want_y=False)
+        return self._events_batch(got, kwargs)
+
+    def _events_batch(self, got, kwargs):
+        res, bufs, off = got
         use_guitar = kwargs.get("use_guitar_filters", True)
-        res, bufs, off = self.handle.analyze_batch(clips, rake_sensitivity=kwargs.get("rake_sensitivity", 0.6), want_sdb=False,
-                                                   want_col_means=use_guitar, views=True, concatenated=True)
         F = int(off[-1])
         items = []
         for i, r in enumerate(res):
@@ -115,8 +134,9 @@ class AegisFinancialEngine:
 
     def audio_to_midi_financial(self, input_wav, output_mid, **kwargs):
         """-> output_mid, or None when no note was found (aegis_engine_financial.py:73-253)."""
-        y = audio_io.read_wav(input_wav, self.sr)
-        events = self.analyze_array(y, **kwargs)
+        src = audio_io.load_pcm_files([input_wav], self.sr)
+        r = self.handle.analyze_pcm(src, rake_sensitivity=kwargs.get("rake_sensitivity", 0.6), want_y=False)[0]
+        events = self._events_of(r, kwargs)
         if not events:
             return None
         with open(output_mid, "wb") as f:
