@@ -217,6 +217,32 @@ int aegis_stream_push(aegis_stream *st, const float *samples, int64_t n, aegis_s
 int aegis_stream_close(aegis_stream *st, double rake_sensitivity, aegis_outputs *host_out, int64_t *n_frames);
 void aegis_stream_free(aegis_stream *st);
 
+/* The frames whose pYIN decode is already final.  aegis_stream_push_commit is aegis_stream_push plus one more kernel behind
+ * the Viterbi: it walks the back-pointers from every state still alive at the newest frame back to the last frame it has
+ * decided (the frontier); a frame at which all those survivor paths give the same output (one voiced bin, or unvoiced) is
+ * decided, and the frontier advances over the decided prefix.  The path aegis_stream_close will return is one of the
+ * survivor paths, so a decided frame's bin is BIT FOR BIT what close returns for it (f0 = freqs[bin] of
+ * aegis_get_table("freqs"), voiced_flag = bin >= 0; -1 = unvoiced: the convention of aegis_outputs.pitch_bin), whatever
+ * audio follows.  The lag between the newest frame and the frontier follows the material: one frame on silence, tens of
+ * frames on a clean note, as long as two lineages (one voiced, one unvoiced) stay alive on an ambiguous one.
+ * Delivered frames are consecutive and never repeated: `first` of a push is the previous `frontier` + 1.  Decided frames
+ * that do not fit into `cap` are delivered by later pushes (a push of n = 0 samples collects them).  After
+ * aegis_stream_close the frames behind `frontier` are in the arrays close returns: a caller concatenates what was
+ * delivered with close()[frontier + 1:].  The two push entries may be mixed on one stream (a commit push after plain pushes
+ * catches up from its last frontier); commit == NULL behaves as aegis_stream_push.  rms and voiced_prob of a frame are
+ * final when the push that produced the frame returns them, as before. */
+typedef struct aegis_stream_commit {
+    int16_t *pitch_bin;   /* host, [cap]: bins of the frames delivered by this push, in frame order (NULL only with cap 0) */
+    int64_t cap;          /* room in pitch_bin (>= 0) */
+    int64_t first;        /* out: index of the first frame delivered */
+    int64_t count;        /* out: frames delivered (0 is common) */
+    int64_t frontier;     /* out: last frame delivered so far, -1 before the first */
+    int64_t walked;       /* out: frames the commit kernel walked back in this push (0: it had nothing new to look at) */
+    int64_t walked_wide;  /* out: how many of them with more than 64 survivor paths alive (whole workgroup, barriers) */
+} aegis_stream_commit;
+int aegis_stream_push_commit(aegis_stream *st, const float *samples, int64_t n, aegis_stream_frames *out, int64_t *n_frames,
+                             aegis_stream_commit *commit);
+
 /* --- v2 "financial" trend filters on pitch tracks -------------------
  * One op-coded entry over a ragged batch of float64 series in host memory: series i is
  * x[offsets[i] .. offsets[i+1]) (NaN = unvoiced); outputs are host arrays of offsets[n_series]

@@ -42,6 +42,11 @@ class StreamFrames(C.Structure):
     _fields_ = [("rms", C.c_void_p), ("voiced_prob", C.c_void_p), ("live_state", C.c_void_p)]
 
 
+class StreamCommit(C.Structure):
+    _fields_ = [("pitch_bin", C.c_void_p), ("cap", C.c_int64), ("first", C.c_int64), ("count", C.c_int64),
+                ("frontier", C.c_int64), ("walked", C.c_int64), ("walked_wide", C.c_int64)]
+
+
 class Outputs(C.Structure):
     _fields_ = [("f0", C.c_void_p), ("voiced_flag", C.c_void_p), ("voiced_prob", C.c_void_p),
                 ("rms", C.c_void_p), ("rake_mask", C.c_void_p), ("S_dB", C.c_void_p), ("pitch_bin", C.c_void_p), ("sdb_col_means", C.c_void_p)]
@@ -52,7 +57,7 @@ EXPORTS = ("aegis_abi_version", "aegis_create", "aegis_destroy", "aegis_last_err
            "aegis_debug_fetch", "aegis_set_profiling", "aegis_last_kernel_ms", "aegis_rake_patterns", "aegis_set_table", "aegis_last_kernel_launches", "aegis_trend", "aegis_ghost_rsi",
            "aegis_stream_open", "aegis_stream_push", "aegis_stream_close", "aegis_stream_free", "aegis_cqt", "aegis_cqt_device", "aegis_chroma_cqt",
            "aegis_extract_events", "aegis_render_smf", "aegis_events_last_error", "aegis_debug_plan",
-           "aegis_analyze_pcm", "aegis_pcm_samples_for", "aegis_resample_taps")
+           "aegis_analyze_pcm", "aegis_pcm_samples_for", "aegis_resample_taps", "aegis_stream_push_commit")
 
 _lib = None
 
@@ -107,6 +112,9 @@ def load():
     lib.aegis_stream_open.restype = C.c_int
     lib.aegis_stream_push.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(StreamFrames), C.POINTER(C.c_int64)]
     lib.aegis_stream_push.restype = C.c_int
+    lib.aegis_stream_push_commit.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(StreamFrames), C.POINTER(C.c_int64),
+                                             C.POINTER(StreamCommit)]
+    lib.aegis_stream_push_commit.restype = C.c_int
     lib.aegis_stream_close.argtypes = [C.c_void_p, C.c_double, C.POINTER(Outputs), C.POINTER(C.c_int64)]
     lib.aegis_stream_close.restype = C.c_int
     lib.aegis_stream_free.argtypes = [C.c_void_p]
@@ -513,8 +521,10 @@ class Handle:
                                               len(off) - 1, n_bins, bins_per_octave, float(fmin), float(filter_scale),
                                               C.c_void_p(int(d_out_ptr)), C.c_void_p(stream or 0), 1 if sync else 0))
 
-    def open_stream(self, max_seconds=600.0):
-        return Stream(self, int(max_seconds * self.sr))
+    def open_stream(self, max_seconds=600.0, commit=False, commit_cap=None):
+        """commit: push() also returns the frames whose decode is already final (Stream); commit_cap: room for them per
+        push (default: every frame of the stream)."""
+        return Stream(self, int(max_seconds * self.sr), commit=commit, commit_cap=commit_cap)
 
     def analyze_batch_device(self, d_pcm_ptr, sample_offsets, outputs, rake_sensitivity=0.6,
                              stages=STAGE_ALL, stream=None, sync=True):
@@ -543,9 +553,15 @@ def resample_taps(up, down):
 class Stream:
     """Incremental analysis of one clip (aegis_stream_*).  push() returns the frames that became complete:
     dict(rms, voiced_prob, live_state); close() returns the same dict analyze_batch() gives for the whole
-    signal (bit-identical)."""
+    signal (bit-identical).
 
-    def __init__(self, handle, max_samples):
+    With commit=True (aegis_stream_push_commit) push() returns two more keys: `committed` = dict(first, pitch_bin
+    int16[count]), the next frames whose pYIN decode is final (bin -1 = unvoiced, otherwise f0 = table("freqs")[bin]:
+    bit for bit what close() will return for them), consecutive from frame 0 over the pushes, and `frontier`, the last
+    frame delivered so far (-1: none).  close()[frontier + 1:] is the rest.  `last_walk` holds the number of frames
+    the last push walked back, `last_walk_wide` how many of them with more than 64 survivor paths alive."""
+
+    def __init__(self, handle, max_samples, commit=False, commit_cap=None):
         self.handle = handle
         self.lib = handle.lib
         s = C.c_void_p()
@@ -557,13 +573,27 @@ class Stream:
         self._live = np.empty(self._cap, np.int32)
         self._frames = StreamFrames(self._rms.ctypes.data, self._vp.ctypes.data, self._live.ctypes.data)
         self.n_bins = handle.param("n_pitch_bins")
+        self.commit = bool(commit)
+        self.last_walk = self.last_walk_wide = 0
+        if self.commit:
+            cap = self._cap if commit_cap is None else int(commit_cap)
+            self._bins = np.empty(max(cap, 1), np.int16)
+            self._commit = StreamCommit(self._bins.ctypes.data, cap, 0, 0, -1, 0, 0)
 
     def push(self, samples):
         x = np.ascontiguousarray(samples, dtype=np.float32)
         k = C.c_int64(0)
-        self.handle._check(self.lib.aegis_stream_push(self._s, x.ctypes.data, len(x), C.byref(self._frames), C.byref(k)))
+        if not self.commit:
+            self.handle._check(self.lib.aegis_stream_push(self._s, x.ctypes.data, len(x), C.byref(self._frames), C.byref(k)))
+            n = k.value
+            return {"rms": self._rms[:n].copy(), "voiced_prob": self._vp[:n].copy(), "live_state": self._live[:n].copy()}
+        c = self._commit
+        self.handle._check(self.lib.aegis_stream_push_commit(self._s, x.ctypes.data, len(x), C.byref(self._frames), C.byref(k),
+                                                             C.byref(c)))
         n = k.value
-        return {"rms": self._rms[:n].copy(), "voiced_prob": self._vp[:n].copy(), "live_state": self._live[:n].copy()}
+        self.last_walk, self.last_walk_wide = int(c.walked), int(c.walked_wide)
+        return {"rms": self._rms[:n].copy(), "voiced_prob": self._vp[:n].copy(), "live_state": self._live[:n].copy(),
+                "committed": {"first": int(c.first), "pitch_bin": self._bins[:c.count].copy()}, "frontier": int(c.frontier)}
 
     def close(self, rake_sensitivity=0.6, want_sdb=True):
         h = self.handle

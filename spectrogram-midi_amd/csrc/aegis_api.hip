@@ -125,13 +125,23 @@ struct aegis_stream {
     DevBuf o_f0, o_voiced, o_vprob, o_rms, o_rake, o_sdb;
     std::vector<int64_t> host_meta;
     // captured hipGraph of one fixed-size push (built lazily for the first push size that is a multiple of hop)
+    // ([0]: aegis_stream_push, [1]: aegis_stream_push_commit, the same chain with the commit kernel behind the Viterbi)
     DevBuf ctl, g_staging, g_result;
     float *pin_samples = nullptr;
     unsigned char *pin_result = nullptr;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t graph_exec = nullptr;
-    int64_t graph_push = 0;
+    hipGraph_t graph[2] = {nullptr, nullptr};
+    hipGraphExec_t graph_exec[2] = {nullptr, nullptr};
+    int64_t graph_push[2] = {0, 0};
     bool graph_failed = false;
+    // streaming commit (aegis_stream_push_commit): the device keeps the frontier in a StreamCommitCtl behind the StreamCtl
+    // of `ctl` and the decided bins in c_bins [cap_frames]; the host mirrors the frontier and counts what it handed out
+    DevBuf c_bins, c_result;
+    unsigned char *pin_commit = nullptr;               // kCommitResultBytes, pinned (the graph's second D2H copy)
+    unsigned char commit_host[kCommitResultBytes] = {};
+    int64_t c_frontier = -1;    // last decided frame on the device
+    int64_t c_newest = -1;      // newest frame the commit kernel has walked from
+    int64_t c_delivered = 0;    // frames handed to the caller so far
+    int64_t c_walked = 0, c_walked_wide = 0;    // frames the last commit launch walked, and how many of them as a bit mask
 };
 
 namespace {
@@ -1550,10 +1560,14 @@ static PassParams stream_params(aegis_stream *st, const int64_t *dm) {
 
 // Captures one fixed-size push as a hipGraph: H2D of the samples, advance (append + geometry), the four
 // analysis kernels reading their geometry from the device control block, result gather, D2H.
-static bool stream_build_graph(aegis_stream *st, int64_t n_push, hipStream_t s) {
+static StreamCommitCtl *stream_commit_ctl(aegis_stream *st) {
+    return reinterpret_cast<StreamCommitCtl *>(static_cast<unsigned char *>(st->ctl.p) + sizeof(StreamCtl));
+}
+
+static bool stream_build_graph(aegis_stream *st, int64_t n_push, hipStream_t s, int commit) {
     aegis_handle *h = st->h;
     const Tables &t = h->tab;
-    if (!st->pin_samples || !st->pin_result || n_push > 8192 || n_push % t.hop != 0 || n_push / t.hop + 1 > 8) return false;
+    if (!st->pin_samples || !st->pin_result || (commit && !st->pin_commit) || n_push > 8192 || n_push % t.hop != 0 || n_push / t.hop + 1 > 8) return false;
     StreamCtl *ctl = static_cast<StreamCtl *>(st->ctl.p);
     PassParams p = stream_params(st, ctl->meta);      // device address arithmetic only
     p.ctl = ctl;
@@ -1566,14 +1580,18 @@ static bool stream_build_graph(aegis_stream *st, int64_t n_push, hipStream_t s) 
     launch_frame(p, h->dt, s);
     launch_pyin_obs(p, h->dt, s);
     ok &= launch_viterbi(p, h->dt, t.log_trans_band.data(), s) == hipSuccess;
+    if (commit)
+        ok &= launch_stream_commit(ctl, 0, stream_commit_ctl(st), p.ptr, p.vstate, t.n_bins, static_cast<int16_t *>(st->c_bins.p),
+                                   st->c_result.p, s) == hipSuccess;
     launch_stream_gather(ctl, p.out_rms, p.out_vprob, p.live_states, st->g_result.p, s);
     ok &= hipMemcpyAsync(st->pin_result, st->g_result.p, 256, hipMemcpyDeviceToHost, s) == hipSuccess;
+    if (commit) ok &= hipMemcpyAsync(st->pin_commit, st->c_result.p, kCommitResultBytes, hipMemcpyDeviceToHost, s) == hipSuccess;
     hipGraph_t g = nullptr;
     ok &= hipStreamEndCapture(s, &g) == hipSuccess && g != nullptr;
     if (!ok) { if (g) (void)hipGraphDestroy(g); (void)hipGetLastError(); return false; }
     hipGraphExec_t ex = nullptr;
     if (hipGraphInstantiate(&ex, g, nullptr, nullptr, 0) != hipSuccess) { (void)hipGraphDestroy(g); (void)hipGetLastError(); return false; }
-    st->graph = g; st->graph_exec = ex; st->graph_push = n_push;
+    st->graph[commit] = g; st->graph_exec[commit] = ex; st->graph_push[commit] = n_push;
     return true;
 }
 
@@ -1612,11 +1630,14 @@ static int stream_run(aegis_stream *st, int64_t f_lo, int64_t f_hi, bool final_p
 // Releases everything a stream owns.  The caller holds h->mu, or the stream was never handed out.
 static void stream_release(aegis_stream *st) noexcept {
     if (st->h && st->h->device >= 0) { (void)hipSetDevice(st->h->device); (void)hipStreamSynchronize(st->h->stream); }
-    if (st->graph_exec) (void)hipGraphExecDestroy(st->graph_exec);
-    if (st->graph) (void)hipGraphDestroy(st->graph);
+    for (int k = 0; k < 2; ++k) {
+        if (st->graph_exec[k]) (void)hipGraphExecDestroy(st->graph_exec[k]);
+        if (st->graph[k]) (void)hipGraphDestroy(st->graph[k]);
+    }
     if (st->pin_samples) (void)hipHostFree(st->pin_samples);
     if (st->pin_result) (void)hipHostFree(st->pin_result);
-    for (DevBuf *b : {&st->ctl, &st->g_staging, &st->g_result, &st->pcm, &st->dfn, &st->logobs, &st->logunv, &st->obs_seg, &st->ptr, &st->cmap, &st->bnd, &st->states,
+    if (st->pin_commit) (void)hipHostFree(st->pin_commit);
+    for (DevBuf *b : {&st->c_bins, &st->c_result, &st->ctl, &st->g_staging, &st->g_result, &st->pcm, &st->dfn, &st->logobs, &st->logunv, &st->obs_seg, &st->ptr, &st->cmap, &st->bnd, &st->states,
                       &st->live, &st->melpow, &st->clipmax, &st->rake_raw, &st->vstate, &st->meta, &st->o_f0, &st->o_voiced,
                       &st->o_vprob, &st->o_rms, &st->o_rake, &st->o_sdb})
         free_buf(*b);
@@ -1637,20 +1658,31 @@ static int stream_open_locked(aegis_handle *h, int64_t max_samples, aegis_stream
     need(st->logobs, F * h->obs_stride * 8); need(st->logunv, F * 8); need(st->obs_seg, F * 4); need(st->ptr, F * S * 2);
     need(st->cmap, nch * S * 2); need(st->bnd, nch * 4); need(st->states, F * 4); need(st->live, F * 4);
     need(st->melpow, F * t.n_mels * 4); need(st->clipmax, 16); need(st->rake_raw, F); need(st->vstate, S * 8);
-    need(st->meta, 9 * 8); need(st->ctl, sizeof(StreamCtl)); need(st->g_staging, 8192 * 4); need(st->g_result, 256);
+    need(st->meta, 9 * 8); need(st->ctl, sizeof(StreamCtl) + sizeof(StreamCommitCtl)); need(st->g_staging, 8192 * 4); need(st->g_result, 256);
+    need(st->c_bins, F * 2); need(st->c_result, kCommitResultBytes);
     need(st->o_f0, F * 8); need(st->o_voiced, F); need(st->o_vprob, F * 8); need(st->o_rms, F * 4); need(st->o_rake, F);
     need(st->o_sdb, F * t.n_mels * 4);
     if (rc != AEGIS_OK) return rc;
     HIPCHK(h, hipMemsetAsync(st->clipmax.p, 0, 16, h->stream));
+    // The band Viterbi leaves the back-pointer of a dead voiced state unwritten, and a launch that starts inside a 16-step
+    // chunk (any push that is not a whole number of chunks) walks the rows of the chunk's earlier steps for EVERY state to
+    // rebuild its chunk map (viterbi_band.inc, "rebuilds org from the HBM pointers").  What it reads for a dead state is
+    // never used, but it is used as the next index: with recycled memory behind the rows an index up to 65535 reaches
+    // 128 KB past a short stream's last row (an illegal access on a 0.5 s stream, met in the test suite).  Zeroed rows keep
+    // every such index at state 0.
+    HIPCHK(h, hipMemsetAsync(st->ptr.p, 0, (size_t)F * S * 2, h->stream));
     {
-        StreamCtl c0{};
-        c0.meta[3] = st->cap_frames;
-        c0.meta[7] = (st->cap_frames - 1 + kViterbiChunk - 1) / kViterbiChunk;
+        struct { StreamCtl ctl; StreamCommitCtl commit; } c0{};
+        static_assert(sizeof(c0) == sizeof(StreamCtl) + sizeof(StreamCommitCtl), "the commit block sits right behind the control block");
+        c0.ctl.meta[3] = st->cap_frames;
+        c0.ctl.meta[7] = (st->cap_frames - 1 + kViterbiChunk - 1) / kViterbiChunk;
+        c0.commit.frontier = -1; c0.commit.newest = -1;
         HIPCHK(h, hipMemcpyAsync(st->ctl.p, &c0, sizeof(c0), hipMemcpyHostToDevice, h->stream));
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (hipHostMalloc(reinterpret_cast<void **>(&st->pin_samples), 8192 * 4, hipHostMallocDefault) != hipSuccess) st->pin_samples = nullptr;
     if (hipHostMalloc(reinterpret_cast<void **>(&st->pin_result), 256, hipHostMallocDefault) != hipSuccess) st->pin_result = nullptr;
+    if (hipHostMalloc(reinterpret_cast<void **>(&st->pin_commit), kCommitResultBytes, hipHostMallocDefault) != hipSuccess) st->pin_commit = nullptr;
     // AEGIS_STREAM_GRAPH=0 keeps every push on the plain-launch path, =1 allows the hipGraph replay.  Unset: the replay,
     // except under an injected rocprofiler tool -- round 1's SIGSEGV in aegis_stream_push (profiles/
     // r1_stream_push_sigsegv_symbolised.txt) was the profiler-side packet copy of an INTERCEPTED queue running off the end
@@ -1700,24 +1732,63 @@ void aegis_stream_free(aegis_stream *st) {
     if (last) destroy_now(h);     // aegis_destroy() was called while this stream was still open
 }
 
-int aegis_stream_push(aegis_stream *st, const float *samples, int64_t n, aegis_stream_frames *out, int64_t *n_frames) {
-    try {
-    if (!st || !st->h) return AEGIS_ERR_INVALID;
+// The host's half of a commit push, after the stream has drained: `res` is the commit kernel's result block (nullptr: no
+// launch was needed, the device frontier is where it was).  Hands out the next decided frames, `cap` at most.
+static int stream_deliver(aegis_stream *st, const unsigned char *res, aegis_stream_commit *commit) {
     aegis_handle *h = st->h;
-    std::lock_guard<std::mutex> lock(h->mu);
+    int64_t staged_lo = -1;
+    if (res) {
+        int64_t r[4];
+        std::memcpy(r, res, 32);
+        if (r[3] < 0) { h->err = "stream commit: the walk met a back-pointer the Viterbi never wrote"; return AEGIS_ERR_DEVICE; }
+        if (r[0] != st->c_frontier || r[1] < r[0] || r[1] >= st->frames_done) {
+            h->err = "stream commit: device and host disagree on the frontier"; return AEGIS_ERR_DEVICE;
+        }
+        staged_lo = r[0] + 1;
+        st->c_frontier = r[1];
+        st->c_walked = r[3] & 0xffffffff;
+        st->c_walked_wide = r[3] >> 32;
+        st->c_newest = st->frames_done - 1;
+    } else {
+        st->c_walked = st->c_walked_wide = 0;
+    }
+    const int64_t first = st->c_delivered;
+    const int64_t k = std::min<int64_t>(st->c_frontier + 1 - first, commit->cap);
+    if (k > 0) {
+        if (staged_lo >= 0 && first >= staged_lo && first + k <= staged_lo + kCommitStage)
+            std::memcpy(commit->pitch_bin, res + 32 + 2 * (first - staged_lo), (size_t)k * 2);
+        else
+            HIPCHK(h, hipMemcpy(commit->pitch_bin, static_cast<int16_t *>(st->c_bins.p) + first, (size_t)k * 2, hipMemcpyDeviceToHost));
+        st->c_delivered += k;
+    }
+    commit->first = first;
+    commit->count = k > 0 ? k : 0;
+    commit->frontier = st->c_delivered - 1;
+    commit->walked = st->c_walked;
+    commit->walked_wide = st->c_walked_wide;
+    return AEGIS_OK;
+}
+
+// aegis_stream_push (commit == nullptr: exactly the launches of a stream without the commit) and aegis_stream_push_commit.
+// The caller holds h->mu.
+static int stream_push_locked(aegis_stream *st, const float *samples, int64_t n, aegis_stream_frames *out, int64_t *n_frames,
+                              aegis_stream_commit *commit) {
+    aegis_handle *h = st->h;
     if (h->destroy_requested) { h->err = "handle was destroyed"; return AEGIS_ERR_INVALID; }
     if (n < 0 || (n > 0 && !samples) || !n_frames) { h->err = "bad argument"; return AEGIS_ERR_INVALID; }
+    if (commit && (commit->cap < 0 || (commit->cap > 0 && !commit->pitch_bin))) { h->err = "bad argument"; return AEGIS_ERR_INVALID; }
     if (st->closed) { h->err = "stream is closed"; return AEGIS_ERR_INVALID; }
     if (st->n_samples + n > st->cap_samples) { h->err = "stream capacity exceeded"; return AEGIS_ERR_INVALID; }
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
+    const int ci = commit ? 1 : 0;
     // ---- fixed-size pushes replay a captured hipGraph ---------------------------------------------
     const bool eligible = n > 0 && n <= 8192 && n % h->tab.hop == 0 && n / h->tab.hop + 1 <= 8;
-    if (eligible && !st->graph_failed && (st->graph_exec == nullptr || st->graph_push == n)) {
-        if (st->graph_exec == nullptr && !stream_build_graph(st, n, s)) st->graph_failed = true;
-        if (st->graph_exec != nullptr && st->graph_push == n) {
+    if (eligible && !st->graph_failed && (st->graph_exec[ci] == nullptr || st->graph_push[ci] == n)) {
+        if (st->graph_exec[ci] == nullptr && !stream_build_graph(st, n, s, ci)) st->graph_failed = true;
+        if (st->graph_exec[ci] != nullptr && st->graph_push[ci] == n) {
             std::memcpy(st->pin_samples, samples, (size_t)n * 4);
-            HIPCHK(h, hipGraphLaunch(st->graph_exec, s));
+            HIPCHK(h, hipGraphLaunch(st->graph_exec[ci], s));
             HIPCHK(h, hipStreamSynchronize(s));
             st->n_samples += n;
             const int64_t ready = st->n_samples >= kFrameLength / 2 ? (st->n_samples - kFrameLength / 2) / h->tab.hop + 1 : 0;
@@ -1732,7 +1803,7 @@ int aegis_stream_push(aegis_stream *st, const float *samples, int64_t n, aegis_s
                 if (out->voiced_prob) std::memcpy(out->voiced_prob, st->pin_result + 8 + 32, (size_t)got * 8);
                 if (out->live_state) std::memcpy(out->live_state, st->pin_result + 8 + 32 + 64, (size_t)got * 4);
             }
-            return AEGIS_OK;
+            return commit ? stream_deliver(st, st->pin_commit, commit) : AEGIS_OK;
         }
     }
     if (n > 0)
@@ -1758,8 +1829,35 @@ int aegis_stream_push(aegis_stream *st, const float *samples, int64_t n, aegis_s
         const int64_t counters[2] = {st->n_samples, st->frames_done};
         HIPCHK(h, hipMemcpyAsync(st->ctl.p, counters, 16, hipMemcpyHostToDevice, s));
     }
+    // commit: one more launch behind the Viterbi, when there is a frame the last walk has not seen (also the frames of
+    // earlier plain pushes: the walk goes from the newest frame back to the frontier, however far that is)
+    unsigned char *cres = nullptr;
+    if (commit && st->frames_done > 0 && st->frames_done - 1 != st->c_newest) {
+        cres = st->pin_commit ? st->pin_commit : st->commit_host;
+        hipError_t ce = launch_stream_commit(nullptr, st->frames_done, stream_commit_ctl(st), static_cast<const uint16_t *>(st->ptr.p),
+                                             static_cast<const double *>(st->vstate.p), h->tab.n_bins, static_cast<int16_t *>(st->c_bins.p),
+                                             st->c_result.p, s);
+        if (ce != hipSuccess) { h->err = std::string("stream commit launch: ") + hipGetErrorString(ce); return AEGIS_ERR_DEVICE; }
+        HIPCHK(h, hipMemcpyAsync(cres, st->c_result.p, kCommitResultBytes, hipMemcpyDeviceToHost, s));
+    }
     HIPCHK(h, hipStreamSynchronize(s));
-    return AEGIS_OK;
+    return commit ? stream_deliver(st, cres, commit) : AEGIS_OK;
+}
+
+int aegis_stream_push(aegis_stream *st, const float *samples, int64_t n, aegis_stream_frames *out, int64_t *n_frames) {
+    try {
+    if (!st || !st->h) return AEGIS_ERR_INVALID;
+    std::lock_guard<std::mutex> lock(st->h->mu);
+    return stream_push_locked(st, samples, n, out, n_frames, nullptr);
+    } catch (...) { return abi_fail((st ? st->h : nullptr)); }
+}
+
+int aegis_stream_push_commit(aegis_stream *st, const float *samples, int64_t n, aegis_stream_frames *out, int64_t *n_frames,
+                             aegis_stream_commit *commit) {
+    try {
+    if (!st || !st->h) return AEGIS_ERR_INVALID;
+    std::lock_guard<std::mutex> lock(st->h->mu);
+    return stream_push_locked(st, samples, n, out, n_frames, commit);
     } catch (...) { return abi_fail((st ? st->h : nullptr)); }
 }
 

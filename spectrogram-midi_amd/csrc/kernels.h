@@ -42,7 +42,15 @@ struct StreamCtl {
     int64_t meta[9];          // sample_off[2] | frame_off[2] | sel_off[2] | chunk_off[2] | order
 };
 
-// Geometry shared by all kernels of one pass.
+// Device state of the streaming commit (aegis_stream_push_commit; stream_commit.hip), kept behind the stream's StreamCtl
+// so that a graph replay needs no new kernel arguments.
+struct StreamCommitCtl {
+    int64_t frontier;         // last frame of the decided prefix, -1 before the first
+    int64_t newest;           // the newest frame the last walk started from, -1 before the first
+};
+constexpr int kCommitStage = 240;          // decided bins a launch also leaves in its result block (the rest stay in `bins`)
+constexpr int kCommitResultBytes = 32 + 2 * kCommitStage;
+
 struct PassParams {
     // configuration
     int32_t sr, hop, n_mels;
@@ -182,6 +190,15 @@ void launch_rake_from_db(const float *sdb, int n_mels, int64_t F, double ratio, 
 void launch_stream_advance(StreamCtl *ctl, const float *staging, int n_push, float *pcm, int hop, hipStream_t s);
 void launch_stream_gather(const StreamCtl *ctl, const float *rms, const double *vprob, const int32_t *live, void *result,
                           hipStream_t s);
+// Streaming commit, one workgroup behind the Viterbi of a push: walks the ancestor sets of the states alive at the newest
+// frame (ctl->frames_done - 1, or frames_done - 1 without ctl) back to cc->frontier, advances the frontier over the
+// frames every ancestor agrees on and writes their pitch bins (-1 unvoiced) to bins[frame].  bins[] beyond the frontier
+// is the walk's scratch row.  result (kCommitResultBytes): int64 frontier before | after | newest frame |
+// frames walked + (frames of them stepped with the whole workgroup << 32) (-1: the walk met an out-of-range back-pointer
+// and left the frontier alone), then the bins of the
+// first kCommitStage newly decided frames.
+hipError_t launch_stream_commit(const StreamCtl *ctl, int64_t frames_done, StreamCommitCtl *cc, const uint16_t *ptr,
+                                const double *vstate, int n_bins, int16_t *bins, void *result, hipStream_t s);
 hipError_t obs_debug_fetch(long long *dst);                  // pyin_obs_kernel section cycles (AEGIS_ABLATE&256)
 hipError_t frame_debug_fetch(long long *dst);                // frame_yin_kernel section cycles (AEGIS_ABLATE&128)
 hipError_t viterbi_debug_fetch(long long *dst, bool reset);   // per-wave section cycles (zeros unless AEGIS_ABLATE&64)

@@ -170,6 +170,12 @@ class AegisEngine:
                           "voiced_probs": r["voiced_prob"], "rms": r["rms"], "y": r["y"]}
         return (results, bufs, off, live) if _concatenated else results
 
+    def open_stream(self, max_seconds=600.0, rake_sensitivity=0.6):
+        """Incremental audio_to_midi of one live signal (not a reference method: the reference analyses whole files):
+        an EngineStream whose push(samples) returns the frames whose pitch decode is already final and whose close()
+        returns the raw_data dict audio_to_midi gives for the whole signal."""
+        return EngineStream(self, max_seconds, rake_sensitivity)
+
     def audio_to_midi_files(self, paths, want_midi=True, **kwargs):
         """audio_to_midi_batch for a folder of WAV files decoded on the GPU (analyze_files): the same triple.  kwargs as
         for audio_to_midi_batch, plus start_time / end_time and want_y."""
@@ -273,3 +279,59 @@ class AegisEngine:
         parts = h.analyze_batch([y[a:b] for a, b in self._turbo_spans(len(y))], stages=_lib.STAGE_PYIN)
         return (np.concatenate([p["f0"] for p in parts]), np.concatenate([p["voiced_flag"] for p in parts]),
                 np.concatenate([p["voiced_prob"] for p in parts]))
+
+
+class EngineStream:
+    """One live signal fed to the engine in pieces (AegisEngine.open_stream; aegis_stream_push_commit underneath).
+
+    push(samples) -> dict(start, f0, voiced_flag, voiced_probs, rms): the next frames whose pYIN decode is FINAL, in
+    the reference's dtypes and conventions (f0 float64 with 0.0 where unvoiced, as audio_to_midi returns it after
+    np.nan_to_num; voiced_flag bool; voiced_probs float64; rms float32); `start` is the index of the first of them.
+    The frames of successive pushes are consecutive from frame 0 and are bit for bit what close() returns at those
+    indices; how far they trail the audio depends on the material.  close() -> the raw_data
+    dict of audio_to_midi for everything pushed (None if nothing was); its arrays from the last delivered frame on
+    complete the pushes' arrays.
+
+    Note events per push are out of scope: get_midi_events gates on amplitude_to_db(rms, ref=np.max) over the whole
+    clip, so an event list cannot be final before the clip's loudest frame is known.  Run extract_events on close()'s
+    dict."""
+
+    def __init__(self, engine, max_seconds=600.0, rake_sensitivity=0.6):
+        self.engine = engine
+        self.rake_sensitivity = rake_sensitivity
+        h = engine.handle
+        self._stream = h.open_stream(max_seconds, commit=True)
+        self._freqs = h.table("freqs")
+        self._rms, self._vp, self._y = [], [], []      # per-push arrays received so far (final when produced)
+        self._kept = 0                                  # index of the first frame still in _rms / _vp
+        self.frontier = -1
+
+    def push(self, samples):
+        x = np.ascontiguousarray(samples, dtype=np.float32)
+        got = self._stream.push(x)
+        self._y.append(x.copy())
+        self._rms.append(got["rms"])
+        self._vp.append(got["voiced_prob"])
+        bins = got["committed"]["pitch_bin"]
+        start, n = got["committed"]["first"], len(bins)
+        self.frontier = got["frontier"]
+        rms, vp = np.concatenate(self._rms), np.concatenate(self._vp)
+        a = start - self._kept
+        out = {"start": start, "f0": np.where(bins >= 0, self._freqs[np.maximum(bins, 0)], 0.0),
+               "voiced_flag": bins >= 0, "voiced_probs": vp[a:a + n].copy(), "rms": rms[a:a + n].copy()}
+        self._rms, self._vp, self._kept = [rms[a + n:]], [vp[a + n:]], start + n
+        return out
+
+    def close(self):
+        st, self._stream = self._stream, None
+        if st is None:
+            raise ValueError("stream is closed")
+        try:
+            y = np.concatenate(self._y) if self._y else np.zeros(0, np.float32)
+            if len(y) == 0:
+                return None                               # audio_to_midi's answer for empty audio
+            r = st.close(rake_sensitivity=self.rake_sensitivity, want_sdb=False)
+        finally:
+            st.free()
+        return {"rake_mask": r["rake_mask"], "f0": np.nan_to_num(r["f0"]), "voiced_flag": r["voiced_flag"],
+                "voiced_probs": r["voiced_prob"], "rms": r["rms"], "y": y}
