@@ -1,491 +1,82 @@
-// C ABI of libaegis_hip.so (see include/aegis_hip.h).  Host-side orchestration:
-// table upload, workspace management, kernel launches of the passes plan.cpp plans
-// on one HIP stream per handle, optional hipEvent timing per kernel.
-#include <hip/hip_runtime.h>
+// The batch pipeline behind the C ABI of libaegis_hip.so (include/aegis_hip.h; aegis_internal.h lists the files of the
+// other entries).  Host-side orchestration: workspace management, kernel launches of the passes plan.cpp plans on the
+// handle's streams, optional hipEvent timing per kernel, the recovery policy, the three analyze entries.
+#include "aegis_internal.h"
 
-#include <algorithm>
-#include <chrono>
 #include <climits>
 #include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <limits>
-#include <map>
-#include <mutex>
-#include <new>
 #include <numeric>
-#include <functional>
-#include <stdexcept>
-#include <string>
-#include <thread>
-#include <vector>
 
-#include "../../include/aegis_hip.h"
-#include "kernels.h"
-#include "plan.h"
-#include "cqt.h"
 #include "pcm.h"
-#include "tables.h"
-#include "trend.h"
 
 using namespace aegis;
 
-namespace {
-
-std::string g_create_error;
-
-struct DevBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-};
-
-}  // namespace
-
-struct aegis_handle {
-    Tables tab;
-    DevTables dt{};
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipStream_t stream2 = nullptr;            // Viterbi stream of the time-chunked pipeline
-    bool troughs_off = false;                 // AEGIS_TROUGHS_IN_FRAME=0 at create
-    bool cmnd_off = false;                    // AEGIS_CMND_IN_FRAME=0 at create: pyin_obs_kernel walks the CMND cumsum (tests compare the two paths)
-    bool debug_stages = false;                // AEGIS_DEBUG_STAGES=1 at create: pyin_obs also writes the CMND rows ("yin") for the stage tests
-    hipStream_t stream4 = nullptr;            // second frame-stage stream: odd time chunks (their FFTs overlap the even chunks' YIN / observation kernels)
-    hipStream_t stream3 = nullptr;            // host->device sample copies of aegis_analyze_batch, chunk by chunk
-    // CU-partitioned stream sets of the pipeline (split_streams): [0] Viterbi on 64 CUs / frame stage on 192, [1] 128 / 128
-    struct SplitSet { hipStream_t frame_a = nullptr, frame_b = nullptr, viterbi = nullptr; bool tried = false; } split[2];
-    int n_cus = 0;                            // compute units of the device (CU masks are built for this count)
-    hipEvent_t copy_event = nullptr;
-    std::vector<hipEvent_t> sync_events;      // cross-stream dependencies (no timing)
-    int64_t max_frames_per_pass = 0;
-    int fail_allocs = 0;                             // test hook: workspace growths left to fail with AEGIS_ERR_NOMEM
-    mutable std::string err;
-    std::vector<void *> table_allocs;
-    // workspaces (grow-only): passes alternate between the two, so that the frame stage of one pass runs under the
-    // Viterbi of the previous one
-    struct Work {
-        DevBuf dfn, yin, logobs, logunv, obs_seg, ptr, cmap, chunk_off, bnd, states, melpow, clipmax, rake_raw;
-        DevBuf sample_off, sample_len, out_off, frame_off, order, sel_off, vstate, chunk_lo, chunk_flag, clip_tb;
-        DevBuf seg64, seg32, seg_col, seg_map, seg_i32, colhist, colG, colkg, clip_flag, flag_order, tube_buf, tube_at, tube_count;    // time-split passes
-    } work[2];
-    DevBuf vstats, rk_raw, abort_flag, finite_flag;
-    uint32_t chunk_gen = 0;                   // generation of the chunk flags of a persistent Viterbi launch
-    int test_drop_signal = -1;
-    bool persist_gave_up = false;
-    int persist_cooldown = 0;                 // calls left on the one-launch-per-chunk schedule after a give-up; then the single launch is tried again
-    int64_t persistent_fallbacks = 0;         // calls repeated with one launch per chunk (aegis_debug_fetch "persistent_fallbacks")
-    bool persist_pending = false;             // a persistent launch ran since the abort flag was last read
-    bool persistent = true;                   // one Viterbi launch per balanced pass now (false for persist_cooldown calls after a give-up)
-    PlanKnobs knobs;                          // scheduling knobs (plan.h), read from the environment at create
-    CqtBank cqt_bank;
-    DevBuf q_pcm, q_soff, q_foff, q_toff, q_out, q_chroma, q_cls;
-    DevBuf t_x, t_off, t_a, t_b, t_c, t_d, t_e, t_i8, t_i64a, t_i64b;   // trend-filter staging
-    DevBuf t_pa;                              // scratch of the fused pitch analysis: 12 rows of doubles + 1 of bytes
-    DevBuf io_pcm, io_f0, io_voiced, io_vprob, io_rms, io_rake, io_sdb, io_bin, io_colmean;
-    DevBuf pcm_raw, pcm_clips, pcm_ranges, pcm_taps;   // aegis_analyze_pcm: raw bytes, clip table, per-chunk range tables, filters
-    int32_t lag_stride = 0, yin_stride = 0, obs_stride = 0;
-    CallPlan plan;                            // the last call's plan: its host arrays stay alive until the stream drained
-    bool plan_in_flight = false;              // the stream may still read them
-    struct SplitCheck { int pass; PassParams p; };
-    hipEvent_t split_ev[2] = {nullptr, nullptr};   // around an automatic split call's Viterbi kernels: the planning rule checks its estimate against them
-    hipEvent_t hyb_ev[3] = {nullptr, nullptr, nullptr};
-    hipEvent_t fin_ev[2] = {nullptr, nullptr};       // fork / join of a split pass's two finishing streams (launch_viterbi_split)
-    int split_bad = 0;                        // automatic split calls in a row that did not pay (two of them start the cool-down)
-    int split_cooldown = 0;                   // automatic mode: calls left without time-split passes after one that did not pay (clips redone sequentially)
-    std::vector<SplitCheck> split_checks;     // split passes of the call in flight whose clip flags have not been read
-    int64_t split_stats[4] = {0, 0, 0, 0};    // since create: split passes, segments, clips flagged for the sequential kernel, lock-on runs that never locked
-    double last_split_viterbi_ms = 0.0;      // measured Viterbi time of the call's last automatic split pass
-    int64_t last_carried_steps = 0;          // rounds of second speculation (viterbi_band.inc, phases 3 / 4) that had work in the call's last split pass
-    std::vector<int64_t> last_split_flags;   // per clip of the call's last split pass (pass order: longest first): the verification's verdict bits
-    // profiling
-    bool profiling = false;
-    std::vector<std::pair<std::string, std::pair<hipEvent_t, hipEvent_t>>> events;
-    std::map<std::string, double> last_ms;
-    std::map<std::string, int> last_count;
-    std::mutex mu;                            // one analyze call at a time per handle (server.py shares an engine)
-    // open aegis_stream objects keep the handle alive: aegis_destroy() with streams still open only marks the handle,
-    // the last aegis_stream_free() tears it down (either order of the two calls is safe)
-    int open_streams = 0;
-    bool destroy_requested = false;
-};
-
-// One clip fed incrementally (aegis_stream_*): its own PCM buffer and workspace, so batch calls on
-// the same handle may interleave.  Frames are analysed as soon as their 2048-sample window is
-// complete; the Viterbi column is carried across pushes exactly as the offline pipeline carries it
-// across time chunks, so aegis_stream_close() returns what aegis_analyze_batch() returns.
-struct aegis_stream {
-    aegis_handle *h = nullptr;
-    int64_t cap_samples = 0, cap_frames = 0;
-    int64_t n_samples = 0;      // samples received
-    int64_t frames_done = 0;    // frames analysed (= Viterbi columns produced)
-    bool closed = false;
-    DevBuf pcm, dfn, logobs, logunv, obs_seg, ptr, cmap, bnd, states, live, melpow, clipmax, rake_raw, vstate, meta;
-    DevBuf o_f0, o_voiced, o_vprob, o_rms, o_rake, o_sdb;
-    std::vector<int64_t> host_meta;
-    // captured hipGraph of one fixed-size push (built lazily for the first push size that is a multiple of hop)
-    // ([0]: aegis_stream_push, [1]: aegis_stream_push_commit, the same chain with the commit kernel behind the Viterbi)
-    DevBuf ctl, g_staging, g_result;
-    float *pin_samples = nullptr;
-    unsigned char *pin_result = nullptr;
-    hipGraph_t graph[2] = {nullptr, nullptr};
-    hipGraphExec_t graph_exec[2] = {nullptr, nullptr};
-    int64_t graph_push[2] = {0, 0};
-    bool graph_failed = false;
-    // streaming commit (aegis_stream_push_commit): the device keeps the frontier in a StreamCommitCtl behind the StreamCtl
-    // of `ctl` and the decided bins in c_bins [cap_frames]; the host mirrors the frontier and counts what it handed out
-    DevBuf c_bins, c_result;
-    unsigned char *pin_commit = nullptr;               // kCommitResultBytes, pinned (the graph's second D2H copy)
-    unsigned char commit_host[kCommitResultBytes] = {};
-    int64_t c_frontier = -1;    // last decided frame on the device
-    int64_t c_newest = -1;      // newest frame the commit kernel has walked from
-    int64_t c_delivered = 0;    // frames handed to the caller so far
-    int64_t c_walked = 0, c_walked_wide = 0;    // frames the last commit launch walked, and how many of them as a bit mask
-};
-
-namespace {
-
-#define HIPCHK(h, expr)                                                                         \
-    do {                                                                                        \
-        hipError_t e__ = (expr);                                                                \
-        if (e__ != hipSuccess) {                                                                \
-            (h)->err = std::string(#expr) + ": " + hipGetErrorString(e__);                      \
-            return AEGIS_ERR_DEVICE;                                                            \
-        }                                                                                       \
-    } while (0)
-
-int ensure(aegis_handle *h, DevBuf &b, size_t bytes) {
-    if (bytes <= b.cap) return AEGIS_OK;
-    if (h->fail_allocs > 0) {                        // test hook (aegis_debug_fetch "fail_allocs"): the next growths fail as hipMalloc would
-        --h->fail_allocs;
-        h->err = "hipMalloc(" + std::to_string(bytes) + " bytes): out of memory (test hook)";
-        return AEGIS_ERR_NOMEM;
-    }
-    if (b.p) {
-        HIPCHK(h, hipDeviceSynchronize());          // kernels on any of the pipeline's streams may still use the old block
-        HIPCHK(h, hipFree(b.p));
-        b.p = nullptr; b.cap = 0;
-    }
-    const size_t want = bytes + bytes / 8 + 256;
-    hipError_t e = hipMalloc(&b.p, want);
-    if (e != hipSuccess) {
-        b.p = nullptr;
-        h->err = "hipMalloc(" + std::to_string(want) + " bytes): " + hipGetErrorString(e);
-        return AEGIS_ERR_NOMEM;
-    }
-    b.cap = want;
-    return AEGIS_OK;
+RakeBounds aegis::rake_frame_bounds(const Tables &t) {
+    const double ms_per_frame = ((double)t.hop / (double)t.sr) * 1000;      // vision.py:23-25
+    return {(int)(10 / ms_per_frame), (int)(30 / ms_per_frame)};
 }
 
-template <typename T>
-int upload_table(aegis_handle *h, const std::vector<T> &v, const T **dst) {
-    void *d = nullptr;
-    const size_t bytes = std::max<size_t>(v.size() * sizeof(T), 16);
-    HIPCHK(h, hipMalloc(&d, bytes));
-    h->table_allocs.push_back(d);
-    if (!v.empty()) HIPCHK(h, hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    *dst = static_cast<const T *>(d);
-    return AEGIS_OK;
-}
-
-PassParams base_params(const Tables &t) {
+PassParams aegis::base_params(const Tables &t) {
     PassParams p{};
     p.sr = t.sr; p.hop = t.hop; p.n_mels = t.n_mels;
     p.min_period = t.min_period; p.max_period = t.max_period; p.n_lags = t.n_lags;
     p.n_bins = t.n_bins; p.half_width = t.half_width; p.width = t.width; p.n_cls = t.n_cls;
     p.f0_unvoiced = NAN;
     p.fmin = t.fmin; p.log_tiny = t.log_tiny; p.log_pinit_v = t.log_pinit[0]; p.log_pinit_u = t.log_pinit[1];
+    const RakeBounds rb = rake_frame_bounds(t);
+    p.rake_min_frames = rb.min_frames; p.rake_max_frames = rb.max_frames;
     return p;
 }
 
 // The frame kernel's epilogue forms the CMND unless the stage tests want the difference function and the CMND as separate
 // buffers (AEGIS_DEBUG_STAGES=1), AEGIS_CMND_IN_FRAME=0 was set when the handle was created, or the lag range does not fit
 // its LDS.
-int cmnd_in_frame(const aegis_handle *h) {
+int aegis::cmnd_in_frame(const aegis_handle *h) {
     return (!h->cmnd_off && !h->debug_stages && frame_cmnd_supported(h->tab.max_period)) ? 1 : 0;
 }
 // ... and finds the CMND's troughs there as well (AEGIS_TROUGHS_IN_FRAME=0 at create: pyin_obs_kernel loads the CMND row and
 // finds them, the round-3 path; tests compare the two)
-int troughs_in_frame(const aegis_handle *h) { return (cmnd_in_frame(h) && !h->troughs_off) ? 1 : 0; }
+int aegis::troughs_in_frame(const aegis_handle *h) { return (cmnd_in_frame(h) && !h->troughs_off) ? 1 : 0; }
 
-void free_buf(DevBuf &b) {
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr; b.cap = 0;
-}
+// (in the order the host-fed entries size, bind and copy them back)
+const OutField aegis::kOutFields[8] = {
+    {AEGIS_STAGE_PYIN, 8, false, offsetof(aegis_outputs, f0), &aegis_handle::io_f0, &aegis_stream::o_f0},
+    {AEGIS_STAGE_PYIN, 1, false, offsetof(aegis_outputs, voiced_flag), &aegis_handle::io_voiced, &aegis_stream::o_voiced},
+    {AEGIS_STAGE_MEL, 12, false, offsetof(aegis_outputs, sdb_col_means), &aegis_handle::io_colmean, nullptr},
+    {AEGIS_STAGE_PYIN, 2, false, offsetof(aegis_outputs, pitch_bin), &aegis_handle::io_bin, nullptr},
+    {AEGIS_STAGE_PYIN, 8, false, offsetof(aegis_outputs, voiced_prob), &aegis_handle::io_vprob, &aegis_stream::o_vprob},
+    {AEGIS_STAGE_RMS, 4, false, offsetof(aegis_outputs, rms), &aegis_handle::io_rms, &aegis_stream::o_rms},
+    {AEGIS_STAGE_RAKE, 1, false, offsetof(aegis_outputs, rake_mask), &aegis_handle::io_rake, &aegis_stream::o_rake},
+    {AEGIS_STAGE_MEL, 4, true, offsetof(aegis_outputs, S_dB), &aegis_handle::io_sdb, &aegis_stream::o_sdb},
+};
 
-void begin_event(aegis_handle *h, const char *name, hipStream_t s) {
-    if (!h->profiling) return;
-    hipEvent_t a, b;
-    if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) return;
-    (void)hipEventRecord(a, s);
-    h->events.push_back({name, {a, b}});
-}
-void end_event(aegis_handle *h, hipStream_t s) {
-    if (!h->profiling || h->events.empty()) return;
-    (void)hipEventRecord(h->events.back().second.second, s);
-}
-void collect_events(aegis_handle *h) {
-    h->last_ms.clear();
-    h->last_count.clear();
-    double total = 0;
-    for (auto &ev : h->events) {
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, ev.second.first, ev.second.second) == hipSuccess) {
-            h->last_ms[ev.first] += ms;
-            h->last_count[ev.first] += 1;
-            total += ms;
-        }
-        (void)hipEventDestroy(ev.second.first);
-        (void)hipEventDestroy(ev.second.second);
-    }
-    h->events.clear();
-    h->last_ms["total"] = total;
-}
-
-// Nothing is thrown across the C boundary (include/aegis_hip.h): every exported entry runs its body inside
-// try { ... } catch (...) { return abi_fail(h); }, which maps the in-flight exception to a return code.
-int abi_fail(aegis_handle *h) noexcept {
-    int code = AEGIS_ERR_DEVICE;
-    const char *msg = "unknown C++ exception";
-    std::string what;
-    try { throw; }
-    catch (const std::bad_alloc &) { code = AEGIS_ERR_NOMEM; msg = "out of host memory"; }
-    catch (const std::length_error &) { code = AEGIS_ERR_NOMEM; msg = "request too large for a host container"; }
-    catch (const std::exception &e) { try { what = e.what(); msg = what.c_str(); } catch (...) {} }
-    catch (...) {}
-    try { (h ? h->err : g_create_error) = msg; } catch (...) {}
-    return code;
+// What the planner needs to know about a call.  masked: whether a CU-masked stream set exists for n clips (the executor
+// creates them through split_streams; aegis_debug_plan only asks whether they would be laid out).
+PlanInput aegis::plan_input(aegis_handle *h, const int64_t *sample_offsets, int32_t n_clips, uint32_t stages, bool feed,
+                            bool caller_stream, int32_t sync, int n_cus, std::function<bool(int)> masked) {
+    const Tables &t = h->tab;
+    PlanInput in;
+    in.sample_offsets.assign(sample_offsets, sample_offsets + n_clips + 1);
+    in.max_frames_per_pass = h->max_frames_per_pass;
+    in.n_cus = n_cus; in.hop = t.hop; in.half_width = t.half_width;
+    in.py = stages & AEGIS_STAGE_PYIN;
+    in.feed = feed; in.caller_stream = caller_stream; in.sync = sync;
+    DevTables dt = h->dt;      // (a host-only handle: the packed table the device would hold)
+    if (h->device < 0 && !t.log_trans_pack.empty()) dt.lt_pack = t.log_trans_pack.data();
+    in.band_applies = viterbi_band_applies(base_params(t), dt);
+    in.split_applies = viterbi_split_applies(base_params(t), dt);
+    in.masked_streams = std::move(masked);
+    in.knobs = h->knobs;
+    in.persistent = h->persist.on;
+    if (split_allowed(in) && in.knobs.split_seglen < 0 && h->tsplit.cooldown > 0) in.cooling = true;
+    return in;
 }
 
-}  // namespace
+static int64_t pcm_width(int32_t fmt) {
+    return fmt == AEGIS_PCM_U8 ? 1 : fmt == AEGIS_PCM_S16 ? 2 : fmt == AEGIS_PCM_S24 ? 3 : fmt == AEGIS_PCM_S32 || fmt == AEGIS_PCM_F32 ? 4 : 0;
+}
 
 extern "C" {
-
-int aegis_abi_version(void) { return AEGIS_ABI_VERSION; }
-
-const char *aegis_last_error(const aegis_handle *h) { return h ? h->err.c_str() : g_create_error.c_str(); }
-
-int aegis_create(const aegis_config *cfg, aegis_handle **out) {
-    aegis_handle *h = nullptr;
-    try {
-    if (!out) { g_create_error = "out == NULL"; return AEGIS_ERR_INVALID; }
-    *out = nullptr;
-    aegis_config c{};
-    if (cfg) c = *cfg;
-    if (c.sample_rate == 0) c.sample_rate = 44100;
-    if (c.hop_length == 0) c.hop_length = 512;
-    if (c.n_fft == 0) c.n_fft = 2048;
-    if (c.n_mels == 0) c.n_mels = 128;
-    if (!(c.fmin > 0)) c.fmin = 82.4068892282175;      // note_to_hz('E2'), aegis_engine.py:63
-    if (!(c.fmax > 0)) c.fmax = 1046.5022612023945;    // note_to_hz('C6')
-    const bool auto_pass = c.max_frames_per_pass <= 0;
-    if (auto_pass) c.max_frames_per_pass = (int64_t)1 << 21;
-
-    h = new (std::nothrow) aegis_handle();
-    if (!h) { g_create_error = "out of host memory"; return AEGIS_ERR_NOMEM; }
-    const std::string terr = h->tab.build(c.sample_rate, c.hop_length, c.n_fft, c.n_mels, c.fmin, c.fmax);
-    if (!terr.empty()) { g_create_error = terr; delete h; return AEGIS_ERR_INVALID; }
-    if (!h->tab.set_pyin_init(c.pyin_init)) { g_create_error = "pyin_init must be AEGIS_PYIN_INIT_UNVOICED (0) or AEGIS_PYIN_INIT_UNIFORM (1)"; delete h; return AEGIS_ERR_INVALID; }
-    h->device = c.device;
-    h->max_frames_per_pass = c.max_frames_per_pass;
-    h->knobs.read_env();                       // (a host-only handle plans with the knobs a device handle would)
-    h->persistent = h->knobs.persistent_wanted;
-
-    h->lag_stride = (h->tab.max_period + 1 + 7) & ~7;
-    // a dfn row also holds the frame's trough list when the frame kernel finds the troughs (PassParams::troughs)
-    h->lag_stride = std::max<int32_t>(h->lag_stride, (trough_row_doubles_host(h->tab.n_lags) + 7) & ~7);
-    h->yin_stride = (h->tab.n_lags + 7) & ~7;
-    h->obs_stride = (h->tab.n_bins + 7) & ~7;
-    if (c.device == -1) { *out = h; return AEGIS_OK; }   // host tables only
-
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev <= 0) {
-        g_create_error = std::string("no HIP device available: ") + hipGetErrorString(e);
-        delete h; return AEGIS_ERR_DEVICE;
-    }
-    if (c.device < 0 || c.device >= ndev) { g_create_error = "device ordinal out of range"; delete h; return AEGIS_ERR_INVALID; }
-    auto fail = [&](int code) { g_create_error = h->err; aegis_destroy(h); return code; };
-#define CRT(expr) do { int rc__ = (expr); if (rc__ != AEGIS_OK) return fail(rc__); } while (0)
-#define CRTHIP(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) { h->err = std::string(#expr) + ": " + hipGetErrorString(e__); return fail(AEGIS_ERR_DEVICE); } } while (0)
-    CRTHIP(hipSetDevice(c.device));
-    CRTHIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    CRTHIP(hipStreamCreateWithFlags(&h->stream4, hipStreamNonBlocking));
-    CRTHIP(hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking));
-    CRTHIP(hipStreamCreateWithFlags(&h->stream3, hipStreamNonBlocking));
-    if (const char *e = std::getenv("AEGIS_DEBUG_STAGES")) h->debug_stages = (e[0] == '1');
-    if (const char *e = std::getenv("AEGIS_CMND_IN_FRAME")) h->cmnd_off = (e[0] == '0');
-    if (const char *e = std::getenv("AEGIS_TROUGHS_IN_FRAME")) h->troughs_off = (e[0] == '0');
-    if (const char *e = std::getenv("AEGIS_TEST_DROP_CHUNK_SIGNAL")) h->test_drop_signal = std::atoi(e);
-    CRTHIP(hipDeviceGetAttribute(&h->n_cus, hipDeviceAttributeMultiprocessorCount, c.device));
-    if (auto_pass) {
-        // Default workspace bound: as many frames per pass as a third of the free device memory holds (a pass needs
-        // ~10.3 KB per frame at the reference's rates, and two workspaces alternate when a call needs several passes), between
-        // 2^21 and 2^24 frames.  On a 288 GB MI355X the 512-clip folder of BASELINE.json configs[3] (8.36 M frames) is then ONE
-        // pass: every clip's Viterbi starts at once and the frame stage of the whole folder runs beside it (411 -> 385 ms).
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-            const int64_t per_frame = (int64_t)h->lag_stride * 8 + (int64_t)h->obs_stride * 8 + 8 + 2 * h->tab.n_bins * 2 +
-                                      2 * h->tab.n_bins * 2 / kViterbiChunk + h->tab.n_mels * 4 + 16;
-            const int64_t fit = (int64_t)(free_b / 3) / per_frame;
-            h->max_frames_per_pass = std::min<int64_t>((int64_t)1 << 24, std::max<int64_t>((int64_t)1 << 21, fit));
-        }
-    }
-    CRTHIP(hipEventCreateWithFlags(&h->copy_event, hipEventDisableTiming));
-    CRTHIP(viterbi_configure());
-    CRT(ensure(h, h->vstats, 32));
-    CRTHIP(hipMemset(h->vstats.p, 0, 32));
-    CRTHIP(cqt_configure());
-
-    const Tables &t = h->tab;
-    CRT(upload_table(h, t.hann, &h->dt.hann));
-    CRT(upload_table(h, t.mel_start, &h->dt.mel_start));
-    CRT(upload_table(h, t.mel_len, &h->dt.mel_len));
-    CRT(upload_table(h, t.mel_off, &h->dt.mel_off));
-    CRT(upload_table(h, t.mel_w, &h->dt.mel_w));
-    CRT(upload_table(h, t.mel_chunk_bin, &h->dt.mel_chunk_bin));
-    CRT(upload_table(h, t.mel_chunk_w, &h->dt.mel_chunk_w));
-    CRT(upload_table(h, t.mel_band_chunk, &h->dt.mel_band_chunk));
-    h->dt.mel_chunks = (int32_t)t.mel_chunk_bin.size();
-    CRT(upload_table(h, t.thresholds, &h->dt.thresholds));
-    CRT(upload_table(h, t.beta_probs, &h->dt.beta_probs));
-    CRT(upload_table(h, t.beta_cumsum, &h->dt.beta_cumsum));
-    CRT(upload_table(h, t.beta_suffix, &h->dt.beta_suffix));
-    CRT(upload_table(h, t.boltz_fact, &h->dt.boltz_fact));
-    CRT(upload_table(h, t.boltz_exp, &h->dt.boltz_exp));
-    CRT(upload_table(h, t.log_trans_band, &h->dt.lt_band));
-    if (!t.log_trans_pack.empty()) CRT(upload_table(h, t.log_trans_pack, &h->dt.lt_pack));
-    CRT(upload_table(h, t.freqs, &h->dt.freqs));
-    {
-        const double *tw = nullptr;
-        CRT(upload_table(h, t.twiddle, &tw));
-        h->dt.twiddle = reinterpret_cast<const double2 *>(tw);
-    }
-#undef CRT
-#undef CRTHIP
-    *out = h;
-    return AEGIS_OK;
-    } catch (...) {
-        const int code = abi_fail(nullptr);
-        if (h) { if (out) *out = nullptr; aegis_destroy(h); }
-        return code;
-    }
-}
-
-static void destroy_now(aegis_handle *h) noexcept;
-
-void aegis_destroy(aegis_handle *h) {
-    if (!h) return;
-    {
-        std::lock_guard<std::mutex> lock(h->mu);
-        if (h->open_streams > 0) { h->destroy_requested = true; return; }   // the last aegis_stream_free() finishes the job
-    }
-    destroy_now(h);
-}
-
-static void destroy_now(aegis_handle *h) noexcept {
-    if (h->device < 0) { delete h; return; }
-    // AEGIS_TRACE_DESTROY=1: one line on stderr before every step that can block (which call a teardown sat in)
-    const bool trace = std::getenv("AEGIS_TRACE_DESTROY") != nullptr;
-    auto T = [&](const char *what) { if (trace) { std::fprintf(stderr, "[aegis destroy] %s\n", what); std::fflush(stderr); } };
-    T("hipSetDevice");
-    (void)hipSetDevice(h->device);
-    // Bounded wait first: the handle's streams normally are idle here (every blocking entry synchronises before it returns).
-    // If something is still running after ten seconds -- a caller that enqueued with sync = 0 and never waited, a wedged
-    // device -- the GPU objects are leaked rather than waited for: a teardown (Handle.__del__ runs it from the garbage
-    // collector, possibly while an exception unwinds) must never be the call that hangs a process.
-    {
-        std::vector<hipStream_t> all{h->stream, h->stream2, h->stream3, h->stream4};
-        for (auto &ss : h->split) for (hipStream_t q : {ss.frame_a, ss.frame_b, ss.viterbi}) all.push_back(q);
-        const auto t0 = std::chrono::steady_clock::now();
-        for (;;) {
-            bool busy = false;
-            for (hipStream_t q : all) if (q && hipStreamQuery(q) == hipErrorNotReady) busy = true;
-            if (!busy) break;
-            if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(10)) {
-                std::fprintf(stderr, "libaegis_hip: aegis_destroy: work still running on the handle's streams after 10 s; its device memory and streams are leaked\n");
-                (void)hipGetLastError();
-                delete h;
-                return;
-            }
-            std::this_thread::sleep_for(std::chrono::milliseconds(1));
-        }
-        (void)hipGetLastError();
-    }
-    // The CU-masked streams own their hardware queues (plain streams draw from the runtime's pool), so destroying one really
-    // tears a queue down -- and hipStreamDestroy sat in that for ever (gpurun_out/call53.log) after
-    // a pass whose streams had waited on each other's events with timing events recorded between them (profiling on, the
-    // host-buffer entry's schedule), although every stream of the handle had been synchronised one by one.  A device-wide
-    // synchronisation first makes the runtime retire what it still tracks across streams; with it the same teardown
-    // returns (tools/exit_hang_probe.py, matrix in profiles/r4_exit_hang_probe.txt).
-    T("device sync");
-    (void)hipDeviceSynchronize();
-    for (auto &ss : h->split)
-        for (hipStream_t q : {ss.frame_a, ss.frame_b, ss.viterbi})
-            if (q) { T("destroy masked stream"); (void)hipStreamDestroy(q); }
-    T("sync stream"); if (h->stream) (void)hipStreamSynchronize(h->stream);
-    T("sync stream2"); if (h->stream2) (void)hipStreamSynchronize(h->stream2);
-    T("sync stream3"); if (h->stream3) (void)hipStreamSynchronize(h->stream3);
-    T("sync stream4"); if (h->stream4) (void)hipStreamSynchronize(h->stream4);
-    T("events");
-    for (auto &ev : h->events) { (void)hipEventDestroy(ev.second.first); (void)hipEventDestroy(ev.second.second); }
-    h->events.clear();
-    for (hipEvent_t e : h->sync_events) (void)hipEventDestroy(e);
-    for (hipEvent_t e : h->split_ev) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : h->hyb_ev) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : h->fin_ev) if (e) (void)hipEventDestroy(e);
-    T("free tables");
-    for (void *p : h->table_allocs) (void)hipFree(p);
-    if (h->cqt_bank.dev) (void)hipFree(h->cqt_bank.dev);
-    T("free workspaces");
-    for (auto &w : h->work)
-        for (DevBuf *b : {&w.dfn, &w.yin, &w.logobs, &w.logunv, &w.obs_seg, &w.ptr, &w.cmap, &w.chunk_off, &w.bnd, &w.states, &w.melpow,
-                          &w.clipmax, &w.rake_raw, &w.sample_off, &w.sample_len, &w.out_off, &w.frame_off, &w.order, &w.sel_off,
-                          &w.vstate, &w.chunk_lo, &w.chunk_flag, &w.clip_tb, &w.seg64, &w.seg32, &w.seg_col, &w.seg_map, &w.seg_i32,
-                          &w.colhist, &w.colG, &w.colkg, &w.clip_flag, &w.flag_order, &w.tube_buf, &w.tube_at, &w.tube_count})
-            free_buf(*b);
-    T("free staging");
-    for (DevBuf *b : {&h->vstats, &h->rk_raw, &h->abort_flag, &h->finite_flag, &h->t_x, &h->t_off, &h->t_a, &h->t_b, &h->t_c, &h->t_d, &h->t_e,
-                      &h->t_i8, &h->t_i64a, &h->t_i64b, &h->t_pa, &h->q_pcm, &h->q_soff, &h->q_foff, &h->q_toff, &h->q_out, &h->q_chroma, &h->q_cls, &h->io_pcm, &h->io_f0, &h->io_voiced, &h->io_vprob, &h->io_rms, &h->io_rake,
-                      &h->io_sdb, &h->io_bin, &h->io_colmean, &h->pcm_raw, &h->pcm_clips, &h->pcm_ranges, &h->pcm_taps})
-        free_buf(*b);
-    T("destroy streams");
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    if (h->stream2) (void)hipStreamDestroy(h->stream2);
-    if (h->stream3) (void)hipStreamDestroy(h->stream3);
-    if (h->stream4) (void)hipStreamDestroy(h->stream4);
-    if (h->copy_event) (void)hipEventDestroy(h->copy_event);
-    T("done");
-    delete h;
-}
-
-int64_t aegis_frames_for(const aegis_handle *h, int64_t n_samples) {
-    try {
-    if (!h || n_samples < 0) return AEGIS_ERR_INVALID;
-    return 1 + n_samples / h->tab.hop;
-    } catch (...) { return abi_fail(const_cast<aegis_handle *>(h)); }
-}
-
-int aegis_set_profiling(aegis_handle *h, int32_t on) {
-    try {
-    if (!h) return AEGIS_ERR_INVALID;
-    h->profiling = on != 0;
-    return AEGIS_OK;
-    } catch (...) { return abi_fail(h); }
-}
-
-int aegis_last_kernel_launches(const aegis_handle *h, const char *name) {
-    if (!h || !name) return -1;
-    auto it = h->last_count.find(name);
-    return it == h->last_count.end() ? 0 : it->second;
-}
-
-double aegis_last_kernel_ms(const aegis_handle *h, const char *name) {
-    if (!h || !name) return -1.0;
-    auto it = h->last_ms.find(name);
-    return it == h->last_ms.end() ? -1.0 : it->second;
-}
 
 // Raw WAV bytes of aegis_analyze_pcm: per time chunk, the bytes of the input frames the chunk's new output samples read
 // are copied on stream3 and one pcm_decode_resample_kernel writes those samples into the PCM buffer.
@@ -517,7 +108,7 @@ static int pcm_feed(aegis_handle *h, HostFeed &feed, const std::vector<int32_t> 
         int64_t &done = feed.copied[(size_t)ci];
         if (need[i] <= done) continue;
         const PcmClipDev &c = pf.clips[(size_t)ci];
-        const int64_t fb = (int64_t)c.ch * (c.fmt == AEGIS_PCM_U8 ? 1 : c.fmt == AEGIS_PCM_S16 ? 2 : c.fmt == AEGIS_PCM_S24 ? 3 : 4);
+        const int64_t fb = (int64_t)c.ch * pcm_width(c.fmt);
         const int64_t in_hi = pcm_inputs_needed(c, need[i]);
         int64_t &din = pf.done_in[(size_t)ci];
         if (in_hi > din) {
@@ -546,59 +137,16 @@ static int pcm_feed(aegis_handle *h, HostFeed &feed, const std::vector<int32_t> 
     return AEGIS_OK;
 }
 
-// sync: 0 = return with the work enqueued, 1 = synchronise and report (give-up of the single Viterbi launch, non-finite
-// samples), 2 = the caller synchronises and makes those checks itself right away (aegis_analyze_batch: the single Viterbi
-// launch is allowed, as with 1)
-static int analyze_device_locked(aegis_handle *h, const float *d_pcm, const int64_t *sample_offsets,
-                                 int32_t n_clips, double rake_sensitivity, uint32_t stages,
-                                 aegis_outputs *dout, void *stream_v, int32_t sync, HostFeed *feed = nullptr);
-
-int aegis_analyze_batch_device(aegis_handle *h, const float *d_pcm, const int64_t *sample_offsets,
-                               int32_t n_clips, double rake_sensitivity, uint32_t stages,
-                               aegis_outputs *dout, void *stream_v, int32_t sync) {
-    try {
-    if (!h) return AEGIS_ERR_INVALID;
-    std::lock_guard<std::mutex> lock(h->mu);
-    if (!h->persistent && h->knobs.persistent_wanted && h->persist_cooldown > 0 && --h->persist_cooldown == 0)
-        h->persistent = true;                 // the give-up is not for good: whatever serialised the kernels may be gone
-    int rc = analyze_device_locked(h, d_pcm, sample_offsets, n_clips, rake_sensitivity, stages, dout, stream_v, sync);
-    // The default pass size was taken from the device memory free when the handle was created; other handles, the caller's
-    // own buffers or a second workspace may have taken it since: on an allocation failure the passes are halved (down to
-    // 2^21 frames) and the call planned again.
-    while (rc == AEGIS_ERR_NOMEM && h->max_frames_per_pass > ((int64_t)1 << 21)) {
-        (void)hipDeviceSynchronize();
-        (void)hipGetLastError();
-        h->max_frames_per_pass = std::max<int64_t>((int64_t)1 << 21, h->max_frames_per_pass / 2);
-        rc = analyze_device_locked(h, d_pcm, sample_offsets, n_clips, rake_sensitivity, stages, dout, stream_v, sync);
-    }
-    if (rc != AEGIS_OK && h->persist_gave_up) {
-        // The single Viterbi launch of a balanced pass found the frame stage not running beside it (a profiler collecting
-        // counters serialises kernels, for one): this handle goes back to one launch per chunk for the next 16 calls and
-        // the call is repeated.
-        h->persist_gave_up = false;
-        h->persistent = false;
-        h->persist_cooldown = 16;
-        ++h->persistent_fallbacks;
-        rc = analyze_device_locked(h, d_pcm, sample_offsets, n_clips, rake_sensitivity, stages, dout, stream_v, sync);
-    }
-    return rc;
-    } catch (...) { return abi_fail(h); }
-}
-
-// the last call's plan: its last pass, and the workspace that pass used
-static const PassPlan *last_pass(const aegis_handle *h) { return h->plan.passes.empty() ? nullptr : &h->plan.passes.back(); }
-static int last_work(const aegis_handle *h) { return h->plan.passes.empty() ? 0 : (int)((h->plan.passes.size() - 1) & 1); }
-
 // After a synchronisation: a persistent Viterbi launch that gave up waiting for its chunk flags says so here.
 static int persistent_check(aegis_handle *h) {
-    if (!h->persist_pending) return AEGIS_OK;
-    h->persist_pending = false;
+    if (!h->persist.pending) return AEGIS_OK;
+    h->persist.pending = false;
     uint32_t aborted = 0;
     HIPCHK(h, hipMemcpy(&aborted, h->abort_flag.p, 4, hipMemcpyDeviceToHost));
     if (aborted) {
         HIPCHK(h, hipMemset(h->abort_flag.p, 0, 4));
         h->err = "the Viterbi kernel gave up waiting for the frame stage (AEGIS_VITERBI_PERSISTENT=0 launches it per chunk)";
-        h->persist_gave_up = true;
+        h->persist.gave_up = true;
         return AEGIS_ERR_DEVICE;
     }
     return AEGIS_OK;
@@ -628,12 +176,12 @@ static int split_check(aegis_handle *h, const aegis_handle::SplitCheck &sc, hipS
     std::vector<uint32_t> flags((size_t)nc);
     HIPCHK(h, hipMemcpy(flags.data(), sc.p.clip_flag, (size_t)nc * 4, hipMemcpyDeviceToHost));
     std::vector<int32_t> redo;
-    h->last_split_flags.assign(flags.begin(), flags.end());
+    h->tsplit.last_flags.assign(flags.begin(), flags.end());
     for (int i = 0; i < nc; ++i)
-        if (flags[i]) { redo.push_back(i); if (flags[i] & 1u) ++h->split_stats[3]; }
+        if (flags[i]) { redo.push_back(i); if (flags[i] & 1u) ++h->tsplit.stats[3]; }
     uint32_t counts[2] = {0, 0};
     HIPCHK(h, hipMemcpy(counts, sc.p.tube_count, 8, hipMemcpyDeviceToHost));
-    h->last_carried_steps = counts[1];
+    h->tsplit.last_carried_steps = counts[1];
     // The planning rule's estimate against the clock.  A split pass's Viterbi kernels come behind its frame stage, and their
     // time depends on the material: a lock-on run that never meets the speculative one runs its whole segment, and the
     // segments behind it speculate again (one more segment time per round).  When frame stage + measured Viterbi time is
@@ -642,23 +190,23 @@ static int split_check(aegis_handle *h, const aegis_handle::SplitCheck &sc, hipS
     // last's.
     bool last_split = true;
     for (size_t j = (size_t)sc.pass + 1; j < h->plan.passes.size(); ++j) last_split = last_split && !h->plan.passes[j].tsplit;
-    if (m.split_auto && h->split_ev[1] && last_split) {
+    if (m.split_auto && last_split) {
         float ms = 0.f;
         if (hipEventElapsedTime(&ms, h->split_ev[0], h->split_ev[1]) == hipSuccess) {
-            h->last_split_viterbi_ms = ms;
-            if (!split_clock_pays(h->plan, ms)) { if (++h->split_bad >= 2) { h->split_cooldown = 32; h->split_bad = 0; } }
-            else h->split_bad = 0;
+            h->tsplit.last_viterbi_ms = ms;
+            if (!split_clock_pays(h->plan, ms)) { if (++h->tsplit.bad >= 2) { h->tsplit.cooldown = 32; h->tsplit.bad = 0; } }
+            else h->tsplit.bad = 0;
         }
     }
     if (redo.empty()) return AEGIS_OK;
-    h->split_stats[2] += (int64_t)redo.size();
+    h->tsplit.stats[2] += (int64_t)redo.size();
     if (m.split_auto) {
         // the redo is sequential and comes on top of the split pass: when it costs too much of what the pass would have
         // taken sequentially (material without voiced notes never locks on and keeps its tubes open: noise, silence), the
         // next 32 calls of this handle plan their passes sequentially
         int64_t redoF = 0;
         for (int i : redo) redoF = std::max(redoF, m.frames(i));
-        if (!split_redo_pays(m, redoF, t.half_width)) h->split_cooldown = 32;
+        if (!split_redo_pays(m, redoF, t.half_width)) h->tsplit.cooldown = 32;
     }
     aegis_handle::Work &w = h->work[sc.pass & 1];
     HIPCHK(h, hipMemcpy(w.flag_order.p, redo.data(), redo.size() * 4, hipMemcpyHostToDevice));
@@ -698,28 +246,6 @@ static aegis_handle::SplitSet *split_streams(aegis_handle *h, int n_clips) {
         }
     }
     return ss.viterbi ? &ss : nullptr;
-}
-
-// What the planner needs to know about a call.  masked: whether a CU-masked stream set exists for n clips (the executor
-// creates them through split_streams; aegis_debug_plan only asks whether they would be laid out).
-static PlanInput plan_input(aegis_handle *h, const int64_t *sample_offsets, int32_t n_clips, uint32_t stages, bool feed,
-                            bool caller_stream, int32_t sync, int n_cus, std::function<bool(int)> masked) {
-    const Tables &t = h->tab;
-    PlanInput in;
-    in.sample_offsets.assign(sample_offsets, sample_offsets + n_clips + 1);
-    in.max_frames_per_pass = h->max_frames_per_pass;
-    in.n_cus = n_cus; in.hop = t.hop; in.half_width = t.half_width;
-    in.py = stages & AEGIS_STAGE_PYIN;
-    in.feed = feed; in.caller_stream = caller_stream; in.sync = sync;
-    DevTables dt = h->dt;      // (a host-only handle: the packed table the device would hold)
-    if (h->device < 0 && !t.log_trans_pack.empty()) dt.lt_pack = t.log_trans_pack.data();
-    in.band_applies = viterbi_band_applies(base_params(t), dt);
-    in.split_applies = viterbi_split_applies(base_params(t), dt);
-    in.masked_streams = std::move(masked);
-    in.knobs = h->knobs;
-    in.persistent = h->persistent;
-    if (split_allowed(in) && in.knobs.split_seglen < 0 && h->split_cooldown > 0) in.cooling = true;
-    return in;
 }
 
 static int ensure_pass(aegis_handle *h, aegis_handle::Work &w, const PassPlan &m, uint32_t stages) {
@@ -818,8 +344,6 @@ static PassParams bind_pass(const aegis_handle *h, const PassPlan &m, const aegi
     p.out_colmean = mel ? dout->sdb_col_means : nullptr;
     p.out_total = h->plan.total_frames;
     p.rake_ratio = rake_sensitivity;
-    const double ms_per_frame = ((double)t.hop / (double)t.sr) * 1000;      // vision.py:23-25
-    p.rake_min_frames = (int)(10 / ms_per_frame); p.rake_max_frames = (int)(30 / ms_per_frame);
     if (opts & AEGIS_OPT_F0_ZERO) p.f0_unvoiced = 0.0;
     p.dense = m.dense ? 1 : 0;
     if (m.tsplit) {
@@ -866,9 +390,12 @@ static hipStream_t lane_stream(const aegis_handle *h, Lane l, hipStream_t s, con
 
 #define VCHK(expr) do { hipError_t ve__ = (expr); if (ve__ != hipSuccess) { h->err = std::string("viterbi launch: ") + hipGetErrorString(ve__); return AEGIS_ERR_DEVICE; } } while (0)
 
+// sync: 0 = return with the work enqueued, 1 = synchronise and report (give-up of the single Viterbi launch, non-finite
+// samples), 2 = the caller synchronises and makes those checks itself right away (aegis_analyze_batch: the single Viterbi
+// launch is allowed, as with 1)
 static int analyze_device_locked(aegis_handle *h, const float *d_pcm, const int64_t *sample_offsets,
                                  int32_t n_clips, double rake_sensitivity, uint32_t stages,
-                                 aegis_outputs *dout, void *stream_v, int32_t sync, HostFeed *feed) {
+                                 aegis_outputs *dout, void *stream_v, int32_t sync, HostFeed *feed = nullptr) {
     // ---- validate -----------------------------------------------------------------------------------------------------
     if (!h) return AEGIS_ERR_INVALID;
     if (n_clips < 0 || (n_clips > 0 && (!sample_offsets || !dout))) { h->err = "null argument"; return AEGIS_ERR_INVALID; }
@@ -881,7 +408,7 @@ static int analyze_device_locked(aegis_handle *h, const float *d_pcm, const int6
         return AEGIS_ERR_INVALID;
     }
     const Tables &t = h->tab;
-    if (h->device < 0) { h->err = "handle was created with device=-1 (host tables only)"; return AEGIS_ERR_DEVICE; }
+    DEVICE_ONLY(h);
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t s = stream_v ? static_cast<hipStream_t>(stream_v) : h->stream;
     for (int i = 0; i < n_clips; ++i) {
@@ -896,24 +423,27 @@ static int analyze_device_locked(aegis_handle *h, const float *d_pcm, const int6
     }
     // host arrays of the previous call's plan are no longer referenced once the stream drained
     if (h->plan_in_flight) { HIPCHK(h, hipStreamSynchronize(s)); h->plan_in_flight = false; }
-    h->split_checks.clear();
-    if (h->profiling) { for (auto &ev : h->events) { (void)hipEventDestroy(ev.second.first); (void)hipEventDestroy(ev.second.second); } h->events.clear(); }
+    h->tsplit.checks.clear();
+    drop_events(h);
 
     // ---- plan ---------------------------------------------------------------------------------------------------------
     const PlanInput in = plan_input(h, sample_offsets, n_clips, stages, feed != nullptr, stream_v != nullptr, sync, h->n_cus,
                                     [h](int n) { return split_streams(h, n) != nullptr; });
-    if (in.cooling) --h->split_cooldown;
+    if (in.cooling) --h->tsplit.cooldown;
     h->plan = plan_call(in);
     h->plan_in_flight = true;
     const bool py = in.py;
 
-    while (h->sync_events.size() < 8) {
-        hipEvent_t e;
-        HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        h->sync_events.push_back(e);
-    }
     // fixed slots of sync_events: 0 call start, 1/2 pass done (workspace parity), 3 frame_b joined, 4 frame_a final, 5.. per chunk
     enum { EV_START = 0, EV_DONE0 = 1, EV_DONE1 = 2, EV_FB = 3, EV_FA = 4, EV_META = 5, EV_CHUNK0 = 6 };
+    // (the fixed events exist since aegis_create; the call's longest pass may need more per-chunk ones)
+    for (const PassPlan &m : h->plan.passes)
+        while ((int)h->sync_events.size() < EV_CHUNK0 + m.nk()) {
+            hipEvent_t e;
+            const int rc = new_event(h, &e, hipEventDisableTiming);
+            if (rc != AEGIS_OK) return rc;
+            h->sync_events.push_back(e);
+        }
     bool done_recorded[2] = {false, false}, split_started = false;
     std::vector<hipStream_t> joined;          // streams whose work s must wait for before the call returns
     for (int pi = 0; pi < (int)h->plan.passes.size(); ++pi) {
@@ -923,20 +453,15 @@ static int analyze_device_locked(aegis_handle *h, const float *d_pcm, const int6
         int rc;
         // ---- wait for the workspace: a split verdict of the pass two back is read (and acted on) before anything
         // overwrites it or ensure() moves its buffers
-        if (!h->split_checks.empty() && h->split_checks.front().pass == pi - 2) {
+        if (!h->tsplit.checks.empty() && h->tsplit.checks.front().pass == pi - 2) {
             HIPCHK(h, hipEventSynchronize(h->sync_events[EV_DONE0 + (pi & 1)]));
-            const aegis_handle::SplitCheck sc = h->split_checks.front();
-            h->split_checks.erase(h->split_checks.begin());
+            const aegis_handle::SplitCheck sc = h->tsplit.checks.front();
+            h->tsplit.checks.erase(h->tsplit.checks.begin());
             if ((rc = split_check(h, sc, s)) != AEGIS_OK) return rc;
         }
         const aegis_handle::SplitSet *ss = m.fa == Lane::masked_frame_a ? split_streams(h, nc) : nullptr;
         hipStream_t fa = lane_stream(h, m.fa, s, ss), fb = lane_stream(h, m.fb, s, ss), sv = lane_stream(h, m.sv, s, ss);
         hipStream_t sd = lane_stream(h, m.sd, s, ss), sa = lane_stream(h, m.sa, s, ss);
-        while ((int)h->sync_events.size() < EV_CHUNK0 + nk) {
-            hipEvent_t e;
-            HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            h->sync_events.push_back(e);
-        }
         auto join_later = [&](hipStream_t q) { if (q != s && std::find(joined.begin(), joined.end(), q) == joined.end()) joined.push_back(q); };
         if (pi == 0) HIPCHK(h, hipEventRecord(h->sync_events[EV_START], s));
         for (hipStream_t q : {fa, fb, sv, sd, sa}) {
@@ -962,8 +487,24 @@ static int analyze_device_locked(aegis_handle *h, const float *d_pcm, const int6
         if (m.persistent) {
             p.chunk_gen = ++h->chunk_gen;
             if (p.chunk_gen == 0) p.chunk_gen = ++h->chunk_gen;
-            h->persist_pending = true;
+            h->persist.pending = true;
         }
+
+        // A time-split launch (a plain split pass's, a hybrid pass's): an automatic call is timed from its first one to its
+        // last one (split_ev), and each leaves a verdict that split_check reads once the pass is done.
+        auto launch_split = [&](const PassParams &q, int n_spec, hipStream_t sq, hipStream_t aux) -> int {
+            begin_event(h, "viterbi", sq);
+            if (m.split_auto && !split_started) { HIPCHK(h, hipEventRecord(h->split_ev[0], sq)); split_started = true; }
+            const hipError_t ve = launch_viterbi_split(q, h->dt, t.log_trans_band.data(), d_seg_order, n_spec, d_lock_order, m.n_lock, sq, aux, h->fin_ev);
+            if (m.split_auto) HIPCHK(h, hipEventRecord(h->split_ev[1], sq));
+            end_event(h, sq);
+            VCHK(ve);
+            h->tsplit.checks.push_back({pi, q});
+            ++h->tsplit.stats[0]; h->tsplit.stats[1] += m.n_seg;
+            return AEGIS_OK;
+        };
+        std::vector<int32_t> cis;
+        std::vector<int64_t> need;          // (a host feed: samples of each clip the chunk at hand needs)
 
         // ---- time chunks: frame stage, then the Viterbi behind it -----------------------------------------------------
         for (int k = 0; k < nk; ++k) {
@@ -975,33 +516,24 @@ static int analyze_device_locked(aegis_handle *h, const float *d_pcm, const int6
             p.vt_end = (k == nk - 1) ? INT64_MAX : m.cb[k + 1];
             p.clip_t0 = m.proportional ? static_cast<const int64_t *>(w.clip_tb.p) + (size_t)k * nc : nullptr;
             p.clip_t1 = m.proportional ? static_cast<const int64_t *>(w.clip_tb.p) + (size_t)(k + 1) * nc : nullptr;
-            if (feed && feed->raw) {      // the same samples, decoded on the device from the raw bytes
-                std::vector<int32_t> cis((size_t)nc);
-                std::vector<int64_t> need((size_t)nc);
+            if (feed) {      // frame t reads samples [t*hop - 1024, t*hop + 1024): what this chunk needs of each clip
+                cis.assign(m.clips.begin(), m.clips.end());
+                need.resize((size_t)nc);
                 bool any = false;
                 for (int i = 0; i < nc; ++i) {
                     const int64_t n = m.sample_len[i];
-                    cis[(size_t)i] = m.clips[i];
                     need[(size_t)i] = (k == nk - 1) ? n : std::min(n, (m.clip_hi(k, i) - 1) * (int64_t)t.hop + t.n_fft / 2);
                     any = any || need[(size_t)i] > feed->copied[(size_t)m.clips[i]];
                 }
-                if (any) {
+                if (any && feed->raw) {      // the same samples, decoded on the device from the raw bytes
                     if ((rc = pcm_feed(h, *feed, cis, need)) != AEGIS_OK) return rc;
-                    HIPCHK(h, hipEventRecord(h->copy_event, h->stream3));
-                    HIPCHK(h, hipStreamWaitEvent(fs, h->copy_event, 0));
-                }
-            } else if (feed) {      // frame t reads samples [t*hop - 1024, t*hop + 1024)
-                bool any = false;
-                for (int i = 0; i < nc; ++i) {
-                    const int ci = m.clips[i];
-                    const int64_t n = m.sample_len[i];
-                    const int64_t need = (k == nk - 1) ? n : std::min(n, (m.clip_hi(k, i) - 1) * (int64_t)t.hop + t.n_fft / 2);
-                    int64_t &done = feed->copied[ci];
-                    if (need > done) {
-                        HIPCHK(h, hipMemcpyAsync(feed->dst + m.sample_off[i] + done, feed->pcm[ci] + done,
-                                                 (size_t)(need - done) * 4, hipMemcpyHostToDevice, h->stream3));
-                        done = need;
-                        any = true;
+                } else if (any) {
+                    for (int i = 0; i < nc; ++i) {
+                        int64_t &done = feed->copied[(size_t)m.clips[i]];
+                        if (need[(size_t)i] <= done) continue;
+                        HIPCHK(h, hipMemcpyAsync(feed->dst + m.sample_off[i] + done, feed->pcm[m.clips[i]] + done,
+                                                 (size_t)(need[(size_t)i] - done) * 4, hipMemcpyHostToDevice, h->stream3));
+                        done = need[(size_t)i];
                     }
                 }
                 if (any) {
@@ -1033,20 +565,14 @@ static int analyze_device_locked(aegis_handle *h, const float *d_pcm, const int6
                 HIPCHK(h, hipEventRecord(h->sync_events[EV_CHUNK0 + k], fs));
                 HIPCHK(h, hipStreamWaitEvent(sv, h->sync_events[EV_CHUNK0 + k], 0));
             }
-            begin_event(h, "viterbi", sv);
-            const bool split_now = m.tsplit && !m.hybrid;
-            if (split_now && m.split_auto) {
-                for (auto &e : h->split_ev) if (!e) HIPCHK(h, hipEventCreate(&e));
-                if (!split_started) { HIPCHK(h, hipEventRecord(h->split_ev[0], sv)); split_started = true; }
+            if (m.tsplit && !m.hybrid) {
+                if ((rc = launch_split(p, m.n_seg, sv, h->stream4 != sv ? h->stream4 : nullptr)) != AEGIS_OK) return rc;
+                continue;
             }
-            if (split_now) for (auto &e : h->fin_ev) if (!e) HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            hipError_t ve = split_now ? launch_viterbi_split(p, h->dt, t.log_trans_band.data(), d_seg_order, m.n_seg, d_lock_order, m.n_lock, sv,
-                                                             h->stream4 != sv ? h->stream4 : nullptr, h->fin_ev)
-                                      : launch_viterbi(p, h->dt, t.log_trans_band.data(), sv);
-            if (split_now && m.split_auto) HIPCHK(h, hipEventRecord(h->split_ev[1], sv));
+            begin_event(h, "viterbi", sv);
+            hipError_t ve = launch_viterbi(p, h->dt, t.log_trans_band.data(), sv);
             end_event(h, sv);
             VCHK(ve);
-            if (split_now) { h->split_checks.push_back({pi, p}); ++h->split_stats[0]; h->split_stats[1] += m.n_seg; }
         }
         if (m.use_fb) {                    // the dB / rake finalisation needs every chunk's mel rows and clip maxima
             HIPCHK(h, hipEventRecord(h->sync_events[EV_FB], fb));
@@ -1055,7 +581,6 @@ static int analyze_device_locked(aegis_handle *h, const float *d_pcm, const int6
         if (m.hybrid) {
             // the segments behind step S: after the last chunk's observations (fa; fb has joined it above) and the sequential
             // kernel's last launch (sv), on the unmasked stream
-            for (auto &e : h->hyb_ev) if (!e) HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
             PassParams ph = p;
             ph.split_hybrid = 1; ph.hybrid_step = (int32_t)m.hyb_S;
             ph.vt_begin = 0; ph.vt_end = INT64_MAX;
@@ -1072,18 +597,7 @@ static int analyze_device_locked(aegis_handle *h, const float *d_pcm, const int6
                 HIPCHK(h, hipStreamWaitEvent(sd, h->hyb_ev[1], 0));
             }
             HIPCHK(h, hipStreamWaitEvent(sd, h->hyb_ev[2], 0));
-            begin_event(h, "viterbi", sd);
-            if (m.split_auto) {
-                for (auto &e : h->split_ev) if (!e) HIPCHK(h, hipEventCreate(&e));
-                if (!split_started) { HIPCHK(h, hipEventRecord(h->split_ev[0], sd)); split_started = true; }
-            }
-            for (auto &e : h->fin_ev) if (!e) HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            hipError_t ve = launch_viterbi_split(ph, h->dt, t.log_trans_band.data(), d_seg_order, 0, d_lock_order, m.n_lock, sd, h->stream4, h->fin_ev);
-            if (m.split_auto) HIPCHK(h, hipEventRecord(h->split_ev[1], sd));
-            end_event(h, sd);
-            VCHK(ve);
-            h->split_checks.push_back({pi, ph});
-            ++h->split_stats[0]; h->split_stats[1] += m.n_seg;
+            if ((rc = launch_split(ph, 0, sd, h->stream4)) != AEGIS_OK) return rc;
         }
         // ---- finalize ---------------------------------------------------------------------------------------------------
         hipStream_t se = m.hybrid ? sd : sv;       // the stream the pass ends on
@@ -1114,13 +628,13 @@ static int analyze_device_locked(aegis_handle *h, const float *d_pcm, const int6
         const int64_t lo = sample_offsets[0], hi = sample_offsets[n_clips];
         launch_finite_check(d_pcm + lo, hi - lo, static_cast<unsigned long long *>(h->finite_flag.p), s);
     }
-    if (!h->split_checks.empty()) {         // (sync != 0: time-split passes are planned for blocking calls only)
+    if (!h->tsplit.checks.empty()) {         // (sync != 0: time-split passes are planned for blocking calls only)
         HIPCHK(h, hipStreamSynchronize(s));
-        for (const auto &sc : h->split_checks) {
+        for (const auto &sc : h->tsplit.checks) {
             const int rc = split_check(h, sc, s);
             if (rc != AEGIS_OK) return rc;
         }
-        h->split_checks.clear();
+        h->tsplit.checks.clear();
     }
     if (sync == 1) {
         HIPCHK(h, hipStreamSynchronize(s));
@@ -1134,8 +648,78 @@ static int analyze_device_locked(aegis_handle *h, const float *d_pcm, const int6
 }
 #undef VCHK
 
+// Runs `attempt` (one planned execution of a blocking call, up to the point where persist.gave_up is known) under the
+// handle's recovery policy.
+//  - The default pass size was taken from the device memory free when the handle was created; other handles, the caller's
+//    own buffers or a second workspace may have taken it since: on an allocation failure the passes are halved (down to
+//    2^21 frames) and the call planned again.
+//  - The single Viterbi launch of a balanced pass found the frame stage not running beside it (a profiler collecting
+//    counters serialises kernels, for one): this handle goes back to one launch per chunk for the next 16 calls and the
+//    call is repeated, once.  The give-up is not for good: whatever serialised the kernels may be gone by then.
+static int run_with_recovery(aegis_handle *h, const std::function<int()> &attempt) {
+    aegis_handle::Persistent &ps = h->persist;
+    if (!ps.on && h->knobs.persistent_wanted && ps.cooldown > 0 && --ps.cooldown == 0) ps.on = true;
+    for (bool repeated = false;;) {
+        const int rc = attempt();
+        if (rc == AEGIS_ERR_NOMEM && h->max_frames_per_pass > ((int64_t)1 << 21)) {
+            (void)hipDeviceSynchronize();
+            (void)hipGetLastError();
+            h->max_frames_per_pass = std::max<int64_t>((int64_t)1 << 21, h->max_frames_per_pass / 2);
+            continue;
+        }
+        if (rc == AEGIS_OK || !ps.gave_up || repeated) return rc;
+        ps.gave_up = false;
+        ps.on = false;
+        ps.cooldown = 16;
+        ++ps.fallbacks;
+        repeated = true;
+    }
+}
+
+int aegis_analyze_batch_device(aegis_handle *h, const float *d_pcm, const int64_t *sample_offsets,
+                               int32_t n_clips, double rake_sensitivity, uint32_t stages,
+                               aegis_outputs *dout, void *stream_v, int32_t sync) {
+    try {
+    if (!h) return AEGIS_ERR_INVALID;
+    std::lock_guard<std::mutex> lock(h->mu);
+    // (sync = 1: analyze_device_locked synchronises and reads the abort flag itself)
+    return run_with_recovery(h, [&] { return analyze_device_locked(h, d_pcm, sample_offsets, n_clips, rake_sensitivity, stages, dout, stream_v, sync); });
+    } catch (...) { return abi_fail(h); }
+}
+
+// The blocking host-fed analysis of aegis_analyze_batch and aegis_analyze_pcm (handle locked, io_pcm sized): the device
+// outputs, the pipeline fed by make_feed() (a fresh feed for every attempt), the outputs back to the host.
 static int host_fed_locked(aegis_handle *h, const std::vector<int64_t> &off, int64_t F, int32_t n_clips, double rake_sensitivity,
-                           uint32_t stages, aegis_outputs *out, const std::function<HostFeed()> &make_feed);
+                           uint32_t stages, aegis_outputs *out, const std::function<HostFeed()> &make_feed) {
+    int rc;
+    hipStream_t s = h->stream;
+    // the previous call's kernels may still read io_pcm only if it returned without a sync -- it never does
+    aegis_outputs d{};
+    const int nm = h->tab.n_mels;
+    for (const OutField &f : kOutFields) {
+        if (!(stages & f.stage) || !f.get(out)) continue;
+        if ((rc = ensure(h, h->*f.io, f.size(F, nm))) != AEGIS_OK) return rc;
+        f.set(&d, (h->*f.io).p);
+    }
+    // stream_v = NULL (the handle's own stream) and sync = 2: the schedule the device-pointer entry takes with
+    // sync = 1, single Viterbi launch included -- the attempt synchronises itself before it reads the abort flag
+    rc = run_with_recovery(h, [&]() -> int {
+        HostFeed feed = make_feed();
+        const int r = analyze_device_locked(h, static_cast<const float *>(h->io_pcm.p), off.data(), n_clips,
+                                            rake_sensitivity, stages, &d, nullptr, 2, &feed);
+        if (r != AEGIS_OK || !h->persist.pending) return r;
+        HIPCHK(h, hipStreamSynchronize(s));
+        return persistent_check(h);
+    });
+    if (rc != AEGIS_OK) return rc;
+    for (const OutField &f : kOutFields)
+        if (f.get(&d)) HIPCHK(h, hipMemcpyAsync(f.get(out), f.get(&d), f.size(F, nm), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    HIPCHK(h, hipStreamSynchronize(h->stream3));      // (a raw-byte feed's decoded samples back to the host)
+    h->plan_in_flight = false;
+    if (h->profiling) collect_events(h);
+    return finite_result(h, stages, off.data(), n_clips);
+}
 
 int aegis_analyze_batch(aegis_handle *h, const float *const *pcm, const int64_t *n_samples, int32_t n_clips,
                         double rake_sensitivity, uint32_t stages, aegis_outputs *out) {
@@ -1144,7 +728,7 @@ int aegis_analyze_batch(aegis_handle *h, const float *const *pcm, const int64_t 
     if (n_clips < 0 || (n_clips > 0 && (!pcm || !n_samples || !out))) { h->err = "null argument"; return AEGIS_ERR_INVALID; }
     if (n_clips == 0) return AEGIS_OK;
     if (stages & AEGIS_STAGE_RAKE) stages |= AEGIS_STAGE_MEL;
-    if (h->device < 0) { h->err = "handle was created with device=-1 (host tables only)"; return AEGIS_ERR_DEVICE; }
+    DEVICE_ONLY(h);
     std::lock_guard<std::mutex> lock(h->mu);
     HIPCHK(h, hipSetDevice(h->device));
     std::vector<int64_t> off(n_clips + 1, 0);
@@ -1161,68 +745,6 @@ int aegis_analyze_batch(aegis_handle *h, const float *const *pcm, const int64_t 
         return HostFeed{pcm, static_cast<float *>(h->io_pcm.p), std::vector<int64_t>((size_t)n_clips, 0)};
     });
     } catch (...) { return abi_fail(h); }
-}
-
-// The blocking host-fed analysis of aegis_analyze_batch and aegis_analyze_pcm (handle locked, io_pcm sized): the device
-// outputs, the pipeline fed by make_feed() (a fresh feed for every attempt), the outputs back to the host.
-static int host_fed_locked(aegis_handle *h, const std::vector<int64_t> &off, int64_t F, int32_t n_clips, double rake_sensitivity,
-                           uint32_t stages, aegis_outputs *out, const std::function<HostFeed()> &make_feed) {
-    int rc;
-    hipStream_t s = h->stream;
-    // the previous call's kernels may still read io_pcm only if it returned without a sync -- it never does
-    if (!h->persistent && h->knobs.persistent_wanted && h->persist_cooldown > 0 && --h->persist_cooldown == 0)
-        h->persistent = true;                 // as in aegis_analyze_batch_device: a give-up is not for good
-    aegis_outputs d{};
-    const int nm = h->tab.n_mels;
-    if ((stages & AEGIS_STAGE_PYIN) && out->f0) { if ((rc = ensure(h, h->io_f0, F * 8))) return rc; d.f0 = static_cast<double *>(h->io_f0.p); }
-    if ((stages & AEGIS_STAGE_PYIN) && out->voiced_flag) { if ((rc = ensure(h, h->io_voiced, F))) return rc; d.voiced_flag = static_cast<uint8_t *>(h->io_voiced.p); }
-    if ((stages & AEGIS_STAGE_MEL) && out->sdb_col_means) { if ((rc = ensure(h, h->io_colmean, F * 12))) return rc; d.sdb_col_means = static_cast<float *>(h->io_colmean.p); }
-    if ((stages & AEGIS_STAGE_PYIN) && out->pitch_bin) { if ((rc = ensure(h, h->io_bin, F * 2))) return rc; d.pitch_bin = static_cast<int16_t *>(h->io_bin.p); }
-    if ((stages & AEGIS_STAGE_PYIN) && out->voiced_prob) { if ((rc = ensure(h, h->io_vprob, F * 8))) return rc; d.voiced_prob = static_cast<double *>(h->io_vprob.p); }
-    if ((stages & AEGIS_STAGE_RMS) && out->rms) { if ((rc = ensure(h, h->io_rms, F * 4))) return rc; d.rms = static_cast<float *>(h->io_rms.p); }
-    if ((stages & AEGIS_STAGE_RAKE) && out->rake_mask) { if ((rc = ensure(h, h->io_rake, F))) return rc; d.rake_mask = static_cast<uint8_t *>(h->io_rake.p); }
-    if ((stages & AEGIS_STAGE_MEL) && out->S_dB) { if ((rc = ensure(h, h->io_sdb, F * nm * 4))) return rc; d.S_dB = static_cast<float *>(h->io_sdb.p); }
-    for (int attempt = 0;; ++attempt) {
-        // stream_v = NULL (the handle's own stream) and sync = 2: the schedule the device-pointer entry takes with
-        // sync = 1, single Viterbi launch included -- this function synchronises below
-        HostFeed feed = make_feed();
-        rc = analyze_device_locked(h, static_cast<const float *>(h->io_pcm.p), off.data(), n_clips,
-                                   rake_sensitivity, stages, &d, nullptr, 2, &feed);
-        if (rc == AEGIS_ERR_NOMEM && h->max_frames_per_pass > ((int64_t)1 << 21)) {      // as in aegis_analyze_batch_device
-            (void)hipDeviceSynchronize();
-            (void)hipGetLastError();
-            h->max_frames_per_pass = std::max<int64_t>((int64_t)1 << 21, h->max_frames_per_pass / 2);
-            --attempt;
-            continue;
-        }
-        if (rc != AEGIS_OK) return rc;
-        if (!h->persist_pending) break;
-        HIPCHK(h, hipStreamSynchronize(s));
-        if ((rc = persistent_check(h)) == AEGIS_OK) break;
-        if (!h->persist_gave_up || attempt > 0) return rc;
-        h->persist_gave_up = false;           // one launch per chunk for the next 16 calls, and this call again
-        h->persistent = false;
-        h->persist_cooldown = 16;
-        ++h->persistent_fallbacks;
-    }
-    if (d.f0) HIPCHK(h, hipMemcpyAsync(out->f0, d.f0, F * 8, hipMemcpyDeviceToHost, s));
-    if (d.voiced_flag) HIPCHK(h, hipMemcpyAsync(out->voiced_flag, d.voiced_flag, F, hipMemcpyDeviceToHost, s));
-    if (d.sdb_col_means) HIPCHK(h, hipMemcpyAsync(out->sdb_col_means, d.sdb_col_means, F * 12, hipMemcpyDeviceToHost, s));
-    if (d.pitch_bin) HIPCHK(h, hipMemcpyAsync(out->pitch_bin, d.pitch_bin, F * 2, hipMemcpyDeviceToHost, s));
-    if (d.voiced_prob) HIPCHK(h, hipMemcpyAsync(out->voiced_prob, d.voiced_prob, F * 8, hipMemcpyDeviceToHost, s));
-    if (d.rms) HIPCHK(h, hipMemcpyAsync(out->rms, d.rms, F * 4, hipMemcpyDeviceToHost, s));
-    if (d.rake_mask) HIPCHK(h, hipMemcpyAsync(out->rake_mask, d.rake_mask, F, hipMemcpyDeviceToHost, s));
-    if (d.S_dB) HIPCHK(h, hipMemcpyAsync(out->S_dB, d.S_dB, (size_t)F * nm * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    HIPCHK(h, hipStreamSynchronize(h->stream3));      // (a raw-byte feed's decoded samples back to the host)
-    h->plan_in_flight = false;
-    if ((rc = persistent_check(h)) != AEGIS_OK) return rc;
-    if (h->profiling) collect_events(h);
-    return finite_result(h, stages, off.data(), n_clips);
-}
-
-static int64_t pcm_width(int32_t fmt) {
-    return fmt == AEGIS_PCM_U8 ? 1 : fmt == AEGIS_PCM_S16 ? 2 : fmt == AEGIS_PCM_S24 ? 3 : fmt == AEGIS_PCM_S32 || fmt == AEGIS_PCM_F32 ? 4 : 0;
 }
 
 // samples of a clip at rate sr (audio_io.resampled_length); negative with a message for an invalid clip
@@ -1263,7 +785,7 @@ int aegis_analyze_pcm(aegis_handle *h, const aegis_pcm_clip *clips, int32_t n_cl
     if (n_clips < 0 || (n_clips > 0 && (!clips || (analyse && !out)))) { h->err = "null argument"; return AEGIS_ERR_INVALID; }
     if (!analyse && !y_out) { h->err = "stages == 0 decodes only and needs y_out"; return AEGIS_ERR_INVALID; }
     if (n_clips == 0) return AEGIS_OK;
-    if (h->device < 0) { h->err = "handle was created with device=-1 (host tables only)"; return AEGIS_ERR_DEVICE; }
+    DEVICE_ONLY(h);
     std::lock_guard<std::mutex> lock(h->mu);
     HIPCHK(h, hipSetDevice(h->device));
     const int32_t sr = h->tab.sr;
@@ -1344,1085 +866,6 @@ int aegis_analyze_pcm(aegis_handle *h, const aegis_pcm_clip *clips, int32_t n_cl
         pf.range_used = 0;
         return HostFeed{nullptr, d_pcm, std::vector<int64_t>((size_t)n_clips, 0), &pf};
     });
-    } catch (...) { return abi_fail(h); }
-}
-
-int aegis_rake_patterns(aegis_handle *h, const float *S_dB, int32_t n_mels, int64_t n_frames,
-                        double broadband_threshold_ratio, uint8_t *mask_out) {
-    try {
-    if (!h) return AEGIS_ERR_INVALID;
-    if (n_mels <= 0 || n_frames < 0 || (n_frames > 0 && (!S_dB || !mask_out))) { h->err = "bad argument"; return AEGIS_ERR_INVALID; }
-    if (n_frames == 0) return AEGIS_OK;
-    if (h->device < 0) { h->err = "handle was created with device=-1 (host tables only)"; return AEGIS_ERR_DEVICE; }
-    std::lock_guard<std::mutex> lock(h->mu);
-    HIPCHK(h, hipSetDevice(h->device));
-    int rc;
-    const size_t img = (size_t)n_mels * n_frames * 4;
-    if ((rc = ensure(h, h->io_sdb, img)) != AEGIS_OK) return rc;
-    if ((rc = ensure(h, h->rk_raw, n_frames)) != AEGIS_OK) return rc;
-    if ((rc = ensure(h, h->io_rake, n_frames)) != AEGIS_OK) return rc;
-    hipStream_t s = h->stream;
-    HIPCHK(h, hipMemcpyAsync(h->io_sdb.p, S_dB, img, hipMemcpyHostToDevice, s));
-    const double ms_per_frame = ((double)h->tab.hop / (double)h->tab.sr) * 1000;   // vision.py:23-25
-    launch_rake_from_db(static_cast<const float *>(h->io_sdb.p), n_mels, n_frames, broadband_threshold_ratio,
-                        (int)(10 / ms_per_frame), (int)(30 / ms_per_frame), static_cast<uint8_t *>(h->rk_raw.p),
-                        static_cast<uint8_t *>(h->io_rake.p), s);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(mask_out, h->io_rake.p, n_frames, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    return AEGIS_OK;
-    } catch (...) { return abi_fail(h); }
-}
-
-// the bank of (n_bins, bins_per_octave, fmin, filter_scale), built and uploaded on first use
-static int cqt_bank_locked(aegis_handle *h, int32_t &n_bins, int32_t &bins_per_octave, double &fmin, double &filter_scale, hipStream_t s) {
-    if (n_bins == 0) n_bins = 84;
-    if (bins_per_octave == 0) bins_per_octave = 12;
-    if (!(fmin > 0)) fmin = 32.70319566257483;            // note_to_hz('C1')
-    if (!(filter_scale > 0)) filter_scale = 1.0;
-    CqtBank &b = h->cqt_bank;
-    if (b.n_bins != n_bins || b.bins_per_octave != bins_per_octave || b.fmin != fmin || b.filter_scale != filter_scale || !b.dev) {
-        HIPCHK(h, hipStreamSynchronize(s));
-        if (b.dev) { (void)hipFree(b.dev); b.dev = nullptr; }
-        const char *msg = build_cqt_bank(b, h->tab.sr, n_bins, fmin, bins_per_octave, filter_scale);
-        if (msg[0]) { h->err = msg; b.n_bins = 0; return AEGIS_ERR_INVALID; }
-        // + 64 KiB: the slide kernel refills a tile's register queue unconditionally, so a wave's last groups request up to
-        // kSlotDepth KiB past its stream (never used)
-        HIPCHK(h, hipMalloc(reinterpret_cast<void **>(&b.dev), b.data.size() * 4 + 65536));
-        HIPCHK(h, hipMemset(reinterpret_cast<char *>(b.dev) + b.data.size() * 4, 0, 65536));
-        HIPCHK(h, hipMemcpy(b.dev, b.data.data(), b.data.size() * 4, hipMemcpyHostToDevice));
-    }
-    return AEGIS_OK;
-}
-
-// clip geometry on the device + the launch; d_pcm and d_out are device pointers
-static int cqt_launch_locked(aegis_handle *h, const float *d_pcm, const int64_t *soff, int32_t n_clips, float *d_out, hipStream_t s,
-                             int64_t *total_frames) {
-    std::vector<int64_t> foff(n_clips + 1, 0), toff(n_clips + 1, 0);
-    for (int i = 0; i < n_clips; ++i) {
-        const int64_t n = soff[i + 1] - soff[i];
-        if (n < 0) { h->err = "sample_offsets must be non-decreasing"; return AEGIS_ERR_INVALID; }
-        foff[i + 1] = foff[i] + 1 + n / h->tab.hop;
-        toff[i + 1] = toff[i] + (1 + n / h->tab.hop + kCqtSlideFrames - 1) / kCqtSlideFrames;
-    }
-    int rc;
-    if ((rc = ensure(h, h->q_soff, (n_clips + 1) * 8)) != AEGIS_OK) return rc;
-    if ((rc = ensure(h, h->q_foff, (n_clips + 1) * 8)) != AEGIS_OK) return rc;
-    if ((rc = ensure(h, h->q_toff, (n_clips + 1) * 8)) != AEGIS_OK) return rc;
-    // (pageable host vectors: the copies complete before hipMemcpyAsync returns)
-    HIPCHK(h, hipMemcpyAsync(h->q_soff.p, soff, (n_clips + 1) * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(h->q_foff.p, foff.data(), (n_clips + 1) * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(h->q_toff.p, toff.data(), (n_clips + 1) * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipStreamSynchronize(s));         // ... but the vectors die with this frame: make it certain
-    CqtArgs a{d_pcm, static_cast<const int64_t *>(h->q_soff.p), static_cast<const int64_t *>(h->q_foff.p), n_clips,
-              foff[n_clips], h->tab.hop, d_out};
-    if (h->profiling) { for (auto &ev : h->events) { (void)hipEventDestroy(ev.second.first); (void)hipEventDestroy(ev.second.second); } h->events.clear(); }
-    begin_event(h, "cqt", s); launch_cqt(a, h->cqt_bank, static_cast<const int64_t *>(h->q_toff.p), toff[n_clips], s); end_event(h, s);
-    HIPCHK(h, hipGetLastError());
-    *total_frames = foff[n_clips];
-    return AEGIS_OK;
-}
-
-int aegis_cqt(aegis_handle *h, const float *const *pcm, const int64_t *n_samples, int32_t n_clips,
-              int32_t n_bins, int32_t bins_per_octave, double fmin, double filter_scale, float *mag_out) {
-    try {
-    if (!h) return AEGIS_ERR_INVALID;
-    if (n_clips < 0 || (n_clips > 0 && (!pcm || !n_samples || !mag_out))) { h->err = "null argument"; return AEGIS_ERR_INVALID; }
-    if (n_clips == 0) return AEGIS_OK;
-    if (h->device < 0) { h->err = "handle was created with device=-1 (host tables only)"; return AEGIS_ERR_DEVICE; }
-    std::lock_guard<std::mutex> lock(h->mu);
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = h->stream;
-    int rc;
-    if ((rc = cqt_bank_locked(h, n_bins, bins_per_octave, fmin, filter_scale, s)) != AEGIS_OK) return rc;
-    std::vector<int64_t> soff(n_clips + 1, 0);
-    int64_t F = 0;
-    for (int i = 0; i < n_clips; ++i) {
-        if (n_samples[i] < 0 || (n_samples[i] > 0 && !pcm[i])) { h->err = "bad clip " + std::to_string(i); return AEGIS_ERR_INVALID; }
-        soff[i + 1] = soff[i] + n_samples[i];
-        F += 1 + n_samples[i] / h->tab.hop;
-    }
-    if ((rc = ensure(h, h->q_pcm, (size_t)std::max<int64_t>(soff[n_clips], 1) * 4)) != AEGIS_OK) return rc;
-    if ((rc = ensure(h, h->q_out, (size_t)F * n_bins * 4)) != AEGIS_OK) return rc;
-    for (int i = 0; i < n_clips; ++i)
-        if (n_samples[i] > 0)
-            HIPCHK(h, hipMemcpyAsync(static_cast<float *>(h->q_pcm.p) + soff[i], pcm[i], n_samples[i] * 4, hipMemcpyHostToDevice, s));
-    int64_t Fd = 0;
-    if ((rc = cqt_launch_locked(h, static_cast<const float *>(h->q_pcm.p), soff.data(), n_clips, static_cast<float *>(h->q_out.p), s, &Fd)) != AEGIS_OK) return rc;
-    HIPCHK(h, hipMemcpyAsync(mag_out, h->q_out.p, (size_t)F * n_bins * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    if (h->profiling) collect_events(h);
-    return AEGIS_OK;
-    } catch (...) { return abi_fail(h); }
-}
-
-int aegis_chroma_cqt(aegis_handle *h, const float *const *pcm, const int64_t *n_samples, int32_t n_clips,
-                     int32_t n_bins, int32_t bins_per_octave, double fmin, double filter_scale, int32_t n_chroma,
-                     const int32_t *bin_class, float *chroma_out) {
-    try {
-    if (!h) return AEGIS_ERR_INVALID;
-    if (n_clips < 0 || (n_clips > 0 && (!pcm || !n_samples || !chroma_out)) || !bin_class) { h->err = "null argument"; return AEGIS_ERR_INVALID; }
-    if (n_clips == 0) return AEGIS_OK;
-    if (n_chroma < 1 || n_chroma > 24) { h->err = "n_chroma must be 1..24"; return AEGIS_ERR_INVALID; }
-    if (h->device < 0) { h->err = "handle was created with device=-1 (host tables only)"; return AEGIS_ERR_DEVICE; }
-    std::lock_guard<std::mutex> lock(h->mu);
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = h->stream;
-    int rc;
-    if ((rc = cqt_bank_locked(h, n_bins, bins_per_octave, fmin, filter_scale, s)) != AEGIS_OK) return rc;
-    for (int b = 0; b < n_bins; ++b)
-        if (bin_class[b] < 0 || bin_class[b] >= n_chroma) { h->err = "bin_class entries must lie in [0, n_chroma)"; return AEGIS_ERR_INVALID; }
-    std::vector<int64_t> soff(n_clips + 1, 0);
-    int64_t F = 0;
-    for (int i = 0; i < n_clips; ++i) {
-        if (n_samples[i] < 0 || (n_samples[i] > 0 && !pcm[i])) { h->err = "bad clip " + std::to_string(i); return AEGIS_ERR_INVALID; }
-        soff[i + 1] = soff[i] + n_samples[i];
-        F += 1 + n_samples[i] / h->tab.hop;
-    }
-    if ((rc = ensure(h, h->q_pcm, (size_t)std::max<int64_t>(soff[n_clips], 1) * 4)) != AEGIS_OK) return rc;
-    if ((rc = ensure(h, h->q_out, (size_t)F * n_bins * 4)) != AEGIS_OK) return rc;
-    if ((rc = ensure(h, h->q_chroma, (size_t)F * n_chroma * 4)) != AEGIS_OK) return rc;
-    if ((rc = ensure(h, h->q_cls, (size_t)n_bins * 4)) != AEGIS_OK) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->q_cls.p, bin_class, (size_t)n_bins * 4, hipMemcpyHostToDevice, s));
-    for (int i = 0; i < n_clips; ++i)
-        if (n_samples[i] > 0)
-            HIPCHK(h, hipMemcpyAsync(static_cast<float *>(h->q_pcm.p) + soff[i], pcm[i], n_samples[i] * 4, hipMemcpyHostToDevice, s));
-    int64_t Fd = 0;
-    if ((rc = cqt_launch_locked(h, static_cast<const float *>(h->q_pcm.p), soff.data(), n_clips, static_cast<float *>(h->q_out.p), s, &Fd)) != AEGIS_OK) return rc;
-    begin_event(h, "chroma", s);
-    launch_chroma_fold(static_cast<const float *>(h->q_out.p), static_cast<const int64_t *>(h->q_foff.p), n_clips, F, n_bins, n_chroma,
-                       static_cast<const int32_t *>(h->q_cls.p), static_cast<float *>(h->q_chroma.p), s);
-    end_event(h, s);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(chroma_out, h->q_chroma.p, (size_t)F * n_chroma * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    if (h->profiling) collect_events(h);
-    return AEGIS_OK;
-    } catch (...) { return abi_fail(h); }
-}
-
-int aegis_cqt_device(aegis_handle *h, const float *d_pcm, const int64_t *sample_offsets, int32_t n_clips,
-                     int32_t n_bins, int32_t bins_per_octave, double fmin, double filter_scale, float *d_mag_out,
-                     void *stream, int32_t sync) {
-    try {
-    if (!h) return AEGIS_ERR_INVALID;
-    if (n_clips < 0 || (n_clips > 0 && (!sample_offsets || !d_mag_out))) { h->err = "null argument"; return AEGIS_ERR_INVALID; }
-    if (n_clips == 0) return AEGIS_OK;
-    if (h->device < 0) { h->err = "handle was created with device=-1 (host tables only)"; return AEGIS_ERR_DEVICE; }
-    if (sample_offsets[n_clips] > sample_offsets[0] && !d_pcm) { h->err = "d_pcm == NULL"; return AEGIS_ERR_INVALID; }
-    std::lock_guard<std::mutex> lock(h->mu);
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
-    int rc;
-    if ((rc = cqt_bank_locked(h, n_bins, bins_per_octave, fmin, filter_scale, s)) != AEGIS_OK) return rc;
-    int64_t F = 0;
-    if ((rc = cqt_launch_locked(h, d_pcm, sample_offsets, n_clips, d_mag_out, s, &F)) != AEGIS_OK) return rc;
-    if (sync) {
-        HIPCHK(h, hipStreamSynchronize(s));
-        if (h->profiling) collect_events(h);
-    }
-    return AEGIS_OK;
-    } catch (...) { return abi_fail(h); }
-}
-
-// ---- streaming -------------------------------------------------------------------------------
-static PassParams stream_params(aegis_stream *st, const int64_t *dm) {
-    aegis_handle *h = st->h;
-    const Tables &t = h->tab;
-    PassParams p = base_params(t);
-    p.stages = AEGIS_STAGE_ALL;
-    p.pcm = static_cast<const float *>(st->pcm.p);
-    p.sample_off = dm; p.sample_len = dm + 1; p.frame_off = dm + 2; p.out_off = dm + 2; p.sel_off = dm + 4;
-    p.chunk_off = const_cast<int64_t *>(dm + 6);
-    p.order = reinterpret_cast<const int32_t *>(dm + 8);
-    p.n_clips = 1;
-    p.dfn = static_cast<double *>(st->dfn.p); p.lag_stride = h->lag_stride;
-    p.yin = nullptr; p.yin_stride = h->yin_stride;
-    p.cmnd_in_frame = cmnd_in_frame(h); p.troughs = troughs_in_frame(h);
-    p.logobs = static_cast<double *>(st->logobs.p); p.obs_stride = h->obs_stride;
-    p.logunv = static_cast<double *>(st->logunv.p);
-    p.obs_seg = static_cast<int32_t *>(st->obs_seg.p);
-    p.ptr = static_cast<uint16_t *>(st->ptr.p); p.cmap = static_cast<uint16_t *>(st->cmap.p);
-    p.bnd = static_cast<int32_t *>(st->bnd.p); p.states = static_cast<int32_t *>(st->states.p);
-    p.live_states = static_cast<int32_t *>(st->live.p);
-    p.melpow = static_cast<float *>(st->melpow.p); p.clipmax = static_cast<uint32_t *>(st->clipmax.p);
-    p.rake_raw = static_cast<uint8_t *>(st->rake_raw.p);
-    p.vstate = static_cast<double *>(st->vstate.p);
-    p.out_vprob = static_cast<double *>(st->o_vprob.p);
-    p.out_rms = static_cast<float *>(st->o_rms.p);
-    p.out_f0 = static_cast<double *>(st->o_f0.p); p.out_voiced = static_cast<uint8_t *>(st->o_voiced.p);
-    p.out_rake = static_cast<uint8_t *>(st->o_rake.p); p.out_sdb = static_cast<float *>(st->o_sdb.p);
-    p.rake_ratio = 0.6;
-    const double ms_per_frame = ((double)t.hop / (double)t.sr) * 1000;
-    p.rake_min_frames = (int)(10 / ms_per_frame); p.rake_max_frames = (int)(30 / ms_per_frame);
-    return p;
-}
-
-// Captures one fixed-size push as a hipGraph: H2D of the samples, advance (append + geometry), the four
-// analysis kernels reading their geometry from the device control block, result gather, D2H.
-static StreamCommitCtl *stream_commit_ctl(aegis_stream *st) {
-    return reinterpret_cast<StreamCommitCtl *>(static_cast<unsigned char *>(st->ctl.p) + sizeof(StreamCtl));
-}
-
-static bool stream_build_graph(aegis_stream *st, int64_t n_push, hipStream_t s, int commit) {
-    aegis_handle *h = st->h;
-    const Tables &t = h->tab;
-    if (!st->pin_samples || !st->pin_result || (commit && !st->pin_commit) || n_push > 8192 || n_push % t.hop != 0 || n_push / t.hop + 1 > 8) return false;
-    StreamCtl *ctl = static_cast<StreamCtl *>(st->ctl.p);
-    PassParams p = stream_params(st, ctl->meta);      // device address arithmetic only
-    p.ctl = ctl;
-    p.n_frames = st->cap_frames;
-    p.n_sel = n_push / t.hop + 1;                       // launch sizes; the kernels clamp to ctl->n_sel
-    if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) != hipSuccess) return false;
-    bool ok = true;
-    ok &= hipMemcpyAsync(st->g_staging.p, st->pin_samples, n_push * 4, hipMemcpyHostToDevice, s) == hipSuccess;
-    launch_stream_advance(ctl, static_cast<const float *>(st->g_staging.p), (int)n_push, static_cast<float *>(st->pcm.p), t.hop, s);
-    launch_frame(p, h->dt, s);
-    launch_pyin_obs(p, h->dt, s);
-    ok &= launch_viterbi(p, h->dt, t.log_trans_band.data(), s) == hipSuccess;
-    if (commit)
-        ok &= launch_stream_commit(ctl, 0, stream_commit_ctl(st), p.ptr, p.vstate, t.n_bins, static_cast<int16_t *>(st->c_bins.p),
-                                   st->c_result.p, s) == hipSuccess;
-    launch_stream_gather(ctl, p.out_rms, p.out_vprob, p.live_states, st->g_result.p, s);
-    ok &= hipMemcpyAsync(st->pin_result, st->g_result.p, 256, hipMemcpyDeviceToHost, s) == hipSuccess;
-    if (commit) ok &= hipMemcpyAsync(st->pin_commit, st->c_result.p, kCommitResultBytes, hipMemcpyDeviceToHost, s) == hipSuccess;
-    hipGraph_t g = nullptr;
-    ok &= hipStreamEndCapture(s, &g) == hipSuccess && g != nullptr;
-    if (!ok) { if (g) (void)hipGraphDestroy(g); (void)hipGetLastError(); return false; }
-    hipGraphExec_t ex = nullptr;
-    if (hipGraphInstantiate(&ex, g, nullptr, nullptr, 0) != hipSuccess) { (void)hipGraphDestroy(g); (void)hipGetLastError(); return false; }
-    st->graph[commit] = g; st->graph_exec[commit] = ex; st->graph_push[commit] = n_push;
-    return true;
-}
-
-static int stream_run(aegis_stream *st, int64_t f_lo, int64_t f_hi, bool final_pass, hipStream_t s) {
-    // analyses frames [f_lo, f_hi) and advances the Viterbi over them; final_pass also finishes the
-    // back-trace and the clip-global stages
-    aegis_handle *h = st->h;
-    const Tables &t = h->tab;
-    const int S = 2 * t.n_bins;
-    const int64_t Ftot = final_pass ? f_hi : st->cap_frames;     // clip length as far as the kernels know
-    // meta layout (int64): sample_off[2] | frame_off[2] | sel_off[2] | chunk_off[2] | order (int32 in one slot)
-    st->host_meta.assign(9, 0);
-    st->host_meta[1] = st->n_samples;
-    st->host_meta[3] = Ftot;
-    st->host_meta[5] = f_hi - f_lo;
-    st->host_meta[7] = (Ftot - 1 + kViterbiChunk - 1) / kViterbiChunk;
-    HIPCHK(h, hipMemcpyAsync(st->meta.p, st->host_meta.data(), 9 * 8, hipMemcpyHostToDevice, s));
-    const int64_t *dm = static_cast<const int64_t *>(st->meta.p);
-    PassParams p = stream_params(st, dm);
-    p.n_frames = Ftot;
-    p.t_begin = f_lo; p.n_sel = f_hi - f_lo;
-    p.vt_begin = f_lo; p.vt_end = final_pass ? INT64_MAX : f_hi;
-    (void)S;
-    if (p.n_sel > 0) {
-        launch_frame(p, h->dt, s);
-        launch_pyin_obs(p, h->dt, s);
-    }
-    if (p.n_sel > 0 || final_pass) {
-        hipError_t ve = launch_viterbi(p, h->dt, t.log_trans_band.data(), s);
-        if (ve != hipSuccess) { h->err = std::string("viterbi launch: ") + hipGetErrorString(ve); return AEGIS_ERR_DEVICE; }
-    }
-    HIPCHK(h, hipGetLastError());
-    return AEGIS_OK;
-}
-
-// Releases everything a stream owns.  The caller holds h->mu, or the stream was never handed out.
-static void stream_release(aegis_stream *st) noexcept {
-    if (st->h && st->h->device >= 0) { (void)hipSetDevice(st->h->device); (void)hipStreamSynchronize(st->h->stream); }
-    for (int k = 0; k < 2; ++k) {
-        if (st->graph_exec[k]) (void)hipGraphExecDestroy(st->graph_exec[k]);
-        if (st->graph[k]) (void)hipGraphDestroy(st->graph[k]);
-    }
-    if (st->pin_samples) (void)hipHostFree(st->pin_samples);
-    if (st->pin_result) (void)hipHostFree(st->pin_result);
-    if (st->pin_commit) (void)hipHostFree(st->pin_commit);
-    for (DevBuf *b : {&st->c_bins, &st->c_result, &st->ctl, &st->g_staging, &st->g_result, &st->pcm, &st->dfn, &st->logobs, &st->logunv, &st->obs_seg, &st->ptr, &st->cmap, &st->bnd, &st->states,
-                      &st->live, &st->melpow, &st->clipmax, &st->rake_raw, &st->vstate, &st->meta, &st->o_f0, &st->o_voiced,
-                      &st->o_vprob, &st->o_rms, &st->o_rake, &st->o_sdb})
-        free_buf(*b);
-    delete st;
-}
-
-static int stream_open_locked(aegis_handle *h, int64_t max_samples, aegis_stream *st) {
-    HIPCHK(h, hipSetDevice(h->device));
-    st->h = h;
-    const Tables &t = h->tab;
-    st->cap_samples = max_samples;
-    st->cap_frames = 1 + max_samples / t.hop;
-    const int64_t F = st->cap_frames, S = 2 * t.n_bins;
-    const int64_t nch = (F - 1 + kViterbiChunk - 1) / kViterbiChunk + 1;
-    int rc = AEGIS_OK;
-    auto need = [&](DevBuf &b, size_t bytes) { if (rc == AEGIS_OK) rc = ensure(h, b, bytes); };
-    need(st->pcm, max_samples * 4); need(st->dfn, F * h->lag_stride * 8);
-    need(st->logobs, F * h->obs_stride * 8); need(st->logunv, F * 8); need(st->obs_seg, F * 4); need(st->ptr, F * S * 2);
-    need(st->cmap, nch * S * 2); need(st->bnd, nch * 4); need(st->states, F * 4); need(st->live, F * 4);
-    need(st->melpow, F * t.n_mels * 4); need(st->clipmax, 16); need(st->rake_raw, F); need(st->vstate, S * 8);
-    need(st->meta, 9 * 8); need(st->ctl, sizeof(StreamCtl) + sizeof(StreamCommitCtl)); need(st->g_staging, 8192 * 4); need(st->g_result, 256);
-    need(st->c_bins, F * 2); need(st->c_result, kCommitResultBytes);
-    need(st->o_f0, F * 8); need(st->o_voiced, F); need(st->o_vprob, F * 8); need(st->o_rms, F * 4); need(st->o_rake, F);
-    need(st->o_sdb, F * t.n_mels * 4);
-    if (rc != AEGIS_OK) return rc;
-    HIPCHK(h, hipMemsetAsync(st->clipmax.p, 0, 16, h->stream));
-    // The band Viterbi leaves the back-pointer of a dead voiced state unwritten, and a launch that starts inside a 16-step
-    // chunk (any push that is not a whole number of chunks) walks the rows of the chunk's earlier steps for EVERY state to
-    // rebuild its chunk map (viterbi_band.inc, "rebuilds org from the HBM pointers").  What it reads for a dead state is
-    // never used, but it is used as the next index: with recycled memory behind the rows an index up to 65535 reaches
-    // 128 KB past a short stream's last row (an illegal access on a 0.5 s stream, met in the test suite).  Zeroed rows keep
-    // every such index at state 0.
-    HIPCHK(h, hipMemsetAsync(st->ptr.p, 0, (size_t)F * S * 2, h->stream));
-    {
-        struct { StreamCtl ctl; StreamCommitCtl commit; } c0{};
-        static_assert(sizeof(c0) == sizeof(StreamCtl) + sizeof(StreamCommitCtl), "the commit block sits right behind the control block");
-        c0.ctl.meta[3] = st->cap_frames;
-        c0.ctl.meta[7] = (st->cap_frames - 1 + kViterbiChunk - 1) / kViterbiChunk;
-        c0.commit.frontier = -1; c0.commit.newest = -1;
-        HIPCHK(h, hipMemcpyAsync(st->ctl.p, &c0, sizeof(c0), hipMemcpyHostToDevice, h->stream));
-    }
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (hipHostMalloc(reinterpret_cast<void **>(&st->pin_samples), 8192 * 4, hipHostMallocDefault) != hipSuccess) st->pin_samples = nullptr;
-    if (hipHostMalloc(reinterpret_cast<void **>(&st->pin_result), 256, hipHostMallocDefault) != hipSuccess) st->pin_result = nullptr;
-    if (hipHostMalloc(reinterpret_cast<void **>(&st->pin_commit), kCommitResultBytes, hipHostMallocDefault) != hipSuccess) st->pin_commit = nullptr;
-    // AEGIS_STREAM_GRAPH=0 keeps every push on the plain-launch path, =1 allows the hipGraph replay.  Unset: the replay,
-    // except under an injected rocprofiler tool -- round 1's SIGSEGV in aegis_stream_push (profiles/
-    // r1_stream_push_sigsegv_symbolised.txt) was the profiler-side packet copy of an INTERCEPTED queue running off the end
-    // of a 1 MiB AQL ring when the HIP runtime rang the doorbell for a graph launch: not this library's memory, and not
-    // something this library can fix, so profiled runs take the plain launches unless told otherwise.
-    if (const char *e = std::getenv("AEGIS_STREAM_GRAPH")) st->graph_failed = (e[0] == '0');
-    else {
-        const char *tool = std::getenv("ROCP_TOOL_LIBRARIES"), *pre = std::getenv("LD_PRELOAD");
-        if ((tool && tool[0]) || (pre && std::strstr(pre, "rocprofiler"))) st->graph_failed = true;
-    }
-    return AEGIS_OK;
-}
-
-int aegis_stream_open(aegis_handle *h, int64_t max_samples, aegis_stream **out) {
-    aegis_stream *st = nullptr;
-    try {
-    if (!h || !out || max_samples <= 0) { if (h) h->err = "bad argument"; return AEGIS_ERR_INVALID; }
-    *out = nullptr;
-    if (h->device < 0) { h->err = "handle was created with device=-1 (host tables only)"; return AEGIS_ERR_DEVICE; }
-    std::lock_guard<std::mutex> lock(h->mu);
-    if (h->destroy_requested) { h->err = "handle was destroyed"; return AEGIS_ERR_INVALID; }
-    st = new (std::nothrow) aegis_stream();
-    if (!st) { h->err = "out of host memory"; return AEGIS_ERR_NOMEM; }
-    const int rc = stream_open_locked(h, max_samples, st);
-    if (rc != AEGIS_OK) { stream_release(st); st = nullptr; return rc; }     // nothing leaks on a failed open
-    ++h->open_streams;
-    *out = st;
-    return AEGIS_OK;
-    } catch (...) {
-        const int code = abi_fail(h);
-        if (st) stream_release(st);
-        return code;
-    }
-}
-
-void aegis_stream_free(aegis_stream *st) {
-    if (!st) return;
-    aegis_handle *h = st->h;
-    if (!h) { stream_release(st); return; }
-    bool last;
-    {
-        std::lock_guard<std::mutex> lock(h->mu);
-        stream_release(st);
-        --h->open_streams;
-        last = h->destroy_requested && h->open_streams == 0;
-    }
-    if (last) destroy_now(h);     // aegis_destroy() was called while this stream was still open
-}
-
-// The host's half of a commit push, after the stream has drained: `res` is the commit kernel's result block (nullptr: no
-// launch was needed, the device frontier is where it was).  Hands out the next decided frames, `cap` at most.
-static int stream_deliver(aegis_stream *st, const unsigned char *res, aegis_stream_commit *commit) {
-    aegis_handle *h = st->h;
-    int64_t staged_lo = -1;
-    if (res) {
-        int64_t r[4];
-        std::memcpy(r, res, 32);
-        if (r[3] < 0) { h->err = "stream commit: the walk met a back-pointer the Viterbi never wrote"; return AEGIS_ERR_DEVICE; }
-        if (r[0] != st->c_frontier || r[1] < r[0] || r[1] >= st->frames_done) {
-            h->err = "stream commit: device and host disagree on the frontier"; return AEGIS_ERR_DEVICE;
-        }
-        staged_lo = r[0] + 1;
-        st->c_frontier = r[1];
-        st->c_walked = r[3] & 0xffffffff;
-        st->c_walked_wide = r[3] >> 32;
-        st->c_newest = st->frames_done - 1;
-    } else {
-        st->c_walked = st->c_walked_wide = 0;
-    }
-    const int64_t first = st->c_delivered;
-    const int64_t k = std::min<int64_t>(st->c_frontier + 1 - first, commit->cap);
-    if (k > 0) {
-        if (staged_lo >= 0 && first >= staged_lo && first + k <= staged_lo + kCommitStage)
-            std::memcpy(commit->pitch_bin, res + 32 + 2 * (first - staged_lo), (size_t)k * 2);
-        else
-            HIPCHK(h, hipMemcpy(commit->pitch_bin, static_cast<int16_t *>(st->c_bins.p) + first, (size_t)k * 2, hipMemcpyDeviceToHost));
-        st->c_delivered += k;
-    }
-    commit->first = first;
-    commit->count = k > 0 ? k : 0;
-    commit->frontier = st->c_delivered - 1;
-    commit->walked = st->c_walked;
-    commit->walked_wide = st->c_walked_wide;
-    return AEGIS_OK;
-}
-
-// aegis_stream_push (commit == nullptr: exactly the launches of a stream without the commit) and aegis_stream_push_commit.
-// The caller holds h->mu.
-static int stream_push_locked(aegis_stream *st, const float *samples, int64_t n, aegis_stream_frames *out, int64_t *n_frames,
-                              aegis_stream_commit *commit) {
-    aegis_handle *h = st->h;
-    if (h->destroy_requested) { h->err = "handle was destroyed"; return AEGIS_ERR_INVALID; }
-    if (n < 0 || (n > 0 && !samples) || !n_frames) { h->err = "bad argument"; return AEGIS_ERR_INVALID; }
-    if (commit && (commit->cap < 0 || (commit->cap > 0 && !commit->pitch_bin))) { h->err = "bad argument"; return AEGIS_ERR_INVALID; }
-    if (st->closed) { h->err = "stream is closed"; return AEGIS_ERR_INVALID; }
-    if (st->n_samples + n > st->cap_samples) { h->err = "stream capacity exceeded"; return AEGIS_ERR_INVALID; }
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = h->stream;
-    const int ci = commit ? 1 : 0;
-    // ---- fixed-size pushes replay a captured hipGraph ---------------------------------------------
-    const bool eligible = n > 0 && n <= 8192 && n % h->tab.hop == 0 && n / h->tab.hop + 1 <= 8;
-    if (eligible && !st->graph_failed && (st->graph_exec[ci] == nullptr || st->graph_push[ci] == n)) {
-        if (st->graph_exec[ci] == nullptr && !stream_build_graph(st, n, s, ci)) st->graph_failed = true;
-        if (st->graph_exec[ci] != nullptr && st->graph_push[ci] == n) {
-            std::memcpy(st->pin_samples, samples, (size_t)n * 4);
-            HIPCHK(h, hipGraphLaunch(st->graph_exec[ci], s));
-            HIPCHK(h, hipStreamSynchronize(s));
-            st->n_samples += n;
-            const int64_t ready = st->n_samples >= kFrameLength / 2 ? (st->n_samples - kFrameLength / 2) / h->tab.hop + 1 : 0;
-            const int64_t lo = st->frames_done, hi = std::max(lo, ready);
-            int64_t got = 0;
-            std::memcpy(&got, st->pin_result, 8);
-            if (got != hi - lo) { h->err = "stream graph and host disagree on the frame count"; return AEGIS_ERR_DEVICE; }
-            st->frames_done = hi;
-            *n_frames = got;
-            if (out) {
-                if (out->rms) std::memcpy(out->rms, st->pin_result + 8, (size_t)got * 4);
-                if (out->voiced_prob) std::memcpy(out->voiced_prob, st->pin_result + 8 + 32, (size_t)got * 8);
-                if (out->live_state) std::memcpy(out->live_state, st->pin_result + 8 + 32 + 64, (size_t)got * 4);
-            }
-            return commit ? stream_deliver(st, st->pin_commit, commit) : AEGIS_OK;
-        }
-    }
-    if (n > 0)
-        HIPCHK(h, hipMemcpyAsync(static_cast<float *>(st->pcm.p) + st->n_samples, samples, n * 4, hipMemcpyHostToDevice, s));
-    st->n_samples += n;
-    // frames whose centred window [t*hop - 1024, t*hop + 1024) is complete
-    const int hop = h->tab.hop;
-    const int64_t ready = st->n_samples >= kFrameLength / 2 ? (st->n_samples - kFrameLength / 2) / hop + 1 : 0;
-    const int64_t lo = st->frames_done, hi = std::max(lo, ready);
-    *n_frames = hi - lo;
-    if (hi > lo) {
-        int rc = stream_run(st, lo, hi, false, s);
-        if (rc != AEGIS_OK) return rc;
-        st->frames_done = hi;
-        if (out) {
-            const int64_t k = hi - lo;
-            if (out->rms) HIPCHK(h, hipMemcpyAsync(out->rms, static_cast<float *>(st->o_rms.p) + lo, k * 4, hipMemcpyDeviceToHost, s));
-            if (out->voiced_prob) HIPCHK(h, hipMemcpyAsync(out->voiced_prob, static_cast<double *>(st->o_vprob.p) + lo, k * 8, hipMemcpyDeviceToHost, s));
-            if (out->live_state) HIPCHK(h, hipMemcpyAsync(out->live_state, static_cast<int32_t *>(st->live.p) + lo, k * 4, hipMemcpyDeviceToHost, s));
-        }
-    }
-    {   // the device control block of the graph path mirrors the host counters
-        const int64_t counters[2] = {st->n_samples, st->frames_done};
-        HIPCHK(h, hipMemcpyAsync(st->ctl.p, counters, 16, hipMemcpyHostToDevice, s));
-    }
-    // commit: one more launch behind the Viterbi, when there is a frame the last walk has not seen (also the frames of
-    // earlier plain pushes: the walk goes from the newest frame back to the frontier, however far that is)
-    unsigned char *cres = nullptr;
-    if (commit && st->frames_done > 0 && st->frames_done - 1 != st->c_newest) {
-        cres = st->pin_commit ? st->pin_commit : st->commit_host;
-        hipError_t ce = launch_stream_commit(nullptr, st->frames_done, stream_commit_ctl(st), static_cast<const uint16_t *>(st->ptr.p),
-                                             static_cast<const double *>(st->vstate.p), h->tab.n_bins, static_cast<int16_t *>(st->c_bins.p),
-                                             st->c_result.p, s);
-        if (ce != hipSuccess) { h->err = std::string("stream commit launch: ") + hipGetErrorString(ce); return AEGIS_ERR_DEVICE; }
-        HIPCHK(h, hipMemcpyAsync(cres, st->c_result.p, kCommitResultBytes, hipMemcpyDeviceToHost, s));
-    }
-    HIPCHK(h, hipStreamSynchronize(s));
-    return commit ? stream_deliver(st, cres, commit) : AEGIS_OK;
-}
-
-int aegis_stream_push(aegis_stream *st, const float *samples, int64_t n, aegis_stream_frames *out, int64_t *n_frames) {
-    try {
-    if (!st || !st->h) return AEGIS_ERR_INVALID;
-    std::lock_guard<std::mutex> lock(st->h->mu);
-    return stream_push_locked(st, samples, n, out, n_frames, nullptr);
-    } catch (...) { return abi_fail((st ? st->h : nullptr)); }
-}
-
-int aegis_stream_push_commit(aegis_stream *st, const float *samples, int64_t n, aegis_stream_frames *out, int64_t *n_frames,
-                             aegis_stream_commit *commit) {
-    try {
-    if (!st || !st->h) return AEGIS_ERR_INVALID;
-    std::lock_guard<std::mutex> lock(st->h->mu);
-    return stream_push_locked(st, samples, n, out, n_frames, commit);
-    } catch (...) { return abi_fail((st ? st->h : nullptr)); }
-}
-
-int aegis_stream_close(aegis_stream *st, double rake_sensitivity, aegis_outputs *out, int64_t *n_frames) {
-    try {
-    if (!st || !st->h) return AEGIS_ERR_INVALID;
-    aegis_handle *h = st->h;
-    std::lock_guard<std::mutex> lock(h->mu);
-    if (h->destroy_requested) { h->err = "handle was destroyed"; return AEGIS_ERR_INVALID; }
-    if (!n_frames) { h->err = "bad argument"; return AEGIS_ERR_INVALID; }
-    if (st->closed) { h->err = "stream is closed"; return AEGIS_ERR_INVALID; }
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = h->stream;
-    const Tables &t = h->tab;
-    const int64_t F = 1 + st->n_samples / t.hop;
-    int rc = stream_run(st, st->frames_done, F, true, s);       // zero-padded tail frames + back-trace
-    if (rc != AEGIS_OK) return rc;
-    // clip-global stages over all F frames
-    st->host_meta[5] = F;
-    PassParams p = base_params(t);
-    p.stages = AEGIS_STAGE_ALL;
-    const int64_t *dm = static_cast<const int64_t *>(st->meta.p);
-    p.sample_off = dm; p.sample_len = dm + 1; p.frame_off = dm + 2; p.out_off = dm + 2; p.sel_off = dm + 2; p.n_clips = 1; p.n_frames = F; p.n_sel = F;
-    p.states = static_cast<int32_t *>(st->states.p);
-    p.melpow = static_cast<float *>(st->melpow.p); p.clipmax = static_cast<uint32_t *>(st->clipmax.p);
-    p.rake_raw = static_cast<uint8_t *>(st->rake_raw.p);
-    p.out_f0 = static_cast<double *>(st->o_f0.p); p.out_voiced = static_cast<uint8_t *>(st->o_voiced.p);
-    p.out_rake = static_cast<uint8_t *>(st->o_rake.p); p.out_sdb = static_cast<float *>(st->o_sdb.p);
-    p.rake_ratio = rake_sensitivity;
-    const double ms_per_frame = ((double)t.hop / (double)t.sr) * 1000;
-    p.rake_min_frames = (int)(10 / ms_per_frame); p.rake_max_frames = (int)(30 / ms_per_frame);
-    launch_finalize_mel(p, h->dt, s);
-    launch_decode(p, h->dt, s);
-    HIPCHK(h, hipGetLastError());
-    st->frames_done = F;
-    st->closed = true;
-    *n_frames = F;
-    if (out) {
-        auto back = [&](void *dst, const void *src, size_t bytes) { return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s) : hipSuccess; };
-        HIPCHK(h, back(out->f0, st->o_f0.p, F * 8)); HIPCHK(h, back(out->voiced_flag, st->o_voiced.p, F));
-        HIPCHK(h, back(out->voiced_prob, st->o_vprob.p, F * 8)); HIPCHK(h, back(out->rms, st->o_rms.p, F * 4));
-        HIPCHK(h, back(out->rake_mask, st->o_rake.p, F)); HIPCHK(h, back(out->S_dB, st->o_sdb.p, (size_t)F * t.n_mels * 4));
-    }
-    HIPCHK(h, hipStreamSynchronize(s));
-    return AEGIS_OK;
-    } catch (...) { return abi_fail((st ? st->h : nullptr)); }
-}
-
-int aegis_ghost_rsi(aegis_handle *h, const int64_t *ev_a, const int64_t *ev_b, const int64_t *event_off, int32_t n_series,
-                    const int64_t *track_len, int32_t period, double *avg_gain, double *avg_loss) {
-    try {
-    if (!h) return AEGIS_ERR_INVALID;
-    if (n_series < 0 || (n_series > 0 && (!event_off || !track_len))) { h->err = "bad argument"; return AEGIS_ERR_INVALID; }
-    if (period < 1 || period > 128) { h->err = "rsi period must be 1..128"; return AEGIS_ERR_INVALID; }
-    if (h->device < 0) { h->err = "handle was created with device=-1 (host tables only)"; return AEGIS_ERR_DEVICE; }
-    if (n_series == 0) return AEGIS_OK;
-    const int64_t E = event_off[n_series] - event_off[0];
-    if (E < 0) { h->err = "event_off must be non-decreasing"; return AEGIS_ERR_INVALID; }
-    if (E == 0) return AEGIS_OK;
-    if (!ev_a || !ev_b || !avg_gain || !avg_loss) { h->err = "null argument"; return AEGIS_ERR_INVALID; }
-    std::vector<int64_t> toff((size_t)n_series + 1, 0);
-    std::vector<int32_t> sid((size_t)E);
-    for (int i = 0; i < n_series; ++i) {
-        if (track_len[i] < 0 || event_off[i + 1] < event_off[i]) { h->err = "bad clip " + std::to_string(i); return AEGIS_ERR_INVALID; }
-        toff[(size_t)i + 1] = toff[(size_t)i] + track_len[i];
-        for (int64_t e = event_off[i]; e < event_off[i + 1]; ++e) sid[(size_t)(e - event_off[0])] = i;
-    }
-    const int64_t total = toff[(size_t)n_series];
-    std::lock_guard<std::mutex> lock(h->mu);
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = h->stream;
-    int rc;
-#define ENS(buf, bytes) if ((rc = ensure(h, h->buf, (size_t)(bytes))) != AEGIS_OK) return rc
-    ENS(t_x, std::max<int64_t>(total, 1) * 8); ENS(t_a, std::max<int64_t>(total, 1) * 8); ENS(t_b, std::max<int64_t>(total, 1) * 8);
-    ENS(t_off, (n_series + 1) * 8); ENS(t_i64a, 2 * E * 8); ENS(t_i64b, E * 4 + 8); ENS(t_c, 2 * E * 8);
-#undef ENS
-    int64_t *d_ab = static_cast<int64_t *>(h->t_i64a.p);
-    int32_t *d_sid = static_cast<int32_t *>(h->t_i64b.p);
-    double *d_out = static_cast<double *>(h->t_c.p);
-    HIPCHK(h, hipMemcpyAsync(d_ab, ev_a + event_off[0], (size_t)E * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(d_ab + E, ev_b + event_off[0], (size_t)E * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(d_sid, sid.data(), (size_t)E * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(h->t_off.p, toff.data(), ((size_t)n_series + 1) * 8, hipMemcpyHostToDevice, s));
-    trend_ghost_rsi(d_ab, d_ab + E, d_sid, E, static_cast<const int64_t *>(h->t_off.p), n_series, total, period,
-                    static_cast<double *>(h->t_x.p), static_cast<double *>(h->t_a.p), static_cast<double *>(h->t_b.p), d_out, d_out + E, s);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(avg_gain + event_off[0], d_out, (size_t)E * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipMemcpyAsync(avg_loss + event_off[0], d_out + E, (size_t)E * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    return AEGIS_OK;
-    } catch (...) { return abi_fail(h); }
-}
-
-int aegis_trend(aegis_handle *h, int32_t op, const double *x, const int64_t *offsets, int32_t n_series,
-                const double *params, int32_t n_params, void *const *outs, int32_t n_outs) {
-    try {
-    if (!h) return AEGIS_ERR_INVALID;
-    if (n_series < 0 || (n_series > 0 && (!x || !offsets)) || !outs || n_params < 0 || (n_params > 0 && !params)) {
-        h->err = "bad argument"; return AEGIS_ERR_INVALID;
-    }
-    if (h->device < 0) { h->err = "handle was created with device=-1 (host tables only)"; return AEGIS_ERR_DEVICE; }
-    auto need = [&](int np, int no) {
-        if (n_params < np || n_outs < no) { h->err = "op needs " + std::to_string(np) + " params and " + std::to_string(no) + " outputs"; return false; }
-        for (int i = 0; i < no; ++i) if (!outs[i]) { h->err = "null output"; return false; }
-        return true;
-    };
-    std::lock_guard<std::mutex> lock(h->mu);
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = h->stream;
-    int rc;
-    int64_t total = n_series > 0 ? offsets[n_series] : 0;
-    int64_t n_in = total;
-    if (op == AEGIS_TREND_CONSENSUS) {       // x = k stacked rows of one series
-        if (!need(1, 2) || n_series != 1) { if (n_series != 1) h->err = "consensus takes one series"; return AEGIS_ERR_INVALID; }
-        const int k = (int)params[0];
-        if (k < 1 || k > 8) { h->err = "consensus of 1..8 filters"; return AEGIS_ERR_INVALID; }
-        n_in = total * k;
-    }
-    if (total == 0) return AEGIS_OK;
-    for (int i = 0; i < n_series; ++i)
-        if (offsets[i + 1] < offsets[i]) { h->err = "offsets must be non-decreasing"; return AEGIS_ERR_INVALID; }
-#define ENS(buf, bytes) if ((rc = ensure(h, h->buf, (size_t)(bytes))) != AEGIS_OK) return rc
-    ENS(t_x, n_in * 8); ENS(t_off, (n_series + 1) * 8);
-    ENS(t_a, total * 8); ENS(t_b, total * 8); ENS(t_c, total * 8); ENS(t_d, total * 8); ENS(t_e, std::max<int64_t>(total, 256) * 8);
-    ENS(t_i8, total); ENS(t_i64a, total * 8); ENS(t_i64b, (n_series + 1) * 8);
-#undef ENS
-    HIPCHK(h, hipMemcpyAsync(h->t_x.p, x, n_in * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(h->t_off.p, offsets, (n_series + 1) * 8, hipMemcpyHostToDevice, s));
-    TrendArgs a{static_cast<const double *>(h->t_x.p), static_cast<const int64_t *>(h->t_off.p), n_series, total};
-    double *A = static_cast<double *>(h->t_a.p), *B = static_cast<double *>(h->t_b.p), *Cc = static_cast<double *>(h->t_c.p);
-    double *D = static_cast<double *>(h->t_d.p), *E = static_cast<double *>(h->t_e.p);
-    int8_t *I8 = static_cast<int8_t *>(h->t_i8.p);
-    auto back = [&](void *dst, const void *src, size_t bytes) { return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s); };
-    auto min_len = [&]() { int64_t m = INT64_MAX; for (int i = 0; i < n_series; ++i) m = std::min(m, offsets[i + 1] - offsets[i]); return m; };
-    switch (op) {
-    case AEGIS_TREND_SMA: {
-        if (!need(1, 1)) return AEGIS_ERR_INVALID;
-        const int w = (int)params[0];
-        if (w < 1 || min_len() < w) { h->err = "series shorter than the window (the reference raises IndexError)"; return AEGIS_ERR_INVALID; }
-        trend_sma(a, w, A, s);
-        HIPCHK(h, back(outs[0], A, total * 8));
-        break;
-    }
-    case AEGIS_TREND_EMA: {
-        if (!need(1, 1)) return AEGIS_ERR_INVALID;
-        trend_ema(a, (int)params[0], A, s);
-        HIPCHK(h, back(outs[0], A, total * 8));
-        break;
-    }
-    case AEGIS_TREND_BOLLINGER:
-    case AEGIS_TREND_ARTICULATION: {
-        const bool art = op == AEGIS_TREND_ARTICULATION;
-        if (!need(2, art ? 1 : 3)) return AEGIS_ERR_INVALID;
-        const int w = (int)params[0];
-        if (w < 1 || w > 128 || min_len() < w) { h->err = "window must be 1..128 and not longer than any series"; return AEGIS_ERR_INVALID; }
-        trend_bollinger(a, w, params[1], A, B, Cc, s);
-        if (art) {
-            trend_articulation(a, B, Cc, I8, s);
-            HIPCHK(h, back(outs[0], I8, total));
-        } else {
-            HIPCHK(h, back(outs[0], A, total * 8)); HIPCHK(h, back(outs[1], B, total * 8)); HIPCHK(h, back(outs[2], Cc, total * 8));
-        }
-        break;
-    }
-    case AEGIS_TREND_MACD: {
-        if (!need(3, 3)) return AEGIS_ERR_INVALID;
-        trend_macd(a, (int)params[0], (int)params[1], (int)params[2], A, B, Cc, s);
-        HIPCHK(h, back(outs[0], A, total * 8)); HIPCHK(h, back(outs[1], B, total * 8)); HIPCHK(h, back(outs[2], Cc, total * 8));
-        break;
-    }
-    case AEGIS_TREND_SLIDES: {      // detect_slides_macd: hz_to_midi, macd(5, 20, 9), threshold test
-        if (!need(1, 1)) return AEGIS_ERR_INVALID;
-        trend_semitones(a.x, total, D, s);
-        TrendArgs st{D, a.off, n_series, total};
-        trend_macd(st, 5, 20, 9, A, B, Cc, s);
-        trend_slides(A, Cc, total, params[0], I8, s);
-        HIPCHK(h, back(outs[0], I8, total));
-        break;
-    }
-    case AEGIS_TREND_RSI: {
-        if (!need(1, 1)) return AEGIS_ERR_INVALID;
-        const int per = (int)params[0];
-        if (per < 1 || per > 128) { h->err = "rsi period must be 1..128"; return AEGIS_ERR_INVALID; }
-        if (n_params >= 2 && params[1] != 0.0) {          // the two Wilder averages instead of the RSI (see trend.hip)
-            if (!need(2, 2)) return AEGIS_ERR_INVALID;
-            trend_rsi_averages(a, per, A, B, s);
-            HIPCHK(h, back(outs[0], A, total * 8)); HIPCHK(h, back(outs[1], B, total * 8));
-            break;
-        }
-        trend_rsi(a, per, A, s);
-        HIPCHK(h, back(outs[0], A, total * 8));
-        break;
-    }
-    case AEGIS_TREND_SAVGOL: {      // params: window, symmetric flag, then `window` reversed coefficients
-        if (n_params < 2 || !need(2 + (int)params[0], 1)) { h->err = "savgol params: window, symmetric, coefficients"; return AEGIS_ERR_INVALID; }
-        const int w = (int)params[0];
-        if (w < 1 || (w & 1) == 0 || w > 255) { h->err = "savgol window must be odd, 1..255"; return AEGIS_ERR_INVALID; }
-        HIPCHK(h, hipMemcpyAsync(E, params + 2, (size_t)w * 8, hipMemcpyHostToDevice, s));
-        trend_savgol(a, E, w, (int)params[1], B, static_cast<int64_t *>(h->t_i64a.p), static_cast<int64_t *>(h->t_i64b.p), A, s);
-        HIPCHK(h, back(outs[0], A, total * 8));
-        break;
-    }
-    case AEGIS_TREND_KALMAN: {
-        if (!need(2, 1)) return AEGIS_ERR_INVALID;
-        trend_kalman(a, params[0], params[1], A, s);
-        HIPCHK(h, back(outs[0], A, total * 8));
-        break;
-    }
-    case AEGIS_TREND_HOLT: {
-        if (!need(2, 1)) return AEGIS_ERR_INVALID;
-        trend_holt(a, params[0], params[1], A, s);
-        HIPCHK(h, back(outs[0], A, total * 8));
-        break;
-    }
-    case AEGIS_TREND_CONSENSUS: {
-        trend_consensus(a.x, (int)params[0], total, A, B, s);
-        HIPCHK(h, back(outs[0], A, total * 8)); HIPCHK(h, back(outs[1], B, total * 8));
-        break;
-    }
-    case AEGIS_TREND_PITCH_ANALYSIS: {
-        // analyze_pitch_financial (financial_analysis.py:368-423): the same kernels as the single ops above, the four
-        // independent sequential walks on four streams at once
-        if (n_params < 2 || !need(2 + (int)params[0] + 7, 4)) { h->err = "pitch analysis params: sg window, symmetric, coefficients, q, r, alpha, beta, band window, num_std, slide threshold"; return AEGIS_ERR_INVALID; }
-        const int w = (int)params[0];
-        if (w < 1 || (w & 1) == 0 || w > 255) { h->err = "savgol window must be odd, 1..255"; return AEGIS_ERR_INVALID; }
-        const double *pp = params + 2 + w;
-        const int bw = (int)pp[4];
-        if (bw < 1 || bw > 128 || min_len() < bw) { h->err = "band window must be 1..128 and not longer than any series"; return AEGIS_ERR_INVALID; }
-        if ((rc = ensure(h, h->t_pa, (size_t)total * (12 * 8 + 1) + 256)) != AEGIS_OK) return rc;
-        double *R = static_cast<double *>(h->t_pa.p);
-        double *stack = R;                              // [3][total]: savgol, kalman, holt (the order multi_filter_consensus stacks them)
-        double *ma = R + 3 * total, *up = R + 4 * total, *lo = R + 5 * total, *semi = R + 6 * total;
-        double *mm = R + 7 * total, *sg = R + 8 * total, *hh = R + 9 * total, *cx = R + 10 * total, *conf = R + 11 * total;
-        int8_t *slide_codes = reinterpret_cast<int8_t *>(R + 12 * total);
-        hipStream_t q1 = h->stream2, q2 = h->stream3, q3 = h->stream4;
-        while (h->sync_events.size() < 5) { hipEvent_t e; HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming)); h->sync_events.push_back(e); }
-        HIPCHK(h, hipMemcpyAsync(E, params + 2, (size_t)w * 8, hipMemcpyHostToDevice, s));
-        HIPCHK(h, hipEventRecord(h->sync_events[0], s));          // input, offsets and coefficients are on the device
-        for (hipStream_t q : {q1, q2, q3}) HIPCHK(h, hipStreamWaitEvent(q, h->sync_events[0], 0));
-        // s: MACD of the semitone track -> slide codes
-        trend_semitones(a.x, total, semi, s);
-        { TrendArgs st{semi, a.off, n_series, total}; trend_macd(st, 5, 20, 9, mm, sg, hh, s); }
-        trend_slides(mm, hh, total, pp[6], slide_codes, s);
-        // q1: Kalman, then the bands and the articulation state machine
-        trend_kalman(a, pp[0], pp[1], stack + total, q1);
-        trend_bollinger(a, bw, pp[5], ma, up, lo, q1);
-        trend_articulation(a, up, lo, I8, q1);
-        trend_band_confidence(a.x, up, lo, total, conf, q1);
-        // q2: Holt; q3: NaN compaction + Savitzky-Golay
-        trend_holt(a, pp[2], pp[3], stack + 2 * total, q2);
-        trend_savgol(a, E, w, (int)params[1], cx, static_cast<int64_t *>(h->t_i64a.p), static_cast<int64_t *>(h->t_i64b.p), stack, q3);
-        int ei = 1;
-        for (hipStream_t q : {q1, q2, q3}) {
-            HIPCHK(h, hipEventRecord(h->sync_events[ei], q));
-            HIPCHK(h, hipStreamWaitEvent(s, h->sync_events[ei], 0));
-            ++ei;
-        }
-        trend_consensus(stack, 3, total, A, B, s);
-        HIPCHK(h, back(outs[0], A, total * 8)); HIPCHK(h, back(outs[1], I8, total));
-        HIPCHK(h, back(outs[2], slide_codes, total)); HIPCHK(h, back(outs[3], conf, total * 8));
-        break;
-    }
-    default:
-        h->err = "unknown trend op " + std::to_string(op);
-        return AEGIS_ERR_INVALID;
-    }
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipStreamSynchronize(s));
-    return AEGIS_OK;
-    } catch (...) { return abi_fail(h); }
-}
-
-int aegis_set_table(aegis_handle *h, const char *name, const double *data, int64_t count) {
-    try {
-    if (!h || !name || !data) return AEGIS_ERR_INVALID;
-    Tables &t = h->tab;
-    const std::string n(name);
-    struct Slot { std::vector<double> *host; const double *dev; };
-    auto slot = [&](const std::string &nm) -> Slot {
-        if (nm == "beta_probs") return {&t.beta_probs, h->dt.beta_probs};
-        if (nm == "beta_cumsum") return {&t.beta_cumsum, h->dt.beta_cumsum};
-        if (nm == "beta_suffix") return {&t.beta_suffix, h->dt.beta_suffix};
-        if (nm == "boltz_fact") return {&t.boltz_fact, h->dt.boltz_fact};
-        if (nm == "boltz_exp") return {&t.boltz_exp, h->dt.boltz_exp};
-        if (nm == "freqs") return {&t.freqs, h->dt.freqs};
-        return {nullptr, nullptr};
-    };
-    auto push = [&](const std::string &nm) -> int {
-        Slot s = slot(nm);
-        if (h->device < 0) return AEGIS_OK;
-        HIPCHK(h, hipSetDevice(h->device));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        HIPCHK(h, hipMemcpy(const_cast<double *>(s.dev), s.host->data(), s.host->size() * 8, hipMemcpyHostToDevice));
-        return AEGIS_OK;
-    };
-    Slot s = slot(n);
-    if (!s.host || n == "beta_cumsum" || n == "beta_suffix") { h->err = "unknown or derived table: " + n; return AEGIS_ERR_INVALID; }
-    if (count != (int64_t)s.host->size()) {
-        h->err = "table " + n + " needs " + std::to_string(s.host->size()) + " entries";
-        return AEGIS_ERR_INVALID;
-    }
-    std::copy(data, data + count, s.host->begin());
-    int rc = push(n);
-    if (rc != AEGIS_OK) return rc;
-    if (n == "beta_probs") {
-        for (int k = 0; k <= kNThresholds; ++k) t.beta_cumsum[k] = np_pairwise_sum(t.beta_probs.data(), k);
-        t.beta_suffix.assign(kNThresholds + 1, 0.0);
-        for (int k = kNThresholds - 1; k >= 0; --k) t.beta_suffix[k] = t.beta_suffix[k + 1] + t.beta_probs[k];
-        if ((rc = push("beta_cumsum")) != AEGIS_OK) return rc;
-        if ((rc = push("beta_suffix")) != AEGIS_OK) return rc;
-    }
-    return AEGIS_OK;
-    } catch (...) { return abi_fail(h); }
-}
-
-int64_t aegis_get_param(const aegis_handle *h, const char *name) {
-    try {
-    if (!h || !name) return AEGIS_ERR_INVALID;
-    const Tables &t = h->tab;
-    const std::string n(name);
-    if (n == "min_period") return t.min_period;
-    if (n == "max_period") return t.max_period;
-    if (n == "n_lags") return t.n_lags;
-    if (n == "n_pitch_bins") return t.n_bins;
-    if (n == "transition_width") return t.width;
-    if (n == "n_trans_classes") return t.n_cls;
-    if (n == "max_frames_per_pass") return h->max_frames_per_pass;
-    if (n == "lag_stride") return h->lag_stride;
-    if (n == "yin_stride") return h->yin_stride;
-    if (n == "obs_stride") return h->obs_stride;
-    const PassPlan *lp = last_pass(h);      // the last call's plan (its last pass; the split segments of all its passes)
-    if (n == "last_frames") return lp ? lp->fp : 0;
-    if (n == "last_passes") return (int64_t)h->plan.passes.size();
-    if (n == "last_split_segments") { int64_t v = 0; for (const PassPlan &q : h->plan.passes) v += q.tsplit ? q.n_seg : 0; return v; }
-    if (n == "split_passes") return h->split_stats[0];
-    if (n == "split_segments") return h->split_stats[1];
-    if (n == "split_flagged_clips") return h->split_stats[2];
-    if (n == "split_unlocked_clips") return h->split_stats[3];
-    if (n == "split_rounds") return h->last_carried_steps;
-    if (n == "split_viterbi_us") return (int64_t)(h->last_split_viterbi_ms * 1e3);
-    if (n == "split_cooldown") return h->split_cooldown;
-    if (n == "last_chunks") return lp ? lp->nk() : 0;
-    if (n == "last_dense") return lp ? lp->dense : 0;
-    if (n == "last_proportional") return lp ? lp->proportional : 0;
-    if (n == "last_balanced") return lp ? lp->balanced : 0;
-    if (n == "last_hybrid_step") return lp ? lp->hyb_S : 0;
-    if (n == "last_persistent") return lp ? lp->persistent : 0;
-    if (n == "pyin_init") return t.pyin_init;
-    return AEGIS_ERR_INVALID;
-    } catch (...) { return abi_fail(const_cast<aegis_handle *>(h)); }
-}
-
-int64_t aegis_get_table(const aegis_handle *h, const char *name, void *dst, int64_t cap) {
-    try {
-    if (!h || !name) return AEGIS_ERR_INVALID;
-    const Tables &t = h->tab;
-    const std::string n(name);
-    const void *src = nullptr;
-    int64_t count = 0;
-    size_t esz = 8;
-    auto setd = [&](const std::vector<double> &v) { src = v.data(); count = (int64_t)v.size(); esz = 8; };
-    if (n == "hann") setd(t.hann);
-    else if (n == "thresholds") setd(t.thresholds);
-    else if (n == "beta_probs") setd(t.beta_probs);
-    else if (n == "beta_cumsum") setd(t.beta_cumsum);
-    else if (n == "beta_suffix") setd(t.beta_suffix);
-    else if (n == "boltz_fact") setd(t.boltz_fact);
-    else if (n == "boltz_exp") setd(t.boltz_exp);
-    else if (n == "log_trans_band") setd(t.log_trans_band);
-    else if (n == "log_trans_pack") setd(t.log_trans_pack);
-    else if (n == "freqs") setd(t.freqs);
-    else if (n == "twiddle") setd(t.twiddle);
-    else if (n == "mel_dense") { src = t.mel_dense.data(); count = (int64_t)t.mel_dense.size(); esz = 4; }
-    else return AEGIS_ERR_INVALID;
-    if (dst && cap > 0) std::memcpy(dst, src, (size_t)std::min(count, cap) * esz);
-    return count;
-    } catch (...) { return abi_fail(const_cast<aegis_handle *>(h)); }
-}
-
-int64_t aegis_debug_plan(aegis_handle *h, const int64_t *n_samples, int32_t n_clips, int32_t entry, int32_t sync,
-                         int32_t n_cus, int64_t *dst, int64_t cap) {
-    try {
-    if (!h || n_clips < 0 || (n_clips > 0 && !n_samples) || cap < 0 || (cap > 0 && !dst)) return AEGIS_ERR_INVALID;
-    std::lock_guard<std::mutex> lock(h->mu);
-    std::vector<int64_t> off((size_t)n_clips + 1, 0);
-    for (int i = 0; i < n_clips; ++i) {
-        if (n_samples[i] < 0 || 1 + n_samples[i] / h->tab.hop > h->max_frames_per_pass) { h->err = "bad clip " + std::to_string(i); return AEGIS_ERR_INVALID; }
-        off[i + 1] = off[i] + n_samples[i];
-    }
-    const int kind = entry & 3;
-    const PlanKnobs &kn = h->knobs;
-    PlanInput in = plan_input(h, off.data(), n_clips, AEGIS_STAGE_ALL, kind == AEGIS_PLAN_HOST_FED, kind == AEGIS_PLAN_CALLER_STREAM,
-                              sync, n_cus, [&kn, n_cus](int n) { return masked_streams_fit(kn, n_cus, n); });
-    if (entry & AEGIS_PLAN_COOLING) in.cooling = split_allowed(in) && kn.split_seglen < 0;
-    if (entry & AEGIS_PLAN_NO_PERSIST) in.persistent = false;
-    const CallPlan c = plan_call(in);
-    std::vector<int64_t> v{(int64_t)c.passes.size()};
-    for (const PassPlan &m : c.passes) {
-        const int64_t flags = m.tsplit * AEGIS_PLAN_F_SPLIT | m.split_auto * AEGIS_PLAN_F_SPLIT_AUTO | m.want_hybrid * AEGIS_PLAN_F_WANT_HYBRID |
-                              m.hybrid * AEGIS_PLAN_F_HYBRID | m.hyb_part * AEGIS_PLAN_F_HYBRID_PART | m.balanced * AEGIS_PLAN_F_BALANCED |
-                              m.may_persist * AEGIS_PLAN_F_MAY_PERSIST | m.persistent * AEGIS_PLAN_F_PERSISTENT | m.dense * AEGIS_PLAN_F_DENSE |
-                              m.proportional * AEGIS_PLAN_F_PROPORTIONAL | m.two_fs * AEGIS_PLAN_F_TWO_FRAME_STREAMS | m.use_fb * AEGIS_PLAN_F_FRAME_B;
-        const int64_t lanes = (int64_t)m.fa | (int64_t)m.fb << 4 | (int64_t)m.sv << 8 | (int64_t)m.sd << 12 | (int64_t)m.sa << 16;
-        uint64_t hash = 1469598103934665603ull;      // FNV-1a over the tables' bytes, each led by its length
-        auto mix = [&hash](const void *p, size_t n) {
-            for (size_t i = 0; i < n; ++i) { hash ^= static_cast<const unsigned char *>(p)[i]; hash *= 1099511628211ull; }
-        };
-        auto table = [&mix](const auto &t) { const uint64_t n = t.size(); mix(&n, 8); mix(t.data(), n * sizeof(t[0])); };
-        table(m.seg32); table(m.seg64); table(m.sel_off); table(m.clip_tb);
-        for (int64_t x : {(int64_t)m.nc(), m.fp, m.maxF, flags, m.seglen, m.hyb_S, (int64_t)m.n_seg, (int64_t)m.n_lock, (int64_t)m.nk(),
-                          (int64_t)m.ramp_k, lanes, (int64_t)hash}) v.push_back(x);
-        v.insert(v.end(), m.cb.begin(), m.cb.end());
-    }
-    if (cap > 0) std::memcpy(dst, v.data(), (size_t)std::min<int64_t>(cap, (int64_t)v.size()) * 8);
-    return (int64_t)v.size();
-    } catch (...) { return abi_fail(h); }
-}
-
-int64_t aegis_debug_fetch(aegis_handle *h, const char *name, void *dst, int64_t cap) {
-    try {
-    if (!h || !name) return AEGIS_ERR_INVALID;
-    const std::string n(name);
-    // test hooks of the exception barrier (tests/test_abi_and_tables.py): the body throws, the entry returns a code
-    if (n == "throw_bad_alloc") throw std::bad_alloc();
-    if (n == "throw_length_error") throw std::length_error("test hook");
-    if (n == "throw_runtime_error") throw std::runtime_error("test hook: runtime_error");
-    if (n == "throw_int") throw 42;
-    if (n == "fail_allocs") { h->fail_allocs = (int)std::max<int64_t>(0, cap); return 0; }      // (count in `cap`, nothing copied)
-    const PassPlan *lp = last_pass(h);
-    const int64_t F = lp ? lp->fp : 0;
-    const int last_pass_segments = lp && lp->tsplit ? lp->n_seg : 0;
-    const void *src = nullptr;
-    int64_t count = 0;
-    size_t esz = 8;
-    const aegis_handle::Work &lw = h->work[last_work(h)];      // rows in the order the last pass took its clips: longest first
-    if (n == "dfn") { src = lw.dfn.p; count = F * h->lag_stride; }
-    else if (n == "yin") { src = lw.yin.p; count = F * h->yin_stride; }
-    else if (n == "logobs") {            // dense rows: the segments the kernel did not store (obs_seg) are all log(tiny)
-        count = F * h->obs_stride;
-        if (h->device < 0 || !lw.logobs.p || !lw.obs_seg.p) { h->err = "stage was not run"; return AEGIS_ERR_INVALID; }
-        if (dst && cap > 0) {
-            HIPCHK(h, hipSetDevice(h->device));
-            HIPCHK(h, hipStreamSynchronize(h->stream));
-            std::vector<double> rows((size_t)count);
-            std::vector<int32_t> seg((size_t)F);
-            HIPCHK(h, hipMemcpy(rows.data(), lw.logobs.p, (size_t)count * 8, hipMemcpyDeviceToHost));
-            HIPCHK(h, hipMemcpy(seg.data(), lw.obs_seg.p, (size_t)F * 4, hipMemcpyDeviceToHost));
-            const double log_tiny = h->tab.log_tiny;
-            for (int64_t f = 0; f < F; ++f)
-                for (int b = 0; b < h->obs_stride; ++b)
-                    if (!(seg[(size_t)f] & (0x40000000 | (1 << (b >> 6))))) rows[(size_t)(f * h->obs_stride + b)] = log_tiny;
-            std::memcpy(dst, rows.data(), (size_t)std::min(count, cap) * 8);
-        }
-        return count;
-    }
-    else if (n == "logunv") { src = lw.logunv.p; count = F; }
-    else if (n == "states") { src = lw.states.p; count = F; esz = 4; }
-    else if (n == "melpow") { src = lw.melpow.p; count = F * h->tab.n_mels; esz = 4; }
-    else if (n == "persistent_fallbacks") {
-        if (dst && cap > 0) *static_cast<int64_t *>(dst) = h->persistent_fallbacks;
-        return 1;
-    }
-    else if (n == "viterbi_stats" || n == "viterbi_stats_peek") {      // [wave-steps, observed-sources-only wave-steps, skipped voiced wave-steps]
-        if (h->device < 0 || !h->vstats.p) return AEGIS_ERR_INVALID;
-        if (dst && cap > 0) {
-            long long v[3];
-            std::lock_guard<std::mutex> lock(h->mu);
-            HIPCHK(h, hipSetDevice(h->device));
-            HIPCHK(h, hipDeviceSynchronize());
-            HIPCHK(h, hipMemcpy(v, h->vstats.p, 24, hipMemcpyDeviceToHost));
-            if (n == "viterbi_stats") HIPCHK(h, hipMemset(h->vstats.p, 0, 24));
-            std::memcpy(dst, v, (size_t)std::min<int64_t>(cap, 3) * 8);
-        }
-        return 3;
-    }
-    else if (n == "obs_cycles") {
-        if (h->device < 0) return AEGIS_ERR_INVALID;
-        if (dst && cap > 0) {
-            long long v[16];
-            HIPCHK(h, hipSetDevice(h->device));
-            HIPCHK(h, hipDeviceSynchronize());
-            HIPCHK(h, obs_debug_fetch(v));
-            std::memcpy(dst, v, (size_t)std::min<int64_t>(cap, 16) * 8);
-        }
-        return 16;
-    }
-    else if (n == "frame_cycles") {
-        if (h->device < 0) return AEGIS_ERR_INVALID;
-        if (dst && cap > 0) {
-            long long v[24];
-            HIPCHK(h, hipSetDevice(h->device));
-            HIPCHK(h, hipDeviceSynchronize());
-            HIPCHK(h, frame_debug_fetch(v));
-            std::memcpy(dst, v, (size_t)std::min<int64_t>(cap, 24) * 8);
-        }
-        return 24;
-    }
-    else if (n == "seg_lock") {           // lock-on run lengths of the last time-split pass, one per segment (0: first of its clip, -1: never met)
-        if (h->device < 0 || last_pass_segments <= 0) return 0;
-        const int ns = last_pass_segments;
-        if (dst && cap > 0) {
-            std::vector<int32_t> v((size_t)ns), st((size_t)ns);
-            HIPCHK(h, hipSetDevice(h->device));
-            HIPCHK(h, hipDeviceSynchronize());
-            HIPCHK(h, hipMemcpy(v.data(), static_cast<const int32_t *>(lw.seg_i32.p) + ns, (size_t)ns * 4, hipMemcpyDeviceToHost));
-            HIPCHK(h, hipMemcpy(st.data(), static_cast<const int32_t *>(lw.seg32.p) + ns, (size_t)ns * 4, hipMemcpyDeviceToHost));
-            int64_t *o = static_cast<int64_t *>(dst);
-            for (int i = 0; i < std::min<int64_t>(cap, ns); ++i) o[i] = v[i] > 0 ? v[i] - st[i] : v[i];
-        }
-        return ns;
-    }
-    else if (n == "split_flags") {
-        if (dst && cap > 0) std::memcpy(dst, h->last_split_flags.data(), (size_t)std::min<int64_t>(cap, (int64_t)h->last_split_flags.size()) * 8);
-        return (int64_t)h->last_split_flags.size();
-    }
-    else if (n == "split_verify") {
-        if (h->device < 0) return AEGIS_ERR_INVALID;
-        if (dst && cap > 0) {                     // reading resets the counters
-            long long v[16];
-            HIPCHK(h, hipSetDevice(h->device));
-            HIPCHK(h, hipDeviceSynchronize());
-            HIPCHK(h, viterbi_verify_fetch(v, true));
-            std::memcpy(dst, v, (size_t)std::min<int64_t>(cap, 16) * 8);
-        }
-        return 16;
-    }
-    else if (n == "viterbi_cycles") {
-        if (h->device < 0) return AEGIS_ERR_INVALID;
-        if (dst && cap > 0) {                     // reading resets the counters
-            long long v[128];
-            HIPCHK(h, hipSetDevice(h->device));
-            HIPCHK(h, hipDeviceSynchronize());
-            HIPCHK(h, viterbi_debug_fetch(v, true));
-            std::memcpy(dst, v, (size_t)std::min<int64_t>(cap, 128) * 8);
-        }
-        return 128;
-    }
-    else if (n == "viterbi_spans") {
-        if (h->device < 0) return AEGIS_ERR_INVALID;
-        if (dst && cap > 0) {                     // reading resets the counters
-            long long v[272];
-            HIPCHK(h, hipSetDevice(h->device));
-            HIPCHK(h, hipDeviceSynchronize());
-            HIPCHK(h, viterbi_span_fetch(v));
-            std::memcpy(dst, v, (size_t)std::min<int64_t>(cap, 272) * 8);
-        }
-        return 272;
-    }
-    else if (n == "cqt_cycles") {
-        if (h->device < 0) return AEGIS_ERR_INVALID;
-        long long v[16];
-        HIPCHK(h, hipSetDevice(h->device));
-        HIPCHK(h, hipDeviceSynchronize());
-        HIPCHK(h, cqt_debug_fetch(v));
-        if (dst && cap > 0) std::memcpy(dst, v, (size_t)std::min<int64_t>(cap, 16) * 8);
-        return 16;
-    }
-    else return AEGIS_ERR_INVALID;
-    if (h->device < 0 || !src) { h->err = "stage was not run"; return AEGIS_ERR_INVALID; }
-    if (dst && cap > 0) {
-        HIPCHK(h, hipSetDevice(h->device));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        HIPCHK(h, hipMemcpy(dst, src, (size_t)std::min(count, cap) * esz, hipMemcpyDeviceToHost));
-    }
-    return count;
     } catch (...) { return abi_fail(h); }
 }
 

@@ -1,0 +1,187 @@
+// Constant-Q entries of libaegis_hip.so (aegis_cqt, aegis_chroma_cqt, aegis_cqt_device) and aegis_rake_patterns.
+#include "aegis_internal.h"
+
+using namespace aegis;
+
+extern "C" {
+
+int aegis_rake_patterns(aegis_handle *h, const float *S_dB, int32_t n_mels, int64_t n_frames,
+                        double broadband_threshold_ratio, uint8_t *mask_out) {
+    try {
+    if (!h) return AEGIS_ERR_INVALID;
+    if (n_mels <= 0 || n_frames < 0 || (n_frames > 0 && (!S_dB || !mask_out))) { h->err = "bad argument"; return AEGIS_ERR_INVALID; }
+    if (n_frames == 0) return AEGIS_OK;
+    DEVICE_ONLY(h);
+    std::lock_guard<std::mutex> lock(h->mu);
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc;
+    const size_t img = (size_t)n_mels * n_frames * 4;
+    if ((rc = ensure(h, h->io_sdb, img)) != AEGIS_OK) return rc;
+    if ((rc = ensure(h, h->rk_raw, n_frames)) != AEGIS_OK) return rc;
+    if ((rc = ensure(h, h->io_rake, n_frames)) != AEGIS_OK) return rc;
+    hipStream_t s = h->stream;
+    HIPCHK(h, hipMemcpyAsync(h->io_sdb.p, S_dB, img, hipMemcpyHostToDevice, s));
+    const RakeBounds rb = rake_frame_bounds(h->tab);
+    launch_rake_from_db(static_cast<const float *>(h->io_sdb.p), n_mels, n_frames, broadband_threshold_ratio,
+                        rb.min_frames, rb.max_frames, static_cast<uint8_t *>(h->rk_raw.p),
+                        static_cast<uint8_t *>(h->io_rake.p), s);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(mask_out, h->io_rake.p, n_frames, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    return AEGIS_OK;
+    } catch (...) { return abi_fail(h); }
+}
+
+// the bank of (n_bins, bins_per_octave, fmin, filter_scale), built and uploaded on first use
+static int cqt_bank_locked(aegis_handle *h, int32_t &n_bins, int32_t &bins_per_octave, double &fmin, double &filter_scale, hipStream_t s) {
+    if (n_bins == 0) n_bins = 84;
+    if (bins_per_octave == 0) bins_per_octave = 12;
+    if (!(fmin > 0)) fmin = 32.70319566257483;            // note_to_hz('C1')
+    if (!(filter_scale > 0)) filter_scale = 1.0;
+    CqtBank &b = h->cqt_bank;
+    if (b.n_bins != n_bins || b.bins_per_octave != bins_per_octave || b.fmin != fmin || b.filter_scale != filter_scale || !b.dev) {
+        HIPCHK(h, hipStreamSynchronize(s));
+        if (b.dev) { (void)hipFree(b.dev); b.dev = nullptr; }
+        const char *msg = build_cqt_bank(b, h->tab.sr, n_bins, fmin, bins_per_octave, filter_scale);
+        if (msg[0]) { h->err = msg; b.n_bins = 0; return AEGIS_ERR_INVALID; }
+        // + 64 KiB: the slide kernel refills a tile's register queue unconditionally, so a wave's last groups request up to
+        // kSlotDepth KiB past its stream (never used)
+        HIPCHK(h, hipMalloc(reinterpret_cast<void **>(&b.dev), b.data.size() * 4 + 65536));
+        HIPCHK(h, hipMemset(reinterpret_cast<char *>(b.dev) + b.data.size() * 4, 0, 65536));
+        HIPCHK(h, hipMemcpy(b.dev, b.data.data(), b.data.size() * 4, hipMemcpyHostToDevice));
+    }
+    return AEGIS_OK;
+}
+
+// clip geometry on the device + the launch; d_pcm and d_out are device pointers
+static int cqt_launch_locked(aegis_handle *h, const float *d_pcm, const int64_t *soff, int32_t n_clips, float *d_out, hipStream_t s,
+                             int64_t *total_frames) {
+    std::vector<int64_t> foff(n_clips + 1, 0), toff(n_clips + 1, 0);
+    for (int i = 0; i < n_clips; ++i) {
+        const int64_t n = soff[i + 1] - soff[i];
+        if (n < 0) { h->err = "sample_offsets must be non-decreasing"; return AEGIS_ERR_INVALID; }
+        foff[i + 1] = foff[i] + 1 + n / h->tab.hop;
+        toff[i + 1] = toff[i] + (1 + n / h->tab.hop + kCqtSlideFrames - 1) / kCqtSlideFrames;
+    }
+    int rc;
+    if ((rc = ensure(h, h->q_soff, (n_clips + 1) * 8)) != AEGIS_OK) return rc;
+    if ((rc = ensure(h, h->q_foff, (n_clips + 1) * 8)) != AEGIS_OK) return rc;
+    if ((rc = ensure(h, h->q_toff, (n_clips + 1) * 8)) != AEGIS_OK) return rc;
+    // (pageable host vectors: the copies complete before hipMemcpyAsync returns)
+    HIPCHK(h, hipMemcpyAsync(h->q_soff.p, soff, (n_clips + 1) * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(h->q_foff.p, foff.data(), (n_clips + 1) * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(h->q_toff.p, toff.data(), (n_clips + 1) * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipStreamSynchronize(s));         // ... but the vectors die with this frame: make it certain
+    CqtArgs a{d_pcm, static_cast<const int64_t *>(h->q_soff.p), static_cast<const int64_t *>(h->q_foff.p), n_clips,
+              foff[n_clips], h->tab.hop, d_out};
+    drop_events(h);
+    begin_event(h, "cqt", s); launch_cqt(a, h->cqt_bank, static_cast<const int64_t *>(h->q_toff.p), toff[n_clips], s); end_event(h, s);
+    HIPCHK(h, hipGetLastError());
+    *total_frames = foff[n_clips];
+    return AEGIS_OK;
+}
+
+// What the two host-buffer entries share (handle locked, device set): the bank, the clips validated and packed, the staging
+// sized, the samples uploaded (behind the chroma fold's bin classes, when there are any), the CQT launched into q_out.
+// F: frames of all clips.
+static int cqt_host_locked(aegis_handle *h, const float *const *pcm, const int64_t *n_samples, int32_t n_clips, int32_t &n_bins,
+                           int32_t bins_per_octave, double fmin, double filter_scale, int32_t n_chroma, const int32_t *bin_class, int64_t *F_out) {
+    hipStream_t s = h->stream;
+    int rc;
+    if ((rc = cqt_bank_locked(h, n_bins, bins_per_octave, fmin, filter_scale, s)) != AEGIS_OK) return rc;
+    for (int b = 0; bin_class && b < n_bins; ++b)
+        if (bin_class[b] < 0 || bin_class[b] >= n_chroma) { h->err = "bin_class entries must lie in [0, n_chroma)"; return AEGIS_ERR_INVALID; }
+    std::vector<int64_t> soff(n_clips + 1, 0);
+    int64_t F = 0;
+    for (int i = 0; i < n_clips; ++i) {
+        if (n_samples[i] < 0 || (n_samples[i] > 0 && !pcm[i])) { h->err = "bad clip " + std::to_string(i); return AEGIS_ERR_INVALID; }
+        soff[i + 1] = soff[i] + n_samples[i];
+        F += 1 + n_samples[i] / h->tab.hop;
+    }
+    if ((rc = ensure(h, h->q_pcm, (size_t)std::max<int64_t>(soff[n_clips], 1) * 4)) != AEGIS_OK) return rc;
+    if ((rc = ensure(h, h->q_out, (size_t)F * n_bins * 4)) != AEGIS_OK) return rc;
+    if (bin_class) {
+        if ((rc = ensure(h, h->q_chroma, (size_t)F * n_chroma * 4)) != AEGIS_OK) return rc;
+        if ((rc = ensure(h, h->q_cls, (size_t)n_bins * 4)) != AEGIS_OK) return rc;
+        HIPCHK(h, hipMemcpyAsync(h->q_cls.p, bin_class, (size_t)n_bins * 4, hipMemcpyHostToDevice, s));
+    }
+    for (int i = 0; i < n_clips; ++i)
+        if (n_samples[i] > 0)
+            HIPCHK(h, hipMemcpyAsync(static_cast<float *>(h->q_pcm.p) + soff[i], pcm[i], n_samples[i] * 4, hipMemcpyHostToDevice, s));
+    int64_t Fd = 0;
+    *F_out = F;
+    return cqt_launch_locked(h, static_cast<const float *>(h->q_pcm.p), soff.data(), n_clips, static_cast<float *>(h->q_out.p), s, &Fd);
+}
+
+int aegis_cqt(aegis_handle *h, const float *const *pcm, const int64_t *n_samples, int32_t n_clips,
+              int32_t n_bins, int32_t bins_per_octave, double fmin, double filter_scale, float *mag_out) {
+    try {
+    if (!h) return AEGIS_ERR_INVALID;
+    if (n_clips < 0 || (n_clips > 0 && (!pcm || !n_samples || !mag_out))) { h->err = "null argument"; return AEGIS_ERR_INVALID; }
+    if (n_clips == 0) return AEGIS_OK;
+    DEVICE_ONLY(h);
+    std::lock_guard<std::mutex> lock(h->mu);
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    int rc;
+    int64_t F = 0;
+    if ((rc = cqt_host_locked(h, pcm, n_samples, n_clips, n_bins, bins_per_octave, fmin, filter_scale, 0, nullptr, &F)) != AEGIS_OK) return rc;
+    HIPCHK(h, hipMemcpyAsync(mag_out, h->q_out.p, (size_t)F * n_bins * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    if (h->profiling) collect_events(h);
+    return AEGIS_OK;
+    } catch (...) { return abi_fail(h); }
+}
+
+int aegis_chroma_cqt(aegis_handle *h, const float *const *pcm, const int64_t *n_samples, int32_t n_clips,
+                     int32_t n_bins, int32_t bins_per_octave, double fmin, double filter_scale, int32_t n_chroma,
+                     const int32_t *bin_class, float *chroma_out) {
+    try {
+    if (!h) return AEGIS_ERR_INVALID;
+    if (n_clips < 0 || (n_clips > 0 && (!pcm || !n_samples || !chroma_out)) || !bin_class) { h->err = "null argument"; return AEGIS_ERR_INVALID; }
+    if (n_clips == 0) return AEGIS_OK;
+    if (n_chroma < 1 || n_chroma > 24) { h->err = "n_chroma must be 1..24"; return AEGIS_ERR_INVALID; }
+    DEVICE_ONLY(h);
+    std::lock_guard<std::mutex> lock(h->mu);
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    int rc;
+    int64_t F = 0;
+    if ((rc = cqt_host_locked(h, pcm, n_samples, n_clips, n_bins, bins_per_octave, fmin, filter_scale, n_chroma, bin_class, &F)) != AEGIS_OK) return rc;
+    begin_event(h, "chroma", s);
+    launch_chroma_fold(static_cast<const float *>(h->q_out.p), static_cast<const int64_t *>(h->q_foff.p), n_clips, F, n_bins, n_chroma,
+                       static_cast<const int32_t *>(h->q_cls.p), static_cast<float *>(h->q_chroma.p), s);
+    end_event(h, s);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(chroma_out, h->q_chroma.p, (size_t)F * n_chroma * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    if (h->profiling) collect_events(h);
+    return AEGIS_OK;
+    } catch (...) { return abi_fail(h); }
+}
+
+int aegis_cqt_device(aegis_handle *h, const float *d_pcm, const int64_t *sample_offsets, int32_t n_clips,
+                     int32_t n_bins, int32_t bins_per_octave, double fmin, double filter_scale, float *d_mag_out,
+                     void *stream, int32_t sync) {
+    try {
+    if (!h) return AEGIS_ERR_INVALID;
+    if (n_clips < 0 || (n_clips > 0 && (!sample_offsets || !d_mag_out))) { h->err = "null argument"; return AEGIS_ERR_INVALID; }
+    if (n_clips == 0) return AEGIS_OK;
+    DEVICE_ONLY(h);
+    if (sample_offsets[n_clips] > sample_offsets[0] && !d_pcm) { h->err = "d_pcm == NULL"; return AEGIS_ERR_INVALID; }
+    std::lock_guard<std::mutex> lock(h->mu);
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
+    int rc;
+    if ((rc = cqt_bank_locked(h, n_bins, bins_per_octave, fmin, filter_scale, s)) != AEGIS_OK) return rc;
+    int64_t F = 0;
+    if ((rc = cqt_launch_locked(h, d_pcm, sample_offsets, n_clips, d_mag_out, s, &F)) != AEGIS_OK) return rc;
+    if (sync) {
+        HIPCHK(h, hipStreamSynchronize(s));
+        if (h->profiling) collect_events(h);
+    }
+    return AEGIS_OK;
+    } catch (...) { return abi_fail(h); }
+}
+
+}  // extern "C"

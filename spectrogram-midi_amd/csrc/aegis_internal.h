@@ -1,0 +1,202 @@
+// What the host-side files of libaegis_hip.so share: the handle, the stream, owned device buffers and events, the error
+// macros.  Internal: not installed, not included by include/aegis_hip.h.
+//   aegis_api.hip     the batch pipeline (plan input, workspaces, analyze_device_locked, recovery, the analyze entries)
+//   aegis_handle.hip  create / destroy, profiling, tables, parameters, aegis_debug_plan / aegis_debug_fetch
+//   aegis_stream.hip  aegis_stream_* (graph capture, commit delivery)
+//   aegis_cqt.hip     CQT, chroma, aegis_rake_patterns
+//   aegis_trend.hip   aegis_trend, aegis_ghost_rsi
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <cstring>
+#include <functional>
+#include <map>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "../../include/aegis_hip.h"
+#include "kernels.h"
+#include "plan.h"
+#include "cqt.h"
+#include "tables.h"
+
+// A grow-only device block.  It is freed by whoever's list ensure() entered it in (aegis_handle::bufs, aegis_stream::bufs):
+// a DevBuf member needs no other mention anywhere to be released.  PassParams and SplitCheck keep raw pointers into the
+// blocks across calls, and the lists keep DevBuf addresses: a DevBuf stays a member of its owner and never moves.
+struct DevBuf {
+    void *p = nullptr;
+    size_t cap = 0;
+    bool listed = false;
+};
+
+struct aegis_handle {
+    aegis::Tables tab;
+    aegis::DevTables dt{};
+    int device = 0;
+    hipStream_t stream = nullptr;
+    hipStream_t stream2 = nullptr;            // Viterbi stream of the time-chunked pipeline
+    bool troughs_off = false;                 // AEGIS_TROUGHS_IN_FRAME=0 at create
+    bool cmnd_off = false;                    // AEGIS_CMND_IN_FRAME=0 at create: pyin_obs_kernel walks the CMND cumsum (tests compare the two paths)
+    bool debug_stages = false;                // AEGIS_DEBUG_STAGES=1 at create: pyin_obs also writes the CMND rows ("yin") for the stage tests
+    hipStream_t stream4 = nullptr;            // second frame-stage stream: odd time chunks (their FFTs overlap the even chunks' YIN / observation kernels)
+    hipStream_t stream3 = nullptr;            // host->device sample copies of aegis_analyze_batch, chunk by chunk
+    // CU-partitioned stream sets of the pipeline (split_streams): [0] Viterbi on 64 CUs / frame stage on 192, [1] 128 / 128
+    struct SplitSet { hipStream_t frame_a = nullptr, frame_b = nullptr, viterbi = nullptr; bool tried = false; } split[2];
+    int n_cus = 0;                            // compute units of the device (CU masks are built for this count)
+    // Events (all made by new_event, which enters them in owned_events: teardown destroys that list).  The fixed ones exist
+    // from aegis_create on; sync_events grows by one per time chunk beyond its fixed slots.
+    std::vector<hipEvent_t> owned_events;
+    hipEvent_t copy_event = nullptr;
+    std::vector<hipEvent_t> sync_events;      // cross-stream dependencies (no timing)
+    hipEvent_t split_ev[2] = {nullptr, nullptr};   // around an automatic split call's Viterbi kernels: the planning rule checks its estimate against them
+    hipEvent_t hyb_ev[3] = {nullptr, nullptr, nullptr};
+    hipEvent_t fin_ev[2] = {nullptr, nullptr};       // fork / join of a split pass's two finishing streams (launch_viterbi_split)
+    int64_t max_frames_per_pass = 0;
+    int fail_allocs = 0;                             // test hook: workspace growths left to fail with AEGIS_ERR_NOMEM
+    mutable std::string err;
+    std::vector<void *> table_allocs;
+    std::vector<DevBuf *> bufs;               // every DevBuf of the handle that holds memory (ensure)
+    // workspaces (grow-only): passes alternate between the two, so that the frame stage of one pass runs under the
+    // Viterbi of the previous one
+    struct Work {
+        DevBuf dfn, yin, logobs, logunv, obs_seg, ptr, cmap, chunk_off, bnd, states, melpow, clipmax, rake_raw;
+        DevBuf sample_off, sample_len, out_off, frame_off, order, sel_off, vstate, chunk_lo, chunk_flag, clip_tb;
+        DevBuf seg64, seg32, seg_col, seg_map, seg_i32, colhist, colG, colkg, clip_flag, flag_order, tube_buf, tube_at, tube_count;    // time-split passes
+    } work[2];
+    DevBuf vstats, rk_raw, abort_flag, finite_flag;
+    uint32_t chunk_gen = 0;                   // generation of the chunk flags of a persistent Viterbi launch
+    int test_drop_signal = -1;
+    // The single Viterbi launch of a balanced pass and its fall-back (run_with_recovery, aegis_api.hip)
+    struct Persistent {
+        bool on = true;                       // one Viterbi launch per balanced pass now (false for `cooldown` calls after a give-up)
+        bool pending = false;                 // a persistent launch ran since the abort flag was last read
+        bool gave_up = false;
+        int cooldown = 0;                     // calls left on the one-launch-per-chunk schedule after a give-up; then the single launch is tried again
+        int64_t fallbacks = 0;                // calls repeated with one launch per chunk (aegis_debug_fetch "persistent_fallbacks")
+    } persist;
+    // Time-split passes: the verdicts still to read, and the rule that stops planning them when they do not pay (split_check)
+    struct SplitCheck { int pass; aegis::PassParams p; };
+    struct TimeSplit {
+        std::vector<SplitCheck> checks;       // split passes of the call in flight whose clip flags have not been read
+        int bad = 0;                          // automatic split calls in a row that did not pay (two of them start the cool-down)
+        int cooldown = 0;                     // automatic mode: calls left without time-split passes after one that did not pay (clips redone sequentially)
+        int64_t stats[4] = {0, 0, 0, 0};      // since create: split passes, segments, clips flagged for the sequential kernel, lock-on runs that never locked
+        double last_viterbi_ms = 0.0;         // measured Viterbi time of the call's last automatic split pass
+        int64_t last_carried_steps = 0;       // rounds of second speculation (viterbi_band.inc, phases 3 / 4) that had work in the call's last split pass
+        std::vector<int64_t> last_flags;      // per clip of the call's last split pass (pass order: longest first): the verification's verdict bits
+    } tsplit;
+    aegis::PlanKnobs knobs;                   // scheduling knobs (plan.h), read from the environment at create
+    aegis::CqtBank cqt_bank;
+    DevBuf q_pcm, q_soff, q_foff, q_toff, q_out, q_chroma, q_cls;
+    DevBuf t_x, t_off, t_a, t_b, t_c, t_d, t_e, t_i8, t_i64a, t_i64b;   // trend-filter staging
+    DevBuf t_pa;                              // scratch of the fused pitch analysis: 12 rows of doubles + 1 of bytes
+    DevBuf io_pcm, io_f0, io_voiced, io_vprob, io_rms, io_rake, io_sdb, io_bin, io_colmean;
+    DevBuf pcm_raw, pcm_clips, pcm_ranges, pcm_taps;   // aegis_analyze_pcm: raw bytes, clip table, per-chunk range tables, filters
+    int32_t lag_stride = 0, yin_stride = 0, obs_stride = 0;
+    aegis::CallPlan plan;                     // the last call's plan: its host arrays stay alive until the stream drained
+    bool plan_in_flight = false;              // the stream may still read them
+    // profiling
+    bool profiling = false;
+    std::vector<std::pair<std::string, std::pair<hipEvent_t, hipEvent_t>>> events;
+    std::map<std::string, double> last_ms;
+    std::map<std::string, int> last_count;
+    std::mutex mu;                            // one analyze call at a time per handle (server.py shares an engine)
+    // open aegis_stream objects keep the handle alive: aegis_destroy() with streams still open only marks the handle,
+    // the last aegis_stream_free() tears it down (either order of the two calls is safe)
+    int open_streams = 0;
+    bool destroy_requested = false;
+};
+
+// One clip fed incrementally (aegis_stream_*): its own PCM buffer and workspace, so batch calls on
+// the same handle may interleave.  Frames are analysed as soon as their 2048-sample window is
+// complete; the Viterbi column is carried across pushes exactly as the offline pipeline carries it
+// across time chunks, so aegis_stream_close() returns what aegis_analyze_batch() returns.
+struct aegis_stream {
+    aegis_handle *h = nullptr;
+    int64_t cap_samples = 0, cap_frames = 0;
+    int64_t n_samples = 0;      // samples received
+    int64_t frames_done = 0;    // frames analysed (= Viterbi columns produced)
+    bool closed = false;
+    std::vector<DevBuf *> bufs; // every DevBuf of the stream that holds memory (sized through the handle's ensure, owned here)
+    DevBuf pcm, dfn, logobs, logunv, obs_seg, ptr, cmap, bnd, states, live, melpow, clipmax, rake_raw, vstate, meta;
+    DevBuf o_f0, o_voiced, o_vprob, o_rms, o_rake, o_sdb;
+    std::vector<int64_t> host_meta;
+    // captured hipGraph of one fixed-size push (built lazily for the first push size that is a multiple of hop)
+    // ([0]: aegis_stream_push, [1]: aegis_stream_push_commit, the same chain with the commit kernel behind the Viterbi)
+    DevBuf ctl, g_staging, g_result;
+    float *pin_samples = nullptr;
+    unsigned char *pin_result = nullptr;
+    hipGraph_t graph[2] = {nullptr, nullptr};
+    hipGraphExec_t graph_exec[2] = {nullptr, nullptr};
+    int64_t graph_push[2] = {0, 0};
+    bool graph_failed = false;
+    // streaming commit (aegis_stream_push_commit): the device keeps the frontier in a StreamCommitCtl behind the StreamCtl
+    // of `ctl` and the decided bins in c_bins [cap_frames]; the host mirrors the frontier and counts what it handed out
+    DevBuf c_bins, c_result;
+    unsigned char *pin_commit = nullptr;               // kCommitResultBytes, pinned (the graph's second D2H copy)
+    unsigned char commit_host[aegis::kCommitResultBytes] = {};
+    int64_t c_frontier = -1;    // last decided frame on the device
+    int64_t c_newest = -1;      // newest frame the commit kernel has walked from
+    int64_t c_delivered = 0;    // frames handed to the caller so far
+    int64_t c_walked = 0, c_walked_wide = 0;    // frames the last commit launch walked, and how many of them as a bit mask
+};
+
+#define HIPCHK(h, expr)                                                                         \
+    do {                                                                                        \
+        hipError_t e__ = (expr);                                                                \
+        if (e__ != hipSuccess) {                                                                \
+            (h)->err = std::string(#expr) + ": " + hipGetErrorString(e__);                      \
+            return AEGIS_ERR_DEVICE;                                                            \
+        }                                                                                       \
+    } while (0)
+#define DEVICE_ONLY(h) \
+    do { if ((h)->device < 0) { (h)->err = "handle was created with device=-1 (host tables only)"; return AEGIS_ERR_DEVICE; } } while (0)
+
+namespace aegis {
+
+// ---- owned buffers and events (aegis_handle.hip) ----
+int grow_buf(aegis_handle *h, std::vector<DevBuf *> &owner, DevBuf &b, size_t bytes);
+// b holds at least `bytes` afterwards (growth rule, the fail_allocs hook and the owner's list: grow_buf)
+inline int ensure(aegis_handle *h, DevBuf &b, size_t bytes) { return bytes <= b.cap ? AEGIS_OK : grow_buf(h, h->bufs, b, bytes); }
+inline int ensure(aegis_stream *st, DevBuf &b, size_t bytes) { return bytes <= b.cap ? AEGIS_OK : grow_buf(st->h, st->bufs, b, bytes); }
+void free_bufs(std::vector<DevBuf *> &owner) noexcept;
+int new_event(aegis_handle *h, hipEvent_t *e, unsigned flags);
+void destroy_now(aegis_handle *h) noexcept;
+// Nothing is thrown across the C boundary (include/aegis_hip.h): every exported entry runs its body inside
+// try { ... } catch (...) { return abi_fail(h); }, which maps the in-flight exception to a return code.
+int abi_fail(aegis_handle *h) noexcept;
+
+// ---- profiling event pairs (aegis_handle.hip) ----
+void begin_event(aegis_handle *h, const char *name, hipStream_t s);
+void end_event(aegis_handle *h, hipStream_t s);
+void drop_events(aegis_handle *h) noexcept;       // destroys the pairs not collected
+void collect_events(aegis_handle *h);
+
+// ---- kernel parameters every entry fills the same way (aegis_api.hip) ----
+struct RakeBounds { int min_frames, max_frames; };
+RakeBounds rake_frame_bounds(const Tables &t);    // a rake lasts 10 .. 30 ms: in frames
+PassParams base_params(const Tables &t);          // (rake_frame_bounds included)
+int cmnd_in_frame(const aegis_handle *h);
+int troughs_in_frame(const aegis_handle *h);
+PlanInput plan_input(aegis_handle *h, const int64_t *sample_offsets, int32_t n_clips, uint32_t stages, bool feed,
+                     bool caller_stream, int32_t sync, int n_cus, std::function<bool(int)> masked);
+
+// The eight fields of aegis_outputs: which stage fills one, its bytes per frame (x n_mels for the dB image), where the pointer
+// sits in the struct, the staging buffer of the host-fed entries and the stream's own buffer (nullptr: a stream has none).
+struct OutField {
+    uint32_t stage;
+    int bytes;
+    bool per_mel;
+    size_t at;
+    DevBuf aegis_handle::*io;
+    DevBuf aegis_stream::*st;
+    size_t size(int64_t F, int n_mels) const { return (size_t)F * bytes * (per_mel ? n_mels : 1); }
+    void *get(const aegis_outputs *o) const { void *p; std::memcpy(&p, reinterpret_cast<const char *>(o) + at, sizeof p); return p; }
+    void set(aegis_outputs *o, void *p) const { std::memcpy(reinterpret_cast<char *>(o) + at, &p, sizeof p); }
+};
+extern const OutField kOutFields[8];
+
+}  // namespace aegis

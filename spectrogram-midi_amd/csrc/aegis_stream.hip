@@ -1,0 +1,383 @@
+// Streaming entries of libaegis_hip.so (aegis_stream_*): one clip fed push by push, the fixed-size push captured as a
+// hipGraph, delivery of the frames whose decode is already final.
+#include "aegis_internal.h"
+
+#include <cstdlib>
+#include <new>
+
+using namespace aegis;
+
+extern "C" {
+
+static PassParams stream_params(aegis_stream *st, const int64_t *dm) {
+    aegis_handle *h = st->h;
+    const Tables &t = h->tab;
+    PassParams p = base_params(t);
+    p.stages = AEGIS_STAGE_ALL;
+    p.pcm = static_cast<const float *>(st->pcm.p);
+    p.sample_off = dm; p.sample_len = dm + 1; p.frame_off = dm + 2; p.out_off = dm + 2; p.sel_off = dm + 4;
+    p.chunk_off = const_cast<int64_t *>(dm + 6);
+    p.order = reinterpret_cast<const int32_t *>(dm + 8);
+    p.n_clips = 1;
+    p.dfn = static_cast<double *>(st->dfn.p); p.lag_stride = h->lag_stride;
+    p.yin = nullptr; p.yin_stride = h->yin_stride;
+    p.cmnd_in_frame = cmnd_in_frame(h); p.troughs = troughs_in_frame(h);
+    p.logobs = static_cast<double *>(st->logobs.p); p.obs_stride = h->obs_stride;
+    p.logunv = static_cast<double *>(st->logunv.p);
+    p.obs_seg = static_cast<int32_t *>(st->obs_seg.p);
+    p.ptr = static_cast<uint16_t *>(st->ptr.p); p.cmap = static_cast<uint16_t *>(st->cmap.p);
+    p.bnd = static_cast<int32_t *>(st->bnd.p); p.states = static_cast<int32_t *>(st->states.p);
+    p.live_states = static_cast<int32_t *>(st->live.p);
+    p.melpow = static_cast<float *>(st->melpow.p); p.clipmax = static_cast<uint32_t *>(st->clipmax.p);
+    p.rake_raw = static_cast<uint8_t *>(st->rake_raw.p);
+    p.vstate = static_cast<double *>(st->vstate.p);
+    p.out_vprob = static_cast<double *>(st->o_vprob.p);
+    p.out_rms = static_cast<float *>(st->o_rms.p);
+    p.out_f0 = static_cast<double *>(st->o_f0.p); p.out_voiced = static_cast<uint8_t *>(st->o_voiced.p);
+    p.out_rake = static_cast<uint8_t *>(st->o_rake.p); p.out_sdb = static_cast<float *>(st->o_sdb.p);
+    p.rake_ratio = 0.6;
+    return p;
+}
+
+// Captures one fixed-size push as a hipGraph: H2D of the samples, advance (append + geometry), the four
+// analysis kernels reading their geometry from the device control block, result gather, D2H.
+static StreamCommitCtl *stream_commit_ctl(aegis_stream *st) {
+    return reinterpret_cast<StreamCommitCtl *>(static_cast<unsigned char *>(st->ctl.p) + sizeof(StreamCtl));
+}
+
+static bool stream_build_graph(aegis_stream *st, int64_t n_push, hipStream_t s, int commit) {
+    aegis_handle *h = st->h;
+    const Tables &t = h->tab;
+    if (!st->pin_samples || !st->pin_result || (commit && !st->pin_commit) || n_push > 8192 || n_push % t.hop != 0 || n_push / t.hop + 1 > 8) return false;
+    StreamCtl *ctl = static_cast<StreamCtl *>(st->ctl.p);
+    PassParams p = stream_params(st, ctl->meta);      // device address arithmetic only
+    p.ctl = ctl;
+    p.n_frames = st->cap_frames;
+    p.n_sel = n_push / t.hop + 1;                       // launch sizes; the kernels clamp to ctl->n_sel
+    if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) != hipSuccess) return false;
+    bool ok = true;
+    ok &= hipMemcpyAsync(st->g_staging.p, st->pin_samples, n_push * 4, hipMemcpyHostToDevice, s) == hipSuccess;
+    launch_stream_advance(ctl, static_cast<const float *>(st->g_staging.p), (int)n_push, static_cast<float *>(st->pcm.p), t.hop, s);
+    launch_frame(p, h->dt, s);
+    launch_pyin_obs(p, h->dt, s);
+    ok &= launch_viterbi(p, h->dt, t.log_trans_band.data(), s) == hipSuccess;
+    if (commit)
+        ok &= launch_stream_commit(ctl, 0, stream_commit_ctl(st), p.ptr, p.vstate, t.n_bins, static_cast<int16_t *>(st->c_bins.p),
+                                   st->c_result.p, s) == hipSuccess;
+    launch_stream_gather(ctl, p.out_rms, p.out_vprob, p.live_states, st->g_result.p, s);
+    ok &= hipMemcpyAsync(st->pin_result, st->g_result.p, 256, hipMemcpyDeviceToHost, s) == hipSuccess;
+    if (commit) ok &= hipMemcpyAsync(st->pin_commit, st->c_result.p, kCommitResultBytes, hipMemcpyDeviceToHost, s) == hipSuccess;
+    hipGraph_t g = nullptr;
+    ok &= hipStreamEndCapture(s, &g) == hipSuccess && g != nullptr;
+    if (!ok) { if (g) (void)hipGraphDestroy(g); (void)hipGetLastError(); return false; }
+    hipGraphExec_t ex = nullptr;
+    if (hipGraphInstantiate(&ex, g, nullptr, nullptr, 0) != hipSuccess) { (void)hipGraphDestroy(g); (void)hipGetLastError(); return false; }
+    st->graph[commit] = g; st->graph_exec[commit] = ex; st->graph_push[commit] = n_push;
+    return true;
+}
+
+static int stream_run(aegis_stream *st, int64_t f_lo, int64_t f_hi, bool final_pass, hipStream_t s) {
+    // analyses frames [f_lo, f_hi) and advances the Viterbi over them; final_pass also finishes the
+    // back-trace and the clip-global stages
+    aegis_handle *h = st->h;
+    const Tables &t = h->tab;
+    const int S = 2 * t.n_bins;
+    const int64_t Ftot = final_pass ? f_hi : st->cap_frames;     // clip length as far as the kernels know
+    // meta layout (int64): sample_off[2] | frame_off[2] | sel_off[2] | chunk_off[2] | order (int32 in one slot)
+    st->host_meta.assign(9, 0);
+    st->host_meta[1] = st->n_samples;
+    st->host_meta[3] = Ftot;
+    st->host_meta[5] = f_hi - f_lo;
+    st->host_meta[7] = (Ftot - 1 + kViterbiChunk - 1) / kViterbiChunk;
+    HIPCHK(h, hipMemcpyAsync(st->meta.p, st->host_meta.data(), 9 * 8, hipMemcpyHostToDevice, s));
+    const int64_t *dm = static_cast<const int64_t *>(st->meta.p);
+    PassParams p = stream_params(st, dm);
+    p.n_frames = Ftot;
+    p.t_begin = f_lo; p.n_sel = f_hi - f_lo;
+    p.vt_begin = f_lo; p.vt_end = final_pass ? INT64_MAX : f_hi;
+    (void)S;
+    if (p.n_sel > 0) {
+        launch_frame(p, h->dt, s);
+        launch_pyin_obs(p, h->dt, s);
+    }
+    if (p.n_sel > 0 || final_pass) {
+        hipError_t ve = launch_viterbi(p, h->dt, t.log_trans_band.data(), s);
+        if (ve != hipSuccess) { h->err = std::string("viterbi launch: ") + hipGetErrorString(ve); return AEGIS_ERR_DEVICE; }
+    }
+    HIPCHK(h, hipGetLastError());
+    return AEGIS_OK;
+}
+
+// Releases everything a stream owns.  The caller holds h->mu, or the stream was never handed out.
+static void stream_release(aegis_stream *st) noexcept {
+    if (st->h && st->h->device >= 0) { (void)hipSetDevice(st->h->device); (void)hipStreamSynchronize(st->h->stream); }
+    for (int k = 0; k < 2; ++k) {
+        if (st->graph_exec[k]) (void)hipGraphExecDestroy(st->graph_exec[k]);
+        if (st->graph[k]) (void)hipGraphDestroy(st->graph[k]);
+    }
+    if (st->pin_samples) (void)hipHostFree(st->pin_samples);
+    if (st->pin_result) (void)hipHostFree(st->pin_result);
+    if (st->pin_commit) (void)hipHostFree(st->pin_commit);
+    free_bufs(st->bufs);
+    delete st;
+}
+
+static int stream_open_locked(aegis_handle *h, int64_t max_samples, aegis_stream *st) {
+    HIPCHK(h, hipSetDevice(h->device));
+    st->h = h;
+    const Tables &t = h->tab;
+    st->cap_samples = max_samples;
+    st->cap_frames = 1 + max_samples / t.hop;
+    const int64_t F = st->cap_frames, S = 2 * t.n_bins;
+    const int64_t nch = (F - 1 + kViterbiChunk - 1) / kViterbiChunk + 1;
+    int rc = AEGIS_OK;
+    auto need = [&](DevBuf &b, size_t bytes) { if (rc == AEGIS_OK) rc = ensure(st, b, bytes); };      // (the handle's fail_allocs hook, the stream's list)
+    need(st->pcm, max_samples * 4); need(st->dfn, F * h->lag_stride * 8);
+    need(st->logobs, F * h->obs_stride * 8); need(st->logunv, F * 8); need(st->obs_seg, F * 4); need(st->ptr, F * S * 2);
+    need(st->cmap, nch * S * 2); need(st->bnd, nch * 4); need(st->states, F * 4); need(st->live, F * 4);
+    need(st->melpow, F * t.n_mels * 4); need(st->clipmax, 16); need(st->rake_raw, F); need(st->vstate, S * 8);
+    need(st->meta, 9 * 8); need(st->ctl, sizeof(StreamCtl) + sizeof(StreamCommitCtl)); need(st->g_staging, 8192 * 4); need(st->g_result, 256);
+    need(st->c_bins, F * 2); need(st->c_result, kCommitResultBytes);
+    need(st->o_f0, F * 8); need(st->o_voiced, F); need(st->o_vprob, F * 8); need(st->o_rms, F * 4); need(st->o_rake, F);
+    need(st->o_sdb, F * t.n_mels * 4);
+    if (rc != AEGIS_OK) return rc;
+    HIPCHK(h, hipMemsetAsync(st->clipmax.p, 0, 16, h->stream));
+    // The band Viterbi leaves the back-pointer of a dead voiced state unwritten, and a launch that starts inside a 16-step
+    // chunk (any push that is not a whole number of chunks) walks the rows of the chunk's earlier steps for EVERY state to
+    // rebuild its chunk map (viterbi_band.inc, "rebuilds org from the HBM pointers").  What it reads for a dead state is
+    // never used, but it is used as the next index: with recycled memory behind the rows an index up to 65535 reaches
+    // 128 KB past a short stream's last row (an illegal access on a 0.5 s stream, met in the test suite).  Zeroed rows keep
+    // every such index at state 0.
+    HIPCHK(h, hipMemsetAsync(st->ptr.p, 0, (size_t)F * S * 2, h->stream));
+    {
+        struct { StreamCtl ctl; StreamCommitCtl commit; } c0{};
+        static_assert(sizeof(c0) == sizeof(StreamCtl) + sizeof(StreamCommitCtl), "the commit block sits right behind the control block");
+        c0.ctl.meta[3] = st->cap_frames;
+        c0.ctl.meta[7] = (st->cap_frames - 1 + kViterbiChunk - 1) / kViterbiChunk;
+        c0.commit.frontier = -1; c0.commit.newest = -1;
+        HIPCHK(h, hipMemcpyAsync(st->ctl.p, &c0, sizeof(c0), hipMemcpyHostToDevice, h->stream));
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (hipHostMalloc(reinterpret_cast<void **>(&st->pin_samples), 8192 * 4, hipHostMallocDefault) != hipSuccess) st->pin_samples = nullptr;
+    if (hipHostMalloc(reinterpret_cast<void **>(&st->pin_result), 256, hipHostMallocDefault) != hipSuccess) st->pin_result = nullptr;
+    if (hipHostMalloc(reinterpret_cast<void **>(&st->pin_commit), kCommitResultBytes, hipHostMallocDefault) != hipSuccess) st->pin_commit = nullptr;
+    // AEGIS_STREAM_GRAPH=0 keeps every push on the plain-launch path, =1 allows the hipGraph replay.  Unset: the replay,
+    // except under an injected rocprofiler tool -- round 1's SIGSEGV in aegis_stream_push (profiles/
+    // r1_stream_push_sigsegv_symbolised.txt) was the profiler-side packet copy of an INTERCEPTED queue running off the end
+    // of a 1 MiB AQL ring when the HIP runtime rang the doorbell for a graph launch: not this library's memory, and not
+    // something this library can fix, so profiled runs take the plain launches unless told otherwise.
+    if (const char *e = std::getenv("AEGIS_STREAM_GRAPH")) st->graph_failed = (e[0] == '0');
+    else {
+        const char *tool = std::getenv("ROCP_TOOL_LIBRARIES"), *pre = std::getenv("LD_PRELOAD");
+        if ((tool && tool[0]) || (pre && std::strstr(pre, "rocprofiler"))) st->graph_failed = true;
+    }
+    return AEGIS_OK;
+}
+
+int aegis_stream_open(aegis_handle *h, int64_t max_samples, aegis_stream **out) {
+    aegis_stream *st = nullptr;
+    try {
+    if (!h || !out || max_samples <= 0) { if (h) h->err = "bad argument"; return AEGIS_ERR_INVALID; }
+    *out = nullptr;
+    DEVICE_ONLY(h);
+    std::lock_guard<std::mutex> lock(h->mu);
+    if (h->destroy_requested) { h->err = "handle was destroyed"; return AEGIS_ERR_INVALID; }
+    st = new (std::nothrow) aegis_stream();
+    if (!st) { h->err = "out of host memory"; return AEGIS_ERR_NOMEM; }
+    const int rc = stream_open_locked(h, max_samples, st);
+    if (rc != AEGIS_OK) { stream_release(st); st = nullptr; return rc; }     // nothing leaks on a failed open
+    ++h->open_streams;
+    *out = st;
+    return AEGIS_OK;
+    } catch (...) {
+        const int code = abi_fail(h);
+        if (st) stream_release(st);
+        return code;
+    }
+}
+
+void aegis_stream_free(aegis_stream *st) {
+    if (!st) return;
+    aegis_handle *h = st->h;
+    if (!h) { stream_release(st); return; }
+    bool last;
+    {
+        std::lock_guard<std::mutex> lock(h->mu);
+        stream_release(st);
+        --h->open_streams;
+        last = h->destroy_requested && h->open_streams == 0;
+    }
+    if (last) destroy_now(h);     // aegis_destroy() was called while this stream was still open
+}
+
+// The host's half of a commit push, after the stream has drained: `res` is the commit kernel's result block (nullptr: no
+// launch was needed, the device frontier is where it was).  Hands out the next decided frames, `cap` at most.
+static int stream_deliver(aegis_stream *st, const unsigned char *res, aegis_stream_commit *commit) {
+    aegis_handle *h = st->h;
+    int64_t staged_lo = -1;
+    if (res) {
+        int64_t r[4];
+        std::memcpy(r, res, 32);
+        if (r[3] < 0) { h->err = "stream commit: the walk met a back-pointer the Viterbi never wrote"; return AEGIS_ERR_DEVICE; }
+        if (r[0] != st->c_frontier || r[1] < r[0] || r[1] >= st->frames_done) {
+            h->err = "stream commit: device and host disagree on the frontier"; return AEGIS_ERR_DEVICE;
+        }
+        staged_lo = r[0] + 1;
+        st->c_frontier = r[1];
+        st->c_walked = r[3] & 0xffffffff;
+        st->c_walked_wide = r[3] >> 32;
+        st->c_newest = st->frames_done - 1;
+    } else {
+        st->c_walked = st->c_walked_wide = 0;
+    }
+    const int64_t first = st->c_delivered;
+    const int64_t k = std::min<int64_t>(st->c_frontier + 1 - first, commit->cap);
+    if (k > 0) {
+        if (staged_lo >= 0 && first >= staged_lo && first + k <= staged_lo + kCommitStage)
+            std::memcpy(commit->pitch_bin, res + 32 + 2 * (first - staged_lo), (size_t)k * 2);
+        else
+            HIPCHK(h, hipMemcpy(commit->pitch_bin, static_cast<int16_t *>(st->c_bins.p) + first, (size_t)k * 2, hipMemcpyDeviceToHost));
+        st->c_delivered += k;
+    }
+    commit->first = first;
+    commit->count = k > 0 ? k : 0;
+    commit->frontier = st->c_delivered - 1;
+    commit->walked = st->c_walked;
+    commit->walked_wide = st->c_walked_wide;
+    return AEGIS_OK;
+}
+
+// aegis_stream_push (commit == nullptr: exactly the launches of a stream without the commit) and aegis_stream_push_commit.
+// The caller holds h->mu.
+static int stream_push_locked(aegis_stream *st, const float *samples, int64_t n, aegis_stream_frames *out, int64_t *n_frames,
+                              aegis_stream_commit *commit) {
+    aegis_handle *h = st->h;
+    if (h->destroy_requested) { h->err = "handle was destroyed"; return AEGIS_ERR_INVALID; }
+    if (n < 0 || (n > 0 && !samples) || !n_frames) { h->err = "bad argument"; return AEGIS_ERR_INVALID; }
+    if (commit && (commit->cap < 0 || (commit->cap > 0 && !commit->pitch_bin))) { h->err = "bad argument"; return AEGIS_ERR_INVALID; }
+    if (st->closed) { h->err = "stream is closed"; return AEGIS_ERR_INVALID; }
+    if (st->n_samples + n > st->cap_samples) { h->err = "stream capacity exceeded"; return AEGIS_ERR_INVALID; }
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    const int ci = commit ? 1 : 0;
+    // ---- fixed-size pushes replay a captured hipGraph ---------------------------------------------
+    const bool eligible = n > 0 && n <= 8192 && n % h->tab.hop == 0 && n / h->tab.hop + 1 <= 8;
+    if (eligible && !st->graph_failed && (st->graph_exec[ci] == nullptr || st->graph_push[ci] == n)) {
+        if (st->graph_exec[ci] == nullptr && !stream_build_graph(st, n, s, ci)) st->graph_failed = true;
+        if (st->graph_exec[ci] != nullptr && st->graph_push[ci] == n) {
+            std::memcpy(st->pin_samples, samples, (size_t)n * 4);
+            HIPCHK(h, hipGraphLaunch(st->graph_exec[ci], s));
+            HIPCHK(h, hipStreamSynchronize(s));
+            st->n_samples += n;
+            const int64_t ready = st->n_samples >= kFrameLength / 2 ? (st->n_samples - kFrameLength / 2) / h->tab.hop + 1 : 0;
+            const int64_t lo = st->frames_done, hi = std::max(lo, ready);
+            int64_t got = 0;
+            std::memcpy(&got, st->pin_result, 8);
+            if (got != hi - lo) { h->err = "stream graph and host disagree on the frame count"; return AEGIS_ERR_DEVICE; }
+            st->frames_done = hi;
+            *n_frames = got;
+            if (out) {
+                if (out->rms) std::memcpy(out->rms, st->pin_result + 8, (size_t)got * 4);
+                if (out->voiced_prob) std::memcpy(out->voiced_prob, st->pin_result + 8 + 32, (size_t)got * 8);
+                if (out->live_state) std::memcpy(out->live_state, st->pin_result + 8 + 32 + 64, (size_t)got * 4);
+            }
+            return commit ? stream_deliver(st, st->pin_commit, commit) : AEGIS_OK;
+        }
+    }
+    if (n > 0)
+        HIPCHK(h, hipMemcpyAsync(static_cast<float *>(st->pcm.p) + st->n_samples, samples, n * 4, hipMemcpyHostToDevice, s));
+    st->n_samples += n;
+    // frames whose centred window [t*hop - 1024, t*hop + 1024) is complete
+    const int hop = h->tab.hop;
+    const int64_t ready = st->n_samples >= kFrameLength / 2 ? (st->n_samples - kFrameLength / 2) / hop + 1 : 0;
+    const int64_t lo = st->frames_done, hi = std::max(lo, ready);
+    *n_frames = hi - lo;
+    if (hi > lo) {
+        int rc = stream_run(st, lo, hi, false, s);
+        if (rc != AEGIS_OK) return rc;
+        st->frames_done = hi;
+        if (out) {
+            const int64_t k = hi - lo;
+            if (out->rms) HIPCHK(h, hipMemcpyAsync(out->rms, static_cast<float *>(st->o_rms.p) + lo, k * 4, hipMemcpyDeviceToHost, s));
+            if (out->voiced_prob) HIPCHK(h, hipMemcpyAsync(out->voiced_prob, static_cast<double *>(st->o_vprob.p) + lo, k * 8, hipMemcpyDeviceToHost, s));
+            if (out->live_state) HIPCHK(h, hipMemcpyAsync(out->live_state, static_cast<int32_t *>(st->live.p) + lo, k * 4, hipMemcpyDeviceToHost, s));
+        }
+    }
+    {   // the device control block of the graph path mirrors the host counters
+        const int64_t counters[2] = {st->n_samples, st->frames_done};
+        HIPCHK(h, hipMemcpyAsync(st->ctl.p, counters, 16, hipMemcpyHostToDevice, s));
+    }
+    // commit: one more launch behind the Viterbi, when there is a frame the last walk has not seen (also the frames of
+    // earlier plain pushes: the walk goes from the newest frame back to the frontier, however far that is)
+    unsigned char *cres = nullptr;
+    if (commit && st->frames_done > 0 && st->frames_done - 1 != st->c_newest) {
+        cres = st->pin_commit ? st->pin_commit : st->commit_host;
+        hipError_t ce = launch_stream_commit(nullptr, st->frames_done, stream_commit_ctl(st), static_cast<const uint16_t *>(st->ptr.p),
+                                             static_cast<const double *>(st->vstate.p), h->tab.n_bins, static_cast<int16_t *>(st->c_bins.p),
+                                             st->c_result.p, s);
+        if (ce != hipSuccess) { h->err = std::string("stream commit launch: ") + hipGetErrorString(ce); return AEGIS_ERR_DEVICE; }
+        HIPCHK(h, hipMemcpyAsync(cres, st->c_result.p, kCommitResultBytes, hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(h, hipStreamSynchronize(s));
+    return commit ? stream_deliver(st, cres, commit) : AEGIS_OK;
+}
+
+int aegis_stream_push(aegis_stream *st, const float *samples, int64_t n, aegis_stream_frames *out, int64_t *n_frames) {
+    try {
+    if (!st || !st->h) return AEGIS_ERR_INVALID;
+    std::lock_guard<std::mutex> lock(st->h->mu);
+    return stream_push_locked(st, samples, n, out, n_frames, nullptr);
+    } catch (...) { return abi_fail((st ? st->h : nullptr)); }
+}
+
+int aegis_stream_push_commit(aegis_stream *st, const float *samples, int64_t n, aegis_stream_frames *out, int64_t *n_frames,
+                             aegis_stream_commit *commit) {
+    try {
+    if (!st || !st->h) return AEGIS_ERR_INVALID;
+    std::lock_guard<std::mutex> lock(st->h->mu);
+    return stream_push_locked(st, samples, n, out, n_frames, commit);
+    } catch (...) { return abi_fail((st ? st->h : nullptr)); }
+}
+
+int aegis_stream_close(aegis_stream *st, double rake_sensitivity, aegis_outputs *out, int64_t *n_frames) {
+    try {
+    if (!st || !st->h) return AEGIS_ERR_INVALID;
+    aegis_handle *h = st->h;
+    std::lock_guard<std::mutex> lock(h->mu);
+    if (h->destroy_requested) { h->err = "handle was destroyed"; return AEGIS_ERR_INVALID; }
+    if (!n_frames) { h->err = "bad argument"; return AEGIS_ERR_INVALID; }
+    if (st->closed) { h->err = "stream is closed"; return AEGIS_ERR_INVALID; }
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    const Tables &t = h->tab;
+    const int64_t F = 1 + st->n_samples / t.hop;
+    int rc = stream_run(st, st->frames_done, F, true, s);       // zero-padded tail frames + back-trace
+    if (rc != AEGIS_OK) return rc;
+    // clip-global stages over all F frames
+    st->host_meta[5] = F;
+    PassParams p = base_params(t);
+    p.stages = AEGIS_STAGE_ALL;
+    const int64_t *dm = static_cast<const int64_t *>(st->meta.p);
+    p.sample_off = dm; p.sample_len = dm + 1; p.frame_off = dm + 2; p.out_off = dm + 2; p.sel_off = dm + 2; p.n_clips = 1; p.n_frames = F; p.n_sel = F;
+    p.states = static_cast<int32_t *>(st->states.p);
+    p.melpow = static_cast<float *>(st->melpow.p); p.clipmax = static_cast<uint32_t *>(st->clipmax.p);
+    p.rake_raw = static_cast<uint8_t *>(st->rake_raw.p);
+    p.out_f0 = static_cast<double *>(st->o_f0.p); p.out_voiced = static_cast<uint8_t *>(st->o_voiced.p);
+    p.out_rake = static_cast<uint8_t *>(st->o_rake.p); p.out_sdb = static_cast<float *>(st->o_sdb.p);
+    p.rake_ratio = rake_sensitivity;
+    launch_finalize_mel(p, h->dt, s);
+    launch_decode(p, h->dt, s);
+    HIPCHK(h, hipGetLastError());
+    st->frames_done = F;
+    st->closed = true;
+    *n_frames = F;
+    if (out) {
+        for (const OutField &f : kOutFields)
+            if (f.st && f.get(out)) HIPCHK(h, hipMemcpyAsync(f.get(out), (st->*f.st).p, f.size(F, t.n_mels), hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(h, hipStreamSynchronize(s));
+    return AEGIS_OK;
+    } catch (...) { return abi_fail((st ? st->h : nullptr)); }
+}
+
+}  // extern "C"

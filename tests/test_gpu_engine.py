@@ -996,6 +996,19 @@ def test_out_of_memory_retry_halves_the_passes():
     for k in want:
         np.testing.assert_array_equal(got[k], want[k], err_msg=k)
     h.close()
+    # The host-buffer entry goes through the same policy.  Its staging buffers are sized before the attempt (smaller passes
+    # would not make them smaller), so one clip as long as the three together grows them first; that call leaves the
+    # workspace's per-clip rows (the Viterbi column carried from chunk to chunk) sized for one clip, and the first growth
+    # of the three-clip call is the workspace's.
+    h = _lib.Handle()
+    before = h.param("max_frames_per_pass")
+    h.analyze_batch([np.concatenate(clips + [np.zeros(4 * 512, np.float32)])])
+    h.lib.aegis_debug_fetch(h._h, b"fail_allocs", None, 1)
+    host = h.analyze_batch(clips)
+    assert h.param("max_frames_per_pass") == max(2 ** 21, before // 2)
+    for k in want:
+        np.testing.assert_array_equal(np.concatenate([r[k] for r in host]).astype(want[k].dtype), want[k], err_msg=f"host {k}")
+    h.close()
     h = _lib.Handle(max_frames_per_pass=2 ** 21)
     h.lib.aegis_debug_fetch(h._h, b"fail_allocs", None, 1)
     with pytest.raises(_lib.AegisError) as ei:
