@@ -360,6 +360,48 @@ int64_t aegis_render_smf(int32_t sample_rate, int32_t hop_length, int32_t midi_p
                          uint8_t *out, int64_t cap, int64_t *clip_byte_off);
 const char *aegis_events_last_error(void);
 
+/* --- ADSR soft-synth: Standard MIDI File bytes -> int16 samples (aegis_engine_core/synthesizer.py:179-507) -------
+ * The reference's pure-NumPy ADSRSynthesizer, which its callers fall back to when FluidSynth is absent (server.py:273-275,
+ * :322-324, :368; aegis_tuner_pro.py:344), and the middle step of every Auto-Match candidate (auto_matcher.py:162-165).
+ * Three steps, so that a caller sizes its own buffers:
+ *   aegis_synth_parse_smf    the notes the loop of midi_to_wav closes, in the order it closes them (synthesizer.py:423-467),
+ *                            and mido's MidiFile.length (:409).  Host code: a device=-1 handle serves too.  SMF type 0 / 1,
+ *                            running status, meta and sysex events skipped, pitch-wheel and program messages ignored as the
+ *                            reference ignores them.  The reference's quirks are kept: ONE tempo converts every delta of
+ *                            the file, the first set_tempo of the last track that has one (_get_tempo, :487-507), while
+ *                            the length honours every tempo change; a re-struck note overwrites the active entry; notes
+ *                            never closed are dropped; duration = max(0.01, end - start).  Returns the note count (which
+ *                            may exceed cap: nothing past cap is written) or a negative code.
+ *   aegis_synth_samples_for  total_samples of a render: int(sample_rate * ((length > 0 ? length : 10) + release_ms / 1000 +
+ *                            0.5)) (:409-415); no handle.
+ *   aegis_synth_adsr         n_clips note lists (clip c = notes[note_off[c] .. note_off[c+1]), each with its own length and
+ *                            parameters, rendered in ONE device pass: per-note oscillator with up to five harmonics below
+ *                            sample_rate / 2, per-note peak normalisation, the ADSR envelope (truncated for short notes, as
+ *                            generate_envelope truncates it, :226-265), velocity, the mix in the reference's order, the
+ *                            master normalisation to 0.9 and the int16 conversion (:469-475).  out[c] is host memory of
+ *                            out_cap[c] >= aegis_synth_samples_for(...) samples.  The samples equal the reference's bit for
+ *                            bit for sawtooth, triangle and square; for sine within one step (the device sin is not libm's).
+ *                            sample_rate is the render's own: the handle supplies the device, its stream and its buffers,
+ *                            not its analysis rate.  Blocking. */
+#define AEGIS_WAVE_SINE 0
+#define AEGIS_WAVE_SAWTOOTH 1
+#define AEGIS_WAVE_SQUARE 2
+#define AEGIS_WAVE_TRIANGLE 3
+typedef struct aegis_synth_note {
+    double start, duration;       /* seconds */
+    int32_t note, velocity;
+} aegis_synth_note;
+typedef struct aegis_adsr_params {
+    double attack_ms, decay_ms, sustain_level, release_ms;   /* GUITAR_ADSR_PRESETS, synthesizer.py:179-200 */
+    int32_t waveform;             /* AEGIS_WAVE_* */
+    int32_t reserved;
+} aegis_adsr_params;
+int64_t aegis_synth_parse_smf(aegis_handle *h, const uint8_t *smf, int64_t n_bytes, aegis_synth_note *notes, int64_t cap,
+                              double *length_seconds);
+int64_t aegis_synth_samples_for(int32_t sample_rate, double length_seconds, const aegis_adsr_params *params);
+int aegis_synth_adsr(aegis_handle *h, int32_t sample_rate, int32_t n_clips, const aegis_synth_note *notes, const int64_t *note_off,
+                     const double *length_seconds, const aegis_adsr_params *params, int16_t *const *out, const int64_t *out_cap);
+
 /* --- introspection used by the tests (no reference counterpart) ------------- */
 
 /* Host-side copies of the tables the kernels use.  `name` is one of

@@ -52,12 +52,25 @@ class Outputs(C.Structure):
                 ("rms", C.c_void_p), ("rake_mask", C.c_void_p), ("S_dB", C.c_void_p), ("pitch_bin", C.c_void_p), ("sdb_col_means", C.c_void_p)]
 
 
+class SynthNote(C.Structure):
+    _fields_ = [("start", C.c_double), ("duration", C.c_double), ("note", C.c_int32), ("velocity", C.c_int32)]
+
+
+class AdsrParams(C.Structure):
+    _fields_ = [("attack_ms", C.c_double), ("decay_ms", C.c_double), ("sustain_level", C.c_double), ("release_ms", C.c_double),
+                ("waveform", C.c_int32), ("reserved", C.c_int32)]
+
+
+WAVEFORMS = {"sine": 0, "sawtooth": 1, "square": 2, "triangle": 3}          # AEGIS_WAVE_*
+SYNTH_NOTE_DTYPE = np.dtype([("start", "<f8"), ("duration", "<f8"), ("note", "<i4"), ("velocity", "<i4")])
+
 EXPORTS = ("aegis_abi_version", "aegis_create", "aegis_destroy", "aegis_last_error", "aegis_frames_for",
            "aegis_analyze_batch", "aegis_analyze_batch_device", "aegis_get_table", "aegis_get_param",
            "aegis_debug_fetch", "aegis_set_profiling", "aegis_last_kernel_ms", "aegis_rake_patterns", "aegis_set_table", "aegis_last_kernel_launches", "aegis_trend", "aegis_ghost_rsi",
            "aegis_stream_open", "aegis_stream_push", "aegis_stream_close", "aegis_stream_free", "aegis_cqt", "aegis_cqt_device", "aegis_chroma_cqt",
            "aegis_extract_events", "aegis_render_smf", "aegis_events_last_error", "aegis_debug_plan",
-           "aegis_analyze_pcm", "aegis_pcm_samples_for", "aegis_resample_taps", "aegis_stream_push_commit")
+           "aegis_analyze_pcm", "aegis_pcm_samples_for", "aegis_resample_taps", "aegis_stream_push_commit",
+           "aegis_synth_parse_smf", "aegis_synth_samples_for", "aegis_synth_adsr")
 
 _lib = None
 
@@ -138,6 +151,13 @@ def load():
     lib.aegis_debug_fetch.restype = C.c_int64
     lib.aegis_debug_plan.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64]
     lib.aegis_debug_plan.restype = C.c_int64
+    lib.aegis_synth_parse_smf.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_double)]
+    lib.aegis_synth_parse_smf.restype = C.c_int64
+    lib.aegis_synth_samples_for.argtypes = [C.c_int32, C.c_double, C.POINTER(AdsrParams)]
+    lib.aegis_synth_samples_for.restype = C.c_int64
+    lib.aegis_synth_adsr.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(AdsrParams),
+                                     C.POINTER(C.c_void_p), C.c_void_p]
+    lib.aegis_synth_adsr.restype = C.c_int
     lib.aegis_set_profiling.argtypes = [C.c_void_p, C.c_int32]
     lib.aegis_set_profiling.restype = C.c_int
     lib.aegis_last_kernel_ms.argtypes = [C.c_void_p, C.c_char_p]
@@ -520,6 +540,49 @@ class Handle:
         self._check(self.lib.aegis_cqt_device(self._h, C.c_void_p(int(d_pcm_ptr)), off.ctypes.data_as(C.POINTER(C.c_int64)),
                                               len(off) - 1, n_bins, bins_per_octave, float(fmin), float(filter_scale),
                                               C.c_void_p(int(d_out_ptr)), C.c_void_p(stream or 0), 1 if sync else 0))
+
+    def synth_parse_smf(self, midi_bytes):
+        """aegis_synth_parse_smf: (notes in the reference's mix order as a SYNTH_NOTE_DTYPE array, mido's length in
+        seconds) of a Standard MIDI File; ValueError for bytes that are not one (mido raises).  Host code."""
+        blob = bytes(midi_bytes)
+        length = C.c_double(0.0)
+        notes = np.empty(max(len(blob) // 3, 1), SYNTH_NOTE_DTYPE)      # a note takes two messages of three bytes or more
+        n = int(self.lib.aegis_synth_parse_smf(self._h, blob, len(blob), notes.ctypes.data, len(notes), C.byref(length)))
+        if n == ERR_INVALID:
+            raise ValueError(self.lib.aegis_last_error(self._h).decode())
+        if n < 0 or n > len(notes):
+            raise AegisError(n, self.lib.aegis_last_error(self._h).decode())
+        return notes[:n].copy(), float(length.value)
+
+    @staticmethod
+    def adsr_params(attack_ms=10, decay_ms=50, sustain_level=0.7, release_ms=100, waveform="sawtooth"):
+        if waveform not in WAVEFORMS:
+            raise ValueError(f"unsupported waveform: {waveform}. Choose from 'sine', 'sawtooth', 'square', 'triangle'.")
+        return AdsrParams(float(attack_ms), float(decay_ms), float(sustain_level), float(release_ms), WAVEFORMS[waveform], 0)
+
+    def synth_adsr(self, note_lists, lengths, params, sample_rate):
+        """aegis_synth_adsr: one device pass for a batch of note lists (SYNTH_NOTE_DTYPE arrays), each with its file
+        length in seconds and its AdsrParams -> list of int16 arrays."""
+        n = len(note_lists)
+        if n == 0:
+            return []
+        lib = self.lib
+        par = (AdsrParams * n)(*params)
+        sizes = [int(lib.aegis_synth_samples_for(int(sample_rate), float(lengths[i]), C.byref(par[i]))) for i in range(n)]
+        if min(sizes) < 0:
+            raise ValueError("bad ADSR parameters, sample rate or length")
+        off = np.concatenate([[0], np.cumsum([len(a) for a in note_lists])]).astype(np.int64)
+        notes = np.ascontiguousarray(np.concatenate(note_lists) if off[-1] else np.empty(0, SYNTH_NOTE_DTYPE), dtype=SYNTH_NOTE_DTYPE)
+        lens = np.ascontiguousarray(lengths, dtype=np.float64)
+        outs = [np.empty(k, np.int16) for k in sizes]
+        ptrs = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
+        caps = np.asarray(sizes, np.int64)
+        rc = lib.aegis_synth_adsr(self._h, int(sample_rate), n, notes.ctypes.data, off.ctypes.data, lens.ctypes.data, par, ptrs,
+                                  caps.ctypes.data)
+        if rc == ERR_INVALID:
+            raise ValueError(lib.aegis_last_error(self._h).decode())
+        self._check(rc)
+        return outs
 
     def open_stream(self, max_seconds=600.0, commit=False, commit_cap=None):
         """commit: push() also returns the frames whose decode is already final (Stream); commit_cap: room for them per

@@ -12,8 +12,8 @@ the clip), and the bank is built for the shifted fmin.
 
 Differences a maintainer should know (all below the score's third decimal on the test signals): the CQT is the
 direct transform (librosa's multirate recursion approximates it), and the mel cosine is taken on 10^(S_dB/10) -- proportional to the mel power except where it sits more
-than 80 dB under the clip maximum (the cosine ignores the per-clip scale).  The grid search around this score needs
-FluidSynth and stays outside this package."""
+than 80 dB under the clip maximum (the cosine ignores the per-clip scale).  The grid search around this score is
+auto_matcher.py, with the ADSR soft-synth (synthesizer.py) in the middle."""
 import numpy as np
 
 from . import _lib, audio_io

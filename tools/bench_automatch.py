@@ -1,0 +1,215 @@
+"""Measures the ADSR soft-synth and one whole Auto-Match on the GPU and writes profiles/automatch.json (merged into what
+is there).  Not a pass/fail check: tests/test_gpu_synth.py asserts, this records.
+
+  python tools/bench_automatch.py                     # everything below
+  python tools/bench_automatch.py --synth-only        # the 27 x 30 s batch alone (the run to put under
+                                                      #   rocprofv3 --kernel-trace --stats -d DIR -- python ...)
+  python tools/bench_automatch.py --kernel-stats CSV  # no GPU: folds the synth_* rows of a rocprofv3 *_kernel_stats.csv in
+
+Recorded:
+  synth_batch_store_mode   the same batch on a handle created under AEGIS_SYNTH_STORE=1 (notes stored by the peak kernel and
+                       read by the mix), alternating with the default form: the measurement behind DESIGN.md 3.12's choice
+  synth_batch          wall time of one aegis_synth_adsr call for 27 candidates of about 30 s (host clock around the
+                       blocking call, after a warm-up call), its hipEvent kernel times, the float64 operation count of the
+                       batch (tools/synth_restated.op_count: what the kernels evaluate, the oscillator twice per note sample)
+                       and `kernel_f64_ops_per_s` = that count over the summed kernel time -- an achieved rate of counted
+                       operations, not a share of peak
+  restated_host        tools/synth_restated.py on this machine's host CPU for one such candidate
+  auto_match           one auto_match_parameters on a seeded 30 s clip, wall time and its breakdown by wrapped calls:
+                       event extraction, synthesis, WAV read-back, host tuning estimate, device mel + CQT, cosines
+  sine_golden_differing_samples   the sine fixture against the device (<= 1 step each, tests/test_gpu_synth.py)"""
+import argparse
+import csv
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+OUT = os.path.join(ROOT, "profiles", "automatch.json")
+
+
+def merge(update, path):
+    data = json.load(open(path)) if os.path.exists(path) else {}
+    data.update(update)
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(data, f, indent=1)
+    return data
+
+
+def candidates():
+    from spectrogram_midi_amd import smf
+    blobs = []
+    for i in range(27):
+        rng = np.random.default_rng(300 + i)
+        frames = int((30.0 - 0.2 * (i % 4)) * 44100 / 512)
+        ev = []
+        for k in range(75 + i % 12):
+            a = int(rng.integers(0, frames - 40))
+            ev.append({"start": a, "end": min(frames - 1, a + int(rng.integers(1, 120))), "note": int(rng.integers(36, 100)),
+                       "velocity": int(rng.integers(20, 127)), "track": "main" if k % 2 else "safe", "technique": None})
+        blobs.append(smf.render(ev, 44100, 512))
+    return blobs
+
+
+def synth_batch(repeats, with_store=True):
+    from spectrogram_midi_amd import _lib, synthesizer
+    from tools import synth_restated as R
+    h = _lib.Handle(device=0)
+    h_store = None
+    if with_store:
+        os.environ["AEGIS_SYNTH_STORE"] = "1"                      # read at create: the stored-notes form of the mix
+        h_store = _lib.Handle(device=0, scipy_tables=False)
+        del os.environ["AEGIS_SYNTH_STORE"]
+    synth = synthesizer.ADSRSynthesizer(44100, h)
+    p = dict(synthesizer.GUITAR_ADSR_PRESETS["electric_clean"])
+    blobs = candidates()
+    parsed = [h.synth_parse_smf(b) for b in blobs]
+    par = [h.adsr_params(**p)] * 27
+    notes, lengths = [n for n, _ in parsed], [l for _, l in parsed]
+    names = ("synth_note_peak", "synth_mix", "synth_master")
+    runs = {"recompute": (h, [], [])}
+    if with_store:
+        runs["store"] = (h_store, [], [])
+    outs = {}
+    for hh, _, _ in runs.values():
+        hh.synth_adsr(notes, lengths, par, 44100)                  # warm-up: code objects, buffer growth
+        hh.set_profiling(True)
+    for _ in range(repeats):                                       # the two forms alternate
+        for key, (hh, walls, kern) in runs.items():
+            t0 = time.perf_counter()
+            outs[key] = hh.synth_adsr(notes, lengths, par, 44100)
+            walls.append(time.perf_counter() - t0)
+            kern.append({k: hh.kernel_ms(k) for k in names})
+    for hh, _, _ in runs.values():
+        hh.set_profiling(False)
+    out = outs["recompute"]
+    assert all(np.array_equal(a, b) for a, b in zip(out, outs.get("store", out)))
+    t0 = time.perf_counter()
+    whole = synth.render_batch(blobs, [p] * 27)                    # with the MIDI reading and the Python layer
+    whole_s = time.perf_counter() - t0
+    assert all(np.array_equal(a, b) for a, b in zip(out, whole))
+    ops = sum(R.op_count(R.parse(b)[0], l, 44100, p["release_ms"], p["waveform"]) for b, l in zip(blobs, lengths))
+    note_samples = int(sum(int(44100 * (d + p["release_ms"] / 1000.0)) for n in notes for d in n["duration"]))
+
+    def summary(walls, kern):
+        best = min(range(repeats), key=lambda i: sum(kern[i].values()))
+        return {"wall_ms_each_call": [round(w * 1e3, 3) for w in walls], "kernel_ms_hip_events": kern[best],
+                "kernel_ms_sum": round(sum(kern[best].values()), 4),
+                "kernel_ms_sum_each_call": [round(sum(k.values()), 4) for k in kern]}
+    rec = summary(*runs["recompute"][1:])
+    ksum = rec["kernel_ms_sum"]
+    t0 = time.perf_counter()
+    ref = R.render(blobs[0], 44100, **p)
+    host_s = time.perf_counter() - t0
+    assert np.array_equal(ref, out[0])
+    h.close()
+    got = {
+        "synth_batch": dict({"candidates": 27, "notes": int(sum(len(n) for n in notes)), "samples": int(sum(len(a) for a in out)),
+                             "note_samples": note_samples, "preset": "electric_clean",
+                             "wall_ms_with_midi_reading": round(whole_s * 1e3, 3), "f64_ops_counted": int(ops),
+                             "kernel_f64_ops_per_s": ops / (ksum * 1e-3) if ksum > 0 else None}, **rec),
+        "restated_host": {"what": "tools/synth_restated.py, one candidate, this machine's host CPU", "seconds": round(host_s, 4),
+                          "notes": int(len(notes[0])), "samples": int(len(ref))},
+    }
+    if with_store:
+        h_store.close()
+        got["synth_batch_store_mode"] = dict(
+            {"what": "AEGIS_SYNTH_STORE=1: the peak kernel stores each note's samples (8 bytes per note sample), the mix reads "
+                     "them instead of recomputing; same samples out", "stored_bytes": note_samples * 8},
+            **summary(*runs["store"][1:]))
+    return got
+
+
+class Timers:
+    def __init__(self):
+        self.t = {}
+
+    def wrap(self, obj, name, key):
+        inner = getattr(obj, name)
+
+        def timed(*a, **k):
+            t0 = time.perf_counter()
+            try:
+                return inner(*a, **k)
+            finally:
+                self.t[key] = self.t.get(key, 0.0) + time.perf_counter() - t0
+        setattr(obj, name, timed)
+
+
+def auto_match(tmp):
+    from spectrogram_midi_amd import audio_io, auto_matcher, similarity
+    from spectrogram_midi_amd.engine import AegisEngine
+    from tools import signals
+    path = os.path.join(tmp, "automatch_original.wav")
+    audio_io.write_wav(path, signals.guitar_clip(30.0), 44100)
+    eng = AegisEngine()
+    raw = eng.audio_to_midi(path, None)
+    tm = Timers()
+    tm.wrap(eng, "extract_events", "event_extraction")
+    tm.wrap(auto_matcher, "synthesize_midi_adsr_batch", "synthesis")
+    tm.wrap(audio_io, "read_wav", "wav_read_back")
+    tm.wrap(similarity, "estimate_tuning", "host_tuning_estimate")
+    tm.wrap(eng.handle, "analyze_batch", "device_mel_cqt")
+    tm.wrap(eng.handle, "chroma_cqt", "device_mel_cqt")
+    tm.wrap(similarity, "_cosine", "cosines")
+    auto_matcher.auto_match_parameters(path, eng, raw)             # warm-up
+    tm.t.clear()
+    t0 = time.perf_counter()
+    res = auto_matcher.auto_match_parameters(path, eng, raw)
+    wall = time.perf_counter() - t0
+    eng.close()
+    os.remove(path)
+    parts = {k: round(v, 4) for k, v in tm.t.items()}
+    parts["other"] = round(wall - sum(tm.t.values()), 4)
+    return {"auto_match": {"clip_seconds": 30.0, "result": res, "wall_s": round(wall, 4), "breakdown_s": parts,
+                           "note": "wav_read_back covers both read_wav calls of a score (original file and synthesised bytes)"}}
+
+
+def sine_check():
+    from spectrogram_midi_amd import synthesizer
+    z = np.load(os.path.join(ROOT, "tests", "golden", "synth_golden.npz"))
+    p = dict(synthesizer.GUITAR_ADSR_PRESETS["nylon"], waveform="sine")
+    got = synthesizer.get_adsr_synthesizer(44100).midi_to_samples(z["sine.midi"].tobytes(), **p)
+    d = np.abs(got.astype(np.int32) - z["sine.pcm"].astype(np.int32))
+    return {"sine_golden_differing_samples": {"case": "sine", "differing": int((d > 0).sum()), "max": int(d.max()), "samples": int(len(d))}}
+
+
+def kernel_stats(path):
+    rows = {}
+    with open(path, newline="") as f:
+        for r in csv.DictReader(f):
+            name = r.get("Name") or r.get("KernelName") or ""
+            for known in ("synth_note_peak_kernel", "synth_mix_kernel", "synth_master_kernel"):
+                if known in name:
+                    rows[known] = {k: r[k] for k in r if k not in ("Name", "KernelName")}
+    return {"rocprofv3_kernel_stats": rows}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--synth-only", action="store_true")
+    ap.add_argument("--kernel-stats")
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--out", default=OUT)
+    ap.add_argument("--tmp", default=None)
+    a = ap.parse_args()
+    if a.kernel_stats:
+        print(json.dumps(merge(kernel_stats(a.kernel_stats), a.out)["rocprofv3_kernel_stats"], indent=1))
+        return
+    got = synth_batch(a.repeats, with_store=not a.synth_only)
+    if not a.synth_only:
+        import tempfile
+        got.update(sine_check())
+        with tempfile.TemporaryDirectory(dir=a.tmp) as tmp:
+            got.update(auto_match(tmp))
+        merge(got, a.out)
+    print(json.dumps(got, indent=1))
+
+
+if __name__ == "__main__":
+    main()
