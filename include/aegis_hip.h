@@ -435,7 +435,7 @@ int64_t aegis_get_param(const aegis_handle *h, const char *name);
 /* Copies an intermediate of the most recent pass (device -> host), for stage-level
  * parity tests.  name in {"dfn" f64[F*lag_stride] (pyin's difference function d[tau], the one pYIN intermediate the
  * frame stage leaves in HBM), "yin" f64[F*yin_stride] (the CMND rows: only on handles created under AEGIS_DEBUG_STAGES=1),
- * "logobs" f64[F*obs_stride], "logunv" f64[F], "states" i32[F], "melpow" f32[F*n_mels]}.
+ * "logobs" f64[F*obs_stride], "logunv" f64[F], "states" i32[F], "melpow" f32[F*n_mels], "rake_raw" u8[F]}.
  * Returns the element count available; copies min(count, cap).
  * "viterbi_stats" i64[3] (reading resets; "viterbi_stats_peek" does not): wave-steps of the band Viterbi since the last
  * reset, how many of them took the exact observed-sources-only path, and how many were voiced waves that skipped the step
@@ -450,6 +450,14 @@ int64_t aegis_get_param(const aegis_handle *h, const char *name);
  * "viterbi_cycles" i64[16 waves][8], "cqt_cycles" i64[16] -- in-kernel s_memtime
  * section counters read by tools/viterbi_cycles.py, cqt_cycles.py (reading resets them). */
 int64_t aegis_debug_fetch(aegis_handle *h, const char *name, void *dst, int64_t cap);
+
+/* The rake mask's column test on caller-supplied rows, for the tests that feed it adversarial spectra: mel_power is
+ * f32[n_rows][n_mels] (n_mels <= 128), clip_max the reference power_to_db(ref=np.max) would take, ratio the broadband
+ * threshold.  from_power != 0 runs the kernel that decides from mel power (what an analyze call without S_dB or column
+ * means runs), 0 the kernel that forms every dB value.  flags_out u8[n_rows]: the column flags before the run-length
+ * filter (what aegis_debug_fetch "rake_raw" u8[F] returns for the most recent pass). */
+int aegis_debug_rake_columns(aegis_handle *h, const float *mel_power, int64_t n_rows, int32_t n_mels, float clip_max,
+                             double ratio, int32_t from_power, uint8_t *flags_out);
 
 /* The pass plan an analyze call would make (CPU only: no device work, a device=-1 handle plans too).  Clips of
  * n_samples[i] samples, every stage, the handle's knobs and max_frames_per_pass, a device of n_cus compute units;

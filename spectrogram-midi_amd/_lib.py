@@ -70,7 +70,7 @@ EXPORTS = ("aegis_abi_version", "aegis_create", "aegis_destroy", "aegis_last_err
            "aegis_stream_open", "aegis_stream_push", "aegis_stream_close", "aegis_stream_free", "aegis_cqt", "aegis_cqt_device", "aegis_chroma_cqt",
            "aegis_extract_events", "aegis_render_smf", "aegis_events_last_error", "aegis_debug_plan",
            "aegis_analyze_pcm", "aegis_pcm_samples_for", "aegis_resample_taps", "aegis_stream_push_commit",
-           "aegis_synth_parse_smf", "aegis_synth_samples_for", "aegis_synth_adsr")
+           "aegis_synth_parse_smf", "aegis_synth_samples_for", "aegis_synth_adsr", "aegis_debug_rake_columns")
 
 _lib = None
 
@@ -169,7 +169,7 @@ def load():
 
 
 _TABLE_DTYPES = {"mel_dense": np.float32}
-_DEBUG_DTYPES = {"persistent_fallbacks": np.int64, "obs_cycles": np.int64, "cqt_cycles": np.int64, "viterbi_cycles": np.int64, "viterbi_spans": np.int64, "split_verify": np.int64, "split_flags": np.int64, "seg_lock": np.int64, "frame_cycles": np.int64, "states": np.int32, "melpow": np.float32}
+_DEBUG_DTYPES = {"persistent_fallbacks": np.int64, "obs_cycles": np.int64, "cqt_cycles": np.int64, "viterbi_cycles": np.int64, "viterbi_spans": np.int64, "split_verify": np.int64, "split_flags": np.int64, "seg_lock": np.int64, "frame_cycles": np.int64, "states": np.int32, "melpow": np.float32, "rake_raw": np.uint8}
 
 
 _live_handles = weakref.WeakSet()
@@ -271,6 +271,19 @@ class Handle:
         if got < 0:
             raise AegisError(got, self.lib.aegis_last_error(self._h).decode())
         return out
+
+    def rake_columns(self, mel_power, clip_max, ratio, from_power):
+        """The rake mask's column flags (before the run-length filter) of mel-power rows [n_rows, n_mels], by the kernel that
+        decides from mel power (from_power=True) or the one that forms every dB value (aegis_debug_rake_columns)."""
+        rows = np.ascontiguousarray(mel_power, dtype=np.float32)
+        out = np.empty(rows.shape[0], dtype=np.uint8)
+        fn = self.lib.aegis_debug_rake_columns      # (bound here: an older library, loaded for a comparison, lacks the entry)
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_double, C.c_int32, C.c_void_p]
+        fn.restype = C.c_int
+        rc = int(fn(self._h, rows.ctypes.data, rows.shape[0], rows.shape[1], float(clip_max), float(ratio), int(bool(from_power)), out.ctypes.data))
+        if rc != 0:
+            raise AegisError(rc, self.lib.aegis_last_error(self._h).decode())
+        return out.astype(bool)
 
     # aegis_debug_plan: entry kinds, option bits and the per-pass flag bits (include/aegis_hip.h AEGIS_PLAN_*)
     PLAN_ENTRIES = {"device": 0, "caller_stream": 1, "host_fed": 2}

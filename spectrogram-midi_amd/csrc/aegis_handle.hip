@@ -543,6 +543,7 @@ int64_t aegis_debug_fetch(aegis_handle *h, const char *name, void *dst, int64_t 
     else if (n == "logunv") { src = lw.logunv.p; count = F; }
     else if (n == "states") { src = lw.states.p; count = F; esz = 4; }
     else if (n == "melpow") { src = lw.melpow.p; count = F * h->tab.n_mels; esz = 4; }
+    else if (n == "rake_raw") { src = lw.rake_raw.p; count = F; esz = 1; }
     else if (n == "persistent_fallbacks") {
         if (dst && cap > 0) *static_cast<int64_t *>(dst) = h->persist.fallbacks;
         return 1;
@@ -586,6 +587,40 @@ int64_t aegis_debug_fetch(aegis_handle *h, const char *name, void *dst, int64_t 
         HIPCHK(h, hipMemcpy(dst, src, (size_t)std::min(count, cap) * esz, hipMemcpyDeviceToHost));
     }
     return count;
+    } catch (...) { return abi_fail(h); }
+}
+
+int aegis_debug_rake_columns(aegis_handle *h, const float *mel_power, int64_t n_rows, int32_t n_mels, float clip_max,
+                             double ratio, int32_t from_power, uint8_t *flags_out) {
+    try {
+    if (!h) return AEGIS_ERR_INVALID;
+    if (n_rows < 0 || n_mels <= 0 || n_mels > 128 || (n_rows > 0 && (!mel_power || !flags_out))) { h->err = "bad argument"; return AEGIS_ERR_INVALID; }
+    if (n_rows == 0) return AEGIS_OK;
+    DEVICE_ONLY(h);
+    std::lock_guard<std::mutex> lock(h->mu);
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc;
+    const size_t bytes = (size_t)n_rows * n_mels * 4;
+    if ((rc = ensure(h, h->io_sdb, bytes)) != AEGIS_OK) return rc;
+    if ((rc = ensure(h, h->rk_raw, n_rows)) != AEGIS_OK) return rc;
+    if ((rc = ensure(h, h->io_rake, 32)) != AEGIS_OK) return rc;        // frame_off[2] | clipmax
+    hipStream_t s = h->stream;
+    struct { int64_t frame_off[2]; uint32_t clipmax; } geo = {{0, n_rows}, 0};
+    std::memcpy(&geo.clipmax, &clip_max, 4);
+    HIPCHK(h, hipMemcpyAsync(h->io_sdb.p, mel_power, bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(h->io_rake.p, &geo, sizeof geo, hipMemcpyHostToDevice, s));
+    PassParams p{};
+    p.n_mels = n_mels; p.n_clips = 1; p.n_frames = n_rows; p.stages = AEGIS_STAGE_MEL;
+    p.frame_off = static_cast<const int64_t *>(h->io_rake.p);
+    p.clipmax = reinterpret_cast<uint32_t *>(static_cast<char *>(h->io_rake.p) + 16);
+    p.melpow = static_cast<float *>(h->io_sdb.p);
+    p.rake_raw = static_cast<uint8_t *>(h->rk_raw.p);
+    p.rake_ratio = ratio;
+    launch_rake_columns(p, from_power != 0, s);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(flags_out, h->rk_raw.p, n_rows, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    return AEGIS_OK;
     } catch (...) { return abi_fail(h); }
 }
 

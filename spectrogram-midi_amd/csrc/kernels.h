@@ -185,6 +185,9 @@ void launch_decode(const PassParams &p, const DevTables &t, hipStream_t s);
 // first_bad (device, preset to ~0): smallest index of a sample of pcm[0..n) that is NaN or infinite
 void launch_finite_check(const float *pcm, int64_t n, unsigned long long *first_bad, hipStream_t s);
 void launch_finalize_mel(const PassParams &p, const DevTables &t, hipStream_t s);
+// the column flags (rake_raw) alone: rake_pow_kernel from mel power, or db_rake_kernel through every dB value (which also
+// writes the image and its column means where p asks for them); launch_finalize_mel picks by those outputs
+void launch_rake_columns(const PassParams &p, bool from_power, hipStream_t s);
 void launch_rake_from_db(const float *sdb, int n_mels, int64_t F, double ratio, int min_frames, int max_frames,
                          uint8_t *raw, uint8_t *out, hipStream_t s);
 void launch_stream_advance(StreamCtl *ctl, const float *staging, int n_push, float *pcm, int hop, hipStream_t s);

@@ -12,6 +12,7 @@
 // NumPy rounds; fused operations are written as fma() where they are wanted.
 #include "kernels.h"
 #include "fft8.h"
+#include "rake_decide.h"
 
 #include <algorithm>
 #include <cfloat>
@@ -1268,15 +1269,97 @@ __global__ __launch_bounds__(256) void db_rake_kernel(PassParams p) {
 }
 
 // ------------------------------------------------------------------------------------------
+// Kernel 5b': the same column flags from mel power alone, for the calls that want neither the dB image nor its column
+// means (rake_decide.h has the construction and its error bound).  A wave owns 64 consecutive frames and never meets the
+// other waves of its workgroup.
+//   (a) row by row, all lanes, the next batch of rows loading meanwhile: row maximum, float32 compares against the three
+//       bounds, ballots.  The bands active for certain are counted; the few values that need the exact V(s) go to the
+//       frame's list in LDS, top set first.
+//   (b) lane r takes frame r: one log10 for the reference, one for s_max, one per list entry -- the loop runs while any
+//       lane has an entry left, so a double log10 is issued about three times per 64 frames, not 128 times per frame.
+//       A frame whose list overflowed (or whose maximum is infinite) walks its whole row as db_rake_kernel does.
+// ------------------------------------------------------------------------------------------
+constexpr int kRakeRows = 5;       // rows per batch of loads; the next batch is in flight while one is classified
+struct RakeLane { float smax; int sure, ntop, n; };      // what lane r keeps of frame r (n < 0: walk the row)
+// rows r0 .. r0 + kRakeRows - 1 of the wave's 64 (rows past its last repeat that one and are not looked at)
+__device__ __forceinline__ void rake_rows_load(float (&a)[kRakeRows], float (&b)[kRakeRows], const float *__restrict__ base,
+                                               int r0, int nrows, int nm, int lane) {
+#pragma unroll
+    for (int i = 0; i < kRakeRows; ++i) {
+        const float *row = base + (int64_t)min(r0 + i, nrows - 1) * nm;
+        a[i] = row[min(lane, nm - 1)];          // unconditional: a load under a test ends at a join that waits for every load in flight
+        b[i] = row[min(lane + 64, nm - 1)];     // (the bands that are not there repeat the last one and are masked in the ballots)
+    }
+}
+__device__ __forceinline__ void rake_rows_classify(const float (&a)[kRakeRows], const float (&b)[kRakeRows], int r0, int nrows, int nm,
+                                                   int lane, float (*lst)[64], RakeLane &mine) {
+    const bool va = lane < nm, vb = lane + 64 < nm;
+#pragma unroll
+    for (int i = 0; i < kRakeRows; ++i) {
+        const int r = r0 + i;
+        if (r >= nrows) break;
+        const float sa = rake_floor(a[i]), sb = rake_floor(b[i]);
+        // s >= 1e-10 > 0: the bit patterns order as the values do, and 0 stands in for the bands that are not there
+        const float smax = __uint_as_float(wave_umax(max(va ? __float_as_uint(sa) : 0u, vb ? __float_as_uint(sb) : 0u)));
+        const RakeWindow w = rake_window(smax);
+        const unsigned long long sure_a = __ballot(va && rake_sure_active(sa, w)), sure_b = __ballot(vb && rake_sure_active(sb, w));
+        const unsigned long long top_a = __ballot(va && rake_top_listed(sa, w)), top_b = __ballot(vb && rake_top_listed(sb, w));
+        const unsigned long long mid_a = __ballot(va && rake_mid_listed(sa, w)), mid_b = __ballot(vb && rake_mid_listed(sb, w));
+        const int sure = __popcll(sure_a) + __popcll(sure_b);
+        const int ntop_a = __popcll(top_a), ntop = ntop_a + __popcll(top_b);
+        const int nmid_a = __popcll(mid_a), n = ntop + nmid_a + __popcll(mid_b);
+        const bool walk = !w.usable || n > kRakeListCap;
+        if (n != 0 && !walk) {
+            const unsigned long long below = (1ull << lane) - 1ull;
+            if ((top_a >> lane) & 1ull) lst[__popcll(top_a & below)][r] = sa;
+            if ((top_b >> lane) & 1ull) lst[ntop_a + __popcll(top_b & below)][r] = sb;
+            if ((mid_a >> lane) & 1ull) lst[ntop + __popcll(mid_a & below)][r] = sa;
+            if ((mid_b >> lane) & 1ull) lst[ntop + nmid_a + __popcll(mid_b & below)][r] = sb;
+        }
+        if (lane == r) { mine.smax = smax; mine.sure = sure; mine.ntop = ntop; mine.n = walk ? -1 : n; }
+    }
+}
+__global__ __launch_bounds__(256) void rake_pow_kernel(PassParams p) {
+    __shared__ float lst[4][kRakeListCap][64];      // [wave][entry][frame]: phase (b) reads along frames
+    const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int nm = p.n_mels;                        // <= 128 (tables.cpp): bands lane and lane + 64
+    const int64_t f0 = ((int64_t)blockIdx.x * 4 + wid) * 64;
+    if (f0 >= p.n_frames) return;
+    const int nrows = (int)min((int64_t)64, p.n_frames - f0);
+    const float *__restrict__ base = p.melpow + f0 * nm;
+    float a0[kRakeRows], b0[kRakeRows], a1[kRakeRows], b1[kRakeRows];
+    rake_rows_load(a0, b0, base, 0, nrows, nm, lane);
+    // the frame's clip and reference level, while the first rows are on their way: one search for the wave when its frames
+    // lie in one clip (scalar loads), one per lane where a clip ends inside it
+    const int64_t f = f0 + min(lane, nrows - 1);
+    const int c_first = find_clip(p.frame_off, p.n_clips, f0), c_last = find_clip(p.frame_off, p.n_clips, f0 + nrows - 1);
+    const int c = c_first == c_last ? c_first : find_clip(p.frame_off, p.n_clips, f);
+    const float refdb = rake_refdb(rake_floor(__uint_as_float(p.clipmax[c])));
+    RakeLane mine = {0.0f, 0, 0, 0};
+    for (int r0 = 0; r0 < nrows; r0 += 2 * kRakeRows) {
+        rake_rows_load(a1, b1, base, r0 + kRakeRows, nrows, nm, lane);
+        rake_rows_classify(a0, b0, r0, nrows, nm, lane, lst[wid], mine);
+        rake_rows_load(a0, b0, base, r0 + 2 * kRakeRows, nrows, nm, lane);
+        rake_rows_classify(a1, b1, r0 + kRakeRows, nrows, nm, lane, lst[wid], mine);
+    }
+    if (lane >= nrows) return;
+    // the wave's own LDS writes are complete before its reads: same wave, program order (no other wave touches lst[wid])
+    int active;
+    if (mine.n < 0) active = rake_column_full(base + (int64_t)lane * nm, nm, refdb);
+    else active = rake_decide(mine.smax, mine.sure, mine.ntop, mine.n, &lst[wid][0][lane], 64, refdb);
+    p.rake_raw[f] = rake_candidate(active, nm, p.rake_ratio) ? 1 : 0;
+}
+
+// ------------------------------------------------------------------------------------------
 // Kernel 5c: run-length filter of vision.py:27-36.  A candidate frame survives when its run
 // is closed before the end of the clip and min_frames <= length <= max_frames.
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void rake_runs_kernel(PassParams p) {
     const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (f >= p.n_frames || p.out_rake == nullptr) return;
+    const int c = find_clip(p.frame_off, p.n_clips, f);
     uint8_t keep = 0;
     if (p.rake_raw[f]) {
-        const int c = find_clip(p.frame_off, p.n_clips, f);
         const int64_t lo = p.frame_off[c], hi = p.frame_off[c + 1];
         const int lim = p.rake_max_frames + 1;
         int64_t s = f, e = f + 1;
@@ -1287,10 +1370,7 @@ __global__ __launch_bounds__(256) void rake_runs_kernel(PassParams p) {
         const bool closed = e < hi;   // a run still open at the end of the clip is dropped
         if (steps <= lim && closed && len >= p.rake_min_frames && len <= p.rake_max_frames) keep = 1;
     }
-    {
-        const int c = find_clip(p.frame_off, p.n_clips, f);
-        p.out_rake[out_index(p, c, f - p.frame_off[c])] = keep;
-    }
+    p.out_rake[out_index(p, c, f - p.frame_off[c])] = keep;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1459,11 +1539,17 @@ void launch_decode(const PassParams &p, const DevTables &t, hipStream_t s) {
     const unsigned g256 = (unsigned)((p.n_frames + 255) / 256);
     hipLaunchKernelGGL(decode_kernel, dim3(g256), dim3(256), 0, s, p, t);
 }
+void launch_rake_columns(const PassParams &p, bool from_power, hipStream_t s) {
+    if (p.n_frames == 0) return;
+    if (from_power) hipLaunchKernelGGL(rake_pow_kernel, dim3((unsigned)((p.n_frames + 255) / 256)), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(db_rake_kernel, dim3((unsigned)((p.n_frames + 63) / 64)), dim3(256), 0, s, p);
+}
 void launch_finalize_mel(const PassParams &p, const DevTables &, hipStream_t s) {
     if (p.n_frames == 0) return;
     const unsigned g256 = (unsigned)((p.n_frames + 255) / 256);
     if (p.stages & 0x3u) {
-        hipLaunchKernelGGL(db_rake_kernel, dim3((unsigned)((p.n_frames + 63) / 64)), dim3(256), 0, s, p);
+        // the dB values themselves are wanted only for the image and its column means; the flags alone come from mel power
+        launch_rake_columns(p, p.out_sdb == nullptr && p.out_colmean == nullptr, s);
         if (p.stages & 0x2u) hipLaunchKernelGGL(rake_runs_kernel, dim3(g256), dim3(256), 0, s, p);
     }
 }

@@ -4,7 +4,7 @@ python3 tools/summarize_sq.py <steps_total> <out.json> <csv> [<csv> ...]"""
 import collections, csv, json, sys
 
 NAMES = {"frame_yin_kernel": "frame", "pyin_obs_kernel": "pyin_obs", "viterbi_band_kernel": "viterbi", "viterbi_band_dense_kernel": "viterbi",
-         "viterbi_band_split_kernel": "viterbi", "viterbi_kernel": "viterbi", "db_rake_kernel": "db_rake"}
+         "viterbi_band_split_kernel": "viterbi", "viterbi_kernel": "viterbi", "db_rake_kernel": "db_rake", "rake_pow_kernel": "db_rake"}
 
 
 def main(n_steps, out, paths):
