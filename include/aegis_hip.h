@@ -429,7 +429,16 @@ int aegis_set_table(aegis_handle *h, const char *name, const double *data, int64
  * of the last split pass: "split_rounds" (rounds of second speculation that had work), "split_viterbi_us" (measured time of its Viterbi
  * kernels, automatic passes only), "split_cooldown" (calls left that plan sequentially after split passes that did not pay),
  * "last_hybrid_step" (the step up to which the sequential kernel ran every clip under the frame stage before the rest was
- * cut into segments; 0: not a hybrid split pass) -- the time-split Viterbi, csrc/viterbi.hip. */
+ * cut into segments; 0: not a hybrid split pass) -- the time-split Viterbi, csrc/viterbi.hip.
+ * Which form of each kernel the handle's geometry selects (read-only, answered by the host rules the launches call, also
+ * by a device = -1 handle): "cmnd_in_frame" (1: the frame kernel's epilogue forms the CMND; 0: pyin_obs walks it -- lag
+ * ranges beyond 768, AEGIS_CMND_IN_FRAME=0, AEGIS_DEBUG_STAGES=1), "troughs_in_frame" (1: it also finds the troughs),
+ * "viterbi_kernel" (0: generic kernel, transition table in LDS; 1: generic kernel, table read from global memory; 25 / 50:
+ * the band kernels of that half width; AEGIS_ERR_UNSUPPORTED if no kernel fits, which no geometry aegis_create
+ * accepts produces: 2 n_pitch_bins <= 1024 threads and the generic kernel's LDS without the table stays under 160 KB),
+ * "frame_fpw" (frames per frame-kernel workgroup of a launch of >= 4096 frames; smaller launches take 2), "obs_waves"
+ * (waves per pyin_obs workgroup of such a launch outside a dense pass), "split_applies" (1: the time-split Viterbi can
+ * take this geometry). */
 int64_t aegis_get_param(const aegis_handle *h, const char *name);
 
 /* Copies an intermediate of the most recent pass (device -> host), for stage-level

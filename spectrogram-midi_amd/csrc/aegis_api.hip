@@ -50,6 +50,14 @@ const OutField aegis::kOutFields[8] = {
     {AEGIS_STAGE_MEL, 4, true, offsetof(aegis_outputs, S_dB), &aegis_handle::io_sdb, &aegis_stream::o_sdb},
 };
 
+// The tables the Viterbi launch rules look at (whether a packed transition table exists).  A host-only handle has uploaded
+// none: it stands in the host copy of the packed table the device would hold, so the rules answer alike.
+DevTables aegis::rule_tables(const aegis_handle *h) {
+    DevTables dt = h->dt;
+    if (h->device < 0 && !h->tab.log_trans_pack.empty()) dt.lt_pack = h->tab.log_trans_pack.data();
+    return dt;
+}
+
 // What the planner needs to know about a call.  masked: whether a CU-masked stream set exists for n clips (the executor
 // creates them through split_streams; aegis_debug_plan only asks whether they would be laid out).
 PlanInput aegis::plan_input(aegis_handle *h, const int64_t *sample_offsets, int32_t n_clips, uint32_t stages, bool feed,
@@ -61,8 +69,7 @@ PlanInput aegis::plan_input(aegis_handle *h, const int64_t *sample_offsets, int3
     in.n_cus = n_cus; in.hop = t.hop; in.half_width = t.half_width;
     in.py = stages & AEGIS_STAGE_PYIN;
     in.feed = feed; in.caller_stream = caller_stream; in.sync = sync;
-    DevTables dt = h->dt;      // (a host-only handle: the packed table the device would hold)
-    if (h->device < 0 && !t.log_trans_pack.empty()) dt.lt_pack = t.log_trans_pack.data();
+    const DevTables dt = rule_tables(h);
     in.band_applies = viterbi_band_applies(base_params(t), dt);
     in.split_applies = viterbi_split_applies(base_params(t), dt);
     in.masked_streams = std::move(masked);

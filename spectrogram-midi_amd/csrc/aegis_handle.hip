@@ -157,6 +157,10 @@ int aegis_create(const aegis_config *cfg, aegis_handle **out) {
     h->lag_stride = std::max<int32_t>(h->lag_stride, (trough_row_doubles_host(h->tab.n_lags) + 7) & ~7);
     h->yin_stride = (h->tab.n_lags + 7) & ~7;
     h->obs_stride = (h->tab.n_bins + 7) & ~7;
+    // (read before a host-only handle returns: its launch-rule parameters answer what a device handle would run)
+    if (const char *e = std::getenv("AEGIS_DEBUG_STAGES")) h->debug_stages = (e[0] == '1');
+    if (const char *e = std::getenv("AEGIS_CMND_IN_FRAME")) h->cmnd_off = (e[0] == '0');
+    if (const char *e = std::getenv("AEGIS_TROUGHS_IN_FRAME")) h->troughs_off = (e[0] == '0');
     if (c.device == -1) { *out = h; return AEGIS_OK; }   // host tables only
 
     int ndev = 0;
@@ -174,9 +178,6 @@ int aegis_create(const aegis_config *cfg, aegis_handle **out) {
     CRTHIP(hipStreamCreateWithFlags(&h->stream4, hipStreamNonBlocking));
     CRTHIP(hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking));
     CRTHIP(hipStreamCreateWithFlags(&h->stream3, hipStreamNonBlocking));
-    if (const char *e = std::getenv("AEGIS_DEBUG_STAGES")) h->debug_stages = (e[0] == '1');
-    if (const char *e = std::getenv("AEGIS_CMND_IN_FRAME")) h->cmnd_off = (e[0] == '0');
-    if (const char *e = std::getenv("AEGIS_TROUGHS_IN_FRAME")) h->troughs_off = (e[0] == '0');
     if (const char *e = std::getenv("AEGIS_SYNTH_STORE")) h->synth_store = (e[0] == '1');      // aegis_synth_adsr: stored notes instead of recomputed ones
     if (const char *e = std::getenv("AEGIS_TEST_DROP_CHUNK_SIGNAL")) h->test_drop_signal = std::atoi(e);
     CRTHIP(hipDeviceGetAttribute(&h->n_cus, hipDeviceAttributeMultiprocessorCount, c.device));
@@ -408,6 +409,13 @@ int64_t aegis_get_param(const aegis_handle *h, const char *name) {
     if (n == "last_hybrid_step") return lp ? lp->hyb_S : 0;
     if (n == "last_persistent") return lp ? lp->persistent : 0;
     if (n == "pyin_init") return t.pyin_init;
+    // the launch rules at this geometry, from the host functions the launches themselves call
+    if (n == "cmnd_in_frame") return cmnd_in_frame(h);
+    if (n == "troughs_in_frame") return troughs_in_frame(h);
+    if (n == "frame_fpw") return frame_batch_fpw(t.max_period);
+    if (n == "obs_waves") { PassParams q = base_params(t); q.n_sel = 4096; return pyin_obs_waves(q); }
+    if (n == "viterbi_kernel") { const int k = viterbi_kernel_choice(base_params(t), rule_tables(h)); return k < 0 ? AEGIS_ERR_UNSUPPORTED : k; }
+    if (n == "split_applies") return viterbi_split_applies(base_params(t), rule_tables(h)) ? 1 : 0;
     return AEGIS_ERR_INVALID;
     } catch (...) { return abi_fail(const_cast<aegis_handle *>(h)); }
 }

@@ -184,6 +184,7 @@ RakeBounds rake_frame_bounds(const Tables &t);    // a rake lasts 10 .. 30 ms: i
 PassParams base_params(const Tables &t);          // (rake_frame_bounds included)
 int cmnd_in_frame(const aegis_handle *h);
 int troughs_in_frame(const aegis_handle *h);
+DevTables rule_tables(const aegis_handle *h);     // h->dt as the Viterbi launch rules read it, also on a host-only handle
 PlanInput plan_input(aegis_handle *h, const int64_t *sample_offsets, int32_t n_clips, uint32_t stages, bool feed,
                      bool caller_stream, int32_t sync, int n_cus, std::function<bool(int)> masked);
 

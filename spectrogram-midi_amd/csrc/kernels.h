@@ -163,8 +163,10 @@ struct PassParams {
 
 void launch_frame(const PassParams &p, const DevTables &t, hipStream_t s);
 bool frame_cmnd_supported(int max_period);
+int frame_batch_fpw(int max_period);        // frames per frame_yin workgroup of a launch that selects >= 4096 frames (smaller launches: 2)
 int trough_row_doubles_host(int n_lags);    // doubles of a dfn row that holds a frame's trough list (PassParams::troughs)   // the frame kernel's LDS holds the CMND rows of a workgroup's frames (PassParams::cmnd_in_frame)
 void launch_pyin_obs(const PassParams &p, const DevTables &t, hipStream_t s);
+int pyin_obs_waves(const PassParams &p);    // waves per pyin_obs workgroup of a launch of p.n_sel frames (p.dense: at most four)
 hipError_t launch_viterbi(const PassParams &p, const DevTables &t, const double *host_lt_band, hipStream_t s);
 // time-split pass: speculative runs (grid = segments), lock-on runs (grid = segments that have a predecessor, listed in
 // lock_order), stitch + back-trace, verification; seg_order (device) lists 0..n_seg-1
@@ -179,6 +181,9 @@ hipError_t launch_viterbi_split_spec(const PassParams &p, const DevTables &t, co
 bool viterbi_split_applies(const PassParams &p, const DevTables &t);
 hipError_t viterbi_verify_fetch(long long *dst, bool reset);
 int viterbi_tube_record_ints();   // counters of the time-split verification kernel (viterbi.hip g_verify_dbg)
+// which kernel launch_viterbi takes: 25 / 50 band kernels, 0 generic with the transition table in LDS, 1 generic reading it
+// from global memory, -1 no kernel fits (launch_viterbi then fails)
+int viterbi_kernel_choice(const PassParams &p, const DevTables &t);
 bool viterbi_band_applies(const PassParams &p, const DevTables &t);   // the band-specialised kernels (the ones that can wait for chunk flags) take this geometry
 void launch_chunk_signal(uint32_t *flag, uint32_t gen, hipStream_t s);
 void launch_decode(const PassParams &p, const DevTables &t, hipStream_t s);

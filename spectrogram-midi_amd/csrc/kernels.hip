@@ -1249,10 +1249,10 @@ __global__ __launch_bounds__(256) void db_rake_kernel(PassParams p) {
         const float lo_sum = a;
         float hs = row[mid];
         for (int m = mid + 1; m < nm; ++m) hs = hs + row[m];
-        for (int m = mid; m < nm; ++m) a = a + row[m];
+        for (int m = max(mid, 1); m < nm; ++m) a = a + row[m];       // (one mel band: row[0] is the whole sum already)
         const int64_t fo = out_index(p, c, fb + tid - p.frame_off[c]);
         p.out_colmean[fo] = a / (float)nm;
-        p.out_colmean[p.out_total + fo] = lo_sum / (float)mid;
+        p.out_colmean[p.out_total + fo] = mid > 0 ? lo_sum / (float)mid : NAN;      // np.mean of no rows
         p.out_colmean[2 * p.out_total + fo] = hs / (float)(nm - mid);
     }
     if (p.out_sdb != nullptr) {
@@ -1477,7 +1477,7 @@ hipError_t viterbi_configure() {
 }
 
 // frames per workgroup of a batch launch: as many as keep two workgroups on a CU (16 at the reference's rates)
-static int frame_batch_fpw(int max_period) {
+int frame_batch_fpw(int max_period) {
     const int stride = frame_en_stride(max_period);
     int fpw = kFramesPerWg;
     while (fpw > 2 && kFrameLdsFixed + (size_t)fpw * stride * 4 > 80 * 1024) fpw -= 2;
@@ -1504,17 +1504,28 @@ void launch_frame(const PassParams &p, const DevTables &t, hipStream_t s) {
     lds = std::max(lds, std::min<size_t>(lds_min, 160 * 1024));
     hipLaunchKernelGGL(frame_yin_kernel, dim3((unsigned)((p.n_sel + fpw - 1) / fpw)), dim3(256), lds, s, p, t, fpw, stride);
 }
-void launch_pyin_obs(const PassParams &p, const DevTables &t, hipStream_t s) {
-    if (p.n_sel == 0) return;
+// LDS doubles of a pyin_obs workgroup: the tables every wave shares (TN) and one wave's rows (YN + UN)
+struct ObsLds { int TN, per_wave; };
+static ObsLds pyin_obs_lds(const PassParams &p) {
     const int KM = p.n_lags / 2 + 2, YN = (std::max(p.n_lags, p.n_bins) + 1) & ~1, DN = (p.max_period + 1 + 32 + 1) & ~1;
     const int UN = (std::max(DN, 2 * KM + (4 * KM + 7) / 8) + 1) & ~1, TN = (2 * (KM + 1) + 101 + 1) & ~1;
-    // eight waves share one copy of the tables (two such workgroups per CU); small launches (streaming pushes) get a wave
-    // per frame and one frame per wave
-    // (a dense pass -- PassParams::dense -- takes four-wave workgroups: one wave per SIMD fits beside a Viterbi workgroup)
+    return {TN, YN + UN};
+}
+// eight waves share one copy of the tables (two such workgroups per CU); small launches (streaming pushes) get a wave
+// per frame and one frame per wave
+// (a dense pass -- PassParams::dense -- takes four-wave workgroups: one wave per SIMD fits beside a Viterbi workgroup)
+int pyin_obs_waves(const PassParams &p) {
+    const ObsLds l = pyin_obs_lds(p);
     int waves = (int)std::min<int64_t>(p.dense ? 4 : 8, p.n_sel);
-    while (waves > 1 && (size_t)(TN + waves * (YN + UN)) * 8 + 1024 > 80 * 1024) --waves;
+    while (waves > 1 && (size_t)(l.TN + waves * l.per_wave) * 8 + 1024 > 80 * 1024) --waves;
+    return waves;
+}
+void launch_pyin_obs(const PassParams &p, const DevTables &t, hipStream_t s) {
+    if (p.n_sel == 0) return;
+    const ObsLds l = pyin_obs_lds(p);
+    const int waves = pyin_obs_waves(p);
     const int fpw = p.n_sel >= 4096 ? (p.dense ? 8 : 4) : 1;     // (dense: half the waves per workgroup, twice the frames per wave)
-    const size_t lds = (size_t)(TN + waves * (YN + UN)) * 8;
+    const size_t lds = (size_t)(l.TN + waves * l.per_wave) * 8;
     const int64_t per_wg = (int64_t)waves * fpw;
     hipLaunchKernelGGL(pyin_obs_kernel, dim3((unsigned)((p.n_sel + per_wg - 1) / per_wg)), dim3(64 * waves), lds, s, p, t, fpw);
 }

@@ -1132,52 +1132,57 @@ static bool band_geometry(const PassParams &p) {
     const int BP = (p.n_bins + 63) & ~63;
     return p.n_cls == p.width && 2 * BP <= 1024 && p.n_bins >= 4 * p.half_width + 128;
 }
-bool viterbi_band_applies(const PassParams &p, const DevTables &t) {      // the two branches of launch_viterbi below
-    if (!band_geometry(p)) return false;
-    if (p.half_width == 25) return viterbi_band_lds<25>(p, true) <= 160 * 1024;
-    if (p.half_width == 50) return t.lt_pack != nullptr && viterbi_band_lds<50>(p, true) <= 160 * 1024;
-    return false;
+// The kernel launch_viterbi takes for a geometry (aegis_get_param "viterbi_kernel"): 25 / 50 the band kernels, 0 the
+// generic kernel with the transition table in LDS, 1 the generic kernel reading it from global memory, -1 none.
+int viterbi_kernel_choice(const PassParams &p, const DevTables &t) {
+    if (band_geometry(p)) {
+        // band-specialised kernels for the two hop/sr ratios the reference uses (44.1k and 22.05k at hop 512)
+        if (p.half_width == 25 && viterbi_band_lds<25>(p, true) <= 160 * 1024) return 25;
+        if (p.half_width == 50 && t.lt_pack != nullptr && viterbi_band_lds<50>(p, true) <= 160 * 1024) return 50;
+    }
+    const bool with_lt = viterbi_lds_bytes(p, true) <= 160 * 1024;
+    if (((2 * p.n_bins + 63) & ~63) > 1024 || viterbi_lds_bytes(p, with_lt) > 160 * 1024) return -1;
+    return with_lt ? 0 : 1;
 }
+bool viterbi_band_applies(const PassParams &p, const DevTables &t) { return viterbi_kernel_choice(p, t) >= 25; }
 
 hipError_t launch_viterbi(const PassParams &p, const DevTables &t, const double *host_lt_band, hipStream_t s) {
     if (p.n_clips == 0) return hipSuccess;
     const int S = 2 * p.n_bins;
     const int BP = (p.n_bins + 63) & ~63;
-    if (band_geometry(p)) {
-        // band-specialised kernels for the two hop/sr ratios the reference uses (44.1k and 22.05k at hop 512)
-        if (p.half_width == 25 && viterbi_band_lds<25>(p, true) <= 160 * 1024) {
-            BandLT<25> blt;
-            for (int q = 0; q < 4; ++q) {
-                std::memcpy(blt.v[q], host_lt_band + ((size_t)q * p.n_cls + 25) * p.width, sizeof(blt.v[q]));
-                blt.lmax[q] = *std::max_element(host_lt_band + (size_t)q * p.n_cls * p.width,
-                                                host_lt_band + (size_t)(q + 1) * p.n_cls * p.width);
-            }
-            blt.lmax_all = *std::max_element(blt.lmax, blt.lmax + 4);
-            if (p.dense)
-                hipLaunchKernelGGL((viterbi_band_dense_kernel<25, true>), dim3((unsigned)p.n_clips), dim3(2 * BP),
-                                   viterbi_launch_lds(viterbi_band_lds<25>(p, true), p.n_clips), s, p, t, blt);
-            else
-                hipLaunchKernelGGL((viterbi_band_kernel<25, true>), dim3((unsigned)p.n_clips), dim3(2 * BP),
-                                   viterbi_launch_lds(viterbi_band_lds<25>(p, true), p.n_clips), s, p, t, blt);
-            return hipGetLastError();
+    const int kind = viterbi_kernel_choice(p, t);
+    if (kind == 25) {
+        BandLT<25> blt;
+        for (int q = 0; q < 4; ++q) {
+            std::memcpy(blt.v[q], host_lt_band + ((size_t)q * p.n_cls + 25) * p.width, sizeof(blt.v[q]));
+            blt.lmax[q] = *std::max_element(host_lt_band + (size_t)q * p.n_cls * p.width,
+                                            host_lt_band + (size_t)(q + 1) * p.n_cls * p.width);
         }
-        if (p.half_width == 50 && t.lt_pack != nullptr && viterbi_band_lds<50>(p, true) <= 160 * 1024) {
-            BandLT<50> blt;
-            for (int q = 0; q < 4; ++q) {
-                std::memcpy(blt.v[q], host_lt_band + ((size_t)q * p.n_cls + 50) * p.width, sizeof(blt.v[q]));
-                blt.lmax[q] = *std::max_element(host_lt_band + (size_t)q * p.n_cls * p.width,
-                                                host_lt_band + (size_t)(q + 1) * p.n_cls * p.width);
-            }
-            blt.lmax_all = *std::max_element(blt.lmax, blt.lmax + 4);
-            hipLaunchKernelGGL((viterbi_band_kernel<50, true>), dim3((unsigned)p.n_clips), dim3(2 * BP),
-                               viterbi_launch_lds(viterbi_band_lds<50>(p, true), p.n_clips), s, p, t, blt);
-            return hipGetLastError();
-        }
+        blt.lmax_all = *std::max_element(blt.lmax, blt.lmax + 4);
+        if (p.dense)
+            hipLaunchKernelGGL((viterbi_band_dense_kernel<25, true>), dim3((unsigned)p.n_clips), dim3(2 * BP),
+                               viterbi_launch_lds(viterbi_band_lds<25>(p, true), p.n_clips), s, p, t, blt);
+        else
+            hipLaunchKernelGGL((viterbi_band_kernel<25, true>), dim3((unsigned)p.n_clips), dim3(2 * BP),
+                               viterbi_launch_lds(viterbi_band_lds<25>(p, true), p.n_clips), s, p, t, blt);
+        return hipGetLastError();
     }
+    if (kind == 50) {
+        BandLT<50> blt;
+        for (int q = 0; q < 4; ++q) {
+            std::memcpy(blt.v[q], host_lt_band + ((size_t)q * p.n_cls + 50) * p.width, sizeof(blt.v[q]));
+            blt.lmax[q] = *std::max_element(host_lt_band + (size_t)q * p.n_cls * p.width,
+                                            host_lt_band + (size_t)(q + 1) * p.n_cls * p.width);
+        }
+        blt.lmax_all = *std::max_element(blt.lmax, blt.lmax + 4);
+        hipLaunchKernelGGL((viterbi_band_kernel<50, true>), dim3((unsigned)p.n_clips), dim3(2 * BP),
+                           viterbi_launch_lds(viterbi_band_lds<50>(p, true), p.n_clips), s, p, t, blt);
+        return hipGetLastError();
+    }
+    if (kind < 0) return hipErrorInvalidValue;
     const int nthr = (S + 63) & ~63;
-    const bool with_lt = viterbi_lds_bytes(p, true) <= 160 * 1024;
+    const bool with_lt = kind == 0;
     const size_t lds = viterbi_lds_bytes(p, with_lt);
-    if (nthr > 1024 || lds > 160 * 1024) return hipErrorInvalidValue;
     hipLaunchKernelGGL(viterbi_kernel, dim3((unsigned)p.n_clips), dim3(nthr), lds, s, p, t, with_lt ? 1 : 0);
     return hipGetLastError();
 }

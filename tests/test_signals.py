@@ -37,3 +37,23 @@ def test_hostile_clips_are_seeded_float32_and_finite():
         assert np.array_equal(a[k], b[k]), k
     assert a["denormal"].max() < 1.2e-38 and a["denormal"].min() > 0                 # float32 denormals, not zeros
     assert np.abs(a["clipped"]).max() == 1.0 and (np.abs(a["clipped"]) == 1.0).mean() > 0.01
+
+
+def test_ranged_clip_is_seeded_and_shaped_as_stated():
+    """tools/signals.py::ranged_clip (the clips of the geometry sweep): the same float32 array for the same seed, another
+    one for another seed, the stated length and level, silent gaps, and nothing above 0.49 sr beyond the noise floor."""
+    for sr, fmin, fmax in ((44100, 41.2, 523.25), (8000, 82.41, 1046.5), (44100, 1200.0, 22050.0), (96000, 82.41, 1046.5)):
+        a = signals.ranged_clip(3.0, sr, fmin, fmax, seed=5)
+        b = signals.ranged_clip(3.0, sr, fmin, fmax, seed=5)
+        c = signals.ranged_clip(3.0, sr, fmin, fmax, seed=6)
+        assert a.dtype == np.float32 and a.shape == (3 * sr,) and np.isfinite(a).all()
+        assert np.array_equal(a, b) and not np.array_equal(a, c)
+        assert 0.85 < float(np.abs(a).max()) < 0.95                       # peak 0.9 plus a -40 dB floor (sigma 0.01)
+        spec = np.abs(np.fft.rfft(a.astype(np.float64))) ** 2
+        top = int(0.49 * len(a))                                          # rfft bin of 0.49 sr
+        assert spec[top:].sum() < 1e-3 * spec.sum(), (sr, spec[top:].sum() / spec.sum())
+    # over a long clip: about 15 % of the time in gaps (noise floor only)
+    y = signals.ranged_clip(60.0, 44100, 82.41, 1046.5, seed=1).astype(np.float64)
+    rms = np.sqrt(np.mean(y[: len(y) // 2205 * 2205].reshape(-1, 2205) ** 2, axis=1))      # 50 ms blocks
+    quiet = float(np.mean(rms < 0.02))
+    assert 0.05 < quiet < 0.6, quiet

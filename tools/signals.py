@@ -143,3 +143,49 @@ def hostile_clips(sr=44100, seconds=2.0):
         "fast_chirp": 0.5 * np.sin(2 * np.pi * (50.0 * t + 0.5 * (4000.0 - 50.0) / seconds * t * t)),
     }
     return {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in out.items()}
+
+
+def ranged_clip(duration, sr, fmin, fmax, seed):
+    """A clip whose notes lie inside a handle's pitch range [fmin, fmax] (the guitar clips voice next to nothing at a bass,
+    a narrow or a near-Nyquist range): harmonic tones of 0.15..0.6 s with decaying envelopes and a slow glide, partials below 0.49 sr,
+    fundamentals log-uniform in [1.03 fmin, min(fmax / 1.03, 0.45 sr)]; about 15 % of the events are silent gaps and
+    about 10 % notes outside the range (below fmin, or above fmax where that stays under 0.45 sr); peak-normalised to 0.9
+    over a -40 dB white noise floor.  float32, seeded."""
+    rng = np.random.default_rng(seed)
+    n_total = int(sr * duration)
+    lo, hi = 1.03 * fmin, min(fmax / 1.03, 0.45 * sr)
+    if not lo < hi:
+        raise ValueError("pitch range too narrow for ranged_clip")
+    y = np.zeros(n_total)
+    pos = 0
+    while pos < n_total:
+        n = min(int(sr * rng.uniform(0.15, 0.6)), n_total - pos)
+        kind = rng.random()
+        if kind < 0.15:                       # gap
+            pos += n
+            continue
+        if kind < 0.25:                       # a note the range cannot hold
+            above = rng.random() < 0.5 and 1.2 * fmax < 0.45 * sr
+            f = rng.uniform(1.2 * fmax, min(2.0 * fmax, 0.45 * sr)) if above else rng.uniform(fmin / 2.0, fmin / 1.2)
+        else:
+            f = float(np.exp(rng.uniform(np.log(lo), np.log(hi))))
+        # a slow glide of up to 40 cents over the note (a few pitch bins: the decode has to follow it), ending inside the
+        # same bounds as it began
+        f1 = f * 2.0 ** (rng.uniform(-40.0, 40.0) / 1200.0)
+        if kind >= 0.25:
+            f1 = min(max(f1, lo), hi)
+        t = np.arange(n) / sr
+        phase = 2 * np.pi * np.cumsum(np.exp(np.linspace(np.log(f), np.log(f1), n))) / sr
+        note = np.zeros(n)
+        for k in range(1, 7):
+            if k * max(f, f1) >= 0.49 * sr:
+                break
+            note += rng.uniform(0.3, 1.0) / k * np.sin(k * phase + rng.uniform(0, 2 * np.pi))
+        env = np.exp(-t * rng.uniform(2.0, 8.0)) * np.minimum(1.0, t / 0.005)
+        y[pos:pos + n] = rng.uniform(0.4, 1.0) * env * note
+        pos += n
+    peak = np.max(np.abs(y))
+    if peak > 0:
+        y = y / peak * 0.9
+    y = y + rng.normal(0, 10 ** (-40.0 / 20), n_total)
+    return y.astype(np.float32)
