@@ -52,3 +52,44 @@ def cqt(y, sr=44100, hop_length=512, n_bins=84, fmin=32.70319566257483, bins_per
         C[k, ok] = full[idx[ok]]
         C[k] *= np.sqrt(ilen)
     return C
+
+
+def _sparse(positions, amps, n, hop_length, bank):
+    pos = np.asarray(positions, dtype=np.int64).reshape(-1)
+    amp = np.asarray(amps, dtype=np.float64).reshape(-1)
+    if pos.shape != amp.shape or (len(pos) and (pos.min() < 0 or pos.max() >= n)):
+        raise ValueError("positions and amps must pair up, every position inside [0, n)")
+    F = 1 + n // hop_length
+    m = (np.arange(F, dtype=np.int64) * hop_length)[None, :] - pos[:, None]      # tap read by (impulse, frame)
+    C = np.zeros((len(bank), F), dtype=np.complex128)
+    A = np.zeros((len(bank), F), dtype=np.float64)
+    count = np.zeros((len(bank), F), dtype=np.int64)
+    for k, (m_lo, sig, ilen) in enumerate(bank):
+        idx = m - m_lo
+        ok = (idx >= 0) & (idx < len(sig))
+        tap = np.where(ok, sig[np.clip(idx, 0, len(sig) - 1)], 0.0) * np.sqrt(ilen)
+        C[k] = (amp[:, None] * tap).sum(axis=0)
+        # rounded up by 2^-48 so that A >= |C| also holds in float64 arithmetic (|a g| against |a| |g| differ in the last bit)
+        A[k] = np.abs(amp[:, None] * tap).sum(axis=0) * (1.0 + 2.0 ** -48)
+        count[k] = ok.sum(axis=0)
+    return C, A, count
+
+
+def cqt_sparse(positions, amps, n, sr=44100, hop_length=512, n_bins=84, fmin=32.70319566257483, bins_per_octave=12,
+               filter_scale=1.0, bank=None):
+    """cqt() of the clip of length n that is zero except y[positions[i]] = amps[i] (positions distinct), straight from the
+    atoms without an FFT:  C[k, t] = sqrt(N_k) * sum_i a_i * atom_k[t*hop - s_i].
+    -> (C complex128 [n_bins, 1 + n//hop],  A = sum_i |a_i| * sqrt(N_k) * |atom_k[t*hop - s_i]|, same shape).
+    Every product a float32 evaluation forms is one of these terms, so its error is a small multiple of 2^-23 * A whatever
+    the summation order.  `bank`: the atoms() of the geometry, to build them once for many clips."""
+    if bank is None:
+        bank = atoms(sr, n_bins, fmin, bins_per_octave, filter_scale)
+    return _sparse(positions, amps, n, hop_length, bank)[:2]
+
+
+def cqt_sparse_counts(positions, n, sr=44100, hop_length=512, n_bins=84, fmin=32.70319566257483, bins_per_octave=12,
+                      filter_scale=1.0, bank=None):
+    """int64 [n_bins, 1 + n//hop]: impulses inside the window of bin k at frame t (the K of the rounding bound)."""
+    if bank is None:
+        bank = atoms(sr, n_bins, fmin, bins_per_octave, filter_scale)
+    return _sparse(positions, np.ones(len(np.reshape(positions, -1))), n, hop_length, bank)[2]

@@ -398,8 +398,14 @@ __global__ __launch_bounds__(1024) void viterbi_segmap_kernel(PassParams p) {
     const int T = p.seg_T[sg], st = p.seg_store[sg];
     const uint16_t *__restrict__ cmap = p.cmap + p.seg_ch0[sg] * S;
     int s = j;
+    // A dead voiced target (viterbi_band.inc: skipped steps) leaves its chunk-map entry unwritten, and the workspace is not
+    // cleared: whatever 16 bits lie there would index the next row up to 128 KB past the map's end.  Such a state is never on
+    // a decoded path (the stitch follows the arg-max's chain, whose entries are all written), so its chain just stops.
     if (T - 1 > st)
-        for (int cc = (T - 2) / C; cc >= st / C; --cc) s = cmap[(int64_t)cc * S + s];
+        for (int cc = (T - 2) / C; cc >= st / C; --cc) {
+            s = cmap[(int64_t)cc * S + s];
+            if (s >= S) { s = 0; break; }
+        }
     p.seg_map[(int64_t)sg * S + j] = (uint16_t)s;
 }
 // Between the rounds of a time-split pass: the first segment of every clip whose lock-on run never met its speculative run

@@ -178,3 +178,36 @@ def test_recursive_cqt_stays_close_to_the_direct_transform():
     assert np.argmax(np.abs(orc.cqt(tone))[:, 40]) == np.argmax(np.abs(od.cqt(tone))[:, 40]) == 45      # A4 = C1 + 45 semitones
     ca, cb = oc.chroma_cqt(y), orc.chroma_cqt(y)
     assert np.abs(ca - cb).max() < 0.02 and oc.cosine(ca, cb) > 0.9999
+
+
+def test_sparse_cqt_equals_the_dense_oracle():
+    """oracle.cqt.cqt_sparse (the atoms read tap by tap, no FFT) against oracle.cqt.cqt of the same clip, and its factor
+    A = sum |a_i| sqrt(N_k) |atom_k| against |C| (triangle inequality); the window counts against a brute-force count."""
+    from oracle import cqt as od
+    rng = np.random.default_rng(11)
+    banks = (dict(), dict(sr=22050, hop_length=441, n_bins=17, bins_per_octave=5, fmin=110.0, filter_scale=0.5))
+    for kw in banks:
+        hop = kw.get("hop_length", 512)
+        bank = od.atoms(**{k: v for k, v in kw.items() if k != "hop_length"})
+        for n, K in ((30000, 9), (6 * hop + 1, 3), (hop - 1, 2)):
+            pos = np.sort(rng.choice(n, size=K, replace=False))
+            pos[0], pos[-1] = 0, n - 1
+            amp = rng.uniform(0.25, 1.0, K) * rng.choice([-1.0, 1.0], K)
+            y = np.zeros(n)
+            y[pos] = amp
+            ref = od.cqt(y, **kw)
+            C, A = od.cqt_sparse(pos, amp, n, **kw)
+            assert C.shape == A.shape == ref.shape and C.dtype == np.complex128
+            assert np.abs(C - ref).max() <= 1e-12 * np.abs(ref).max()
+            assert (A >= np.abs(C)).all() and (A >= 0).all()
+            cnt = od.cqt_sparse_counts(pos, n, **kw)
+            for k, (m_lo, sig, _) in enumerate(bank):
+                m = np.arange(ref.shape[1])[None, :] * hop - pos[:, None]
+                assert np.array_equal(cnt[k], ((m >= m_lo) & (m < m_lo + len(sig))).sum(axis=0))
+            assert (A[cnt == 0] == 0).all() and (A[cnt > 0] > 0).any()
+    # one impulse reads one tap: |C[k, t]| = sqrt(N_k) |atom_k[t*hop - s]|
+    C, A = od.cqt_sparse([1000], [-0.5], 4096)
+    m_lo, sig, ilen = od.atoms()[0]
+    assert abs(abs(C[0, 3]) - 0.5 * np.sqrt(ilen) * abs(sig[3 * 512 - 1000 - m_lo])) < 1e-18 and np.allclose(np.abs(C), A, rtol=1e-14, atol=0)
+    with pytest.raises(ValueError):
+        od.cqt_sparse([4096], [1.0], 4096)
