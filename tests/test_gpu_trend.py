@@ -10,6 +10,7 @@ import pytest
 
 from spectrogram_midi_amd import _lib
 from spectrogram_midi_amd.financial import FinancialNoiseFilters, FinancialPitchAnalyzer, multi_filter_consensus
+from tools import trend_restated as R
 
 pytestmark = pytest.mark.gpu
 G = np.load(os.path.join(os.path.dirname(__file__), "golden", "v2_trend_golden.npz"))
@@ -121,6 +122,12 @@ def test_ghost_rsi_on_the_device_equals_the_rsi_of_the_density_tracks():
         ag, al = h.trend(_lib.TREND_RSI, [dens], [14, 1], n_out=2)
         np.testing.assert_array_equal(g[sl][inside], ag[0][a[sl][inside]])
         np.testing.assert_array_equal(l[sl][inside], al[0][a[sl][inside]])
+        # ... and to an independent statement of both: the restated Wilder averages of the restated density track
+        rdens = R.density_track(a[sl], b[sl], int(n[j]))
+        np.testing.assert_array_equal(rdens, dens)
+        _, rg, rl = R.rsi(rdens, 14)
+        np.testing.assert_array_equal(g[sl][inside], rg[a[sl][inside]])
+        np.testing.assert_array_equal(l[sl][inside], rl[a[sl][inside]])
 
 
 def test_ghost_note_filter_matches_reference():
