@@ -236,6 +236,13 @@ __device__ __forceinline__ int wave_incl_scan(int v, int lane) {
 __host__ __device__ inline int trough_km(int n_lags) { return n_lags / 2 + 2; }
 __host__ __device__ inline int trough_row_doubles(int n_lags) { const int km = trough_km(n_lags); return 8 + 2 * km + (km + 3) / 4; }
 
+// s_waitcnt immediate, gfx9 encoding ONLY (vmcnt in bits 3:0 and 15:14, expcnt 6:4, lgkmcnt 11:8): vmcnt(0), expcnt and
+// lgkmcnt left alone.  gfx10 and later encode the counters differently (and count stores in a counter of their own).
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(__GFX9__)
+#error "kWaitVmcnt0 is a gfx9 s_waitcnt encoding: this file is built for gfx950"
+#endif
+constexpr int kWaitVmcnt0 = 0x0F70;
+
 constexpr size_t kFrameLdsFixed = (size_t)2048 * 16 + 2048 * 4 + 1040 * 4 + 128 * 4 + 16 * 4 + 256 * 4;
 
 #if defined(AEGIS_ABLATE) && (AEGIS_ABLATE & 128)
@@ -391,6 +398,17 @@ __global__ __launch_bounds__(256, 2) void frame_yin_kernel(PassParams p, DevTabl
     // (the first barrier of the frame loop publishes the rows)
     if (want_fft) fft8_load_twiddles(twr, tb.twiddle, tid);      // 40 registers: loaded after the walk, which wants its own
     FRM_TICK(0)
+    // Loads and stores share ONE vector-memory counter, and the difference-function stores that end a pair are conditional,
+    // so a wait for the prefetched samples at the top of the next pair can only be vmcnt(0): it also waited for those rows
+    // (4.3 KB each, a few hundred cycles old) to be acknowledged, once per pair.  The samples are waited for explicitly
+    // instead, where no fresh stores are outstanding: here, and behind the pair's second frame (below).  With nothing of
+    // theirs pending on any path into the loop head, the frame buffer writes of a pair's first frame need no wait, and the
+    // d rows are first waited for at the top of the pair's second frame, a forward transform later.
+    // This rests on where the compiler's wait insertion puts its own waits: results never depend on it, the time does.
+    // After a compiler upgrade, or an edit that leaves a sample load pending on some path into the loop head, look at the
+    // ISA again (hipcc -O3 -ffp-contract=off --offload-arch=gfx950 --cuda-device-only -S): no `s_waitcnt vmcnt` may
+    // stand in front of the first four `ds_write2st64_b32` of the pair loop (the first frame's buffer writes).
+    __builtin_amdgcn_s_waitcnt(kWaitVmcnt0);
 
     for (int pr = 0; pr < nfr; pr += 2) {
         double2 P[2][5];
@@ -509,6 +527,9 @@ __global__ __launch_bounds__(256, 2) void frame_yin_kernel(PassParams p, DevTabl
             __syncthreads();
             FRM_TICK(3)
         }
+        // The next pair's first frame (requested a forward transform ago) is waited for HERE, see above: what is outstanding
+        // besides it is the second frame's rms store, a power section old.  The mel section waits for its weights anyway.
+        __builtin_amdgcn_s_waitcnt(kWaitVmcnt0);
         // ---- mel projection of BOTH frames of the pair: sparse Slaney triangles.  Every <= 16-bin chunk of a triangle is
         // one thread's float32 fma chain per frame (the 16 weights requested once per pair); a band then adds its
         // chunks' sums in order (the widest band has six), threads 0..127 for the first frame and 128..255 for the
@@ -833,9 +854,11 @@ __global__ __launch_bounds__(512, 4) void pyin_obs_kernel(PassParams p, DevTable
     __syncthreads();
 
     int64_t f = 0, fo = 0, sel_end = 0;                   // the wave's frames are normally consecutive frames of one clip:
+    int Kn = -1;                                          // >= 0: the frame's trough list is in LDS already (see `ahead` below)
+    const int64_t n_sel = geo_n_sel(p);                   // read once: a load per frame is a wait per frame, for the stores too
     for (int it = 0; it < frames_per_wave; ++it) {        // the binary search of map_frame runs once, not per frame
     const int64_t fsel = ((int64_t)blockIdx.x * nwaves + wid) * frames_per_wave + it;
-    if (fsel >= geo_n_sel(p)) break;                      // wave-uniform
+    if (fsel >= n_sel) break;                             // wave-uniform
     if (it > 0 && fsel < sel_end) { ++f; ++fo; }
     else {
         int c;
@@ -856,12 +879,15 @@ __global__ __launch_bounds__(512, 4) void pyin_obs_kernel(PassParams p, DevTable
     if (p.troughs) {
         // the frame kernel's epilogue has found the troughs already (frame_yin_kernel): count, values, parabolic shifts, lags
         const int KMt = trough_km(nl);
+        if (Kn >= 0) K = Kn;                // the frame before this one has put the list into th / tsh / ti already
+        else {
         K = __builtin_amdgcn_readfirstlane((int)__double_as_longlong(dr[0]));
         const int16_t *__restrict__ tiv = reinterpret_cast<const int16_t *>(dr + 8 + 2 * KMt);
         for (int k = lane; k < K; k += 64) {
             const double h = dr[8 + k], sh = dr[8 + KMt + k];
             const int16_t ix = tiv[k];
             th[k] = h; tsh[k] = sh; ti[k] = ix;
+        }
         }
         wave_sync();
         OBS_TICK(0)
@@ -966,6 +992,13 @@ __global__ __launch_bounds__(512, 4) void pyin_obs_kernel(PassParams p, DevTable
     double vp = 0.0;
     unsigned segm = 0;               // 64-bin segments of the observation row with an observed bin (wave-uniform)
     const int rounds = (K + 63) >> 6;
+    // The list of the wave's NEXT frame, when that is the next frame of this clip: its count and its first two rounds are
+    // requested below, once this frame's trough registers are dead, and taken over at the end of the frame IN FRONT of the
+    // frame's global stores.  Loads and stores share one memory counter: requested at the top of the next frame, the count
+    // waited for those stores to be acknowledged, and the list itself was a second, dependent round trip behind it.
+    const bool ahead = p.troughs && it + 1 < frames_per_wave && fsel + 1 < sel_end;      // (uniform)
+    double nK = 0.0, nh[2] = {0.0, 0.0}, nsh[2] = {0.0, 0.0};
+    int16_t nix[2] = {0, 0};
     // Everything below is unrolled over the rounds of 64 troughs a frame may need (up to 8); nearly every frame has at
     // most 128 troughs, so the body exists twice: the two-round instance is what runs (a quarter of the code: the three
     // frame-stage kernels and the Viterbi share instruction caches), the eight-round one covers the rest.
@@ -1091,6 +1124,18 @@ __global__ __launch_bounds__(512, 4) void pyin_obs_kernel(PassParams p, DevTable
             }
         }
         OBS_TICK(6)
+        if (ahead) {
+            // unconditional loads, the index clamped inside the row (a branch per lane would cost a wait per element)
+            const int KMt = trough_km(nl);
+            const double *__restrict__ drn = dr + p.lag_stride;
+            const int16_t *__restrict__ tivn = reinterpret_cast<const int16_t *>(drn + 8 + 2 * KMt);
+            nK = drn[0];
+    #pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                const int k = min(q * 64 + lane, KMt - 1);
+                nh[q] = drn[8 + k]; nsh[q] = drn[8 + KMt + k]; nix[q] = tivn[k];
+            }
+        }
         wave_sync();                 // last read of y is behind us: the buffer becomes the output row
         for (int b = lane; b < B; b += 64) row[b] = p.log_tiny;
         wave_sync();
@@ -1155,6 +1200,19 @@ __global__ __launch_bounds__(512, 4) void pyin_obs_kernel(PassParams p, DevTable
     else tail(std::integral_constant<int, kMaxRounds>{});
     wave_sync();
     OBS_TICK(7)
+    Kn = -1;
+    if (ahead) {
+        // th and ti were last read before the request above; the shifts go where this frame's output row still lies and
+        // follow once the row has been read out (below).  More than two rounds: the next frame loads its own list.
+        __builtin_amdgcn_s_waitcnt(kWaitVmcnt0);
+        Kn = __builtin_amdgcn_readfirstlane((int)__double_as_longlong(nK));
+        if (Kn > 128) Kn = -1;
+    #pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const int k = q * 64 + lane;
+            if (k < Kn) { th[k] = nh[q]; ti[k] = nix[q]; }
+        }
+    }
     // Only the 64-bin segments that hold an observed bin are stored (the Viterbi kernel skips a voiced wave whose segment
     // is all log(tiny) at an easy frame and never loads it); at a hard frame -- unvoiced observation log(tiny) -- every
     // value matters and the whole row goes out.
@@ -1167,6 +1225,11 @@ __global__ __launch_bounds__(512, 4) void pyin_obs_kernel(PassParams p, DevTable
         p.obs_seg[f] = (int32_t)segm;
         p.logunv[f] = log(unv + DBL_MIN);
         if (p.out_vprob != nullptr) p.out_vprob[fo] = vp;
+    }
+    #pragma unroll
+    for (int q = 0; q < 2; ++q) {        // (LDS operations of a wave complete in order: the row has been read)
+        const int k = q * 64 + lane;
+        if (k < Kn) y[k] = nsh[q];
     }
     OBS_TICK(8)
     }   // frames of this wave
