@@ -468,6 +468,22 @@ int64_t aegis_debug_fetch(aegis_handle *h, const char *name, void *dst, int64_t 
 int aegis_debug_rake_columns(aegis_handle *h, const float *mel_power, int64_t n_rows, int32_t n_mels, float clip_max,
                              double ratio, int32_t from_power, uint8_t *flags_out);
 
+/* Replaces the observation kernel's output, for the tests that put the Viterbi kernels under adversarial rows: logobs is
+ * f64[F][n_pitch_bins] (log observation of the voiced states), logunv f64[F] (the one value every unvoiced state observes),
+ * rows in the caller's clip order, clip after clip (the order of the output arrays).  Arms the handle for the NEXT
+ * aegis_analyze_batch / _batch_device / _pcm call only: that call must have the PYIN stage and exactly F frames in total
+ * (AEGIS_ERR_INVALID otherwise, the handle stays usable), it runs its whole schedule as planned -- the samples it is
+ * handed only size the clips -- with every launch of the observation kernel replaced by a copy of the given rows
+ * (voiced_prob is not written), and the handle is disarmed when it returns, whatever it returns.  logobs == NULL disarms;
+ * arming again replaces the rows.
+ * Domain: the Viterbi kernels are exact on the rows pYIN can emit, and rows outside are rejected with AEGIS_ERR_INVALID
+ * and a message naming the frame: no NaN; log(tiny) <= logobs <= 0 (tiny = DBL_MIN; the 32-bit reductions rely on
+ * values <= 0); logunv == log(tiny) (a hard frame: voiced_prob == 1) or log(2^-53 / n_pitch_bins) <= logunv <= 0 (an easy
+ * frame: the dead-target skip relies on that floor); a hard frame has a bin above log(tiny), as voiced_prob == 1 implies.
+ * The rows are validated before the device is looked at: a device = -1 handle rejects what a device handle rejects and
+ * answers AEGIS_ERR_DEVICE to rows inside the domain. */
+int aegis_debug_set_observations(aegis_handle *h, const double *logobs, const double *logunv, int64_t F);
+
 /* The pass plan an analyze call would make (CPU only: no device work, a device=-1 handle plans too).  Clips of
  * n_samples[i] samples, every stage, the handle's knobs and max_frames_per_pass, a device of n_cus compute units;
  * entry: AEGIS_PLAN_DEVICE (aegis_analyze_batch_device on the handle's stream), AEGIS_PLAN_CALLER_STREAM (on a stream of

@@ -70,7 +70,8 @@ EXPORTS = ("aegis_abi_version", "aegis_create", "aegis_destroy", "aegis_last_err
            "aegis_stream_open", "aegis_stream_push", "aegis_stream_close", "aegis_stream_free", "aegis_cqt", "aegis_cqt_device", "aegis_chroma_cqt",
            "aegis_extract_events", "aegis_render_smf", "aegis_events_last_error", "aegis_debug_plan",
            "aegis_analyze_pcm", "aegis_pcm_samples_for", "aegis_resample_taps", "aegis_stream_push_commit",
-           "aegis_synth_parse_smf", "aegis_synth_samples_for", "aegis_synth_adsr", "aegis_debug_rake_columns")
+           "aegis_synth_parse_smf", "aegis_synth_samples_for", "aegis_synth_adsr", "aegis_debug_rake_columns",
+           "aegis_debug_set_observations")
 
 _lib = None
 
@@ -284,6 +285,22 @@ class Handle:
         if rc != 0:
             raise AegisError(rc, self.lib.aegis_last_error(self._h).decode())
         return out.astype(bool)
+
+    def set_observations(self, logobs, logunv=None):
+        """aegis_debug_set_observations: the NEXT analyze call decodes these rows (logobs [F, n_pitch_bins], logunv [F], in
+        the caller's clip order) instead of its observation kernel's; None disarms.  AegisError(ERR_INVALID) for rows
+        outside the documented domain."""
+        fn = self.lib.aegis_debug_set_observations
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+        fn.restype = C.c_int
+        if logobs is None:
+            self._check(fn(self._h, None, None, 0))
+            return
+        rows = np.ascontiguousarray(logobs, dtype=np.float64)
+        unv = np.ascontiguousarray(logunv, dtype=np.float64)
+        if rows.ndim != 2 or rows.shape[1] != self.param("n_pitch_bins") or unv.shape != (rows.shape[0],):
+            raise ValueError("logobs must be [F, n_pitch_bins] and logunv [F]")
+        self._check(fn(self._h, rows.ctypes.data, unv.ctypes.data, rows.shape[0]))
 
     # aegis_debug_plan: entry kinds, option bits and the per-pass flag bits (include/aegis_hip.h AEGIS_PLAN_*)
     PLAN_ENTRIES = {"device": 0, "caller_stream": 1, "host_fed": 2}

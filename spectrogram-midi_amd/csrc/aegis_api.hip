@@ -428,6 +428,15 @@ static int analyze_device_locked(aegis_handle *h, const float *d_pcm, const int6
             return AEGIS_ERR_INVALID;
         }
     }
+    if (h->inject.armed) {      // aegis_debug_set_observations: the rows are indexed by this call's output frames
+        int64_t F = 0;
+        for (int i = 0; i < n_clips; ++i) F += 1 + (sample_offsets[i + 1] - sample_offsets[i]) / t.hop;
+        if (!(stages & AEGIS_STAGE_PYIN) || F != h->inject.F) {
+            h->err = "injected observations: the call needs the PYIN stage and exactly " + std::to_string(h->inject.F) + " frames (it has " +
+                     std::to_string(F) + ")";
+            return AEGIS_ERR_INVALID;
+        }
+    }
     // host arrays of the previous call's plan are no longer referenced once the stream drained
     if (h->plan_in_flight) { HIPCHK(h, hipStreamSynchronize(s)); h->plan_in_flight = false; }
     h->tsplit.checks.clear();
@@ -550,7 +559,10 @@ static int analyze_device_locked(aegis_handle *h, const float *d_pcm, const int6
             }
             begin_event(h, "frame", fs); launch_frame(p, h->dt, fs); end_event(h, fs);
             if (!py) continue;
-            begin_event(h, "pyin_obs", fs); launch_pyin_obs(p, h->dt, fs); end_event(h, fs);
+            begin_event(h, "pyin_obs", fs);
+            if (h->inject.armed) launch_inject_obs(p, static_cast<const double *>(h->inject.obs.p), static_cast<const double *>(h->inject.unv.p), fs);
+            else launch_pyin_obs(p, h->dt, fs);
+            end_event(h, fs);
             if (m.persistent) {
                 if (k != h->test_drop_signal)      // AEGIS_TEST_DROP_CHUNK_SIGNAL=k: the kernel's bounded wait is tested with it
                     launch_chunk_signal(static_cast<uint32_t *>(w.chunk_flag.p) + k, p.chunk_gen, fs);
@@ -683,11 +695,19 @@ static int run_with_recovery(aegis_handle *h, const std::function<int()> &attemp
     }
 }
 
+// aegis_debug_set_observations arms ONE analyze call: every analyze entry holds one of these from its first line on, so
+// the handle is disarmed when the entry returns, whatever it returns (declared before the entry's lock: it runs after it)
+struct DisarmInjection {
+    aegis_handle *h;
+    ~DisarmInjection() { std::lock_guard<std::mutex> lock(h->mu); h->inject.armed = false; }
+};
+
 int aegis_analyze_batch_device(aegis_handle *h, const float *d_pcm, const int64_t *sample_offsets,
                                int32_t n_clips, double rake_sensitivity, uint32_t stages,
                                aegis_outputs *dout, void *stream_v, int32_t sync) {
     try {
     if (!h) return AEGIS_ERR_INVALID;
+    DisarmInjection disarm{h};
     std::lock_guard<std::mutex> lock(h->mu);
     // (sync = 1: analyze_device_locked synchronises and reads the abort flag itself)
     return run_with_recovery(h, [&] { return analyze_device_locked(h, d_pcm, sample_offsets, n_clips, rake_sensitivity, stages, dout, stream_v, sync); });
@@ -732,6 +752,7 @@ int aegis_analyze_batch(aegis_handle *h, const float *const *pcm, const int64_t 
                         double rake_sensitivity, uint32_t stages, aegis_outputs *out) {
     try {
     if (!h) return AEGIS_ERR_INVALID;
+    DisarmInjection disarm{h};
     if (n_clips < 0 || (n_clips > 0 && (!pcm || !n_samples || !out))) { h->err = "null argument"; return AEGIS_ERR_INVALID; }
     if (n_clips == 0) return AEGIS_OK;
     if (stages & AEGIS_STAGE_RAKE) stages |= AEGIS_STAGE_MEL;
@@ -787,6 +808,7 @@ int aegis_analyze_pcm(aegis_handle *h, const aegis_pcm_clip *clips, int32_t n_cl
                       aegis_outputs *out, float *y_out) {
     try {
     if (!h) return AEGIS_ERR_INVALID;
+    DisarmInjection disarm{h};
     if (stages & AEGIS_STAGE_RAKE) stages |= AEGIS_STAGE_MEL;
     const bool analyse = (stages & AEGIS_STAGE_ALL) != 0;
     if (n_clips < 0 || (n_clips > 0 && (!clips || (analyse && !out)))) { h->err = "null argument"; return AEGIS_ERR_INVALID; }

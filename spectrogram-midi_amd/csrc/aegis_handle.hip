@@ -3,6 +3,7 @@
 #include "aegis_internal.h"
 
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <new>
@@ -628,6 +629,48 @@ int aegis_debug_rake_columns(aegis_handle *h, const float *mel_power, int64_t n_
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpyAsync(flags_out, h->rk_raw.p, n_rows, hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipStreamSynchronize(s));
+    return AEGIS_OK;
+    } catch (...) { return abi_fail(h); }
+}
+
+int aegis_debug_set_observations(aegis_handle *h, const double *logobs, const double *logunv, int64_t F) {
+    try {
+    if (!h) return AEGIS_ERR_INVALID;
+    std::lock_guard<std::mutex> lock(h->mu);
+    h->inject.armed = false;
+    if (!logobs) return AEGIS_OK;
+    if (!logunv || F <= 0) { h->err = "bad argument"; return AEGIS_ERR_INVALID; }
+    // the domain the Viterbi kernels are exact on (include/aegis_hip.h): rows pyin_obs_kernel can emit
+    const int B = h->tab.n_bins;
+    const double log_tiny = h->tab.log_tiny, easy_min = std::log(std::ldexp(1.0, -53) / B);
+    auto reject = [&](int64_t f, const char *why) {
+        h->err = "injected observations, frame " + std::to_string(f) + ": " + why;
+        return AEGIS_ERR_INVALID;
+    };
+    for (int64_t f = 0; f < F; ++f) {
+        const double u = logunv[f];
+        const bool hard = u == log_tiny;
+        if (u != u) return reject(f, "logunv is NaN");
+        if (!hard && !(u >= easy_min && u <= 0.0)) return reject(f, "logunv must be log(tiny) or within [log(2^-53 / n_pitch_bins), 0]");
+        const double *row = logobs + f * B;
+        bool observed = false;
+        for (int b = 0; b < B; ++b) {
+            if (row[b] != row[b]) return reject(f, "logobs is NaN");
+            if (!(row[b] >= log_tiny && row[b] <= 0.0)) return reject(f, "logobs must be within [log(tiny), 0]");
+            observed = observed || row[b] != log_tiny;
+        }
+        if (hard && !observed) return reject(f, "a hard frame (logunv == log(tiny)) needs a bin above log(tiny)");
+    }
+    DEVICE_ONLY(h);
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipDeviceSynchronize());        // (an earlier armed call that returned without a sync may still read the rows)
+    int rc;
+    if ((rc = ensure(h, h->inject.obs, (size_t)F * B * 8)) != AEGIS_OK) return rc;
+    if ((rc = ensure(h, h->inject.unv, (size_t)F * 8)) != AEGIS_OK) return rc;
+    HIPCHK(h, hipMemcpy(h->inject.obs.p, logobs, (size_t)F * B * 8, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(h->inject.unv.p, logunv, (size_t)F * 8, hipMemcpyHostToDevice));
+    h->inject.F = F;
+    h->inject.armed = true;
     return AEGIS_OK;
     } catch (...) { return abi_fail(h); }
 }

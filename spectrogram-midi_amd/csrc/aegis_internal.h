@@ -68,6 +68,9 @@ struct aegis_handle {
         DevBuf seg64, seg32, seg_col, seg_map, seg_i32, colhist, colG, colkg, clip_flag, flag_order, tube_buf, tube_at, tube_count;    // time-split passes
     } work[2];
     DevBuf vstats, rk_raw, abort_flag, finite_flag;
+    // aegis_debug_set_observations: rows [F][n_bins] / [F] in the caller's clip order that the next analyze call feeds its
+    // Viterbi in place of pyin_obs_kernel's (armed for that one call: the analyze entries disarm when they return)
+    struct Inject { bool armed = false; int64_t F = 0; DevBuf obs, unv; } inject;
     uint32_t chunk_gen = 0;                   // generation of the chunk flags of a persistent Viterbi launch
     int test_drop_signal = -1;
     // The single Viterbi launch of a balanced pass and its fall-back (run_with_recovery, aegis_api.hip)

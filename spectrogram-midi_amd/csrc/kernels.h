@@ -166,6 +166,8 @@ bool frame_cmnd_supported(int max_period);
 int frame_batch_fpw(int max_period);        // frames per frame_yin workgroup of a launch that selects >= 4096 frames (smaller launches: 2)
 int trough_row_doubles_host(int n_lags);    // doubles of a dfn row that holds a frame's trough list (PassParams::troughs)   // the frame kernel's LDS holds the CMND rows of a workgroup's frames (PassParams::cmnd_in_frame)
 void launch_pyin_obs(const PassParams &p, const DevTables &t, hipStream_t s);
+// in its place (aegis_debug_set_observations): the launch's selected frames take their rows from src_obs [out_total][n_bins] / src_unv
+void launch_inject_obs(const PassParams &p, const double *src_obs, const double *src_unv, hipStream_t s);
 int pyin_obs_waves(const PassParams &p);    // waves per pyin_obs workgroup of a launch of p.n_sel frames (p.dense: at most four)
 hipError_t launch_viterbi(const PassParams &p, const DevTables &t, const double *host_lt_band, hipStream_t s);
 // time-split pass: speculative runs (grid = segments), lock-on runs (grid = segments that have a predecessor, listed in

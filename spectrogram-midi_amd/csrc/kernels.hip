@@ -1592,6 +1592,37 @@ void launch_pyin_obs(const PassParams &p, const DevTables &t, hipStream_t s) {
     const int64_t per_wg = (int64_t)waves * fpw;
     hipLaunchKernelGGL(pyin_obs_kernel, dim3((unsigned)((p.n_sel + per_wg - 1) / per_wg)), dim3(64 * waves), lds, s, p, t, fpw);
 }
+// Test hook (aegis_debug_set_observations): what pyin_obs_kernel leaves for the Viterbi -- logunv, obs_seg and the named
+// 64-bin segments of logobs -- for the launch's selected frames, from caller-supplied rows in output order.  One wave per
+// frame; out_vprob is not written.
+__global__ __launch_bounds__(256) void inject_obs_kernel(PassParams p, const double *__restrict__ src_obs, const double *__restrict__ src_unv) {
+    const int lane = threadIdx.x & 63, B = p.n_bins, nseg = (B + 63) >> 6;
+    const int64_t fs = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (fs >= geo_n_sel(p)) return;                       // wave-uniform
+    int c;
+    int64_t t, f;
+    map_frame(p, fs, c, t, f);
+    const int64_t fo = out_index(p, c, t);
+    const double *__restrict__ row = src_obs + fo * (int64_t)B;
+    const double unv = src_unv[fo];
+    unsigned segm = 0;
+    for (int sg = 0; sg < nseg; ++sg) {
+        const int b = sg * 64 + lane;
+        if (__ballot(b < B && row[b] != p.log_tiny)) segm |= 1u << sg;
+    }
+    if (unv == p.log_tiny) segm = 0x40000000u | ((1u << nseg) - 1u);
+    double *__restrict__ orow = p.logobs + f * (int64_t)p.obs_stride;
+    for (int b = lane, sg = 0; b < B; b += 64, ++sg)
+        if ((segm >> sg) & 1u) orow[b] = row[b];
+    if (lane == 0) {
+        p.obs_seg[f] = (int32_t)segm;
+        p.logunv[f] = unv;
+    }
+}
+void launch_inject_obs(const PassParams &p, const double *src_obs, const double *src_unv, hipStream_t s) {
+    if (p.n_sel == 0) return;
+    hipLaunchKernelGGL(inject_obs_kernel, dim3((unsigned)((p.n_sel + 3) / 4)), dim3(256), 0, s, p, src_obs, src_unv);
+}
 // librosa.util.valid_audio: every sample finite.  16 bytes per thread and iteration, one atomic per wave that finds one.
 __global__ __launch_bounds__(256) void finite_check_kernel(const float *__restrict__ pcm, int64_t n, unsigned long long *first_bad) {
     const int64_t stride = (int64_t)gridDim.x * 256 * 4;
