@@ -484,6 +484,22 @@ int aegis_debug_rake_columns(aegis_handle *h, const float *mel_power, int64_t n_
  * answers AEGIS_ERR_DEVICE to rows inside the domain. */
 int aegis_debug_set_observations(aegis_handle *h, const double *logobs, const double *logunv, int64_t F);
 
+/* Replaces the frame kernel's difference function, for the tests that put everything between it and the observation row
+ * (the cumulative mean, the troughs, the threshold prior, parabolic refinement, bin assignment: the CMND epilogue of
+ * frame_yin_kernel and pyin_obs_kernel) under rows built to sit on their decisions: d is f64[F][max_period + 1], pyin's
+ * d[tau] for lags 0 .. max_period, rows in the caller's clip order, clip after clip (the order of the output arrays).
+ * Arms the handle for the NEXT aegis_analyze_batch / _batch_device / _pcm call only: that call must have the PYIN stage
+ * and exactly F frames in total (AEGIS_ERR_INVALID otherwise, the handle stays usable).  It runs the kernels and the
+ * schedule of an ordinary call -- energy walk, FFTs, mel and RMS on the samples it is handed -- through an instantiation
+ * of the frame kernel (frame_yin_kernel<true>) that stores row `output frame` of d at the point where the shipping one stores its own difference
+ * function; nothing downstream knows.  The handle is disarmed when that call returns, whatever it returns; stream pushes
+ * neither consume nor disturb the arming.  d == NULL disarms; arming again replaces the rows; arming while
+ * aegis_debug_set_observations is armed (or the reverse) is AEGIS_ERR_INVALID: one hook per call.
+ * Domain: every d finite (anything else is rejected with AEGIS_ERR_INVALID and a message naming the frame, before the
+ * device is looked at) AND a finite CMND d[tau] / (cumsum(d[1:])[tau] / tau + tiny) at every lag min_period .. max_period,
+ * which is the caller's to ensure: behaviour on rows whose CMND holds a NaN or an infinity is unspecified. */
+int aegis_debug_set_difference(aegis_handle *h, const double *d, int64_t F);
+
 /* The pass plan an analyze call would make (CPU only: no device work, a device=-1 handle plans too).  Clips of
  * n_samples[i] samples, every stage, the handle's knobs and max_frames_per_pass, a device of n_cus compute units;
  * entry: AEGIS_PLAN_DEVICE (aegis_analyze_batch_device on the handle's stream), AEGIS_PLAN_CALLER_STREAM (on a stream of

@@ -61,14 +61,20 @@ def difference_terms(y_frames, p):
     return acf, energy, d
 
 
-def cmnd(y_frames, p):
-    """_cumulative_mean_normalized_difference -> float64[n_lags, F]."""
-    _, _, d = difference_terms(y_frames, p)
+def cmnd_from_d(d, p):
+    """The CMND of difference-function rows d float64[>= max_period + 1, F] (lags 0 ..) -> float64[n_lags, F]: one
+    sequential float64 cumulative sum, one division by the lag, one addition of tiny and one division per value."""
     num = d[p.min_period : p.max_period + 1, :]
     tau = np.arange(1, p.max_period + 1).reshape(-1, 1)
     cum_mean = np.cumsum(d[1 : p.max_period + 1, :], axis=-2) / tau
     den = cum_mean[p.min_period - 1 : p.max_period, :]
     return num / (den + TINY)
+
+
+def cmnd(y_frames, p):
+    """_cumulative_mean_normalized_difference -> float64[n_lags, F]."""
+    _, _, d = difference_terms(y_frames, p)
+    return cmnd_from_d(d, p)
 
 
 def parabolic_shifts(x):

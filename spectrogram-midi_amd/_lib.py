@@ -71,7 +71,7 @@ EXPORTS = ("aegis_abi_version", "aegis_create", "aegis_destroy", "aegis_last_err
            "aegis_extract_events", "aegis_render_smf", "aegis_events_last_error", "aegis_debug_plan",
            "aegis_analyze_pcm", "aegis_pcm_samples_for", "aegis_resample_taps", "aegis_stream_push_commit",
            "aegis_synth_parse_smf", "aegis_synth_samples_for", "aegis_synth_adsr", "aegis_debug_rake_columns",
-           "aegis_debug_set_observations")
+           "aegis_debug_set_observations", "aegis_debug_set_difference")
 
 _lib = None
 
@@ -301,6 +301,21 @@ class Handle:
         if rows.ndim != 2 or rows.shape[1] != self.param("n_pitch_bins") or unv.shape != (rows.shape[0],):
             raise ValueError("logobs must be [F, n_pitch_bins] and logunv [F]")
         self._check(fn(self._h, rows.ctypes.data, unv.ctypes.data, rows.shape[0]))
+
+    def set_difference(self, d):
+        """aegis_debug_set_difference: the NEXT analyze call's frame kernel stores these rows (d [F, max_period + 1], in the
+        caller's clip order) in place of its own difference function; None disarms.  AegisError(ERR_INVALID) for a value
+        that is not finite."""
+        fn = self.lib.aegis_debug_set_difference
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+        fn.restype = C.c_int
+        if d is None:
+            self._check(fn(self._h, None, 0))
+            return
+        rows = np.ascontiguousarray(d, dtype=np.float64)
+        if rows.ndim != 2 or rows.shape[1] != self.param("max_period") + 1:
+            raise ValueError("d must be [F, max_period + 1]")
+        self._check(fn(self._h, rows.ctypes.data, rows.shape[0]))
 
     # aegis_debug_plan: entry kinds, option bits and the per-pass flag bits (include/aegis_hip.h AEGIS_PLAN_*)
     PLAN_ENTRIES = {"device": 0, "caller_stream": 1, "host_fed": 2}

@@ -437,6 +437,15 @@ static int analyze_device_locked(aegis_handle *h, const float *d_pcm, const int6
             return AEGIS_ERR_INVALID;
         }
     }
+    if (h->inject_d.armed) {    // aegis_debug_set_difference: likewise (never both: each setter refuses while the other hook is armed)
+        int64_t F = 0;
+        for (int i = 0; i < n_clips; ++i) F += 1 + (sample_offsets[i + 1] - sample_offsets[i]) / t.hop;
+        if (!(stages & AEGIS_STAGE_PYIN) || F != h->inject_d.F) {
+            h->err = "injected difference rows: the call needs the PYIN stage and exactly " + std::to_string(h->inject_d.F) + " frames (it has " +
+                     std::to_string(F) + ")";
+            return AEGIS_ERR_INVALID;
+        }
+    }
     // host arrays of the previous call's plan are no longer referenced once the stream drained
     if (h->plan_in_flight) { HIPCHK(h, hipStreamSynchronize(s)); h->plan_in_flight = false; }
     h->tsplit.checks.clear();
@@ -557,7 +566,9 @@ static int analyze_device_locked(aegis_handle *h, const float *d_pcm, const int6
                     HIPCHK(h, hipStreamWaitEvent(fs, h->copy_event, 0));
                 }
             }
-            begin_event(h, "frame", fs); launch_frame(p, h->dt, fs); end_event(h, fs);
+            begin_event(h, "frame", fs);
+            launch_frame(p, h->dt, fs, h->inject_d.armed ? static_cast<const double *>(h->inject_d.d.p) : nullptr);
+            end_event(h, fs);
             if (!py) continue;
             begin_event(h, "pyin_obs", fs);
             if (h->inject.armed) launch_inject_obs(p, static_cast<const double *>(h->inject.obs.p), static_cast<const double *>(h->inject.unv.p), fs);
@@ -695,11 +706,11 @@ static int run_with_recovery(aegis_handle *h, const std::function<int()> &attemp
     }
 }
 
-// aegis_debug_set_observations arms ONE analyze call: every analyze entry holds one of these from its first line on, so
+// aegis_debug_set_observations and aegis_debug_set_difference arm ONE analyze call: every analyze entry holds one of these from its first line on, so
 // the handle is disarmed when the entry returns, whatever it returns (declared before the entry's lock: it runs after it)
 struct DisarmInjection {
     aegis_handle *h;
-    ~DisarmInjection() { std::lock_guard<std::mutex> lock(h->mu); h->inject.armed = false; }
+    ~DisarmInjection() { std::lock_guard<std::mutex> lock(h->mu); h->inject.armed = false; h->inject_d.armed = false; }
 };
 
 int aegis_analyze_batch_device(aegis_handle *h, const float *d_pcm, const int64_t *sample_offsets,

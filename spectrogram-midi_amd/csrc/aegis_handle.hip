@@ -640,6 +640,7 @@ int aegis_debug_set_observations(aegis_handle *h, const double *logobs, const do
     h->inject.armed = false;
     if (!logobs) return AEGIS_OK;
     if (!logunv || F <= 0) { h->err = "bad argument"; return AEGIS_ERR_INVALID; }
+    if (h->inject_d.armed) { h->err = "injected observations: injected difference rows are armed already (one hook per call)"; return AEGIS_ERR_INVALID; }
     // the domain the Viterbi kernels are exact on (include/aegis_hip.h): rows pyin_obs_kernel can emit
     const int B = h->tab.n_bins;
     const double log_tiny = h->tab.log_tiny, easy_min = std::log(std::ldexp(1.0, -53) / B);
@@ -671,6 +672,33 @@ int aegis_debug_set_observations(aegis_handle *h, const double *logobs, const do
     HIPCHK(h, hipMemcpy(h->inject.unv.p, logunv, (size_t)F * 8, hipMemcpyHostToDevice));
     h->inject.F = F;
     h->inject.armed = true;
+    return AEGIS_OK;
+    } catch (...) { return abi_fail(h); }
+}
+
+int aegis_debug_set_difference(aegis_handle *h, const double *d, int64_t F) {
+    try {
+    if (!h) return AEGIS_ERR_INVALID;
+    std::lock_guard<std::mutex> lock(h->mu);
+    h->inject_d.armed = false;
+    if (!d) return AEGIS_OK;
+    if (F <= 0) { h->err = "bad argument"; return AEGIS_ERR_INVALID; }
+    if (h->inject.armed) { h->err = "injected difference rows: injected observations are armed already (one hook per call)"; return AEGIS_ERR_INVALID; }
+    const int64_t W = (int64_t)h->tab.max_period + 1;
+    for (int64_t f = 0; f < F; ++f)
+        for (int64_t tau = 0; tau < W; ++tau)
+            if (!std::isfinite(d[f * W + tau])) {
+                h->err = "injected difference rows, frame " + std::to_string(f) + ": d[" + std::to_string(tau) + "] is not finite";
+                return AEGIS_ERR_INVALID;
+            }
+    DEVICE_ONLY(h);
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipDeviceSynchronize());        // (an earlier armed call that returned without a sync may still read the rows)
+    int rc;
+    if ((rc = ensure(h, h->inject_d.d, (size_t)F * W * 8)) != AEGIS_OK) return rc;
+    HIPCHK(h, hipMemcpy(h->inject_d.d.p, d, (size_t)F * W * 8, hipMemcpyHostToDevice));
+    h->inject_d.F = F;
+    h->inject_d.armed = true;
     return AEGIS_OK;
     } catch (...) { return abi_fail(h); }
 }

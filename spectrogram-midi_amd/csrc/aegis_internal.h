@@ -71,6 +71,9 @@ struct aegis_handle {
     // aegis_debug_set_observations: rows [F][n_bins] / [F] in the caller's clip order that the next analyze call feeds its
     // Viterbi in place of pyin_obs_kernel's (armed for that one call: the analyze entries disarm when they return)
     struct Inject { bool armed = false; int64_t F = 0; DevBuf obs, unv; } inject;
+    // aegis_debug_set_difference: rows [F][max_period + 1] in the caller's clip order that the next analyze call's frame kernel
+    // stores in place of its own difference function (armed for one call, like `inject`; never both)
+    struct InjectD { bool armed = false; int64_t F = 0; DevBuf d; } inject_d;
     uint32_t chunk_gen = 0;                   // generation of the chunk flags of a persistent Viterbi launch
     int test_drop_signal = -1;
     // The single Viterbi launch of a balanced pass and its fall-back (run_with_recovery, aegis_api.hip)

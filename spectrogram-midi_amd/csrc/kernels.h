@@ -161,7 +161,9 @@ struct PassParams {
     double f0_unvoiced;                  // what an unvoiced frame's f0 reads: NaN (librosa.pyin fill_na) or 0.0 (np.nan_to_num)
 };
 
-void launch_frame(const PassParams &p, const DevTables &t, hipStream_t s);
+// inject_d (aegis_debug_set_difference): rows [out_total][max_period + 1] that replace the difference function where the kernel
+// stores it, by a kernel instantiation of its own; NULL: the shipping kernel
+void launch_frame(const PassParams &p, const DevTables &t, hipStream_t s, const double *inject_d = nullptr);
 bool frame_cmnd_supported(int max_period);
 int frame_batch_fpw(int max_period);        // frames per frame_yin workgroup of a launch that selects >= 4096 frames (smaller launches: 2)
 int trough_row_doubles_host(int n_lags);    // doubles of a dfn row that holds a frame's trough list (PassParams::troughs)   // the frame kernel's LDS holds the CMND rows of a workgroup's frames (PassParams::cmnd_in_frame)

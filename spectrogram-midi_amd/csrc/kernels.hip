@@ -251,7 +251,13 @@ __device__ long long g_frm_dbg[24];
 #else
 #define FRM_TICK(k)
 #endif
-__global__ __launch_bounds__(256, 2) void frame_yin_kernel(PassParams p, DevTables tb, int frames_per_wg, int en_stride) {
+// INJECT (aegis_debug_set_difference, a test hook): the difference function is not stored but REPLACED, where it is stored,
+// by the caller's row of the frame's output index (inj [out_total][max_period + 1]); everything else runs as always.  The
+// shipping kernel is the INJECT = false instantiation, which holds no trace of the hook (inj is NULL and never read); the
+// INJECT = true one is launched by an armed call only.
+template <bool INJECT>
+__global__ __launch_bounds__(256, 2) void frame_yin_kernel(PassParams p, DevTables tb, int frames_per_wg, int en_stride,
+                                                           const double *__restrict__ inj) {
 #if defined(AEGIS_ABLATE) && (AEGIS_ABLATE & 128)
     long long facc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, flast = clock64();
 #endif
@@ -413,6 +419,7 @@ __global__ __launch_bounds__(256, 2) void frame_yin_kernel(PassParams p, DevTabl
     for (int pr = 0; pr < nfr; pr += 2) {
         double2 P[2][5];
         int64_t fidx[2] = {0, 0};
+        int64_t fout[2] = {0, 0};             // (INJECT only) output index of each frame: the caller's rows are in output order
         bool flive[2] = {false, false};
         int fclip[2] = {0, 0};
 #pragma unroll
@@ -424,6 +431,7 @@ __global__ __launch_bounds__(256, 2) void frame_yin_kernel(PassParams p, DevTabl
             const int c = geo.c;
             const int64_t f = geo.f, fo = geo.o;
             fidx[h] = f; flive[h] = live; fclip[h] = c;
+            if constexpr (INJECT) fout[h] = fo;
             if (tid == 0) frow[pr + h] = live ? f : -1;
 #pragma unroll
             for (int r = 0; r < 8; ++r) xs[tid + r * 256] = nx[r];
@@ -639,8 +647,13 @@ __global__ __launch_bounds__(256, 2) void frame_yin_kernel(PassParams p, DevTabl
                     double a0 = zz.x * (1.0 / 8192.0), a1 = -zz.y * (1.0 / 8192.0);      // 1/2048 of the transform, 1/4 of P (see A2, B2)
                     if (fabs(a0) < 1e-6) a0 = 0.0;
                     if (fabs(a1) < 1e-6) a1 = 0.0;
-                    if (flive[0]) d0[tau] = (double)es[0][u] - 2.0 * a0;
-                    if (flive[1]) d1[tau] = (double)es[1][u] - 2.0 * a1;
+                    if constexpr (INJECT) {
+                        if (flive[0]) d0[tau] = inj[fout[0] * (int64_t)(mp + 1) + tau];
+                        if (flive[1]) d1[tau] = inj[fout[1] * (int64_t)(mp + 1) + tau];
+                    } else {
+                        if (flive[0]) d0[tau] = (double)es[0][u] - 2.0 * a0;
+                        if (flive[1]) d1[tau] = (double)es[1][u] - 2.0 * a1;
+                    }
                 }
             }
         } else {
@@ -658,7 +671,8 @@ __global__ __launch_bounds__(256, 2) void frame_yin_kernel(PassParams p, DevTabl
                 float e = row[tau];
                 if (fabsf(e) < 1e-6f) e = 0.0f;
                 const float esum = en0 + e;
-                drow[tau] = (double)esum - 2.0 * a;
+                if constexpr (INJECT) drow[tau] = inj[fout[h] * (int64_t)(mp + 1) + tau];
+                else drow[tau] = (double)esum - 2.0 * a;
             }
         }
         }
@@ -1530,7 +1544,10 @@ void launch_stream_gather(const StreamCtl *ctl, const float *rms, const double *
 // launch wrappers
 // ------------------------------------------------------------------------------------------
 hipError_t viterbi_configure() {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(frame_yin_kernel),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(frame_yin_kernel<false>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e != hipSuccess) return e;
+    e = hipFuncSetAttribute(reinterpret_cast<const void *>(frame_yin_kernel<true>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) return e;
     e = hipFuncSetAttribute(reinterpret_cast<const void *>(pyin_obs_kernel),
@@ -1556,7 +1573,7 @@ bool frame_cmnd_supported(int max_period) {
         if ((size_t)(fpw / 2) * rs * 8 + 64 > kFrameLdsFixed) return false;
     return true;
 }
-void launch_frame(const PassParams &p, const DevTables &t, hipStream_t s) {
+void launch_frame(const PassParams &p, const DevTables &t, hipStream_t s, const double *inject_d) {
     if (p.n_sel == 0 || !(p.stages & 0xFu)) return;
     const int stride = frame_en_stride(p.max_period);
     // the running-energy prologue is one serial walk per workgroup, so small launches (streaming pushes) take a pair each
@@ -1565,7 +1582,9 @@ void launch_frame(const PassParams &p, const DevTables &t, hipStream_t s) {
     // AEGIS_FRAME_LDS_MIN=<bytes> (experiment knob): ask for at least that much LDS, e.g. 100000 keeps one workgroup per CU
     static const size_t lds_min = [] { const char *e = std::getenv("AEGIS_FRAME_LDS_MIN"); return e ? (size_t)std::atol(e) : (size_t)0; }();
     lds = std::max(lds, std::min<size_t>(lds_min, 160 * 1024));
-    hipLaunchKernelGGL(frame_yin_kernel, dim3((unsigned)((p.n_sel + fpw - 1) / fpw)), dim3(256), lds, s, p, t, fpw, stride);
+    const dim3 grid((unsigned)((p.n_sel + fpw - 1) / fpw));
+    if (inject_d) hipLaunchKernelGGL(frame_yin_kernel<true>, grid, dim3(256), lds, s, p, t, fpw, stride, inject_d);
+    else hipLaunchKernelGGL(frame_yin_kernel<false>, grid, dim3(256), lds, s, p, t, fpw, stride, static_cast<const double *>(nullptr));
 }
 // LDS doubles of a pyin_obs workgroup: the tables every wave shares (TN) and one wave's rows (YN + UN)
 struct ObsLds { int TN, per_wave; };

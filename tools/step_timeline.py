@@ -17,7 +17,7 @@ def main(path):
     step = rows[(dec[-2] + 1 if len(dec) > 1 else 0):dec[-1] + 1]
     t0 = int(step[0]["Start_Timestamp"])
     for r in step:
-        name = r["Kernel_Name"].split("(")[0].replace("void ", "").replace("aegis::", "")
+        name = r["Kernel_Name"].split("(")[0].split("<")[0].replace("void ", "").replace("aegis::", "")
         if name == "chunk_signal_kernel":
             continue
         name = SHORT.get(name, "viterbi" if "viterbi" in name else name)
