@@ -819,6 +819,19 @@ __device__ __forceinline__ int wave_min_i32(int v) {   // uniform result
     v = dpp_imin<0x143, 0xc>(v);   // row_bcast:31
     return __builtin_amdgcn_readlane(v, 63);
 }
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ unsigned dpp_or(unsigned v) {
+    return v | (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, CTRL, ROW_MASK, 0xf, false);
+}
+__device__ __forceinline__ unsigned wave_or_u32(unsigned v) {   // uniform result
+    v = dpp_or<0x111, 0xf>(v);
+    v = dpp_or<0x112, 0xf>(v);
+    v = dpp_or<0x114, 0xf>(v);
+    v = dpp_or<0x118, 0xf>(v);
+    v = dpp_or<0x142, 0xa>(v);
+    v = dpp_or<0x143, 0xc>(v);
+    return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
+}
 
 // One frame per wave; a workgroup is up to 8 waves that share ONE copy of the scipy tables in LDS (16 waves per CU instead
 // of the 10 a private copy allowed) and walk `frames_per_wave` consecutive frames each.  The waves never exchange data: after
@@ -1021,7 +1034,10 @@ __global__ __launch_bounds__(512, 4) void pyin_obs_kernel(PassParams p, DevTable
         if (K > 0) {
             int jk[MAXR];
             double acc[MAXR];
-            int jmin = 101;
+            // the 100 Beta masses, two per lane (lane l: beta[l] and beta[64 + l]): requested here, taken out of the lanes
+            // with v_readlane in the prior loop below.  Reloaded per frame: held across the wave's frames the four
+            // registers cost one more spilled register.
+            const double blo = beta_s[lane], bhi = beta_s[min(64 + lane, 99)];     // (lanes 36 .. 63 of bhi are never taken out)
     #pragma unroll
             for (int q = 0; q < MAXR; ++q) {
                 jk[q] = 101; acc[q] = 0.0;
@@ -1039,11 +1055,9 @@ __global__ __launch_bounds__(512, 4) void pyin_obs_kernel(PassParams p, DevTable
                         while (g < 100 && !(h < thr(g + 1))) ++g;
                         while (g > 0 && h < thr(g)) --g;
                         jk[q] = g;
-                        jmin = min(jmin, g);
                     }
                 }
             }
-            jmin = wave_min_i32(jmin);
             OBS_TICK(4)
 
             // probs[k] = sum_j [h_k < thr_{j+1}] * boltzmann.pmf(pos_k(j); 2, n_j) * beta_probs[j],
@@ -1051,39 +1065,87 @@ __global__ __launch_bounds__(512, 4) void pyin_obs_kernel(PassParams p, DevTable
             // The set of troughs below threshold j only changes where j passes some trough's first
             // threshold, so the prior is rebuilt at those change points only; inside a stretch every
             // j still contributes its own rounded product, which keeps the sum bit-identical.
-            const unsigned long long lt_mask = (1ull << lane) - 1ull;
-            int j = jmin;
-            while (j < 100) {
-                unsigned long long M[MAXR];
-                int nj = 0, nxt = 100;
+            //
+            // No LDS round trip per threshold, and no reduction per change point:
+            //  - beta[jj] comes out of blo / bhi with v_readlane on the uniform jj (as prq does further down);
+            //  - the change points are the distinct first-threshold indices below 100.  They are gathered ONCE per frame
+            //    into a 100-bit set in scalar registers (one bit per index, an OR over the wave), and the end of every
+            //    stretch is the next set bit: scalar work, where a wave_min_i32 chain per change point used to be;
+            //  - a change point's table reads -- bfact[nj] and every round's bexp[...], unmasked: a lane that is not below
+            //    the threshold reads a neighbour's entry and drops it -- go out together and are waited for once;
+            //  - the two-round instance rebuilds the prior ONE STRETCH AHEAD: the change point at nxt is worked out and
+            //    its reads are issued before the threshold loop of [j, nxt) and taken over after it, so its round trips
+            //    run under the add chain (fact / e are the second prior).  The eight-round instance (under 2 % of the
+            //    frames) keeps the plain order.
+            // Assembly of both instances (hipcc -O3 -ffp-contract=off --offload-arch=gfx950 --cuda-device-only -S): the
+            // per-threshold loops are v_readlane x2, s_add, s_cmp, v_mul_f64 / v_add_f64 per round and the back-branch;
+            // from the last ds_read of a change point to the back-branch of its stretch's loops there is no ds_read and
+            // no s_waitcnt lgkmcnt.
+            constexpr bool AHEAD = MAXR == 2;
+            const int blo_l = __double2loint(blo), blo_h = __double2hiint(blo), bhi_l = __double2loint(bhi), bhi_h = __double2hiint(bhi);
+            unsigned long long left_lo, left_hi;        // change points not yet taken: indices 0 .. 63, 64 .. 99 (uniform)
+            {
+                unsigned w[4] = {0u, 0u, 0u, 0u};
     #pragma unroll
                 for (int q = 0; q < MAXR; ++q) {
-                    M[q] = 0ull;
-                    if (q < rounds) {
-                        M[q] = __ballot(jk[q] <= j);
-                        nj += __popcll(M[q]);
-                        if (jk[q] > j) nxt = min(nxt, jk[q]);
-                    }
+                    const unsigned bit = jk[q] < 100 ? 1u << (jk[q] & 31) : 0u;
+    #pragma unroll
+                    for (int i = 0; i < 4; ++i) w[i] |= (jk[q] >> 5) == i ? bit : 0u;
                 }
-                nxt = wave_min_i32(nxt);
-                const double fact = bfact[nj];
-                double prior[MAXR];
+    #pragma unroll
+                for (int i = 0; i < 4; ++i) w[i] = wave_or_u32(w[i]);
+                left_lo = ((unsigned long long)w[1] << 32) | w[0];
+                left_hi = ((unsigned long long)w[3] << 32) | w[2];
+            }
+            auto take_next = [&]() {                    // the lowest change point left (100 when none), taken out of the set
+                const bool in_lo = left_lo != 0ull;
+                const unsigned long long m = in_lo ? left_lo : left_hi, rest = m & (m - 1ull);
+                const int r = m ? (in_lo ? 0 : 64) + (int)__builtin_ctzll(m) : 100;
+                left_lo = in_lo ? rest : 0ull;
+                left_hi = in_lo ? left_hi : rest;
+                return r;
+            };
+            // the change point at threshold j0: where its stretch ends, and the pieces of its prior (jk is 101 on a
+            // lane without a trough and in a round the frame does not have: those ballots are empty).  j0 == 100 asks
+            // for nothing that is used, and stays inside the tables (nj <= K).
+            auto change = [&](int j0, int &nxt, double &fact, double (&e)[MAXR]) {
+                unsigned long long M[MAXR];
+                int nj = 0;
+    #pragma unroll
+                for (int q = 0; q < MAXR; ++q) {
+                    M[q] = __ballot(jk[q] <= j0);
+                    nj += __popcll(M[q]);
+                }
+                fact = bfact[nj];
                 int before = 0;
     #pragma unroll
                 for (int q = 0; q < MAXR; ++q) {
-                    prior[q] = 0.0;
-                    if (q < rounds) {
-                        if (jk[q] <= j) prior[q] = fact * bexp[before + __popcll(M[q] & lt_mask)];
-                        before += __popcll(M[q]);
-                    }
+                    e[q] = bexp[before + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(M[q] >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)M[q], 0u))];
+                    before += __popcll(M[q]);
                 }
-                for (int jj = j; jj < nxt; ++jj) {
-                    const double bj = beta_s[jj];
+                nxt = take_next();
+            };
+            auto stretch = [&](const double (&prior)[MAXR], int lo_l, int lo_h, int jj, int jend, int off) {
+                for (; jj < jend; ++jj) {
+                    const double bj = __hiloint2double(__builtin_amdgcn_readlane(lo_h, jj - off), __builtin_amdgcn_readlane(lo_l, jj - off));
     #pragma unroll
-                    for (int q = 0; q < MAXR; ++q)
-                        if (q < rounds) acc[q] = acc[q] + prior[q] * bj;
+                    for (int q = 0; q < MAXR; ++q)      // (a round the frame does not have adds +0.0 * bj to +0.0)
+                        if (MAXR == 2 || q < rounds) acc[q] = acc[q] + prior[q] * bj;
                 }
-                j = nxt;
+            };
+            int j = take_next(), nxt = 100;             // (the smallest first-threshold index of the frame)
+            double fact = 0.0, e[MAXR];
+            change(j, nxt, fact, e);
+            while (j < 100) {
+                double prior[MAXR];
+    #pragma unroll
+                for (int q = 0; q < MAXR; ++q) prior[q] = jk[q] <= j ? fact * e[q] : 0.0;
+                const int j1 = nxt;
+                if (AHEAD) change(j1, nxt, fact, e);
+                stretch(prior, blo_l, blo_h, j, min(j1, 64), 0);
+                stretch(prior, bhi_l, bhi_h, max(j, 64), j1, 64);
+                if (!AHEAD) change(j1, nxt, fact, e);
+                j = j1;
             }
 
             OBS_TICK(5)
