@@ -199,6 +199,31 @@ int aegis_chroma_cqt(aegis_handle *h, const float *const *pcm, const int64_t *n_
                      int32_t n_bins, int32_t bins_per_octave, double fmin, double filter_scale, int32_t n_chroma,
                      const int32_t *bin_class, float *chroma_out);
 
+/* Filter banks.  A bank (the atoms of one (n_bins, bins_per_octave, fmin, filter_scale), tens of MB for chroma_cqt's 252 bins)
+ * is built on the host and uploaded the first time a call names it, and kept: the handle holds the 8 most recently used
+ * banks (AEGIS_CQT_BANKS = 1..32 in the environment at aegis_create), so calls that alternate between a few tunings
+ * stop rebuilding.  The least recently used bank is freed, after a device synchronisation, when a new one needs its place;
+ * a bank that cannot be allocated frees every other one and tries once more.  A call's output does not depend on what the
+ * cache holds.  aegis_get_param: "cqt_bank_builds" (banks built since create), "cqt_banks" (held now), "cqt_bank_cap",
+ * "cqt_bank_bytes" and "cqt_bank_build_us" (device bytes, and host build + upload time, of the last bank built). */
+
+/* librosa.estimate_tuning(y=y, sr=sr, bins_per_octave=...) as cqt(tuning=None) calls it, for n_clips clips (float32 mono
+ * PCM in host memory at the handle's rate) in one call: piptrack on a 2048-point STFT at hop 512 (centre padded, periodic
+ * Hann; independent of the handle's hop) -- local maxima above a tenth of the frame maximum between 150 Hz and
+ * min(4000 Hz, sr / 2), refined by parabolic interpolation --, the peaks at or above the median peak magnitude, and the
+ * most populated of the 100 cells of width 0.01 of their deviation from the equal-tempered grid.  All arithmetic follows
+ * the reference's float32 / float64 steps; counts are integers, and nothing depends on the order in which the device
+ * runs workgroups.  What may differ from a host evaluation is the last bit of log2f and of a float32-rounded FFT output,
+ * i.e. a count moving by one between neighbouring cells.
+ *   tuning_out   f64[n_clips]        fractions of a bin, in [-0.5, 0.5); 0.0 for a clip without peaks
+ *   counts_out   NULL or i32[n_clips][100]  the histogram the answer was read from (tuning = edge of its first arg-max;
+ *                                    the 101 edges: aegis_get_table "tuning_edges")
+ *   n_peaks_out  NULL or i64[n_clips]  peaks found before the median cut
+ * Only n_fft = 2048 is built (anything else: AEGIS_ERR_INVALID).  Kernel times: "tuning_peaks", "tuning_select",
+ * "tuning_hist" of aegis_last_kernel_ms.  Blocking. */
+int aegis_estimate_tuning(aegis_handle *h, const float *const *pcm, const int64_t *n_samples, int32_t n_clips,
+                          int32_t bins_per_octave, double *tuning_out, int32_t *counts_out, int64_t *n_peaks_out);
+
 /* --- incremental analysis of one clip (BASELINE.json configs[4]; the reference has no streaming path:
  * financial_app_realtime.py analyses whole files).  Samples are pushed in any chunk sizes; every frame whose
  * centred 2048-sample window is complete is analysed at once (mel, YIN, observation) and the Viterbi advances
@@ -409,7 +434,8 @@ int aegis_synth_adsr(aegis_handle *h, int32_t sample_rate, int32_t n_clips, cons
  * "beta_probs" f64[100], "beta_cumsum" f64[101], "boltz_fact" f64[n], "boltz_exp" f64[n],
  * "log_trans_band" f64[4*n_cls*width], "log_trans_pack" f64[2*(3H^2+3H+2)] (H = (width-1)/2: the band table
  * without its duplicate (v,v') blocks and unreachable edge-row entries, as the Viterbi kernel keeps it in LDS),
- * "freqs" f64[n_pitch_bins], "twiddle" f64[2*n_fft].
+ * "freqs" f64[n_pitch_bins], "twiddle" f64[2*n_fft], "tuning_edges" f64[101] (np.linspace(-0.5, 0.5, 101), the cell
+ * edges of aegis_estimate_tuning).
  * Returns the element count (or a negative code); copies min(count, cap) elements. */
 int64_t aegis_get_table(const aegis_handle *h, const char *name, void *dst, int64_t cap);
 

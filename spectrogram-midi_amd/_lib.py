@@ -71,7 +71,7 @@ EXPORTS = ("aegis_abi_version", "aegis_create", "aegis_destroy", "aegis_last_err
            "aegis_extract_events", "aegis_render_smf", "aegis_events_last_error", "aegis_debug_plan",
            "aegis_analyze_pcm", "aegis_pcm_samples_for", "aegis_resample_taps", "aegis_stream_push_commit",
            "aegis_synth_parse_smf", "aegis_synth_samples_for", "aegis_synth_adsr", "aegis_debug_rake_columns",
-           "aegis_debug_set_observations", "aegis_debug_set_difference")
+           "aegis_debug_set_observations", "aegis_debug_set_difference", "aegis_estimate_tuning")
 
 _lib = None
 
@@ -142,6 +142,9 @@ def load():
     lib.aegis_chroma_cqt.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.c_int32,
                                      C.c_double, C.c_double, C.c_int32, C.c_void_p, C.c_void_p]
     lib.aegis_chroma_cqt.restype = C.c_int
+    lib.aegis_estimate_tuning.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int32, C.c_int32,
+                                          C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.aegis_estimate_tuning.restype = C.c_int
     lib.aegis_set_table.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64]
     lib.aegis_set_table.restype = C.c_int
     lib.aegis_get_table.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64]
@@ -577,6 +580,24 @@ class Handle:
             res.append(out[o:o + Fc * n_chroma].reshape(n_chroma, Fc).copy())
             o += Fc * n_chroma
         return res
+
+    def estimate_tuning(self, clips, bins_per_octave=36, want_counts=False):
+        """aegis_estimate_tuning: librosa.estimate_tuning of every clip in ONE device call -> list of floats (fractions of a
+        bin, in [-0.5, 0.5); 0.0 for a clip without peaks).  want_counts: (tunings, counts int32 [n, 100], n_peaks int64 [n])
+        -- the histogram each answer is the first arg-max of, and the peaks found before the median cut."""
+        clips = [np.ascontiguousarray(c, dtype=np.float32) for c in clips]
+        n = len(clips)
+        tun = np.zeros(n, np.float64)
+        counts = np.zeros((n, 100), np.int32) if want_counts else None
+        peaks = np.zeros(n, np.int64) if want_counts else None
+        if n:
+            ptrs = (C.c_void_p * n)(*[c.ctypes.data for c in clips])
+            lens = (C.c_int64 * n)(*[len(c) for c in clips])
+            self._check(self.lib.aegis_estimate_tuning(self._h, ptrs, lens, n, int(bins_per_octave), tun.ctypes.data,
+                                                       counts.ctypes.data if want_counts else None,
+                                                       peaks.ctypes.data if want_counts else None))
+        out = [float(t) for t in tun]
+        return (out, counts, peaks) if want_counts else out
 
     def cqt_device(self, d_pcm_ptr, sample_offsets, d_out_ptr, n_bins=84, bins_per_octave=12, fmin=32.70319566257483,
                    filter_scale=1.0, stream=None, sync=True):

@@ -12,11 +12,19 @@ on the machines this package runs on.  A candidate whose MIDI cannot be rendered
 The 27 candidates of a stage are independent, so a stage extracts all their events first, renders them in ONE synth batch
 (`synthesize_midi_adsr_batch`, csrc/synth.hip) and then scores them one by one through `similarity._calculate_similarity`
 (mel on the frame kernel, chroma on the MFMA CQT).  Scoring candidate by candidate keeps every score exactly what the
-three public pieces give when they are called in a plain loop."""
+three public pieces give when they are called in a plain loop.
+
+`scoring="batch"` (opt-in) reads the original once, takes the stage's synth batch as sample arrays and scores the whole
+stage through `similarity.score_batch`: one mel call and one device tuning call per stage, one chroma call per distinct
+tuning, the original's features once per distinct length.  Visiting order, the strict `>`, skips, casts and progress calls
+are the loop's; a score may differ from the loop's only where the device's tuning estimate of a clip differs from the
+host's (a near-tie of its histogram)."""
 import io
 
-from . import _lib
-from .similarity import _calculate_similarity          # re-exported: auto_matcher._calculate_similarity, as in the reference
+import numpy as np
+
+from . import _lib, audio_io
+from .similarity import _calculate_similarity, score_batch    # _calculate_similarity re-exported, as in the reference
 from .synthesizer import synthesize_midi_adsr_batch
 
 __all__ = ["auto_match_parameters", "_calculate_similarity"]
@@ -57,7 +65,28 @@ class _Handles:
             self._own.close()
 
 
-def _stage(grid, fine, original_audio_path, engine, raw_data, sample_rate, progress_callback, best_score, best_params, handle):
+def _batch_scores(handle, y_orig, arrays):
+    """score_batch over a stage's int16 renders (None where a candidate has none): a score per candidate, None where it
+    could not be scored.  The samples are read_wav_bytes' (int16 / 32768 in float32).  If the batch as a whole raises, the
+    candidates are scored one by one and the failing ones are skipped alone."""
+    idx = [i for i, a in enumerate(arrays) if a is not None and len(a)]
+    ys = [arrays[i].astype(np.float32) / np.float32(32768.0) for i in idx]
+    out = [None] * len(arrays)
+    try:
+        for i, sc in zip(idx, score_batch(handle, y_orig, ys)):
+            out[i] = sc
+    except Exception as e:                         # noqa: BLE001
+        print(f"  [AutoMatcher] batch scoring failed ({e}): scoring candidate by candidate")
+        for i, y in zip(idx, ys):
+            try:
+                out[i] = score_batch(handle, y_orig, [y])[0]
+            except Exception as e2:                # noqa: BLE001
+                print(f"  [AutoMatcher] candidate {i} failed: {e2}")
+    return out
+
+
+def _stage(grid, fine, original_audio_path, engine, raw_data, sample_rate, progress_callback, best_score, best_params, handle,
+           y_orig=None):
     """One grid of the search: (best_score, best_params) after its candidates, visited in the reference's order."""
     cast = int if fine else (lambda v: v)
     message = "세밀 탐색 중... ({}/{})" if fine else "탐색 중... ({}/{})"        # the reference's progress texts
@@ -83,14 +112,21 @@ def _stage(grid, fine, original_audio_path, engine, raw_data, sample_rate, progr
     if not midis:
         return best_score, best_params
     handle = handle.get()
-    wavs = synthesize_midi_adsr_batch(midis, preset=SYNTH_PRESET, sample_rate=sample_rate, handle=handle)
+    batch = y_orig is not None
+    wavs = synthesize_midi_adsr_batch(midis, preset=SYNTH_PRESET, sample_rate=sample_rate, handle=handle, as_arrays=batch)
     if not wavs:
         return best_score, best_params
-    for (conf, min_dur, sustain), wav in zip(kept, wavs):
-        if not wav:
+    scores = _batch_scores(handle, y_orig, wavs) if batch else None
+    for k, ((conf, min_dur, sustain), wav) in enumerate(zip(kept, wavs)):
+        if wav is None or not len(wav):
             continue
         try:
-            score = _calculate_similarity(original_audio_path, wav, sample_rate, handle=handle)
+            if batch:
+                if scores[k] is None:
+                    continue
+                score = scores[k]
+            else:
+                score = _calculate_similarity(original_audio_path, wav, sample_rate, handle=handle)
             print(f"  conf={conf:.2f}, dur={min_dur}, sus={sustain} -> score={score:.3f}")
             if score > best_score:
                 best_score = score
@@ -100,20 +136,31 @@ def _stage(grid, fine, original_audio_path, engine, raw_data, sample_rate, progr
     return best_score, best_params
 
 
-def auto_match_parameters(original_audio_path, engine, raw_data, sample_rate=44100, progress_callback=None):
+def auto_match_parameters(original_audio_path, engine, raw_data, sample_rate=44100, progress_callback=None, scoring="loop"):
     """-> {'confidence_threshold', 'min_note_duration_ms', 'sustain_ms', 'score'}, or None when no candidate could be
-    scored.  `engine`: an AegisEngine; `raw_data`: what its audio_to_midi returned for the original audio."""
+    scored.  `engine`: an AegisEngine; `raw_data`: what its audio_to_midi returned for the original audio.
+    scoring: "loop" (default) scores candidate by candidate through _calculate_similarity; "batch" scores a stage's
+    candidates in one similarity.score_batch call against the original read once (see the module text)."""
+    if scoring not in ("loop", "batch"):
+        raise ValueError('scoring must be "loop" or "batch"')
     print("[AutoMatcher] auto parameter matching: coarse grid (27 candidates)")
     handles = _Handles(engine, sample_rate)
     try:
+        y_orig = None
+        if scoring == "batch":
+            try:
+                y_orig = audio_io.read_wav(original_audio_path, sample_rate, duration=30)
+            except Exception as e:                 # noqa: BLE001 -- the loop scores 0.0 for every candidate then
+                print(f"[AutoMatcher] similarity failed: {e}")
+                y_orig = np.zeros(0, np.float32)
         best_score, best_params = _stage(COARSE_GRID, False, original_audio_path, engine, raw_data, sample_rate,
-                                         progress_callback, -1.0, None, handles)
+                                         progress_callback, -1.0, None, handles, y_orig)
         if not best_params:
             print("[AutoMatcher] no valid result")
             return None
         print(f"[AutoMatcher] coarse best: {best_params}, score={best_score:.3f}")
         best_score, best_params = _stage(_fine_grid(best_params), True, original_audio_path, engine, raw_data, sample_rate,
-                                         progress_callback, best_score, best_params, handles)
+                                         progress_callback, best_score, best_params, handles, y_orig)
         print(f"[AutoMatcher] final best: {best_params}, score={best_score:.3f}")
         return {**best_params, "score": best_score}
     finally:

@@ -1,6 +1,8 @@
 // Constant-Q entries of libaegis_hip.so (aegis_cqt, aegis_chroma_cqt, aegis_cqt_device) and aegis_rake_patterns.
 #include "aegis_internal.h"
 
+#include <chrono>
+
 using namespace aegis;
 
 extern "C" {
@@ -32,24 +34,72 @@ int aegis_rake_patterns(aegis_handle *h, const float *S_dB, int32_t n_mels, int6
     } catch (...) { return abi_fail(h); }
 }
 
-// the bank of (n_bins, bins_per_octave, fmin, filter_scale), built and uploaded on first use
+// Frees the least recently used banks until at most `keep` are left.  A kernel enqueued by an earlier call (on the handle's
+// stream, or on a caller's with sync == 0) may still read a bank: the device is synchronised before the first one goes.
+static int cqt_evict_locked(aegis_handle *h, size_t keep) {
+    if (h->cqt_banks.size() <= keep) return AEGIS_OK;
+    HIPCHK(h, hipDeviceSynchronize());
+    while (h->cqt_banks.size() > keep) {
+        if (h->cqt_banks.back().bank.dev) (void)hipFree(h->cqt_banks.back().bank.dev);
+        h->cqt_banks.pop_back();
+    }
+    return AEGIS_OK;
+}
+
+// The bank of (n_bins, bins_per_octave, fmin, filter_scale) at the front of h->cqt_banks: found among the banks built so
+// far, or built on the host and uploaded (the least recently used one leaves when the cache is full).  A refused bank
+// touches nothing.
 static int cqt_bank_locked(aegis_handle *h, int32_t &n_bins, int32_t &bins_per_octave, double &fmin, double &filter_scale, hipStream_t s) {
     if (n_bins == 0) n_bins = 84;
     if (bins_per_octave == 0) bins_per_octave = 12;
     if (!(fmin > 0)) fmin = 32.70319566257483;            // note_to_hz('C1')
     if (!(filter_scale > 0)) filter_scale = 1.0;
-    CqtBank &b = h->cqt_bank;
-    if (b.n_bins != n_bins || b.bins_per_octave != bins_per_octave || b.fmin != fmin || b.filter_scale != filter_scale || !b.dev) {
-        HIPCHK(h, hipStreamSynchronize(s));
-        if (b.dev) { (void)hipFree(b.dev); b.dev = nullptr; }
-        const char *msg = build_cqt_bank(b, h->tab.sr, n_bins, fmin, bins_per_octave, filter_scale);
-        if (msg[0]) { h->err = msg; b.n_bins = 0; return AEGIS_ERR_INVALID; }
-        // + 64 KiB: the slide kernel refills a tile's register queue unconditionally, so a wave's last groups request up to
-        // kSlotDepth KiB past its stream (never used)
-        HIPCHK(h, hipMalloc(reinterpret_cast<void **>(&b.dev), b.data.size() * 4 + 65536));
-        HIPCHK(h, hipMemset(reinterpret_cast<char *>(b.dev) + b.data.size() * 4, 0, 65536));
-        HIPCHK(h, hipMemcpy(b.dev, b.data.data(), b.data.size() * 4, hipMemcpyHostToDevice));
+    auto &banks = h->cqt_banks;
+    for (auto it = banks.begin(); it != banks.end(); ++it) {
+        const CqtBank &b = it->bank;
+        if (b.n_bins == n_bins && b.bins_per_octave == bins_per_octave && b.fmin == fmin && b.filter_scale == filter_scale && b.dev) {
+            banks.splice(banks.begin(), banks, it);
+            return AEGIS_OK;
+        }
     }
+    const auto t0 = std::chrono::steady_clock::now();
+    aegis_handle::CachedBank nb;
+    const char *msg = build_cqt_bank(nb.bank, h->tab.sr, n_bins, fmin, bins_per_octave, filter_scale);
+    if (msg[0]) { h->err = msg; return AEGIS_ERR_INVALID; }
+    int rc;
+    if ((rc = cqt_evict_locked(h, (size_t)h->cqt_bank_cap - 1)) != AEGIS_OK) return rc;
+    // + 64 KiB: the slide kernel refills a tile's register queue unconditionally, so a wave's last groups request up to
+    // kSlotDepth KiB past its stream (never used)
+    nb.bytes = nb.bank.data.size() * 4 + 65536;
+    auto alloc = [&]() -> hipError_t {
+        if (h->fail_allocs > 0) { --h->fail_allocs; return hipErrorOutOfMemory; }      // test hook, as in grow_buf
+        return hipMalloc(reinterpret_cast<void **>(&nb.bank.dev), nb.bytes);
+    };
+    hipError_t e = alloc();
+    if (e != hipSuccess) {                                 // make room: every other bank goes, then one more try
+        (void)hipGetLastError();
+        nb.bank.dev = nullptr;
+        if ((rc = cqt_evict_locked(h, 0)) != AEGIS_OK) return rc;
+        e = alloc();
+    }
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        h->err = "hipMalloc(" + std::to_string(nb.bytes) + " bytes) for a CQT filter bank: " + hipGetErrorString(e);
+        return AEGIS_ERR_NOMEM;
+    }
+    hipError_t up = hipMemset(reinterpret_cast<char *>(nb.bank.dev) + nb.bank.data.size() * 4, 0, 65536);
+    if (up == hipSuccess) up = hipMemcpy(nb.bank.dev, nb.bank.data.data(), nb.bank.data.size() * 4, hipMemcpyHostToDevice);
+    if (up != hipSuccess) {
+        (void)hipFree(nb.bank.dev);
+        h->err = std::string("upload of a CQT filter bank: ") + hipGetErrorString(up);
+        return AEGIS_ERR_DEVICE;
+    }
+    std::vector<float>().swap(nb.bank.data);               // the kernels read the device copy only
+    banks.push_front(std::move(nb));
+    ++h->cqt_bank_builds;
+    h->cqt_bank_bytes = (int64_t)banks.front().bytes;
+    h->cqt_bank_build_us = (int64_t)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
+    (void)s;
     return AEGIS_OK;
 }
 
@@ -75,7 +125,7 @@ static int cqt_launch_locked(aegis_handle *h, const float *d_pcm, const int64_t 
     CqtArgs a{d_pcm, static_cast<const int64_t *>(h->q_soff.p), static_cast<const int64_t *>(h->q_foff.p), n_clips,
               foff[n_clips], h->tab.hop, d_out};
     drop_events(h);
-    begin_event(h, "cqt", s); launch_cqt(a, h->cqt_bank, static_cast<const int64_t *>(h->q_toff.p), toff[n_clips], s); end_event(h, s);
+    begin_event(h, "cqt", s); launch_cqt(a, h->cqt_banks.front().bank, static_cast<const int64_t *>(h->q_toff.p), toff[n_clips], s); end_event(h, s);
     HIPCHK(h, hipGetLastError());
     *total_frames = foff[n_clips];
     return AEGIS_OK;
@@ -180,6 +230,77 @@ int aegis_cqt_device(aegis_handle *h, const float *d_pcm, const int64_t *sample_
         HIPCHK(h, hipStreamSynchronize(s));
         if (h->profiling) collect_events(h);
     }
+    return AEGIS_OK;
+    } catch (...) { return abi_fail(h); }
+}
+
+/* see include/aegis_hip.h */
+int aegis_estimate_tuning(aegis_handle *h, const float *const *pcm, const int64_t *n_samples, int32_t n_clips,
+                          int32_t bins_per_octave, double *tuning_out, int32_t *counts_out, int64_t *n_peaks_out) {
+    try {
+    if (!h) return AEGIS_ERR_INVALID;
+    if (n_clips < 0 || (n_clips > 0 && (!pcm || !n_samples || !tuning_out))) { h->err = "null argument"; return AEGIS_ERR_INVALID; }
+    if (bins_per_octave < 1) { h->err = "bins_per_octave must be positive"; return AEGIS_ERR_INVALID; }
+    if (h->tab.n_fft != kTunFft) { h->err = "estimate_tuning: only n_fft = 2048 is built (the twiddle and window tables are the handle's)"; return AEGIS_ERR_INVALID; }
+    if (n_clips == 0) return AEGIS_OK;
+    DEVICE_ONLY(h);
+    std::lock_guard<std::mutex> lock(h->mu);
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    TuningArgs a{};
+    a.sr = h->tab.sr; a.bpo = bins_per_octave; a.n_clips = n_clips;
+    tuning_band(a.sr, &a.k_lo, &a.k_hi);
+    const int64_t per_frame = (a.k_hi - a.k_lo + 1) / 2;       // two adjacent bins cannot both be peaks
+    // geometry: [sample_off | frame_off | peak_off], n_clips + 1 entries each
+    const size_t m = (size_t)n_clips + 1;
+    std::vector<int64_t> geo(3 * m, 0);
+    int64_t *soff = geo.data(), *foff = soff + m, *poff = foff + m;
+    for (int i = 0; i < n_clips; ++i) {
+        if (n_samples[i] < 0 || (n_samples[i] > 0 && !pcm[i])) { h->err = "bad clip " + std::to_string(i); return AEGIS_ERR_INVALID; }
+        const int64_t frames = 1 + n_samples[i] / kTunHop;
+        soff[i + 1] = soff[i] + n_samples[i];
+        foff[i + 1] = foff[i] + frames;
+        poff[i + 1] = poff[i] + frames * per_frame;
+    }
+    if (foff[n_clips] >= ((int64_t)1 << 31)) { h->err = "estimate_tuning: too many frames for one call"; return AEGIS_ERR_INVALID; }
+    int rc;
+    const size_t peaks = (size_t)std::max<int64_t>(poff[n_clips], 1);
+    if ((rc = ensure(h, h->q_pcm, (size_t)std::max<int64_t>(soff[n_clips], 1) * 4)) != AEGIS_OK) return rc;
+    if ((rc = ensure(h, h->tn_meta, geo.size() * 8)) != AEGIS_OK) return rc;
+    if ((rc = ensure(h, h->tn_pitch, peaks * 4)) != AEGIS_OK) return rc;
+    if ((rc = ensure(h, h->tn_mag, peaks * 4)) != AEGIS_OK) return rc;
+    if ((rc = ensure(h, h->tn_count, (size_t)n_clips * 8)) != AEGIS_OK) return rc;
+    if ((rc = ensure(h, h->tn_median, (size_t)n_clips * 4)) != AEGIS_OK) return rc;
+    if ((rc = ensure(h, h->tn_cells, (size_t)n_clips * kTunCells * 4)) != AEGIS_OK) return rc;
+    if ((rc = ensure(h, h->tn_tuning, (size_t)n_clips * 8)) != AEGIS_OK) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->tn_meta.p, geo.data(), geo.size() * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemsetAsync(h->tn_count.p, 0, (size_t)n_clips * 8, s));
+    for (int i = 0; i < n_clips; ++i)
+        if (n_samples[i] > 0)
+            HIPCHK(h, hipMemcpyAsync(static_cast<float *>(h->q_pcm.p) + soff[i], pcm[i], n_samples[i] * 4, hipMemcpyHostToDevice, s));
+    a.pcm = static_cast<const float *>(h->q_pcm.p);
+    a.sample_off = static_cast<const int64_t *>(h->tn_meta.p);
+    a.frame_off = a.sample_off + m;
+    a.peak_off = a.frame_off + m;
+    a.n_frames = foff[n_clips];
+    a.hann = h->dt.hann; a.twiddle = h->dt.twiddle; a.edges = h->d_tuning_edges;
+    a.pitch = static_cast<float *>(h->tn_pitch.p); a.mag = static_cast<float *>(h->tn_mag.p);
+    a.n_peaks = static_cast<unsigned long long *>(h->tn_count.p);
+    a.median = static_cast<float *>(h->tn_median.p);
+    a.counts = static_cast<int32_t *>(h->tn_cells.p);
+    a.tuning = static_cast<double *>(h->tn_tuning.p);
+    drop_events(h);
+    begin_event(h, "tuning_peaks", s); launch_tuning_peaks(a, s); end_event(h, s);
+    begin_event(h, "tuning_select", s); launch_tuning_select(a, s); end_event(h, s);
+    begin_event(h, "tuning_hist", s); launch_tuning_hist(a, s); end_event(h, s);
+    HIPCHK(h, hipGetLastError());
+    std::vector<unsigned long long> np_host(n_peaks_out ? (size_t)n_clips : 0);
+    HIPCHK(h, hipMemcpyAsync(tuning_out, h->tn_tuning.p, (size_t)n_clips * 8, hipMemcpyDeviceToHost, s));
+    if (counts_out) HIPCHK(h, hipMemcpyAsync(counts_out, h->tn_cells.p, (size_t)n_clips * kTunCells * 4, hipMemcpyDeviceToHost, s));
+    if (n_peaks_out) HIPCHK(h, hipMemcpyAsync(np_host.data(), h->tn_count.p, (size_t)n_clips * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    for (size_t i = 0; i < np_host.size(); ++i) n_peaks_out[i] = (int64_t)np_host[i];
+    if (h->profiling) collect_events(h);
     return AEGIS_OK;
     } catch (...) { return abi_fail(h); }
 }

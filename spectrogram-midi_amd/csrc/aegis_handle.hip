@@ -162,6 +162,9 @@ int aegis_create(const aegis_config *cfg, aegis_handle **out) {
     if (const char *e = std::getenv("AEGIS_DEBUG_STAGES")) h->debug_stages = (e[0] == '1');
     if (const char *e = std::getenv("AEGIS_CMND_IN_FRAME")) h->cmnd_off = (e[0] == '0');
     if (const char *e = std::getenv("AEGIS_TROUGHS_IN_FRAME")) h->troughs_off = (e[0] == '0');
+    if (const char *e = std::getenv("AEGIS_CQT_BANKS")) { const int v = std::atoi(e); if (v >= 1 && v <= 32) h->cqt_bank_cap = v; }
+    h->tuning_edges.resize(kTunCells + 1);
+    tuning_edges(h->tuning_edges.data());
     if (c.device == -1) { *out = h; return AEGIS_OK; }   // host tables only
 
     int ndev = 0;
@@ -225,6 +228,7 @@ int aegis_create(const aegis_config *cfg, aegis_handle **out) {
         CRT(upload_table(h, t.twiddle, &tw));
         h->dt.twiddle = reinterpret_cast<const double2 *>(tw);
     }
+    CRT(upload_table(h, h->tuning_edges, &h->d_tuning_edges));
 #undef CRT
 #undef CRTHIP
     *out = h;
@@ -296,7 +300,8 @@ void aegis::destroy_now(aegis_handle *h) noexcept {
     for (hipEvent_t e : h->owned_events) (void)hipEventDestroy(e);
     T("free tables");
     for (void *p : h->table_allocs) (void)hipFree(p);
-    if (h->cqt_bank.dev) (void)hipFree(h->cqt_bank.dev);
+    for (auto &cb : h->cqt_banks) if (cb.bank.dev) (void)hipFree(cb.bank.dev);
+    h->cqt_banks.clear();
     T("free workspaces and staging");
     free_bufs(h->bufs);
     T("destroy streams");
@@ -410,6 +415,11 @@ int64_t aegis_get_param(const aegis_handle *h, const char *name) {
     if (n == "last_hybrid_step") return lp ? lp->hyb_S : 0;
     if (n == "last_persistent") return lp ? lp->persistent : 0;
     if (n == "pyin_init") return t.pyin_init;
+    if (n == "cqt_bank_builds") return h->cqt_bank_builds;
+    if (n == "cqt_banks") return (int64_t)h->cqt_banks.size();
+    if (n == "cqt_bank_cap") return h->cqt_bank_cap;
+    if (n == "cqt_bank_bytes") return h->cqt_bank_bytes;
+    if (n == "cqt_bank_build_us") return h->cqt_bank_build_us;
     // the launch rules at this geometry, from the host functions the launches themselves call
     if (n == "cmnd_in_frame") return cmnd_in_frame(h);
     if (n == "troughs_in_frame") return troughs_in_frame(h);
@@ -441,6 +451,7 @@ int64_t aegis_get_table(const aegis_handle *h, const char *name, void *dst, int6
     else if (n == "log_trans_pack") setd(t.log_trans_pack);
     else if (n == "freqs") setd(t.freqs);
     else if (n == "twiddle") setd(t.twiddle);
+    else if (n == "tuning_edges") setd(h->tuning_edges);
     else if (n == "mel_dense") { src = t.mel_dense.data(); count = (int64_t)t.mel_dense.size(); esz = 4; }
     else return AEGIS_ERR_INVALID;
     if (dst && cap > 0) std::memcpy(dst, src, (size_t)std::min(count, cap) * esz);

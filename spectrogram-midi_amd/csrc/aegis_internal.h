@@ -3,7 +3,7 @@
 //   aegis_api.hip     the batch pipeline (plan input, workspaces, analyze_device_locked, recovery, the analyze entries)
 //   aegis_handle.hip  create / destroy, profiling, tables, parameters, aegis_debug_plan / aegis_debug_fetch
 //   aegis_stream.hip  aegis_stream_* (graph capture, commit delivery)
-//   aegis_cqt.hip     CQT, chroma, aegis_rake_patterns
+//   aegis_cqt.hip     CQT, chroma, the filter-bank cache, aegis_estimate_tuning, aegis_rake_patterns
 //   aegis_trend.hip   aegis_trend, aegis_ghost_rsi
 //   aegis_synth.hip   aegis_synth_* (the ADSR soft-synth; kernels in synth.hip, the MIDI reader in synth_smf.cpp)
 #pragma once
@@ -13,6 +13,7 @@
 #include <cstdint>
 #include <cstring>
 #include <functional>
+#include <list>
 #include <map>
 #include <mutex>
 #include <string>
@@ -23,6 +24,7 @@
 #include "plan.h"
 #include "cqt.h"
 #include "tables.h"
+#include "tuning.h"
 
 // A grow-only device block.  It is freed by whoever's list ensure() entered it in (aegis_handle::bufs, aegis_stream::bufs):
 // a DevBuf member needs no other mention anywhere to be released.  PassParams and SplitCheck keep raw pointers into the
@@ -96,8 +98,18 @@ struct aegis_handle {
         std::vector<int64_t> last_flags;      // per clip of the call's last split pass (pass order: longest first): the verification's verdict bits
     } tsplit;
     aegis::PlanKnobs knobs;                   // scheduling knobs (plan.h), read from the environment at create
-    aegis::CqtBank cqt_bank;
+    // Filter banks built and uploaded so far, most recently used first (aegis_cqt.hip::cqt_bank_locked): at most
+    // cqt_bank_cap of them (8, or AEGIS_CQT_BANKS = 1..32 at create); the least recently used one is evicted.
+    struct CachedBank { aegis::CqtBank bank; size_t bytes = 0; };
+    std::list<CachedBank> cqt_banks;
+    int cqt_bank_cap = 8;
+    int64_t cqt_bank_builds = 0;              // banks built since create (aegis_get_param "cqt_bank_builds")
+    int64_t cqt_bank_bytes = 0, cqt_bank_build_us = 0;   // of the last build: device bytes, host build + upload time
     DevBuf q_pcm, q_soff, q_foff, q_toff, q_out, q_chroma, q_cls;
+    // aegis_estimate_tuning: the 101 histogram edges (host, and uploaded at create), geometry, peak lists, per-clip results
+    std::vector<double> tuning_edges;
+    const double *d_tuning_edges = nullptr;
+    DevBuf tn_meta, tn_pitch, tn_mag, tn_count, tn_median, tn_cells, tn_tuning;
     DevBuf t_x, t_off, t_a, t_b, t_c, t_d, t_e, t_i8, t_i64a, t_i64b;   // trend-filter staging
     DevBuf t_pa;                              // scratch of the fused pitch analysis: 12 rows of doubles + 1 of bytes
     DevBuf io_pcm, io_f0, io_voiced, io_vprob, io_rms, io_rake, io_sdb, io_bin, io_colmean;

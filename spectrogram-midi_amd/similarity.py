@@ -80,9 +80,19 @@ def estimate_tuning(y, sr=44100, bins_per_octave=36, n_fft=2048, resolution=0.01
 
 def chroma_cqt(handle, clips, n_chroma=12, n_octaves=7, bins_per_octave=36, fmin=_C1, tuning=None):
     """librosa.feature.chroma_cqt(y, sr) for every clip: float32 [n_chroma, F], each frame divided by its maximum.
-    `tuning=None` estimates it per clip as librosa does; a number fixes it (0.0 = the nominal grid)."""
+    `tuning=None` estimates it per clip as librosa does, on the host; "device" estimates every clip's in one
+    aegis_estimate_tuning call; a number fixes it (0.0 = the nominal grid); a list gives one number per clip."""
     n_bins = n_octaves * bins_per_octave
-    tunings = [estimate_tuning(c, handle.sr, bins_per_octave) if tuning is None else float(tuning) for c in clips]
+    if isinstance(tuning, str):
+        if tuning != "device":
+            raise ValueError('tuning must be None, a number, a list of numbers or "device"')
+        tunings = handle.estimate_tuning(clips, bins_per_octave)
+    elif isinstance(tuning, (list, tuple, np.ndarray)):
+        tunings = [float(t) for t in tuning]
+        if len(tunings) != len(clips):
+            raise ValueError("one tuning per clip")
+    else:
+        tunings = [estimate_tuning(c, handle.sr, bins_per_octave) if tuning is None else float(tuning) for c in clips]
     fold = cq_to_chroma(n_bins, bins_per_octave, n_chroma, fmin)
     if n_chroma > 24 or not np.array_equal(fold.sum(axis=0), np.ones(n_bins, np.float32)):
         return _chroma_cqt_host_fold(handle, clips, tunings, fold, n_bins, bins_per_octave, fmin)
@@ -132,6 +142,35 @@ def similarity_arrays(handle, y_orig, y_synth):
     ch_o, ch_s = chroma_cqt(handle, clips)
     score = 0.4 * _cosine(mel_o, mel_s) + 0.6 * _cosine(ch_o.astype(np.float64), ch_s.astype(np.float64))
     return max(0.0, min(1.0, score))
+
+
+def score_batch(handle, y_orig, candidates, tuning="device"):
+    """similarity_arrays(handle, y_orig, c) for every candidate c, as a list, with the device work of all of them shared:
+    ONE analyze_batch(STAGE_MEL) call for every mel, ONE tuning call (tuning="device": aegis_estimate_tuning; "host":
+    estimate_tuning per clip, as similarity_arrays does), one Handle.chroma_cqt call per distinct tuning, and the original's
+    features once per distinct truncated length n = min(len(y_orig), len(c)) instead of once per candidate.  The two cosines
+    per candidate stay on the host.  With "host" every score equals similarity_arrays'; with "device" the same holds for
+    every candidate whose two device tunings equal the host's."""
+    if tuning not in ("device", "host"):
+        raise ValueError('tuning must be "device" or "host"')
+    y_orig = np.ascontiguousarray(y_orig, np.float32)
+    cands = [np.ascontiguousarray(c, np.float32) for c in candidates]
+    ns = [min(len(y_orig), len(c)) for c in cands]
+    scores = [0.0] * len(cands)
+    live = [i for i, n in enumerate(ns) if not n < handle.sr * 0.5]
+    if not live:
+        return scores
+    lens = sorted({ns[i] for i in live})
+    orig_at = {n: k for k, n in enumerate(lens)}
+    clips = [y_orig[:n] for n in lens] + [cands[i][:ns[i]] for i in live]
+    raw = handle.analyze_batch(clips, stages=_lib.STAGE_MEL, want_sdb=True)
+    mels = [np.power(10.0, r["S_dB"].astype(np.float64) / 10.0) for r in raw]
+    chroma = [c.astype(np.float64) for c in chroma_cqt(handle, clips, tuning="device" if tuning == "device" else None)]
+    for k, i in enumerate(live):
+        o, c = orig_at[ns[i]], len(lens) + k
+        score = 0.4 * _cosine(mels[o], mels[c]) + 0.6 * _cosine(chroma[o], chroma[c])
+        scores[i] = max(0.0, min(1.0, score))
+    return scores
 
 
 def _calculate_similarity(original_audio_path, synthesized_wav_data, sample_rate=44100, handle=None):

@@ -5,6 +5,10 @@ is there).  Not a pass/fail check: tests/test_gpu_synth.py asserts, this records
   python tools/bench_automatch.py --synth-only        # the 27 x 30 s batch alone (the run to put under
                                                       #   rocprofv3 --kernel-trace --stats -d DIR -- python ...)
   python tools/bench_automatch.py --kernel-stats CSV  # no GPU: folds the synth_* rows of a rocprofv3 *_kernel_stats.csv in
+  python tools/bench_automatch.py --scoring loop|batch [--label NAME] [--searches 3]
+                                                      # the search alone, candidate by candidate or batched: a warm-up
+                                                      #   search, then the median of --searches, into
+                                                      #   profiles/automatch_batch.json under NAME (default: the mode)
 
 Recorded:
   synth_batch_store_mode   the same batch on a handle created under AEGIS_SYNTH_STORE=1 (notes stored by the peak kernel and
@@ -17,6 +21,9 @@ Recorded:
   restated_host        tools/synth_restated.py on this machine's host CPU for one such candidate
   auto_match           one auto_match_parameters on a seeded 30 s clip, wall time and its breakdown by wrapped calls:
                        event extraction, synthesis, WAV read-back, host tuning estimate, device mel + CQT, cosines
+  --scoring            per search: wall time, the breakdown by wrapped calls (score_batch_total contains the device calls
+                       and cosines listed beside it), cqt_bank_builds; once: the hipEvent times of the three tuning kernels
+                       for 28 clips of 30 s in one call, and the bytes and build time (host build + upload) of the 252-bin bank
   sine_golden_differing_samples   the sine fixture against the device (<= 1 step each, tests/test_gpu_synth.py)"""
 import argparse
 import csv
@@ -170,6 +177,79 @@ def auto_match(tmp):
                            "note": "wav_read_back covers both read_wav calls of a score (original file and synthesised bytes)"}}
 
 
+def search_breakdown(tmp, scoring, searches):
+    """Warm-up search, then `searches` timed ones: the median search's wall time and breakdown.  Runs on a tree without
+    the batch path too (scoring="loop": no keyword is passed, missing entry points are not wrapped)."""
+    from spectrogram_midi_amd import audio_io, auto_matcher, similarity
+    from spectrogram_midi_amd.engine import AegisEngine
+    from tools import signals
+    path = os.path.join(tmp, "automatch_original.wav")
+    y = signals.guitar_clip(30.0)
+    audio_io.write_wav(path, y, 44100)
+    eng = AegisEngine()
+    h = eng.handle
+    raw = eng.audio_to_midi(path, None)
+    tm = Timers()
+    tm.wrap(eng, "extract_events", "event_extraction")
+    tm.wrap(auto_matcher, "synthesize_midi_adsr_batch", "synthesis")
+    tm.wrap(audio_io, "read_wav", "wav_read_back")
+    tm.wrap(similarity, "estimate_tuning", "host_tuning_estimate")
+    tm.wrap(h, "analyze_batch", "device_mel")
+    tm.wrap(h, "chroma_cqt", "device_chroma_cqt_with_bank_builds")
+    tm.wrap(similarity, "_cosine", "cosines")
+    if hasattr(h, "estimate_tuning"):
+        tm.wrap(h, "estimate_tuning", "device_tuning_estimate")
+    if hasattr(auto_matcher, "score_batch"):
+        tm.wrap(auto_matcher, "score_batch", "score_batch_total")
+    kw = {} if scoring == "loop" else {"scoring": scoring}
+
+    def builds():
+        try:
+            return h.param("cqt_bank_builds")
+        except Exception:       # noqa: BLE001 -- a library without the counter
+            return None
+    auto_matcher.auto_match_parameters(path, eng, raw, **kw)       # warm-up
+    runs = []
+    for _ in range(searches):
+        tm.t.clear()
+        b0 = builds()
+        t0 = time.perf_counter()
+        res = auto_matcher.auto_match_parameters(path, eng, raw, **kw)
+        wall = time.perf_counter() - t0
+        parts = {k: round(v, 4) for k, v in tm.t.items()}
+        nested = parts.pop("score_batch_total", None)
+        outer = sum(v for k, v in tm.t.items() if k != "score_batch_total") if nested is None else \
+            sum(tm.t.get(k, 0.0) for k in ("event_extraction", "synthesis", "wav_read_back")) + tm.t["score_batch_total"]
+        parts["other"] = round(wall - outer, 4)
+        if nested is not None:
+            parts["score_batch_total"] = nested
+        runs.append({"wall_s": round(wall, 4), "breakdown_s": parts, "result": res,
+                     "cqt_bank_builds": None if b0 is None else builds() - b0})
+    runs.sort(key=lambda r: r["wall_s"])
+    out = dict(runs[len(runs) // 2], clip_seconds=30.0, scoring=scoring, searches=searches, wall_s_each=[r["wall_s"] for r in runs])
+    if hasattr(h, "estimate_tuning"):
+        clips = [y] + [signals.guitar_clip(30.0, seed=40 + i) for i in range(27)]
+        h.estimate_tuning(clips)
+        h.set_profiling(True)
+        t0 = time.perf_counter()
+        h.estimate_tuning(clips)
+        call = time.perf_counter() - t0
+        out["tuning_kernels_28_clips_of_30s"] = dict({k: round(h.kernel_ms(k), 4) for k in ("tuning_peaks", "tuning_select", "tuning_hist")},
+                                                     call_wall_ms=round(call * 1e3, 3))
+        h.set_profiling(False)
+        t0 = time.perf_counter()
+        similarity.estimate_tuning(y, 44100, 36)
+        out["host_tuning_estimate_one_clip_ms"] = round((time.perf_counter() - t0) * 1e3, 3)
+        from spectrogram_midi_amd import _lib
+        hb = _lib.Handle(scipy_tables=False)
+        similarity.chroma_cqt(hb, [y[:44100]], tuning=0.0)
+        out["bank_252_bins"] = {"device_bytes": hb.param("cqt_bank_bytes"), "host_build_and_upload_ms": round(hb.param("cqt_bank_build_us") / 1e3, 3)}
+        hb.close()
+    eng.close()
+    os.remove(path)
+    return out
+
+
 def sine_check():
     from spectrogram_midi_amd import synthesizer
     z = np.load(os.path.join(ROOT, "tests", "golden", "synth_golden.npz"))
@@ -195,9 +275,20 @@ def main():
     ap.add_argument("--synth-only", action="store_true")
     ap.add_argument("--kernel-stats")
     ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--out", default=OUT)
+    ap.add_argument("--out", default=None)
     ap.add_argument("--tmp", default=None)
+    ap.add_argument("--scoring", choices=("loop", "batch"))
+    ap.add_argument("--label")
+    ap.add_argument("--searches", type=int, default=3)
     a = ap.parse_args()
+    if a.scoring:
+        import tempfile
+        with tempfile.TemporaryDirectory(dir=a.tmp) as tmp:
+            got = {a.label or a.scoring: search_breakdown(tmp, a.scoring, a.searches)}
+        merge(got, a.out or os.path.join(ROOT, "profiles", "automatch_batch.json"))
+        print(json.dumps(got, indent=1))
+        return
+    a.out = a.out or OUT
     if a.kernel_stats:
         print(json.dumps(merge(kernel_stats(a.kernel_stats), a.out)["rocprofv3_kernel_stats"], indent=1))
         return
