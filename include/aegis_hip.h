@@ -427,6 +427,56 @@ int64_t aegis_synth_samples_for(int32_t sample_rate, double length_seconds, cons
 int aegis_synth_adsr(aegis_handle *h, int32_t sample_rate, int32_t n_clips, const aegis_synth_note *notes, const int64_t *note_off,
                      const double *length_seconds, const aegis_adsr_params *params, int16_t *const *out, const int64_t *out_cap);
 
+/* --- Effect chain: distortion, reverb, delay, chorus (aegis_engine_core/effect_learning_loop.py:56-275) ----------
+ * The reference's pure-NumPy effects, each ending in a whole-clip normalisation, which its learning loop
+ * (effect_learning_loop.py:489-725) puts between the synthesiser and the engine.  Float64 throughout.
+ *   aegis_reverb_ir   the impulse response apply_reverb builds (:100-117): int(sample_rate * 3 * room_size) taps,
+ *                     exp(-decay_rate * t / sample_rate) * RandomState(42).uniform(0.8, 1.0), divided by the sum of
+ *                     magnitudes.  The uniform draws are NumPy's bit for bit (std::mt19937(42), 53-bit doubles) and the sum is
+ *                     NumPy's pairwise one; np.exp is not libm's exp, so the taps sit within a few ulp of NumPy's, not on
+ *                     them.  Host only, no handle.  Returns the tap count (0: the reverb is a copy) and copies
+ *                     min(count, cap) taps; AEGIS_ERR_INVALID for a non-finite room size, a sample rate <= 0 or more than
+ *                     2^22 taps (aegis_get_param "fx_max_taps").
+ *   aegis_effects     apply_effect_chain (:234-275) for n_clips clips in ONE call: clip c runs effects
+ *                     fx[fx_off[c] .. fx_off[c+1]) in order (fx_off has n_clips + 1 entries).
+ *                       distortion (:56-81)   tanh(x * (1 + drive * 19)), scaled by 1 / max(max|.|, 1e-6), clipped to [-1, 1]
+ *                       reverb (:84-134)      wet[n] = sum_k ir[k] x[n-k] by direct convolution (taps ascending into one
+ *                                             accumulator per output: the same bits from run to run; within
+ *                                             n_ir * 2^-53 * max|x| of any other summation order when sum|ir| = 1),
+ *                                             (1 - 0.3 room_size) x + 0.6 room_size wet; ir == NULL takes aegis_reverb_ir's
+ *                                             design, otherwise ir[0 .. n_ir) is used as given (the Python binding passes
+ *                                             NumPy's own array, as aegis_pcm_clip.taps and aegis_set_table do);
+ *                                             int(sample_rate * 3 * room_size) <= 0 is a copy either way
+ *                       delay (:137-182)      x[n] + x[n - i D] * feedback**i for i = 1, 2, ... in that order, a rounded
+ *                                             multiply and a rounded add per echo; D = int(delay_ms / 1000 * sample_rate);
+ *                                             the echo list stops at i D >= n, at feedback**i < 0.01, or after
+ *                                             min(int(log(0.01) / log(max(feedback, 0.01))), 20) echoes.  D <= 0 or
+ *                                             feedback <= 0 is a copy WITHOUT normalisation; feedback == 1 makes the
+ *                                             reference raise: AEGIS_ERR_INVALID
+ *                       chorus (:185-231)     the LFO-modulated delay line with linear interpolation, 0.7 x + 0.3 wet
+ *                     Reverb, delay and chorus divide by max|.| only if it exceeds 1.0.  The results equal the reference's
+ *                     bit for bit for delay; distortion and chorus differ by the device tanh / sin, reverb by the
+ *                     summation order (bounds: DESIGN.md 3.13).
+ *                     in_format: AEGIS_PCM_S16 (v / 32768.0: what _wav_bytes_to_float gives for a mono 16-bit file) or
+ *                     AEGIS_PCM_F64.  out_f64[c] (optional, as is the array): the float64 result, n_samples[c] values.
+ *                     out_i16[c] (optional): np.clip(y, -1, 1) * 32767 truncated toward zero, the samples
+ *                     _float_to_wav_bytes writes (:322-346).  Host pointers; blocking.  sample_rate is the chain's own:
+ *                     the handle supplies the device, its stream and its buffers.
+ *                     Validated before the device is looked at (a device = -1 handle rejects what a device handle
+ *                     rejects and answers AEGIS_ERR_DEVICE to valid requests): an unknown kind, a non-finite parameter,
+ *                     sample or tap, n_samples < 1 with a non-empty chain (np.max of an empty array raises), n_ir < 1 with
+ *                     ir given, more than 2^22 taps. */
+#define AEGIS_PCM_F64 6
+#define AEGIS_FX_DISTORTION 1   /* p0 = drive                      effect_learning_loop.py:56-81   */
+#define AEGIS_FX_REVERB     2   /* p0 = room_size; ir / n_ir       :84-134                         */
+#define AEGIS_FX_DELAY      3   /* p0 = delay_ms, p1 = feedback    :137-182                        */
+#define AEGIS_FX_CHORUS     4   /* p0 = depth (s), p1 = rate (Hz)  :185-231                        */
+typedef struct aegis_effect { int32_t kind; int32_t n_ir; double p0, p1; const double *ir; } aegis_effect;
+int64_t aegis_reverb_ir(double room_size, int32_t sample_rate, double *dst, int64_t cap);
+int aegis_effects(aegis_handle *h, int32_t sample_rate, int32_t n_clips, const void *const *in, int32_t in_format,
+                  const int64_t *n_samples, const aegis_effect *fx, const int64_t *fx_off,
+                  double *const *out_f64, int16_t *const *out_i16);
+
 /* --- introspection used by the tests (no reference counterpart) ------------- */
 
 /* Host-side copies of the tables the kernels use.  `name` is one of
@@ -464,7 +514,8 @@ int aegis_set_table(aegis_handle *h, const char *name, const double *data, int64
  * accepts produces: 2 n_pitch_bins <= 1024 threads and the generic kernel's LDS without the table stays under 160 KB),
  * "frame_fpw" (frames per frame-kernel workgroup of a launch of >= 4096 frames; smaller launches take 2), "obs_waves"
  * (waves per pyin_obs workgroup of such a launch outside a dense pass), "split_applies" (1: the time-split Viterbi can
- * take this geometry). */
+ * take this geometry).  Constants of the effect kernels (csrc/effects.h): "fx_tile" (reverb outputs per workgroup), "fx_chunk"
+ * (taps per staged window of the reverb), "fx_max_taps". */
 int64_t aegis_get_param(const aegis_handle *h, const char *name);
 
 /* Copies an intermediate of the most recent pass (device -> host), for stage-level

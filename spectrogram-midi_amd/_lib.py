@@ -61,6 +61,15 @@ class AdsrParams(C.Structure):
                 ("waveform", C.c_int32), ("reserved", C.c_int32)]
 
 
+class Effect(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("n_ir", C.c_int32), ("p0", C.c_double), ("p1", C.c_double), ("ir", C.c_void_p)]
+
+
+PCM_S16, PCM_F64 = 2, 6                                                   # AEGIS_PCM_*: what aegis_effects reads
+FX_DISTORTION, FX_REVERB, FX_DELAY, FX_CHORUS = 1, 2, 3, 4                # AEGIS_FX_*
+# effect name -> (kind, (parameter, the reference's default) for p0 and p1): effect_learning_loop.py:56, :84, :137, :185
+EFFECT_KINDS = {"distortion": (FX_DISTORTION, (("drive", 0.5),)), "reverb": (FX_REVERB, (("room_size", 0.5),)),
+                "delay": (FX_DELAY, (("delay_ms", 300), ("feedback", 0.3))), "chorus": (FX_CHORUS, (("depth", 0.003), ("rate", 1.5)))}
 WAVEFORMS = {"sine": 0, "sawtooth": 1, "square": 2, "triangle": 3}          # AEGIS_WAVE_*
 SYNTH_NOTE_DTYPE = np.dtype([("start", "<f8"), ("duration", "<f8"), ("note", "<i4"), ("velocity", "<i4")])
 
@@ -71,7 +80,8 @@ EXPORTS = ("aegis_abi_version", "aegis_create", "aegis_destroy", "aegis_last_err
            "aegis_extract_events", "aegis_render_smf", "aegis_events_last_error", "aegis_debug_plan",
            "aegis_analyze_pcm", "aegis_pcm_samples_for", "aegis_resample_taps", "aegis_stream_push_commit",
            "aegis_synth_parse_smf", "aegis_synth_samples_for", "aegis_synth_adsr", "aegis_debug_rake_columns",
-           "aegis_debug_set_observations", "aegis_debug_set_difference", "aegis_estimate_tuning")
+           "aegis_debug_set_observations", "aegis_debug_set_difference", "aegis_estimate_tuning",
+           "aegis_reverb_ir", "aegis_effects")
 
 _lib = None
 
@@ -162,6 +172,11 @@ def load():
     lib.aegis_synth_adsr.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(AdsrParams),
                                      C.POINTER(C.c_void_p), C.c_void_p]
     lib.aegis_synth_adsr.restype = C.c_int
+    lib.aegis_reverb_ir.argtypes = [C.c_double, C.c_int32, C.c_void_p, C.c_int64]
+    lib.aegis_reverb_ir.restype = C.c_int64
+    lib.aegis_effects.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.c_int32, C.c_void_p, C.POINTER(Effect),
+                                  C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    lib.aegis_effects.restype = C.c_int
     lib.aegis_set_profiling.argtypes = [C.c_void_p, C.c_int32]
     lib.aegis_set_profiling.restype = C.c_int
     lib.aegis_last_kernel_ms.argtypes = [C.c_void_p, C.c_char_p]
@@ -650,6 +665,54 @@ class Handle:
         self._check(rc)
         return outs
 
+    def effects(self, clips, chains, sample_rate, want_f64=True, want_i16=False, numpy_ir=True):
+        """aegis_effects: the reference's apply_effect_chain for a batch of clips in ONE device call.  clips: int16 arrays
+        (read as v / 32768.0) or float64 arrays, all of one kind; chains: per clip a list of (effect name, parameter
+        dict) as EFFECT_PRESETS holds them (missing parameters take the reference's defaults; unknown names raise
+        ValueError).  numpy_ir: a reverb runs with the impulse response NumPy builds (`numpy_reverb_ir`), so that the
+        chain matches the reference on this host; False takes the library's own design; a reverb's parameter dict may
+        carry its own taps as "ir" (used as given, whatever room_size says about their number).  -> list of float64 arrays,
+        list of int16 arrays (np.clip(y, -1, 1) * 32767 truncated), or a pair of both."""
+        n = len(clips)
+        if len(chains) != n:
+            raise ValueError("one chain per clip")
+        if n == 0:
+            return ([], []) if (want_f64 and want_i16) else []
+        s16 = all(np.asarray(c).dtype == np.int16 for c in clips)
+        clips = [np.ascontiguousarray(c, dtype=np.int16 if s16 else np.float64) for c in clips]
+        fx, off, keep = [], [0], {}
+        for chain in chains:
+            for name, params in chain:
+                if name not in EFFECT_KINDS:
+                    raise ValueError(f"unknown effect: {name}")
+                kind, spec = EFFECT_KINDS[name]
+                p = [float(params.get(k, d)) for k, d in spec] + [0.0]
+                e = Effect(kind, 0, p[0], p[1], None)
+                if kind == FX_REVERB and (numpy_ir or "ir" in params):
+                    key = (p[0], int(sample_rate)) if "ir" not in params else id(params["ir"])
+                    if key not in keep:
+                        keep[key] = (numpy_reverb_ir(*key) if "ir" not in params
+                                     else np.ascontiguousarray(params["ir"], dtype=np.float64))
+                    if len(keep[key]):
+                        e.n_ir, e.ir = len(keep[key]), keep[key].ctypes.data
+                fx.append(e)
+            off.append(len(fx))
+        arr = (Effect * max(len(fx), 1))(*fx)
+        offs = np.asarray(off, np.int64)
+        lens = np.asarray([len(c) for c in clips], np.int64)
+        ptrs = (C.c_void_p * n)(*[c.ctypes.data for c in clips])
+        f64 = [np.empty(len(c), np.float64) for c in clips] if want_f64 else None
+        i16 = [np.empty(len(c), np.int16) for c in clips] if want_i16 else None
+        p64 = (C.c_void_p * n)(*[a.ctypes.data for a in f64]) if want_f64 else None
+        p16 = (C.c_void_p * n)(*[a.ctypes.data for a in i16]) if want_i16 else None
+        rc = self.lib.aegis_effects(self._h, int(sample_rate), n, ptrs, PCM_S16 if s16 else PCM_F64, lens.ctypes.data, arr,
+                                    offs.ctypes.data, p64, p16)
+        del keep
+        if rc == ERR_INVALID:
+            raise ValueError(self.lib.aegis_last_error(self._h).decode())
+        self._check(rc)
+        return (f64, i16) if (want_f64 and want_i16) else (f64 if want_f64 else i16)
+
     def open_stream(self, max_seconds=600.0, commit=False, commit_cap=None):
         """commit: push() also returns the frames whose decode is already final (Stream); commit_cap: room for them per
         push (default: every frame of the stream)."""
@@ -677,6 +740,31 @@ def resample_taps(up, down):
     out = np.empty(n, np.float32)
     lib.aegis_resample_taps(int(up), int(down), out.ctypes.data, n)
     return out
+
+
+def reverb_ir(room_size, sr):
+    """aegis_reverb_ir: the library's own design of apply_reverb's impulse response (host code, no handle, no GPU); an
+    empty array where the reference's reverb is a copy."""
+    lib = load()
+    n = int(lib.aegis_reverb_ir(float(room_size), int(sr), None, 0))
+    if n < 0:
+        raise AegisError(n, "bad room size or sample rate")
+    out = np.empty(n, np.float64)
+    lib.aegis_reverb_ir(float(room_size), int(sr), out.ctypes.data, n)
+    return out
+
+
+def numpy_reverb_ir(room_size, sr):
+    """The same impulse response from NumPy's own exp, uniform and sum (effect_learning_loop.py:100-117): what
+    Handle.effects hands the library, as Handle.pcm_clips hands it scipy's resampling taps."""
+    duration = room_size * 3.0
+    n = int(sr * duration)
+    if n <= 0:
+        return np.empty(0, np.float64)
+    ir = np.exp(-(5.0 / max(duration, 0.01)) * np.arange(n, dtype=np.float64) / sr)
+    ir *= np.random.RandomState(42).uniform(0.8, 1.0, size=n)
+    ir /= max(np.sum(np.abs(ir)), 1e-6)
+    return ir
 
 
 class Stream:

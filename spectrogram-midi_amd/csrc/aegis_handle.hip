@@ -1,6 +1,7 @@
 // Handle life cycle and introspection of libaegis_hip.so: create / destroy, the owned device buffers and events every
 // other file allocates through, profiling, tables and parameters, aegis_debug_plan / aegis_debug_fetch.
 #include "aegis_internal.h"
+#include "effects.h"
 
 #include <chrono>
 #include <cmath>
@@ -427,6 +428,9 @@ int64_t aegis_get_param(const aegis_handle *h, const char *name) {
     if (n == "obs_waves") { PassParams q = base_params(t); q.n_sel = 4096; return pyin_obs_waves(q); }
     if (n == "viterbi_kernel") { const int k = viterbi_kernel_choice(base_params(t), rule_tables(h)); return k < 0 ? AEGIS_ERR_UNSUPPORTED : k; }
     if (n == "split_applies") return viterbi_split_applies(base_params(t), rule_tables(h)) ? 1 : 0;
+    if (n == "fx_tile") return kFxRevTile;
+    if (n == "fx_chunk") return kFxChunk;
+    if (n == "fx_max_taps") return kFxMaxTaps;
     return AEGIS_ERR_INVALID;
     } catch (...) { return abi_fail(const_cast<aegis_handle *>(h)); }
 }

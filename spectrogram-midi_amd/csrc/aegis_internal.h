@@ -6,6 +6,7 @@
 //   aegis_cqt.hip     CQT, chroma, the filter-bank cache, aegis_estimate_tuning, aegis_rake_patterns
 //   aegis_trend.hip   aegis_trend, aegis_ghost_rsi
 //   aegis_synth.hip   aegis_synth_* (the ADSR soft-synth; kernels in synth.hip, the MIDI reader in synth_smf.cpp)
+//   aegis_effects.hip aegis_reverb_ir, aegis_effects (the effect chain; kernels in effects.hip)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -115,6 +116,7 @@ struct aegis_handle {
     DevBuf io_pcm, io_f0, io_voiced, io_vprob, io_rms, io_rake, io_sdb, io_bin, io_colmean;
     DevBuf pcm_raw, pcm_clips, pcm_ranges, pcm_taps;   // aegis_analyze_pcm: raw bytes, clip table, per-chunk range tables, filters
     DevBuf sy_notes, sy_clips, sy_tiles, sy_tile_notes, sy_note_peak, sy_clip_peak, sy_mix, sy_out, sy_sig;   // aegis_synth_adsr: records, float64 mix, int16 result
+    DevBuf fx_a, fx_b, fx_recs, fx_tiles, fx_peak, fx_taps, fx_i16;   // aegis_effects: the two float64 batch buffers, records, clip maxima, taps, int16 in / out
     bool synth_store = false;                 // AEGIS_SYNTH_STORE=1 at create: notes stored by the peak kernel and read by the mix (sy_sig) instead of recomputed
     int32_t lag_stride = 0, yin_stride = 0, obs_stride = 0;
     aegis::CallPlan plan;                     // the last call's plan: its host arrays stay alive until the stream drained

@@ -1,0 +1,41 @@
+"""Reverse analysis on the GPU path: the reference's aegis_engine_core/reverse_analyzer.py:143-247.  MIDI -> audio ->
+MIDI again -> how much of the original came back.  The audio is the device ADSR synth's (the reference's FluidSynth-only
+`synthesize_midi` finds nothing where this package runs), analysed as the int16 samples its WAV file would hold."""
+import io
+
+from . import synthesizer as _synth
+from .effect_learning_loop import START_PARAMS, _analysis_input, _compare_note_lists, _extract_notes_from_midi
+
+__all__ = ["reverse_analysis", "_extract_notes_from_midi", "_compare_note_lists"]
+
+
+def reverse_analysis(midi_data, engine, sample_rate=44100, preset="electric_clean"):
+    """-> {'original_notes', 'reversed_notes', 'note_accuracy', 'pitch_accuracy', 'timing_accuracy', 'reversed_midi',
+    'reversed_events'}, or None (after printing) when the file holds no notes or any step fails."""
+    try:
+        blob = _synth._midi_bytes(midi_data)
+        original_notes = _extract_notes_from_midi(blob)
+        if not original_notes:
+            print("[ReverseAnalyzer] no notes in the original MIDI")
+            return None
+        if getattr(engine, "sr", sample_rate) != sample_rate:
+            raise ValueError("the engine must analyse at the synthesis rate")
+        rendered = _synth.synthesize_midi_adsr_batch([blob], preset=preset, sample_rate=sample_rate, as_arrays=True, handle=engine.handle)
+        if not rendered or rendered[0] is None:
+            print("[ReverseAnalyzer] MIDI synthesis failed")
+            return None
+        raw_data = engine.analyze_array(_analysis_input(rendered[0]))
+        if not raw_data:
+            print("[ReverseAnalyzer] analysis failed")
+            return None
+        buf = io.BytesIO()
+        reversed_events = engine.extract_events(raw_data, buf, midi_program=27, **START_PARAMS)   # 0.3 / 50 / 200 (:203-205)
+        reversed_midi = buf.getvalue()
+        reversed_notes = _extract_notes_from_midi(reversed_midi)
+        comparison = _compare_note_lists(original_notes, reversed_notes)
+        return {"original_notes": len(original_notes), "reversed_notes": len(reversed_notes),
+                "note_accuracy": comparison["note_accuracy"], "pitch_accuracy": comparison["pitch_accuracy"],
+                "timing_accuracy": comparison["timing_accuracy"], "reversed_midi": reversed_midi, "reversed_events": reversed_events}
+    except Exception as e:                                   # noqa: BLE001 -- mirrors the reference's catch-all
+        print(f"[ReverseAnalyzer] reverse analysis failed: {e}")
+        return None

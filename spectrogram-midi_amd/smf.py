@@ -103,3 +103,68 @@ def render(events, sr, hop_length, midi_program=27, vibrato_rate=5.0, vibrato_de
             t.note_off(tick, a, b)
     header = b"MThd" + struct.pack(">IHHH", 6, 1, 2, TICKS_PER_BEAT)
     return header + tracks["main"].chunk() + tracks["safe"].chunk()
+
+
+def read_tracks(blob):
+    """SMF bytes -> (ticks_per_beat, tracks); a track is a list of (delta_ticks, kind, a, b) in file order with kind one of
+    "note_on" (a = note, b = velocity), "note_off" (same), "set_tempo" (a = microseconds per beat) and "other" (every other
+    channel, meta or sysex event: kept for its delta).  Running status is honoured; ValueError for bytes that are not a
+    Standard MIDI File."""
+    data = bytes(blob)
+    if len(data) < 14 or data[:4] != b"MThd":
+        raise ValueError("not a Standard MIDI File")
+    head_len, _, n_tracks, tpb = struct.unpack(">IHHH", data[4:14])
+    if tpb & 0x8000 or tpb == 0:
+        raise ValueError("SMPTE time division is not supported")
+    at, tracks = 8 + head_len, []
+    for _ in range(n_tracks):
+        if data[at:at + 4] != b"MTrk" or at + 8 > len(data):
+            raise ValueError("missing track chunk")
+        (size,) = struct.unpack(">I", data[at + 4:at + 8])
+        body = data[at + 8:at + 8 + size]
+        if len(body) != size:
+            raise ValueError("truncated track chunk")
+        at += 8 + size
+        i, status, msgs = 0, None, []
+
+        def varlen():
+            nonlocal i
+            v = 0
+            while True:
+                c = body[i]
+                i += 1
+                v = (v << 7) | (c & 0x7F)
+                if not c & 0x80:
+                    return v
+        try:
+            while i < size:
+                delta = varlen()
+                c = body[i]
+                if c == 0xFF:
+                    kind, i = body[i + 1], i + 2
+                    n = varlen()
+                    payload, i = body[i:i + n], i + n
+                    if kind == 0x51 and n == 3:
+                        msgs.append((delta, "set_tempo", int.from_bytes(payload, "big"), 0))
+                    else:
+                        msgs.append((delta, "other", 0, 0))
+                    continue
+                if c in (0xF0, 0xF7):
+                    i += 1
+                    n = varlen()
+                    i += n
+                    msgs.append((delta, "other", 0, 0))
+                    continue
+                if c & 0x80:
+                    status, i = c, i + 1
+                if status is None:
+                    raise ValueError("data byte without a status")
+                n = 1 if status & 0xF0 in (0xC0, 0xD0) else 2
+                a, b = body[i], (body[i + 1] if n == 2 else 0)
+                i += n
+                hi = status & 0xF0
+                msgs.append((delta, "note_on" if hi == 0x90 else "note_off" if hi == 0x80 else "other", a, b))
+        except IndexError:
+            raise ValueError("truncated track data") from None
+        tracks.append(msgs)
+    return tpb, tracks
