@@ -427,6 +427,57 @@ int64_t aegis_synth_samples_for(int32_t sample_rate, double length_seconds, cons
 int aegis_synth_adsr(aegis_handle *h, int32_t sample_rate, int32_t n_clips, const aegis_synth_note *notes, const int64_t *note_off,
                      const double *length_seconds, const aegis_adsr_params *params, int16_t *const *out, const int64_t *out_cap);
 
+/* --- Per-note ADSR fit and render (aegis_engine_core/per_note_optimizer.py:72-327, :549-659) ---------------------
+ * The reference's per-note optimiser scores, for every detected note, candidate envelopes and waveforms against the note's
+ * slice of the original audio, and then renders the file with one envelope and waveform per note.
+ *   aegis_note_fit    n_notes notes over n_clips clips in ONE call.  Clip c is audio[c], n_samples[c] float32 samples in host
+ *                     memory.  Note k reads the slice [lo, hi) of clip notes[k].clip (slice_audio_for_note's bounds are the
+ *                     caller's to compute) and has the candidates cands[cand_off[k] .. cand_off[k+1]).  A candidate is
+ *                     synthesize_note(freq of the MIDI note, duration + release_ms / 1000, velocity, the candidate's
+ *                     envelope and waveform, harmonics) truncated to the slice length, scored as compare_note_audio scores
+ *                     it on librosa 0.10's rms (512 / 256), spectral_centroid (2048 / 512, periodic Hann, float64) and
+ *                     zero_crossing_rate (2048 / 512).  Per candidate, at the caller's candidate index: the clipped score
+ *                     0.5 env + 0.3 centroid + 0.2 zcr and the three terms; per note best[k], the index within the note of
+ *                     the FIRST maximum (`sim > best`; -1 for a note without candidates).  hi == lo scores 0.0 everywhere
+ *                     without a launch.  A result is a function of the note alone -- the same bits alone, in any batch and
+ *                     under any regrouping -- and candidates with equal samples score equally.  The zero-crossing term
+ *                     equals the NumPy statement bit for bit; the other two within the bounds of DESIGN.md 3.14.
+ *                     Rejected (AEGIS_ERR_INVALID): non-finite or negative parameters, an unknown waveform, lo > hi, a range
+ *                     outside its clip, a candidate whose int(sample_rate * full duration) is 0 (the reference's np.max
+ *                     raises), sample rates whose RMS frame max(512, int(sr * 0.01)) is not 512, a handle whose n_fft is
+ *                     not 2048.  Requests are validated before the device is looked at: a device = -1 handle rejects what
+ *                     a device handle rejects and answers AEGIS_ERR_DEVICE to valid requests.  When the workspace cannot
+ *                     be allocated the batch is halved and retried.  Blocking; host pointers.
+ *   aegis_compare_audio   compare_note_audio on n_pairs pairs of given float64 signals (host memory): the shorter of a pair is
+ *                     zero-padded to the longer, out[4 k ..] = score, envelope, centroid and zero-crossing terms of pair k
+ *                     (all 0.0 when both are empty, without a launch).  Same kernels, same rules as aegis_note_fit.
+ *   aegis_synth_one_note  ADSRSynthesizer.synthesize_note (synthesizer.py:316-374, harmonics on): the float64 samples of one
+ *                     note of `freq` Hz and `duration` seconds (the FULL duration, release included).  out == NULL: returns
+ *                     int(sample_rate * duration) without device work; otherwise writes that many samples (cap >= that)
+ *                     and returns the count.  Bit-equal to NumPy for sawtooth, triangle and square.
+ *   aegis_synth_notes_samples_for   total_samples of a per-note render: int(sample_rate * (length_seconds + max release_ms
+ *                     / 1000 + 0.5)), length_seconds being the latest note END (release not included), the maximum taken
+ *                     over the clip's notes (100 ms for a clip without notes); no handle.
+ *   aegis_synth_adsr_notes          aegis_synth_adsr with one aegis_adsr_params per NOTE (params[q] belongs to notes[q]) and
+ *                     the length rule above.  A note that starts at or past total_samples is skipped; the mix order is the
+ *                     note order; master normalisation and int16 conversion as aegis_synth_adsr. */
+typedef struct aegis_fit_note {
+    int32_t clip, note;           /* index into audio[], MIDI note number */
+    int64_t lo, hi;               /* the slice within the clip */
+    int32_t velocity, reserved;
+    double duration;              /* seconds, without the release */
+} aegis_fit_note;
+int aegis_note_fit(aegis_handle *h, int32_t sample_rate, int32_t n_clips, const float *const *audio, const int64_t *n_samples,
+                   int32_t n_notes, const aegis_fit_note *notes, const aegis_adsr_params *cands, const int64_t *cand_off,
+                   double *score, double *env, double *centroid, double *zcr, int32_t *best);
+int aegis_compare_audio(aegis_handle *h, int32_t sample_rate, int32_t n_pairs, const double *const *orig, const int64_t *n_orig,
+                        const double *const *synth, const int64_t *n_synth, double *out);
+int64_t aegis_synth_one_note(aegis_handle *h, int32_t sample_rate, double freq, double duration, int32_t velocity,
+                         const aegis_adsr_params *params, double *out, int64_t cap);
+int64_t aegis_synth_notes_samples_for(int32_t sample_rate, double length_seconds, const aegis_adsr_params *params, int64_t n_notes);
+int aegis_synth_adsr_notes(aegis_handle *h, int32_t sample_rate, int32_t n_clips, const aegis_synth_note *notes, const int64_t *note_off,
+                           const double *length_seconds, const aegis_adsr_params *params, int16_t *const *out, const int64_t *out_cap);
+
 /* --- Effect chain: distortion, reverb, delay, chorus (aegis_engine_core/effect_learning_loop.py:56-275) ----------
  * The reference's pure-NumPy effects, each ending in a whole-clip normalisation, which its learning loop
  * (effect_learning_loop.py:489-725) puts between the synthesiser and the engine.  Float64 throughout.

@@ -61,6 +61,11 @@ class AdsrParams(C.Structure):
                 ("waveform", C.c_int32), ("reserved", C.c_int32)]
 
 
+class FitNote(C.Structure):
+    _fields_ = [("clip", C.c_int32), ("note", C.c_int32), ("lo", C.c_int64), ("hi", C.c_int64), ("velocity", C.c_int32),
+                ("reserved", C.c_int32), ("duration", C.c_double)]
+
+
 class Effect(C.Structure):
     _fields_ = [("kind", C.c_int32), ("n_ir", C.c_int32), ("p0", C.c_double), ("p1", C.c_double), ("ir", C.c_void_p)]
 
@@ -81,7 +86,8 @@ EXPORTS = ("aegis_abi_version", "aegis_create", "aegis_destroy", "aegis_last_err
            "aegis_analyze_pcm", "aegis_pcm_samples_for", "aegis_resample_taps", "aegis_stream_push_commit",
            "aegis_synth_parse_smf", "aegis_synth_samples_for", "aegis_synth_adsr", "aegis_debug_rake_columns",
            "aegis_debug_set_observations", "aegis_debug_set_difference", "aegis_estimate_tuning",
-           "aegis_reverb_ir", "aegis_effects")
+           "aegis_reverb_ir", "aegis_effects",
+           "aegis_note_fit", "aegis_compare_audio", "aegis_synth_one_note", "aegis_synth_notes_samples_for", "aegis_synth_adsr_notes")
 
 _lib = None
 
@@ -177,6 +183,19 @@ def load():
     lib.aegis_effects.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.c_int32, C.c_void_p, C.POINTER(Effect),
                                   C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     lib.aegis_effects.restype = C.c_int
+    lib.aegis_note_fit.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.c_void_p, C.c_int32, C.POINTER(FitNote),
+                                   C.POINTER(AdsrParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.aegis_note_fit.restype = C.c_int
+    lib.aegis_compare_audio.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p,
+                                        C.c_void_p]
+    lib.aegis_compare_audio.restype = C.c_int
+    lib.aegis_synth_one_note.argtypes = [C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_int32, C.POINTER(AdsrParams), C.c_void_p, C.c_int64]
+    lib.aegis_synth_one_note.restype = C.c_int64
+    lib.aegis_synth_notes_samples_for.argtypes = [C.c_int32, C.c_double, C.POINTER(AdsrParams), C.c_int64]
+    lib.aegis_synth_notes_samples_for.restype = C.c_int64
+    lib.aegis_synth_adsr_notes.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(AdsrParams),
+                                           C.POINTER(C.c_void_p), C.c_void_p]
+    lib.aegis_synth_adsr_notes.restype = C.c_int
     lib.aegis_set_profiling.argtypes = [C.c_void_p, C.c_int32]
     lib.aegis_set_profiling.restype = C.c_int
     lib.aegis_last_kernel_ms.argtypes = [C.c_void_p, C.c_char_p]
@@ -660,6 +679,91 @@ class Handle:
         caps = np.asarray(sizes, np.int64)
         rc = lib.aegis_synth_adsr(self._h, int(sample_rate), n, notes.ctypes.data, off.ctypes.data, lens.ctypes.data, par, ptrs,
                                   caps.ctypes.data)
+        if rc == ERR_INVALID:
+            raise ValueError(lib.aegis_last_error(self._h).decode())
+        self._check(rc)
+        return outs
+
+    def note_fit(self, clips, notes, candidates, sample_rate):
+        """aegis_note_fit: ONE device call for any number of notes of any number of clips.  clips: 1-D arrays (read as
+        float32); notes: per note (clip index, lo, hi, MIDI note, velocity, duration in seconds); candidates: per note a
+        list of AdsrParams.  -> (scores [n_cands][4] float64: score, envelope, centroid, zero-crossing terms, in the
+        order the candidates were given; offsets [n_notes + 1]; best [n_notes]: index within the note of the first
+        maximum).  ValueError for what the library rejects."""
+        if len(notes) != len(candidates):
+            raise ValueError("one candidate list per note")
+        clips = [np.ascontiguousarray(c, dtype=np.float32) for c in clips]
+        n = len(notes)
+        off = np.zeros(n + 1, np.int64)
+        off[1:] = np.cumsum([len(c) for c in candidates])
+        total = int(off[-1])
+        out = np.zeros((4, max(total, 1)), np.float64)
+        best = np.full(max(n, 1), -1, np.int32)
+        arr = (FitNote * max(n, 1))(*[FitNote(int(c), int(m), int(lo), int(hi), int(v), 0, float(d)) for c, lo, hi, m, v, d in notes])
+        par = (AdsrParams * max(total, 1))(*[p for c in candidates for p in c])
+        ptrs = (C.c_void_p * max(len(clips), 1))(*[c.ctypes.data for c in clips])
+        lens = np.asarray([len(c) for c in clips] or [0], np.int64)
+        rc = self.lib.aegis_note_fit(self._h, int(sample_rate), len(clips), ptrs, lens.ctypes.data, n, arr, par, off.ctypes.data,
+                                     out[0].ctypes.data, out[1].ctypes.data, out[2].ctypes.data, out[3].ctypes.data, best.ctypes.data)
+        if rc == ERR_INVALID:
+            raise ValueError(self.lib.aegis_last_error(self._h).decode())
+        self._check(rc)
+        return np.ascontiguousarray(out[:, :total].T), off, best[:n]
+
+    def compare_audio(self, pairs, sample_rate):
+        """aegis_compare_audio: compare_note_audio's (score, envelope, centroid, zero-crossing terms) of every (original,
+        synthesised) pair of 1-D signals (read as float64), in ONE device call -> float64 [n_pairs][4]."""
+        a = [np.ascontiguousarray(p[0], dtype=np.float64) for p in pairs]
+        b = [np.ascontiguousarray(p[1], dtype=np.float64) for p in pairs]
+        n = len(pairs)
+        out = np.zeros((max(n, 1), 4), np.float64)
+        pa = (C.c_void_p * max(n, 1))(*[x.ctypes.data for x in a])
+        pb = (C.c_void_p * max(n, 1))(*[x.ctypes.data for x in b])
+        la, lb = np.asarray([len(x) for x in a] or [0], np.int64), np.asarray([len(x) for x in b] or [0], np.int64)
+        rc = self.lib.aegis_compare_audio(self._h, int(sample_rate), n, pa, la.ctypes.data, pb, lb.ctypes.data, out.ctypes.data)
+        if rc == ERR_INVALID:
+            raise ValueError(self.lib.aegis_last_error(self._h).decode())
+        self._check(rc)
+        return out[:n]
+
+    def synth_note(self, freq, duration, velocity, params, sample_rate):
+        """aegis_synth_one_note: ADSRSynthesizer.synthesize_note (harmonics on) -> float64 array of int(sr * duration)."""
+        n = int(self.lib.aegis_synth_one_note(self._h, int(sample_rate), float(freq), float(duration), int(velocity), C.byref(params), None, 0))
+        if n == ERR_INVALID:
+            raise ValueError(self.lib.aegis_last_error(self._h).decode())
+        self._check(min(n, 0))
+        out = np.empty(n, np.float64)
+        got = int(self.lib.aegis_synth_one_note(self._h, int(sample_rate), float(freq), float(duration), int(velocity), C.byref(params),
+                                                out.ctypes.data, n))
+        if got == ERR_INVALID:
+            raise ValueError(self.lib.aegis_last_error(self._h).decode())
+        self._check(min(got, 0))
+        return out
+
+    def synth_adsr_notes(self, note_lists, end_times, param_lists, sample_rate):
+        """aegis_synth_adsr_notes: aegis_synth_adsr with one AdsrParams per NOTE.  note_lists: SYNTH_NOTE_DTYPE arrays;
+        end_times: per clip the latest note end in seconds; param_lists: per clip one AdsrParams per note -> int16 arrays."""
+        n = len(note_lists)
+        if n == 0:
+            return []
+        if any(len(a) != len(p) for a, p in zip(note_lists, param_lists)):
+            raise ValueError("one parameter set per note")
+        lib = self.lib
+        flat = [p for c in param_lists for p in c]
+        par = (AdsrParams * max(len(flat), 1))(*flat)
+        off = np.concatenate([[0], np.cumsum([len(a) for a in note_lists])]).astype(np.int64)
+        sizes = [int(lib.aegis_synth_notes_samples_for(int(sample_rate), float(end_times[i]),
+                                                       C.cast(C.byref(par, int(off[i]) * C.sizeof(AdsrParams)), C.POINTER(AdsrParams)),
+                                                       int(off[i + 1] - off[i]))) for i in range(n)]
+        if min(sizes) < 0:
+            raise ValueError("bad ADSR parameters, sample rate or length")
+        notes = np.ascontiguousarray(np.concatenate(note_lists) if off[-1] else np.empty(0, SYNTH_NOTE_DTYPE), dtype=SYNTH_NOTE_DTYPE)
+        lens = np.ascontiguousarray(end_times, dtype=np.float64)
+        outs = [np.empty(k, np.int16) for k in sizes]
+        ptrs = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
+        caps = np.asarray(sizes, np.int64)
+        rc = lib.aegis_synth_adsr_notes(self._h, int(sample_rate), n, notes.ctypes.data, off.ctypes.data, lens.ctypes.data, par, ptrs,
+                                        caps.ctypes.data)
         if rc == ERR_INVALID:
             raise ValueError(lib.aegis_last_error(self._h).decode())
         self._check(rc)

@@ -7,6 +7,7 @@
 //   aegis_trend.hip   aegis_trend, aegis_ghost_rsi
 //   aegis_synth.hip   aegis_synth_* (the ADSR soft-synth; kernels in synth.hip, the MIDI reader in synth_smf.cpp)
 //   aegis_effects.hip aegis_reverb_ir, aegis_effects (the effect chain; kernels in effects.hip)
+//   aegis_notefit.hip aegis_note_fit, aegis_synth_one_note, aegis_synth_adsr_notes (the per-note optimiser; kernels in notefit.hip)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -117,6 +118,10 @@ struct aegis_handle {
     DevBuf pcm_raw, pcm_clips, pcm_ranges, pcm_taps;   // aegis_analyze_pcm: raw bytes, clip table, per-chunk range tables, filters
     DevBuf sy_notes, sy_clips, sy_tiles, sy_tile_notes, sy_note_peak, sy_clip_peak, sy_mix, sy_out, sy_sig;   // aegis_synth_adsr: records, float64 mix, int16 result
     DevBuf fx_a, fx_b, fx_recs, fx_tiles, fx_peak, fx_taps, fx_i16;   // aegis_effects: the two float64 batch buffers, records, clip maxima, taps, int16 in / out
+    // aegis_note_fit / aegis_synth_one_note / aegis_synth_adsr_notes: slices, records, per-frame features, scores; stored note, mix
+    DevBuf nf_audio, nf_oscs, nf_cands, nf_notes, nf_boff, nf_peak, nf_cnum, nf_cden, nf_zc, nf_rms, nf_out, nf_best;
+    DevBuf nf_sig, nf_sigoff, nf_cands2, nf_tiles, nf_tile_notes, nf_cpeak, nf_mix, nf_i16;
+    bool notefit_store = false;               // AEGIS_NOTEFIT_STORE=1 at create: every candidate rendered once into nf_sig and read by the frames instead of recomputed
     bool synth_store = false;                 // AEGIS_SYNTH_STORE=1 at create: notes stored by the peak kernel and read by the mix (sy_sig) instead of recomputed
     int32_t lag_stride = 0, yin_stride = 0, obs_stride = 0;
     aegis::CallPlan plan;                     // the last call's plan: its host arrays stay alive until the stream drained

@@ -87,6 +87,17 @@ class ADSRSynthesizer:
         that are not a MIDI file, an unknown waveform."""
         return wav_bytes(self.midi_to_samples(midi_data, attack_ms, decay_ms, sustain_level, release_ms, waveform), self.sr)
 
+    def synthesize_note(self, freq, duration, velocity=100, attack_ms=10, decay_ms=50, sustain_level=0.7, release_ms=100,
+                        waveform="sawtooth", harmonics=True):
+        """synthesizer.py:316-374 on the device: one note of `freq` Hz and `duration` seconds (release included) as a
+        float64 array of int(sr * duration) samples -- oscillator plus the harmonics below sr / 2, peak normalisation,
+        envelope, velocity.  Equal to the reference bit for bit for sawtooth, triangle and square.  Only harmonics=True
+        is built (every caller of the reference passes it)."""
+        if not harmonics:
+            raise NotImplementedError("synthesize_note: only harmonics=True is built")
+        h = self.handle
+        return h.synth_note(freq, duration, velocity, h.adsr_params(attack_ms, decay_ms, sustain_level, release_ms, waveform), self.sr)
+
     def analyze_envelope(self, audio_data, sr=44100):
         """synthesizer.py:512-627 (host): ADSR-like figures of an audio segment from its 5 ms RMS track -- time to the
         RMS peak, mean level over the middle of what follows, time down to that level, length of the quiet tail."""
