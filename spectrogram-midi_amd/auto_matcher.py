@@ -10,7 +10,7 @@ the reference's own callers (server.py:273-275) -- because the reference's Fluid
 on the machines this package runs on.  A candidate whose MIDI cannot be rendered is skipped alone, as in the reference.
 
 The 27 candidates of a stage are independent, so a stage extracts all their events first, renders them in ONE synth batch
-(`synthesize_midi_adsr_batch`, csrc/synth.hip) and then scores them one by one through `similarity._calculate_similarity`
+(`synthesize_midi_adsr_batch`, csrc/adsr.hip) and then scores them one by one through `similarity._calculate_similarity`
 (mel on the frame kernel, chroma on the MFMA CQT).  Scoring candidate by candidate keeps every score exactly what the
 three public pieces give when they are called in a plain loop.
 

@@ -215,41 +215,29 @@ int effects_group(aegis_handle *h, const Planned &P, int32_t c0, int32_t c1, con
     tiles.insert(tiles.end(), whole.begin(), whole.end());
 
     hipStream_t s = h->stream;
-    int rc;
     const bool s16 = in_format == AEGIS_PCM_S16;
     bool want_i16 = false;
     for (size_t c = 0; c < nc; ++c) want_i16 = want_i16 || (out_i16 && out_i16[c0 + (int32_t)c]);
-#define ENS(buf, bytes) if ((rc = ensure(h, h->buf, (size_t)(bytes))) != AEGIS_OK) return rc
-    ENS(fx_a, (size_t)total * 8); ENS(fx_b, (size_t)total * 8);
-    ENS(fx_recs, recs.size() * sizeof(FxClip)); ENS(fx_tiles, tiles.size() * sizeof(FxTile));
-    ENS(fx_peak, recs.size() * 8); ENS(fx_taps, std::max<size_t>(P.taps.size(), 1) * 8);
-    if (s16 || want_i16) ENS(fx_i16, (size_t)total * 2);
-#undef ENS
-    // From here on the stream may still read the host vectors above: an error return waits for it first.
-#define HIPCHK_SYNC(expr)                                                                       \
-    do {                                                                                        \
-        hipError_t e__ = (expr);                                                                \
-        if (e__ != hipSuccess) {                                                                \
-            h->err = std::string(#expr) + ": " + hipGetErrorString(e__);                        \
-            (void)hipStreamSynchronize(s);                                                      \
-            return AEGIS_ERR_DEVICE;                                                            \
-        }                                                                                       \
-    } while (0)
+    ENSURE(h, fx_a, (size_t)total * 8); ENSURE(h, fx_b, (size_t)total * 8);
+    ENSURE(h, fx_recs, recs.size() * sizeof(FxClip)); ENSURE(h, fx_tiles, tiles.size() * sizeof(FxTile));
+    ENSURE(h, fx_peak, recs.size() * 8); ENSURE(h, fx_taps, std::max<size_t>(P.taps.size(), 1) * 8);
+    if (s16 || want_i16) ENSURE(h, fx_i16, (size_t)total * 2);
+    // From here on the stream may still read the host vectors above: HIPCHK_SYNC.
     double *buf0 = static_cast<double *>(h->fx_a.p), *buf1 = static_cast<double *>(h->fx_b.p);
     int16_t *d_i16 = static_cast<int16_t *>(h->fx_i16.p);
     const FxClip *d_recs = static_cast<const FxClip *>(h->fx_recs.p);
     const FxTile *d_tiles = static_cast<const FxTile *>(h->fx_tiles.p);
     unsigned long long *d_peak = static_cast<unsigned long long *>(h->fx_peak.p);
     const double *d_taps = static_cast<const double *>(h->fx_taps.p);
-    HIPCHK_SYNC(hipMemcpyAsync(h->fx_recs.p, recs.data(), recs.size() * sizeof(FxClip), hipMemcpyHostToDevice, s));
-    HIPCHK_SYNC(hipMemcpyAsync(h->fx_tiles.p, tiles.data(), tiles.size() * sizeof(FxTile), hipMemcpyHostToDevice, s));
-    if (!P.taps.empty()) HIPCHK_SYNC(hipMemcpyAsync(h->fx_taps.p, P.taps.data(), P.taps.size() * 8, hipMemcpyHostToDevice, s));
-    HIPCHK_SYNC(hipMemsetAsync(h->fx_peak.p, 0, recs.size() * 8, s));
+    HIPCHK_SYNC(h, s, hipMemcpyAsync(h->fx_recs.p, recs.data(), recs.size() * sizeof(FxClip), hipMemcpyHostToDevice, s));
+    HIPCHK_SYNC(h, s, hipMemcpyAsync(h->fx_tiles.p, tiles.data(), tiles.size() * sizeof(FxTile), hipMemcpyHostToDevice, s));
+    if (!P.taps.empty()) HIPCHK_SYNC(h, s, hipMemcpyAsync(h->fx_taps.p, P.taps.data(), P.taps.size() * 8, hipMemcpyHostToDevice, s));
+    HIPCHK_SYNC(h, s, hipMemsetAsync(h->fx_peak.p, 0, recs.size() * 8, s));
     for (size_t c = 0; c < nc; ++c) {
         const int64_t n = off[c + 1] - off[c];
         if (n == 0) continue;
-        if (s16) HIPCHK_SYNC(hipMemcpyAsync(d_i16 + off[c], in[c0 + (int32_t)c], (size_t)n * 2, hipMemcpyHostToDevice, s));
-        else HIPCHK_SYNC(hipMemcpyAsync(buf0 + off[c], in[c0 + (int32_t)c], (size_t)n * 8, hipMemcpyHostToDevice, s));
+        if (s16) HIPCHK_SYNC(h, s, hipMemcpyAsync(d_i16 + off[c], in[c0 + (int32_t)c], (size_t)n * 2, hipMemcpyHostToDevice, s));
+        else HIPCHK_SYNC(h, s, hipMemcpyAsync(buf0 + off[c], in[c0 + (int32_t)c], (size_t)n * 8, hipMemcpyHostToDevice, s));
     }
     if (s16) {
         begin_event(h, "fx_load", s);
@@ -280,19 +268,18 @@ int effects_group(aegis_handle *h, const Planned &P, int32_t c0, int32_t c1, con
         fx_i16(d_recs, d_tiles + at_whole, buf0, buf1, d_i16, (int32_t)whole.size(), s);
         end_event(h, s);
     }
-    HIPCHK_SYNC(hipGetLastError());
+    HIPCHK_SYNC(h, s, hipGetLastError());
     for (size_t c = 0; c < nc; ++c) {
         const int64_t n = off[c + 1] - off[c];
         if (n == 0) continue;
         const int32_t cc = c0 + (int32_t)c;
         if (out_f64 && out_f64[cc])
-            HIPCHK_SYNC(hipMemcpyAsync(out_f64[cc], (src[c] ? buf1 : buf0) + off[c], (size_t)n * 8, hipMemcpyDeviceToHost, s));
-        if (out_i16 && out_i16[cc]) HIPCHK_SYNC(hipMemcpyAsync(out_i16[cc], d_i16 + off[c], (size_t)n * 2, hipMemcpyDeviceToHost, s));
+            HIPCHK_SYNC(h, s, hipMemcpyAsync(out_f64[cc], (src[c] ? buf1 : buf0) + off[c], (size_t)n * 8, hipMemcpyDeviceToHost, s));
+        if (out_i16 && out_i16[cc]) HIPCHK_SYNC(h, s, hipMemcpyAsync(out_i16[cc], d_i16 + off[c], (size_t)n * 2, hipMemcpyDeviceToHost, s));
     }
-    HIPCHK_SYNC(hipStreamSynchronize(s));
+    HIPCHK_SYNC(h, s, hipStreamSynchronize(s));
     if (h->profiling) collect_events(h);
     return AEGIS_OK;
-#undef HIPCHK_SYNC
 }
 
 }  // namespace
@@ -327,22 +314,9 @@ int aegis_effects(aegis_handle *h, int32_t sample_rate, int32_t n_clips, const v
     DEVICE_ONLY(h);
     if (n_clips == 0) return AEGIS_OK;
     HIPCHK(h, hipSetDevice(h->device));
-    // One device pass for the whole batch; when its buffers cannot be allocated, passes of half as many clips (clips are
-    // independent: the result does not depend on the grouping), as aegis_synth_adsr does.
-    int32_t group = n_clips;
-    for (int32_t c0 = 0; c0 < n_clips;) {
-        const int32_t c1 = std::min(n_clips, c0 + group);
-        const int rc = effects_group(h, P, c0, c1, in, in_format, n_samples, out_f64, out_i16);
-        if (rc == AEGIS_ERR_NOMEM && group > 1) {
-            (void)hipDeviceSynchronize();
-            (void)hipGetLastError();
-            group = (group + 1) / 2;
-            continue;
-        }
-        if (rc != AEGIS_OK) { drop_events(h); return rc; }
-        c0 = c1;
-    }
-    return AEGIS_OK;
+    return run_halving(h, n_clips, [&](int32_t c0, int32_t c1) {
+        return effects_group(h, P, c0, c1, in, in_format, n_samples, out_f64, out_i16);
+    });
     } catch (...) { return abi_fail(h); }
 }
 

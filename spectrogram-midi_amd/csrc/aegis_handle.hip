@@ -184,7 +184,6 @@ int aegis_create(const aegis_config *cfg, aegis_handle **out) {
     CRTHIP(hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking));
     CRTHIP(hipStreamCreateWithFlags(&h->stream3, hipStreamNonBlocking));
     if (const char *e = std::getenv("AEGIS_NOTEFIT_STORE")) h->notefit_store = (e[0] == '1');  // aegis_note_fit: candidates stored once instead of recomputed per frame
-    if (const char *e = std::getenv("AEGIS_SYNTH_STORE")) h->synth_store = (e[0] == '1');      // aegis_synth_adsr: stored notes instead of recomputed ones
     if (const char *e = std::getenv("AEGIS_TEST_DROP_CHUNK_SIGNAL")) h->test_drop_signal = std::atoi(e);
     CRTHIP(hipDeviceGetAttribute(&h->n_cus, hipDeviceAttributeMultiprocessorCount, c.device));
     if (auto_pass) {

@@ -5,9 +5,11 @@
 //   aegis_stream.hip  aegis_stream_* (graph capture, commit delivery)
 //   aegis_cqt.hip     CQT, chroma, the filter-bank cache, aegis_estimate_tuning, aegis_rake_patterns
 //   aegis_trend.hip   aegis_trend, aegis_ghost_rsi
-//   aegis_synth.hip   aegis_synth_* (the ADSR soft-synth; kernels in synth.hip, the MIDI reader in synth_smf.cpp)
+//   aegis_synth.hip   aegis_synth_* (the ADSR soft-synth, one envelope per clip or per note; kernels in adsr.hip, host
+//                     preparation in adsr_host.h, the MIDI reader in synth_smf.cpp)
 //   aegis_effects.hip aegis_reverb_ir, aegis_effects (the effect chain; kernels in effects.hip)
-//   aegis_notefit.hip aegis_note_fit, aegis_synth_one_note, aegis_synth_adsr_notes (the per-note optimiser; kernels in notefit.hip)
+//   aegis_notefit.hip aegis_note_fit, aegis_compare_audio, aegis_synth_one_note (the per-note optimiser; kernels in
+//                     notefit.hip and adsr.hip)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -116,13 +118,12 @@ struct aegis_handle {
     DevBuf t_pa;                              // scratch of the fused pitch analysis: 12 rows of doubles + 1 of bytes
     DevBuf io_pcm, io_f0, io_voiced, io_vprob, io_rms, io_rake, io_sdb, io_bin, io_colmean;
     DevBuf pcm_raw, pcm_clips, pcm_ranges, pcm_taps;   // aegis_analyze_pcm: raw bytes, clip table, per-chunk range tables, filters
-    DevBuf sy_notes, sy_clips, sy_tiles, sy_tile_notes, sy_note_peak, sy_clip_peak, sy_mix, sy_out, sy_sig;   // aegis_synth_adsr: records, float64 mix, int16 result
+    DevBuf sy_oscs, sy_notes, sy_tiles, sy_tile_notes, sy_osc_peak, sy_clip_peak, sy_mix, sy_out;   // aegis_synth_adsr / aegis_synth_adsr_notes: records, peaks, float64 mix, int16 result
     DevBuf fx_a, fx_b, fx_recs, fx_tiles, fx_peak, fx_taps, fx_i16;   // aegis_effects: the two float64 batch buffers, records, clip maxima, taps, int16 in / out
-    // aegis_note_fit / aegis_synth_one_note / aegis_synth_adsr_notes: slices, records, per-frame features, scores; stored note, mix
+    // aegis_note_fit / aegis_compare_audio / aegis_synth_one_note: slices, records, per-frame features, scores; stored note
     DevBuf nf_audio, nf_oscs, nf_cands, nf_notes, nf_boff, nf_peak, nf_cnum, nf_cden, nf_zc, nf_rms, nf_out, nf_best;
-    DevBuf nf_sig, nf_sigoff, nf_cands2, nf_tiles, nf_tile_notes, nf_cpeak, nf_mix, nf_i16;
+    DevBuf nf_sig, nf_sigoff, nf_cands2;
     bool notefit_store = false;               // AEGIS_NOTEFIT_STORE=1 at create: every candidate rendered once into nf_sig and read by the frames instead of recomputed
-    bool synth_store = false;                 // AEGIS_SYNTH_STORE=1 at create: notes stored by the peak kernel and read by the mix (sy_sig) instead of recomputed
     int32_t lag_stride = 0, yin_stride = 0, obs_stride = 0;
     aegis::CallPlan plan;                     // the last call's plan: its host arrays stay alive until the stream drained
     bool plan_in_flight = false;              // the stream may still read them
@@ -180,6 +181,24 @@ struct aegis_stream {
             return AEGIS_ERR_DEVICE;                                                            \
         }                                                                                       \
     } while (0)
+// HIPCHK for code behind the first asynchronous copy of a call: stream s may still read host vectors of the caller's
+// frame, so an error return waits for it first.
+#define HIPCHK_SYNC(h, s, expr)                                                                 \
+    do {                                                                                        \
+        hipError_t e__ = (expr);                                                                \
+        if (e__ != hipSuccess) {                                                                \
+            (h)->err = std::string(#expr) + ": " + hipGetErrorString(e__);                      \
+            (void)hipStreamSynchronize(s);                                                      \
+            return AEGIS_ERR_DEVICE;                                                            \
+        }                                                                                       \
+    } while (0)
+// h->buf holds at least `bytes` afterwards, and at least 8 (an empty vector still gets a valid pointer), or the caller returns
+// what ensure() answered
+#define ENSURE(h, buf, bytes)                                                                               \
+    do {                                                                                                    \
+        const int rc__ = aegis::ensure(h, (h)->buf, std::max<size_t>((size_t)(bytes), 8));                 \
+        if (rc__ != AEGIS_OK) return rc__;                                                                  \
+    } while (0)
 #define DEVICE_ONLY(h) \
     do { if ((h)->device < 0) { (h)->err = "handle was created with device=-1 (host tables only)"; return AEGIS_ERR_DEVICE; } } while (0)
 
@@ -190,6 +209,9 @@ int grow_buf(aegis_handle *h, std::vector<DevBuf *> &owner, DevBuf &b, size_t by
 // b holds at least `bytes` afterwards (growth rule, the fail_allocs hook and the owner's list: grow_buf)
 inline int ensure(aegis_handle *h, DevBuf &b, size_t bytes) { return bytes <= b.cap ? AEGIS_OK : grow_buf(h, h->bufs, b, bytes); }
 inline int ensure(aegis_stream *st, DevBuf &b, size_t bytes) { return bytes <= b.cap ? AEGIS_OK : grow_buf(st->h, st->bufs, b, bytes); }
+inline hipError_t upload(DevBuf &b, const void *src, size_t bytes, hipStream_t s) {
+    return bytes ? hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
+}
 void free_bufs(std::vector<DevBuf *> &owner) noexcept;
 int new_event(aegis_handle *h, hipEvent_t *e, unsigned flags);
 void destroy_now(aegis_handle *h) noexcept;
@@ -202,6 +224,27 @@ void begin_event(aegis_handle *h, const char *name, hipStream_t s);
 void end_event(aegis_handle *h, hipStream_t s);
 void drop_events(aegis_handle *h) noexcept;       // destroys the pairs not collected
 void collect_events(aegis_handle *h);
+
+// One device pass for the whole batch of n independent items (clips, notes, pairs): group(i0, i1) runs items [i0, i1).
+// When its buffers cannot be allocated (AEGIS_ERR_NOMEM) the batch is cut into passes of half as many items and the rest
+// is tried again: an item's result does not depend on the grouping.  Any other failure drops the profiling events.
+template <class F>
+int run_halving(aegis_handle *h, int32_t n, F &&group) {
+    int32_t size = n;
+    for (int32_t i0 = 0; i0 < n;) {
+        const int32_t i1 = std::min(n, i0 + size);
+        const int rc = group(i0, i1);
+        if (rc == AEGIS_ERR_NOMEM && size > 1) {
+            (void)hipDeviceSynchronize();
+            (void)hipGetLastError();
+            size = (size + 1) / 2;
+            continue;
+        }
+        if (rc != AEGIS_OK) { drop_events(h); return rc; }
+        i0 = i1;
+    }
+    return AEGIS_OK;
+}
 
 // ---- kernel parameters every entry fills the same way (aegis_api.hip) ----
 struct RakeBounds { int min_frames, max_frames; };

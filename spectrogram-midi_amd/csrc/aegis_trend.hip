@@ -29,11 +29,8 @@ int aegis_ghost_rsi(aegis_handle *h, const int64_t *ev_a, const int64_t *ev_b, c
     std::lock_guard<std::mutex> lock(h->mu);
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
-    int rc;
-#define ENS(buf, bytes) if ((rc = ensure(h, h->buf, (size_t)(bytes))) != AEGIS_OK) return rc
-    ENS(t_x, std::max<int64_t>(total, 1) * 8); ENS(t_a, std::max<int64_t>(total, 1) * 8); ENS(t_b, std::max<int64_t>(total, 1) * 8);
-    ENS(t_off, (n_series + 1) * 8); ENS(t_i64a, 2 * E * 8); ENS(t_i64b, E * 4 + 8); ENS(t_c, 2 * E * 8);
-#undef ENS
+    ENSURE(h, t_x, std::max<int64_t>(total, 1) * 8); ENSURE(h, t_a, std::max<int64_t>(total, 1) * 8); ENSURE(h, t_b, std::max<int64_t>(total, 1) * 8);
+    ENSURE(h, t_off, (n_series + 1) * 8); ENSURE(h, t_i64a, 2 * E * 8); ENSURE(h, t_i64b, E * 4 + 8); ENSURE(h, t_c, 2 * E * 8);
     int64_t *d_ab = static_cast<int64_t *>(h->t_i64a.p);
     int32_t *d_sid = static_cast<int32_t *>(h->t_i64b.p);
     double *d_out = static_cast<double *>(h->t_c.p);
@@ -79,11 +76,9 @@ int aegis_trend(aegis_handle *h, int32_t op, const double *x, const int64_t *off
     if (total == 0) return AEGIS_OK;
     for (int i = 0; i < n_series; ++i)
         if (offsets[i + 1] < offsets[i]) { h->err = "offsets must be non-decreasing"; return AEGIS_ERR_INVALID; }
-#define ENS(buf, bytes) if ((rc = ensure(h, h->buf, (size_t)(bytes))) != AEGIS_OK) return rc
-    ENS(t_x, n_in * 8); ENS(t_off, (n_series + 1) * 8);
-    ENS(t_a, total * 8); ENS(t_b, total * 8); ENS(t_c, total * 8); ENS(t_d, total * 8); ENS(t_e, std::max<int64_t>(total, 256) * 8);
-    ENS(t_i8, total); ENS(t_i64a, total * 8); ENS(t_i64b, (n_series + 1) * 8);
-#undef ENS
+    ENSURE(h, t_x, n_in * 8); ENSURE(h, t_off, (n_series + 1) * 8);
+    ENSURE(h, t_a, total * 8); ENSURE(h, t_b, total * 8); ENSURE(h, t_c, total * 8); ENSURE(h, t_d, total * 8); ENSURE(h, t_e, std::max<int64_t>(total, 256) * 8);
+    ENSURE(h, t_i8, total); ENSURE(h, t_i64a, total * 8); ENSURE(h, t_i64b, (n_series + 1) * 8);
     HIPCHK(h, hipMemcpyAsync(h->t_x.p, x, n_in * 8, hipMemcpyHostToDevice, s));
     HIPCHK(h, hipMemcpyAsync(h->t_off.p, offsets, (n_series + 1) * 8, hipMemcpyHostToDevice, s));
     TrendArgs a{static_cast<const double *>(h->t_x.p), static_cast<const int64_t *>(h->t_off.p), n_series, total};

@@ -1,7 +1,7 @@
 // Effect-chain kernels (gfx950), float64.  Reference: aegis_engine_core/effect_learning_loop.py:56-231 (distortion,
 // reverb, delay, chorus), each followed by a whole-clip normalisation.  A stage of a chain is two passes over the clip:
 // the effect itself, which also takes the clip's max |.| by an integer atomic max on the bit pattern (order-independent,
-// as synth.hip takes the mix peak), and fx_scale_kernel, which applies the normalisation that maximum decides.
+// as adsr.hip takes the mix peak), and fx_scale_kernel, which applies the normalisation that maximum decides.
 // Every operation is an IEEE add, multiply, divide, floor, compare or max in the reference's order; the file is built
 // with -ffp-contract=off and without fast-math.  The one fusion is the explicit fma() of the reverb's sum.
 //

@@ -2,9 +2,9 @@
 // (aegis_note_fit): every candidate of every note is the reference's synthesize_note truncated to the note's slice of the
 // original audio, scored against that slice by three features -- the correlation of the 512 / 256 RMS tracks, the mean
 // spectral centroid of the 2048 / 512 STFT, the mean zero-crossing rate of the 2048 / 512 frames -- and the first maximum
-// wins.  Four kernels (notefit.hip): the peak of every oscillator (the candidates of a note that share waveform and
-// duration share it), the features of every (signal, frame), the score of every candidate, the choice of every note.
-// Candidates are never stored: a frame recomputes the samples it covers from the oscillator.
+// wins.  Four kernels: the peak of every oscillator (adsr.hip; the candidates of a note that share waveform and duration
+// share it), then in notefit.hip the features of every (signal, frame), the score of every candidate, the choice of every
+// note.  Candidates are never stored: a frame recomputes the samples it covers from the oscillator (adsr.h).
 //
 // A result is a pure function of the candidate's samples and the slice: every sum has a fixed order (a tree over the 256
 // threads of a frame, a serial loop over the frames of a track), nothing is accumulated across workgroups.
@@ -20,6 +20,7 @@
 #include <cmath>
 #include <cstdint>
 
+#include "adsr.h"
 #include "fft8.h"
 
 namespace aegis {
@@ -30,27 +31,6 @@ constexpr int kFitBins = kFitFft / 2 + 1;
 constexpr int kFitRms = 512;             // rms frame: max(512, int(sr * 0.01)), which is 512 below 51.3 kHz (the entry checks)
 constexpr int kFitRmsHop = kFitRms / 2;
 constexpr int kFitThreads = 256;
-constexpr int kFitTile = 1024;           // output samples per workgroup of the per-note mix
-
-// One oscillator: the summed harmonics of one (note, waveform, full duration).  Same preparation as SynthNote (synth.h).
-struct FitOsc {
-    double fh[5];                        // freq * h (sine / square: (2 pi) * (freq * h)); the first n_harm are used
-    double step;                         // full_duration / n
-    int64_t n;                           // int(sr * full_duration): the peak is taken over all of them
-    int32_t n_harm;
-    int32_t waveform;                    // AEGIS_WAVE_*
-};
-
-// One candidate: an envelope and a velocity on an oscillator.
-struct FitCand {
-    int64_t attack, decay, release, sustain;     // segment lengths in samples (sustain = max(0, n - a - d - r))
-    double attack_step, decay_step, release_step, sustain_level;
-    double vel;                          // max(0, min(1, velocity / 127))
-    int64_t n_cut;                       // samples that count: min(n, slice length) for a fit, min(n, total - start) for a mix
-    int64_t start;                       // per-note mix: first output sample; a given signal (osc < 0): its first sample in the audio
-    int32_t osc;                         // < 0: the candidate is not synthesised, its n_cut samples are read (aegis_compare_audio)
-    int32_t note;
-};
 
 // One note of a fit.  Its signals are j = 0 (the slice) and j = 1 .. n_cand (candidates cand0 + j - 1), all of length L.
 struct FitNote {
@@ -66,8 +46,8 @@ struct FitNote {
 
 struct FitArgs {
     const double *audio;                 // slices (float32 widened on the host) and given signals, back to back
-    const FitOsc *oscs;
-    const FitCand *cands;
+    const AdsrOsc *oscs;
+    const AdsrNote *cands;               // the candidates (adsr.h: a note whose n_cut is cut to the slice)
     const FitNote *notes;
     const int64_t *block_off;            // [n_notes + 1]: FitNote::block0 of every note, then the grid size
     int32_t n_oscs, n_cands, n_notes;
@@ -83,62 +63,13 @@ struct FitArgs {
     int32_t *best;                       // [n_notes]: index within the note of the first maximum (-1: no candidates)
 };
 
-// ---- the candidate signal (synthesizer.py:226-374), as synth.hip states it ---------------------------------------------
-AEGIS_HD double fit_osc(double f, double t, int waveform) {
-    if (waveform == 0) return sin(f * t);
-    if (waveform == 2) {
-        const double v = sin(f * t);
-        return v > 0.0 ? 1.0 : (v < 0.0 ? -1.0 : 0.0);
-    }
-    const double x = f * t;
-    const double phase = x - floor(x);
-    const double saw = 2.0 * phase - 1.0;
-    if (waveform == 1) return saw;
-    return 2.0 * fabs(saw) - 1.0;
-}
-
-AEGIS_HD double fit_harmonics(const FitOsc &o, int64_t i) {
-    const double t = (double)i * o.step;
-    double sig = fit_osc(o.fh[0], t, o.waveform);
-    double amp = 0.5;
-#pragma unroll
-    for (int h = 1; h < 5; ++h) {
-        if (h < o.n_harm) sig = sig + amp * fit_osc(o.fh[h], t, o.waveform);
-        amp = amp * 0.5;
-    }
-    return sig;
-}
-
-AEGIS_HD double fit_envelope(const FitCand &c, int64_t i) {
-    if (i < c.attack) return (double)i * c.attack_step;
-    i -= c.attack;
-    if (i < c.decay) return (double)i * c.decay_step + 1.0;
-    i -= c.decay;
-    if (i < c.sustain) return c.sustain_level;
-    i -= c.sustain;
-    if (i < c.release) {
-        if (c.release == 1) return c.sustain_level;
-        if (i == c.release - 1) return 0.0;
-        return (double)i * c.release_step + c.sustain_level;
-    }
-    return 0.0;
-}
-
-// sample i of a candidate, 0 <= i < its oscillator's n: harmonics, / peak, * envelope, * velocity
-AEGIS_HD double fit_cand_sample(const FitOsc &o, const FitCand &c, double peak, int64_t i) {
-    double v = fit_harmonics(o, i);
-    if (peak > 0.0) v = v / peak;
-    v = v * fit_envelope(c, i);
-    return v * c.vel;
-}
-
 // sample i of signal j of a note, 0 <= i < L (a candidate is zero beyond n_cut)
 AEGIS_HD double fit_signal_sample(const FitArgs &a, const FitNote &nt, int j, int64_t i) {
     if (j == 0) return i < nt.n_slice ? a.audio[nt.audio_off + i] : 0.0;
-    const FitCand &c = a.cands[nt.cand0 + j - 1];
+    const AdsrNote &c = a.cands[nt.cand0 + j - 1];
     if (i >= c.n_cut) return 0.0;
     if (c.osc < 0) return a.audio[c.start + i];
-    return fit_cand_sample(a.oscs[c.osc], c, a.osc_peak[c.osc], i);
+    return adsr_sample(a.oscs[c.osc], c, a.osc_peak[c.osc], i);
 }
 
 // ---- one thread's share of each phase of a frame ------------------------------------------------------------------------
@@ -268,20 +199,8 @@ AEGIS_HD int32_t fit_best(const double *out, const FitNote &nt) {
 }
 
 // ---- launches (notefit.hip) ---------------------------------------------------------------------------------------------
-// kernels (stable names for the profiler): notefit_peak_kernel, notefit_feat_kernel, notefit_score_kernel,
-// notefit_best_kernel, notefit_render_kernel, notefit_mix_kernel
-void launch_notefit_peak(const FitOsc *oscs, double *osc_peak, int32_t n_oscs, hipStream_t s);
+// kernels (stable names for the profiler): notefit_feat_kernel, notefit_score_kernel, notefit_best_kernel
 void launch_notefit_feat(const FitArgs &a, hipStream_t s);
 void launch_notefit_score(const FitArgs &a, hipStream_t s);
-// sig[sig_off[c] + i] = sample i of candidate c, i < n_cut (ADSRSynthesizer.synthesize_note, and the tests' view of a candidate)
-void launch_notefit_render(const FitOsc *oscs, const FitCand *cands, const double *osc_peak, const int64_t *sig_off, double *sig,
-                           int32_t n_cands, hipStream_t s);
-
-// the per-note mix (synthesize_with_per_note_params): SynthTile lists as in synth.h, but note q of tile_notes is candidate q
-struct FitMixTile { int64_t out_off, total, first; int32_t note_lo, note_hi; int32_t clip; int32_t reserved; };
-void launch_notefit_mix(const FitOsc *oscs, const FitCand *cands, const double *osc_peak, const FitMixTile *tiles,
-                        const int32_t *tile_notes, double *mixed, unsigned long long *clip_peak_bits, int32_t n_tiles, hipStream_t s);
-void launch_notefit_master(const FitMixTile *tiles, const double *mixed, const unsigned long long *clip_peak_bits, int16_t *out,
-                           int32_t n_tiles, hipStream_t s);
 
 }  // namespace aegis

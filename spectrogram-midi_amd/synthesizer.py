@@ -4,7 +4,7 @@ the reference's names and return values.  MIDI bytes go in, the WAV bytes `wave`
 of the reference bit for bit for sawtooth, triangle and square, and within one int16 step for sine.
 
 The MIDI file is read by the library's own reader (csrc/synth_smf.cpp: mido is not a dependency), the per-sample work
-runs in csrc/synth.hip (`aegis_synth_adsr`).  There is no CPU path.  `FluidSynthSynthesizer` and `synthesize_midi` are
+runs in csrc/adsr.hip (`aegis_synth_adsr`).  There is no CPU path.  `FluidSynthSynthesizer` and `synthesize_midi` are
 not ported.  New here: `synthesize_midi_adsr_batch`, any number of files with their own parameters in one device call
 (what Auto-Match renders a stage of candidates with, auto_matcher.py)."""
 import io

@@ -83,6 +83,21 @@ def test_delay_and_empty_chain_equal_goldens(gpu_handle, gold):
         assert np.array_equal(q, gold[f"{c['name']}.pcm"]), c["name"]
 
 
+def test_allocation_failure_cuts_the_batch_and_gives_the_same_samples(gpu_handle):
+    """A fresh handle has to grow its workspace and the first growth fails: the batch of two is cut into single clips."""
+    clips = [seeded(3000, 3), seeded(5000, 5, 1.2)]
+    chains = [[("distortion", {"drive": 0.4}), ("delay", {"delay_ms": 7, "feedback": 0.5})]] * 2
+    f64, i16 = run(gpu_handle, clips, chains)
+    h = _lib.Handle(device=0, scipy_tables=False)
+    try:
+        h.lib.aegis_debug_fetch(h._h, b"fail_allocs", None, 1)
+        cut64, cut16 = run(h, clips, chains)
+    finally:
+        h.close()
+    for k in range(2):
+        assert f64[k].any() and np.array_equal(cut64[k], f64[k]) and np.array_equal(cut16[k], i16[k]), k
+
+
 def test_delay_restated_edges_equal(gpu_handle):
     D = 56                                    # int(7 / 1000 * 8000)
     clips, chains = [], []

@@ -94,6 +94,22 @@ def test_compare_note_audio_is_the_same_call(gpu_handle):
 
 
 # ------------------------------------------------------------------------------------------------ the candidate signal
+def test_compare_audio_survives_a_failed_allocation(gpu_handle):
+    """A fresh handle has to grow its workspace and the first growth fails: the three pairs are cut into groups of two and one."""
+    rng = np.random.default_rng(11)
+    t = np.arange(4096) / 22050
+    pairs = [(np.sin(2 * np.pi * f * t) * np.exp(-3 * t), 0.8 * np.sin(2 * np.pi * f * t + 0.3) + 0.05 * rng.uniform(-1, 1, 4096))
+             for f in (196.0, 330.0, 523.25)]
+    want = gpu_handle.compare_audio(pairs, 22050)
+    h = _lib.Handle(device=0, scipy_tables=False)
+    try:
+        h.lib.aegis_debug_fetch(h._h, b"fail_allocs", None, 1)
+        got = h.compare_audio(pairs, 22050)
+    finally:
+        h.close()
+    assert want.shape == (3, 4) and want[:, 0].all() and got.tobytes() == want.tobytes()
+
+
 def note_shapes():
     """(sr, freq, full duration, velocity, attack, decay, sustain, release): the lengths, envelopes, harmonic counts and
     velocities at which the candidate signal can go wrong."""

@@ -1,4 +1,4 @@
-"""GPU checks of the ADSR soft-synth (csrc/synth.hip) and of Auto-Match on top of it.
+"""GPU checks of the ADSR soft-synth (csrc/adsr.hip) and of Auto-Match on top of it.
 
 Exactness rules: for sawtooth, triangle and square every operation on the path is an IEEE add, multiply,
 divide, floor, compare or max in the reference's order, and the square wave reads only the sign of sin -- the int16
@@ -142,6 +142,62 @@ def test_allocation_failure_cuts_the_batch_and_gives_the_same_samples(gold):
             np.testing.assert_array_equal(a, gold[f"{n}.pcm"], err_msg=n)
     finally:
         h.close()
+
+
+# ------------------------------------------------------------------------------------- one code path for both entries
+def test_one_envelope_and_per_note_entries_give_the_same_samples(gpu_handle):
+    """aegis_synth_adsr and aegis_synth_adsr_notes run the same kernels on the same records (csrc/adsr.hip), so a clip
+    whose notes all carry the clip's parameters must give the same int16 samples through both, `sine` included: the device
+    sin is the same on both sides.  One call each at 22050 Hz.  Clip A (1.0 s, sawtooth, release 250.0 ms) and clip B
+    (0.5 s, sine, attack 0, decay 0, sustain 1.0, release 125.0 ms) hold seven notes each: two overlapping across a
+    1024-sample tile border, one covering whole tiles (three in B; six in A, whose release alone is 5512 samples), one
+    ending on the last sample of a tile, one truncated by the end of the file, one starting at (A) or past (B) the end,
+    one with velocity 0.  A release of exactly one sample needs a third parameter set, and one envelope per clip then a third
+    clip: C (0.25 s, triangle, release 0.0625 ms) rides in the same two calls with seven notes of the same kinds."""
+    sr = 22050
+
+    def clip(length, rows, **p):
+        rel = p["release_ms"]
+        notes = np.zeros(len(rows), _lib.SYNTH_NOTE_DTYPE)
+        for q, (k, n, midi, vel) in enumerate(rows):
+            notes[q] = ((k + 0.5) / sr, (n + 0.5) / sr - rel / 1000.0, midi, vel)
+            assert notes[q]["duration"] >= 0.0
+            assert int(notes[q]["start"] * sr) == k and int(sr * (notes[q]["duration"] + rel / 1000.0)) == n      # the placement is the intended one
+        return notes, length, p
+
+    a = clip(1.0, [(1000, 6000, 45, 100), (1020, 5600, 52, 90),          # both cross sample 1024
+                   (8192, 6144, 64, 80),                                   # tiles 8 .. 13, whole
+                   (15000, 21504 - 15000, 57, 110),                        # ends on sample 21503, the last of tile 20
+                   (36000, 6000, 100, 127),                                # cut at 38587; four harmonics below 11025 Hz
+                   (38587, 5600, 60, 100),                                 # starts at the end: skipped
+                   (22000, 7000, 40, 0)],                                  # velocity 0
+             attack_ms=3, decay_ms=20, sustain_level=0.6, release_ms=250.0, waveform="sawtooth")
+    b = clip(0.5, [(1000, 2800, 45, 100), (1023, 2757, 52, 90), (4096, 3072, 64, 80), (8000, 11264 - 8000, 57, 110),
+                   (23000, 3000, 100, 127), (25306, 2800, 60, 100), (12000, 3000, 40, 0)],
+             attack_ms=0, decay_ms=0, sustain_level=1.0, release_ms=125.0, waveform="sine")
+    c = clip(0.25, [(1000, 100, 45, 100), (1020, 10, 52, 90), (2000, 2000, 64, 80), (5000, 5120 - 5000, 57, 110),
+                    (16500, 100, 100, 127), (16538, 60, 60, 100), (6000, 50, 40, 0)],
+             attack_ms=1.0, decay_ms=2.0, sustain_level=0.5, release_ms=0.0625, waveform="triangle")
+    assert int(sr * 0.0625 / 1000.0) == 1
+    clips = [a, b, c]
+    lib = gpu_handle.lib
+    for (notes, length, p), want in zip(clips, (int(22050 * 1.75), int(22050 * 1.125), None)):
+        par = _lib.Handle.adsr_params(**p)
+        per_note = (_lib.AdsrParams * len(notes))(*[par] * len(notes))
+        one = lib.aegis_synth_samples_for(sr, length, par)
+        assert one == lib.aegis_synth_notes_samples_for(sr, length, per_note, len(notes)) and one > 0       # the premise: one file length
+        assert want is None or one == want
+    assert lib.aegis_synth_samples_for(sr, 1.0, _lib.Handle.adsr_params(**a[2])) == 38587
+    pars = [_lib.Handle.adsr_params(**p) for _, _, p in clips]
+    one = gpu_handle.synth_adsr([n for n, _, _ in clips], [ln for _, ln, _ in clips], pars, sr)
+    per = gpu_handle.synth_adsr_notes([n for n, _, _ in clips], [ln for _, ln, _ in clips], [[q] * len(n) for (n, _, _), q in zip(clips, pars)], sr)
+    for name, x, y in zip("ABC", one, per):
+        assert x.dtype == y.dtype == np.int16 and x.any()
+        print(f"clip {name}: {len(x)} samples, {int((x != y).sum())} differ between the entries")
+        assert np.array_equal(x, y), f"clip {name}"
+    for name, (notes, length, p), x in zip("ABC", clips, one):
+        if p["waveform"] != "sine":
+            assert np.array_equal(x, R.render_notes(notes.tolist(), length, sr, **p)), f"clip {name} against the restatement"
 
 
 # ---------------------------------------------------------------------------------------------------- item 8

@@ -1,4 +1,4 @@
-"""GPU checks of the per-note render (aegis_synth_adsr_notes, csrc/notefit.hip; the reference's
+"""GPU checks of the per-note render (aegis_synth_adsr_notes, csrc/adsr.hip; the reference's
 synthesize_with_per_note_params, per_note_optimizer.py:549-659): every note with its own envelope and waveform.
 
 Exactness rules as for the one-envelope render: the int16 samples EQUAL the reference's for sawtooth,

@@ -4,15 +4,13 @@ is there).  Not a pass/fail check: tests/test_gpu_synth.py asserts, this records
   python tools/bench_automatch.py                     # everything below
   python tools/bench_automatch.py --synth-only        # the 27 x 30 s batch alone (the run to put under
                                                       #   rocprofv3 --kernel-trace --stats -d DIR -- python ...)
-  python tools/bench_automatch.py --kernel-stats CSV  # no GPU: folds the synth_* rows of a rocprofv3 *_kernel_stats.csv in
+  python tools/bench_automatch.py --kernel-stats CSV  # no GPU: folds the adsr_* rows of a rocprofv3 *_kernel_stats.csv in
   python tools/bench_automatch.py --scoring loop|batch [--label NAME] [--searches 3]
                                                       # the search alone, candidate by candidate or batched: a warm-up
                                                       #   search, then the median of --searches, into
                                                       #   profiles/automatch_batch.json under NAME (default: the mode)
 
 Recorded:
-  synth_batch_store_mode   the same batch on a handle created under AEGIS_SYNTH_STORE=1 (notes stored by the peak kernel and
-                       read by the mix), alternating with the default form: the measurement behind DESIGN.md 3.12's choice
   synth_batch          wall time of one aegis_synth_adsr call for 27 candidates of about 30 s (host clock around the
                        blocking call, after a warm-up call), its hipEvent kernel times, the float64 operation count of the
                        batch (tools/synth_restated.op_count: what the kernels evaluate, the oscillator twice per note sample)
@@ -63,15 +61,10 @@ def candidates():
     return blobs
 
 
-def synth_batch(repeats, with_store=True):
+def synth_batch(repeats):
     from spectrogram_midi_amd import _lib, synthesizer
     from tools import synth_restated as R
     h = _lib.Handle(device=0)
-    h_store = None
-    if with_store:
-        os.environ["AEGIS_SYNTH_STORE"] = "1"                      # read at create: the stored-notes form of the mix
-        h_store = _lib.Handle(device=0, scipy_tables=False)
-        del os.environ["AEGIS_SYNTH_STORE"]
     synth = synthesizer.ADSRSynthesizer(44100, h)
     p = dict(synthesizer.GUITAR_ADSR_PRESETS["electric_clean"])
     blobs = candidates()
@@ -79,43 +72,32 @@ def synth_batch(repeats, with_store=True):
     par = [h.adsr_params(**p)] * 27
     notes, lengths = [n for n, _ in parsed], [l for _, l in parsed]
     names = ("synth_note_peak", "synth_mix", "synth_master")
-    runs = {"recompute": (h, [], [])}
-    if with_store:
-        runs["store"] = (h_store, [], [])
-    outs = {}
-    for hh, _, _ in runs.values():
-        hh.synth_adsr(notes, lengths, par, 44100)                  # warm-up: code objects, buffer growth
-        hh.set_profiling(True)
-    for _ in range(repeats):                                       # the two forms alternate
-        for key, (hh, walls, kern) in runs.items():
-            t0 = time.perf_counter()
-            outs[key] = hh.synth_adsr(notes, lengths, par, 44100)
-            walls.append(time.perf_counter() - t0)
-            kern.append({k: hh.kernel_ms(k) for k in names})
-    for hh, _, _ in runs.values():
-        hh.set_profiling(False)
-    out = outs["recompute"]
-    assert all(np.array_equal(a, b) for a, b in zip(out, outs.get("store", out)))
+    walls, kern = [], []
+    h.synth_adsr(notes, lengths, par, 44100)                       # warm-up: code objects, buffer growth
+    h.set_profiling(True)
+    for _ in range(repeats):
+        t0 = time.perf_counter()
+        out = h.synth_adsr(notes, lengths, par, 44100)
+        walls.append(time.perf_counter() - t0)
+        kern.append({k: h.kernel_ms(k) for k in names})
+    h.set_profiling(False)
     t0 = time.perf_counter()
     whole = synth.render_batch(blobs, [p] * 27)                    # with the MIDI reading and the Python layer
     whole_s = time.perf_counter() - t0
     assert all(np.array_equal(a, b) for a, b in zip(out, whole))
     ops = sum(R.op_count(R.parse(b)[0], l, 44100, p["release_ms"], p["waveform"]) for b, l in zip(blobs, lengths))
     note_samples = int(sum(int(44100 * (d + p["release_ms"] / 1000.0)) for n in notes for d in n["duration"]))
-
-    def summary(walls, kern):
-        best = min(range(repeats), key=lambda i: sum(kern[i].values()))
-        return {"wall_ms_each_call": [round(w * 1e3, 3) for w in walls], "kernel_ms_hip_events": kern[best],
-                "kernel_ms_sum": round(sum(kern[best].values()), 4),
-                "kernel_ms_sum_each_call": [round(sum(k.values()), 4) for k in kern]}
-    rec = summary(*runs["recompute"][1:])
+    best = min(range(repeats), key=lambda i: sum(kern[i].values()))
+    rec = {"wall_ms_each_call": [round(w * 1e3, 3) for w in walls], "kernel_ms_hip_events": kern[best],
+           "kernel_ms_sum": round(sum(kern[best].values()), 4),
+           "kernel_ms_sum_each_call": [round(sum(k.values()), 4) for k in kern]}
     ksum = rec["kernel_ms_sum"]
     t0 = time.perf_counter()
     ref = R.render(blobs[0], 44100, **p)
     host_s = time.perf_counter() - t0
     assert np.array_equal(ref, out[0])
     h.close()
-    got = {
+    return {
         "synth_batch": dict({"candidates": 27, "notes": int(sum(len(n) for n in notes)), "samples": int(sum(len(a) for a in out)),
                              "note_samples": note_samples, "preset": "electric_clean",
                              "wall_ms_with_midi_reading": round(whole_s * 1e3, 3), "f64_ops_counted": int(ops),
@@ -123,13 +105,6 @@ def synth_batch(repeats, with_store=True):
         "restated_host": {"what": "tools/synth_restated.py, one candidate, this machine's host CPU", "seconds": round(host_s, 4),
                           "notes": int(len(notes[0])), "samples": int(len(ref))},
     }
-    if with_store:
-        h_store.close()
-        got["synth_batch_store_mode"] = dict(
-            {"what": "AEGIS_SYNTH_STORE=1: the peak kernel stores each note's samples (8 bytes per note sample), the mix reads "
-                     "them instead of recomputing; same samples out", "stored_bytes": note_samples * 8},
-            **summary(*runs["store"][1:]))
-    return got
 
 
 class Timers:
@@ -264,7 +239,7 @@ def kernel_stats(path):
     with open(path, newline="") as f:
         for r in csv.DictReader(f):
             name = r.get("Name") or r.get("KernelName") or ""
-            for known in ("synth_note_peak_kernel", "synth_mix_kernel", "synth_master_kernel"):
+            for known in ("adsr_peak_kernel", "adsr_mix_kernel", "adsr_master_kernel"):
                 if known in name:
                     rows[known] = {k: r[k] for k in r if k not in ("Name", "KernelName")}
     return {"rocprofv3_kernel_stats": rows}
@@ -292,7 +267,7 @@ def main():
     if a.kernel_stats:
         print(json.dumps(merge(kernel_stats(a.kernel_stats), a.out)["rocprofv3_kernel_stats"], indent=1))
         return
-    got = synth_batch(a.repeats, with_store=not a.synth_only)
+    got = synth_batch(a.repeats)
     if not a.synth_only:
         import tempfile
         got.update(sine_check())

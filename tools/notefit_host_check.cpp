@@ -85,7 +85,7 @@ int main(int argc, char **argv) {
         nt.nf = 1 + L / kFitHop; nt.nr = 1 + L / kFitRmsHop;
         nt.cand0 = 0; nt.n_cand = 1;
         if (nt.nf != nf) { fprintf(stderr, "frame count %lld, the restatement has %lld\n", (long long)nt.nf, (long long)nf); return 1; }
-        FitCand c{};
+        AdsrNote c{};
         c.osc = -1; c.start = na; c.n_cut = nb; c.note = 0;
         std::vector<double> cnum((size_t)(2 * nf)), cden((size_t)(2 * nf)), rms((size_t)(2 * nt.nr)), out(4);
         std::vector<int32_t> zc((size_t)(2 * nf)), best(1);
