@@ -574,6 +574,11 @@ int64_t aegis_get_param(const aegis_handle *h, const char *name);
  * frame stage leaves in HBM), "yin" f64[F*yin_stride] (the CMND rows: only on handles created under AEGIS_DEBUG_STAGES=1),
  * "logobs" f64[F*obs_stride], "logunv" f64[F], "states" i32[F], "melpow" f32[F*n_mels], "rake_raw" u8[F]}.
  * Returns the element count available; copies min(count, cap).
+ * What the most recent aegis_estimate_tuning call left on the device (0 before one has run, so always on a
+ * device = -1 handle): "tuning_peak_off" i64[n_clips + 1] (each clip's room in the peak lists: frames * ceil(bins / 2)),
+ * "tuning_pitch" f32 and "tuning_mag" f32 [peak_off[n_clips]] (the piptrack peaks; of clip c only the first
+ * min(n_peaks[c], room) entries behind peak_off[c] mean anything, in no particular order), "tuning_median" f32[n_clips]
+ * (np.median of a clip's peak magnitudes, 0 for a clip without peaks).
  * "viterbi_stats" i64[3] (reading resets; "viterbi_stats_peek" does not): wave-steps of the band Viterbi since the last
  * reset, how many of them took the exact observed-sources-only path, and how many were voiced waves that skipped the step
  * because all their targets were dead at an easy frame (bench.py reports the ratios).

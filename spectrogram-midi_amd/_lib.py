@@ -207,7 +207,8 @@ def load():
 
 
 _TABLE_DTYPES = {"mel_dense": np.float32}
-_DEBUG_DTYPES = {"persistent_fallbacks": np.int64, "obs_cycles": np.int64, "cqt_cycles": np.int64, "viterbi_cycles": np.int64, "viterbi_spans": np.int64, "split_verify": np.int64, "split_flags": np.int64, "seg_lock": np.int64, "frame_cycles": np.int64, "states": np.int32, "melpow": np.float32, "rake_raw": np.uint8}
+_DEBUG_DTYPES = {"persistent_fallbacks": np.int64, "obs_cycles": np.int64, "cqt_cycles": np.int64, "viterbi_cycles": np.int64, "viterbi_spans": np.int64, "split_verify": np.int64, "split_flags": np.int64, "seg_lock": np.int64, "frame_cycles": np.int64, "states": np.int32, "melpow": np.float32, "rake_raw": np.uint8,
+                 "tuning_pitch": np.float32, "tuning_mag": np.float32, "tuning_median": np.float32, "tuning_peak_off": np.int64}
 
 
 _live_handles = weakref.WeakSet()
@@ -632,6 +633,20 @@ class Handle:
                                                        peaks.ctypes.data if want_counts else None))
         out = [float(t) for t in tun]
         return (out, counts, peaks) if want_counts else out
+
+    def tuning_peaks(self, n_peaks):
+        """What the most recent estimate_tuning call left on the device, per clip: (pitch f32[k], mag f32[k], median
+        float32) with k = min(n_peaks[c], the clip's room) -- the piptrack peaks in the order the workgroups appended them
+        and the median the histogram cut at (aegis_debug_fetch "tuning_*")."""
+        off = self.debug_fetch("tuning_peak_off")
+        if len(off) != len(n_peaks) + 1:
+            raise ValueError(f"the last estimate_tuning call had {max(len(off) - 1, 0)} clips, not {len(n_peaks)}")
+        pitch, mag, med = self.debug_fetch("tuning_pitch"), self.debug_fetch("tuning_mag"), self.debug_fetch("tuning_median")
+        out = []
+        for c, k in enumerate(n_peaks):
+            k = min(int(k), int(off[c + 1] - off[c]))
+            out.append((pitch[off[c]:off[c] + k].copy(), mag[off[c]:off[c] + k].copy(), med[c]))
+        return out
 
     def cqt_device(self, d_pcm_ptr, sample_offsets, d_out_ptr, n_bins=84, bins_per_octave=12, fmin=32.70319566257483,
                    filter_scale=1.0, stream=None, sync=True):

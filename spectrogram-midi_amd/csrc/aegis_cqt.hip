@@ -247,6 +247,7 @@ int aegis_estimate_tuning(aegis_handle *h, const float *const *pcm, const int64_
     std::lock_guard<std::mutex> lock(h->mu);
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
+    h->tn_last_peak_off.clear();                               // a call that fails below leaves nothing to fetch
     TuningArgs a{};
     a.sr = h->tab.sr; a.bpo = bins_per_octave; a.n_clips = n_clips;
     tuning_band(a.sr, &a.k_lo, &a.k_hi);
@@ -300,6 +301,7 @@ int aegis_estimate_tuning(aegis_handle *h, const float *const *pcm, const int64_
     if (n_peaks_out) HIPCHK(h, hipMemcpyAsync(np_host.data(), h->tn_count.p, (size_t)n_clips * 8, hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipStreamSynchronize(s));
     for (size_t i = 0; i < np_host.size(); ++i) n_peaks_out[i] = (int64_t)np_host[i];
+    h->tn_last_peak_off.assign(poff, poff + m);
     if (h->profiling) collect_events(h);
     return AEGIS_OK;
     } catch (...) { return abi_fail(h); }

@@ -568,6 +568,17 @@ int64_t aegis_debug_fetch(aegis_handle *h, const char *name, void *dst, int64_t 
     else if (n == "states") { src = lw.states.p; count = F; esz = 4; }
     else if (n == "melpow") { src = lw.melpow.p; count = F * h->tab.n_mels; esz = 4; }
     else if (n == "rake_raw") { src = lw.rake_raw.p; count = F; esz = 1; }
+    else if (n == "tuning_peak_off") {    // what the most recent aegis_estimate_tuning left: each clip's room in the peak lists
+        const std::vector<int64_t> &po = h->tn_last_peak_off;
+        if (dst && cap > 0) std::memcpy(dst, po.data(), (size_t)std::min<int64_t>(cap, (int64_t)po.size()) * 8);
+        return (int64_t)po.size();
+    }
+    else if (n == "tuning_pitch" || n == "tuning_mag" || n == "tuning_median") {
+        if (h->tn_last_peak_off.empty()) return 0;
+        if (n == "tuning_median") { src = h->tn_median.p; count = (int64_t)h->tn_last_peak_off.size() - 1; }
+        else { src = n == "tuning_pitch" ? h->tn_pitch.p : h->tn_mag.p; count = h->tn_last_peak_off.back(); }
+        esz = 4;
+    }
     else if (n == "persistent_fallbacks") {
         if (dst && cap > 0) *static_cast<int64_t *>(dst) = h->persist.fallbacks;
         return 1;

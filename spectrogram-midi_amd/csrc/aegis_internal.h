@@ -114,6 +114,7 @@ struct aegis_handle {
     std::vector<double> tuning_edges;
     const double *d_tuning_edges = nullptr;
     DevBuf tn_meta, tn_pitch, tn_mag, tn_count, tn_median, tn_cells, tn_tuning;
+    std::vector<int64_t> tn_last_peak_off;    // [n_clips + 1] of the most recent call that ran (aegis_debug_fetch "tuning_*"); empty before one
     DevBuf t_x, t_off, t_a, t_b, t_c, t_d, t_e, t_i8, t_i64a, t_i64b;   // trend-filter staging
     DevBuf t_pa;                              // scratch of the fused pitch analysis: 12 rows of doubles + 1 of bytes
     DevBuf io_pcm, io_f0, io_voiced, io_vprob, io_rms, io_rake, io_sdb, io_bin, io_colmean;

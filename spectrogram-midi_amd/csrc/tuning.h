@@ -66,6 +66,8 @@ AEGIS_HD float tun_magnitude(double2 z) {
 
 // piptrack at bin k of one frame (1 <= k <= 1023; S = the frame's 1025 magnitudes, ref = float32(0.1) * max S): is it a
 // peak, and if so its interpolated pitch and magnitude.  float32 in the oracle's order.
+// (The reference's `|b| >= |a| -> shift 0` is kept for the oracle's order of operations; a local maximum cannot take it:
+// with sp = s0 - e, sm = s0 - d, d > 0, e >= 0 it would need |d - e| >= 2 (d + e).)
 AEGIS_HD bool tun_peak(const float *S, int k, float ref, int sr, float *pitch, float *mag) {
     const float sm = S[k - 1], s0 = S[k], sp = S[k + 1];
     const float xm = sm > ref ? sm : 0.0f, x0 = s0 > ref ? s0 : 0.0f, xp = sp > ref ? sp : 0.0f;

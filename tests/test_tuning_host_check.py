@@ -7,7 +7,7 @@ import subprocess
 
 import pytest
 
-from tools import tuning_cases
+from tools import tuning_cases, tuning_probes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -33,3 +33,17 @@ def test_emulated_kernels_reproduce_the_oracle(checker, tmp_path):
     n = len(tuning_cases.reference(44100)) + len(tuning_cases.reference(22050))
     assert f"{n} clips, 0 out of bounds" in r.stdout
     assert "ERROR" not in r.stderr                     # a sanitizer report
+
+
+def test_emulated_kernels_take_the_probe_clips(checker, tmp_path):
+    """The probes of tests/test_gpu_tuning_probes.py (tools/tuning_probes.py), the comb that fills a frame's room, the empty
+    and the one-sample clip among them: an index out of range stops the program here, before the first device run."""
+    path = str(tmp_path / "probes.bin")
+    tuning_probes.dump(path)
+    r = subprocess.run([checker, path], capture_output=True, text=True)
+    os.remove(path)
+    print(r.stdout[-3000:], r.stderr)
+    assert r.returncode == 0
+    n = sum(len(tuning_probes.reference(sr)) for sr in tuning_probes.RATES)
+    assert f"{n} clips, 0 out of bounds" in r.stdout
+    assert "ERROR" not in r.stderr
