@@ -200,7 +200,7 @@ int aegis_create(const aegis_config *cfg, aegis_handle **out) {
         }
     }
     CRT(create_events(h));
-    CRTHIP(viterbi_configure());
+    CRTHIP(configure_lds_limits());
     CRT(ensure(h, h->vstats, 32));
     CRTHIP(hipMemset(h->vstats.p, 0, 32));
     CRTHIP(cqt_configure());

@@ -135,7 +135,7 @@ struct PassParams {
     int32_t cmnd_in_frame;               // the frame kernel's epilogue forms the CMND (cumsum walk of all its frames at once);
                                          // 0: pyin_obs_kernel walks it frame by frame (stage tests, lag ranges the epilogue cannot hold)
     int32_t troughs;                     // with cmnd_in_frame: the frame kernel also finds the CMND's troughs and leaves each frame's
-                                         // trough list (count, values, parabolic shifts, lags: kernels.hip trough_row_doubles) in its dfn row
+                                         // trough list (count, values, parabolic shifts, lags: frame_walk.h trough_row_doubles) in its dfn row
                                          // instead of the CMND; pyin_obs_kernel starts at the threshold prior
     double *yin;   int32_t yin_stride;   // optional [F][yin_stride]: CMND for lags min..max, written only for the stage tests
     double *logobs; int32_t obs_stride;  // [F][obs_stride]   log(obs+tiny), voiced bins
@@ -215,7 +215,12 @@ hipError_t obs_debug_fetch(long long *dst);                  // pyin_obs_kernel 
 hipError_t frame_debug_fetch(long long *dst);                // frame_yin_kernel section cycles (AEGIS_ABLATE&128)
 hipError_t viterbi_debug_fetch(long long *dst, bool reset);   // per-wave section cycles (zeros unless AEGIS_ABLATE&64)
 hipError_t viterbi_span_fetch(long long *dst);               // arg-max span statistics (zeros unless AEGIS_ABLATE&512); reading resets
-hipError_t viterbi_configure();   // raises the dynamic-LDS limits once (all kernels)
-hipError_t viterbi_set_lds_limits();   // viterbi.hip's share of it
+// Raises the dynamic-LDS limits once: frame.hip, obs.hip and viterbi.hip each set those of their own kernels.
+hipError_t frame_set_lds_limits(), obs_set_lds_limits(), viterbi_set_lds_limits();
+inline hipError_t configure_lds_limits() {
+    hipError_t e = frame_set_lds_limits();
+    if (e == hipSuccess) e = obs_set_lds_limits();
+    return e == hipSuccess ? viterbi_set_lds_limits() : e;
+}
 
 }  // namespace aegis

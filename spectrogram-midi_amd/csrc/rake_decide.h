@@ -1,5 +1,5 @@
 // The per-column broadband test of the rake mask (vision.py:11-21 on power_to_db(ref=np.max, top_db=80)), decided from
-// mel POWER.  Shared by rake_pow_kernel (kernels.hip) and the host check (tools/rake_decide_host_check.cpp): the same
+// mel POWER.  Shared by rake_pow_kernel (finalize.hip) and the host check (tools/rake_decide_host_check.cpp): the same
 // text compiles for both.
 //
 // A column's dB values are V(s) = max(fl(fl(10 * fl((double)log10(s))) - refdb), -80) in float32, s = max(1e-10, power),

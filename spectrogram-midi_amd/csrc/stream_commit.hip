@@ -15,6 +15,7 @@
 // most 64 members one wave carries one member per lane with no barrier at all: per frame one dependent 2-byte load
 // (rows written microseconds to seconds earlier: L2 or Infinity Cache), a readfirstlane and a ballot.  The walk stops
 // at the previous frontier, so a push pays for its lag, not for the length of the stream.
+// Behind it, the two small kernels at the head and the tail of a push's captured graph (advance, gather).
 #include "kernels.h"
 
 namespace aegis {
@@ -147,6 +148,50 @@ hipError_t launch_stream_commit(const StreamCtl *ctl, int64_t frames_done, Strea
     hipLaunchKernelGGL(stream_commit_kernel, dim3(1), dim3(nthr), 0, s, ctl, frames_done, cc, ptr, vstate, n_bins, bins,
                        static_cast<unsigned char *>(result));
     return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------
+// Streaming graph helpers.  stream_advance_kernel appends the pushed samples (already on the device in
+// a fixed staging buffer) to the clip and derives the push's geometry exactly as the host path does:
+// a frame is ready when its centred 2048-sample window is complete.  stream_gather_kernel packs the
+// push's outputs into a fixed result block: [0] n_frames, then rms[8] f32, vprob[8] f64, live[8] i32.
+// ------------------------------------------------------------------------------------------
+__global__ void stream_advance_kernel(StreamCtl *ctl, const float *__restrict__ staging, int n_push,
+                                      float *__restrict__ pcm, int hop) {
+    const int64_t n0 = ctl->n_samples;
+    for (int i = threadIdx.x; i < n_push; i += blockDim.x) pcm[n0 + i] = staging[i];
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int64_t n = n0 + n_push;
+        const int64_t ready = n >= 1024 ? (n - 1024) / hop + 1 : 0;
+        const int64_t lo = ctl->frames_done, hi = ready > lo ? ready : lo;
+        ctl->n_samples = n;
+        ctl->t_begin = lo; ctl->n_sel = hi - lo;
+        ctl->vt_begin = lo; ctl->vt_end = hi;
+        ctl->frames_done = hi;
+        ctl->meta[1] = n;            // sample_off[1]
+        ctl->meta[5] = hi - lo;      // sel_off[1]
+    }
+}
+
+__global__ void stream_gather_kernel(const StreamCtl *ctl, const float *__restrict__ rms, const double *__restrict__ vprob,
+                                     const int32_t *__restrict__ live, unsigned char *__restrict__ result) {
+    const int i = threadIdx.x;
+    int64_t *cnt = reinterpret_cast<int64_t *>(result);
+    float *r = reinterpret_cast<float *>(result + 8);
+    double *v = reinterpret_cast<double *>(result + 8 + 32);
+    int32_t *l = reinterpret_cast<int32_t *>(result + 8 + 32 + 64);
+    const int64_t n = ctl->n_sel, t0 = ctl->t_begin;
+    if (i == 0) *cnt = n;
+    if (i < 8 && i < n) { r[i] = rms[t0 + i]; v[i] = vprob[t0 + i]; l[i] = live[t0 + i]; }
+}
+
+void launch_stream_advance(StreamCtl *ctl, const float *staging, int n_push, float *pcm, int hop, hipStream_t s) {
+    hipLaunchKernelGGL(stream_advance_kernel, dim3(1), dim3(256), 0, s, ctl, staging, n_push, pcm, hop);
+}
+void launch_stream_gather(const StreamCtl *ctl, const float *rms, const double *vprob, const int32_t *live, void *result,
+                          hipStream_t s) {
+    hipLaunchKernelGGL(stream_gather_kernel, dim3(1), dim3(64), 0, s, ctl, rms, vprob, live, static_cast<unsigned char *>(result));
 }
 
 }  // namespace aegis

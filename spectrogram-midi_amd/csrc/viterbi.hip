@@ -10,6 +10,8 @@
 // Built with -ffp-contract=off: every add below rounds exactly where NumPy rounds.
 #include <functional>
 #include "kernels.h"
+#include "pass_geometry.h"
+#include "wave_ops.h"
 
 #include <algorithm>
 #include <cfloat>
@@ -18,10 +20,6 @@
 #include <cstring>
 
 namespace aegis {
-
-// step range of this launch: by-value fields, or the device control block of a graph replay
-__device__ __forceinline__ int64_t geo_vt_begin(const PassParams &p) { return p.ctl ? p.ctl->vt_begin : p.vt_begin; }
-__device__ __forceinline__ int64_t geo_vt_end(const PassParams &p) { return p.ctl ? p.ctl->vt_end : p.vt_end; }
 
 // ------------------------------------------------------------------------------------------
 // Kernel 4: log-domain Viterbi, one workgroup per clip, one thread per HMM state.
@@ -213,37 +211,8 @@ __device__ __forceinline__ double row16_prefix_max(double v) {   // lane 15 of e
 // log-transition < 0, observations <= log(1 + tiny)): for such values the larger double has the smaller bit pattern, so
 // the maximum is an unsigned minimum of the high words followed by one of the low words among the lanes that hold
 // that high word.  A 32-bit minimum takes its DPP operand directly (one v_min_u32_dpp per level: identity as the "old"
-// value of lanes without a source); the float64 form needs two DPP moves, two copies and a canonicalising max per level.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ unsigned dpp_umin(unsigned v) {
-    return min(v, (unsigned)__builtin_amdgcn_update_dpp(-1, (int)v, CTRL, ROW_MASK, 0xf, false));
-}
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ unsigned dpp_umax(unsigned v) {
-    return max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xf, false));
-}
-__device__ __forceinline__ unsigned row16_umin(unsigned v) {      // lane 15 of each row = row minimum
-    v = dpp_umin<0x111, 0xf>(v);
-    v = dpp_umin<0x112, 0xf>(v);
-    v = dpp_umin<0x114, 0xf>(v);
-    v = dpp_umin<0x118, 0xf>(v);
-    return v;
-}
-__device__ __forceinline__ unsigned wave_umin(unsigned v) {       // uniform result
-    v = row16_umin(v);
-    v = dpp_umin<0x142, 0xa>(v);   // row_bcast:15
-    v = dpp_umin<0x143, 0xc>(v);   // row_bcast:31
-    return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
-}
-__device__ __forceinline__ unsigned wave_umax(unsigned v) {
-    v = dpp_umax<0x111, 0xf>(v);
-    v = dpp_umax<0x112, 0xf>(v);
-    v = dpp_umax<0x114, 0xf>(v);
-    v = dpp_umax<0x118, 0xf>(v);
-    v = dpp_umax<0x142, 0xa>(v);
-    v = dpp_umax<0x143, 0xc>(v);
-    return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
-}
+// value of lanes without a source; wave_ops.h); the float64 form needs two DPP moves, two copies and a canonicalising max
+// per level.
 // largest value of the wave and the lanes that hold it
 __device__ __forceinline__ double wave_max_neg(double v, unsigned long long &at) {
     const unsigned hi = (unsigned)__double2hiint(v), lo = (unsigned)__double2loint(v);

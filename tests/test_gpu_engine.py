@@ -216,7 +216,7 @@ def test_dead_voiced_waves_skip_their_steps(eng):
 
 @pytest.mark.parametrize("sr,hop", [(44100, 512), (22050, 256), (48000, 512)])
 def test_cmnd_in_the_frame_kernel_equals_the_walk_in_pyin_obs(sr, hop, monkeypatch):
-    """kernels.hip: the frame kernel's epilogue forms the CMND of a workgroup's 16 frames at once (what runs); with
+    """frame.hip: the frame kernel's epilogue forms the CMND of a workgroup's 16 frames at once (what runs); with
     AEGIS_CMND_IN_FRAME=0 at create, pyin_obs_kernel walks the cumsum frame by frame as before (what the stage tests and lag
     ranges the epilogue cannot hold use).  Same operations in the same order: every output bit-identical, on a ragged batch
     whose workgroups straddle clips, with a clip shorter than one hop and an empty one."""

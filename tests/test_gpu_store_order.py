@@ -1,5 +1,5 @@
 """The frame kernel and the observation kernel wait for their prefetched inputs where no fresh global stores are outstanding
-(kernels.hip: the samples of a pair's first frame; the trough list of a wave's next frame, taken over in front of the
+(frame.hip, obs.hip: the samples of a pair's first frame; the trough list of a wave's next frame, taken over in front of the
 frame's stores).  Pure reordering: every output bit stays what it was.  The batches (tools/store_order_crc.py) are the
 shapes at which a hand-over can go missing or double: one frame, an odd workgroup, pairs and workgroups that straddle
 clips, silence (no trough), noise (more troughs than the two prefetched rounds), a sine, and a run of more than 4096

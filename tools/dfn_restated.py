@@ -41,7 +41,7 @@ EDGE_COUNTS = (1, 2, 3, 511, 512, 513, 1023, 1024, 1025, 2047, 2048, 2049, 20 * 
 
 
 def energy_groups(max_period):
-    """Groups of 32 lags the kernel's running-energy walk stores (kernels.hip::energy_groups)."""
+    """Groups of 32 lags the kernel's running-energy walk stores (frame_walk.h::energy_groups)."""
     return (max_period + 32) >> 5
 
 

@@ -2,7 +2,7 @@
 // otherwise idle CU: the product's energy_walk against the bare dependent chain (the retired 8-sample-block walk it
 // replaced is recorded in profiles/r2_ubench_walk.txt: 23.7 cycles per add).
 //   hipcc -O3 -std=c++17 -ffp-contract=off --offload-arch=gfx950 -I spectrogram-midi_amd/csrc tools/ubench_walk.hip -o tools/_build/ubench_walk
-#include "../spectrogram-midi_amd/csrc/kernels.hip"
+#include "frame_walk.h"
 #include <cstdio>
 namespace aegis {
 // no LDS in the loop at all: the chain alone (values from registers)
@@ -42,7 +42,6 @@ __global__ __launch_bounds__(256) void walk_bench(long long *out, float *sink, i
     if (tid < 16) sink[tid] = en[tid * en_stride + 5] + acc;
 }
 }  // namespace aegis
-namespace aegis { hipError_t viterbi_set_lds_limits() { return hipSuccess; } }
 int main() {
     long long *d, h[4] = {0};
     float *sink;
