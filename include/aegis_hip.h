@@ -391,12 +391,13 @@ const char *aegis_events_last_error(void);
  * Three steps, so that a caller sizes its own buffers:
  *   aegis_synth_parse_smf    the notes the loop of midi_to_wav closes, in the order it closes them (synthesizer.py:423-467),
  *                            and mido's MidiFile.length (:409).  Host code: a device=-1 handle serves too.  SMF type 0 / 1,
- *                            running status, meta and sysex events skipped, pitch-wheel and program messages ignored as the
- *                            reference ignores them.  The reference's quirks are kept: ONE tempo converts every delta of
- *                            the file, the first set_tempo of the last track that has one (_get_tempo, :487-507), while
- *                            the length honours every tempo change; a re-struck note overwrites the active entry; notes
- *                            never closed are dropped; duration = max(0.01, end - start).  Returns the note count (which
- *                            may exceed cap: nothing past cap is written) or a negative code.
+ *                            running status, meta and sysex events skipped, program messages ignored as the reference
+ *                            ignores them, pitch-wheel messages ignored unless asked for (aegis_synth_parse_smf_wheel).
+ *                            The reference's quirks are kept: ONE tempo converts every delta of the file, the first
+ *                            set_tempo of the last track that has one (_get_tempo, :487-507), while the length honours
+ *                            every tempo change; a re-struck note overwrites the active entry; notes never closed are
+ *                            dropped; duration = max(0.01, end - start).  Returns the note count (which may exceed cap:
+ *                            nothing past cap is written) or a negative code.
  *   aegis_synth_samples_for  total_samples of a render: int(sample_rate * ((length > 0 ? length : 10) + release_ms / 1000 +
  *                            0.5)) (:409-415); no handle.
  *   aegis_synth_adsr         n_clips note lists (clip c = notes[note_off[c] .. note_off[c+1]), each with its own length and
@@ -426,6 +427,33 @@ int64_t aegis_synth_parse_smf(aegis_handle *h, const uint8_t *smf, int64_t n_byt
 int64_t aegis_synth_samples_for(int32_t sample_rate, double length_seconds, const aegis_adsr_params *params);
 int aegis_synth_adsr(aegis_handle *h, int32_t sample_rate, int32_t n_clips, const aegis_synth_note *notes, const int64_t *note_off,
                      const double *length_seconds, const aegis_adsr_params *params, int16_t *const *out, const int64_t *out_cap);
+
+/* Pitch wheel, opt-in (not in the reference's NumPy synth, which ignores the wheel; its FluidSynth path honours it with
+ * the default range of +-2 semitones, which aegis_render_smf assumes when it writes bends and vibratos).
+ *   aegis_synth_parse_smf_wheel  aegis_synth_parse_smf (the same notes and length) plus note_track[i], the index of the
+ *                            track of notes[i] (cap entries, may be null), and the file's pitch-wheel messages, track
+ *                            after track in file order: time in seconds accumulated per track exactly as the notes'
+ *                            (a note_on and a wheel at one tick have bit-equal times), the track, the value -8192..8191.
+ *                            *n_wheel is their count (which may exceed wheel_cap: nothing past it is written).  Host code.
+ *   aegis_synth_adsr_bend    aegis_synth_adsr in which the wheel bends the notes of its own track (channels ignored, as
+ *                            the note loop ignores them): note_track[q] belongs to notes[q]; clip c has the wheel events
+ *                            wheel[wheel_off[c] .. wheel_off[c+1]), per track in non-decreasing time, and the range
+ *                            bend_range[c] in semitones (finite, > 0, <= 24; else AEGIS_ERR_INVALID).  A value v scales
+ *                            the frequency by 2 ** (((v / 8192) * range) / 12) from its time on; the phase is continuous
+ *                            (csrc/adsr.h states the arithmetic).  A note that no non-zero wheel value reaches is rendered
+ *                            exactly as aegis_synth_adsr renders it; total samples, peaks, envelope, mix and master are
+ *                            unchanged.  Pinned to tools/bend_restated.py: equal for sawtooth, triangle and square, within
+ *                            one step for sine.  Blocking. */
+typedef struct aegis_synth_wheel {
+    double time;                  /* seconds */
+    int32_t track, value;
+} aegis_synth_wheel;
+int64_t aegis_synth_parse_smf_wheel(aegis_handle *h, const uint8_t *smf, int64_t n_bytes, aegis_synth_note *notes, int32_t *note_track,
+                                    int64_t cap, aegis_synth_wheel *wheel, int64_t wheel_cap, int64_t *n_wheel, double *length_seconds);
+int aegis_synth_adsr_bend(aegis_handle *h, int32_t sample_rate, int32_t n_clips, const aegis_synth_note *notes, const int64_t *note_off,
+                          const double *length_seconds, const aegis_adsr_params *params, const int32_t *note_track,
+                          const aegis_synth_wheel *wheel, const int64_t *wheel_off, const double *bend_range, int16_t *const *out,
+                          const int64_t *out_cap);
 
 /* --- Per-note ADSR fit and render (aegis_engine_core/per_note_optimizer.py:72-327, :549-659) ---------------------
  * The reference's per-note optimiser scores, for every detected note, candidate envelopes and waveforms against the note's

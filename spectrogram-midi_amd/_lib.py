@@ -77,6 +77,7 @@ EFFECT_KINDS = {"distortion": (FX_DISTORTION, (("drive", 0.5),)), "reverb": (FX_
                 "delay": (FX_DELAY, (("delay_ms", 300), ("feedback", 0.3))), "chorus": (FX_CHORUS, (("depth", 0.003), ("rate", 1.5)))}
 WAVEFORMS = {"sine": 0, "sawtooth": 1, "square": 2, "triangle": 3}          # AEGIS_WAVE_*
 SYNTH_NOTE_DTYPE = np.dtype([("start", "<f8"), ("duration", "<f8"), ("note", "<i4"), ("velocity", "<i4")])
+SYNTH_WHEEL_DTYPE = np.dtype([("time", "<f8"), ("track", "<i4"), ("value", "<i4")])      # aegis_synth_wheel
 
 EXPORTS = ("aegis_abi_version", "aegis_create", "aegis_destroy", "aegis_last_error", "aegis_frames_for",
            "aegis_analyze_batch", "aegis_analyze_batch_device", "aegis_get_table", "aegis_get_param",
@@ -87,7 +88,8 @@ EXPORTS = ("aegis_abi_version", "aegis_create", "aegis_destroy", "aegis_last_err
            "aegis_synth_parse_smf", "aegis_synth_samples_for", "aegis_synth_adsr", "aegis_debug_rake_columns",
            "aegis_debug_set_observations", "aegis_debug_set_difference", "aegis_estimate_tuning",
            "aegis_reverb_ir", "aegis_effects",
-           "aegis_note_fit", "aegis_compare_audio", "aegis_synth_one_note", "aegis_synth_notes_samples_for", "aegis_synth_adsr_notes")
+           "aegis_note_fit", "aegis_compare_audio", "aegis_synth_one_note", "aegis_synth_notes_samples_for", "aegis_synth_adsr_notes",
+           "aegis_synth_parse_smf_wheel", "aegis_synth_adsr_bend")
 
 _lib = None
 
@@ -178,6 +180,12 @@ def load():
     lib.aegis_synth_adsr.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(AdsrParams),
                                      C.POINTER(C.c_void_p), C.c_void_p]
     lib.aegis_synth_adsr.restype = C.c_int
+    lib.aegis_synth_parse_smf_wheel.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                                C.POINTER(C.c_int64), C.POINTER(C.c_double)]
+    lib.aegis_synth_parse_smf_wheel.restype = C.c_int64
+    lib.aegis_synth_adsr_bend.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(AdsrParams),
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p]
+    lib.aegis_synth_adsr_bend.restype = C.c_int
     lib.aegis_reverb_ir.argtypes = [C.c_double, C.c_int32, C.c_void_p, C.c_int64]
     lib.aegis_reverb_ir.restype = C.c_int64
     lib.aegis_effects.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.c_int32, C.c_void_p, C.POINTER(Effect),
@@ -656,17 +664,28 @@ class Handle:
                                               len(off) - 1, n_bins, bins_per_octave, float(fmin), float(filter_scale),
                                               C.c_void_p(int(d_out_ptr)), C.c_void_p(stream or 0), 1 if sync else 0))
 
-    def synth_parse_smf(self, midi_bytes):
+    def synth_parse_smf(self, midi_bytes, want_wheel=False):
         """aegis_synth_parse_smf: (notes in the reference's mix order as a SYNTH_NOTE_DTYPE array, mido's length in
-        seconds) of a Standard MIDI File; ValueError for bytes that are not one (mido raises).  Host code."""
+        seconds) of a Standard MIDI File; ValueError for bytes that are not one (mido raises).  Host code.
+        want_wheel=True (aegis_synth_parse_smf_wheel): (notes, length, note_track, wheel) -- the same notes and length,
+        the track index of every note (int32) and the file's pitch-wheel messages as a SYNTH_WHEEL_DTYPE array."""
         blob = bytes(midi_bytes)
         length = C.c_double(0.0)
         notes = np.empty(max(len(blob) // 3, 1), SYNTH_NOTE_DTYPE)      # a note takes two messages of three bytes or more
-        n = int(self.lib.aegis_synth_parse_smf(self._h, blob, len(blob), notes.ctypes.data, len(notes), C.byref(length)))
+        if want_wheel:
+            track = np.empty(len(notes), np.int32)
+            wheel = np.empty(max(len(blob) // 3, 1), SYNTH_WHEEL_DTYPE)      # a wheel message takes three bytes or more
+            n_wheel = C.c_int64(0)
+            n = int(self.lib.aegis_synth_parse_smf_wheel(self._h, blob, len(blob), notes.ctypes.data, track.ctypes.data, len(notes),
+                                                         wheel.ctypes.data, len(wheel), C.byref(n_wheel), C.byref(length)))
+        else:
+            n = int(self.lib.aegis_synth_parse_smf(self._h, blob, len(blob), notes.ctypes.data, len(notes), C.byref(length)))
         if n == ERR_INVALID:
             raise ValueError(self.lib.aegis_last_error(self._h).decode())
-        if n < 0 or n > len(notes):
+        if n < 0 or n > len(notes) or (want_wheel and not 0 <= n_wheel.value <= len(wheel)):
             raise AegisError(n, self.lib.aegis_last_error(self._h).decode())
+        if want_wheel:
+            return notes[:n].copy(), float(length.value), track[:n].copy(), wheel[:n_wheel.value].copy()
         return notes[:n].copy(), float(length.value)
 
     @staticmethod
@@ -675,9 +694,11 @@ class Handle:
             raise ValueError(f"unsupported waveform: {waveform}. Choose from 'sine', 'sawtooth', 'square', 'triangle'.")
         return AdsrParams(float(attack_ms), float(decay_ms), float(sustain_level), float(release_ms), WAVEFORMS[waveform], 0)
 
-    def synth_adsr(self, note_lists, lengths, params, sample_rate):
+    def synth_adsr(self, note_lists, lengths, params, sample_rate, bends=None):
         """aegis_synth_adsr: one device pass for a batch of note lists (SYNTH_NOTE_DTYPE arrays), each with its file
-        length in seconds and its AdsrParams -> list of int16 arrays."""
+        length in seconds and its AdsrParams -> list of int16 arrays.
+        bends (aegis_synth_adsr_bend): per clip (note_track, wheel, bend_range) -- the track of every note, the clip's
+        pitch-wheel events (SYNTH_WHEEL_DTYPE) and the wheel's range in semitones; None renders without the wheel."""
         n = len(note_lists)
         if n == 0:
             return []
@@ -692,8 +713,20 @@ class Handle:
         outs = [np.empty(k, np.int16) for k in sizes]
         ptrs = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
         caps = np.asarray(sizes, np.int64)
-        rc = lib.aegis_synth_adsr(self._h, int(sample_rate), n, notes.ctypes.data, off.ctypes.data, lens.ctypes.data, par, ptrs,
-                                  caps.ctypes.data)
+        if bends is None:
+            rc = lib.aegis_synth_adsr(self._h, int(sample_rate), n, notes.ctypes.data, off.ctypes.data, lens.ctypes.data, par, ptrs,
+                                      caps.ctypes.data)
+        else:
+            if len(bends) != n or any(len(b[0]) != len(a) for b, a in zip(bends, note_lists)):
+                raise ValueError("one (note_track, wheel, bend_range) per clip, one track per note")
+            track = np.ascontiguousarray(np.concatenate([np.asarray(b[0], np.int32) for b in bends]), dtype=np.int32)
+            woff = np.concatenate([[0], np.cumsum([len(b[1]) for b in bends])]).astype(np.int64)
+            wheel = np.ascontiguousarray(np.concatenate([np.asarray(b[1], SYNTH_WHEEL_DTYPE) for b in bends]) if woff[-1]
+                                         else np.empty(0, SYNTH_WHEEL_DTYPE), dtype=SYNTH_WHEEL_DTYPE)
+            ranges = np.ascontiguousarray([float(b[2]) for b in bends], dtype=np.float64)
+            rc = lib.aegis_synth_adsr_bend(self._h, int(sample_rate), n, notes.ctypes.data, off.ctypes.data, lens.ctypes.data, par,
+                                           track.ctypes.data, wheel.ctypes.data, woff.ctypes.data, ranges.ctypes.data, ptrs,
+                                           caps.ctypes.data)
         if rc == ERR_INVALID:
             raise ValueError(lib.aegis_last_error(self._h).decode())
         self._check(rc)

@@ -25,7 +25,7 @@ import numpy as np
 
 from . import _lib, audio_io
 from .similarity import _calculate_similarity, score_batch    # _calculate_similarity re-exported, as in the reference
-from .synthesizer import synthesize_midi_adsr_batch
+from .synthesizer import _bend_kwargs, synthesize_midi_adsr_batch
 
 __all__ = ["auto_match_parameters", "_calculate_similarity"]
 
@@ -86,7 +86,7 @@ def _batch_scores(handle, y_orig, arrays):
 
 
 def _stage(grid, fine, original_audio_path, engine, raw_data, sample_rate, progress_callback, best_score, best_params, handle,
-           y_orig=None):
+           y_orig=None, pitch_bend=False, pitch_bend_range=2.0):
     """One grid of the search: (best_score, best_params) after its candidates, visited in the reference's order."""
     cast = int if fine else (lambda v: v)
     message = "세밀 탐색 중... ({}/{})" if fine else "탐색 중... ({}/{})"        # the reference's progress texts
@@ -113,7 +113,8 @@ def _stage(grid, fine, original_audio_path, engine, raw_data, sample_rate, progr
         return best_score, best_params
     handle = handle.get()
     batch = y_orig is not None
-    wavs = synthesize_midi_adsr_batch(midis, preset=SYNTH_PRESET, sample_rate=sample_rate, handle=handle, as_arrays=batch)
+    wavs = synthesize_midi_adsr_batch(midis, preset=SYNTH_PRESET, sample_rate=sample_rate, handle=handle, as_arrays=batch,
+                                      **_bend_kwargs(pitch_bend, pitch_bend_range))
     if not wavs:
         return best_score, best_params
     scores = _batch_scores(handle, y_orig, wavs) if batch else None
@@ -136,11 +137,14 @@ def _stage(grid, fine, original_audio_path, engine, raw_data, sample_rate, progr
     return best_score, best_params
 
 
-def auto_match_parameters(original_audio_path, engine, raw_data, sample_rate=44100, progress_callback=None, scoring="loop"):
+def auto_match_parameters(original_audio_path, engine, raw_data, sample_rate=44100, progress_callback=None, scoring="loop",
+                          pitch_bend=False, pitch_bend_range=2.0):
     """-> {'confidence_threshold', 'min_note_duration_ms', 'sustain_ms', 'score'}, or None when no candidate could be
     scored.  `engine`: an AegisEngine; `raw_data`: what its audio_to_midi returned for the original audio.
     scoring: "loop" (default) scores candidate by candidate through _calculate_similarity; "batch" scores a stage's
-    candidates in one similarity.score_batch call against the original read once (see the module text)."""
+    candidates in one similarity.score_batch call against the original read once (see the module text).
+    pitch_bend / pitch_bend_range: render every candidate's pitch wheel, the engine's own bends and vibratos
+    (synthesizer.ADSRSynthesizer.render_batch); off by default, as the reference's NumPy synth ignores the wheel."""
     if scoring not in ("loop", "batch"):
         raise ValueError('scoring must be "loop" or "batch"')
     print("[AutoMatcher] auto parameter matching: coarse grid (27 candidates)")
@@ -154,13 +158,13 @@ def auto_match_parameters(original_audio_path, engine, raw_data, sample_rate=441
                 print(f"[AutoMatcher] similarity failed: {e}")
                 y_orig = np.zeros(0, np.float32)
         best_score, best_params = _stage(COARSE_GRID, False, original_audio_path, engine, raw_data, sample_rate,
-                                         progress_callback, -1.0, None, handles, y_orig)
+                                         progress_callback, -1.0, None, handles, y_orig, pitch_bend, pitch_bend_range)
         if not best_params:
             print("[AutoMatcher] no valid result")
             return None
         print(f"[AutoMatcher] coarse best: {best_params}, score={best_score:.3f}")
         best_score, best_params = _stage(_fine_grid(best_params), True, original_audio_path, engine, raw_data, sample_rate,
-                                         progress_callback, best_score, best_params, handles, y_orig)
+                                         progress_callback, best_score, best_params, handles, y_orig, pitch_bend, pitch_bend_range)
         print(f"[AutoMatcher] final best: {best_params}, score={best_score:.3f}")
         return {**best_params, "score": best_score}
     finally:

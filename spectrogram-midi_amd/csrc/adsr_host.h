@@ -1,6 +1,7 @@
 // Host preparation of the ADSR note (adsr.h): everything that is Python-float arithmetic in the reference (frequencies
 // through the host pow, durations, segment lengths and steps, the velocity scale: synthesizer.py:226-374), and the per-tile
-// note lists of the mix.  Host-only and free of the handle: tools/adsr_host_check.cpp includes it without the library.
+// note lists of the mix, and the pitch-wheel segments of a bent note (adsr_bend_segments; adsr.h states the semantics).
+// Host-only and free of the handle: tools/adsr_host_check.cpp and tools/bend_host_check.cpp include it without the library.
 #pragma once
 #include <algorithm>
 #include <climits>
@@ -44,6 +45,69 @@ inline bool adsr_make_osc(int32_t sr, double freq, double full, int32_t waveform
     return true;
 }
 
+// ---- pitch wheel (the semantics are stated in adsr.h) -------------------------------------------------------------------
+inline bool adsr_bend_range_ok(double range) { return std::isfinite(range) && range > 0.0 && range <= 24.0; }
+
+// r(v): Python-float arithmetic, as adsr_midi_freq is.  Python's 2.0 ** x is libm's pow; a compiler that sees the constant
+// base turns pow(2, x) into exp2(x), which libm rounds differently for 25 of the 16384 wheel values at range 2: the base is
+// read through a volatile so that the call stays pow.
+inline double adsr_bend_ratio(int32_t v, double range) {
+    const volatile double two = 2.0;
+    return std::pow(two, (((double)v / 8192.0) * range) / 12.0);
+}
+
+// The segments of one note from the wheel events of its track in file order, times NON-DECREASING (the reader gives them
+// so, aegis_synth_adsr_bend refuses others): `out` gets (T_k, C_k, g_k, s_k) and r_max the largest ratio among them.  False,
+// with `out` empty, for an unbent note (one segment of value 0).  start, full, step: the note's start in seconds, its
+// oscillator's full duration and its step (full / n).  Only the events of [start, start + full) and the last one before
+// are looked at, one bisection and then the note's own events: a clip costs O(notes * log(events) + segments).
+inline bool adsr_bend_segments(double freq, double start, double full, double step, const double *time,
+                               const int32_t *value, int64_t n_events, double range, std::vector<AdsrSeg> &out, double &r_max) {
+    out.clear();
+    r_max = 1.0;
+    struct Ev { double time, T; int32_t v; };
+    std::vector<Ev> ev;                              // collapsed: segment 0, then one entry per distinct later time
+    const double end = start + full;
+    const int64_t first = std::upper_bound(time, time + n_events, start) - time;      // the first event after note-on
+    ev.push_back({start, 0.0, first > 0 ? value[first - 1] : 0});                      // the last one up to it wins
+    for (int64_t e = first; e < n_events && time[e] < end; ++e) {
+        if (ev.size() > 1 && ev.back().time == time[e]) ev.back().v = value[e];
+        else ev.push_back({time[e], time[e] - start, value[e]});
+    }
+    size_t kept = 1;                                 // merge adjacent segments of equal value
+    for (size_t e = 1; e < ev.size(); ++e)
+        if (ev[e].v != ev[kept - 1].v) ev[kept++] = ev[e];
+    ev.resize(kept);
+    if (kept == 1 && ev[0].v == 0) return false;
+    double C = 0.0;
+    for (size_t k = 0; k < kept; ++k) {
+        const double r = adsr_bend_ratio(ev[k].v, range);
+        AdsrSeg sg{ev[k].T, C, freq * r, 0};
+        if (k > 0) {
+            int64_t i = (int64_t)std::ceil(sg.T / step);                     // a guess, then the rule itself
+            if (i < 0) i = 0;
+            while (i > 0 && (double)(i - 1) * step >= sg.T) --i;
+            while ((double)i * step < sg.T) ++i;
+            sg.s = i;
+        }
+        if (k == 0 || r > r_max) r_max = r;
+        out.push_back(sg);
+        if (k + 1 < kept) C = C + sg.g * (ev[k + 1].T - sg.T);
+    }
+    return true;
+}
+
+// adsr_make_osc of a bent note: harmonic h >= 2 is used while (freq * h) * r_max < sr / 2
+inline bool adsr_make_bent_osc(int32_t sr, double freq, double full, int32_t waveform, double r_max, AdsrOsc &o) {
+    if (!adsr_make_osc(sr, freq, full, waveform, o)) return false;
+    o.n_harm = 1;
+    for (int hh = 2; hh <= 5; ++hh) {
+        if (!((freq * (double)hh) * r_max < (double)sr / 2.0)) break;
+        o.n_harm = hh;
+    }
+    return true;
+}
+
 // envelope p and velocity on an oscillator of n samples: all of them count, from output sample 0 (the caller places it)
 inline AdsrNote adsr_make_note(int32_t sr, const aegis_adsr_params &p, int64_t n, int32_t velocity) {
     AdsrNote c{};
@@ -65,11 +129,14 @@ inline AdsrNote adsr_make_note(int32_t sr, const aegis_adsr_params &p, int64_t n
 struct AdsrBatch {
     std::vector<AdsrOsc> oscs;
     std::vector<AdsrNote> notes;                     // notes[q] plays oscs[q]
+    std::vector<AdsrBend> bends;                     // bends[q]: the slice of segs of oscs[q]; count 0: unbent
+    std::vector<AdsrSeg> segs;                       // empty: no note of the batch is bent, and bends is not looked at
     std::vector<AdsrTile> tiles;
     std::vector<int32_t> tile_notes;
     std::vector<int64_t> clip_off, clip_total;       // per clip: first sample in the batch, samples
     int64_t samples = 0;
     size_t tile0 = 0, note0 = 0;                     // of the open clip
+    bool too_large = false;                          // the segment table outgrew 32-bit indices (add_note)
 
     void add_clip(int64_t total) {
         tile0 = tiles.size(); note0 = notes.size();
@@ -80,16 +147,26 @@ struct AdsrBatch {
     }
     // nt.start is the note's first output sample.  A note that does not reach the mix (it starts at or past the end of the
     // file) leaves no record: no peak is computed for it.
-    void add_note(const AdsrOsc &o, AdsrNote nt) {
+    // bent: the note's segments (adsr_bend_segments), or null / empty for an unbent note.  A segment table past 2^31 - 1
+    // entries has no 32-bit slice: the batch is marked too large and close_clip refuses it, so no such slice is ever used.
+    void add_note(const AdsrOsc &o, AdsrNote nt, const std::vector<AdsrSeg> *bent = nullptr) {
         const int64_t total = clip_total.back();
         nt.n_cut = nt.start < total ? std::min(o.n, total - nt.start) : 0;
         if (nt.n_cut <= 0) return;
         nt.osc = (int32_t)oscs.size();
         oscs.push_back(o);
         notes.push_back(nt);
+        if (bent && !bent->empty()) {
+            if (segs.size() + bent->size() > (size_t)INT32_MAX) { too_large = true; bends.push_back(AdsrBend{0, 0}); return; }
+            bends.push_back(AdsrBend{(int32_t)segs.size(), (int32_t)bent->size()});
+            segs.insert(segs.end(), bent->begin(), bent->end());
+        } else {
+            bends.push_back(AdsrBend{0, 0});
+        }
     }
     // per-tile note lists in mix order (counting pass, then fill); false when the batch outgrows 32-bit indices
     bool close_clip() {
+        if (too_large) return false;
         const size_t n_tiles = tiles.size() - tile0;
         std::vector<int64_t> count(n_tiles, 0);
         for (size_t q = note0; q < notes.size(); ++q)

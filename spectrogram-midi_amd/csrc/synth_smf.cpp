@@ -11,6 +11,9 @@
 //   that one value converts every delta of every track; the time is accumulated per track in float64, message by message;
 //   a note_on with velocity > 0 overwrites an active entry of the same note number (per track, channels ignored); a
 //   note_off or a note_on of velocity 0 closes it with duration = max(0.01, now - start); notes never closed are dropped.
+// Beyond the reference, for the opt-in pitch-wheel render (adsr.h): every pitch-wheel message is kept as (time, track,
+// value), its time from the same per-track `now += delta * scale` as the notes' (a note_on and a wheel at one tick have
+// bit-equal times), channels ignored as the note loop ignores them; and every note keeps the index of its track.
 #include <algorithm>
 #include <cstdint>
 #include <string>
@@ -22,7 +25,7 @@ namespace aegis {
 namespace {
 
 constexpr size_t kMaxMessages = (size_t)1 << 26;      // x 2^28 ticks each: absolute ticks stay below 2^54
-enum Kind : uint8_t { kOther, kNoteOn, kNoteOff, kTempo, kEndOfTrack };
+enum Kind : uint8_t { kOther, kNoteOn, kNoteOff, kTempo, kEndOfTrack, kWheel };
 struct Msg { int64_t delta; Kind kind; int32_t a, b; };
 
 struct Reader {
@@ -81,7 +84,8 @@ bool read_track(const uint8_t *d, int64_t n, std::vector<Msg> &msgs, std::string
         if (!r.ok) break;
         if (hi == 0x90) msgs.push_back({delta, kNoteOn, data[0], data[1]});
         else if (hi == 0x80) msgs.push_back({delta, kNoteOff, data[0], data[1]});
-        else msgs.push_back({delta, kOther, 0, 0});      // pitch wheel, program, controllers: ignored by the reference
+        else if (hi == 0xE0) msgs.push_back({delta, kWheel, (data[0] | (data[1] << 7)) - 8192, 0});   // ignored by the reference
+        else msgs.push_back({delta, kOther, 0, 0});      // program, controllers: ignored by the reference
     }
     if (!r.ok) { err = "truncated track data"; return false; }
     return true;
@@ -91,6 +95,8 @@ bool read_track(const uint8_t *d, int64_t n, std::vector<Msg> &msgs, std::string
 
 bool parse_smf_notes(const uint8_t *data, int64_t n, SmfNotes &out, std::string &err) {
     out.notes.clear();
+    out.note_track.clear();
+    out.wheel.clear();
     out.length = 0.0;
     if (!data || n < 14 || data[0] != 'M' || data[1] != 'T' || data[2] != 'h' || data[3] != 'd') { err = "not a Standard MIDI File"; return false; }
     Reader r{data, n};
@@ -117,7 +123,8 @@ bool parse_smf_notes(const uint8_t *data, int64_t n, SmfNotes &out, std::string 
             if (m.kind == kTempo) { tempo = m.a; break; }
     const double scale = (double)tempo * 1e-6 / (double)tpb;
     // the note loop, track after track
-    for (const auto &tr : tracks) {
+    for (size_t t = 0; t < tracks.size(); ++t) {
+        const auto &tr = tracks[t];
         double now = 0.0;
         double start[128];
         int32_t vel[128];
@@ -133,7 +140,9 @@ bool parse_smf_notes(const uint8_t *data, int64_t n, SmfNotes &out, std::string 
                 nt.note = m.a;
                 nt.velocity = vel[m.a];
                 out.notes.push_back(nt);
+                out.note_track.push_back((int32_t)t);
             }
+            else if (m.kind == kWheel) out.wheel.push_back(aegis_synth_wheel{now, (int32_t)t, m.a});
         }
     }
     // MidiFile.length

@@ -234,9 +234,10 @@ def _engine_rate_ok(engine):
 
 
 def learning_loop(midi_data, engine, effects_config, max_iterations=5, target_accuracy=0.95, progress_callback=None,
-                  preset="electric_clean", rng=None, reanalyse=False):
+                  preset="electric_clean", rng=None, reanalyse=False, pitch_bend=False, pitch_bend_range=2.0):
     """:489-725 -> {'best_params', 'best_accuracy', 'history', 'effect_profile'}, or None when the file holds no notes or
-    cannot be rendered."""
+    cannot be rendered.  pitch_bend / pitch_bend_range: render the file's pitch wheel
+    (synthesizer.ADSRSynthesizer.render_batch)."""
     effect_profile = _identify_effect_profile(effects_config)
     print(f"[EffectLearningLoop] effect profile: {effect_profile}")
     blob = _synth._midi_bytes(midi_data)
@@ -246,7 +247,8 @@ def learning_loop(midi_data, engine, effects_config, max_iterations=5, target_ac
         return None
     _engine_rate_ok(engine)
     handle = engine.handle
-    rendered = _synth.synthesize_midi_adsr_batch([blob], preset=preset, sample_rate=SYNTH_RATE, as_arrays=True, handle=handle)
+    rendered = _synth.synthesize_midi_adsr_batch([blob], preset=preset, sample_rate=SYNTH_RATE, as_arrays=True, handle=handle,
+                                                 **_synth._bend_kwargs(pitch_bend, pitch_bend_range))
     if not rendered or rendered[0] is None:
         print("[EffectLearningLoop] MIDI synthesis failed")
         return None
@@ -264,8 +266,8 @@ def learning_sweep(midi_list, engine, presets=EFFECT_PRESETS, timings=None, **lo
     """Not in the reference: every (file, preset) pair -> {(file_index, preset_name): what learning_loop returns for the
     pair}.  The files are rendered in ONE synth call, all pairs go through ONE aegis_effects call and ONE
     audio_to_midi_batch call (which also yields iteration 1's MIDI); the parameter loops then run on the host.
-    loop_kwargs: max_iterations, target_accuracy, progress_callback, preset, rng (one generator, consumed pair after
-    pair in the order of the result).  timings: a dict that receives the wall seconds of the stages."""
+    loop_kwargs: max_iterations, target_accuracy, progress_callback, preset, pitch_bend, pitch_bend_range, rng (one
+    generator, consumed pair after pair in the order of the result).  timings: a dict that receives the wall seconds of the stages."""
     import time
     _engine_rate_ok(engine)
     synth_preset = loop_kwargs.pop("preset", "electric_clean")
@@ -273,13 +275,16 @@ def learning_sweep(midi_list, engine, presets=EFFECT_PRESETS, timings=None, **lo
     target_accuracy = loop_kwargs.pop("target_accuracy", 0.95)
     progress_callback = loop_kwargs.pop("progress_callback", None)
     rng = loop_kwargs.pop("rng", None)
+    pitch_bend = loop_kwargs.pop("pitch_bend", False)
+    pitch_bend_range = loop_kwargs.pop("pitch_bend_range", 2.0)
     if loop_kwargs:
         raise TypeError(f"unexpected arguments: {sorted(loop_kwargs)}")
     handle = engine.handle
     t0 = time.perf_counter()
     blobs = [_synth._midi_bytes(m) for m in midi_list]
     notes = [_extract_notes_from_midi(b) for b in blobs]
-    rendered = _synth.synthesize_midi_adsr_batch(blobs, preset=synth_preset, sample_rate=SYNTH_RATE, as_arrays=True, handle=handle) or []
+    rendered = _synth.synthesize_midi_adsr_batch(blobs, preset=synth_preset, sample_rate=SYNTH_RATE, as_arrays=True, handle=handle,
+                                                 **_synth._bend_kwargs(pitch_bend, pitch_bend_range)) or []
     t1 = time.perf_counter()
     pairs = [(i, name) for i in range(len(blobs)) if notes[i] and i < len(rendered) and rendered[i] is not None for name in presets]
     results = {(i, name): None for i in range(len(blobs)) for name in presets}

@@ -9,9 +9,10 @@ from .effect_learning_loop import START_PARAMS, _analysis_input, _compare_note_l
 __all__ = ["reverse_analysis", "_extract_notes_from_midi", "_compare_note_lists"]
 
 
-def reverse_analysis(midi_data, engine, sample_rate=44100, preset="electric_clean"):
+def reverse_analysis(midi_data, engine, sample_rate=44100, preset="electric_clean", pitch_bend=False, pitch_bend_range=2.0):
     """-> {'original_notes', 'reversed_notes', 'note_accuracy', 'pitch_accuracy', 'timing_accuracy', 'reversed_midi',
-    'reversed_events'}, or None (after printing) when the file holds no notes or any step fails."""
+    'reversed_events'}, or None (after printing) when the file holds no notes or any step fails.
+    pitch_bend / pitch_bend_range: render the file's pitch wheel (synthesizer.ADSRSynthesizer.render_batch)."""
     try:
         blob = _synth._midi_bytes(midi_data)
         original_notes = _extract_notes_from_midi(blob)
@@ -20,7 +21,8 @@ def reverse_analysis(midi_data, engine, sample_rate=44100, preset="electric_clea
             return None
         if getattr(engine, "sr", sample_rate) != sample_rate:
             raise ValueError("the engine must analyse at the synthesis rate")
-        rendered = _synth.synthesize_midi_adsr_batch([blob], preset=preset, sample_rate=sample_rate, as_arrays=True, handle=engine.handle)
+        rendered = _synth.synthesize_midi_adsr_batch([blob], preset=preset, sample_rate=sample_rate, as_arrays=True, handle=engine.handle,
+                                                     **_synth._bend_kwargs(pitch_bend, pitch_bend_range))
         if not rendered or rendered[0] is None:
             print("[ReverseAnalyzer] MIDI synthesis failed")
             return None

@@ -6,7 +6,9 @@ of the reference bit for bit for sawtooth, triangle and square, and within one i
 The MIDI file is read by the library's own reader (csrc/synth_smf.cpp: mido is not a dependency), the per-sample work
 runs in csrc/adsr.hip (`aegis_synth_adsr`).  There is no CPU path.  `FluidSynthSynthesizer` and `synthesize_midi` are
 not ported.  New here: `synthesize_midi_adsr_batch`, any number of files with their own parameters in one device call
-(what Auto-Match renders a stage of candidates with, auto_matcher.py)."""
+(what Auto-Match renders a stage of candidates with, auto_matcher.py); and `pitch_bend=True`, which renders the file's
+pitch-wheel messages (the bends and vibratos smf.render writes) as FluidSynth would, `pitch_bend_range` semitones at full
+deflection (`aegis_synth_adsr_bend`).  The reference's NumPy synth ignores the wheel, and so does the default here."""
 import io
 import wave
 
@@ -37,6 +39,14 @@ def _default_handle():
         live = [h for h in list(_lib._live_handles) if getattr(h, "_h", None) and h.device >= 0]
         _shared_handle = live[0] if live else _lib.Handle(device=0, scipy_tables=False)
     return _shared_handle
+
+
+def _bend_kwargs(pitch_bend, pitch_bend_range=2.0):
+    """What a consumer (auto_matcher, effect_learning_loop, reverse_analyzer) adds to its synthesize_midi_adsr_batch call:
+    the two pitch-wheel keywords when the wheel is asked for, and nothing otherwise.  The default call is thereby the very
+    call it was before the wheel existed, which is what stand-ins for the synth with the earlier signature (as the
+    Auto-Match host tests patch in) still accept."""
+    return {"pitch_bend": True, "pitch_bend_range": pitch_bend_range} if pitch_bend else {}
 
 
 def _midi_bytes(midi_data):
@@ -71,21 +81,26 @@ class ADSRSynthesizer:
             self._handle = _default_handle()
         return self._handle
 
-    def render_batch(self, midi_list, param_list):
-        """int16 arrays of several files, each with its own parameter dict, in ONE device call."""
+    def render_batch(self, midi_list, param_list, pitch_bend=False, pitch_bend_range=2.0):
+        """int16 arrays of several files, each with its own parameter dict, in ONE device call.  pitch_bend=True: the
+        wheel of every file bends the notes of its track, pitch_bend_range semitones at full deflection."""
         h = self.handle
-        parsed = [h.synth_parse_smf(_midi_bytes(m)) for m in midi_list]
+        parsed = [h.synth_parse_smf(_midi_bytes(m), want_wheel=bool(pitch_bend)) for m in midi_list]
         params = [h.adsr_params(**{k: p.get(k, v) for k, v in _PARAM_DEFAULTS.items()}) for p in param_list]
-        return h.synth_adsr([n for n, _ in parsed], [length for _, length in parsed], params, self.sr)
+        bends = [(p[2], p[3], pitch_bend_range) for p in parsed] if pitch_bend else None
+        return h.synth_adsr([p[0] for p in parsed], [p[1] for p in parsed], params, self.sr, bends=bends)
 
-    def midi_to_samples(self, midi_data, attack_ms=10, decay_ms=50, sustain_level=0.7, release_ms=100, waveform="sawtooth"):
+    def midi_to_samples(self, midi_data, attack_ms=10, decay_ms=50, sustain_level=0.7, release_ms=100, waveform="sawtooth",
+                        pitch_bend=False, pitch_bend_range=2.0):
         return self.render_batch([midi_data], [dict(attack_ms=attack_ms, decay_ms=decay_ms, sustain_level=sustain_level,
-                                                    release_ms=release_ms, waveform=waveform)])[0]
+                                                    release_ms=release_ms, waveform=waveform)], pitch_bend, pitch_bend_range)[0]
 
-    def midi_to_wav(self, midi_data, attack_ms=10, decay_ms=50, sustain_level=0.7, release_ms=100, waveform="sawtooth"):
+    def midi_to_wav(self, midi_data, attack_ms=10, decay_ms=50, sustain_level=0.7, release_ms=100, waveform="sawtooth",
+                    pitch_bend=False, pitch_bend_range=2.0):
         """synthesizer.py:379-485: MIDI bytes (or BytesIO) -> WAV bytes.  Raises what the reference raises on: bytes
-        that are not a MIDI file, an unknown waveform."""
-        return wav_bytes(self.midi_to_samples(midi_data, attack_ms, decay_ms, sustain_level, release_ms, waveform), self.sr)
+        that are not a MIDI file, an unknown waveform.  pitch_bend / pitch_bend_range: see render_batch."""
+        return wav_bytes(self.midi_to_samples(midi_data, attack_ms, decay_ms, sustain_level, release_ms, waveform,
+                                              pitch_bend, pitch_bend_range), self.sr)
 
     def synthesize_note(self, freq, duration, velocity=100, attack_ms=10, decay_ms=50, sustain_level=0.7, release_ms=100,
                         waveform="sawtooth", harmonics=True):
@@ -172,24 +187,27 @@ def _preset_params(preset, overrides=None):
     return params
 
 
-def synthesize_midi_adsr(midi_data, preset="electric_clean", sample_rate=44100, **adsr_overrides):
-    """synthesizer.py:642-699: WAV bytes, or None (after printing) on any failure."""
+def synthesize_midi_adsr(midi_data, preset="electric_clean", sample_rate=44100, pitch_bend=False, pitch_bend_range=2.0, **adsr_overrides):
+    """synthesizer.py:642-699: WAV bytes, or None (after printing) on any failure.  pitch_bend / pitch_bend_range (not in
+    the reference): see ADSRSynthesizer.render_batch."""
     synth = get_adsr_synthesizer(sr=sample_rate)
     params = _preset_params(preset, adsr_overrides)
     try:
         return synth.midi_to_wav(midi_data, attack_ms=params.get("attack_ms", 10), decay_ms=params.get("decay_ms", 50),
                                  sustain_level=params.get("sustain_level", 0.7), release_ms=params.get("release_ms", 100),
-                                 waveform=params.get("waveform", "sawtooth"))
+                                 waveform=params.get("waveform", "sawtooth"), pitch_bend=pitch_bend, pitch_bend_range=pitch_bend_range)
     except Exception as e:                                   # noqa: BLE001 -- mirrors the reference's catch-all
         print(f"ADSR MIDI 합성 실패: {e}")
         return None
 
 
-def synthesize_midi_adsr_batch(midi_list, preset="electric_clean", sample_rate=44100, as_arrays=False, handle=None):
+def synthesize_midi_adsr_batch(midi_list, preset="electric_clean", sample_rate=44100, as_arrays=False, handle=None,
+                               pitch_bend=False, pitch_bend_range=2.0):
     """Not in the reference: several MIDI files in ONE device call.  `preset`: a preset name for all of them, or a list
     with one entry per file, each a preset name or a parameter dict (missing keys take midi_to_wav's defaults).
     -> list of WAV bytes (int16 arrays with as_arrays=True); a file that fails gives None at its place, after printing, as
-    the single call does (None for the whole list only when the arguments do not fit together)."""
+    the single call does (None for the whole list only when the arguments do not fit together).  pitch_bend /
+    pitch_bend_range: see ADSRSynthesizer.render_batch."""
     midi_list = list(midi_list)
     per = list(preset) if isinstance(preset, (list, tuple)) else [preset] * len(midi_list)
     try:
@@ -205,22 +223,23 @@ def synthesize_midi_adsr_batch(midi_list, preset="electric_clean", sample_rate=4
     for i, (m, p) in enumerate(zip(midi_list, params)):      # a file that cannot be read or rendered costs its own entry only
         try:
             blob = _midi_bytes(m)
-            notes, length = synth.handle.synth_parse_smf(blob)
+            notes, length, *wheel = synth.handle.synth_parse_smf(blob, want_wheel=bool(pitch_bend))
             par = synth.handle.adsr_params(**{k: p.get(k, v) for k, v in _PARAM_DEFAULTS.items()})
             if synth.handle.lib.aegis_synth_samples_for(int(sample_rate), length, par) < 0:
                 raise ValueError("bad ADSR parameters, sample rate or length")
-            good.append((i, notes, length, par))
+            good.append((i, notes, length, par, (wheel[0], wheel[1], pitch_bend_range) if pitch_bend else None))
         except Exception as e:                               # noqa: BLE001
             print(f"ADSR MIDI 합성 실패: {e}")
     try:
-        got = synth.handle.synth_adsr([g[1] for g in good], [g[2] for g in good], [g[3] for g in good], sample_rate)
+        got = synth.handle.synth_adsr([g[1] for g in good], [g[2] for g in good], [g[3] for g in good], sample_rate,
+                                      bends=[g[4] for g in good] if pitch_bend else None)
         for (i, *_), a in zip(good, got):
             out[i] = a
     except Exception as e:                                   # noqa: BLE001 -- the batch failed as a whole: file by file
         print(f"ADSR MIDI 합성 실패: {e}")
-        for i, notes, length, par in good:
+        for i, notes, length, par, bend in good:
             try:
-                out[i] = synth.handle.synth_adsr([notes], [length], [par], sample_rate)[0]
+                out[i] = synth.handle.synth_adsr([notes], [length], [par], sample_rate, bends=[bend] if pitch_bend else None)[0]
             except Exception as e2:                          # noqa: BLE001
                 print(f"ADSR MIDI 합성 실패: {e2}")
     return out if as_arrays else [None if a is None else wav_bytes(a, sample_rate) for a in out]
