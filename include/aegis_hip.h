@@ -506,6 +506,45 @@ int64_t aegis_synth_notes_samples_for(int32_t sample_rate, double length_seconds
 int aegis_synth_adsr_notes(aegis_handle *h, int32_t sample_rate, int32_t n_clips, const aegis_synth_note *notes, const int64_t *note_off,
                            const double *length_seconds, const aegis_adsr_params *params, int16_t *const *out, const int64_t *out_cap);
 
+/* --- Technique verifier (aegis_engine_core/technique_verifier.py, corrected) ---------------------------------------
+ * The reference renders every event that carries a technique twice, with the technique and as a plain note, compares both
+ * renders with the take's own segment by the cosine of their mel-dB images, and keeps the technique only if the first wins
+ * and scores above 0.6.  Two corrections (csrc/verify.h and DESIGN.md 3.15 state the semantics): the variants are rendered
+ * from frame 0, where the reference keeps the event's absolute tick and compares the segment with silence; and the
+ * velocity-only variants (hammer_on, pull_off), which a peak-normalising synth renders as the same samples, are the
+ * caller's to pass through.
+ *   aegis_verify_techniques   n_events events over n_clips clips in ONE call.  Clip c is audio[c], n_samples[c] float32
+ *                     samples in host memory.  Event k compares the segment [lo, hi) of clip events[k].clip (the reference's
+ *                     bounds are the caller's to compute) with the first hi - lo samples of two one-file renders: file 2k is
+ *                     the event "with" its technique, file 2k + 1 "without", given as aegis_synth_adsr_bend takes its clips
+ *                     (notes, note_off, length_seconds, params, note_track, wheel, wheel_off, bend_range, all of 2 * n_events
+ *                     files) and rendered by the same kernels, master normalisation and int16 conversion included; the signal
+ *                     is int16 / 32768 and never leaves the device.  The score of a signal pair: mel power of 2048 / 512
+ *                     frames (center, zero padding, periodic Hann) through the Slaney bank of 128 bands from 0 to 8000 Hz,
+ *                     power_to_db(ref=max, amin 1e-10, top_db 80), cosine of the flattened images, 0.0 when either image has
+ *                     norm zero.  sim[2k] = with, sim[2k + 1] = without; keep[k] = sim_with > sim_without && sim_with > 0.6.
+ *                     float64 throughout, within the bound of DESIGN.md 3.15 of tools/verify_restated.py.  A result is a
+ *                     function of the event alone: the same bits alone, in any batch and under any regrouping.
+ *                     Rejected (AEGIS_ERR_INVALID): lo > hi, a slice outside its clip, hi - lo < sample_rate * 0.05 (the
+ *                     caller's to filter), sample_rate < 16000 (8000 Hz would exceed Nyquist), a handle whose n_fft is not
+ *                     2048, everything aegis_synth_adsr_bend rejects, a render shorter than its segment.  Requests are
+ *                     validated before the device is looked at: a device = -1 handle rejects what a device handle rejects
+ *                     and answers AEGIS_ERR_DEVICE to valid requests.  n_events == 0: AEGIS_OK without a launch.  When the
+ *                     workspace (3 * (1 + (hi - lo) / 512) * 128 doubles per event) cannot be allocated the batch is
+ *                     halved and retried.  Kernel times: "verify_note_peak", "verify_mix", "verify_master", "verify_mel",
+ *                     "verify_score".  Blocking; host pointers. */
+typedef struct aegis_verify_event {
+    int32_t clip, reserved;       /* index into audio[] */
+    int64_t lo, hi;               /* the segment within the clip */
+} aegis_verify_event;
+int aegis_verify_techniques(aegis_handle *h, int32_t sample_rate, int32_t n_clips, const float *const *audio,
+                            const int64_t *n_samples, int32_t n_events, const aegis_verify_event *events,
+                            /* 2 * n_events one-file renders, file 2k = with, 2k + 1 = without, as aegis_synth_adsr_bend takes them */
+                            const aegis_synth_note *notes, const int64_t *note_off, const double *length_seconds,
+                            const aegis_adsr_params *params, const int32_t *note_track, const aegis_synth_wheel *wheel,
+                            const int64_t *wheel_off, const double *bend_range,
+                            double *sim /* [2 * n_events] */, uint8_t *keep /* [n_events] */);
+
 /* --- Effect chain: distortion, reverb, delay, chorus (aegis_engine_core/effect_learning_loop.py:56-275) ----------
  * The reference's pure-NumPy effects, each ending in a whole-clip normalisation, which its learning loop
  * (effect_learning_loop.py:489-725) puts between the synthesiser and the engine.  Float64 throughout.

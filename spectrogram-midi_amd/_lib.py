@@ -66,6 +66,10 @@ class FitNote(C.Structure):
                 ("reserved", C.c_int32), ("duration", C.c_double)]
 
 
+class VerifyEvent(C.Structure):
+    _fields_ = [("clip", C.c_int32), ("reserved", C.c_int32), ("lo", C.c_int64), ("hi", C.c_int64)]
+
+
 class Effect(C.Structure):
     _fields_ = [("kind", C.c_int32), ("n_ir", C.c_int32), ("p0", C.c_double), ("p1", C.c_double), ("ir", C.c_void_p)]
 
@@ -89,7 +93,7 @@ EXPORTS = ("aegis_abi_version", "aegis_create", "aegis_destroy", "aegis_last_err
            "aegis_debug_set_observations", "aegis_debug_set_difference", "aegis_estimate_tuning",
            "aegis_reverb_ir", "aegis_effects",
            "aegis_note_fit", "aegis_compare_audio", "aegis_synth_one_note", "aegis_synth_notes_samples_for", "aegis_synth_adsr_notes",
-           "aegis_synth_parse_smf_wheel", "aegis_synth_adsr_bend")
+           "aegis_synth_parse_smf_wheel", "aegis_synth_adsr_bend", "aegis_verify_techniques")
 
 _lib = None
 
@@ -204,6 +208,10 @@ def load():
     lib.aegis_synth_adsr_notes.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(AdsrParams),
                                            C.POINTER(C.c_void_p), C.c_void_p]
     lib.aegis_synth_adsr_notes.restype = C.c_int
+    lib.aegis_verify_techniques.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.c_void_p, C.c_int32, C.POINTER(VerifyEvent),
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(AdsrParams), C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.aegis_verify_techniques.restype = C.c_int
     lib.aegis_set_profiling.argtypes = [C.c_void_p, C.c_int32]
     lib.aegis_set_profiling.restype = C.c_int
     lib.aegis_last_kernel_ms.argtypes = [C.c_void_p, C.c_char_p]
@@ -773,6 +781,43 @@ class Handle:
             raise ValueError(self.lib.aegis_last_error(self._h).decode())
         self._check(rc)
         return out[:n]
+
+    def verify_techniques(self, clips, events, variants, sample_rate):
+        """aegis_verify_techniques: ONE device call for any number of events of any number of clips.  clips: 1-D arrays
+        (read as float32); events: per event (clip index, lo, hi); variants: per event the two one-file renders, "with"
+        then "without", each (notes SYNTH_NOTE_DTYPE, length in seconds, AdsrParams, note_track, wheel SYNTH_WHEEL_DTYPE,
+        bend_range) as synth_parse_smf(want_wheel=True) gives them.  -> (sim float64 [n_events, 2]: with, without;
+        keep bool [n_events]).  ValueError for what the library rejects."""
+        if len(events) != len(variants) or any(len(v) != 2 for v in variants):
+            raise ValueError("two variants per event")
+        clips = [np.ascontiguousarray(c, dtype=np.float32) for c in clips]
+        n = len(events)
+        files = [f for v in variants for f in v]
+        off = np.zeros(2 * n + 1, np.int64)
+        off[1:] = np.cumsum([len(f[0]) for f in files])
+        woff = np.zeros(2 * n + 1, np.int64)
+        woff[1:] = np.cumsum([len(f[4]) for f in files])
+        notes = np.ascontiguousarray(np.concatenate([np.asarray(f[0], SYNTH_NOTE_DTYPE) for f in files]) if off[-1]
+                                     else np.empty(0, SYNTH_NOTE_DTYPE), dtype=SYNTH_NOTE_DTYPE)
+        track = np.ascontiguousarray(np.concatenate([np.asarray(f[3], np.int32) for f in files]) if off[-1] else np.empty(0, np.int32),
+                                     dtype=np.int32)
+        wheel = np.ascontiguousarray(np.concatenate([np.asarray(f[4], SYNTH_WHEEL_DTYPE) for f in files]) if woff[-1]
+                                     else np.empty(0, SYNTH_WHEEL_DTYPE), dtype=SYNTH_WHEEL_DTYPE)
+        lens = np.ascontiguousarray([float(f[1]) for f in files] or [0.0], dtype=np.float64)
+        ranges = np.ascontiguousarray([float(f[5]) for f in files] or [0.0], dtype=np.float64)
+        par = (AdsrParams * max(2 * n, 1))(*[f[2] for f in files])
+        arr = (VerifyEvent * max(n, 1))(*[VerifyEvent(int(c), 0, int(lo), int(hi)) for c, lo, hi in events])
+        ptrs = (C.c_void_p * max(len(clips), 1))(*[c.ctypes.data for c in clips])
+        sizes = np.asarray([len(c) for c in clips] or [0], np.int64)
+        sim = np.zeros((max(n, 1), 2), np.float64)
+        keep = np.zeros(max(n, 1), np.uint8)
+        rc = self.lib.aegis_verify_techniques(self._h, int(sample_rate), len(clips), ptrs, sizes.ctypes.data, n, arr, notes.ctypes.data,
+                                              off.ctypes.data, lens.ctypes.data, par, track.ctypes.data, wheel.ctypes.data,
+                                              woff.ctypes.data, ranges.ctypes.data, sim.ctypes.data, keep.ctypes.data)
+        if rc == ERR_INVALID:
+            raise ValueError(self.lib.aegis_last_error(self._h).decode())
+        self._check(rc)
+        return sim[:n], keep[:n].astype(bool)
 
     def synth_note(self, freq, duration, velocity, params, sample_rate):
         """aegis_synth_one_note: ADSRSynthesizer.synthesize_note (harmonics on) -> float64 array of int(sr * duration)."""

@@ -10,6 +10,8 @@
 //   aegis_effects.hip aegis_reverb_ir, aegis_effects (the effect chain; kernels in effects.hip)
 //   aegis_notefit.hip aegis_note_fit, aegis_compare_audio, aegis_synth_one_note (the per-note optimiser; kernels in
 //                     notefit.hip and adsr.hip)
+//   aegis_verify.hip  aegis_verify_techniques (the technique verifier; kernels in verify.hip, its renders through
+//                     aegis_synth.hip's render_into)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -125,6 +127,11 @@ struct aegis_handle {
     // aegis_note_fit / aegis_compare_audio / aegis_synth_one_note: slices, records, per-frame features, scores; stored note
     DevBuf nf_audio, nf_oscs, nf_cands, nf_notes, nf_boff, nf_peak, nf_cnum, nf_cden, nf_zc, nf_rms, nf_out, nf_best;
     DevBuf nf_sig, nf_sigoff, nf_cands2;
+    // aegis_verify_techniques: segments, event records, mel power, signal maxima, results; the fmax-8000 mel bank of every
+    // sample rate asked for so far (map nodes never move, so the DevBufs inside may be listed in bufs)
+    DevBuf vf_audio, vf_events, vf_boff, vf_mel, vf_max, vf_sim, vf_keep;
+    struct VerifyBank { aegis::MelBank host; int32_t n_used = 0; bool uploaded = false; DevBuf start, len, off, w; };
+    std::map<int32_t, VerifyBank> vf_banks;
     bool notefit_store = false;               // AEGIS_NOTEFIT_STORE=1 at create: every candidate rendered once into nf_sig and read by the frames instead of recomputed
     int32_t lag_stride = 0, yin_stride = 0, obs_stride = 0;
     aegis::CallPlan plan;                     // the last call's plan: its host arrays stay alive until the stream drained
@@ -247,6 +254,17 @@ int run_halving(aegis_handle *h, int32_t n, F &&group) {
     }
     return AEGIS_OK;
 }
+
+// ---- the bent ADSR render as a stage of another entry (aegis_synth.hip; AdsrBatch: adsr_host.h) ----
+struct AdsrBatch;
+int check_bend_request(aegis_handle *h, int32_t sample_rate, int32_t n_clips, const aegis_synth_note *notes, const int64_t *note_off,
+                       const double *length_seconds, const aegis_adsr_params *params, const int32_t *note_track,
+                       const aegis_synth_wheel *wheel, const int64_t *wheel_off, const double *bend_range, int16_t *const *out,
+                       const int64_t *out_cap);
+int fill_bend_batch(aegis_handle *h, int32_t sr, int32_t c0, int32_t c1, const aegis_synth_note *notes, const int64_t *note_off,
+                    const double *length_seconds, const aegis_adsr_params *params, const int32_t *note_track,
+                    const aegis_synth_wheel *wheel, const int64_t *wheel_off, const double *bend_range, AdsrBatch &B);
+int render_into(aegis_handle *h, const AdsrBatch &B, const char *const (&labels)[3]);
 
 // ---- kernel parameters every entry fills the same way (aegis_api.hip) ----
 struct RakeBounds { int min_frames, max_frames; };

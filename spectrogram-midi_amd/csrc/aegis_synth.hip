@@ -62,13 +62,13 @@ bool add_note(AdsrBatch &B, int32_t sr, const aegis_synth_note &in, const aegis_
 }
 
 // What both one-envelope entries ask of clip c before anything runs: its slice of the notes, its parameters and length, room
-// for its samples.  AEGIS_ERR_INVALID with h->err set, or AEGIS_OK.
+// for its samples (out null: the samples stay on the device, nothing to size).  AEGIS_ERR_INVALID with h->err set, or AEGIS_OK.
 int check_clip(aegis_handle *h, int32_t sr, int32_t c, const aegis_synth_note *notes, const int64_t *note_off,
                const double *length_seconds, const aegis_adsr_params *params, int16_t *const *out, const int64_t *out_cap) {
     if (note_off[c + 1] < note_off[c] || (note_off[c + 1] > note_off[c] && !notes)) { h->err = "note_off must be non-decreasing"; return AEGIS_ERR_INVALID; }
     const int64_t need = aegis_synth_samples_for(sr, length_seconds[c], &params[c]);
     if (need < 0) { h->err = "bad ADSR parameters or length (clip " + std::to_string(c) + ")"; return AEGIS_ERR_INVALID; }
-    if (out_cap[c] < need || (need > 0 && !out[c])) { h->err = "output of clip " + std::to_string(c) + " is too small"; return AEGIS_ERR_INVALID; }
+    if (out && (out_cap[c] < need || (need > 0 && !out[c]))) { h->err = "output of clip " + std::to_string(c) + " is too small"; return AEGIS_ERR_INVALID; }
     return AEGIS_OK;
 }
 
@@ -80,9 +80,12 @@ int check_note(aegis_handle *h, int32_t sr, int32_t c, int64_t k, const aegis_sy
     return AEGIS_OK;
 }
 
-// One device pass (handle locked): upload, peaks, mix, master, every clip's samples to out[clip of the batch].
+}  // namespace
+
+// The render half of a device pass (handle locked): upload, peaks, mix, master.  Clip c of the batch then lies as int16 at
+// sy_out + B.clip_off[c] once the stream has run; nothing is copied out and nothing is waited for.
 // labels: the profiling names of the three kernels.
-int render_group(aegis_handle *h, const AdsrBatch &B, int16_t *const *out, const char *const (&labels)[3]) {
+int aegis::render_into(aegis_handle *h, const AdsrBatch &B, const char *const (&labels)[3]) {
     if (B.samples == 0) return AEGIS_OK;
     hipStream_t s = h->stream;
     const size_t nc = B.clip_off.size();
@@ -121,6 +124,19 @@ int render_group(aegis_handle *h, const AdsrBatch &B, int16_t *const *out, const
     launch_adsr_master(d_tiles, d_mix, d_cpeak, d_out, (int32_t)B.tiles.size(), s);
     end_event(h, s);
     HIPCHK_SYNC(h, s, hipGetLastError());
+    return AEGIS_OK;
+}
+
+namespace {
+
+// One device pass (handle locked): render_into, then every clip's samples to out[clip of the batch].
+int render_group(aegis_handle *h, const AdsrBatch &B, int16_t *const *out, const char *const (&labels)[3]) {
+    if (B.samples == 0) return AEGIS_OK;
+    const int rc = render_into(h, B, labels);
+    if (rc != AEGIS_OK) return rc;
+    hipStream_t s = h->stream;
+    const size_t nc = B.clip_off.size();
+    const int16_t *d_out = static_cast<const int16_t *>(h->sy_out.p);
     for (size_t c = 0; c < nc; ++c)
         if (B.clip_total[c] > 0) HIPCHK_SYNC(h, s, hipMemcpyAsync(out[c], d_out + B.clip_off[c], (size_t)B.clip_total[c] * 2, hipMemcpyDeviceToHost, s));
     HIPCHK_SYNC(h, s, hipStreamSynchronize(s));
@@ -131,11 +147,10 @@ int render_group(aegis_handle *h, const AdsrBatch &B, int16_t *const *out, const
 const char *const kSynthLabels[3] = {"synth_note_peak", "synth_mix", "synth_master"};
 const char *const kNotesLabels[3] = {"notefit_peak", "notefit_mix", "notefit_master"};
 
-// clips [c0, c1) of aegis_synth_adsr as one device pass; AEGIS_ERR_INVALID with h->err set for arguments the reference
-// would raise on.  bend: the wheel of aegis_synth_adsr_bend, or null.
-int synth_group(aegis_handle *h, int32_t sr, int32_t c0, int32_t c1, const aegis_synth_note *notes, const int64_t *note_off,
-                const double *length_seconds, const aegis_adsr_params *params, int16_t *const *out, const BendArgs *bend = nullptr) {
-    AdsrBatch B;
+// clips [c0, c1) of aegis_synth_adsr as the batch of one device pass; AEGIS_ERR_INVALID with h->err set for arguments the
+// reference would raise on.  bend: the wheel of aegis_synth_adsr_bend, or null.
+int fill_group(aegis_handle *h, int32_t sr, int32_t c0, int32_t c1, const aegis_synth_note *notes, const int64_t *note_off,
+               const double *length_seconds, const aegis_adsr_params *params, const BendArgs *bend, AdsrBatch &B) {
     for (int32_t c = c0; c < c1; ++c) {
         const aegis_adsr_params &p = params[c];
         std::map<int32_t, TrackWheel> tracks;
@@ -159,6 +174,15 @@ int synth_group(aegis_handle *h, int32_t sr, int32_t c0, int32_t c1, const aegis
         }
         if (!B.close_clip()) { h->err = "batch too large"; return AEGIS_ERR_INVALID; }
     }
+    return AEGIS_OK;
+}
+
+// clips [c0, c1) of aegis_synth_adsr as one device pass
+int synth_group(aegis_handle *h, int32_t sr, int32_t c0, int32_t c1, const aegis_synth_note *notes, const int64_t *note_off,
+                const double *length_seconds, const aegis_adsr_params *params, int16_t *const *out, const BendArgs *bend = nullptr) {
+    AdsrBatch B;
+    const int rc = fill_group(h, sr, c0, c1, notes, note_off, length_seconds, params, bend, B);
+    if (rc != AEGIS_OK) return rc;
     return render_group(h, B, out + c0, kSynthLabels);
 }
 
@@ -176,6 +200,44 @@ int notes_group(aegis_handle *h, int32_t sr, int32_t c0, int32_t c1, const aegis
 }
 
 }  // namespace
+
+// What aegis_synth_adsr_bend asks of its n_clips files before the device is looked at (out null: as check_clip).
+int aegis::check_bend_request(aegis_handle *h, int32_t sample_rate, int32_t n_clips, const aegis_synth_note *notes, const int64_t *note_off,
+                              const double *length_seconds, const aegis_adsr_params *params, const int32_t *note_track,
+                              const aegis_synth_wheel *wheel, const int64_t *wheel_off, const double *bend_range, int16_t *const *out,
+                              const int64_t *out_cap) {
+    for (int32_t c = 0; c < n_clips; ++c) {
+        const std::string clip = "clip " + std::to_string(c);
+        const int64_t q0 = note_off[c], q1 = note_off[c + 1], e0 = wheel_off[c], e1 = wheel_off[c + 1];
+        if (q0 < 0 || (q1 > q0 && !note_track)) { h->err = "note_off must be non-decreasing"; return AEGIS_ERR_INVALID; }
+        int rc = check_clip(h, sample_rate, c, notes, note_off, length_seconds, params, out, out_cap);
+        if (rc != AEGIS_OK) return rc;
+        if (!adsr_params_ok(params[c], INFINITY)) { h->err = "bad ADSR parameters or length (" + clip + ")"; return AEGIS_ERR_INVALID; }
+        if (e0 < 0 || e1 < e0 || (e1 > e0 && !wheel)) { h->err = "wheel_off must be non-decreasing"; return AEGIS_ERR_INVALID; }
+        if (!adsr_bend_range_ok(bend_range[c])) { h->err = "bend range of " + clip + " must be in (0, 24] semitones"; return AEGIS_ERR_INVALID; }
+        std::map<int32_t, double> last;                      // per track: the time of its latest wheel event
+        for (int64_t e = e0; e < e1; ++e) {
+            const aegis_synth_wheel &w = wheel[e];
+            const bool ok = w.track >= 0 && w.value >= -8192 && w.value <= 8191 && adsr_finite_nonneg(w.time) && w.time <= 86400.0;
+            const auto it = last.find(w.track);
+            if (!ok || (it != last.end() && w.time < it->second)) { h->err = "bad wheel event " + std::to_string(e - e0) + " of " + clip; return AEGIS_ERR_INVALID; }
+            last[w.track] = w.time;
+        }
+        for (int64_t q = q0; q < q1; ++q) {
+            if ((rc = check_note(h, sample_rate, c, q - q0, notes[q], params[c])) != AEGIS_OK) return rc;
+            if (note_track[q] < 0) { h->err = "bad note " + std::to_string(q - q0) + " of " + clip; return AEGIS_ERR_INVALID; }
+        }
+    }
+    return AEGIS_OK;
+}
+
+// files [c0, c1) of a validated aegis_synth_adsr_bend request as the batch of one device pass
+int aegis::fill_bend_batch(aegis_handle *h, int32_t sr, int32_t c0, int32_t c1, const aegis_synth_note *notes, const int64_t *note_off,
+                           const double *length_seconds, const aegis_adsr_params *params, const int32_t *note_track,
+                           const aegis_synth_wheel *wheel, const int64_t *wheel_off, const double *bend_range, AdsrBatch &B) {
+    const BendArgs bend{note_track, wheel, wheel_off, bend_range};
+    return fill_group(h, sr, c0, c1, notes, note_off, length_seconds, params, &bend, B);
+}
 
 extern "C" {
 
@@ -254,28 +316,9 @@ int aegis_synth_adsr_bend(aegis_handle *h, int32_t sample_rate, int32_t n_clips,
         (n_clips > 0 && (!note_off || !length_seconds || !params || !out || !out_cap || !wheel_off || !bend_range))) {
         h->err = "bad argument"; return AEGIS_ERR_INVALID;
     }
-    for (int32_t c = 0; c < n_clips; ++c) {
-        const std::string clip = "clip " + std::to_string(c);
-        const int64_t q0 = note_off[c], q1 = note_off[c + 1], e0 = wheel_off[c], e1 = wheel_off[c + 1];
-        if (q0 < 0 || (q1 > q0 && !note_track)) { h->err = "note_off must be non-decreasing"; return AEGIS_ERR_INVALID; }
-        int rc = check_clip(h, sample_rate, c, notes, note_off, length_seconds, params, out, out_cap);
-        if (rc != AEGIS_OK) return rc;
-        if (!adsr_params_ok(params[c], INFINITY)) { h->err = "bad ADSR parameters or length (" + clip + ")"; return AEGIS_ERR_INVALID; }
-        if (e0 < 0 || e1 < e0 || (e1 > e0 && !wheel)) { h->err = "wheel_off must be non-decreasing"; return AEGIS_ERR_INVALID; }
-        if (!adsr_bend_range_ok(bend_range[c])) { h->err = "bend range of " + clip + " must be in (0, 24] semitones"; return AEGIS_ERR_INVALID; }
-        std::map<int32_t, double> last;                      // per track: the time of its latest wheel event
-        for (int64_t e = e0; e < e1; ++e) {
-            const aegis_synth_wheel &w = wheel[e];
-            const bool ok = w.track >= 0 && w.value >= -8192 && w.value <= 8191 && adsr_finite_nonneg(w.time) && w.time <= 86400.0;
-            const auto it = last.find(w.track);
-            if (!ok || (it != last.end() && w.time < it->second)) { h->err = "bad wheel event " + std::to_string(e - e0) + " of " + clip; return AEGIS_ERR_INVALID; }
-            last[w.track] = w.time;
-        }
-        for (int64_t q = q0; q < q1; ++q) {
-            if ((rc = check_note(h, sample_rate, c, q - q0, notes[q], params[c])) != AEGIS_OK) return rc;
-            if (note_track[q] < 0) { h->err = "bad note " + std::to_string(q - q0) + " of " + clip; return AEGIS_ERR_INVALID; }
-        }
-    }
+    const int rc = check_bend_request(h, sample_rate, n_clips, notes, note_off, length_seconds, params, note_track, wheel, wheel_off,
+                                      bend_range, out, out_cap);
+    if (rc != AEGIS_OK) return rc;
     DEVICE_ONLY(h);
     if (n_clips == 0) return AEGIS_OK;
     HIPCHK(h, hipSetDevice(h->device));

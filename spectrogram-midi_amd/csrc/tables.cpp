@@ -49,6 +49,44 @@ static double mel_to_hz(double m) {
     return m >= min_log_mel ? min_log_hz * std::exp(logstep * (m - min_log_mel)) : f_sp * m;
 }
 
+// filters.py::mel(sr, n_fft, n_mels, fmin=0, fmax, htk=False, norm='slaney', dtype=float32): the float64 triangle rounded
+// to float32, then times the float64 Slaney norm and rounded again, as librosa's in-place `weights *= enorm` does.
+void build_mel_bank(int sr, int n_fft, int n_mels, double fmax, MelBank &bank) {
+    const int n_bins_fft = 1 + n_fft / 2;
+    const double d = 1.0 / sr, val = 1.0 / (n_fft * d);
+    std::vector<double> fftfreqs(n_bins_fft);
+    for (int k = 0; k < n_bins_fft; ++k) fftfreqs[k] = k * val;
+    std::vector<double> mels = np_linspace(hz_to_mel(0.0), hz_to_mel(fmax), n_mels + 2);
+    std::vector<double> mel_f(n_mels + 2);
+    for (int i = 0; i < n_mels + 2; ++i) mel_f[i] = mel_to_hz(mels[i]);
+    bank.n_mels = n_mels; bank.n_bins = n_bins_fft;
+    bank.dense.assign((size_t)n_mels * n_bins_fft, 0.0f);
+    for (int i = 0; i < n_mels; ++i) {
+        const double fd0 = mel_f[i + 1] - mel_f[i], fd1 = mel_f[i + 2] - mel_f[i + 1];
+        const double enorm = 2.0 / (mel_f[i + 2] - mel_f[i]);
+        for (int k = 0; k < n_bins_fft; ++k) {
+            const double lower = -(mel_f[i] - fftfreqs[k]) / fd0;
+            const double upper = (mel_f[i + 2] - fftfreqs[k]) / fd1;
+            const double w = std::fmax(0.0, std::fmin(lower, upper));
+            float w32 = (float)w;
+            w32 = (float)((double)w32 * enorm);
+            bank.dense[(size_t)i * n_bins_fft + k] = w32;
+        }
+    }
+    bank.start.assign(n_mels, 0); bank.len.assign(n_mels, 0); bank.off.assign(n_mels, 0);
+    bank.w.clear();
+    for (int i = 0; i < n_mels; ++i) {
+        int lo = -1, hi = -1;
+        for (int k = 0; k < n_bins_fft; ++k)
+            if (bank.dense[(size_t)i * n_bins_fft + k] != 0.0f) { if (lo < 0) lo = k; hi = k; }
+        bank.off[i] = (int32_t)bank.w.size();
+        if (lo >= 0) {
+            bank.start[i] = lo; bank.len[i] = hi - lo + 1;
+            for (int k = lo; k <= hi; ++k) bank.w.push_back(bank.dense[(size_t)i * n_bins_fft + k]);
+        }
+    }
+}
+
 // librosa core/pitch.py::pyin: `p_init = np.zeros(2 * n_pitch_bins); p_init[n_pitch_bins:] = 1 / n_pitch_bins`, then
 // sequence.viterbi takes log(p_init + tiny).  Mode 1 is the uniform start SURVEY.md P11 describes.
 bool Tables::set_pyin_init(int mode) {
@@ -97,40 +135,13 @@ std::string Tables::build(int sr_, int hop_, int n_fft_, int n_mels_, double fmi
         }
     }
 
-    // ---- mel filterbank: filters.py::mel(htk=False, norm='slaney', dtype=float32) -------------
+    // ---- mel filterbank: filters.py::mel(htk=False, norm='slaney', dtype=float32), fmax = sr / 2 --
     {
-        const int n_bins_fft = 1 + n_fft / 2;
-        const double d = 1.0 / sr, val = 1.0 / (n_fft * d);
-        std::vector<double> fftfreqs(n_bins_fft);
-        for (int k = 0; k < n_bins_fft; ++k) fftfreqs[k] = k * val;
-        std::vector<double> mels = np_linspace(hz_to_mel(0.0), hz_to_mel(sr / 2.0), n_mels + 2);
-        std::vector<double> mel_f(n_mels + 2);
-        for (int i = 0; i < n_mels + 2; ++i) mel_f[i] = mel_to_hz(mels[i]);
-        mel_dense.assign((size_t)n_mels * n_bins_fft, 0.0f);
-        for (int i = 0; i < n_mels; ++i) {
-            const double fd0 = mel_f[i + 1] - mel_f[i], fd1 = mel_f[i + 2] - mel_f[i + 1];
-            const double enorm = 2.0 / (mel_f[i + 2] - mel_f[i]);
-            for (int k = 0; k < n_bins_fft; ++k) {
-                const double lower = -(mel_f[i] - fftfreqs[k]) / fd0;
-                const double upper = (mel_f[i + 2] - fftfreqs[k]) / fd1;
-                const double w = std::fmax(0.0, std::fmin(lower, upper));
-                float w32 = (float)w;
-                w32 = (float)((double)w32 * enorm);
-                mel_dense[(size_t)i * n_bins_fft + k] = w32;
-            }
-        }
-        mel_start.assign(n_mels, 0); mel_len.assign(n_mels, 0); mel_off.assign(n_mels, 0);
-        mel_w.clear();
-        for (int i = 0; i < n_mels; ++i) {
-            int lo = -1, hi = -1;
-            for (int k = 0; k < n_bins_fft; ++k)
-                if (mel_dense[(size_t)i * n_bins_fft + k] != 0.0f) { if (lo < 0) lo = k; hi = k; }
-            mel_off[i] = (int32_t)mel_w.size();
-            if (lo >= 0) {
-                mel_start[i] = lo; mel_len[i] = hi - lo + 1;
-                for (int k = lo; k <= hi; ++k) mel_w.push_back(mel_dense[(size_t)i * n_bins_fft + k]);
-            }
-        }
+        MelBank bank;
+        build_mel_bank(sr, n_fft, n_mels, sr / 2.0, bank);
+        mel_dense = std::move(bank.dense);
+        mel_start = std::move(bank.start); mel_len = std::move(bank.len); mel_off = std::move(bank.off);
+        mel_w = std::move(bank.w);
     }
 
     // chunks of <= 16 bins: the frame kernel gives every chunk to one thread (balanced: the widest band has ~85 bins)

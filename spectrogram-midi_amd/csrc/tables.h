@@ -56,6 +56,17 @@ struct Tables {
     bool set_pyin_init(int mode);
 };
 
+// The Slaney mel filter bank of librosa's filters.py::mel from 0 Hz to fmax, float32 weights: dense [n_mels][n_bins] and
+// packed per band (first non-zero bin, run length, offset into w; a band no bin falls into has length 0).  The handle's
+// bank is this with fmax = sr / 2 (Tables::build); the technique verifier's with fmax = 8000 (aegis_verify.hip).
+struct MelBank {
+    int n_mels = 0, n_bins = 0;
+    std::vector<float> dense;
+    std::vector<int32_t> start, len, off;
+    std::vector<float> w;
+};
+void build_mel_bank(int sr, int n_fft, int n_mels, double fmax, MelBank &bank);
+
 // numpy's pairwise summation (umath loops: pairwise_sum_DOUBLE), used where the
 // reference's tables are defined through np.sum.
 double np_pairwise_sum(const double *a, int64_t n);

@@ -249,6 +249,12 @@ class AegisEngine:
             events = res[0]
         return events
 
+    def verify_techniques(self, events, raw_data, **kw):
+        """technique_verifier.verify_technique_by_audio_matching on the engine's own handle and rate: the bends (and, if
+        asked for, vibratos) of `events` kept or stripped by A/B renders scored against raw_data['y'], one device call."""
+        from . import technique_verifier
+        return technique_verifier.verify_technique_by_audio_matching(events, raw_data, self, None, self.sr, self.hop_length, **kw)
+
     # ------------------------------------------------------------------ Turbo Mode
     def _turbo_spans(self, n_samples):
         """Equal frame spans per core, last one takes the remainder (aegis_engine.py:192-204)."""
