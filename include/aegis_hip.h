@@ -545,6 +545,40 @@ int aegis_verify_techniques(aegis_handle *h, int32_t sample_rate, int32_t n_clip
                             const int64_t *wheel_off, const double *bend_range,
                             double *sim /* [2 * n_events] */, uint8_t *keep /* [n_events] */);
 
+/* --- Harmonic-sum salience and multi-pitch candidates behind the constant-Q magnitudes ------------------------------
+ * The reference has no harmonic stacking; the semantics are this project's, stated once in csrc/salience.h
+ * and DESIGN.md 3.16 and pinned to tools/salience_restated.py: the arithmetic of librosa.salience over interp_harmonics on
+ * a geometric bin grid, in IEEE float32 with a fixed order, so the same bits come out of the host and of the device.
+ *   harmonic h    reads bin b + k_h, linearly interpolated towards b + k_h + 1 with weight a_h (k_h, a_h from
+ *                 bins_per_octave * log2(harmonics[h]); 0 outside the grid); sal = sum_h weights[h] * v_h / sum_h weights[h]
+ *   peak          a bin strictly above both neighbours (scipy.signal.argrelmax; the edges never peak)
+ *   sal_out       NULL, or per clip [n_bins, F_clip]: sal where !filter_peaks or the bin peaks, else 0.0f (the one
+ *                 deviation from librosa.salience, whose fill value is NaN)
+ *   candidates    per clip [F_clip, top_k], frame-major, clip after clip: the top_k most salient bins among the peaks in
+ *                 [bin_lo, bin_hi] whose magnitude is at least peak_floor times the frame maximum and whose salience is
+ *                 positive, salience descending, then bin ascending; cand_shift the parabolic offset of the magnitude
+ *                 peak in bins (-0.5 .. 0.5; f = fmin * 2^((bin + shift) / bins_per_octave)).  Unused slots: bin -1,
+ *                 salience 0, shift 0.  cand_* may be NULL when top_k == 0.
+ * aegis_salience takes magnitudes from host memory (per clip [n_bins, n_frames[c]] C-order, clip after clip).
+ * aegis_cqt_salience takes PCM as aegis_cqt does, runs the same CQT (the cached filter bank; 252 bins as three launches)
+ * into the handle's device buffer and the salience kernel behind it; mag_out (NULL, or as aegis_cqt's) is the only way the
+ * magnitudes cross to the host.  A frame's results depend on that frame alone: the same bits alone, batched, regrouped.
+ * AEGIS_ERR_INVALID with a message: n_bins > 256, top_k outside 0..8, n_harm outside 1..8, a harmonic <= 0, a negative
+ * weight or all weights zero, bin_lo / bin_hi outside 0 <= bin_lo <= bin_hi <= n_bins - 1, a negative peak_floor.
+ * Kernel time: "salience" of aegis_last_kernel_ms (and "cqt").  Blocking; host pointers. */
+typedef struct aegis_salience_params {
+    int32_t n_harm;                 /* 1..8 */
+    double harmonics[8], weights[8];
+    int32_t filter_peaks;
+    float peak_floor;
+    int32_t bin_lo, bin_hi, top_k;
+} aegis_salience_params;
+int aegis_salience(aegis_handle *h, const float *mag, const int64_t *n_frames, int32_t n_clips, int32_t n_bins, int32_t bins_per_octave,
+                   const aegis_salience_params *p, float *sal_out /* NULL ok */, int32_t *cand_bin, float *cand_sal, float *cand_shift);
+int aegis_cqt_salience(aegis_handle *h, const float *const *pcm, const int64_t *n_samples, int32_t n_clips, int32_t n_bins,
+                       int32_t bins_per_octave, double fmin, double filter_scale, const aegis_salience_params *p,
+                       float *mag_out /* NULL ok */, float *sal_out /* NULL ok */, int32_t *cand_bin, float *cand_sal, float *cand_shift);
+
 /* --- Effect chain: distortion, reverb, delay, chorus (aegis_engine_core/effect_learning_loop.py:56-275) ----------
  * The reference's pure-NumPy effects, each ending in a whole-clip normalisation, which its learning loop
  * (effect_learning_loop.py:489-725) puts between the synthesiser and the engine.  Float64 throughout.

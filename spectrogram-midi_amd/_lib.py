@@ -70,6 +70,11 @@ class VerifyEvent(C.Structure):
     _fields_ = [("clip", C.c_int32), ("reserved", C.c_int32), ("lo", C.c_int64), ("hi", C.c_int64)]
 
 
+class SalienceParams(C.Structure):
+    _fields_ = [("n_harm", C.c_int32), ("harmonics", C.c_double * 8), ("weights", C.c_double * 8), ("filter_peaks", C.c_int32),
+                ("peak_floor", C.c_float), ("bin_lo", C.c_int32), ("bin_hi", C.c_int32), ("top_k", C.c_int32)]
+
+
 class Effect(C.Structure):
     _fields_ = [("kind", C.c_int32), ("n_ir", C.c_int32), ("p0", C.c_double), ("p1", C.c_double), ("ir", C.c_void_p)]
 
@@ -93,7 +98,8 @@ EXPORTS = ("aegis_abi_version", "aegis_create", "aegis_destroy", "aegis_last_err
            "aegis_debug_set_observations", "aegis_debug_set_difference", "aegis_estimate_tuning",
            "aegis_reverb_ir", "aegis_effects",
            "aegis_note_fit", "aegis_compare_audio", "aegis_synth_one_note", "aegis_synth_notes_samples_for", "aegis_synth_adsr_notes",
-           "aegis_synth_parse_smf_wheel", "aegis_synth_adsr_bend", "aegis_verify_techniques")
+           "aegis_synth_parse_smf_wheel", "aegis_synth_adsr_bend", "aegis_verify_techniques",
+           "aegis_salience", "aegis_cqt_salience")
 
 _lib = None
 
@@ -212,6 +218,14 @@ def load():
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(AdsrParams), C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_void_p]
     lib.aegis_verify_techniques.restype = C.c_int
+    if hasattr(lib, "aegis_salience"):      # (an older library, loaded through AEGIS_HIP_LIB for a comparison, lacks the two entries)
+        lib.aegis_salience.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(SalienceParams),
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.aegis_salience.restype = C.c_int
+        lib.aegis_cqt_salience.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.c_int32,
+                                           C.c_double, C.c_double, C.POINTER(SalienceParams), C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p]
+        lib.aegis_cqt_salience.restype = C.c_int
     lib.aegis_set_profiling.argtypes = [C.c_void_p, C.c_int32]
     lib.aegis_set_profiling.restype = C.c_int
     lib.aegis_last_kernel_ms.argtypes = [C.c_void_p, C.c_char_p]
@@ -671,6 +685,82 @@ class Handle:
         self._check(self.lib.aegis_cqt_device(self._h, C.c_void_p(int(d_pcm_ptr)), off.ctypes.data_as(C.POINTER(C.c_int64)),
                                               len(off) - 1, n_bins, bins_per_octave, float(fmin), float(filter_scale),
                                               C.c_void_p(int(d_out_ptr)), C.c_void_p(stream or 0), 1 if sync else 0))
+
+    @staticmethod
+    def salience_params(harmonics=(1, 2, 3, 4, 5), weights=None, filter_peaks=True, peak_floor=0.02, bin_lo=0, bin_hi=0, top_k=6):
+        """aegis_salience_params; weights default to 1 / h.  The library validates (AegisError from the calls below)."""
+        harmonics = [float(h) for h in harmonics]
+        weights = [1.0 / h for h in harmonics] if weights is None else [float(w) for w in weights]
+        if len(harmonics) > 8 or len(weights) != len(harmonics):
+            raise ValueError("at most 8 harmonics, one weight each")
+        p = SalienceParams()
+        p.n_harm = len(harmonics)
+        for i, (h, w) in enumerate(zip(harmonics, weights)):
+            p.harmonics[i], p.weights[i] = h, w
+        p.filter_peaks, p.peak_floor, p.bin_lo, p.bin_hi, p.top_k = int(bool(filter_peaks)), float(peak_floor), int(bin_lo), int(bin_hi), int(top_k)
+        return p
+
+    @staticmethod
+    def _salience_split(frames, n_bins, top_k, img, cb, cs, csh):
+        """The batch buffers of a salience call -> per clip (image or None, bins, saliences, shifts)."""
+        res, fo = [], 0
+        for Fc in frames:
+            res.append((img[fo * n_bins:(fo + Fc) * n_bins].reshape(n_bins, Fc).copy() if img is not None else None,
+                        cb[fo * top_k:(fo + Fc) * top_k].reshape(Fc, top_k).copy(),
+                        cs[fo * top_k:(fo + Fc) * top_k].reshape(Fc, top_k).copy(),
+                        csh[fo * top_k:(fo + Fc) * top_k].reshape(Fc, top_k).copy()))
+            fo += Fc
+        return res
+
+    def salience(self, mags, params, bins_per_octave=12, want_image=True):
+        """aegis_salience: harmonic-sum salience and pitch candidates of caller magnitudes (a list of float32 [n_bins, F_c]
+        arrays, one n_bins) in ONE device call -> per clip (image float32 [n_bins, F_c] or None, bins int32 [F_c, top_k],
+        saliences float32 [F_c, top_k], shifts float32 [F_c, top_k]).  params: salience_params(...).  AegisError with code
+        ERR_INVALID for what the library rejects."""
+        mags = [np.ascontiguousarray(m, dtype=np.float32) for m in mags]
+        if not mags:
+            return []
+        n_bins = mags[0].shape[0]
+        if any(m.ndim != 2 or m.shape[0] != n_bins for m in mags):
+            raise ValueError("magnitudes must be [n_bins, F] arrays of one n_bins")
+        frames = [m.shape[1] for m in mags]
+        F, K = sum(frames), int(params.top_k)
+        flat = np.concatenate([m.ravel() for m in mags]) if F else np.zeros(0, np.float32)
+        nf = np.asarray(frames, np.int64)
+        img = np.zeros(F * n_bins, np.float32) if want_image else None
+        cb, cs, csh = np.full(F * max(K, 0), -1, np.int32), np.zeros(F * max(K, 0), np.float32), np.zeros(F * max(K, 0), np.float32)
+        rc = self.lib.aegis_salience(self._h, flat.ctypes.data, nf.ctypes.data, len(mags), n_bins, int(bins_per_octave), C.byref(params),
+                                     img.ctypes.data if want_image else None, cb.ctypes.data, cs.ctypes.data, csh.ctypes.data)
+        self._check(rc)
+        return self._salience_split(frames, n_bins, K, img, cb, cs, csh)
+
+    def cqt_salience(self, clips, params, n_bins=252, bins_per_octave=36, fmin=32.70319566257483, filter_scale=1.0, want_mag=False,
+                     want_image=False):
+        """aegis_cqt_salience: the CQT of aegis_cqt and the salience kernel behind it on the device -> (per clip tuples as
+        salience() returns them, per clip magnitudes float32 [n_bins, F_c] or None).  The magnitudes leave the device only
+        with want_mag."""
+        clips = [np.ascontiguousarray(c, dtype=np.float32) for c in clips]
+        n = len(clips)
+        if n == 0:
+            return [], ([] if want_mag else None)
+        ptrs = (C.c_void_p * n)(*[c.ctypes.data for c in clips])
+        lens = (C.c_int64 * n)(*[len(c) for c in clips])
+        frames = [self.frames_for(len(c)) for c in clips]
+        F, K = sum(frames), int(params.top_k)
+        mag = np.zeros(F * n_bins, np.float32) if want_mag else None
+        img = np.zeros(F * n_bins, np.float32) if want_image else None
+        cb, cs, csh = np.full(F * max(K, 0), -1, np.int32), np.zeros(F * max(K, 0), np.float32), np.zeros(F * max(K, 0), np.float32)
+        rc = self.lib.aegis_cqt_salience(self._h, ptrs, lens, n, int(n_bins), int(bins_per_octave), float(fmin), float(filter_scale),
+                                         C.byref(params), mag.ctypes.data if want_mag else None, img.ctypes.data if want_image else None,
+                                         cb.ctypes.data, cs.ctypes.data, csh.ctypes.data)
+        self._check(rc)
+        mags = None
+        if want_mag:
+            mags, o = [], 0
+            for Fc in frames:
+                mags.append(mag[o:o + Fc * n_bins].reshape(n_bins, Fc).copy())
+                o += Fc * n_bins
+        return self._salience_split(frames, n_bins, K, img, cb, cs, csh), mags
 
     def synth_parse_smf(self, midi_bytes, want_wheel=False):
         """aegis_synth_parse_smf: (notes in the reference's mix order as a SYNTH_NOTE_DTYPE array, mido's length in

@@ -134,7 +134,9 @@ static int cqt_launch_locked(aegis_handle *h, const float *d_pcm, const int64_t 
 // What the two host-buffer entries share (handle locked, device set): the bank, the clips validated and packed, the staging
 // sized, the samples uploaded (behind the chroma fold's bin classes, when there are any), the CQT launched into q_out.
 // F: frames of all clips.
-static int cqt_host_locked(aegis_handle *h, const float *const *pcm, const int64_t *n_samples, int32_t n_clips, int32_t &n_bins,
+// (declared in aegis_internal.h with C++ linkage: aegis_salience.hip runs it in front of its kernel)
+}  // extern "C"
+int aegis::cqt_host_locked(aegis_handle *h, const float *const *pcm, const int64_t *n_samples, int32_t n_clips, int32_t &n_bins,
                            int32_t bins_per_octave, double fmin, double filter_scale, int32_t n_chroma, const int32_t *bin_class, int64_t *F_out) {
     hipStream_t s = h->stream;
     int rc;
@@ -162,6 +164,7 @@ static int cqt_host_locked(aegis_handle *h, const float *const *pcm, const int64
     *F_out = F;
     return cqt_launch_locked(h, static_cast<const float *>(h->q_pcm.p), soff.data(), n_clips, static_cast<float *>(h->q_out.p), s, &Fd);
 }
+extern "C" {
 
 int aegis_cqt(aegis_handle *h, const float *const *pcm, const int64_t *n_samples, int32_t n_clips,
               int32_t n_bins, int32_t bins_per_octave, double fmin, double filter_scale, float *mag_out) {

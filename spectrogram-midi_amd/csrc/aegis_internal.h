@@ -12,6 +12,8 @@
 //                     notefit.hip and adsr.hip)
 //   aegis_verify.hip  aegis_verify_techniques (the technique verifier; kernels in verify.hip, its renders through
 //                     aegis_synth.hip's render_into)
+//   aegis_salience.hip aegis_salience, aegis_cqt_salience (harmonic-sum salience and pitch candidates; kernel in
+//                     salience.hip, the CQT in front of it through aegis_cqt.hip's cqt_host_locked)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -132,6 +134,7 @@ struct aegis_handle {
     DevBuf vf_audio, vf_events, vf_boff, vf_mel, vf_max, vf_sim, vf_keep;
     struct VerifyBank { aegis::MelBank host; int32_t n_used = 0; bool uploaded = false; DevBuf start, len, off, w; };
     std::map<int32_t, VerifyBank> vf_banks;
+    DevBuf sl_mag, sl_foff, sl_img, sl_bin, sl_sal, sl_shift;   // aegis_salience / aegis_cqt_salience: caller magnitudes, frame offsets, image, candidates
     bool notefit_store = false;               // AEGIS_NOTEFIT_STORE=1 at create: every candidate rendered once into nf_sig and read by the frames instead of recomputed
     int32_t lag_stride = 0, yin_stride = 0, obs_stride = 0;
     aegis::CallPlan plan;                     // the last call's plan: its host arrays stay alive until the stream drained
@@ -265,6 +268,13 @@ int fill_bend_batch(aegis_handle *h, int32_t sr, int32_t c0, int32_t c1, const a
                     const double *length_seconds, const aegis_adsr_params *params, const int32_t *note_track,
                     const aegis_synth_wheel *wheel, const int64_t *wheel_off, const double *bend_range, AdsrBatch &B);
 int render_into(aegis_handle *h, const AdsrBatch &B, const char *const (&labels)[3]);
+
+// ---- the CQT as a stage of another entry (aegis_cqt.hip) ----
+// Handle locked, device set: the bank found or built, the clips validated, packed and uploaded, the CQT launched on the
+// handle's stream into q_out (per clip [n_bins, F_c]) with the frame offsets in q_foff; n_bins comes back with its default
+// filled in, *F_out is the frame total.  bin_class: the chroma fold's classes (uploaded to q_cls), or nullptr.
+int cqt_host_locked(aegis_handle *h, const float *const *pcm, const int64_t *n_samples, int32_t n_clips, int32_t &n_bins,
+                    int32_t bins_per_octave, double fmin, double filter_scale, int32_t n_chroma, const int32_t *bin_class, int64_t *F_out);
 
 // ---- kernel parameters every entry fills the same way (aegis_api.hip) ----
 struct RakeBounds { int min_frames, max_frames; };

@@ -255,6 +255,59 @@ class AegisEngine:
         from . import technique_verifier
         return technique_verifier.verify_technique_by_audio_matching(events, raw_data, self, None, self.sr, self.hop_length, **kw)
 
+    # ------------------------------------------------------------------ polyphonic entry (not a reference method)
+    _POLY_DEVICE_KW = ("n_bins", "bins_per_octave", "fmin", "filter_scale", "harmonics", "weights", "filter_peaks", "peak_floor",
+                       "bin_lo", "bin_hi", "top_k")
+
+    def audio_to_midi_polyphonic(self, input_wav_or_array, **kw):
+        """A WAV path or decoded samples -> {"cands": multi-pitch candidates (polyphonic.multipitch_candidates), "rms", "y"},
+        or None for empty audio.  kw: the device defaults of polyphonic.py by name (harmonics, top_k, ...), start_time /
+        end_time for a path."""
+        if isinstance(input_wav_or_array, (str, bytes)) or hasattr(input_wav_or_array, "__fspath__"):
+            end, start = kw.get("end_time", None), kw.get("start_time", 0)
+            srcs = audio_io.load_pcm_files([input_wav_or_array], self.sr, start, (end - start) if end else None)
+            y = self.handle.analyze_pcm(srcs, stages=0, check_finite=True)[0]["y"]
+        else:
+            y = input_wav_or_array
+        return self.audio_to_midi_polyphonic_batch([y], want_events=False, **kw)[0][0]
+
+    def audio_to_midi_polyphonic_batch(self, clips, want_midi=True, want_events=True, **kw):
+        """A folder of decoded clips -> (raw dicts, event lists, SMF bytes per clip): ONE CQT + salience call and ONE rms
+        call on the device for the whole batch, the piano-roll per clip on the host.  Empty clips give (None, [], None)."""
+        from . import polyphonic
+        clips = [np.ascontiguousarray(c, dtype=np.float32) for c in clips]
+        live = [i for i, c in enumerate(clips) if len(c) > 0]
+        raws, events, blobs = [None] * len(clips), [[] for _ in clips], [None] * len(clips)
+        if not live:
+            return raws, events, blobs
+        h = self.handle
+        batch = [clips[i] for i in live]
+        cands = polyphonic.multipitch_candidates(h, batch, **{k: kw[k] for k in self._POLY_DEVICE_KW if k in kw})
+        rms = h.analyze_batch(batch, stages=_lib.STAGE_RMS, check_finite=True)
+        for i, c, r in zip(live, cands, rms):
+            raws[i] = {"cands": c, "rms": r["rms"], "y": clips[i]}
+            if want_events:
+                events[i] = polyphonic.get_midi_events_polyphonic(c, r["rms"], self.sr, self.hop_length, **kw)
+                if want_midi:
+                    blobs[i] = smf.render(events[i], self.sr, self.hop_length, midi_program=kw.get("midi_program", 27),
+                                          vibrato_rate=kw.get("vibrato_rate", 5.0), vibrato_depth=kw.get("vibrato_depth", 0.3))
+        return raws, events, blobs
+
+    def extract_events_polyphonic(self, raw, output_mid, **kw):
+        """raw of audio_to_midi_polyphonic -> note events (polyphonic.get_midi_events_polyphonic), optional SMF to a path
+        or a file-like object through the engine's writer."""
+        from . import polyphonic
+        events = polyphonic.get_midi_events_polyphonic(raw["cands"], raw["rms"], self.sr, self.hop_length, **kw)
+        if output_mid:
+            blob = smf.render(events, self.sr, self.hop_length, midi_program=kw.get("midi_program", 27),
+                              vibrato_rate=kw.get("vibrato_rate", 5.0), vibrato_depth=kw.get("vibrato_depth", 0.3))
+            if hasattr(output_mid, "write"):
+                output_mid.write(blob)
+            else:
+                with open(output_mid, "wb") as f:
+                    f.write(blob)
+        return events
+
     # ------------------------------------------------------------------ Turbo Mode
     def _turbo_spans(self, n_samples):
         """Equal frame spans per core, last one takes the remainder (aegis_engine.py:192-204)."""
