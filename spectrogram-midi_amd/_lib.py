@@ -1,23 +1,17 @@
-"""ctypes binding of libaegis_hip.so (include/aegis_hip.h).  Fails loudly when the
-extension has not been built: `python -c "import __graft_entry__ as g; g.build()"`."""
+"""ctypes binding of libaegis_hip.so (include/aegis_hip.h): Handle and Stream, a short method per entry.  The ABI itself --
+constants, structures, the prototype table and load() -- is _abi.py and is re-exported here, so this module stays the
+import point; the marshalling the methods share is _marshal.py.  Fails loudly when the extension has not been built:
+`python -c "import __graft_entry__ as g; g.build()"`."""
 import atexit
 import ctypes as C
-import os
 import sys
 import weakref
 
 import numpy as np
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("AEGIS_HIP_LIB", os.path.join(_HERE, "libaegis_hip.so"))
+from . import _marshal
+from ._abi import *      # noqa: F401,F403 -- the ABI's names are this module's too
 
-STAGE_MEL, STAGE_RAKE, STAGE_PYIN, STAGE_RMS, STAGE_ALL = 0x1, 0x2, 0x4, 0x8, 0xF
-OPT_CHECK_FINITE, OPT_F0_ZERO = 0x10, 0x20
-(TREND_SMA, TREND_EMA, TREND_BOLLINGER, TREND_ARTICULATION, TREND_MACD, TREND_SLIDES, TREND_RSI, TREND_SAVGOL,
- TREND_KALMAN, TREND_HOLT, TREND_CONSENSUS, TREND_PITCH_ANALYSIS) = range(1, 13)
-OK, ERR_INVALID, ERR_NOMEM, ERR_DEVICE, ERR_UNSUPPORTED = 0, -22, -12, -5, -95
-PYIN_INIT_UNVOICED, PYIN_INIT_UNIFORM = 0, 1      # aegis_config.pyin_init
-ABI_VERSION = 2                                   # include/aegis_hip.h AEGIS_ABI_VERSION: the layout Config / Outputs below assume
 _PYIN_INIT = {"unvoiced": 0, "uniform": 1, 0: 0, 1: 1}
 
 
@@ -25,215 +19,6 @@ class AegisError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libaegis_hip error {code}: {msg}")
         self.code = code
-
-
-class Config(C.Structure):
-    _fields_ = [("sample_rate", C.c_int32), ("hop_length", C.c_int32), ("n_fft", C.c_int32),
-                ("n_mels", C.c_int32), ("fmin", C.c_double), ("fmax", C.c_double),
-                ("device", C.c_int32), ("pyin_init", C.c_int32), ("max_frames_per_pass", C.c_int64)]
-
-
-class PcmClip(C.Structure):
-    _fields_ = [("data", C.c_void_p), ("n_frames", C.c_int64), ("format", C.c_int32), ("channels", C.c_int32),
-                ("sample_rate", C.c_int32), ("n_taps", C.c_int32), ("taps", C.c_void_p)]
-
-
-class StreamFrames(C.Structure):
-    _fields_ = [("rms", C.c_void_p), ("voiced_prob", C.c_void_p), ("live_state", C.c_void_p)]
-
-
-class StreamCommit(C.Structure):
-    _fields_ = [("pitch_bin", C.c_void_p), ("cap", C.c_int64), ("first", C.c_int64), ("count", C.c_int64),
-                ("frontier", C.c_int64), ("walked", C.c_int64), ("walked_wide", C.c_int64)]
-
-
-class Outputs(C.Structure):
-    _fields_ = [("f0", C.c_void_p), ("voiced_flag", C.c_void_p), ("voiced_prob", C.c_void_p),
-                ("rms", C.c_void_p), ("rake_mask", C.c_void_p), ("S_dB", C.c_void_p), ("pitch_bin", C.c_void_p), ("sdb_col_means", C.c_void_p)]
-
-
-class SynthNote(C.Structure):
-    _fields_ = [("start", C.c_double), ("duration", C.c_double), ("note", C.c_int32), ("velocity", C.c_int32)]
-
-
-class AdsrParams(C.Structure):
-    _fields_ = [("attack_ms", C.c_double), ("decay_ms", C.c_double), ("sustain_level", C.c_double), ("release_ms", C.c_double),
-                ("waveform", C.c_int32), ("reserved", C.c_int32)]
-
-
-class FitNote(C.Structure):
-    _fields_ = [("clip", C.c_int32), ("note", C.c_int32), ("lo", C.c_int64), ("hi", C.c_int64), ("velocity", C.c_int32),
-                ("reserved", C.c_int32), ("duration", C.c_double)]
-
-
-class VerifyEvent(C.Structure):
-    _fields_ = [("clip", C.c_int32), ("reserved", C.c_int32), ("lo", C.c_int64), ("hi", C.c_int64)]
-
-
-class SalienceParams(C.Structure):
-    _fields_ = [("n_harm", C.c_int32), ("harmonics", C.c_double * 8), ("weights", C.c_double * 8), ("filter_peaks", C.c_int32),
-                ("peak_floor", C.c_float), ("bin_lo", C.c_int32), ("bin_hi", C.c_int32), ("top_k", C.c_int32)]
-
-
-class Effect(C.Structure):
-    _fields_ = [("kind", C.c_int32), ("n_ir", C.c_int32), ("p0", C.c_double), ("p1", C.c_double), ("ir", C.c_void_p)]
-
-
-PCM_S16, PCM_F64 = 2, 6                                                   # AEGIS_PCM_*: what aegis_effects reads
-FX_DISTORTION, FX_REVERB, FX_DELAY, FX_CHORUS = 1, 2, 3, 4                # AEGIS_FX_*
-# effect name -> (kind, (parameter, the reference's default) for p0 and p1): effect_learning_loop.py:56, :84, :137, :185
-EFFECT_KINDS = {"distortion": (FX_DISTORTION, (("drive", 0.5),)), "reverb": (FX_REVERB, (("room_size", 0.5),)),
-                "delay": (FX_DELAY, (("delay_ms", 300), ("feedback", 0.3))), "chorus": (FX_CHORUS, (("depth", 0.003), ("rate", 1.5)))}
-WAVEFORMS = {"sine": 0, "sawtooth": 1, "square": 2, "triangle": 3}          # AEGIS_WAVE_*
-SYNTH_NOTE_DTYPE = np.dtype([("start", "<f8"), ("duration", "<f8"), ("note", "<i4"), ("velocity", "<i4")])
-SYNTH_WHEEL_DTYPE = np.dtype([("time", "<f8"), ("track", "<i4"), ("value", "<i4")])      # aegis_synth_wheel
-
-EXPORTS = ("aegis_abi_version", "aegis_create", "aegis_destroy", "aegis_last_error", "aegis_frames_for",
-           "aegis_analyze_batch", "aegis_analyze_batch_device", "aegis_get_table", "aegis_get_param",
-           "aegis_debug_fetch", "aegis_set_profiling", "aegis_last_kernel_ms", "aegis_rake_patterns", "aegis_set_table", "aegis_last_kernel_launches", "aegis_trend", "aegis_ghost_rsi",
-           "aegis_stream_open", "aegis_stream_push", "aegis_stream_close", "aegis_stream_free", "aegis_cqt", "aegis_cqt_device", "aegis_chroma_cqt",
-           "aegis_extract_events", "aegis_render_smf", "aegis_events_last_error", "aegis_debug_plan",
-           "aegis_analyze_pcm", "aegis_pcm_samples_for", "aegis_resample_taps", "aegis_stream_push_commit",
-           "aegis_synth_parse_smf", "aegis_synth_samples_for", "aegis_synth_adsr", "aegis_debug_rake_columns",
-           "aegis_debug_set_observations", "aegis_debug_set_difference", "aegis_estimate_tuning",
-           "aegis_reverb_ir", "aegis_effects",
-           "aegis_note_fit", "aegis_compare_audio", "aegis_synth_one_note", "aegis_synth_notes_samples_for", "aegis_synth_adsr_notes",
-           "aegis_synth_parse_smf_wheel", "aegis_synth_adsr_bend", "aegis_verify_techniques",
-           "aegis_salience", "aegis_cqt_salience")
-
-_lib = None
-
-
-def load():
-    """Returns the loaded library; raises ImportError with build instructions if absent."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise ImportError(
-            f"{LIB_PATH} is missing: the HIP extension must be built (make -C {_HERE}/csrc, or "
-            "__graft_entry__.build()).  There is no CPU fallback for the analyze path.")
-    lib = C.CDLL(LIB_PATH)
-    lib.aegis_abi_version.restype = C.c_int
-    got = int(lib.aegis_abi_version())
-    if got != ABI_VERSION:
-        # aegis_outputs / aegis_config carry no size field: a library of another ABI would read this module's structs at
-        # the wrong offsets and write device or host memory through stale pointers (AEGIS_HIP_LIB is routinely pointed at
-        # other builds)
-        raise ImportError(f"{LIB_PATH} has ABI version {got}, this binding was written for {ABI_VERSION} "
-                          "(include/aegis_hip.h AEGIS_ABI_VERSION): rebuild the library or update the binding")
-    lib.aegis_create.argtypes = [C.POINTER(Config), C.POINTER(C.c_void_p)]
-    lib.aegis_create.restype = C.c_int
-    lib.aegis_destroy.argtypes = [C.c_void_p]
-    lib.aegis_destroy.restype = None
-    lib.aegis_last_error.argtypes = [C.c_void_p]
-    lib.aegis_last_error.restype = C.c_char_p
-    lib.aegis_frames_for.argtypes = [C.c_void_p, C.c_int64]
-    lib.aegis_frames_for.restype = C.c_int64
-    lib.aegis_analyze_batch.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int32,
-                                        C.c_double, C.c_uint32, C.POINTER(Outputs)]
-    lib.aegis_analyze_batch.restype = C.c_int
-    lib.aegis_analyze_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int32,
-                                               C.c_double, C.c_uint32, C.POINTER(Outputs), C.c_void_p, C.c_int32]
-    lib.aegis_analyze_batch_device.restype = C.c_int
-    lib.aegis_analyze_pcm.argtypes = [C.c_void_p, C.POINTER(PcmClip), C.c_int32, C.c_double, C.c_uint32, C.POINTER(Outputs),
-                                      C.c_void_p]
-    lib.aegis_analyze_pcm.restype = C.c_int
-    lib.aegis_pcm_samples_for.argtypes = [C.c_void_p, C.POINTER(PcmClip)]
-    lib.aegis_pcm_samples_for.restype = C.c_int64
-    lib.aegis_resample_taps.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_int64]
-    lib.aegis_resample_taps.restype = C.c_int64
-    lib.aegis_rake_patterns.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.c_void_p]
-    lib.aegis_rake_patterns.restype = C.c_int
-    lib.aegis_trend.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
-                                C.POINTER(C.c_void_p), C.c_int32]
-    lib.aegis_trend.restype = C.c_int
-    lib.aegis_ghost_rsi.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
-    lib.aegis_ghost_rsi.restype = C.c_int
-    lib.aegis_stream_open.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]
-    lib.aegis_stream_open.restype = C.c_int
-    lib.aegis_stream_push.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(StreamFrames), C.POINTER(C.c_int64)]
-    lib.aegis_stream_push.restype = C.c_int
-    lib.aegis_stream_push_commit.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(StreamFrames), C.POINTER(C.c_int64),
-                                             C.POINTER(StreamCommit)]
-    lib.aegis_stream_push_commit.restype = C.c_int
-    lib.aegis_stream_close.argtypes = [C.c_void_p, C.c_double, C.POINTER(Outputs), C.POINTER(C.c_int64)]
-    lib.aegis_stream_close.restype = C.c_int
-    lib.aegis_stream_free.argtypes = [C.c_void_p]
-    lib.aegis_stream_free.restype = None
-    lib.aegis_cqt.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.c_int32,
-                              C.c_double, C.c_double, C.c_void_p]
-    lib.aegis_cqt.restype = C.c_int
-    lib.aegis_cqt_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.c_int32, C.c_double,
-                                     C.c_double, C.c_void_p, C.c_void_p, C.c_int32]
-    lib.aegis_cqt_device.restype = C.c_int
-    lib.aegis_chroma_cqt.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.c_int32,
-                                     C.c_double, C.c_double, C.c_int32, C.c_void_p, C.c_void_p]
-    lib.aegis_chroma_cqt.restype = C.c_int
-    lib.aegis_estimate_tuning.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int32, C.c_int32,
-                                          C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.aegis_estimate_tuning.restype = C.c_int
-    lib.aegis_set_table.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64]
-    lib.aegis_set_table.restype = C.c_int
-    lib.aegis_get_table.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64]
-    lib.aegis_get_table.restype = C.c_int64
-    lib.aegis_get_param.argtypes = [C.c_void_p, C.c_char_p]
-    lib.aegis_get_param.restype = C.c_int64
-    lib.aegis_debug_fetch.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64]
-    lib.aegis_debug_fetch.restype = C.c_int64
-    lib.aegis_debug_plan.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64]
-    lib.aegis_debug_plan.restype = C.c_int64
-    lib.aegis_synth_parse_smf.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_double)]
-    lib.aegis_synth_parse_smf.restype = C.c_int64
-    lib.aegis_synth_samples_for.argtypes = [C.c_int32, C.c_double, C.POINTER(AdsrParams)]
-    lib.aegis_synth_samples_for.restype = C.c_int64
-    lib.aegis_synth_adsr.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(AdsrParams),
-                                     C.POINTER(C.c_void_p), C.c_void_p]
-    lib.aegis_synth_adsr.restype = C.c_int
-    lib.aegis_synth_parse_smf_wheel.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
-                                                C.POINTER(C.c_int64), C.POINTER(C.c_double)]
-    lib.aegis_synth_parse_smf_wheel.restype = C.c_int64
-    lib.aegis_synth_adsr_bend.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(AdsrParams),
-                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p]
-    lib.aegis_synth_adsr_bend.restype = C.c_int
-    lib.aegis_reverb_ir.argtypes = [C.c_double, C.c_int32, C.c_void_p, C.c_int64]
-    lib.aegis_reverb_ir.restype = C.c_int64
-    lib.aegis_effects.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.c_int32, C.c_void_p, C.POINTER(Effect),
-                                  C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
-    lib.aegis_effects.restype = C.c_int
-    lib.aegis_note_fit.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.c_void_p, C.c_int32, C.POINTER(FitNote),
-                                   C.POINTER(AdsrParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.aegis_note_fit.restype = C.c_int
-    lib.aegis_compare_audio.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p,
-                                        C.c_void_p]
-    lib.aegis_compare_audio.restype = C.c_int
-    lib.aegis_synth_one_note.argtypes = [C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_int32, C.POINTER(AdsrParams), C.c_void_p, C.c_int64]
-    lib.aegis_synth_one_note.restype = C.c_int64
-    lib.aegis_synth_notes_samples_for.argtypes = [C.c_int32, C.c_double, C.POINTER(AdsrParams), C.c_int64]
-    lib.aegis_synth_notes_samples_for.restype = C.c_int64
-    lib.aegis_synth_adsr_notes.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(AdsrParams),
-                                           C.POINTER(C.c_void_p), C.c_void_p]
-    lib.aegis_synth_adsr_notes.restype = C.c_int
-    lib.aegis_verify_techniques.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.c_void_p, C.c_int32, C.POINTER(VerifyEvent),
-                                            C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(AdsrParams), C.c_void_p, C.c_void_p, C.c_void_p,
-                                            C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.aegis_verify_techniques.restype = C.c_int
-    if hasattr(lib, "aegis_salience"):      # (an older library, loaded through AEGIS_HIP_LIB for a comparison, lacks the two entries)
-        lib.aegis_salience.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(SalienceParams),
-                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.aegis_salience.restype = C.c_int
-        lib.aegis_cqt_salience.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.c_int32,
-                                           C.c_double, C.c_double, C.POINTER(SalienceParams), C.c_void_p, C.c_void_p, C.c_void_p,
-                                           C.c_void_p, C.c_void_p]
-        lib.aegis_cqt_salience.restype = C.c_int
-    lib.aegis_set_profiling.argtypes = [C.c_void_p, C.c_int32]
-    lib.aegis_set_profiling.restype = C.c_int
-    lib.aegis_last_kernel_ms.argtypes = [C.c_void_p, C.c_char_p]
-    lib.aegis_last_kernel_ms.restype = C.c_double
-    lib.aegis_last_kernel_launches.argtypes = [C.c_void_p, C.c_char_p]
-    lib.aegis_last_kernel_launches.restype = C.c_int
-    _lib = lib
-    return lib
 
 
 _TABLE_DTYPES = {"mel_dense": np.float32}
@@ -310,9 +95,15 @@ class Handle:
         if not sys.is_finalizing():
             self.close()
 
-    def _check(self, rc):
+    def _error(self, rc, invalid=None):
+        """The exception of a failed call: AegisError with the library's message, or `invalid` (an exception type, given
+        the message alone) where the code is ERR_INVALID."""
+        msg = self.lib.aegis_last_error(self._h).decode()
+        return invalid(msg) if invalid and rc == ERR_INVALID else AegisError(rc, msg)
+
+    def _check(self, rc, invalid=None):
         if rc != OK:
-            raise AegisError(rc, self.lib.aegis_last_error(self._h).decode())
+            raise self._error(rc, invalid)
 
     def frames_for(self, n_samples):
         return int(self.lib.aegis_frames_for(self._h, int(n_samples)))
@@ -324,34 +115,20 @@ class Handle:
         return v
 
     def table(self, name):
-        n = int(self.lib.aegis_get_table(self._h, name.encode(), None, 0))
-        if n < 0:
-            raise AegisError(n, f"unknown table {name}")
-        out = np.empty(n, dtype=_TABLE_DTYPES.get(name, np.float64))
-        self.lib.aegis_get_table(self._h, name.encode(), out.ctypes.data, n)
-        return out
+        return _marshal.sized(lambda dst, cap: self.lib.aegis_get_table(self._h, name.encode(), dst, cap),
+                              _TABLE_DTYPES.get(name, np.float64), lambda rc: AegisError(rc, f"unknown table {name}"))
 
     def debug_fetch(self, name):
-        n = int(self.lib.aegis_debug_fetch(self._h, name.encode(), None, 0))
-        if n < 0:
-            raise AegisError(n, self.lib.aegis_last_error(self._h).decode())
-        out = np.empty(n, dtype=_DEBUG_DTYPES.get(name, np.float64))
-        got = int(self.lib.aegis_debug_fetch(self._h, name.encode(), out.ctypes.data, n))
-        if got < 0:
-            raise AegisError(got, self.lib.aegis_last_error(self._h).decode())
-        return out
+        return _marshal.sized(lambda dst, cap: self.lib.aegis_debug_fetch(self._h, name.encode(), dst, cap),
+                              _DEBUG_DTYPES.get(name, np.float64), self._error)
 
     def rake_columns(self, mel_power, clip_max, ratio, from_power):
         """The rake mask's column flags (before the run-length filter) of mel-power rows [n_rows, n_mels], by the kernel that
         decides from mel power (from_power=True) or the one that forms every dB value (aegis_debug_rake_columns)."""
         rows = np.ascontiguousarray(mel_power, dtype=np.float32)
         out = np.empty(rows.shape[0], dtype=np.uint8)
-        fn = self.lib.aegis_debug_rake_columns      # (bound here: an older library, loaded for a comparison, lacks the entry)
-        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_double, C.c_int32, C.c_void_p]
-        fn.restype = C.c_int
-        rc = int(fn(self._h, rows.ctypes.data, rows.shape[0], rows.shape[1], float(clip_max), float(ratio), int(bool(from_power)), out.ctypes.data))
-        if rc != 0:
-            raise AegisError(rc, self.lib.aegis_last_error(self._h).decode())
+        self._check(self.lib.aegis_debug_rake_columns(self._h, rows.ctypes.data, rows.shape[0], rows.shape[1], float(clip_max),
+                                                      float(ratio), int(bool(from_power)), out.ctypes.data))
         return out.astype(bool)
 
     def set_observations(self, logobs, logunv=None):
@@ -359,8 +136,6 @@ class Handle:
         the caller's clip order) instead of its observation kernel's; None disarms.  AegisError(ERR_INVALID) for rows
         outside the documented domain."""
         fn = self.lib.aegis_debug_set_observations
-        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
-        fn.restype = C.c_int
         if logobs is None:
             self._check(fn(self._h, None, None, 0))
             return
@@ -375,8 +150,6 @@ class Handle:
         caller's clip order) in place of its own difference function; None disarms.  AegisError(ERR_INVALID) for a value
         that is not finite."""
         fn = self.lib.aegis_debug_set_difference
-        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
-        fn.restype = C.c_int
         if d is None:
             self._check(fn(self._h, None, 0))
             return
@@ -397,11 +170,7 @@ class Handle:
         ns = np.ascontiguousarray(n_samples, dtype=np.int64)
         kind = self.PLAN_ENTRIES[entry] | (4 if cooling else 0) | (0 if persistent else 8)
         args = (self._h, ns.ctypes.data_as(C.POINTER(C.c_int64)), len(ns), kind, int(sync), int(n_cus))
-        n = int(self.lib.aegis_debug_plan(*args, None, 0))
-        if n < 0:
-            raise AegisError(n, self.lib.aegis_last_error(self._h).decode())
-        v = np.empty(n, np.int64)
-        self.lib.aegis_debug_plan(*args, v.ctypes.data, n)
+        v = _marshal.sized(lambda dst, cap: self.lib.aegis_debug_plan(*args, dst, cap), np.int64, self._error)
         passes, at = [], 1
         for _ in range(int(v[0])):
             d = {k: int(x) for k, x in zip(self.PLAN_FIELDS, v[at:at + len(self.PLAN_FIELDS)])}
@@ -441,12 +210,10 @@ class Handle:
         (np.nan_to_num, aegis_engine.py:69).  check_finite: librosa's valid_audio test on the device -> ValueError.
         views: the per-clip arrays are slices of the batch's buffers instead of copies.  concatenated: also return
         (buffers dict, frame offsets) of the whole batch, for the batched event extraction."""
-        clips = [np.ascontiguousarray(c, dtype=np.float32) for c in clips]
+        clips, ptrs, lens = _marshal.clips(clips, np.float32)
         n = len(clips)
         if n == 0:
             return ([], {}, np.zeros(1, np.int64)) if concatenated else []
-        ptrs = (C.c_void_p * n)(*[c.ctypes.data for c in clips])
-        lens = (C.c_int64 * n)(*[len(c) for c in clips])
         frames = [1 + len(c) // self.hop for c in clips]
         bufs, out, flags = self._outputs(frames, stages, want_sdb, check_finite, f0_zero, concatenated, want_col_means)
         rc = self.lib.aegis_analyze_batch(self._h, ptrs, lens, n, float(rake_sensitivity), flags, C.byref(out))
@@ -505,7 +272,7 @@ class Handle:
             res.append(d)
             fo += Fc
         if concatenated:
-            return res, bufs, np.concatenate([[0], np.cumsum(frames)]).astype(np.int64)
+            return res, bufs, _marshal.offsets(frames)
         return res
 
     def pcm_clips(self, sources, builtin_taps=False):
@@ -581,10 +348,10 @@ class Handle:
             lens = [x.shape[1]]
             flat = x.ravel()
         else:
-            series = [np.ascontiguousarray(s, dtype=np.float64) for s in series]
+            series = [np.ascontiguousarray(s, dtype=np.float64) for s in series]      # (a scalar becomes a series of one)
             lens = [len(s) for s in series]
-            flat = np.concatenate(series) if series else np.zeros(0)
-        off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+            flat = _marshal.concat(series, np.float64)
+        off = _marshal.offsets(lens)
         total = int(off[-1])
         par = np.ascontiguousarray(params, dtype=np.float64)
         dtypes = out_dtype if isinstance(out_dtype, (list, tuple)) else [out_dtype] * n_out
@@ -608,31 +375,23 @@ class Handle:
 
     def cqt(self, clips, n_bins=84, bins_per_octave=12, fmin=32.70319566257483, filter_scale=1.0):
         """|CQT| of each clip, float32 [n_bins, 1 + len//hop] (aegis_cqt: direct transform on the MFMA units)."""
-        clips = [np.ascontiguousarray(c, dtype=np.float32) for c in clips]
+        clips, ptrs, lens = _marshal.clips(clips, np.float32)
         n = len(clips)
         if n == 0:
             return []
-        ptrs = (C.c_void_p * n)(*[c.ctypes.data for c in clips])
-        lens = (C.c_int64 * n)(*[len(c) for c in clips])
         frames = [self.frames_for(len(c)) for c in clips]
         out = np.empty(sum(frames) * n_bins, np.float32)
         self._check(self.lib.aegis_cqt(self._h, ptrs, lens, n, n_bins, bins_per_octave, float(fmin), float(filter_scale),
                                        out.ctypes.data))
-        res, o = [], 0
-        for Fc in frames:
-            res.append(out[o:o + Fc * n_bins].reshape(n_bins, Fc).copy())
-            o += Fc * n_bins
-        return res
+        return _marshal.per_clip(out, frames, n_bins)
 
     def chroma_cqt(self, clips, bin_class, n_chroma=12, n_bins=252, bins_per_octave=36, fmin=32.70319566257483, filter_scale=1.0):
         """aegis_chroma_cqt: |CQT| folded into chroma classes (bin_class[n_bins] -> 0..n_chroma-1) and divided by the frame
         maximum, all on the device: float32 [n_chroma, 1 + len//hop] per clip."""
-        clips = [np.ascontiguousarray(c, dtype=np.float32) for c in clips]
+        clips, ptrs, lens = _marshal.clips(clips, np.float32)
         n = len(clips)
         if n == 0:
             return []
-        ptrs = (C.c_void_p * n)(*[c.ctypes.data for c in clips])
-        lens = (C.c_int64 * n)(*[len(c) for c in clips])
         frames = [self.frames_for(len(c)) for c in clips]
         cls = np.ascontiguousarray(bin_class, dtype=np.int32)
         if len(cls) != n_bins:
@@ -640,24 +399,18 @@ class Handle:
         out = np.empty(sum(frames) * n_chroma, np.float32)
         self._check(self.lib.aegis_chroma_cqt(self._h, ptrs, lens, n, n_bins, bins_per_octave, float(fmin), float(filter_scale),
                                               n_chroma, cls.ctypes.data, out.ctypes.data))
-        res, o = [], 0
-        for Fc in frames:
-            res.append(out[o:o + Fc * n_chroma].reshape(n_chroma, Fc).copy())
-            o += Fc * n_chroma
-        return res
+        return _marshal.per_clip(out, frames, n_chroma)
 
     def estimate_tuning(self, clips, bins_per_octave=36, want_counts=False):
         """aegis_estimate_tuning: librosa.estimate_tuning of every clip in ONE device call -> list of floats (fractions of a
         bin, in [-0.5, 0.5); 0.0 for a clip without peaks).  want_counts: (tunings, counts int32 [n, 100], n_peaks int64 [n])
         -- the histogram each answer is the first arg-max of, and the peaks found before the median cut."""
-        clips = [np.ascontiguousarray(c, dtype=np.float32) for c in clips]
+        clips, ptrs, lens = _marshal.clips(clips, np.float32)
         n = len(clips)
         tun = np.zeros(n, np.float64)
         counts = np.zeros((n, 100), np.int32) if want_counts else None
         peaks = np.zeros(n, np.int64) if want_counts else None
         if n:
-            ptrs = (C.c_void_p * n)(*[c.ctypes.data for c in clips])
-            lens = (C.c_int64 * n)(*[len(c) for c in clips])
             self._check(self.lib.aegis_estimate_tuning(self._h, ptrs, lens, n, int(bins_per_octave), tun.ctypes.data,
                                                        counts.ctypes.data if want_counts else None,
                                                        peaks.ctypes.data if want_counts else None))
@@ -703,14 +456,8 @@ class Handle:
     @staticmethod
     def _salience_split(frames, n_bins, top_k, img, cb, cs, csh):
         """The batch buffers of a salience call -> per clip (image or None, bins, saliences, shifts)."""
-        res, fo = [], 0
-        for Fc in frames:
-            res.append((img[fo * n_bins:(fo + Fc) * n_bins].reshape(n_bins, Fc).copy() if img is not None else None,
-                        cb[fo * top_k:(fo + Fc) * top_k].reshape(Fc, top_k).copy(),
-                        cs[fo * top_k:(fo + Fc) * top_k].reshape(Fc, top_k).copy(),
-                        csh[fo * top_k:(fo + Fc) * top_k].reshape(Fc, top_k).copy()))
-            fo += Fc
-        return res
+        imgs = _marshal.per_clip(img, frames, n_bins) if img is not None else [None] * len(frames)
+        return list(zip(imgs, *(_marshal.per_clip(a, frames, top_k, frame_major=True) for a in (cb, cs, csh))))
 
     def salience(self, mags, params, bins_per_octave=12, want_image=True):
         """aegis_salience: harmonic-sum salience and pitch candidates of caller magnitudes (a list of float32 [n_bins, F_c]
@@ -725,7 +472,7 @@ class Handle:
             raise ValueError("magnitudes must be [n_bins, F] arrays of one n_bins")
         frames = [m.shape[1] for m in mags]
         F, K = sum(frames), int(params.top_k)
-        flat = np.concatenate([m.ravel() for m in mags]) if F else np.zeros(0, np.float32)
+        flat = _marshal.concat([m.ravel() for m in mags], np.float32)
         nf = np.asarray(frames, np.int64)
         img = np.zeros(F * n_bins, np.float32) if want_image else None
         cb, cs, csh = np.full(F * max(K, 0), -1, np.int32), np.zeros(F * max(K, 0), np.float32), np.zeros(F * max(K, 0), np.float32)
@@ -739,12 +486,10 @@ class Handle:
         """aegis_cqt_salience: the CQT of aegis_cqt and the salience kernel behind it on the device -> (per clip tuples as
         salience() returns them, per clip magnitudes float32 [n_bins, F_c] or None).  The magnitudes leave the device only
         with want_mag."""
-        clips = [np.ascontiguousarray(c, dtype=np.float32) for c in clips]
+        clips, ptrs, lens = _marshal.clips(clips, np.float32)
         n = len(clips)
         if n == 0:
             return [], ([] if want_mag else None)
-        ptrs = (C.c_void_p * n)(*[c.ctypes.data for c in clips])
-        lens = (C.c_int64 * n)(*[len(c) for c in clips])
         frames = [self.frames_for(len(c)) for c in clips]
         F, K = sum(frames), int(params.top_k)
         mag = np.zeros(F * n_bins, np.float32) if want_mag else None
@@ -754,13 +499,7 @@ class Handle:
                                          C.byref(params), mag.ctypes.data if want_mag else None, img.ctypes.data if want_image else None,
                                          cb.ctypes.data, cs.ctypes.data, csh.ctypes.data)
         self._check(rc)
-        mags = None
-        if want_mag:
-            mags, o = [], 0
-            for Fc in frames:
-                mags.append(mag[o:o + Fc * n_bins].reshape(n_bins, Fc).copy())
-                o += Fc * n_bins
-        return self._salience_split(frames, n_bins, K, img, cb, cs, csh), mags
+        return self._salience_split(frames, n_bins, K, img, cb, cs, csh), (_marshal.per_clip(mag, frames, n_bins) if want_mag else None)
 
     def synth_parse_smf(self, midi_bytes, want_wheel=False):
         """aegis_synth_parse_smf: (notes in the reference's mix order as a SYNTH_NOTE_DTYPE array, mido's length in
@@ -778,10 +517,8 @@ class Handle:
                                                          wheel.ctypes.data, len(wheel), C.byref(n_wheel), C.byref(length)))
         else:
             n = int(self.lib.aegis_synth_parse_smf(self._h, blob, len(blob), notes.ctypes.data, len(notes), C.byref(length)))
-        if n == ERR_INVALID:
-            raise ValueError(self.lib.aegis_last_error(self._h).decode())
         if n < 0 or n > len(notes) or (want_wheel and not 0 <= n_wheel.value <= len(wheel)):
-            raise AegisError(n, self.lib.aegis_last_error(self._h).decode())
+            raise self._error(n, ValueError)
         if want_wheel:
             return notes[:n].copy(), float(length.value), track[:n].copy(), wheel[:n_wheel.value].copy()
         return notes[:n].copy(), float(length.value)
@@ -805,29 +542,22 @@ class Handle:
         sizes = [int(lib.aegis_synth_samples_for(int(sample_rate), float(lengths[i]), C.byref(par[i]))) for i in range(n)]
         if min(sizes) < 0:
             raise ValueError("bad ADSR parameters, sample rate or length")
-        off = np.concatenate([[0], np.cumsum([len(a) for a in note_lists])]).astype(np.int64)
-        notes = np.ascontiguousarray(np.concatenate(note_lists) if off[-1] else np.empty(0, SYNTH_NOTE_DTYPE), dtype=SYNTH_NOTE_DTYPE)
+        off = _marshal.offsets([len(a) for a in note_lists])
+        notes = _marshal.concat(note_lists, SYNTH_NOTE_DTYPE)
         lens = np.ascontiguousarray(lengths, dtype=np.float64)
-        outs = [np.empty(k, np.int16) for k in sizes]
-        ptrs = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
-        caps = np.asarray(sizes, np.int64)
+        outs, ptrs, caps = _marshal.clips([np.empty(k, np.int16) for k in sizes], np.int16)
         if bends is None:
-            rc = lib.aegis_synth_adsr(self._h, int(sample_rate), n, notes.ctypes.data, off.ctypes.data, lens.ctypes.data, par, ptrs,
-                                      caps.ctypes.data)
+            rc = lib.aegis_synth_adsr(self._h, int(sample_rate), n, notes.ctypes.data, off.ctypes.data, lens.ctypes.data, par, ptrs, caps)
         else:
             if len(bends) != n or any(len(b[0]) != len(a) for b, a in zip(bends, note_lists)):
                 raise ValueError("one (note_track, wheel, bend_range) per clip, one track per note")
-            track = np.ascontiguousarray(np.concatenate([np.asarray(b[0], np.int32) for b in bends]), dtype=np.int32)
-            woff = np.concatenate([[0], np.cumsum([len(b[1]) for b in bends])]).astype(np.int64)
-            wheel = np.ascontiguousarray(np.concatenate([np.asarray(b[1], SYNTH_WHEEL_DTYPE) for b in bends]) if woff[-1]
-                                         else np.empty(0, SYNTH_WHEEL_DTYPE), dtype=SYNTH_WHEEL_DTYPE)
+            track = _marshal.concat([b[0] for b in bends], np.int32)
+            woff = _marshal.offsets([len(b[1]) for b in bends])
+            wheel = _marshal.concat([b[1] for b in bends], SYNTH_WHEEL_DTYPE)
             ranges = np.ascontiguousarray([float(b[2]) for b in bends], dtype=np.float64)
             rc = lib.aegis_synth_adsr_bend(self._h, int(sample_rate), n, notes.ctypes.data, off.ctypes.data, lens.ctypes.data, par,
-                                           track.ctypes.data, wheel.ctypes.data, woff.ctypes.data, ranges.ctypes.data, ptrs,
-                                           caps.ctypes.data)
-        if rc == ERR_INVALID:
-            raise ValueError(lib.aegis_last_error(self._h).decode())
-        self._check(rc)
+                                           track.ctypes.data, wheel.ctypes.data, woff.ctypes.data, ranges.ctypes.data, ptrs, caps)
+        self._check(rc, ValueError)
         return outs
 
     def note_fit(self, clips, notes, candidates, sample_rate):
@@ -838,38 +568,27 @@ class Handle:
         maximum).  ValueError for what the library rejects."""
         if len(notes) != len(candidates):
             raise ValueError("one candidate list per note")
-        clips = [np.ascontiguousarray(c, dtype=np.float32) for c in clips]
+        clips, ptrs, lens = _marshal.clips(clips, np.float32)
         n = len(notes)
-        off = np.zeros(n + 1, np.int64)
-        off[1:] = np.cumsum([len(c) for c in candidates])
+        off = _marshal.offsets([len(c) for c in candidates])
         total = int(off[-1])
         out = np.zeros((4, max(total, 1)), np.float64)
         best = np.full(max(n, 1), -1, np.int32)
         arr = (FitNote * max(n, 1))(*[FitNote(int(c), int(m), int(lo), int(hi), int(v), 0, float(d)) for c, lo, hi, m, v, d in notes])
         par = (AdsrParams * max(total, 1))(*[p for c in candidates for p in c])
-        ptrs = (C.c_void_p * max(len(clips), 1))(*[c.ctypes.data for c in clips])
-        lens = np.asarray([len(c) for c in clips] or [0], np.int64)
-        rc = self.lib.aegis_note_fit(self._h, int(sample_rate), len(clips), ptrs, lens.ctypes.data, n, arr, par, off.ctypes.data,
+        rc = self.lib.aegis_note_fit(self._h, int(sample_rate), len(clips), ptrs, lens, n, arr, par, off.ctypes.data,
                                      out[0].ctypes.data, out[1].ctypes.data, out[2].ctypes.data, out[3].ctypes.data, best.ctypes.data)
-        if rc == ERR_INVALID:
-            raise ValueError(self.lib.aegis_last_error(self._h).decode())
-        self._check(rc)
+        self._check(rc, ValueError)
         return np.ascontiguousarray(out[:, :total].T), off, best[:n]
 
     def compare_audio(self, pairs, sample_rate):
         """aegis_compare_audio: compare_note_audio's (score, envelope, centroid, zero-crossing terms) of every (original,
         synthesised) pair of 1-D signals (read as float64), in ONE device call -> float64 [n_pairs][4]."""
-        a = [np.ascontiguousarray(p[0], dtype=np.float64) for p in pairs]
-        b = [np.ascontiguousarray(p[1], dtype=np.float64) for p in pairs]
+        a, pa, la = _marshal.clips([p[0] for p in pairs], np.float64)
+        b, pb, lb = _marshal.clips([p[1] for p in pairs], np.float64)
         n = len(pairs)
         out = np.zeros((max(n, 1), 4), np.float64)
-        pa = (C.c_void_p * max(n, 1))(*[x.ctypes.data for x in a])
-        pb = (C.c_void_p * max(n, 1))(*[x.ctypes.data for x in b])
-        la, lb = np.asarray([len(x) for x in a] or [0], np.int64), np.asarray([len(x) for x in b] or [0], np.int64)
-        rc = self.lib.aegis_compare_audio(self._h, int(sample_rate), n, pa, la.ctypes.data, pb, lb.ctypes.data, out.ctypes.data)
-        if rc == ERR_INVALID:
-            raise ValueError(self.lib.aegis_last_error(self._h).decode())
-        self._check(rc)
+        self._check(self.lib.aegis_compare_audio(self._h, int(sample_rate), n, pa, la, pb, lb, out.ctypes.data), ValueError)
         return out[:n]
 
     def verify_techniques(self, clips, events, variants, sample_rate):
@@ -880,48 +599,31 @@ class Handle:
         keep bool [n_events]).  ValueError for what the library rejects."""
         if len(events) != len(variants) or any(len(v) != 2 for v in variants):
             raise ValueError("two variants per event")
-        clips = [np.ascontiguousarray(c, dtype=np.float32) for c in clips]
+        clips, ptrs, sizes = _marshal.clips(clips, np.float32)
         n = len(events)
         files = [f for v in variants for f in v]
-        off = np.zeros(2 * n + 1, np.int64)
-        off[1:] = np.cumsum([len(f[0]) for f in files])
-        woff = np.zeros(2 * n + 1, np.int64)
-        woff[1:] = np.cumsum([len(f[4]) for f in files])
-        notes = np.ascontiguousarray(np.concatenate([np.asarray(f[0], SYNTH_NOTE_DTYPE) for f in files]) if off[-1]
-                                     else np.empty(0, SYNTH_NOTE_DTYPE), dtype=SYNTH_NOTE_DTYPE)
-        track = np.ascontiguousarray(np.concatenate([np.asarray(f[3], np.int32) for f in files]) if off[-1] else np.empty(0, np.int32),
-                                     dtype=np.int32)
-        wheel = np.ascontiguousarray(np.concatenate([np.asarray(f[4], SYNTH_WHEEL_DTYPE) for f in files]) if woff[-1]
-                                     else np.empty(0, SYNTH_WHEEL_DTYPE), dtype=SYNTH_WHEEL_DTYPE)
+        off = _marshal.offsets([len(f[0]) for f in files])
+        woff = _marshal.offsets([len(f[4]) for f in files])
+        notes = _marshal.concat([f[0] for f in files], SYNTH_NOTE_DTYPE)
+        track = _marshal.concat([f[3] for f in files], np.int32)
+        wheel = _marshal.concat([f[4] for f in files], SYNTH_WHEEL_DTYPE)
         lens = np.ascontiguousarray([float(f[1]) for f in files] or [0.0], dtype=np.float64)
         ranges = np.ascontiguousarray([float(f[5]) for f in files] or [0.0], dtype=np.float64)
         par = (AdsrParams * max(2 * n, 1))(*[f[2] for f in files])
         arr = (VerifyEvent * max(n, 1))(*[VerifyEvent(int(c), 0, int(lo), int(hi)) for c, lo, hi in events])
-        ptrs = (C.c_void_p * max(len(clips), 1))(*[c.ctypes.data for c in clips])
-        sizes = np.asarray([len(c) for c in clips] or [0], np.int64)
         sim = np.zeros((max(n, 1), 2), np.float64)
         keep = np.zeros(max(n, 1), np.uint8)
-        rc = self.lib.aegis_verify_techniques(self._h, int(sample_rate), len(clips), ptrs, sizes.ctypes.data, n, arr, notes.ctypes.data,
+        rc = self.lib.aegis_verify_techniques(self._h, int(sample_rate), len(clips), ptrs, sizes, n, arr, notes.ctypes.data,
                                               off.ctypes.data, lens.ctypes.data, par, track.ctypes.data, wheel.ctypes.data,
                                               woff.ctypes.data, ranges.ctypes.data, sim.ctypes.data, keep.ctypes.data)
-        if rc == ERR_INVALID:
-            raise ValueError(self.lib.aegis_last_error(self._h).decode())
-        self._check(rc)
+        self._check(rc, ValueError)
         return sim[:n], keep[:n].astype(bool)
 
     def synth_note(self, freq, duration, velocity, params, sample_rate):
         """aegis_synth_one_note: ADSRSynthesizer.synthesize_note (harmonics on) -> float64 array of int(sr * duration)."""
-        n = int(self.lib.aegis_synth_one_note(self._h, int(sample_rate), float(freq), float(duration), int(velocity), C.byref(params), None, 0))
-        if n == ERR_INVALID:
-            raise ValueError(self.lib.aegis_last_error(self._h).decode())
-        self._check(min(n, 0))
-        out = np.empty(n, np.float64)
-        got = int(self.lib.aegis_synth_one_note(self._h, int(sample_rate), float(freq), float(duration), int(velocity), C.byref(params),
-                                                out.ctypes.data, n))
-        if got == ERR_INVALID:
-            raise ValueError(self.lib.aegis_last_error(self._h).decode())
-        self._check(min(got, 0))
-        return out
+        args = (self._h, int(sample_rate), float(freq), float(duration), int(velocity), C.byref(params))
+        return _marshal.sized(lambda dst, cap: self.lib.aegis_synth_one_note(*args, dst, cap), np.float64,
+                              lambda rc: self._error(rc, ValueError))
 
     def synth_adsr_notes(self, note_lists, end_times, param_lists, sample_rate):
         """aegis_synth_adsr_notes: aegis_synth_adsr with one AdsrParams per NOTE.  note_lists: SYNTH_NOTE_DTYPE arrays;
@@ -934,22 +636,17 @@ class Handle:
         lib = self.lib
         flat = [p for c in param_lists for p in c]
         par = (AdsrParams * max(len(flat), 1))(*flat)
-        off = np.concatenate([[0], np.cumsum([len(a) for a in note_lists])]).astype(np.int64)
+        off = _marshal.offsets([len(a) for a in note_lists])
         sizes = [int(lib.aegis_synth_notes_samples_for(int(sample_rate), float(end_times[i]),
                                                        C.cast(C.byref(par, int(off[i]) * C.sizeof(AdsrParams)), C.POINTER(AdsrParams)),
                                                        int(off[i + 1] - off[i]))) for i in range(n)]
         if min(sizes) < 0:
             raise ValueError("bad ADSR parameters, sample rate or length")
-        notes = np.ascontiguousarray(np.concatenate(note_lists) if off[-1] else np.empty(0, SYNTH_NOTE_DTYPE), dtype=SYNTH_NOTE_DTYPE)
+        notes = _marshal.concat(note_lists, SYNTH_NOTE_DTYPE)
         lens = np.ascontiguousarray(end_times, dtype=np.float64)
-        outs = [np.empty(k, np.int16) for k in sizes]
-        ptrs = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
-        caps = np.asarray(sizes, np.int64)
-        rc = lib.aegis_synth_adsr_notes(self._h, int(sample_rate), n, notes.ctypes.data, off.ctypes.data, lens.ctypes.data, par, ptrs,
-                                        caps.ctypes.data)
-        if rc == ERR_INVALID:
-            raise ValueError(lib.aegis_last_error(self._h).decode())
-        self._check(rc)
+        outs, ptrs, caps = _marshal.clips([np.empty(k, np.int16) for k in sizes], np.int16)
+        rc = lib.aegis_synth_adsr_notes(self._h, int(sample_rate), n, notes.ctypes.data, off.ctypes.data, lens.ctypes.data, par, ptrs, caps)
+        self._check(rc, ValueError)
         return outs
 
     def effects(self, clips, chains, sample_rate, want_f64=True, want_i16=False, numpy_ir=True):
@@ -966,7 +663,7 @@ class Handle:
         if n == 0:
             return ([], []) if (want_f64 and want_i16) else []
         s16 = all(np.asarray(c).dtype == np.int16 for c in clips)
-        clips = [np.ascontiguousarray(c, dtype=np.int16 if s16 else np.float64) for c in clips]
+        clips, ptrs, lens = _marshal.clips(clips, np.int16 if s16 else np.float64)
         fx, off, keep = [], [0], {}
         for chain in chains:
             for name, params in chain:
@@ -986,18 +683,12 @@ class Handle:
             off.append(len(fx))
         arr = (Effect * max(len(fx), 1))(*fx)
         offs = np.asarray(off, np.int64)
-        lens = np.asarray([len(c) for c in clips], np.int64)
-        ptrs = (C.c_void_p * n)(*[c.ctypes.data for c in clips])
-        f64 = [np.empty(len(c), np.float64) for c in clips] if want_f64 else None
-        i16 = [np.empty(len(c), np.int16) for c in clips] if want_i16 else None
-        p64 = (C.c_void_p * n)(*[a.ctypes.data for a in f64]) if want_f64 else None
-        p16 = (C.c_void_p * n)(*[a.ctypes.data for a in i16]) if want_i16 else None
-        rc = self.lib.aegis_effects(self._h, int(sample_rate), n, ptrs, PCM_S16 if s16 else PCM_F64, lens.ctypes.data, arr,
+        f64, p64 = _marshal.clips([np.empty(len(c), np.float64) for c in clips], np.float64)[:2] if want_f64 else (None, None)
+        i16, p16 = _marshal.clips([np.empty(len(c), np.int16) for c in clips], np.int16)[:2] if want_i16 else (None, None)
+        rc = self.lib.aegis_effects(self._h, int(sample_rate), n, ptrs, PCM_S16 if s16 else PCM_F64, lens, arr,
                                     offs.ctypes.data, p64, p16)
         del keep
-        if rc == ERR_INVALID:
-            raise ValueError(self.lib.aegis_last_error(self._h).decode())
-        self._check(rc)
+        self._check(rc, ValueError)
         return (f64, i16) if (want_f64 and want_i16) else (f64 if want_f64 else i16)
 
     def open_stream(self, max_seconds=600.0, commit=False, commit_cap=None):
@@ -1020,25 +711,15 @@ class Handle:
 
 def resample_taps(up, down):
     """aegis_resample_taps: the library's built-in low-pass for a rate pair (host code, no handle, no GPU)."""
-    lib = load()
-    n = int(lib.aegis_resample_taps(int(up), int(down), None, 0))
-    if n < 0:
-        raise AegisError(n, "bad rate pair")
-    out = np.empty(n, np.float32)
-    lib.aegis_resample_taps(int(up), int(down), out.ctypes.data, n)
-    return out
+    return _marshal.sized(lambda dst, cap: load().aegis_resample_taps(int(up), int(down), dst, cap), np.float32,
+                          lambda rc: AegisError(rc, "bad rate pair"))
 
 
 def reverb_ir(room_size, sr):
     """aegis_reverb_ir: the library's own design of apply_reverb's impulse response (host code, no handle, no GPU); an
     empty array where the reference's reverb is a copy."""
-    lib = load()
-    n = int(lib.aegis_reverb_ir(float(room_size), int(sr), None, 0))
-    if n < 0:
-        raise AegisError(n, "bad room size or sample rate")
-    out = np.empty(n, np.float64)
-    lib.aegis_reverb_ir(float(room_size), int(sr), out.ctypes.data, n)
-    return out
+    return _marshal.sized(lambda dst, cap: load().aegis_reverb_ir(float(room_size), int(sr), dst, cap), np.float64,
+                          lambda rc: AegisError(rc, "bad room size or sample rate"))
 
 
 def numpy_reverb_ir(room_size, sr):
@@ -1101,26 +782,11 @@ class Stream:
 
     def close(self, rake_sensitivity=0.6, want_sdb=True):
         h = self.handle
-        cap = self._cap
-        bufs = {"f0": np.empty(cap, np.float64), "voiced_flag": np.empty(cap, np.uint8), "voiced_prob": np.empty(cap, np.float64),
-                "rms": np.empty(cap, np.float32), "rake_mask": np.empty(cap, np.uint8)}
-        if want_sdb:
-            bufs["S_dB"] = np.empty(cap * h.n_mels, np.float32)
-        out = Outputs()
-        for k, v in bufs.items():
-            setattr(out, k, v.ctypes.data)
+        # room for every frame the stream can hold, as one clip of a batch; the library says how many it wrote
+        bufs, out, _ = h._outputs([self._cap], STAGE_ALL, want_sdb, False, False, False, False)
         F = C.c_int64(0)
         h._check(self.lib.aegis_stream_close(self._s, float(rake_sensitivity), C.byref(out), C.byref(F)))
-        F = F.value
-        res = {}
-        for k, v in bufs.items():
-            if k == "S_dB":
-                res[k] = v[:F * h.n_mels].reshape(h.n_mels, F).copy()
-            elif k in ("voiced_flag", "rake_mask"):
-                res[k] = v[:F].astype(bool)
-            else:
-                res[k] = v[:F].copy()
-        return res
+        return h._split(bufs, [F.value], False, False)[0]
 
     def free(self):
         # safe in either order with Handle.close(): the C handle outlives its open streams (aegis_destroy defers)

@@ -16,6 +16,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 
 from . import _lib, midi_logic, smf
+from ._abi import Event, EventBatch, EventParams, RunFit      # noqa: F401 -- the ABI's structures, importable from here as before
 
 try:        # csrc/pyevents.c, built by csrc/Makefile next to libaegis_hip.so
     from . import _aegis_pyevents as _pyevents
@@ -26,49 +27,12 @@ TECH = (None, "vibrato", "bend", "slide", "hammer_on", "pull_off")
 _TECH_CODE = {t: i for i, t in enumerate(TECH)}
 
 
-class Event(C.Structure):
-    _fields_ = [("clip", C.c_int32), ("note", C.c_int32), ("start", C.c_int32), ("end", C.c_int32), ("velocity", C.c_int32),
-                ("track", C.c_uint8), ("technique", C.c_uint8), ("reserved0", C.c_uint8), ("reserved1", C.c_uint8),
-                ("rms_energy", C.c_float), ("reserved2", C.c_int32), ("confidence", C.c_double), ("slope", C.c_double)]
-
-
 EVENT_DTYPE = np.dtype([("clip", "<i4"), ("note", "<i4"), ("start", "<i4"), ("end", "<i4"), ("velocity", "<i4"),
                         ("track", "u1"), ("technique", "u1"), ("reserved0", "u1"), ("reserved1", "u1"),
                         ("rms_energy", "<f4"), ("reserved2", "<i4"), ("confidence", "<f8"), ("slope", "<f8")])
 assert EVENT_DTYPE.itemsize == C.sizeof(Event) == 48
-
-
-class RunFit(C.Structure):
-    _fields_ = [("clip", C.c_int32), ("start", C.c_int32), ("end", C.c_int32), ("technique", C.c_int32), ("slope", C.c_double)]
-
-
 FIT_DTYPE = np.dtype([("clip", "<i4"), ("start", "<i4"), ("end", "<i4"), ("technique", "<i4"), ("slope", "<f8")])
 assert FIT_DTYPE.itemsize == C.sizeof(RunFit) == 24
-
-
-class EventBatch(C.Structure):
-    _fields_ = [("n_clips", C.c_int32), ("reserved", C.c_int32), ("frame_off", C.c_void_p), ("sounding", C.c_void_p),
-                ("semitones", C.c_void_p), ("pitch_bin", C.c_void_p), ("bin_semitones", C.c_void_p), ("rms_db", C.c_void_p),
-                ("probs", C.c_void_p), ("fits", C.c_void_p), ("n_fits", C.c_int64)]
-
-
-class EventParams(C.Structure):
-    _fields_ = [("sample_rate", C.c_int32), ("hop_length", C.c_int32), ("confidence_threshold", C.c_double),
-                ("sustain_ms", C.c_double), ("min_note_duration_ms", C.c_double)]
-
-
-def _bind():
-    lib = _lib.load()
-    if not hasattr(lib, "_events_bound"):
-        lib.aegis_extract_events.argtypes = [C.POINTER(EventParams), C.POINTER(EventBatch), C.c_void_p, C.c_int64, C.c_void_p,
-                                             C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
-        lib.aegis_extract_events.restype = C.c_int64
-        lib.aegis_render_smf.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_void_p,
-                                         C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
-        lib.aegis_render_smf.restype = C.c_int64
-        lib.aegis_events_last_error.restype = C.c_char_p
-        lib._events_bound = True
-    return lib
 
 
 def _rms_db_block(rms, frame_off, amin=1e-5, top_db=80.0):
@@ -154,7 +118,7 @@ def extract_batch(frame_off, rake_mask, f0, voiced_flag, active_probs, rms, sr, 
     packed=True returns the structured array of all events + offsets instead of dicts (dist.pack_events's input).
     pitch_bin + freqs (the analysis's decoded bins, f0 == freqs[bin] where voiced): hz_to_midi comes from a table of
     len(freqs) entries instead of a logarithm per frame -- the same values."""
-    lib = _bind()
+    lib = _lib.load()
     noise_gate_db = kwargs.get("noise_gate_db", -40)
     frame_off = np.ascontiguousarray(frame_off, dtype=np.int64)
     n = len(frame_off) - 1
@@ -275,7 +239,7 @@ def get_midi_events(rake_mask, f0, voiced_flag, active_probs, rms, sr, hop_lengt
 
 def render_smf(events, sr, hop_length, midi_program=27, vibrato_rate=5.0, vibrato_depth=0.3):
     """smf.render through the native writer (one clip's list of event dicts -> SMF bytes)."""
-    lib = _bind()
+    lib = _lib.load()
     ev = pack([events])
     ev_off = np.array([0, len(ev)], np.int64)
     byte_off = np.zeros(2, np.int64)

@@ -25,7 +25,8 @@ def timed(name, fn):
     return w
 
 
-lib = en._bind()
+binding = en._lib
+lib = binding.load()
 
 
 class Lib:
@@ -34,8 +35,14 @@ class Lib:
         return timed(k, v) if k in ("aegis_extract_events", "aegis_render_smf") else v
 
 
+class Binding:
+    """events_native's own view of the binding: the same module, with load() answering the timing proxy."""
+    def __getattr__(self, k):
+        return (lambda: proxy) if k == "load" else getattr(binding, k)
+
+
 proxy = Lib()
-en._bind = lambda: proxy
+en._lib = Binding()
 en.batch_rms_db = timed("rms_db_and_gate", en.batch_rms_db)
 en_extract = en.extract_batch
 en.extract_batch = timed("extract_batch", en_extract)
