@@ -636,7 +636,8 @@ int aegis_effects(aegis_handle *h, int32_t sample_rate, int32_t n_clips, const v
  * "beta_probs" f64[100], "beta_cumsum" f64[101], "boltz_fact" f64[n], "boltz_exp" f64[n],
  * "log_trans_band" f64[4*n_cls*width], "log_trans_pack" f64[2*(3H^2+3H+2)] (H = (width-1)/2: the band table
  * without its duplicate (v,v') blocks and unreachable edge-row entries, as the Viterbi kernel keeps it in LDS),
- * "freqs" f64[n_pitch_bins], "twiddle" f64[2*n_fft], "tuning_edges" f64[101] (np.linspace(-0.5, 0.5, 101), the cell
+ * "freqs" f64[n_pitch_bins], "bin_edges" f64[n_pitch_bins + 2] (the period, in samples, at which the pitch bin steps
+ * from b - 1 to b: sample_rate / (fmin 2^((b - 0.5) / 120)), decreasing in b), "twiddle" f64[2*n_fft], "tuning_edges" f64[101] (np.linspace(-0.5, 0.5, 101), the cell
  * edges of aegis_estimate_tuning).
  * Returns the element count (or a negative code); copies min(count, cap) elements. */
 int64_t aegis_get_table(const aegis_handle *h, const char *name, void *dst, int64_t cap);
@@ -673,7 +674,8 @@ int64_t aegis_get_param(const aegis_handle *h, const char *name);
 /* Copies an intermediate of the most recent pass (device -> host), for stage-level
  * parity tests.  name in {"dfn" f64[F*lag_stride] (pyin's difference function d[tau], the one pYIN intermediate the
  * frame stage leaves in HBM), "yin" f64[F*yin_stride] (the CMND rows: only on handles created under AEGIS_DEBUG_STAGES=1),
- * "logobs" f64[F*obs_stride], "logunv" f64[F], "states" i32[F], "melpow" f32[F*n_mels], "rake_raw" u8[F]}.
+ * "logobs" f64[F*obs_stride], "logunv" f64[F], "obs_seg" i32[F] (which 64-bin segments of a logobs row the observation
+ * kernel stored: bit s = segment s, bit 30 = a hard frame, the whole row), "states" i32[F], "melpow" f32[F*n_mels], "rake_raw" u8[F]}.
  * Returns the element count available; copies min(count, cap).
  * What the most recent aegis_estimate_tuning call left on the device (0 before one has run, so always on a
  * device = -1 handle): "tuning_peak_off" i64[n_clips + 1] (each clip's room in the peak lists: frames * ceil(bins / 2)),
@@ -701,6 +703,16 @@ int64_t aegis_debug_fetch(aegis_handle *h, const char *name, void *dst, int64_t 
  * filter (what aegis_debug_fetch "rake_raw" u8[F] returns for the most recent pass). */
 int aegis_debug_rake_columns(aegis_handle *h, const float *mel_power, int64_t n_rows, int32_t n_mels, float clip_max,
                              double ratio, int32_t from_power, uint8_t *flags_out);
+
+/* The pitch bin of a refined trough period as pyin_obs_kernel decides it, on caller-supplied periods (in samples), for the
+ * tests that put periods on the edges of the decision (csrc/bin_decide.h): bin_table i16[n] is the bin read off the
+ * handle's table of period edges (aegis_get_table "bin_edges" f64[n_pitch_bins + 2]), or -1 where the table does not
+ * decide and the kernel evaluates the expression -- a period within 2^-30 of an edge, or one that is NaN, infinite, zero
+ * or negative; fell_through u8[n] is 1 there.  bin_exact i16[n] is the expression itself,
+ * clip(rint(120 log2((sr / period) / fmin)), 0, n_pitch_bins), which the kernel evaluates for every trough on a handle
+ * created under AEGIS_OBS_BIN_TABLE=0. */
+int aegis_debug_pitch_bins(aegis_handle *h, const double *periods, int64_t n, int16_t *bin_table, int16_t *bin_exact,
+                           uint8_t *fell_through);
 
 /* Replaces the observation kernel's output, for the tests that put the Viterbi kernels under adversarial rows: logobs is
  * f64[F][n_pitch_bins] (log observation of the voiced states), logunv f64[F] (the one value every unvoiced state observes),

@@ -22,7 +22,7 @@ class AegisError(RuntimeError):
 
 
 _TABLE_DTYPES = {"mel_dense": np.float32}
-_DEBUG_DTYPES = {"persistent_fallbacks": np.int64, "obs_cycles": np.int64, "cqt_cycles": np.int64, "viterbi_cycles": np.int64, "viterbi_spans": np.int64, "split_verify": np.int64, "split_flags": np.int64, "seg_lock": np.int64, "frame_cycles": np.int64, "states": np.int32, "melpow": np.float32, "rake_raw": np.uint8,
+_DEBUG_DTYPES = {"persistent_fallbacks": np.int64, "obs_cycles": np.int64, "cqt_cycles": np.int64, "viterbi_cycles": np.int64, "viterbi_spans": np.int64, "split_verify": np.int64, "split_flags": np.int64, "seg_lock": np.int64, "frame_cycles": np.int64, "states": np.int32, "obs_seg": np.int32, "melpow": np.float32, "rake_raw": np.uint8,
                  "tuning_pitch": np.float32, "tuning_mag": np.float32, "tuning_median": np.float32, "tuning_peak_off": np.int64}
 
 
@@ -130,6 +130,14 @@ class Handle:
         self._check(self.lib.aegis_debug_rake_columns(self._h, rows.ctypes.data, rows.shape[0], rows.shape[1], float(clip_max),
                                                       float(ratio), int(bool(from_power)), out.ctypes.data))
         return out.astype(bool)
+
+    def pitch_bins(self, periods):
+        """aegis_debug_pitch_bins: (bin read off the period-edge table, or -1; bin of the exact expression; fell-through
+        flags) of float64 periods, by the device functions pyin_obs_kernel decides a trough's pitch bin with."""
+        per = np.ascontiguousarray(periods, dtype=np.float64).ravel()
+        table, exact, fell = np.empty(len(per), np.int16), np.empty(len(per), np.int16), np.empty(len(per), np.uint8)
+        self._check(self.lib.aegis_debug_pitch_bins(self._h, per.ctypes.data, len(per), table.ctypes.data, exact.ctypes.data, fell.ctypes.data))
+        return table, exact, fell.astype(bool)
 
     def set_observations(self, logobs, logunv=None):
         """aegis_debug_set_observations: the NEXT analyze call decodes these rows (logobs [F, n_pitch_bins], logunv [F], in

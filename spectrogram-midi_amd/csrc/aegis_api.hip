@@ -7,6 +7,7 @@
 #include <cmath>
 #include <numeric>
 
+#include "bin_decide.h"
 #include "pcm.h"
 
 using namespace aegis;
@@ -22,7 +23,7 @@ PassParams aegis::base_params(const Tables &t) {
     p.min_period = t.min_period; p.max_period = t.max_period; p.n_lags = t.n_lags;
     p.n_bins = t.n_bins; p.half_width = t.half_width; p.width = t.width; p.n_cls = t.n_cls;
     p.f0_unvoiced = NAN;
-    p.fmin = t.fmin; p.log_tiny = t.log_tiny; p.log_pinit_v = t.log_pinit[0]; p.log_pinit_u = t.log_pinit[1];
+    p.fmin = t.fmin; p.bin_scale = bin_guess_scale(t.sr, t.fmin); p.log_tiny = t.log_tiny; p.log_pinit_v = t.log_pinit[0]; p.log_pinit_u = t.log_pinit[1];
     const RakeBounds rb = rake_frame_bounds(t);
     p.rake_min_frames = rb.min_frames; p.rake_max_frames = rb.max_frames;
     return p;
@@ -327,7 +328,7 @@ static PassParams bind_pass(const aegis_handle *h, const PassPlan &m, const aegi
     p.n_clips = nc; p.n_frames = m.fp;
     p.dfn = static_cast<double *>(w.dfn.p); p.lag_stride = h->lag_stride;
     p.yin = (py && h->debug_stages) ? static_cast<double *>(w.yin.p) : nullptr; p.yin_stride = h->yin_stride;
-    p.cmnd_in_frame = cmnd_in_frame(h); p.troughs = troughs_in_frame(h);
+    p.cmnd_in_frame = cmnd_in_frame(h); p.troughs = troughs_in_frame(h); p.bin_table = h->bin_table_off ? 0 : 1;
     p.logobs = static_cast<double *>(w.logobs.p); p.obs_stride = h->obs_stride;
     p.logunv = static_cast<double *>(w.logunv.p);
     p.obs_seg = static_cast<int32_t *>(w.obs_seg.p);

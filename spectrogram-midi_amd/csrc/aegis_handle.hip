@@ -163,6 +163,7 @@ int aegis_create(const aegis_config *cfg, aegis_handle **out) {
     if (const char *e = std::getenv("AEGIS_DEBUG_STAGES")) h->debug_stages = (e[0] == '1');
     if (const char *e = std::getenv("AEGIS_CMND_IN_FRAME")) h->cmnd_off = (e[0] == '0');
     if (const char *e = std::getenv("AEGIS_TROUGHS_IN_FRAME")) h->troughs_off = (e[0] == '0');
+    if (const char *e = std::getenv("AEGIS_OBS_BIN_TABLE")) h->bin_table_off = (e[0] == '0');
     if (const char *e = std::getenv("AEGIS_CQT_BANKS")) { const int v = std::atoi(e); if (v >= 1 && v <= 32) h->cqt_bank_cap = v; }
     h->tuning_edges.resize(kTunCells + 1);
     tuning_edges(h->tuning_edges.data());
@@ -224,6 +225,7 @@ int aegis_create(const aegis_config *cfg, aegis_handle **out) {
     CRT(upload_table(h, t.log_trans_band, &h->dt.lt_band));
     if (!t.log_trans_pack.empty()) CRT(upload_table(h, t.log_trans_pack, &h->dt.lt_pack));
     CRT(upload_table(h, t.freqs, &h->dt.freqs));
+    CRT(upload_table(h, t.bin_edges, &h->dt.bin_edges));
     {
         const double *tw = nullptr;
         CRT(upload_table(h, t.twiddle, &tw));
@@ -454,6 +456,7 @@ int64_t aegis_get_table(const aegis_handle *h, const char *name, void *dst, int6
     else if (n == "log_trans_band") setd(t.log_trans_band);
     else if (n == "log_trans_pack") setd(t.log_trans_pack);
     else if (n == "freqs") setd(t.freqs);
+    else if (n == "bin_edges") setd(t.bin_edges);
     else if (n == "twiddle") setd(t.twiddle);
     else if (n == "tuning_edges") setd(h->tuning_edges);
     else if (n == "mel_dense") { src = t.mel_dense.data(); count = (int64_t)t.mel_dense.size(); esz = 4; }
@@ -565,6 +568,7 @@ int64_t aegis_debug_fetch(aegis_handle *h, const char *name, void *dst, int64_t 
         return count;
     }
     else if (n == "logunv") { src = lw.logunv.p; count = F; }
+    else if (n == "obs_seg") { src = lw.obs_seg.p; count = F; esz = 4; }
     else if (n == "states") { src = lw.states.p; count = F; esz = 4; }
     else if (n == "melpow") { src = lw.melpow.p; count = F * h->tab.n_mels; esz = 4; }
     else if (n == "rake_raw") { src = lw.rake_raw.p; count = F; esz = 1; }
@@ -654,6 +658,31 @@ int aegis_debug_rake_columns(aegis_handle *h, const float *mel_power, int64_t n_
     launch_rake_columns(p, from_power != 0, s);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpyAsync(flags_out, h->rk_raw.p, n_rows, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    return AEGIS_OK;
+    } catch (...) { return abi_fail(h); }
+}
+
+int aegis_debug_pitch_bins(aegis_handle *h, const double *periods, int64_t n, int16_t *bin_table, int16_t *bin_exact, uint8_t *fell_through) {
+    try {
+    if (!h) return AEGIS_ERR_INVALID;
+    if (n < 0 || (n > 0 && (!periods || !bin_table || !bin_exact || !fell_through))) { h->err = "bad argument"; return AEGIS_ERR_INVALID; }
+    if (n == 0) return AEGIS_OK;
+    DEVICE_ONLY(h);
+    std::lock_guard<std::mutex> lock(h->mu);
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc;
+    if ((rc = ensure(h, h->dbg_bins, (size_t)n * 13)) != AEGIS_OK) return rc;     // periods f64 | table i16 | exact i16 | fell u8
+    hipStream_t s = h->stream;
+    double *d_per = static_cast<double *>(h->dbg_bins.p);
+    int16_t *d_fast = reinterpret_cast<int16_t *>(d_per + n), *d_exact = d_fast + n;
+    uint8_t *d_fell = reinterpret_cast<uint8_t *>(d_exact + n);
+    HIPCHK(h, hipMemcpyAsync(d_per, periods, (size_t)n * 8, hipMemcpyHostToDevice, s));
+    launch_pitch_bins(base_params(h->tab), h->dt, d_per, n, d_fast, d_exact, d_fell, s);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(bin_table, d_fast, (size_t)n * 2, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(bin_exact, d_exact, (size_t)n * 2, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(fell_through, d_fell, (size_t)n, hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipStreamSynchronize(s));
     return AEGIS_OK;
     } catch (...) { return abi_fail(h); }

@@ -50,6 +50,7 @@ struct aegis_handle {
     hipStream_t stream = nullptr;
     hipStream_t stream2 = nullptr;            // Viterbi stream of the time-chunked pipeline
     bool troughs_off = false;                 // AEGIS_TROUGHS_IN_FRAME=0 at create
+    bool bin_table_off = false;               // AEGIS_OBS_BIN_TABLE=0 at create: pyin_obs_kernel evaluates the exact pitch-bin expression for every trough
     bool cmnd_off = false;                    // AEGIS_CMND_IN_FRAME=0 at create: pyin_obs_kernel walks the CMND cumsum (tests compare the two paths)
     bool debug_stages = false;                // AEGIS_DEBUG_STAGES=1 at create: pyin_obs also writes the CMND rows ("yin") for the stage tests
     hipStream_t stream4 = nullptr;            // second frame-stage stream: odd time chunks (their FFTs overlap the even chunks' YIN / observation kernels)
@@ -77,7 +78,7 @@ struct aegis_handle {
         DevBuf sample_off, sample_len, out_off, frame_off, order, sel_off, vstate, chunk_lo, chunk_flag, clip_tb;
         DevBuf seg64, seg32, seg_col, seg_map, seg_i32, colhist, colG, colkg, clip_flag, flag_order, tube_buf, tube_at, tube_count;    // time-split passes
     } work[2];
-    DevBuf vstats, rk_raw, abort_flag, finite_flag;
+    DevBuf vstats, rk_raw, abort_flag, finite_flag, dbg_bins;
     // aegis_debug_set_observations: rows [F][n_bins] / [F] in the caller's clip order that the next analyze call feeds its
     // Viterbi in place of pyin_obs_kernel's (armed for that one call: the analyze entries disarm when they return)
     struct Inject { bool armed = false; int64_t F = 0; DevBuf obs, unv; } inject;

@@ -21,7 +21,7 @@ static PassParams stream_params(aegis_stream *st, const int64_t *dm) {
     p.n_clips = 1;
     p.dfn = static_cast<double *>(st->dfn.p); p.lag_stride = h->lag_stride;
     p.yin = nullptr; p.yin_stride = h->yin_stride;
-    p.cmnd_in_frame = cmnd_in_frame(h); p.troughs = troughs_in_frame(h);
+    p.cmnd_in_frame = cmnd_in_frame(h); p.troughs = troughs_in_frame(h); p.bin_table = h->bin_table_off ? 0 : 1;
     p.logobs = static_cast<double *>(st->logobs.p); p.obs_stride = h->obs_stride;
     p.logunv = static_cast<double *>(st->logunv.p);
     p.obs_seg = static_cast<int32_t *>(st->obs_seg.p);

@@ -28,6 +28,7 @@ struct DevTables {
     const double *lt_band;     // [4][n_cls][width]
     const double *lt_pack;     // [2 (stay, switch)][3H^2+3H+2] packed band table (viterbi.hip pk_*), or nullptr
     const double *freqs;       // [n_bins]
+    const double *bin_edges;   // [n_bins + 2] period edges of the pitch bins (bin_decide.h)
     const double2 *twiddle;    // [2048]
 };
 
@@ -57,6 +58,7 @@ struct PassParams {
     int32_t min_period, max_period, n_lags;
     int32_t n_bins, half_width, width, n_cls;
     double fmin;
+    float bin_scale;                   // sr / fmin in float32: the constant of the pitch-bin guess (bin_decide.h bin_guess_scale)
     double log_tiny;
     double log_pinit_v, log_pinit_u;   // log(p_init + tiny) of a voiced / an unvoiced state
     uint32_t stages;
@@ -134,6 +136,8 @@ struct PassParams {
                                          //                   cmnd_in_frame the entries tau >= min_period hold the CMND instead
     int32_t cmnd_in_frame;               // the frame kernel's epilogue forms the CMND (cumsum walk of all its frames at once);
                                          // 0: pyin_obs_kernel walks it frame by frame (stage tests, lag ranges the epilogue cannot hold)
+    int32_t bin_table;                   // pyin_obs_kernel reads a trough's pitch bin off DevTables::bin_edges (bin_decide.h); 0 (AEGIS_OBS_BIN_TABLE=0 at
+                                         // create: tests and A/B runs): two float64 divisions and a log2 for every trough
     int32_t troughs;                     // with cmnd_in_frame: the frame kernel also finds the CMND's troughs and leaves each frame's
                                          // trough list (count, values, parabolic shifts, lags: frame_walk.h trough_row_doubles) in its dfn row
                                          // instead of the CMND; pyin_obs_kernel starts at the threshold prior
@@ -170,6 +174,8 @@ int trough_row_doubles_host(int n_lags);    // doubles of a dfn row that holds a
 void launch_pyin_obs(const PassParams &p, const DevTables &t, hipStream_t s);
 // in its place (aegis_debug_set_observations): the launch's selected frames take their rows from src_obs [out_total][n_bins] / src_unv
 void launch_inject_obs(const PassParams &p, const double *src_obs, const double *src_unv, hipStream_t s);
+// aegis_debug_pitch_bins: bin_decide.h's bin_fast (-1 where it does not decide, fell = 1 there) and bin_exact of n periods (device arrays)
+void launch_pitch_bins(const PassParams &p, const DevTables &t, const double *periods, int64_t n, int16_t *fast, int16_t *exact, uint8_t *fell, hipStream_t s);
 int pyin_obs_waves(const PassParams &p);    // waves per pyin_obs workgroup of a launch of p.n_sel frames (p.dense: at most four)
 hipError_t launch_viterbi(const PassParams &p, const DevTables &t, const double *host_lt_band, hipStream_t s);
 // time-split pass: speculative runs (grid = segments), lock-on runs (grid = segments that have a predecessor, listed in

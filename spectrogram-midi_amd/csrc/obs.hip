@@ -1,6 +1,7 @@
 // pYIN's observation stage on gfx950 (MI355X / CDNA4, wave64); frame.hip lists what lives where.
 // Built with -ffp-contract=off: every multiply/add below rounds exactly where NumPy rounds.
 #include "kernels.h"
+#include "bin_decide.h"     // pitch bin from the period-edge table, threshold index in one step
 #include "frame_walk.h"      // the trough-list layout of a dfn row
 #include "pass_geometry.h"
 #include "wave_ops.h"
@@ -29,15 +30,17 @@ constexpr int kMaxRounds = 8; // kKMax / 64
     const int YN = (MAX(nl, B) + 1) & ~1;                                   \
     const int DN = ((mp) + 1 + 32 + 1) & ~1;                                \
     const int UN = (MAX(DN, 2 * KM + (4 * KM + 7) / 8) + 1) & ~1;           \
-    const int TN = (2 * (KM + 1) + 101 + 1) & ~1;
+    const int TN = (2 * (KM + 1) + 101 + (B) + 2 + 1) & ~1;
+#if defined(AEGIS_ABLATE) && (AEGIS_ABLATE & (256 | 1024))
+__device__ long long g_obs_dbg[16];       // [0 .. 9] section ticks (256); [10], [11] troughs that asked for a pitch bin / fell through to bin_exact (1024)
+#endif
 #if defined(AEGIS_ABLATE) && (AEGIS_ABLATE & 256)
-__device__ long long g_obs_dbg[16];
 #define OBS_TICK(k) { const long long now__ = clock64(); oacc[k] += now__ - olast; olast = now__; }
 #else
 #define OBS_TICK(k)
 #endif
 __global__ __launch_bounds__(512, 4) void pyin_obs_kernel(PassParams p, DevTables tb, int frames_per_wave) {
-    // dynamic LDS: bfact[KM+1] | bexp[KM+1] | bcum[101] (shared), then per wave y[YN] (CMND, reused as the output row) | U,
+    // dynamic LDS: bfact[KM+1] | bexp[KM+1] | bcum[101] | bedge[B+2] (shared), then per wave y[YN] (CMND, reused as the output row) | U,
     // where U holds first the difference function dd[DN] and later, once the CMND is formed, the trough arrays th[KM],
     // tp[KM], ti[KM], tbin[KM]
     extern __shared__ __align__(16) unsigned char osm[];
@@ -48,6 +51,7 @@ __global__ __launch_bounds__(512, 4) void pyin_obs_kernel(PassParams p, DevTable
     double *bfact = reinterpret_cast<double *>(osm);      // scipy.stats.boltzmann pieces and the Beta mass prefix sums: every lookup
     double *bexp = bfact + (KM + 1);                      // below is data dependent, so they sit in LDS instead of behind a global
     double *bcum = bexp + (KM + 1);                       // load each
+    double *bedge = bcum + 101;                           // period edges of the pitch bins (bin_decide.h)
     double *y = bfact + TN + (size_t)wid * (YN + UN);
     double *row = y;                       // written only after the last read of y
     double *dd = y + YN;
@@ -63,6 +67,7 @@ __global__ __launch_bounds__(512, 4) void pyin_obs_kernel(PassParams p, DevTable
     for (int i = threadIdx.x; i < 100; i += blockDim.x) beta_s[i] = tb.beta_probs[i];
     for (int i = threadIdx.x; i <= KM; i += blockDim.x) { bfact[i] = tb.boltz_fact[i]; bexp[i] = tb.boltz_exp[i]; }
     for (int i = threadIdx.x; i <= 100; i += blockDim.x) bcum[i] = tb.beta_cumsum[i];
+    for (int i = threadIdx.x; i < B + 2; i += blockDim.x) bedge[i] = tb.bin_edges[i];
     __syncthreads();
 
     int64_t f = 0, fo = 0, sel_end = 0;                   // the wave's frames are normally consecutive frames of one clip:
@@ -201,7 +206,8 @@ __global__ __launch_bounds__(512, 4) void pyin_obs_kernel(PassParams p, DevTable
     }   // troughs found here
 
     OBS_TICK(3)
-    double vp = 0.0;
+    double vp = 0.0, unv = 0.0, logu = 0.0;   // voiced_prob, the unvoiced observation (1 - vp) / B, log(unv + tiny)
+    bool have_logu = false;
     unsigned segm = 0;               // 64-bin segments of the observation row with an observed bin (wave-uniform)
     const int rounds = (K + 63) >> 6;
     // The list of the wave's NEXT frame, when that is the next frame of this clip: its count and its first two rounds are
@@ -229,17 +235,9 @@ __global__ __launch_bounds__(512, 4) void pyin_obs_kernel(PassParams p, DevTable
                 if (q < rounds) {
                     const int k = q * 64 + lane;
                     if (k < K) {
-                        // first threshold index j with h < thresholds[j+1]; 100 when none
-                        const double h = th[k];
-                        int g;
-                        if (!(h < 1.0)) g = 100;          // thresholds[100] == 1.0 (also NaN)
-                        else if (h <= 0.0) g = 0;
-                        else g = (int)(h * 100.0);
-                        // thresholds = np.linspace(0, 1, 101): i * 0.01 (one rounding), the last one forced to 1.0
-                        auto thr = [](int i) { return i >= 100 ? 1.0 : (double)i * 0.01; };
-                        while (g < 100 && !(h < thr(g + 1))) ++g;
-                        while (g > 0 && h < thr(g)) --g;
-                        jk[q] = g;
+                        // first threshold index j with h < thresholds[j+1]; 100 when none: (int)(h * 100) and at most one
+                        // step up or down, no data-dependent loop (bin_decide.h has the proof that one step is enough)
+                        jk[q] = threshold_index(th[k]);
                     }
                 }
             }
@@ -356,7 +354,26 @@ __global__ __launch_bounds__(512, 4) void pyin_obs_kernel(PassParams p, DevTable
                 }
             }
 
-            // parabolic refinement and pitch bin for every trough that carries probability
+            // parabolic refinement and pitch bin for every trough that carries probability.  The bin is read off the
+            // period-edge table (bin_decide.h): a float32 guess, accepted without a branch when the period lies inside the
+            // guess's interval by a guard band.  What that leaves -- a guess one bin off (1e-5 of the troughs), a period
+            // within 2^-30 of an edge, one that is not finite and positive, every trough under AEGIS_OBS_BIN_TABLE=0 -- is
+            // marked -2 and goes through ONE rolled loop behind the rounds, entered on a wave-uniform test: the neighbour
+            // bins, then the exact expression (two float64 divisions and a log2).  A single copy of that code per
+            // instance, out of the hot path's way in the shared instruction cache.
+            auto period_of = [&](int k) {
+                const int i = ti[k];
+                double shift = 0.0;
+                if (p.troughs) shift = tsh[k];
+                else if (i > 0 && i < nl - 1) {
+                    const double ym = y[i - 1], y0 = y[i], yp = y[i + 1];
+                    const double a = yp + ym - 2.0 * y0;
+                    const double b = (yp - ym) / 2.0;
+                    if (fabs(b) < fabs(a)) shift = -b / a;
+                }
+                return (double)(p.min_period + i) + shift;
+            };
+            bool unsure = false;
     #pragma unroll
             for (int q = 0; q < MAXR; ++q) {
                 const int k = q * 64 + lane;
@@ -364,25 +381,50 @@ __global__ __launch_bounds__(512, 4) void pyin_obs_kernel(PassParams p, DevTable
                     const double pr = acc[q];
                     int bin = -1;
                     if (pr != 0.0) {
-                        const int i = ti[k];
-                        double shift = 0.0;
-                        if (p.troughs) shift = tsh[k];
-                        else if (i > 0 && i < nl - 1) {
-                            const double ym = y[i - 1], y0 = y[i], yp = y[i + 1];
-                            const double a = yp + ym - 2.0 * y0;
-                            const double b = (yp - ym) / 2.0;
-                            if (fabs(b) < fabs(a)) shift = -b / a;
-                        }
-                        const double period = (double)(p.min_period + i) + shift;
-                        const double f0c = (double)p.sr / period;
-                        double r = rint(120.0 * log2(f0c / p.fmin));
-                        r = !(r >= 0.0) ? 0.0 : (r > (double)B ? (double)B : r);      // NaN-safe (np.clip would keep NaN; no finite input gets here with one)
-                        bin = (int)r;
+                        bin = bin_first(period_of(k), p.bin_scale, bedge, B);
+                        if (bin < 0 || !p.bin_table) { bin = -2; unsure = true; }
                     }
                     tp[k] = pr;
                     tbin[k] = (int16_t)bin;
                 }
             }
+            const unsigned long long unsure_m = __ballot(unsure);
+            if (__builtin_expect(unsure_m != 0ull, 0)) {
+    #if defined(AEGIS_ABLATE) && (AEGIS_ABLATE & 1024)
+                int n_exact = 0;
+    #endif
+                // (the expression's constants are formed here, where they are used: hoisted out of the frame loop they
+                // would sit in registers -- spilled ones -- for the sake of a loop that nearly never runs)
+                int sr_c = p.sr, B_c = B;
+                double fmin_c = p.fmin;
+                asm volatile("" : "+s"(sr_c), "+s"(B_c), "+s"(fmin_c));
+    #pragma unroll 1
+                for (int q = 0; q < rounds; ++q) {
+                    const int k = q * 64 + lane;
+                    if (k < K && tbin[k] == -2) {
+                        const double period = period_of(k);
+                        bool retried;
+                        int bin = p.bin_table ? bin_fast(period, p.bin_scale, bedge, B_c, &retried) : -1;     // (the neighbour bins)
+                        if (bin < 0) {
+                            bin = bin_exact(period, sr_c, fmin_c, B_c);
+    #if defined(AEGIS_ABLATE) && (AEGIS_ABLATE & 1024)
+                            ++n_exact;
+    #endif
+                        }
+                        tbin[k] = (int16_t)bin;
+                    }
+                }
+    #if defined(AEGIS_ABLATE) && (AEGIS_ABLATE & 1024)
+                if (n_exact) atomicAdd(reinterpret_cast<unsigned long long *>(&g_obs_dbg[11]), (unsigned long long)n_exact);
+    #endif
+            }
+    #if defined(AEGIS_ABLATE) && (AEGIS_ABLATE & 1024)
+            {   // troughs that carry probability (what the fell-through count above is a share of)
+                int n_bins_asked = 0;
+                for (int q = 0; q < rounds; ++q) { const int k = q * 64 + lane; if (k < K && tbin[k] >= 0) ++n_bins_asked; }
+                if (n_bins_asked) atomicAdd(reinterpret_cast<unsigned long long *>(&g_obs_dbg[10]), (unsigned long long)n_bins_asked);
+            }
+    #endif
         }
         OBS_TICK(6)
         if (ahead) {
@@ -400,12 +442,18 @@ __global__ __launch_bounds__(512, 4) void pyin_obs_kernel(PassParams p, DevTable
         wave_sync();                 // last read of y is behind us: the buffer becomes the output row
         for (int b = lane; b < B; b += 64) row[b] = p.log_tiny;
         wave_sync();
+        // The winners' probabilities and voiced_prob first, the logarithms after them: the frame's unvoiced observation
+        // log(unv + DBL_MIN) then rides in a lane of the winners' last log call that holds no winner (most lanes of that
+        // call are idle anyway) instead of costing a whole-wave float64 log of its own for one lane.  Same function, same
+        // argument, same bits.
+        bool winq[MAXR];
+        double prq[MAXR];
+    #pragma unroll
+        for (int q = 0; q < MAXR; ++q) { winq[q] = false; prq[q] = 0.0; }
         if (K > 0) {
             // observation_probs[bin, t] = probs: on duplicate bins the largest lag wins; bins are
             // non-increasing in lag, so a trough loses exactly when the next trough with
             // probability has the same bin.  Bin == B falls in the unvoiced half and is dropped.
-            bool winq[MAXR];
-            double prq[MAXR];
             unsigned lseg = 0;           // segments of the row this lane's winners fall in
             // the next trough that carries probability, for every trough at once: one ballot per round of 64 troughs and a
             // per-lane shift instead of a walk over tbin (a data-dependent loop of dependent LDS reads per lane)
@@ -419,7 +467,6 @@ __global__ __launch_bounds__(512, 4) void pyin_obs_kernel(PassParams p, DevTable
             }
     #pragma unroll
             for (int q = 0; q < MAXR; ++q) {
-                winq[q] = false; prq[q] = 0.0;
                 const int bin = binq[q];
                 if (bin >= 0 && bin < B) {
                     const unsigned long long above = lane < 63 ? hasm[q] >> (lane + 1) : 0ull;
@@ -431,7 +478,7 @@ __global__ __launch_bounds__(512, 4) void pyin_obs_kernel(PassParams p, DevTable
                             if (hasm[q2]) k2 = q2 * 64 + (int)__ffsll((long long)hasm[q2]) - 1;
                     }
                     const bool win = (k2 < 0) || ((int)tbin[k2 < 0 ? 0 : k2] != bin);
-                    if (win) { prq[q] = tp[q * 64 + lane]; row[bin] = log(prq[q] + DBL_MIN); lseg |= 1u << (bin >> 6); }
+                    if (win) { prq[q] = tp[q * 64 + lane]; lseg |= 1u << (bin >> 6); }
                     winq[q] = win;
                 }
             }
@@ -456,16 +503,40 @@ __global__ __launch_bounds__(512, 4) void pyin_obs_kernel(PassParams p, DevTable
             for (int sg = 0; sg * 64 < B; ++sg)
                 if (__ballot((lseg >> sg) & 1u)) segm |= 1u << sg;
         }
+        unv = (1.0 - vp) / (double)B;
+        if (K > 0) {
+            const double ua = unv + DBL_MIN;
+    #pragma unroll
+            for (int q = 0; q < MAXR; ++q) {
+                const bool last = q == rounds - 1;            // (uniform) the last round the frame has: every lane joins its call
+                if (q < rounds && (winq[q] || last)) {
+                    const double r = log(winq[q] ? prq[q] + DBL_MIN : ua);
+                    if (winq[q]) row[(int)tbin[q * 64 + lane]] = r;
+                    if (last) {
+                        const unsigned long long idle = ~__ballot(winq[q]);
+                        if (idle) {                           // (all 64 lanes win: the separate call below)
+                            const int l = (int)__builtin_ctzll(idle);
+                            logu = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(r), l), __builtin_amdgcn_readlane(__double2loint(r), l));
+                            have_logu = true;
+                        }
+                    }
+                }
+            }
+        }
     };
     if (rounds <= 2) tail(std::integral_constant<int, 2>{});
     else tail(std::integral_constant<int, kMaxRounds>{});
     wave_sync();
     OBS_TICK(7)
     Kn = -1;
+    // The wait for the look-ahead stands on every path, not only under `ahead`: without the requests nothing is outstanding
+    // here (the previous frame's stores were acknowledged long ago), and the compiler's own counter bookkeeping then knows
+    // on every path that nh / nsh / nix have arrived -- tied to `ahead` it added waits of its own behind the frame's stores,
+    // where they wait for the stores' acknowledgements.
+    __builtin_amdgcn_s_waitcnt(kWaitVmcnt0);
     if (ahead) {
         // th and ti were last read before the request above; the shifts go where this frame's output row still lies and
         // follow once the row has been read out (below).  More than two rounds: the next frame loads its own list.
-        __builtin_amdgcn_s_waitcnt(kWaitVmcnt0);
         Kn = __builtin_amdgcn_readfirstlane((int)__double_as_longlong(nK));
         if (Kn > 128) Kn = -1;
     #pragma unroll
@@ -477,14 +548,14 @@ __global__ __launch_bounds__(512, 4) void pyin_obs_kernel(PassParams p, DevTable
     // Only the 64-bin segments that hold an observed bin are stored (the Viterbi kernel skips a voiced wave whose segment
     // is all log(tiny) at an easy frame and never loads it); at a hard frame -- unvoiced observation log(tiny) -- every
     // value matters and the whole row goes out.
-    const double unv = (1.0 - vp) / (double)B;
+    if (!have_logu) logu = log(unv + DBL_MIN);      // (no trough at all, or 64 winners in the last round)
     if (unv == 0.0) segm = 0x40000000u | ((1u << ((B + 63) >> 6)) - 1u);
     double *__restrict__ orow = p.logobs + f * (int64_t)p.obs_stride;
     for (int b = lane, sg = 0; b < B; b += 64, ++sg)
         if ((segm >> sg) & 1u) orow[b] = row[b];
     if (lane == 0) {
         p.obs_seg[f] = (int32_t)segm;
-        p.logunv[f] = log(unv + DBL_MIN);
+        p.logunv[f] = logu;
         if (p.out_vprob != nullptr) p.out_vprob[fo] = vp;
     }
     #pragma unroll
@@ -498,7 +569,7 @@ __global__ __launch_bounds__(512, 4) void pyin_obs_kernel(PassParams p, DevTable
     if (blockIdx.x == 100 && threadIdx.x == 0) { for (int k = 0; k < 9; ++k) g_obs_dbg[k] = oacc[k]; g_obs_dbg[9] = frames_per_wave; }
 #endif
 }
-#if defined(AEGIS_ABLATE) && (AEGIS_ABLATE & 256)
+#if defined(AEGIS_ABLATE) && (AEGIS_ABLATE & (256 | 1024))
 hipError_t obs_debug_fetch(long long *dst) { return hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_obs_dbg), sizeof(long long) * 16); }
 #else
 hipError_t obs_debug_fetch(long long *dst) { for (int i = 0; i < 16; ++i) dst[i] = 0; return hipSuccess; }
@@ -557,6 +628,24 @@ __global__ __launch_bounds__(256) void inject_obs_kernel(PassParams p, const dou
         p.obs_seg[f] = (int32_t)segm;
         p.logunv[f] = unv;
     }
+}
+// Test hook (aegis_debug_pitch_bins): the device's bin_fast and bin_exact (bin_decide.h) over an array of periods, the edge
+// table read where the handle uploaded it.  fast is -1 and fell is 1 where the table does not decide.
+__global__ __launch_bounds__(256) void pitch_bins_kernel(const double *__restrict__ periods, int64_t n, const double *__restrict__ edges, int sr,
+                                                         double fmin, float scale, int B, int16_t *__restrict__ fast, int16_t *__restrict__ exact,
+                                                         uint8_t *__restrict__ fell) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    bool retried;
+    const int b = bin_fast(periods[i], scale, edges, B, &retried);
+    fast[i] = (int16_t)b;
+    exact[i] = (int16_t)bin_exact(periods[i], sr, fmin, B);
+    fell[i] = b < 0 ? 1 : 0;
+}
+void launch_pitch_bins(const PassParams &p, const DevTables &t, const double *periods, int64_t n, int16_t *fast, int16_t *exact, uint8_t *fell, hipStream_t s) {
+    if (n == 0) return;
+    hipLaunchKernelGGL(pitch_bins_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, periods, n, t.bin_edges, p.sr, p.fmin, p.bin_scale,
+                       p.n_bins, fast, exact, fell);
 }
 void launch_inject_obs(const PassParams &p, const double *src_obs, const double *src_unv, hipStream_t s) {
     if (p.n_sel == 0) return;

@@ -239,6 +239,10 @@ std::string Tables::build(int sr_, int hop_, int n_fft_, int n_mels_, double fmi
         }
         freqs.resize(B);
         for (int i = 0; i < B; ++i) freqs[i] = fmin * std::pow(2.0, (double)i / (12 * bps));
+        // the period edges of the pitch bins (bin_decide.h), formed in extended precision and rounded once
+        bin_edges.resize(B + 2);
+        for (int b = 0; b <= B + 1; ++b)
+            bin_edges[b] = (double)((long double)sr / ((long double)fmin * exp2l(((long double)b - 0.5L) / 120.0L)));
     }
 
     // ---- FFT twiddles exp(-2*pi*i*m/n), rounded from extended precision -----------------------

@@ -49,6 +49,8 @@ struct Tables {
                                         // without the unreachable parts of the edge rows (viterbi.hip pk_*); empty if
                                         // the (v,v') blocks are not pairwise identical
     std::vector<double> freqs;         // [n_bins]
+    std::vector<double> bin_edges;     // [n_bins + 2] period at which the pitch bin steps from b - 1 to b: sr / (fmin 2^((b - 0.5) / 120)),
+                                       // decreasing in b (bin_decide.h; bin n_bins is the clip value pyin drops)
     std::vector<double> twiddle;       // [n_fft][2]  cos, sin of -2*pi*m/n_fft
 
     std::string build(int sr, int hop, int n_fft, int n_mels, double fmin, double fmax);
