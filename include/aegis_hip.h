@@ -579,6 +579,53 @@ int aegis_cqt_salience(aegis_handle *h, const float *const *pcm, const int64_t *
                        int32_t bins_per_octave, double fmin, double filter_scale, const aegis_salience_params *p,
                        float *mag_out /* NULL ok */, float *sal_out /* NULL ok */, int32_t *cand_bin, float *cand_sal, float *cand_shift);
 
+/* --- Onset strength and onset picking behind the dB mel image ---------------------------------------------------------
+ * The reference calls no onset detector; the semantics are librosa 0.10's onset_strength / onset_detect /
+ * util.peak_pick / onset_backtrack in a fixed arithmetic order, stated once in csrc/onset.h and DESIGN.md 3.17 and pinned
+ * to tools/onset_restated.py, so the same bits come out of the host and of the device.
+ *   envelope      S: a clip's dB image, float32 [n_mels, F] C-order.  p = lag + shift, r = max_size / 2,
+ *                 ref[m, u] = max S[m - r .. m + r, u] (cut at the image's edges); env[t] = 0 for t < p, otherwise the
+ *                 float32 sum over m ascending of max(0, S[m, t - shift] - ref[m, t - p]), divided by n_mels.  F entries.
+ *                 librosa forms its own power_to_db(ref=1.0); this takes the engine's image (ref=max): the one deviation.
+ *   picking       no envelope value non-zero: no onsets.  normalize: x = (env - min) / ((max - min) + FLT_MIN) in float32.
+ *                 Frame i is a candidate when x[i] is the maximum of x[i - pre_max .. i + post_max - 1] and, in float64,
+ *                 x[i] >= mean(x[i - pre_avg .. i + post_avg - 1]) + delta (windows cut at the clip's ends, the sum
+ *                 ascending); candidates are kept left to right when i > last + wait.
+ *   backtrack     the reported frame of an onset i is the largest j <= i that is 0 or has e[j] <= e[j-1], e[j] < e[j+1]
+ *                 (0 < j < F - 1) on the energy track e (default: the envelope itself).
+ * Every field of aegis_onset_params has a "take the default" value: -1 for the integers (0 is a legal pre_max and wait),
+ * a negative delta.  Defaults: lag 1, max_size 1, shift n_fft / (2 hop) (librosa's center=True padding), librosa's
+ * pre_max = int(0.03 sr // hop), post_max = 1, pre_avg = int(0.10 sr // hop), post_avg = pre_avg + 1, wait = pre_max,
+ * normalize 1, delta 0.07.  p == NULL: every default.
+ * Results, concatenated over the clips as everything else is: env float32 [F_total]; onset_mask uint8 [F_total];
+ * onset_back (NULL, or) int32 [F_total]: the backtracked frame (within its clip) at onset frames, -1 elsewhere;
+ * n_onsets int64 [n_clips].
+ *   aegis_onset_strength   dB images from host memory (per clip [n_mels, n_frames[c]], clip after clip; n_mels 1..256).
+ *   aegis_onset_detect     envelopes from host memory, energy NULL or an energy track per frame.
+ *   aegis_analyze_onsets   PCM as aegis_analyze_batch takes it (a clip without samples is one frame of silence): the
+ *                          handle's mel stage into a device buffer, the two kernels behind it; only the envelope and the
+ *                          masks cross to the host.  env_out may be NULL; onset_mask NULL: the envelope only.
+ * A clip's results depend on that clip alone: the same bits alone, batched, reversed.
+ * AEGIS_ERR_INVALID with a message, before the device is looked at: lag outside 1..8, max_size even or outside 1..9,
+ * shift outside 0..64, pre_max / pre_avg outside 0..4096, post_max / post_avg outside 1..4096, wait outside 0..2^30,
+ * normalize not 0 / 1, a delta that is not finite, n_mels outside 1..256, NULL inputs or outputs.  A device = -1 handle
+ * rejects the same requests and answers AEGIS_ERR_DEVICE to a valid one.
+ * Kernel time: "onset_env" and "onset_pick" of aegis_last_kernel_ms.  Blocking; host pointers. */
+typedef struct aegis_onset_params {
+    int32_t lag, max_size, shift;
+    int32_t pre_max, post_max, pre_avg, post_avg, wait;
+    int32_t normalize;
+    int32_t reserved;
+    double delta;
+} aegis_onset_params;
+int aegis_onset_strength(aegis_handle *h, const float *S_dB, const int64_t *n_frames, int32_t n_clips, int32_t n_mels,
+                         const aegis_onset_params *p, float *env_out);
+int aegis_onset_detect(aegis_handle *h, const float *env, const float *energy /* NULL ok */, const int64_t *n_frames, int32_t n_clips,
+                       const aegis_onset_params *p, uint8_t *onset_mask, int32_t *onset_back /* NULL ok */, int64_t *n_onsets);
+int aegis_analyze_onsets(aegis_handle *h, const float *const *pcm, const int64_t *n_samples, int32_t n_clips,
+                         const aegis_onset_params *p, float *env_out /* NULL ok */, uint8_t *onset_mask /* NULL ok */,
+                         int32_t *onset_back /* NULL ok */, int64_t *n_onsets);
+
 /* --- Effect chain: distortion, reverb, delay, chorus (aegis_engine_core/effect_learning_loop.py:56-275) ----------
  * The reference's pure-NumPy effects, each ending in a whole-clip normalisation, which its learning loop
  * (effect_learning_loop.py:489-725) puts between the synthesiser and the engine.  Float64 throughout.

@@ -509,6 +509,83 @@ class Handle:
         self._check(rc)
         return self._salience_split(frames, n_bins, K, img, cb, cs, csh), (_marshal.per_clip(mag, frames, n_bins) if want_mag else None)
 
+    @staticmethod
+    def onset_params(lag=-1, max_size=-1, shift=-1, pre_max=-1, post_max=-1, pre_avg=-1, post_avg=-1, wait=-1, normalize=-1,
+                     delta=-1.0):
+        """aegis_onset_params; every argument left at -1 (None too) takes the library's default.  The library validates."""
+        v = [-1 if a is None else int(a) for a in (lag, max_size, shift, pre_max, post_max, pre_avg, post_avg, wait, normalize)]
+        return OnsetParams(*v, 0, -1.0 if delta is None else float(delta))
+
+    @staticmethod
+    def _onset_split(frames, env, mask, back, counts):
+        """The batch buffers of an onset call -> per clip (envelope or None, onset frames int64, backtracked frames int64 or None)."""
+        res, o = [], 0
+        for c, Fc in enumerate(frames):
+            on = np.flatnonzero(mask[o:o + Fc]) if mask is not None else None
+            if on is not None and len(on) != counts[c]:
+                raise AegisError(ERR_DEVICE, f"clip {c}: n_onsets says {int(counts[c])}, the mask holds {len(on)}")
+            res.append((env[o:o + Fc].copy() if env is not None else None, on,
+                        back[o:o + Fc][on].astype(np.int64) if back is not None else None))
+            o += Fc
+        return res
+
+    def onset_strength(self, images, params=None):
+        """aegis_onset_strength: the onset-strength envelope of caller dB images (a list of float32 [n_mels, F_c] arrays, one
+        n_mels) in ONE device call -> list of float32 [F_c].  params: onset_params(...).  AegisError with code ERR_INVALID
+        for what the library rejects."""
+        images = [np.ascontiguousarray(m, dtype=np.float32) for m in images]
+        if not images:
+            return []
+        n_mels = images[0].shape[0]
+        if any(m.ndim != 2 or m.shape[0] != n_mels for m in images):
+            raise ValueError("images must be [n_mels, F] arrays of one n_mels")
+        frames = [m.shape[1] for m in images]
+        flat = _marshal.concat([m.ravel() for m in images], np.float32)
+        nf = np.asarray(frames, np.int64)
+        env = np.zeros(sum(frames), np.float32)
+        self._check(self.lib.aegis_onset_strength(self._h, flat.ctypes.data, nf.ctypes.data, len(images), n_mels,
+                                                  C.byref(params) if params is not None else None, env.ctypes.data))
+        return [e for e, _, _ in self._onset_split(frames, env, None, None, None)]
+
+    def onset_detect(self, envelopes, params=None, energy=None, backtrack=False):
+        """aegis_onset_detect: the onset frames of caller envelopes (float32 [F_c] each; energy: None or one track per
+        envelope) in ONE device call -> per clip (onset frames int64, backtracked frames int64 or None)."""
+        envs = [np.ascontiguousarray(e, dtype=np.float32).ravel() for e in envelopes]
+        if not envs:
+            return []
+        frames = [len(e) for e in envs]
+        if energy is not None and [len(np.ravel(e)) for e in energy] != frames:
+            raise ValueError("one energy value per envelope frame")
+        flat = _marshal.concat(envs, np.float32)
+        en = _marshal.concat([np.ravel(e) for e in energy], np.float32) if energy is not None else None
+        nf = np.asarray(frames, np.int64)
+        F = sum(frames)
+        mask, back, counts = np.zeros(F, np.uint8), (np.full(F, -1, np.int32) if backtrack else None), np.zeros(len(envs), np.int64)
+        self._check(self.lib.aegis_onset_detect(self._h, flat.ctypes.data, en.ctypes.data if en is not None else None, nf.ctypes.data,
+                                                len(envs), C.byref(params) if params is not None else None, mask.ctypes.data,
+                                                back.ctypes.data if backtrack else None, counts.ctypes.data))
+        return [(on, bk) for _, on, bk in self._onset_split(frames, None, mask, back, counts)]
+
+    def analyze_onsets(self, clips, params=None, want_env=True, want_onsets=True, backtrack=False):
+        """aegis_analyze_onsets: the handle's mel stage and the two onset kernels behind it on the device, ONE call for the
+        batch -> per clip (envelope float32 [F_c] or None, onset frames int64 or None, backtracked frames int64 or None).
+        A clip without samples is one frame of silence."""
+        clips, ptrs, lens = _marshal.clips(clips, np.float32)
+        n = len(clips)
+        if n == 0:
+            return []
+        frames = [self.frames_for(len(c)) for c in clips]
+        F = sum(frames)
+        env = np.zeros(F, np.float32) if want_env else None
+        mask = np.zeros(F, np.uint8) if want_onsets else None
+        back = np.full(F, -1, np.int32) if (want_onsets and backtrack) else None
+        counts = np.zeros(n, np.int64)
+        self._check(self.lib.aegis_analyze_onsets(self._h, ptrs, lens, n, C.byref(params) if params is not None else None,
+                                                  env.ctypes.data if env is not None else None,
+                                                  mask.ctypes.data if mask is not None else None,
+                                                  back.ctypes.data if back is not None else None, counts.ctypes.data))
+        return self._onset_split(frames, env, mask, back, counts)
+
     def synth_parse_smf(self, midi_bytes, want_wheel=False):
         """aegis_synth_parse_smf: (notes in the reference's mix order as a SYNTH_NOTE_DTYPE array, mido's length in
         seconds) of a Standard MIDI File; ValueError for bytes that are not one (mido raises).  Host code.

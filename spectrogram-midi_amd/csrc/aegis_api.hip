@@ -726,23 +726,23 @@ int aegis_analyze_batch_device(aegis_handle *h, const float *d_pcm, const int64_
     } catch (...) { return abi_fail(h); }
 }
 
-// The blocking host-fed analysis of aegis_analyze_batch and aegis_analyze_pcm (handle locked, io_pcm sized): the device
-// outputs, the pipeline fed by make_feed() (a fresh feed for every attempt), the outputs back to the host.
-static int host_fed_locked(aegis_handle *h, const std::vector<int64_t> &off, int64_t F, int32_t n_clips, double rake_sensitivity,
-                           uint32_t stages, aegis_outputs *out, const std::function<HostFeed()> &make_feed) {
+// The device half of a host-fed analysis (handle locked, io_pcm sized): the staging buffer of every output `want` names is
+// sized and entered in d, and the pipeline fed by make_feed() (a fresh feed for every attempt) is enqueued on the handle's
+// stream.  Not synchronised, unless the single Viterbi launch had to be checked.
+static int host_fed_run_locked(aegis_handle *h, const std::vector<int64_t> &off, int64_t F, int32_t n_clips, double rake_sensitivity,
+                               uint32_t stages, const aegis_outputs *want, aegis_outputs &d, const std::function<HostFeed()> &make_feed) {
     int rc;
     hipStream_t s = h->stream;
     // the previous call's kernels may still read io_pcm only if it returned without a sync -- it never does
-    aegis_outputs d{};
     const int nm = h->tab.n_mels;
     for (const OutField &f : kOutFields) {
-        if (!(stages & f.stage) || !f.get(out)) continue;
+        if (!(stages & f.stage) || !f.get(want)) continue;
         if ((rc = ensure(h, h->*f.io, f.size(F, nm))) != AEGIS_OK) return rc;
         f.set(&d, (h->*f.io).p);
     }
     // stream_v = NULL (the handle's own stream) and sync = 2: the schedule the device-pointer entry takes with
     // sync = 1, single Viterbi launch included -- the attempt synchronises itself before it reads the abort flag
-    rc = run_with_recovery(h, [&]() -> int {
+    return run_with_recovery(h, [&]() -> int {
         HostFeed feed = make_feed();
         const int r = analyze_device_locked(h, static_cast<const float *>(h->io_pcm.p), off.data(), n_clips,
                                             rake_sensitivity, stages, &d, nullptr, 2, &feed);
@@ -750,6 +750,16 @@ static int host_fed_locked(aegis_handle *h, const std::vector<int64_t> &off, int
         HIPCHK(h, hipStreamSynchronize(s));
         return persistent_check(h);
     });
+}
+
+// The blocking host-fed analysis of aegis_analyze_batch and aegis_analyze_pcm (handle locked, io_pcm sized): the device
+// half above, the outputs back to the host.
+static int host_fed_locked(aegis_handle *h, const std::vector<int64_t> &off, int64_t F, int32_t n_clips, double rake_sensitivity,
+                           uint32_t stages, aegis_outputs *out, const std::function<HostFeed()> &make_feed) {
+    hipStream_t s = h->stream;
+    aegis_outputs d{};
+    const int nm = h->tab.n_mels;
+    const int rc = host_fed_run_locked(h, off, F, n_clips, rake_sensitivity, stages, out, d, make_feed);
     if (rc != AEGIS_OK) return rc;
     for (const OutField &f : kOutFields)
         if (f.get(&d)) HIPCHK(h, hipMemcpyAsync(f.get(out), f.get(&d), f.size(F, nm), hipMemcpyDeviceToHost, s));
@@ -759,6 +769,27 @@ static int host_fed_locked(aegis_handle *h, const std::vector<int64_t> &off, int
     if (h->profiling) collect_events(h);
     return finite_result(h, stages, off.data(), n_clips);
 }
+
+// (declared in aegis_internal.h with C++ linkage: aegis_onset.hip runs it in front of its kernels)
+}  // extern "C"
+int aegis::mel_host_locked(aegis_handle *h, const float *const *pcm, const int64_t *n_samples, int32_t n_clips, std::vector<int64_t> &off,
+                           std::vector<int64_t> &foff) {
+    struct Disarm { aegis_handle *h; ~Disarm() { h->inject.armed = false; h->inject_d.armed = false; } } disarm{h};   // as every analyze entry
+    off.assign((size_t)n_clips + 1, 0);
+    foff.assign((size_t)n_clips + 1, 0);
+    for (int i = 0; i < n_clips; ++i) {
+        off[(size_t)i + 1] = off[(size_t)i] + n_samples[i];
+        foff[(size_t)i + 1] = foff[(size_t)i] + 1 + n_samples[i] / h->tab.hop;
+    }
+    int rc;
+    if ((rc = ensure(h, h->io_pcm, (size_t)std::max<int64_t>(off[(size_t)n_clips], 1) * 4)) != AEGIS_OK) return rc;
+    aegis_outputs want{}, d{};
+    want.S_dB = reinterpret_cast<float *>(h);          // any non-NULL value: the dB image is the one output wanted
+    return host_fed_run_locked(h, off, foff[(size_t)n_clips], n_clips, 0.6, AEGIS_STAGE_MEL, &want, d, [&]() {
+        return HostFeed{pcm, static_cast<float *>(h->io_pcm.p), std::vector<int64_t>((size_t)n_clips, 0)};
+    });
+}
+extern "C" {
 
 int aegis_analyze_batch(aegis_handle *h, const float *const *pcm, const int64_t *n_samples, int32_t n_clips,
                         double rake_sensitivity, uint32_t stages, aegis_outputs *out) {

@@ -14,6 +14,8 @@
 //                     aegis_synth.hip's render_into)
 //   aegis_salience.hip aegis_salience, aegis_cqt_salience (harmonic-sum salience and pitch candidates; kernel in
 //                     salience.hip, the CQT in front of it through aegis_cqt.hip's cqt_host_locked)
+//   aegis_onset.hip   aegis_onset_strength, aegis_onset_detect, aegis_analyze_onsets (onset envelope and onset picking;
+//                     kernels in onset.hip, the mel stage in front of them through aegis_api.hip's mel_host_locked)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -136,6 +138,7 @@ struct aegis_handle {
     struct VerifyBank { aegis::MelBank host; int32_t n_used = 0; bool uploaded = false; DevBuf start, len, off, w; };
     std::map<int32_t, VerifyBank> vf_banks;
     DevBuf sl_mag, sl_foff, sl_img, sl_bin, sl_sal, sl_shift;   // aegis_salience / aegis_cqt_salience: caller magnitudes, frame offsets, image, candidates
+    DevBuf on_img, on_foff, on_env, on_energy, on_x, on_mask, on_back, on_count;   // aegis_onset_* / aegis_analyze_onsets: caller images / envelopes, frame offsets, envelope, energy track, normalised envelope, results
     bool notefit_store = false;               // AEGIS_NOTEFIT_STORE=1 at create: every candidate rendered once into nf_sig and read by the frames instead of recomputed
     int32_t lag_stride = 0, yin_stride = 0, obs_stride = 0;
     aegis::CallPlan plan;                     // the last call's plan: its host arrays stay alive until the stream drained
@@ -276,6 +279,15 @@ int render_into(aegis_handle *h, const AdsrBatch &B, const char *const (&labels)
 // filled in, *F_out is the frame total.  bin_class: the chroma fold's classes (uploaded to q_cls), or nullptr.
 int cqt_host_locked(aegis_handle *h, const float *const *pcm, const int64_t *n_samples, int32_t n_clips, int32_t &n_bins,
                     int32_t bins_per_octave, double fmin, double filter_scale, int32_t n_chroma, const int32_t *bin_class, int64_t *F_out);
+
+// ---- the mel stage as a stage of another entry (aegis_api.hip) ----
+// Handle locked, device set, clips validated (n_samples[i] >= 0, pcm[i] != NULL where there are samples): the samples fed
+// as aegis_analyze_batch feeds them and the pipeline's AEGIS_STAGE_MEL pass enqueued on the handle's stream into io_sdb
+// (per clip [n_mels, F_c], clip after clip, the caller's order; a clip without samples is one frame of silence).  Not
+// synchronised: the caller enqueues behind it, synchronises the stream and clears plan_in_flight.  off / foff: sample and
+// frame offsets [n_clips + 1]; off must outlive that synchronisation.
+int mel_host_locked(aegis_handle *h, const float *const *pcm, const int64_t *n_samples, int32_t n_clips, std::vector<int64_t> &off,
+                    std::vector<int64_t> &foff);
 
 // ---- kernel parameters every entry fills the same way (aegis_api.hip) ----
 struct RakeBounds { int min_frames, max_frames; };

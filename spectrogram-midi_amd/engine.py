@@ -13,12 +13,12 @@ import multiprocessing
 
 import numpy as np
 
-from . import _lib, audio_io, events_native, midi_logic, smf
+from . import _lib, audio_io, events_native, midi_logic, onsets as _onsets, smf
 from .convert import note_to_hz
 
 _FMIN, _FMAX = note_to_hz("E2"), note_to_hz("C6")
 _ENGINE_ONLY_KWARGS = ("confidence_threshold", "start_time", "end_time", "turbo_mode", "rake_sensitivity",
-                       "vibrato_rate", "vibrato_depth")
+                       "vibrato_rate", "vibrato_depth", "onsets", "split_on_onsets")
 
 
 class AegisEngine:
@@ -92,19 +92,46 @@ class AegisEngine:
         `output_mid` is accepted and ignored, as in the reference."""
         return self.analyze_files([input_wav], turbo_mode=kwargs.get("turbo_mode", False),
                                   rake_sensitivity=kwargs.get("rake_sensitivity", 0.6), start_time=kwargs.get("start_time", 0),
-                                  end_time=kwargs.get("end_time", None))[0]
+                                  end_time=kwargs.get("end_time", None), onsets=kwargs.get("onsets", False))[0]
 
     analyze = audio_to_midi      # BASELINE.json's name for the same call
 
-    def analyze_array(self, y, turbo_mode=False, rake_sensitivity=0.6):
+    def analyze_array(self, y, turbo_mode=False, rake_sensitivity=0.6, onsets=False):
         """audio_to_midi from decoded PCM onward (aegis_engine.py:51-75)."""
-        res = self.analyze_arrays([y], turbo_mode=turbo_mode, rake_sensitivity=rake_sensitivity)
+        res = self.analyze_arrays([y], turbo_mode=turbo_mode, rake_sensitivity=rake_sensitivity, onsets=onsets)
         return res[0]
 
-    def analyze_arrays(self, clips, turbo_mode=False, rake_sensitivity=0.6, _concatenated=False):
+    # ------------------------------------------------------------------ onsets (not reference methods)
+    def detect_onsets(self, path_or_array, **kw):
+        """A WAV path or decoded samples -> the onset frames (onsets.onset_detect: backtrack, units and the pick's
+        parameters by keyword; start_time / end_time for a path); an empty array for empty audio."""
+        if isinstance(path_or_array, (str, bytes)) or hasattr(path_or_array, "__fspath__"):
+            end, start = kw.pop("end_time", None), kw.pop("start_time", 0)
+            srcs = audio_io.load_pcm_files([path_or_array], self.sr, start, (end - start) if end else None)
+            y = self.handle.analyze_pcm(srcs, stages=0, check_finite=True)[0]["y"]
+        else:
+            y = np.ascontiguousarray(path_or_array, dtype=np.float32)
+        if len(y) == 0:
+            return np.zeros(0, np.float64 if kw.get("units") == "time" else np.int64)
+        return _onsets.onset_detect(self.handle, [y], **kw)[0]
+
+    def _add_onsets(self, raws, clips):
+        """raw["onset_env"] / raw["onset_frames"] of every analysed clip, from ONE aegis_analyze_onsets call for the batch."""
+        live = [i for i, r in enumerate(raws) if r is not None]
+        if live:
+            for i, (env, on, _) in zip(live, self.handle.analyze_onsets([clips[i] for i in live])):
+                raws[i]["onset_env"], raws[i]["onset_frames"] = env, on
+
+    def _split_on_onsets(self, events, raw, kwargs):
+        if raw is None or "onset_frames" not in raw:
+            raise ValueError("split_on_onsets needs raw data analysed with onsets=True (raw['onset_frames'] is missing)")
+        return _onsets.split_events_at_onsets(events, raw["onset_frames"], raw, self.sr, self.hop_length,
+                                              kwargs.get("confidence_threshold", 0.70), kwargs.get("min_note_duration_ms", 50))
+
+    def analyze_arrays(self, clips, turbo_mode=False, rake_sensitivity=0.6, onsets=False, _concatenated=False):
         """Batch form: one ragged GPU batch for a folder of clips; element i is what
         audio_to_midi returns for clip i (None for an empty clip).  The arrays of a batch are slices of the batch's
-        buffers (one allocation per output, not one per clip)."""
+        buffers (one allocation per output, not one per clip).  onsets=True adds "onset_env" and "onset_frames"."""
         clips = [np.ascontiguousarray(c, dtype=np.float32) for c in clips]
         live = [i for i, c in enumerate(clips) if len(c) > 0]
         results = [None] * len(clips)
@@ -136,10 +163,12 @@ class AegisEngine:
             results[i] = {"rake_mask": r["rake_mask"], "f0": r["f0"],
                           "voiced_flag": r["voiced_flag"], "voiced_probs": r["voiced_prob"],
                           "rms": r["rms"], "y": clips[i]}
+        if onsets:
+            self._add_onsets(results, clips)
         return (results, bufs, off, live) if _concatenated else results
 
     def analyze_files(self, paths, turbo_mode=False, rake_sensitivity=0.6, start_time=0, end_time=None, want_y=True,
-                      _concatenated=False):
+                      onsets=False, _concatenated=False):
         """A folder of WAV files -> element i is what audio_to_midi(paths[i], None, ...) returns.  The files are read
         one after the other as raw sample bytes (audio_io.load_pcm); decoding, the channel mean and the resampling to
         the engine rate run on the GPU, inside the analysis (Handle.analyze_pcm).  want_y=False: "y" is None and the
@@ -149,7 +178,7 @@ class AegisEngine:
         if turbo_mode:          # decode only, then the Turbo-Mode analysis of the decoded clips
             h = self.handle
             ys = [r["y"] for r in h.analyze_pcm(srcs, stages=0)] if srcs else []
-            got = self.analyze_arrays(ys, turbo_mode=True, rake_sensitivity=rake_sensitivity, _concatenated=_concatenated)
+            got = self.analyze_arrays(ys, turbo_mode=True, rake_sensitivity=rake_sensitivity, onsets=onsets, _concatenated=_concatenated)
             if not want_y:
                 for r in (got[0] if _concatenated else got):
                     if r is not None:
@@ -164,10 +193,15 @@ class AegisEngine:
         self._say("[Aegis] Using Stable Single-core Analysis.")
         frames, bufs, off = self.handle.analyze_pcm([srcs[i] for i in live], rake_sensitivity=rake_sensitivity,
                                                     stages=_lib.STAGE_ALL, want_sdb=False, check_finite=True, f0_zero=True,
-                                                    views=True, concatenated=True, want_y=want_y)
+                                                    views=True, concatenated=True, want_y=want_y or onsets)
         for i, r in zip(live, frames):
             results[i] = {"rake_mask": r["rake_mask"], "f0": r["f0"], "voiced_flag": r["voiced_flag"],
                           "voiced_probs": r["voiced_prob"], "rms": r["rms"], "y": r["y"]}
+        if onsets:              # (the decoded samples go through the onset entry; they are dropped again without want_y)
+            self._add_onsets(results, [r and r["y"] for r in results])
+            if not want_y:
+                for i in live:
+                    results[i]["y"] = None
         return (results, bufs, off, live) if _concatenated else results
 
     def open_stream(self, max_seconds=600.0, rake_sensitivity=0.6):
@@ -181,7 +215,8 @@ class AegisEngine:
         for audio_to_midi_batch, plus start_time / end_time and want_y."""
         got = self.analyze_files(paths, turbo_mode=kwargs.get("turbo_mode", False),
                                  rake_sensitivity=kwargs.get("rake_sensitivity", 0.6), start_time=kwargs.get("start_time", 0),
-                                 end_time=kwargs.get("end_time", None), want_y=kwargs.pop("want_y", True), _concatenated=True)
+                                 end_time=kwargs.get("end_time", None), want_y=kwargs.pop("want_y", True),
+                                 onsets=kwargs.get("onsets", False), _concatenated=True)
         return self._events_batch(len(paths), got, want_midi, kwargs)
 
     def audio_to_midi_batch(self, clips, want_midi=True, **kwargs):
@@ -189,7 +224,8 @@ class AegisEngine:
         for every clip (aegis_engine.py:41-181) as ONE analysis batch and ONE batched event extraction / MIDI rendering
         (C++, clips in parallel).  Empty clips give (None, [], None).  kwargs as for both reference methods."""
         turbo = kwargs.get("turbo_mode", False)
-        got = self.analyze_arrays(clips, turbo_mode=turbo, rake_sensitivity=kwargs.get("rake_sensitivity", 0.6), _concatenated=True)
+        got = self.analyze_arrays(clips, turbo_mode=turbo, rake_sensitivity=kwargs.get("rake_sensitivity", 0.6),
+                                  onsets=kwargs.get("onsets", False), _concatenated=True)
         return self._events_batch(len(clips), got, want_midi, kwargs)
 
     def _events_batch(self, n, got, want_midi, kwargs):
@@ -216,13 +252,18 @@ class AegisEngine:
             if self._freqs is None:
                 self._freqs = self.handle.table("freqs")
             grid = dict(pitch_bin=bufs["pitch_bin"], freqs=self._freqs)
+        split = bool(kwargs.get("split_on_onsets", False))
         res = events_native.extract_batch(off, bufs["rake_mask"], bufs["f0"], bufs["voiced_flag"], bufs["voiced_prob"], bufs["rms"],
                                           self.sr, self.hop_length, kwargs.get("confidence_threshold", 0.70),
-                                          want_midi=want_midi, **grid, **smf_kw, **passthrough)
-        per, bl = res if want_midi else (res, None)
+                                          want_midi=want_midi and not split, **grid, **smf_kw, **passthrough)
+        per, bl = res if (want_midi and not split) else (res, None)
         for j, i in enumerate(live):
             events[i] = per[j]
-            if want_midi:
+            if split:           # a post-pass on the finished list; the bytes come from the split list
+                events[i] = self._split_on_onsets(per[j], raws[i], kwargs)
+                if want_midi:
+                    blobs[i] = smf.render(events[i], self.sr, self.hop_length, **smf_kw)
+            elif want_midi:
                 blobs[i] = bl[j]
         return raws, events, blobs
 
@@ -235,9 +276,13 @@ class AegisEngine:
         passthrough = {k: v for k, v in kwargs.items() if k not in _ENGINE_ONLY_KWARGS + ("midi_program",)}
         smf_kw = dict(midi_program=kwargs.get("midi_program", 27), vibrato_rate=kwargs.get("vibrato_rate", 5.0),
                       vibrato_depth=kwargs.get("vibrato_depth", 0.3))
+        split = bool(kwargs.get("split_on_onsets", False))
         res = events_native.extract_batch([0, n], rake_mask, f0, voiced_flag, voiced_probs, rms, self.sr, self.hop_length,
-                                          kwargs.get("confidence_threshold", 0.70), want_midi=bool(output_mid), **smf_kw,
+                                          kwargs.get("confidence_threshold", 0.70), want_midi=bool(output_mid) and not split, **smf_kw,
                                           **passthrough)
+        if split:               # a post-pass on the finished list; the bytes come from the split list
+            events = self._split_on_onsets(res[0], raw_data, kwargs)
+            res = ([events], [smf.render(events, self.sr, self.hop_length, **smf_kw)]) if output_mid else [events]
         if output_mid:
             events, blob = res[0][0], res[1][0]
             if hasattr(output_mid, "write"):
@@ -286,8 +331,13 @@ class AegisEngine:
         rms = h.analyze_batch(batch, stages=_lib.STAGE_RMS, check_finite=True)
         for i, c, r in zip(live, cands, rms):
             raws[i] = {"cands": c, "rms": r["rms"], "y": clips[i]}
+        if kw.get("onsets", False):
+            self._add_onsets(raws, clips)
+        for i, c, r in zip(live, cands, rms):
             if want_events:
                 events[i] = polyphonic.get_midi_events_polyphonic(c, r["rms"], self.sr, self.hop_length, **kw)
+                if kw.get("split_on_onsets", False):
+                    events[i] = self._split_on_onsets(events[i], raws[i], kw)
                 if want_midi:
                     blobs[i] = smf.render(events[i], self.sr, self.hop_length, midi_program=kw.get("midi_program", 27),
                                           vibrato_rate=kw.get("vibrato_rate", 5.0), vibrato_depth=kw.get("vibrato_depth", 0.3))
@@ -298,6 +348,8 @@ class AegisEngine:
         or a file-like object through the engine's writer."""
         from . import polyphonic
         events = polyphonic.get_midi_events_polyphonic(raw["cands"], raw["rms"], self.sr, self.hop_length, **kw)
+        if kw.get("split_on_onsets", False):
+            events = self._split_on_onsets(events, raw, kw)
         if output_mid:
             blob = smf.render(events, self.sr, self.hop_length, midi_program=kw.get("midi_program", 27),
                               vibrato_rate=kw.get("vibrato_rate", 5.0), vibrato_depth=kw.get("vibrato_depth", 0.3))
