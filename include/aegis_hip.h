@@ -136,7 +136,8 @@ int aegis_analyze_batch_device(aegis_handle *h, const float *d_pcm, const int64_
  * aegis_analyze_batch do), and one kernel per chunk decodes, mixes down and resamples them into the PCM the analysis
  * reads; the float32 result is bit for bit what the host loader returns:
  *   u8 (v - 128) / 128, s16 v / 32768, s24 double(v) / 2^23, s32 double(v) / 2^31 (rounded to float32), f32 as stored;
- *   the channel mean in NumPy's float32 order (2..7 channels summed in order, 8 as a pairwise tree), then / channels;
+ *   the channel mean in NumPy's float32 order (2..7 channels summed in order, 8 as a pairwise tree, the sum added to
+ *   +0 as NumPy's reduction starts there: frames of nothing but -0.0 average to +0.0), then / channels;
  *   the polyphase FIR in scipy's tap order, a float32 multiply and a float32 add per tap, ceil(n * sr_out / sr_in)
  *   samples (those past scipy's own ceil(n * up / down) are 0). */
 #define AEGIS_PCM_U8 1
@@ -166,6 +167,11 @@ int64_t aegis_pcm_samples_for(const aegis_handle *h, const aegis_pcm_clip *clip)
 /* The built-in low-pass of a rate pair in lowest terms (host only, no handle): 2 * 10 * max(up, down) + 1 float32 taps,
  * within one float32 ulp of scipy's.  Returns the count and copies min(count, cap) of them. */
 int64_t aegis_resample_taps(int32_t up, int32_t down, float *dst, int64_t cap);
+/* The path the decode kernel takes for a clip's format, channels, rate and taps at a handle rate (host only, no handle;
+ * data and n_frames are not read): out = { up, down, P (taps per output phase), rm (outputs dropped at the front),
+ * tile (output samples per workgroup), slabs (LDS slabs a full tile's input window is walked in) }; up = down = P = 1
+ * at the handle's own rate.  AEGIS_ERR_INVALID for a clip aegis_analyze_pcm rejects. */
+int aegis_pcm_geometry(int32_t handle_rate, const aegis_pcm_clip *clip, int64_t *out /* [6] */);
 
 /* AegisEngine.detect_rake_patterns(S_dB) (aegis_engine.py:38-39 -> vision.py:3-38) on a
  * caller-supplied dB image in host memory, [n_mels, n_frames] C-order; mask_out is

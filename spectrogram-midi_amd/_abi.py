@@ -127,6 +127,7 @@ PROTOTYPES = {
     "aegis_analyze_pcm": (C.c_int, [_P, C.POINTER(PcmClip), _I32, _F64, _U32, _OUT, _P]),
     "aegis_pcm_samples_for": (_I64, [_P, C.POINTER(PcmClip)]),
     "aegis_resample_taps": (_I64, [_I32, _I32, _P, _I64]),
+    "aegis_pcm_geometry": (C.c_int, [_I32, C.POINTER(PcmClip), _PI64]),
     "aegis_rake_patterns": (C.c_int, [_P, _P, _I32, _I64, _F64, _P]),
     "aegis_cqt": (C.c_int, [_P, _PP, _PI64, _I32, _I32, _I32, _F64, _F64, _P]),
     "aegis_cqt_device": (C.c_int, [_P, _P, _PI64, _I32, _I32, _I32, _F64, _F64, _P, _P, _I32]),

@@ -283,19 +283,25 @@ class Handle:
             return res, bufs, _marshal.offsets(frames)
         return res
 
-    def pcm_clips(self, sources, builtin_taps=False):
+    def pcm_clips(self, sources, builtin_taps=False, taps=None):
         """aegis_pcm_clip array for sources (audio_io.PcmSource: raw frames as a uint8 array, format, channels, rate);
-        scipy's own taps for every rate pair unless builtin_taps.  Returns (array, objects to keep alive)."""
+        scipy's own taps for every rate pair unless builtin_taps.  taps: {file rate: odd-length float32 array}, the
+        caller's own low-pass (already times up) for the files of that rate, handed on as aegis_pcm_clip.taps.
+        Returns (array, objects to keep alive)."""
         from . import audio_io
         arr = (PcmClip * max(len(sources), 1))()
-        keep, taps = [], {}
+        keep = []
+        taps = {int(r): np.ascontiguousarray(h, dtype=np.float32) for r, h in (taps or {}).items()}
+        for r, h in taps.items():
+            if h.ndim != 1 or not len(h) & 1:
+                raise ValueError(f"taps for {r} Hz: an odd-length 1-D array is needed")
         for i, src in enumerate(sources):
             data = np.ascontiguousarray(src.data, dtype=np.uint8)
             keep.append(data)
             fb = audio_io.PCM_WIDTH[src.format] * src.channels
             c = arr[i]
             c.data, c.n_frames, c.format, c.channels, c.sample_rate = data.ctypes.data, len(data) // fb, src.format, src.channels, src.sample_rate
-            if src.sample_rate != self.sr and not builtin_taps:
+            if src.sample_rate != self.sr and (not builtin_taps or src.sample_rate in taps):
                 if src.sample_rate not in taps:
                     taps[src.sample_rate] = audio_io.resample_taps(src.sample_rate, self.sr)[2]
                 h = taps[src.sample_rate]
@@ -311,15 +317,15 @@ class Handle:
         return n
 
     def analyze_pcm(self, sources, rake_sensitivity=0.6, stages=STAGE_ALL, want_sdb=True, check_finite=False, f0_zero=False,
-                    views=False, concatenated=False, want_col_means=False, want_y=True, builtin_taps=False):
+                    views=False, concatenated=False, want_col_means=False, want_y=True, builtin_taps=False, taps=None):
         """analyze_batch on WAV sample data decoded, mixed down and resampled to the handle's rate on the device
-        (aegis_analyze_pcm).  sources: audio_io.PcmSource tuples.  Each per-clip dict also carries "y", the float32
-        samples the analysis saw (None with want_y=False: then they do not come back from the device).  stages=0 decodes
-        only: the dicts hold "y" alone."""
+        (aegis_analyze_pcm).  sources: audio_io.PcmSource tuples; taps: see pcm_clips.  Each per-clip dict also carries
+        "y", the float32 samples the analysis saw (None with want_y=False: then they do not come back from the device).
+        stages=0 decodes only: the dicts hold "y" alone."""
         n = len(sources)
         if n == 0:
             return ([], {}, np.zeros(1, np.int64)) if concatenated else []
-        arr, keep = self.pcm_clips(sources, builtin_taps)
+        arr, keep = self.pcm_clips(sources, builtin_taps, taps)
         lens = [int(self.lib.aegis_pcm_samples_for(self._h, C.byref(arr[i]))) for i in range(n)]
         if min(lens) < 0:
             raise AegisError(ERR_INVALID, "invalid PCM clip")
@@ -792,6 +798,22 @@ class Handle:
         self._check(self.lib.aegis_analyze_batch_device(
             self._h, C.c_void_p(int(d_pcm_ptr)), off.ctypes.data_as(C.POINTER(C.c_int64)), len(off) - 1,
             float(rake_sensitivity), int(stages), C.byref(out), C.c_void_p(stream or 0), 1 if sync else 0))
+
+
+def pcm_geometry(handle_rate, source, taps=None):
+    """aegis_pcm_geometry: the decode kernel's path for a source's format, channels and rate at a handle rate, as the
+    library's own layout and tile choice give it (host code, no handle, no GPU).  source: audio_io.PcmSource (its data is
+    not read); taps: the caller's low-pass for it, None = the built-in design.  -> dict up, down, P, rm, tile, slabs."""
+    c = PcmClip()
+    c.format, c.channels, c.sample_rate = int(source.format), int(source.channels), int(source.sample_rate)
+    if taps is not None:
+        taps = np.ascontiguousarray(taps, dtype=np.float32)
+        c.n_taps, c.taps = len(taps), taps.ctypes.data
+    out = np.zeros(6, np.int64)
+    rc = load().aegis_pcm_geometry(int(handle_rate), C.byref(c), out.ctypes.data_as(C.POINTER(C.c_int64)))
+    if rc != OK:
+        raise AegisError(rc, "invalid PCM clip")
+    return dict(zip(("up", "down", "P", "rm", "tile", "slabs"), (int(v) for v in out)))
 
 
 def resample_taps(up, down):

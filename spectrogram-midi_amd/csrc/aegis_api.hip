@@ -847,6 +847,28 @@ int64_t aegis_resample_taps(int32_t up, int32_t down, float *dst, int64_t cap) {
     } catch (...) { return AEGIS_ERR_NOMEM; }
 }
 
+int aegis_pcm_geometry(int32_t handle_rate, const aegis_pcm_clip *clip, int64_t *out) {
+    try {
+    if (handle_rate <= 0 || !clip || !out) return AEGIS_ERR_INVALID;
+    aegis_pcm_clip a = *clip;
+    a.n_frames = 0; a.data = nullptr;              // the geometry is the format's and the rate pair's, not the length's
+    if (pcm_samples(handle_rate, a, nullptr) < 0) return AEGIS_ERR_INVALID;
+    PcmClipDev c{};
+    c.fmt = a.format; c.ch = a.channels;
+    c.up = 1; c.down = 1; c.P = 1; c.rm = 0;
+    if (a.sample_rate != handle_rate) {
+        const int32_t g = std::gcd(a.sample_rate, handle_rate);
+        c.up = handle_rate / g; c.down = a.sample_rate / g;
+        const std::vector<float> own = a.taps ? std::vector<float>(a.taps, a.taps + a.n_taps) : pcm_builtin_taps(c.up, c.down);
+        std::vector<float> htf;
+        c.P = pcm_filter_layout(own.data(), (int)own.size(), c.up, c.down, htf, &c.rm);
+    }
+    c.tile = pcm_tile(c);
+    out[0] = c.up; out[1] = c.down; out[2] = c.P; out[3] = c.rm; out[4] = c.tile; out[5] = pcm_slabs_per_tile(c, c.tile);
+    return AEGIS_OK;
+    } catch (...) { return AEGIS_ERR_NOMEM; }
+}
+
 int aegis_analyze_pcm(aegis_handle *h, const aegis_pcm_clip *clips, int32_t n_clips, double rake_sensitivity, uint32_t stages,
                       aegis_outputs *out, float *y_out) {
     try {

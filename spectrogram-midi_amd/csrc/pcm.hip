@@ -12,16 +12,12 @@
 #include "pcm.h"
 
 #include <algorithm>
-#include <cmath>
 
 namespace aegis {
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kRawBytes = 32768;           // raw-byte slab in LDS
-constexpr int kWin = 4096;                 // decoded frames of a slab
-constexpr int kOutPerThread = 4;           // outputs per thread of a resampling tile (tile <= 1024)
+constexpr int kThreads = kPcmThreads, kRawBytes = kPcmRawBytes, kWin = kPcmWin, kOutPerThread = kPcmOutPerThread;   // pcm_host.h
 
 __device__ __forceinline__ float pcm_sample(const uint32_t *sraw, int byte, int fmt) {
     const int w = byte >> 2;
@@ -36,7 +32,7 @@ __device__ __forceinline__ float pcm_sample(const uint32_t *sraw, int byte, int 
     }
 }
 
-// x.reshape(-1, ch).mean(axis=1) in float32: 2..7 channels summed in channel order, 8 as NumPy's pairwise block
+// x.reshape(-1, ch).mean(axis=1) in float32: 2..7 channels summed in channel order, 8 as NumPy's pairwise block, onto +0
 __device__ __forceinline__ float pcm_frame(const uint32_t *sraw, int byte, int fmt, int ch, int width) {
     float x[8];
 #pragma unroll
@@ -51,7 +47,7 @@ __device__ __forceinline__ float pcm_frame(const uint32_t *sraw, int byte, int f
         for (int c = 1; c < 7; ++c)
             if (c < ch) s = s + x[c];
     }
-    return s / (float)ch;
+    return (0.0f + s) / (float)ch;         // NumPy's reduction starts at +0: a frame of nothing but -0.0 has the mean +0.0
 }
 
 // bytes [b0, b1) of a clip (b1 - b0 <= kRawBytes - 32) into sraw with 16-byte loads; returns the LDS byte of b0
@@ -141,69 +137,6 @@ void launch_pcm_decode(const uint8_t *raw, const PcmClipDev *clips, const PcmRan
     if (n_ranges <= 0 || n_tiles <= 0) return;
     hipLaunchKernelGGL(pcm_decode_resample_kernel, dim3((unsigned)n_tiles), dim3(kThreads), 0, s, raw, clips, ranges, n_ranges,
                        taps, pcm);
-}
-
-int pcm_tile(const PcmClipDev &c) {
-    if (c.up == c.down) return 2048;
-    const int fb = (c.fmt == 1 ? 1 : c.fmt == 2 ? 2 : c.fmt == 3 ? 3 : 4) * c.ch;
-    const int64_t slab = std::min(kWin, (kRawBytes - 32) / fb);
-    int tile = kThreads * kOutPerThread;   // the largest tile whose input window fits one slab
-    while (tile > kThreads && (int64_t)(tile - 1) * c.down / c.up + c.P + 1 > slab) tile >>= 1;
-    return tile;
-}
-
-int64_t pcm_inputs_needed(const PcmClipDev &c, int64_t n_out) {
-    if (n_out <= 0) return 0;
-    if (c.up == c.down) return std::min(n_out, c.n_in);
-    const int64_t j = std::min(n_out, c.n_res) - 1;
-    if (j < 0) return 0;
-    return std::min<int64_t>(c.n_in, ((j + c.rm) * c.down) / c.up + 1);
-}
-
-int pcm_filter_layout(const float *h, int n_taps, int up, int down, std::vector<float> &htf, int64_t *rm) {
-    const int64_t half = (n_taps - 1) / 2;
-    const int64_t pre = down - half % down;
-    const int64_t L = pre + n_taps;
-    const int64_t P = (L + up - 1) / up;
-    std::vector<float> hp((size_t)(P * up), 0.0f);
-    for (int i = 0; i < n_taps; ++i) hp[(size_t)(pre + i)] = h[i];
-    htf.assign((size_t)(P * up), 0.0f);
-    for (int t = 0; t < up; ++t)
-        for (int64_t k = 0; k < P; ++k) htf[(size_t)(t * P + k)] = hp[(size_t)((P - 1 - k) * up + t)];
-    *rm = (half + pre) / down;
-    return (int)P;
-}
-
-static double bessel_i0(double x) {       // power series: sum ((x/2)^k / k!)^2, to the last bit for the Kaiser beta of 5
-    double term = 1.0, sum = 1.0;
-    const double q = 0.25 * x * x;
-    for (int k = 1; k < 200; ++k) {
-        term *= q / ((double)k * (double)k);
-        sum += term;
-        if (term < sum * 1e-18) break;
-    }
-    return sum;
-}
-
-std::vector<float> pcm_builtin_taps(int up, int down) {
-    const int mr = std::max(up, down);
-    const int64_t n = 2 * 10 * (int64_t)mr + 1;
-    const double cutoff = 1.0 / mr, alpha = 0.5 * (double)(n - 1), beta = 5.0, pi = 3.14159265358979323846;
-    std::vector<double> h((size_t)n);
-    double sum = 0.0;
-    const double i0b = bessel_i0(beta);
-    for (int64_t i = 0; i < n; ++i) {
-        const double m = (double)i - alpha;
-        const double x = cutoff * m;
-        const double sinc = x == 0.0 ? 1.0 : std::sin(pi * x) / (pi * x);
-        const double r = m / alpha;
-        const double w = bessel_i0(beta * std::sqrt(std::max(0.0, 1.0 - r * r))) / i0b;
-        h[(size_t)i] = cutoff * sinc * w;
-        sum += h[(size_t)i];
-    }
-    std::vector<float> out((size_t)n);
-    for (int64_t i = 0; i < n; ++i) out[(size_t)i] = (float)(h[(size_t)i] / sum) * (float)up;
-    return out;
 }
 
 }  // namespace aegis

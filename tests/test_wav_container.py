@@ -1,5 +1,6 @@
 """The RIFF/WAVE reader and the host decoder (audio_io), the resampler's arithmetic as the device kernel runs it
-(csrc/pcm.hip: this file's emulate() is its specification), the built-in low-pass and the output lengths.  CPU only."""
+(csrc/pcm.hip: tools/pcm_restated.py's emulate() is its specification), the built-in low-pass and the output lengths.
+CPU only."""
 import io
 import math
 import struct
@@ -11,6 +12,7 @@ import scipy.signal
 
 from spectrogram_midi_amd import _lib, audio_io
 from tools import wavgen
+from tools.pcm_restated import emulate, mean_emulation
 
 FORMATS = (wavgen.PCM_U8, wavgen.PCM_S16, wavgen.PCM_S24, wavgen.PCM_S32, wavgen.PCM_F32)
 RATIOS = ((147, 160), (160, 147), (1, 2), (2, 1), (441, 80), (147, 320))     # up / down
@@ -117,51 +119,12 @@ def test_parser_rejections():
         audio_io.load_pcm(io.BytesIO(pcm9), offset=-0.5)
 
 
-def mean_emulation(x):
-    """The device kernel's channel mean: 2..7 channels in channel order, 8 as NumPy's pairwise block, then / ch."""
-    ch = x.shape[1]
-    if ch == 1:
-        return x[:, 0]
-    if ch == 8:
-        s = ((x[:, 0] + x[:, 1]) + (x[:, 2] + x[:, 3])) + ((x[:, 4] + x[:, 5]) + (x[:, 6] + x[:, 7]))
-    else:
-        s = x[:, 0].copy()
-        for c in range(1, ch):
-            s = s + x[:, c]
-    return s / np.float32(ch)
-
-
 @pytest.mark.parametrize("ch", range(2, 9))
 def test_channel_mean_order(ch):
     rng = np.random.default_rng(ch)
     n = 200_000
     x = (rng.standard_normal((n, ch)) * 10.0 ** rng.integers(-8, 8, (n, ch))).astype(np.float32)
     np.testing.assert_array_equal(mean_emulation(x), audio_io.decode(x.tobytes(), audio_io.PCM_F32, ch))
-
-
-def emulate(x, up, down, h):
-    """scipy.signal.resample_poly(x, up, down) on float32 as pcm_decode_resample_kernel computes it: the filter h
-    (after `h *= up`) behind down - half % down zeros, stored phase-major and flipped (htf), and for every output j
-    the tap loop k = 0 .. P-1 over inputs i0 - P + 1 + k, one float32 multiply and one float32 add per tap."""
-    x = np.asarray(x, np.float32)
-    half = (len(h) - 1) // 2
-    pre = down - half % down
-    hp = np.concatenate([np.zeros(pre, np.float32), np.asarray(h, np.float32)])
-    P = -(-len(hp) // up)
-    hp = np.pad(hp, (0, P * up - len(hp)))
-    htf = hp.reshape(P, up).T[:, ::-1].ravel()
-    rm = (half + pre) // down
-    n_res = (len(x) * up + down - 1) // down
-    j = np.arange(n_res, dtype=np.int64)
-    q = (j + rm) * down
-    i0, t = q // up, q % up
-    acc = np.zeros(n_res, np.float32)
-    for k in range(P):
-        i = i0 - P + 1 + k
-        ok = (i >= 0) & (i < len(x))
-        term = x[np.clip(i, 0, len(x) - 1)] * htf[t * P + k]
-        acc = acc + np.where(ok, term, np.float32(0))
-    return acc
 
 
 @pytest.mark.parametrize("up,down", RATIOS)
