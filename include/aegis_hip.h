@@ -632,6 +632,61 @@ int aegis_analyze_onsets(aegis_handle *h, const float *const *pcm, const int64_t
                          const aegis_onset_params *p, float *env_out /* NULL ok */, uint8_t *onset_mask /* NULL ok */,
                          int32_t *onset_back /* NULL ok */, int64_t *n_onsets);
 
+/* --- Tempo and beat tracking behind the onset envelope -----------------------------------------------------------------
+ * The reference has neither.  The semantics are librosa 0.10's feature.tempogram / beat.tempo /
+ * beat.beat_track, written from memory of upstream 0.10.0 (it could not be run where this was written), in a fixed
+ * arithmetic order: csrc/beat.h states them once and is the contract, DESIGN.md 3.18 explains them, tools/beat_restated.py
+ * restates them, and host and device give that restatement's bits.
+ *   tempogram mean  the envelope padded by win_length / 2 linear-ramp values on either side, Hann-windowed frames of
+ *                   win_length, the autocorrelation of every frame in float32 (direct form, terms ascending), divided by
+ *                   lag 0; tg = the mean over the clip's frames in float64 (256-frame tiles, in order).  double [W] a clip.
+ *   tempo           score[l] = log1p(1e6 tg[l]) - 0.5 ((log2 bpm[l] - log2 start_bpm) / std_bpm)^2 over the lags l >= 1 with
+ *                   bpm[l] = 60 sr / (hop l) < max_tempo; period = the first arg-max, the tempo is bpm[period].
+ *   beat tracker    ls = the envelope divided by its standard deviation (ddof 1), convolved with exp(-0.5 (32 j / period)^2);
+ *                   cum[i] = ls[i] + max over k of (-tightness log(-wv[k] / period)^2 + cum[i + wv[k]]), wv = -2 period ..
+ *                   -rint(period / 2), the first maximum; back[i] = the frame that maximum came from, -1 until ls reaches
+ *                   0.01 max ls.  Tail (host): the last beat is the largest local maximum of cum above half the median of
+ *                   the local maxima, the beats are the back chain from it, trimmed where the smoothed ls at the beats
+ *                   falls below half its rms (the last valid beat is dropped, as librosa 0.10.0 writes it).
+ * A clip with fewer than 2 frames or no non-zero envelope value: tempo 0.0 and no beats (librosa's early return).  A
+ * constant envelope (standard deviation 0, where librosa divides by zero): no beats, the tempo is still reported.
+ * Every field of aegis_beat_params has a "take the default" value: -1 (or 0) for win_length, -1 for trim, 0 for the
+ * doubles.  Defaults: win_length int(8.0 sr / hop) (689 at 44.1 kHz / 512), start_bpm 120, std_bpm 1.0, max_tempo 320,
+ * tightness 100, trim 1, bpm 0 = estimate it per clip (otherwise period = rint(60 sr / (hop bpm)), which must be 2..1023).
+ * p == NULL: every default.
+ *   aegis_tempo          envelopes from host memory (float32, clip after clip, n_frames[c] each).  tg_out NULL or double
+ *                        [n_clips * W]; bpm_out double [n_clips]; period_out int32 [n_clips].  params.bpm is not read.  A
+ *                        clip of 0 frames has tg = 0 and takes the prior's tempo.
+ *   aegis_beat_track     envelopes from host memory.  bpm_in NULL (params.bpm, or the estimate per clip) or double
+ *                        [n_clips].  beat_mask uint8 [F_total], n_beats int64 [n_clips], bpm_out double [n_clips]; the
+ *                        probes ls_out / cum_out double [F_total] and back_out int32 [F_total] may each be NULL.
+ *   aegis_beat_tables    the host tables of a period 2..1023 and a tightness > 0, no handle: g_out double [2 period + 1],
+ *                        tx_out double [K], K = 2 period - rint(period / 2) + 1 <= 1535.  Returns K or AEGIS_ERR_INVALID.
+ *   aegis_analyze_beats  PCM as aegis_analyze_batch takes it (a clip without samples is one frame of silence): the handle's
+ *                        mel stage, the onset-envelope kernel (onset_params NULL: its defaults) and the beat kernels on the
+ *                        device; only the envelope (env_out NULL or float32 [F_total]), the masks and the tempi leave it,
+ *                        apart from the tail's traffic (ls, cum, back: 20 bytes a frame).
+ * A clip's results depend on that clip alone: the same bits alone, batched, reversed.
+ * AEGIS_ERR_INVALID with a message, before the device is looked at: win_length outside 4..1024 (a default above 1024 says to
+ * pass win_length), trim not 0 / 1, a double that is negative or not finite, a bpm whose period lies outside 2..1023, NULL
+ * inputs or outputs; after the tempogram: a clip with no lag below max_tempo or an estimated period below 2.  A device = -1
+ * handle rejects the same requests and answers AEGIS_ERR_DEVICE to a valid one.
+ * Kernel time: "beat_tempogram", "beat_score" and "beat_dp" of aegis_last_kernel_ms.  Blocking; host pointers. */
+typedef struct aegis_beat_params {
+    int32_t win_length;
+    int32_t trim;
+    double start_bpm, std_bpm, max_tempo, tightness, bpm;
+} aegis_beat_params;
+int aegis_tempo(aegis_handle *h, const float *env, const int64_t *n_frames, int32_t n_clips, const aegis_beat_params *p,
+                double *tg_out /* NULL ok */, double *bpm_out, int32_t *period_out);
+int aegis_beat_track(aegis_handle *h, const float *env, const int64_t *n_frames, int32_t n_clips, const aegis_beat_params *p,
+                     const double *bpm_in /* NULL ok */, uint8_t *beat_mask, int64_t *n_beats, double *bpm_out,
+                     double *ls_out /* NULL ok */, double *cum_out /* NULL ok */, int32_t *back_out /* NULL ok */);
+int aegis_beat_tables(int32_t period, double tightness, double *g_out, double *tx_out);
+int aegis_analyze_beats(aegis_handle *h, const float *const *pcm, const int64_t *n_samples, int32_t n_clips,
+                        const aegis_onset_params *onset_params, const aegis_beat_params *beat_params, float *env_out /* NULL ok */,
+                        uint8_t *beat_mask, int64_t *n_beats, double *bpm_out);
+
 /* --- Effect chain: distortion, reverb, delay, chorus (aegis_engine_core/effect_learning_loop.py:56-275) ----------
  * The reference's pure-NumPy effects, each ending in a whole-clip normalisation, which its learning loop
  * (effect_learning_loop.py:489-725) puts between the synthesiser and the engine.  Float64 throughout.

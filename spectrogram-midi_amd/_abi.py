@@ -100,6 +100,11 @@ class OnsetParams(C.Structure):
                 ("post_avg", _I32), ("wait", _I32), ("normalize", _I32), ("reserved", _I32), ("delta", _F64)]
 
 
+class BeatParams(C.Structure):
+    _fields_ = [("win_length", _I32), ("trim", _I32), ("start_bpm", _F64), ("std_bpm", _F64), ("max_tempo", _F64),
+                ("tightness", _F64), ("bpm", _F64)]
+
+
 class Effect(C.Structure):
     _fields_ = [("kind", _I32), ("n_ir", _I32), ("p0", _F64), ("p1", _F64), ("ir", _P)]
 
@@ -109,10 +114,10 @@ STRUCTS = {"aegis_config": Config, "aegis_outputs": Outputs, "aegis_pcm_clip": P
            "aegis_stream_commit": StreamCommit, "aegis_event": Event, "aegis_event_params": EventParams, "aegis_run_fit": RunFit,
            "aegis_event_batch": EventBatch, "aegis_synth_note": SynthNote, "aegis_adsr_params": AdsrParams,
            "aegis_fit_note": FitNote, "aegis_verify_event": VerifyEvent, "aegis_salience_params": SalienceParams,
-           "aegis_onset_params": OnsetParams, "aegis_effect": Effect}
+           "aegis_onset_params": OnsetParams, "aegis_beat_params": BeatParams, "aegis_effect": Effect}
 
 _OUT, _ADSR, _SAL = C.POINTER(Outputs), C.POINTER(AdsrParams), C.POINTER(SalienceParams)
-_FRAMES, _ONS = C.POINTER(StreamFrames), C.POINTER(OnsetParams)
+_FRAMES, _ONS, _BEAT = C.POINTER(StreamFrames), C.POINTER(OnsetParams), C.POINTER(BeatParams)
 
 # every function the header declares, in its order: name -> (restype, argtypes).  Handles and plain arrays travel as void
 # pointers (NumPy hands over addresses); arrays the binding builds with ctypes are typed.
@@ -159,6 +164,10 @@ PROTOTYPES = {
     "aegis_onset_strength": (C.c_int, [_P, _P, _P, _I32, _I32, _ONS, _P]),
     "aegis_onset_detect": (C.c_int, [_P, _P, _P, _P, _I32, _ONS, _P, _P, _P]),
     "aegis_analyze_onsets": (C.c_int, [_P, _PP, _PI64, _I32, _ONS, _P, _P, _P, _P]),
+    "aegis_tempo": (C.c_int, [_P, _P, _P, _I32, _BEAT, _P, _P, _P]),
+    "aegis_beat_track": (C.c_int, [_P, _P, _P, _I32, _BEAT, _P, _P, _P, _P, _P, _P, _P]),
+    "aegis_beat_tables": (C.c_int, [_I32, _F64, _P, _P]),
+    "aegis_analyze_beats": (C.c_int, [_P, _PP, _PI64, _I32, _ONS, _BEAT, _P, _P, _P, _P]),
     "aegis_reverb_ir": (_I64, [_F64, _I32, _P, _I64]),
     "aegis_effects": (C.c_int, [_P, _I32, _I32, _PP, _I32, _P, C.POINTER(Effect), _P, _PP, _PP]),
     "aegis_get_table": (_I64, [_P, _S, _P, _I64]),

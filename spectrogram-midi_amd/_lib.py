@@ -592,6 +592,87 @@ class Handle:
                                                   back.ctypes.data if back is not None else None, counts.ctypes.data))
         return self._onset_split(frames, env, mask, back, counts)
 
+    @staticmethod
+    def beat_params(win_length=-1, trim=-1, start_bpm=0.0, std_bpm=0.0, max_tempo=0.0, tightness=0.0, bpm=0.0):
+        """aegis_beat_params; every argument left at its default (None too) takes the library's.  The library validates."""
+        d = [0.0 if a is None else float(a) for a in (start_bpm, std_bpm, max_tempo, tightness, bpm)]
+        return BeatParams(-1 if win_length is None else int(win_length), -1 if trim is None else int(trim), *d)
+
+    def beat_win_length(self, params=None):
+        """The tempogram's window in frames: params' own, or the library's default int(8.0 * sr / hop)."""
+        w = params.win_length if params is not None else -1
+        return int(w) if w > 0 else int(8.0 * self.sr / self.hop)
+
+    @staticmethod
+    def _beat_split(frames, mask, counts):
+        res, o = [], 0
+        for c, Fc in enumerate(frames):
+            b = np.flatnonzero(mask[o:o + Fc])
+            if len(b) != counts[c]:
+                raise AegisError(ERR_DEVICE, f"clip {c}: n_beats says {int(counts[c])}, the mask holds {len(b)}")
+            res.append(b)
+            o += Fc
+        return res
+
+    def tempo(self, envelopes, params=None, want_tg=False):
+        """aegis_tempo: caller envelopes (float32 [F_c] each) in ONE device call -> per clip (bpm, period), or
+        (bpm, period, tg float64 [W]) with want_tg."""
+        envs = [np.ascontiguousarray(e, dtype=np.float32).ravel() for e in envelopes]
+        if not envs:
+            return []
+        W, n = self.beat_win_length(params), len(envs)
+        flat, nf = _marshal.concat(envs, np.float32), np.asarray([len(e) for e in envs], np.int64)
+        tg = np.zeros(n * W, np.float64) if want_tg else None
+        bpm, period = np.zeros(n, np.float64), np.zeros(n, np.int32)
+        self._check(self.lib.aegis_tempo(self._h, flat.ctypes.data, nf.ctypes.data, n, C.byref(params) if params is not None else None,
+                                         tg.ctypes.data if want_tg else None, bpm.ctypes.data, period.ctypes.data))
+        return [(float(bpm[c]), int(period[c])) + ((tg[c * W:(c + 1) * W].copy(),) if want_tg else ()) for c in range(n)]
+
+    def beat_track(self, envelopes, params=None, bpm=None, probes=False):
+        """aegis_beat_track: caller envelopes in ONE device call -> per clip (bpm, beat frames int64), or with probes
+        (bpm, beat frames, ls float64 [F_c], cum float64 [F_c], back int32 [F_c]).  bpm: None (params' bpm, or the estimate
+        per clip) or one tempo per clip."""
+        envs = [np.ascontiguousarray(e, dtype=np.float32).ravel() for e in envelopes]
+        if not envs:
+            return []
+        n, frames = len(envs), [len(e) for e in envs]
+        F = sum(frames)
+        flat, nf = _marshal.concat(envs, np.float32), np.asarray(frames, np.int64)
+        bin_ = None
+        if bpm is not None:
+            bin_ = np.ascontiguousarray(bpm, dtype=np.float64).ravel()
+            if len(bin_) != n:
+                raise ValueError("one bpm per envelope")
+        mask, counts, out = np.zeros(F, np.uint8), np.zeros(n, np.int64), np.zeros(n, np.float64)
+        ls, cum, back = (np.zeros(F, np.float64), np.zeros(F, np.float64), np.zeros(F, np.int32)) if probes else (None, None, None)
+        self._check(self.lib.aegis_beat_track(self._h, flat.ctypes.data, nf.ctypes.data, n, C.byref(params) if params is not None else None,
+                                              bin_.ctypes.data if bin_ is not None else None, mask.ctypes.data, counts.ctypes.data,
+                                              out.ctypes.data, ls.ctypes.data if probes else None, cum.ctypes.data if probes else None,
+                                              back.ctypes.data if probes else None))
+        beats = self._beat_split(frames, mask, counts)
+        off = _marshal.offsets(frames)
+        return [(float(out[c]), beats[c]) + ((ls[off[c]:off[c + 1]].copy(), cum[off[c]:off[c + 1]].copy(), back[off[c]:off[c + 1]].copy())
+                                             if probes else ()) for c in range(n)]
+
+    def analyze_beats(self, clips, onset_params=None, beat_params=None, want_env=True):
+        """aegis_analyze_beats: the handle's mel stage, the onset envelope and the beat kernels on the device, ONE call for
+        the batch -> per clip (envelope float32 [F_c] or None, bpm, beat frames int64).  A clip without samples is one
+        frame of silence."""
+        clips, ptrs, lens = _marshal.clips(clips, np.float32)
+        n = len(clips)
+        if n == 0:
+            return []
+        frames = [self.frames_for(len(c)) for c in clips]
+        F = sum(frames)
+        env = np.zeros(F, np.float32) if want_env else None
+        mask, counts, bpm = np.zeros(F, np.uint8), np.zeros(n, np.int64), np.zeros(n, np.float64)
+        self._check(self.lib.aegis_analyze_beats(self._h, ptrs, lens, n, C.byref(onset_params) if onset_params is not None else None,
+                                                 C.byref(beat_params) if beat_params is not None else None,
+                                                 env.ctypes.data if want_env else None, mask.ctypes.data, counts.ctypes.data, bpm.ctypes.data))
+        beats = self._beat_split(frames, mask, counts)
+        off = _marshal.offsets(frames)
+        return [(env[off[c]:off[c + 1]].copy() if want_env else None, float(bpm[c]), beats[c]) for c in range(n)]
+
     def synth_parse_smf(self, midi_bytes, want_wheel=False):
         """aegis_synth_parse_smf: (notes in the reference's mix order as a SYNTH_NOTE_DTYPE array, mido's length in
         seconds) of a Standard MIDI File; ValueError for bytes that are not one (mido raises).  Host code.
@@ -827,6 +908,18 @@ def reverb_ir(room_size, sr):
     empty array where the reference's reverb is a copy."""
     return _marshal.sized(lambda dst, cap: load().aegis_reverb_ir(float(room_size), int(sr), dst, cap), np.float64,
                           lambda rc: AegisError(rc, "bad room size or sample rate"))
+
+
+def beat_tables(period, tightness=100.0):
+    """aegis_beat_tables (host code, no handle, no GPU): (g float64 [2 period + 1], tx float64 [K]) of a period 2..1023."""
+    period = int(period)
+    if not 2 <= period <= 1023:
+        raise ValueError("period must be 2..1023")
+    g, tx = np.zeros(2 * period + 1, np.float64), np.zeros(2 * period + 2, np.float64)
+    K = int(load().aegis_beat_tables(period, float(tightness), g.ctypes.data, tx.ctypes.data))
+    if K < 0:
+        raise AegisError(K, "aegis_beat_tables: a period 2..1023 and a tightness > 0 are needed")
+    return g, tx[:K].copy()
 
 
 def numpy_reverb_ir(room_size, sr):

@@ -16,6 +16,8 @@
 //                     salience.hip, the CQT in front of it through aegis_cqt.hip's cqt_host_locked)
 //   aegis_onset.hip   aegis_onset_strength, aegis_onset_detect, aegis_analyze_onsets (onset envelope and onset picking;
 //                     kernels in onset.hip, the mel stage in front of them through aegis_api.hip's mel_host_locked)
+//   aegis_beat.hip    aegis_tempo, aegis_beat_track, aegis_beat_tables, aegis_analyze_beats (tempogram mean, tempo, beat
+//                     tracker; kernels in beat.hip, the mel stage and onset.hip's envelope kernel in front of them)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -139,6 +141,9 @@ struct aegis_handle {
     std::map<int32_t, VerifyBank> vf_banks;
     DevBuf sl_mag, sl_foff, sl_img, sl_bin, sl_sal, sl_shift;   // aegis_salience / aegis_cqt_salience: caller magnitudes, frame offsets, image, candidates
     DevBuf on_img, on_foff, on_env, on_energy, on_x, on_mask, on_back, on_count;   // aegis_onset_* / aegis_analyze_onsets: caller images / envelopes, frame offsets, envelope, energy track, normalised envelope, results
+    // aegis_tempo / aegis_beat_track / aegis_analyze_beats: caller envelopes, frame and tile offsets, window, tile sums, tempogram means,
+    // moments, per-clip periods / table offsets / tables, local score, cumulative score, back links
+    DevBuf bt_env, bt_foff, bt_toff, bt_win, bt_parts, bt_tg, bt_stats, bt_period, bt_taboff, bt_tabs, bt_ls, bt_cum, bt_back;
     bool notefit_store = false;               // AEGIS_NOTEFIT_STORE=1 at create: every candidate rendered once into nf_sig and read by the frames instead of recomputed
     int32_t lag_stride = 0, yin_stride = 0, obs_stride = 0;
     aegis::CallPlan plan;                     // the last call's plan: its host arrays stay alive until the stream drained

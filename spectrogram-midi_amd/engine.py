@@ -13,12 +13,13 @@ import multiprocessing
 
 import numpy as np
 
-from . import _lib, audio_io, events_native, midi_logic, onsets as _onsets, smf
+from . import _lib, audio_io, beats as _beats, events_native, midi_logic, onsets as _onsets, smf
 from .convert import note_to_hz
 
 _FMIN, _FMAX = note_to_hz("E2"), note_to_hz("C6")
 _ENGINE_ONLY_KWARGS = ("confidence_threshold", "start_time", "end_time", "turbo_mode", "rake_sensitivity",
-                       "vibrato_rate", "vibrato_depth", "onsets", "split_on_onsets")
+                       "vibrato_rate", "vibrato_depth", "onsets", "split_on_onsets", "beats", "quantize_to_beats", "beat_subdivisions",
+                       "tempo_map")
 
 
 class AegisEngine:
@@ -92,13 +93,14 @@ class AegisEngine:
         `output_mid` is accepted and ignored, as in the reference."""
         return self.analyze_files([input_wav], turbo_mode=kwargs.get("turbo_mode", False),
                                   rake_sensitivity=kwargs.get("rake_sensitivity", 0.6), start_time=kwargs.get("start_time", 0),
-                                  end_time=kwargs.get("end_time", None), onsets=kwargs.get("onsets", False))[0]
+                                  end_time=kwargs.get("end_time", None), onsets=kwargs.get("onsets", False),
+                                  beats=kwargs.get("beats", False))[0]
 
     analyze = audio_to_midi      # BASELINE.json's name for the same call
 
-    def analyze_array(self, y, turbo_mode=False, rake_sensitivity=0.6, onsets=False):
+    def analyze_array(self, y, turbo_mode=False, rake_sensitivity=0.6, onsets=False, beats=False):
         """audio_to_midi from decoded PCM onward (aegis_engine.py:51-75)."""
-        res = self.analyze_arrays([y], turbo_mode=turbo_mode, rake_sensitivity=rake_sensitivity, onsets=onsets)
+        res = self.analyze_arrays([y], turbo_mode=turbo_mode, rake_sensitivity=rake_sensitivity, onsets=onsets, beats=beats)
         return res[0]
 
     # ------------------------------------------------------------------ onsets (not reference methods)
@@ -128,10 +130,61 @@ class AegisEngine:
         return _onsets.split_events_at_onsets(events, raw["onset_frames"], raw, self.sr, self.hop_length,
                                               kwargs.get("confidence_threshold", 0.70), kwargs.get("min_note_duration_ms", 50))
 
-    def analyze_arrays(self, clips, turbo_mode=False, rake_sensitivity=0.6, onsets=False, _concatenated=False):
+    # ------------------------------------------------------------------ tempo and beats (not reference methods)
+    def detect_beats(self, path_or_array, **kw):
+        """A WAV path or decoded samples -> (bpm, beat frames) (beats.beat_track: units, bpm, tightness, trim and the tempo
+        estimate's parameters by keyword; start_time / end_time for a path); (0.0, an empty array) for empty audio."""
+        if isinstance(path_or_array, (str, bytes)) or hasattr(path_or_array, "__fspath__"):
+            end, start = kw.pop("end_time", None), kw.pop("start_time", 0)
+            srcs = audio_io.load_pcm_files([path_or_array], self.sr, start, (end - start) if end else None)
+            y = self.handle.analyze_pcm(srcs, stages=0, check_finite=True)[0]["y"]
+        else:
+            y = np.ascontiguousarray(path_or_array, dtype=np.float32)
+        if len(y) == 0:
+            return 0.0, np.zeros(0, np.float64 if kw.get("units") == "time" else np.int64)
+        return _beats.beat_track(self.handle, [y], **kw)[0]
+
+    def _add_beats(self, raws, clips):
+        """raw["tempo"] / raw["beat_frames"] of every analysed clip, from ONE aegis_analyze_beats call for the batch."""
+        live = [i for i, r in enumerate(raws) if r is not None]
+        if live:
+            for i, (_, bpm, bt) in zip(live, self.handle.analyze_beats([clips[i] for i in live], want_env=False)):
+                raws[i]["tempo"], raws[i]["beat_frames"] = bpm, bt
+
+    def _quantize_to_beats(self, events, raw, kwargs, monophonic=True):
+        if raw is None or "beat_frames" not in raw:
+            raise ValueError("quantize_to_beats needs raw data analysed with beats=True (raw['beat_frames'] is missing)")
+        min_frames = int((kwargs.get("min_note_duration_ms", 50) / 1000.0) * self.sr / self.hop_length)
+        return _beats.quantize_events(events, raw["beat_frames"], kwargs.get("beat_subdivisions", 4), min_frames=min_frames,
+                                      n_frames=len(raw["rms"]), monophonic=monophonic)
+
+    @staticmethod
+    def _tempo_of(raw, kwargs):
+        """The tempo_bpm of smf.render: raw["tempo"] with tempo_map=True (None, today's file, where no tempo was found)."""
+        if not kwargs.get("tempo_map", False):
+            return None
+        if raw is None or "tempo" not in raw:
+            raise ValueError("tempo_map needs raw data analysed with beats=True (raw['tempo'] is missing)")
+        return raw["tempo"] if raw["tempo"] > 0 else None
+
+    def _post_passes(self, events, raw, kwargs, monophonic=True):
+        """The opt-in passes on a finished event list, in their order: split_on_onsets, then quantize_to_beats."""
+        if kwargs.get("split_on_onsets", False):
+            events = self._split_on_onsets(events, raw, kwargs)
+        if kwargs.get("quantize_to_beats", False):
+            events = self._quantize_to_beats(events, raw, kwargs, monophonic)
+        return events
+
+    @staticmethod
+    def _python_writer(kwargs):
+        """Do the keywords ask for a pass that the batched C++ writer does not know?  Then the bytes come from smf.render."""
+        return bool(kwargs.get("split_on_onsets", False) or kwargs.get("quantize_to_beats", False) or kwargs.get("tempo_map", False))
+
+    def analyze_arrays(self, clips, turbo_mode=False, rake_sensitivity=0.6, onsets=False, beats=False, _concatenated=False):
         """Batch form: one ragged GPU batch for a folder of clips; element i is what
         audio_to_midi returns for clip i (None for an empty clip).  The arrays of a batch are slices of the batch's
-        buffers (one allocation per output, not one per clip).  onsets=True adds "onset_env" and "onset_frames"."""
+        buffers (one allocation per output, not one per clip).  onsets=True adds "onset_env" and "onset_frames", beats=True
+        "tempo" and "beat_frames"."""
         clips = [np.ascontiguousarray(c, dtype=np.float32) for c in clips]
         live = [i for i, c in enumerate(clips) if len(c) > 0]
         results = [None] * len(clips)
@@ -165,10 +218,12 @@ class AegisEngine:
                           "rms": r["rms"], "y": clips[i]}
         if onsets:
             self._add_onsets(results, clips)
+        if beats:
+            self._add_beats(results, clips)
         return (results, bufs, off, live) if _concatenated else results
 
     def analyze_files(self, paths, turbo_mode=False, rake_sensitivity=0.6, start_time=0, end_time=None, want_y=True,
-                      onsets=False, _concatenated=False):
+                      onsets=False, beats=False, _concatenated=False):
         """A folder of WAV files -> element i is what audio_to_midi(paths[i], None, ...) returns.  The files are read
         one after the other as raw sample bytes (audio_io.load_pcm); decoding, the channel mean and the resampling to
         the engine rate run on the GPU, inside the analysis (Handle.analyze_pcm).  want_y=False: "y" is None and the
@@ -178,7 +233,8 @@ class AegisEngine:
         if turbo_mode:          # decode only, then the Turbo-Mode analysis of the decoded clips
             h = self.handle
             ys = [r["y"] for r in h.analyze_pcm(srcs, stages=0)] if srcs else []
-            got = self.analyze_arrays(ys, turbo_mode=True, rake_sensitivity=rake_sensitivity, onsets=onsets, _concatenated=_concatenated)
+            got = self.analyze_arrays(ys, turbo_mode=True, rake_sensitivity=rake_sensitivity, onsets=onsets, beats=beats,
+                                      _concatenated=_concatenated)
             if not want_y:
                 for r in (got[0] if _concatenated else got):
                     if r is not None:
@@ -193,12 +249,15 @@ class AegisEngine:
         self._say("[Aegis] Using Stable Single-core Analysis.")
         frames, bufs, off = self.handle.analyze_pcm([srcs[i] for i in live], rake_sensitivity=rake_sensitivity,
                                                     stages=_lib.STAGE_ALL, want_sdb=False, check_finite=True, f0_zero=True,
-                                                    views=True, concatenated=True, want_y=want_y or onsets)
+                                                    views=True, concatenated=True, want_y=want_y or onsets or beats)
         for i, r in zip(live, frames):
             results[i] = {"rake_mask": r["rake_mask"], "f0": r["f0"], "voiced_flag": r["voiced_flag"],
                           "voiced_probs": r["voiced_prob"], "rms": r["rms"], "y": r["y"]}
-        if onsets:              # (the decoded samples go through the onset entry; they are dropped again without want_y)
-            self._add_onsets(results, [r and r["y"] for r in results])
+        if onsets or beats:     # (the decoded samples go through the onset / beat entry; they are dropped again without want_y)
+            if onsets:
+                self._add_onsets(results, [r and r["y"] for r in results])
+            if beats:
+                self._add_beats(results, [r and r["y"] for r in results])
             if not want_y:
                 for i in live:
                     results[i]["y"] = None
@@ -216,7 +275,7 @@ class AegisEngine:
         got = self.analyze_files(paths, turbo_mode=kwargs.get("turbo_mode", False),
                                  rake_sensitivity=kwargs.get("rake_sensitivity", 0.6), start_time=kwargs.get("start_time", 0),
                                  end_time=kwargs.get("end_time", None), want_y=kwargs.pop("want_y", True),
-                                 onsets=kwargs.get("onsets", False), _concatenated=True)
+                                 onsets=kwargs.get("onsets", False), beats=kwargs.get("beats", False), _concatenated=True)
         return self._events_batch(len(paths), got, want_midi, kwargs)
 
     def audio_to_midi_batch(self, clips, want_midi=True, **kwargs):
@@ -225,7 +284,7 @@ class AegisEngine:
         (C++, clips in parallel).  Empty clips give (None, [], None).  kwargs as for both reference methods."""
         turbo = kwargs.get("turbo_mode", False)
         got = self.analyze_arrays(clips, turbo_mode=turbo, rake_sensitivity=kwargs.get("rake_sensitivity", 0.6),
-                                  onsets=kwargs.get("onsets", False), _concatenated=True)
+                                  onsets=kwargs.get("onsets", False), beats=kwargs.get("beats", False), _concatenated=True)
         return self._events_batch(len(clips), got, want_midi, kwargs)
 
     def _events_batch(self, n, got, want_midi, kwargs):
@@ -252,17 +311,17 @@ class AegisEngine:
             if self._freqs is None:
                 self._freqs = self.handle.table("freqs")
             grid = dict(pitch_bin=bufs["pitch_bin"], freqs=self._freqs)
-        split = bool(kwargs.get("split_on_onsets", False))
+        split = self._python_writer(kwargs)
         res = events_native.extract_batch(off, bufs["rake_mask"], bufs["f0"], bufs["voiced_flag"], bufs["voiced_prob"], bufs["rms"],
                                           self.sr, self.hop_length, kwargs.get("confidence_threshold", 0.70),
                                           want_midi=want_midi and not split, **grid, **smf_kw, **passthrough)
         per, bl = res if (want_midi and not split) else (res, None)
         for j, i in enumerate(live):
             events[i] = per[j]
-            if split:           # a post-pass on the finished list; the bytes come from the split list
-                events[i] = self._split_on_onsets(per[j], raws[i], kwargs)
+            if split:           # post-passes on the finished list; the bytes come from the list they leave
+                events[i] = self._post_passes(per[j], raws[i], kwargs)
                 if want_midi:
-                    blobs[i] = smf.render(events[i], self.sr, self.hop_length, **smf_kw)
+                    blobs[i] = smf.render(events[i], self.sr, self.hop_length, tempo_bpm=self._tempo_of(raws[i], kwargs), **smf_kw)
             elif want_midi:
                 blobs[i] = bl[j]
         return raws, events, blobs
@@ -276,13 +335,14 @@ class AegisEngine:
         passthrough = {k: v for k, v in kwargs.items() if k not in _ENGINE_ONLY_KWARGS + ("midi_program",)}
         smf_kw = dict(midi_program=kwargs.get("midi_program", 27), vibrato_rate=kwargs.get("vibrato_rate", 5.0),
                       vibrato_depth=kwargs.get("vibrato_depth", 0.3))
-        split = bool(kwargs.get("split_on_onsets", False))
+        split = self._python_writer(kwargs)
         res = events_native.extract_batch([0, n], rake_mask, f0, voiced_flag, voiced_probs, rms, self.sr, self.hop_length,
                                           kwargs.get("confidence_threshold", 0.70), want_midi=bool(output_mid) and not split, **smf_kw,
                                           **passthrough)
-        if split:               # a post-pass on the finished list; the bytes come from the split list
-            events = self._split_on_onsets(res[0], raw_data, kwargs)
-            res = ([events], [smf.render(events, self.sr, self.hop_length, **smf_kw)]) if output_mid else [events]
+        if split:               # post-passes on the finished list; the bytes come from the list they leave
+            events = self._post_passes(res[0], raw_data, kwargs)
+            res = ([events], [smf.render(events, self.sr, self.hop_length, tempo_bpm=self._tempo_of(raw_data, kwargs), **smf_kw)]) \
+                if output_mid else [events]
         if output_mid:
             events, blob = res[0][0], res[1][0]
             if hasattr(output_mid, "write"):
@@ -333,14 +393,16 @@ class AegisEngine:
             raws[i] = {"cands": c, "rms": r["rms"], "y": clips[i]}
         if kw.get("onsets", False):
             self._add_onsets(raws, clips)
+        if kw.get("beats", False):
+            self._add_beats(raws, clips)
         for i, c, r in zip(live, cands, rms):
             if want_events:
                 events[i] = polyphonic.get_midi_events_polyphonic(c, r["rms"], self.sr, self.hop_length, **kw)
-                if kw.get("split_on_onsets", False):
-                    events[i] = self._split_on_onsets(events[i], raws[i], kw)
+                events[i] = self._post_passes(events[i], raws[i], kw, monophonic=False)
                 if want_midi:
                     blobs[i] = smf.render(events[i], self.sr, self.hop_length, midi_program=kw.get("midi_program", 27),
-                                          vibrato_rate=kw.get("vibrato_rate", 5.0), vibrato_depth=kw.get("vibrato_depth", 0.3))
+                                          vibrato_rate=kw.get("vibrato_rate", 5.0), vibrato_depth=kw.get("vibrato_depth", 0.3),
+                                          tempo_bpm=self._tempo_of(raws[i], kw))
         return raws, events, blobs
 
     def extract_events_polyphonic(self, raw, output_mid, **kw):
@@ -348,11 +410,11 @@ class AegisEngine:
         or a file-like object through the engine's writer."""
         from . import polyphonic
         events = polyphonic.get_midi_events_polyphonic(raw["cands"], raw["rms"], self.sr, self.hop_length, **kw)
-        if kw.get("split_on_onsets", False):
-            events = self._split_on_onsets(events, raw, kw)
+        events = self._post_passes(events, raw, kw, monophonic=False)
         if output_mid:
             blob = smf.render(events, self.sr, self.hop_length, midi_program=kw.get("midi_program", 27),
-                              vibrato_rate=kw.get("vibrato_rate", 5.0), vibrato_depth=kw.get("vibrato_depth", 0.3))
+                              vibrato_rate=kw.get("vibrato_rate", 5.0), vibrato_depth=kw.get("vibrato_depth", 0.3),
+                              tempo_bpm=self._tempo_of(raw, kw))
             if hasattr(output_mid, "write"):
                 output_mid.write(blob)
             else:

@@ -50,20 +50,42 @@ class Track:
         v = pitch + 8192
         self._emit(tick, 0xE0, v & 0x7F, v >> 7)
 
+    def set_tempo(self, tick, microseconds_per_beat):
+        """The set_tempo meta event (FF 51 03 tt tt tt); a meta event ends running status."""
+        if not 0 < microseconds_per_beat < 1 << 24:
+            raise ValueError("tempo out of range")
+        self._data += self._varlen(tick - self._clock) + b"\xff\x51\x03" + int(microseconds_per_beat).to_bytes(3, "big")
+        self._clock = tick
+        self._status = None
+
     def chunk(self):
         body = bytes(self._data) + b"\x00\xff\x2f\x00"
         return b"MTrk" + struct.pack(">I", len(body)) + body
 
 
-def render(events, sr, hop_length, midi_program=27, vibrato_rate=5.0, vibrato_depth=0.3):
+def render(events, sr, hop_length, midi_program=27, vibrato_rate=5.0, vibrato_depth=0.3, tempo_bpm=None):
     """events -> SMF bytes.  Tick = int(frame * hop/sr * 960); hammer-on / pull-off scale the
     velocity by 0.6 / 0.5; bend = 15-point ease-out curve up to +-8191; vibrato = 10..20 sine
-    points; all messages stable-sorted by tick, per-track delta times."""
+    points; all messages stable-sorted by tick, per-track delta times.
+    tempo_bpm (not None): the file carries the tempo -- the first message of the first track is a set_tempo of
+    tempo_us = int(round(6e7 / tempo_bpm)) microseconds per beat and Tick = int(frame * hop/sr * 480e6 / tempo_us), so a
+    beat is 480 ticks.  None: the bytes of the fixed 120 bpm file."""
     frame_ticks = hop_length / sr
+    tempo_us = None
+    ticks_per_second = TICKS_PER_SECOND
+    if tempo_bpm is not None:
+        if not tempo_bpm > 0:
+            raise ValueError("tempo_bpm must be positive")
+        tempo_us = int(round(6e7 / tempo_bpm))
+        ticks_per_second = TICKS_PER_BEAT * 1e6 / tempo_us
     rows = []   # (tick, order, track, kind, a, b)
     for ev in events:
-        t_on = int(ev["start"] * frame_ticks * TICKS_PER_SECOND)
-        t_off = int(ev["end"] * frame_ticks * TICKS_PER_SECOND)
+        if tempo_us is None:
+            t_on = int(ev["start"] * frame_ticks * TICKS_PER_SECOND)
+            t_off = int(ev["end"] * frame_ticks * TICKS_PER_SECOND)
+        else:
+            t_on = int(ev["start"] * frame_ticks * 480e6 / tempo_us)
+            t_off = int(ev["end"] * frame_ticks * 480e6 / tempo_us)
         technique, vel, trk = ev.get("technique"), ev["velocity"], ev["track"]
         if technique == "hammer_on":
             vel = int(vel * 0.6)
@@ -81,7 +103,7 @@ def render(events, sr, hop_length, midi_program=27, vibrato_rate=5.0, vibrato_de
                 rows.append((t_on + int(u * length), trk, "pw", int(top * (1 - (1 - u) ** 2)), 0))
             rows.append((t_off, trk, "pw", 0, 0))
         elif technique == "vibrato":
-            secs = length / TICKS_PER_SECOND
+            secs = length / ticks_per_second
             count = max(10, min(20, int(secs * vibrato_rate * 4)))
             for i in range(count):
                 angle = (i / count) * secs * vibrato_rate * 2 * np.pi
@@ -91,6 +113,8 @@ def render(events, sr, hop_length, midi_program=27, vibrato_rate=5.0, vibrato_de
     rows.sort(key=lambda r: r[0])
 
     tracks = {"main": Track(), "safe": Track()}
+    if tempo_us is not None:
+        tracks["main"].set_tempo(0, tempo_us)
     for t in tracks.values():
         t.program_change(0, midi_program)
     for tick, trk, kind, a, b in rows:
