@@ -14,8 +14,7 @@ using namespace aegis;
 
 namespace {
 
-// Host arrays the stream may still read or write when a step fails: they live in the entry's frame, and the entry
-// synchronises the stream on every path before that frame dies.
+// Host arrays the stream reads or writes: they live in the entry's frame, declared before its StreamScope.
 struct BeatHost {
     std::vector<int64_t> foff, toff, tab_off;
     std::vector<float> win;
@@ -36,27 +35,22 @@ int beat_request(aegis_handle *h, const aegis_beat_params *p, BeatParams &o) {
     return AEGIS_OK;
 }
 
-// n_frames[] -> frame and tile offsets and the longest clip, or AEGIS_ERR_INVALID
-int beat_offsets(aegis_handle *h, const int64_t *n_frames, int32_t n_clips, BeatHost &B, int64_t &maxF) {
-    B.foff.assign((size_t)n_clips + 1, 0);
-    B.toff.assign((size_t)n_clips + 1, 0);
-    maxF = 0;
-    for (int32_t c = 0; c < n_clips; ++c) {
-        if (n_frames[c] < 0) { h->err = "beat: bad clip " + std::to_string(c); return AEGIS_ERR_INVALID; }
-        B.foff[(size_t)c + 1] = B.foff[(size_t)c] + n_frames[c];
-        B.toff[(size_t)c + 1] = B.toff[(size_t)c] + (n_frames[c] + kBeatTile - 1) / kBeatTile;
-        maxF = std::max(maxF, n_frames[c]);
-    }
-    if (maxF > INT32_MAX) { h->err = "beat: too many frames for one call"; return AEGIS_ERR_INVALID; }
+// the tile offsets behind B.foff, and both on the device
+int beat_upload_offsets(aegis_handle *h, BeatHost &B) {
+    hipStream_t s = h->stream;
+    B.toff.assign(B.foff.size(), 0);
+    for (size_t c = 0; c + 1 < B.foff.size(); ++c) B.toff[c + 1] = B.toff[c] + (B.foff[c + 1] - B.foff[c] + kBeatTile - 1) / kBeatTile;
+    ENSURE(h, bt_foff, B.foff.size() * 8); ENSURE(h, bt_toff, B.toff.size() * 8);
+    HIPCHK(h, upload(h->bt_foff, B.foff.data(), B.foff.size() * 8, s));
+    HIPCHK(h, upload(h->bt_toff, B.toff.data(), B.toff.size() * 8, s));
     return AEGIS_OK;
 }
 
-int beat_upload_offsets(aegis_handle *h, const BeatHost &B) {
-    hipStream_t s = h->stream;
-    ENSURE(h, bt_foff, B.foff.size() * 8); ENSURE(h, bt_toff, B.toff.size() * 8);
-    HIPCHK_SYNC(h, s, upload(h->bt_foff, B.foff.data(), B.foff.size() * 8, s));
-    HIPCHK_SYNC(h, s, upload(h->bt_toff, B.toff.data(), B.toff.size() * 8, s));
-    return AEGIS_OK;
+// the caller's envelopes into bt_env, and the offsets
+int beat_upload_env(aegis_handle *h, const float *env, int64_t F, BeatHost &B) {
+    ENSURE(h, bt_env, (size_t)F * 4);
+    HIPCHK(h, upload(h->bt_env, env, (size_t)F * 4, h->stream));
+    return beat_upload_offsets(h, B);
 }
 
 // The tempogram kernels over d_env (offsets uploaded) and the means into B.tg [n_clips * W]: enqueued, not synchronised.
@@ -69,13 +63,13 @@ int beat_tempogram_locked(aegis_handle *h, const float *d_env, int32_t n_clips, 
     ENSURE(h, bt_win, (size_t)W * 4);
     ENSURE(h, bt_parts, (size_t)B.toff[(size_t)n_clips] * W * 8);
     ENSURE(h, bt_tg, (size_t)n_clips * W * 8);
-    HIPCHK_SYNC(h, s, upload(h->bt_win, B.win.data(), (size_t)W * 4, s));
+    HIPCHK(h, upload(h->bt_win, B.win.data(), (size_t)W * 4, s));
     begin_event(h, "beat_tempogram", s);
-    launch_beat_tempogram(d_env, static_cast<const int64_t *>(h->bt_foff.p), static_cast<const int64_t *>(h->bt_toff.p), n_clips, maxF, W,
-                          static_cast<const float *>(h->bt_win.p), static_cast<double *>(h->bt_parts.p), static_cast<double *>(h->bt_tg.p), s);
+    launch_beat_tempogram(d_env, h->bt_foff.as<const int64_t>(), h->bt_toff.as<const int64_t>(), n_clips, maxF, W,
+                          h->bt_win.as<const float>(), h->bt_parts.as<double>(), h->bt_tg.as<double>(), s);
     end_event(h, s);
-    HIPCHK_SYNC(h, s, hipGetLastError());
-    HIPCHK_SYNC(h, s, hipMemcpyAsync(B.tg.data(), h->bt_tg.p, B.tg.size() * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(B.tg.data(), h->bt_tg.p, B.tg.size() * 8, hipMemcpyDeviceToHost, s));
     return AEGIS_OK;
 }
 
@@ -86,19 +80,19 @@ int beat_pick_clip(aegis_handle *h, const BeatHost &B, int32_t c, const BeatPara
 }
 
 // The beat tracker over d_env (offsets uploaded): moments, tempogram where the tempo is to be estimated, the tempo choice,
-// local score, DP, tail.  Synchronises the stream twice when all goes well; on a failure the entry does.
+// local score, DP, tail.  Synchronises the stream twice, between its device and host steps.
 int beat_track_locked(aegis_handle *h, const float *d_env, int32_t n_clips, int64_t maxF, const BeatParams &o, const double *bpm_in,
                       BeatHost &B, uint8_t *beat_mask, int64_t *n_beats, double *bpm_out, double *ls_out, double *cum_out, int32_t *back_out) {
     hipStream_t s = h->stream;
     const int64_t F = B.foff[(size_t)n_clips];
-    const int64_t *d_foff = static_cast<const int64_t *>(h->bt_foff.p);
+    const int64_t *d_foff = h->bt_foff.as<const int64_t>();
     B.stats.assign((size_t)n_clips * 3, 0.0);
     ENSURE(h, bt_stats, B.stats.size() * 8);
     begin_event(h, "beat_score", s);
-    launch_beat_moments(d_env, d_foff, n_clips, static_cast<double *>(h->bt_stats.p), s);
+    launch_beat_moments(d_env, d_foff, n_clips, h->bt_stats.as<double>(), s);
     end_event(h, s);
-    HIPCHK_SYNC(h, s, hipGetLastError());
-    HIPCHK_SYNC(h, s, hipMemcpyAsync(B.stats.data(), h->bt_stats.p, B.stats.size() * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(B.stats.data(), h->bt_stats.p, B.stats.size() * 8, hipMemcpyDeviceToHost, s));
     const bool estimate = !bpm_in && o.bpm == 0.0;
     if (estimate) {
         const int rc = beat_tempogram_locked(h, d_env, n_clips, maxF, o, B);
@@ -145,27 +139,27 @@ int beat_track_locked(aegis_handle *h, const float *d_env, int32_t n_clips, int6
     // ---- device: local score and DP ----------------------------------------------------------------------------------------
     ENSURE(h, bt_period, (size_t)n_clips * 4); ENSURE(h, bt_taboff, (size_t)n_clips * 8); ENSURE(h, bt_tabs, B.tabs.size() * 8);
     ENSURE(h, bt_ls, (size_t)F * 8); ENSURE(h, bt_cum, (size_t)F * 8); ENSURE(h, bt_back, (size_t)F * 4);
-    HIPCHK_SYNC(h, s, upload(h->bt_period, B.period.data(), (size_t)n_clips * 4, s));
-    HIPCHK_SYNC(h, s, upload(h->bt_taboff, B.tab_off.data(), (size_t)n_clips * 8, s));
-    HIPCHK_SYNC(h, s, upload(h->bt_tabs, B.tabs.data(), B.tabs.size() * 8, s));
-    const int32_t *d_period = static_cast<const int32_t *>(h->bt_period.p);
-    const int64_t *d_taboff = static_cast<const int64_t *>(h->bt_taboff.p);
-    const double *d_tabs = static_cast<const double *>(h->bt_tabs.p);
+    HIPCHK(h, upload(h->bt_period, B.period.data(), (size_t)n_clips * 4, s));
+    HIPCHK(h, upload(h->bt_taboff, B.tab_off.data(), (size_t)n_clips * 8, s));
+    HIPCHK(h, upload(h->bt_tabs, B.tabs.data(), B.tabs.size() * 8, s));
+    const int32_t *d_period = h->bt_period.as<const int32_t>();
+    const int64_t *d_taboff = h->bt_taboff.as<const int64_t>();
+    const double *d_tabs = h->bt_tabs.as<const double>();
     begin_event(h, "beat_score", s);
-    launch_beat_score(d_env, d_foff, n_clips, maxF, d_period, d_taboff, d_tabs, static_cast<const double *>(h->bt_stats.p),
-                      static_cast<double *>(h->bt_ls.p), s);
+    launch_beat_score(d_env, d_foff, n_clips, maxF, d_period, d_taboff, d_tabs, h->bt_stats.as<const double>(),
+                      h->bt_ls.as<double>(), s);
     end_event(h, s);
-    HIPCHK_SYNC(h, s, hipGetLastError());
+    HIPCHK(h, hipGetLastError());
     begin_event(h, "beat_dp", s);
-    launch_beat_dp(static_cast<const double *>(h->bt_ls.p), d_foff, n_clips, d_period, d_taboff, d_tabs, static_cast<double *>(h->bt_cum.p),
-                   static_cast<int32_t *>(h->bt_back.p), s);
+    launch_beat_dp(h->bt_ls.as<const double>(), d_foff, n_clips, d_period, d_taboff, d_tabs, h->bt_cum.as<double>(),
+                   h->bt_back.as<int32_t>(), s);
     end_event(h, s);
-    HIPCHK_SYNC(h, s, hipGetLastError());
+    HIPCHK(h, hipGetLastError());
     B.ls.assign((size_t)F, 0.0); B.cum.assign((size_t)F, 0.0); B.back.assign((size_t)F, -1);
     if (F) {
-        HIPCHK_SYNC(h, s, hipMemcpyAsync(B.ls.data(), h->bt_ls.p, (size_t)F * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK_SYNC(h, s, hipMemcpyAsync(B.cum.data(), h->bt_cum.p, (size_t)F * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK_SYNC(h, s, hipMemcpyAsync(B.back.data(), h->bt_back.p, (size_t)F * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipMemcpyAsync(B.ls.data(), h->bt_ls.p, (size_t)F * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipMemcpyAsync(B.cum.data(), h->bt_cum.p, (size_t)F * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipMemcpyAsync(B.back.data(), h->bt_back.p, (size_t)F * 4, hipMemcpyDeviceToHost, s));
     }
     HIPCHK(h, hipStreamSynchronize(s));
     // ---- host: the tail ------------------------------------------------------------------------------------------------------
@@ -208,28 +202,20 @@ int aegis_tempo(aegis_handle *h, const float *env, const int64_t *n_frames, int3
     if (n_clips < 0 || (n_clips > 0 && (!n_frames || !bpm_out || !period_out))) { h->err = "beat: null argument"; return AEGIS_ERR_INVALID; }
     BeatHost B;
     int64_t maxF = 0;
-    if ((rc = beat_offsets(h, n_frames, n_clips, B, maxF)) != AEGIS_OK) return rc;
+    if ((rc = frame_offsets(h, "beat: ", "beat: ", n_frames, n_clips, B.foff, maxF)) != AEGIS_OK) return rc;
     const int64_t F = B.foff[(size_t)n_clips];
     if (F > 0 && !env) { h->err = "beat: null argument"; return AEGIS_ERR_INVALID; }
     DEVICE_ONLY(h);
     if (n_clips == 0) return AEGIS_OK;
     HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = h->stream;
     drop_events(h);
-    rc = ensure(h, h->bt_env, std::max<size_t>((size_t)F * 4, 8));
-    if (rc == AEGIS_OK) {
-        const hipError_t e = upload(h->bt_env, env, (size_t)F * 4, s);
-        if (e != hipSuccess) { h->err = std::string("upload of the envelopes: ") + hipGetErrorString(e); rc = AEGIS_ERR_DEVICE; }
-    }
-    if (rc == AEGIS_OK) rc = beat_upload_offsets(h, B);
-    if (rc == AEGIS_OK) rc = beat_tempogram_locked(h, static_cast<const float *>(h->bt_env.p), n_clips, maxF, o, B);
-    const hipError_t e = hipStreamSynchronize(s);               // B dies with this frame, whatever happened
-    if (rc != AEGIS_OK) { drop_events(h); return rc; }
-    HIPCHK(h, e);
+    StreamScope scope(h);
+    if ((rc = beat_upload_env(h, env, F, B)) != AEGIS_OK) return rc;
+    if ((rc = beat_tempogram_locked(h, h->bt_env.as<const float>(), n_clips, maxF, o, B)) != AEGIS_OK) return rc;
+    if ((rc = scope.finish()) != AEGIS_OK) return rc;
     for (int32_t c = 0; c < n_clips; ++c)
-        if ((rc = beat_pick_clip(h, B, c, o, period_out[c], bpm_out[c])) != AEGIS_OK) { drop_events(h); return rc; }
+        if ((rc = beat_pick_clip(h, B, c, o, period_out[c], bpm_out[c])) != AEGIS_OK) return rc;
     if (tg_out) std::memcpy(tg_out, B.tg.data(), B.tg.size() * 8);
-    if (h->profiling) collect_events(h);
     return AEGIS_OK;
     } catch (...) { return abi_fail(h); }
 }
@@ -246,28 +232,17 @@ int aegis_beat_track(aegis_handle *h, const float *env, const int64_t *n_frames,
     if (n_clips < 0 || (n_clips > 0 && (!n_frames || !n_beats || !bpm_out))) { h->err = "beat: null argument"; return AEGIS_ERR_INVALID; }
     BeatHost B;
     int64_t maxF = 0;
-    if ((rc = beat_offsets(h, n_frames, n_clips, B, maxF)) != AEGIS_OK) return rc;
+    if ((rc = frame_offsets(h, "beat: ", "beat: ", n_frames, n_clips, B.foff, maxF)) != AEGIS_OK) return rc;
     const int64_t F = B.foff[(size_t)n_clips];
     if (F > 0 && (!env || !beat_mask)) { h->err = "beat: null argument"; return AEGIS_ERR_INVALID; }
     DEVICE_ONLY(h);
     if (n_clips == 0) return AEGIS_OK;
     HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = h->stream;
     drop_events(h);
-    rc = ensure(h, h->bt_env, std::max<size_t>((size_t)F * 4, 8));
-    if (rc == AEGIS_OK) {
-        const hipError_t e = upload(h->bt_env, env, (size_t)F * 4, s);
-        if (e != hipSuccess) { h->err = std::string("upload of the envelopes: ") + hipGetErrorString(e); rc = AEGIS_ERR_DEVICE; }
-    }
-    if (rc == AEGIS_OK) rc = beat_upload_offsets(h, B);
-    if (rc == AEGIS_OK)
-        rc = beat_track_locked(h, static_cast<const float *>(h->bt_env.p), n_clips, maxF, o, bpm_in, B, beat_mask, n_beats, bpm_out, ls_out,
-                               cum_out, back_out);
-    const hipError_t e = hipStreamSynchronize(s);               // B dies with this frame, whatever happened
-    if (rc != AEGIS_OK) { drop_events(h); return rc; }
-    HIPCHK(h, e);
-    if (h->profiling) collect_events(h);
-    return AEGIS_OK;
+    StreamScope scope(h);
+    if ((rc = beat_upload_env(h, env, F, B)) != AEGIS_OK) return rc;
+    rc = beat_track_locked(h, h->bt_env.as<const float>(), n_clips, maxF, o, bpm_in, B, beat_mask, n_beats, bpm_out, ls_out, cum_out, back_out);
+    return rc != AEGIS_OK ? rc : scope.finish();
     } catch (...) { return abi_fail(h); }
 }
 
@@ -281,56 +256,25 @@ int aegis_analyze_beats(aegis_handle *h, const float *const *pcm, const int64_t 
     int rc = beat_request(h, beat_params, o);
     if (rc != AEGIS_OK) return rc;
     OnsetParams on;
-    {
-        const aegis_onset_params all{-1, -1, -1, -1, -1, -1, -1, -1, -1, 0, -1.0};
-        const aegis_onset_params *q = onset_params ? onset_params : &all;
-        const char *msg = onset_fill(h->tab.sr, h->tab.hop, h->tab.n_fft, q->lag, q->max_size, q->shift, q->pre_max, q->post_max, q->pre_avg,
-                                     q->post_avg, q->wait, q->normalize, q->delta, on);
-        if (msg[0]) { h->err = std::string("onset: ") + msg; return AEGIS_ERR_INVALID; }
-    }
+    if ((rc = onset_request(h, onset_params, on)) != AEGIS_OK) return rc;
     if (h->tab.n_mels < 1 || h->tab.n_mels > kOnsMaxMels) { h->err = "onset: n_mels must be 1..256"; return AEGIS_ERR_INVALID; }
     if (n_clips < 0 || (n_clips > 0 && (!pcm || !n_samples || !beat_mask || !n_beats || !bpm_out))) { h->err = "beat: null argument"; return AEGIS_ERR_INVALID; }
-    std::vector<int64_t> nf((size_t)std::max(n_clips, 0));
-    for (int32_t c = 0; c < n_clips; ++c) {
-        if (n_samples[c] < 0 || (n_samples[c] > 0 && !pcm[c])) { h->err = "beat: bad clip " + std::to_string(c); return AEGIS_ERR_INVALID; }
-        nf[(size_t)c] = 1 + n_samples[c] / h->tab.hop;
-    }
     BeatHost B;
+    std::vector<int64_t> off, foff;
     int64_t maxF = 0;
-    if ((rc = beat_offsets(h, nf.data(), n_clips, B, maxF)) != AEGIS_OK) return rc;
+    if ((rc = clip_frames(h, "beat: ", pcm, n_samples, n_clips, B.foff, maxF)) != AEGIS_OK) return rc;
     DEVICE_ONLY(h);
     if (n_clips == 0) return AEGIS_OK;
     HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = h->stream;
-    std::vector<int64_t> off, foff;                            // (they outlive the synchronisation below)
-    rc = mel_host_locked(h, pcm, n_samples, n_clips, off, foff);
-    if (rc == AEGIS_OK && foff != B.foff) { h->err = "beat: the mel stage's frame counts differ from 1 + n_samples / hop"; rc = AEGIS_ERR_DEVICE; }
+    StreamScope scope(h);                                       // the feed's copies and the pipeline read pcm, off and foff
+    if ((rc = mel_host_locked(h, pcm, n_samples, n_clips, off, foff)) != AEGIS_OK) return rc;
+    if (foff != B.foff) { h->err = "beat: the mel stage's frame counts differ from 1 + n_samples / hop"; return AEGIS_ERR_DEVICE; }
     const int64_t F = B.foff[(size_t)n_clips];
-    if (rc == AEGIS_OK) rc = beat_upload_offsets(h, B);
-    if (rc == AEGIS_OK) rc = ensure(h, h->on_env, std::max<size_t>((size_t)F * 4, 8));
-    if (rc == AEGIS_OK) {
-        begin_event(h, "onset_env", s);
-        launch_onset_env(static_cast<const float *>(h->io_sdb.p), static_cast<const int64_t *>(h->bt_foff.p), n_clips, maxF, h->tab.n_mels, on,
-                         static_cast<float *>(h->on_env.p), s);
-        end_event(h, s);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { h->err = std::string("onset_env launch: ") + hipGetErrorString(e); rc = AEGIS_ERR_DEVICE; }
-    }
-    if (rc == AEGIS_OK && env_out) {
-        const hipError_t e = hipMemcpyAsync(env_out, h->on_env.p, (size_t)F * 4, hipMemcpyDeviceToHost, s);
-        if (e != hipSuccess) { h->err = std::string("hipMemcpyAsync(env_out): ") + hipGetErrorString(e); rc = AEGIS_ERR_DEVICE; }
-    }
-    if (rc == AEGIS_OK)
-        rc = beat_track_locked(h, static_cast<const float *>(h->on_env.p), n_clips, maxF, o, nullptr, B, beat_mask, n_beats, bpm_out, nullptr,
-                               nullptr, nullptr);
-    // the feed's copies and the pipeline may still read pcm, off and foff: drained on every path
-    const hipError_t e3 = hipStreamSynchronize(h->stream3), e = hipStreamSynchronize(s);
-    h->plan_in_flight = false;
-    if (rc != AEGIS_OK) { drop_events(h); return rc; }
-    HIPCHK(h, e3);
-    HIPCHK(h, e);
-    if (h->profiling) collect_events(h);
-    return AEGIS_OK;
+    if ((rc = beat_upload_offsets(h, B)) != AEGIS_OK) return rc;
+    if ((rc = onset_env_locked(h, h->io_sdb.as<const float>(), h->bt_foff.as<const int64_t>(), n_clips, F, maxF, h->tab.n_mels, on)) != AEGIS_OK) return rc;
+    if (env_out) HIPCHK(h, hipMemcpyAsync(env_out, h->on_env.p, (size_t)F * 4, hipMemcpyDeviceToHost, h->stream));
+    rc = beat_track_locked(h, h->on_env.as<const float>(), n_clips, maxF, o, nullptr, B, beat_mask, n_beats, bpm_out, nullptr, nullptr, nullptr);
+    return rc != AEGIS_OK ? rc : scope.finish();
     } catch (...) { return abi_fail(h); }
 }
 

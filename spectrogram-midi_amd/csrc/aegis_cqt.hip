@@ -22,15 +22,15 @@ int aegis_rake_patterns(aegis_handle *h, const float *S_dB, int32_t n_mels, int6
     if ((rc = ensure(h, h->rk_raw, n_frames)) != AEGIS_OK) return rc;
     if ((rc = ensure(h, h->io_rake, n_frames)) != AEGIS_OK) return rc;
     hipStream_t s = h->stream;
+    StreamScope scope(h);
     HIPCHK(h, hipMemcpyAsync(h->io_sdb.p, S_dB, img, hipMemcpyHostToDevice, s));
     const RakeBounds rb = rake_frame_bounds(h->tab);
-    launch_rake_from_db(static_cast<const float *>(h->io_sdb.p), n_mels, n_frames, broadband_threshold_ratio,
-                        rb.min_frames, rb.max_frames, static_cast<uint8_t *>(h->rk_raw.p),
-                        static_cast<uint8_t *>(h->io_rake.p), s);
+    launch_rake_from_db(h->io_sdb.as<const float>(), n_mels, n_frames, broadband_threshold_ratio,
+                        rb.min_frames, rb.max_frames, h->rk_raw.as<uint8_t>(),
+                        h->io_rake.as<uint8_t>(), s);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpyAsync(mask_out, h->io_rake.p, n_frames, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    return AEGIS_OK;
+    return scope.finish();
     } catch (...) { return abi_fail(h); }
 }
 
@@ -117,15 +117,17 @@ static int cqt_launch_locked(aegis_handle *h, const float *d_pcm, const int64_t 
     if ((rc = ensure(h, h->q_soff, (n_clips + 1) * 8)) != AEGIS_OK) return rc;
     if ((rc = ensure(h, h->q_foff, (n_clips + 1) * 8)) != AEGIS_OK) return rc;
     if ((rc = ensure(h, h->q_toff, (n_clips + 1) * 8)) != AEGIS_OK) return rc;
-    // (pageable host vectors: the copies complete before hipMemcpyAsync returns)
-    HIPCHK(h, hipMemcpyAsync(h->q_soff.p, soff, (n_clips + 1) * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(h->q_foff.p, foff.data(), (n_clips + 1) * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(h->q_toff.p, toff.data(), (n_clips + 1) * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipStreamSynchronize(s));         // ... but the vectors die with this frame: make it certain
-    CqtArgs a{d_pcm, static_cast<const int64_t *>(h->q_soff.p), static_cast<const int64_t *>(h->q_foff.p), n_clips,
+    {   // foff and toff (and the caller's soff) leave with this frame: a scope of their own, drained before the launch
+        StreamScope geometry(h, s);
+        HIPCHK(h, hipMemcpyAsync(h->q_soff.p, soff, (n_clips + 1) * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(h, hipMemcpyAsync(h->q_foff.p, foff.data(), (n_clips + 1) * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(h, hipMemcpyAsync(h->q_toff.p, toff.data(), (n_clips + 1) * 8, hipMemcpyHostToDevice, s));
+        if ((rc = geometry.finish()) != AEGIS_OK) return rc;
+    }
+    CqtArgs a{d_pcm, h->q_soff.as<const int64_t>(), h->q_foff.as<const int64_t>(), n_clips,
               foff[n_clips], h->tab.hop, d_out};
     drop_events(h);
-    begin_event(h, "cqt", s); launch_cqt(a, h->cqt_banks.front().bank, static_cast<const int64_t *>(h->q_toff.p), toff[n_clips], s); end_event(h, s);
+    begin_event(h, "cqt", s); launch_cqt(a, h->cqt_banks.front().bank, h->q_toff.as<const int64_t>(), toff[n_clips], s); end_event(h, s);
     HIPCHK(h, hipGetLastError());
     *total_frames = foff[n_clips];
     return AEGIS_OK;
@@ -159,10 +161,10 @@ int aegis::cqt_host_locked(aegis_handle *h, const float *const *pcm, const int64
     }
     for (int i = 0; i < n_clips; ++i)
         if (n_samples[i] > 0)
-            HIPCHK(h, hipMemcpyAsync(static_cast<float *>(h->q_pcm.p) + soff[i], pcm[i], n_samples[i] * 4, hipMemcpyHostToDevice, s));
+            HIPCHK(h, hipMemcpyAsync(h->q_pcm.as<float>() + soff[i], pcm[i], n_samples[i] * 4, hipMemcpyHostToDevice, s));
     int64_t Fd = 0;
     *F_out = F;
-    return cqt_launch_locked(h, static_cast<const float *>(h->q_pcm.p), soff.data(), n_clips, static_cast<float *>(h->q_out.p), s, &Fd);
+    return cqt_launch_locked(h, h->q_pcm.as<const float>(), soff.data(), n_clips, h->q_out.as<float>(), s, &Fd);
 }
 extern "C" {
 
@@ -178,11 +180,10 @@ int aegis_cqt(aegis_handle *h, const float *const *pcm, const int64_t *n_samples
     hipStream_t s = h->stream;
     int rc;
     int64_t F = 0;
+    StreamScope scope(h);
     if ((rc = cqt_host_locked(h, pcm, n_samples, n_clips, n_bins, bins_per_octave, fmin, filter_scale, 0, nullptr, &F)) != AEGIS_OK) return rc;
     HIPCHK(h, hipMemcpyAsync(mag_out, h->q_out.p, (size_t)F * n_bins * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    if (h->profiling) collect_events(h);
-    return AEGIS_OK;
+    return scope.finish();
     } catch (...) { return abi_fail(h); }
 }
 
@@ -200,16 +201,15 @@ int aegis_chroma_cqt(aegis_handle *h, const float *const *pcm, const int64_t *n_
     hipStream_t s = h->stream;
     int rc;
     int64_t F = 0;
+    StreamScope scope(h);
     if ((rc = cqt_host_locked(h, pcm, n_samples, n_clips, n_bins, bins_per_octave, fmin, filter_scale, n_chroma, bin_class, &F)) != AEGIS_OK) return rc;
     begin_event(h, "chroma", s);
-    launch_chroma_fold(static_cast<const float *>(h->q_out.p), static_cast<const int64_t *>(h->q_foff.p), n_clips, F, n_bins, n_chroma,
-                       static_cast<const int32_t *>(h->q_cls.p), static_cast<float *>(h->q_chroma.p), s);
+    launch_chroma_fold(h->q_out.as<const float>(), h->q_foff.as<const int64_t>(), n_clips, F, n_bins, n_chroma,
+                       h->q_cls.as<const int32_t>(), h->q_chroma.as<float>(), s);
     end_event(h, s);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpyAsync(chroma_out, h->q_chroma.p, (size_t)F * n_chroma * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    if (h->profiling) collect_events(h);
-    return AEGIS_OK;
+    return scope.finish();
     } catch (...) { return abi_fail(h); }
 }
 
@@ -226,13 +226,12 @@ int aegis_cqt_device(aegis_handle *h, const float *d_pcm, const int64_t *sample_
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
     int rc;
+    StreamScope scope(h, s);
     if ((rc = cqt_bank_locked(h, n_bins, bins_per_octave, fmin, filter_scale, s)) != AEGIS_OK) return rc;
     int64_t F = 0;
     if ((rc = cqt_launch_locked(h, d_pcm, sample_offsets, n_clips, d_mag_out, s, &F)) != AEGIS_OK) return rc;
-    if (sync) {
-        HIPCHK(h, hipStreamSynchronize(s));
-        if (h->profiling) collect_events(h);
-    }
+    if (sync) return scope.finish();
+    scope.leave_enqueued();
     return AEGIS_OK;
     } catch (...) { return abi_fail(h); }
 }
@@ -267,6 +266,7 @@ int aegis_estimate_tuning(aegis_handle *h, const float *const *pcm, const int64_
         poff[i + 1] = poff[i] + frames * per_frame;
     }
     if (foff[n_clips] >= ((int64_t)1 << 31)) { h->err = "estimate_tuning: too many frames for one call"; return AEGIS_ERR_INVALID; }
+    std::vector<unsigned long long> np_host(n_peaks_out ? (size_t)n_clips : 0);
     int rc;
     const size_t peaks = (size_t)std::max<int64_t>(poff[n_clips], 1);
     if ((rc = ensure(h, h->q_pcm, (size_t)std::max<int64_t>(soff[n_clips], 1) * 4)) != AEGIS_OK) return rc;
@@ -277,35 +277,34 @@ int aegis_estimate_tuning(aegis_handle *h, const float *const *pcm, const int64_
     if ((rc = ensure(h, h->tn_median, (size_t)n_clips * 4)) != AEGIS_OK) return rc;
     if ((rc = ensure(h, h->tn_cells, (size_t)n_clips * kTunCells * 4)) != AEGIS_OK) return rc;
     if ((rc = ensure(h, h->tn_tuning, (size_t)n_clips * 8)) != AEGIS_OK) return rc;
+    StreamScope scope(h);
     HIPCHK(h, hipMemcpyAsync(h->tn_meta.p, geo.data(), geo.size() * 8, hipMemcpyHostToDevice, s));
     HIPCHK(h, hipMemsetAsync(h->tn_count.p, 0, (size_t)n_clips * 8, s));
     for (int i = 0; i < n_clips; ++i)
         if (n_samples[i] > 0)
-            HIPCHK(h, hipMemcpyAsync(static_cast<float *>(h->q_pcm.p) + soff[i], pcm[i], n_samples[i] * 4, hipMemcpyHostToDevice, s));
-    a.pcm = static_cast<const float *>(h->q_pcm.p);
-    a.sample_off = static_cast<const int64_t *>(h->tn_meta.p);
+            HIPCHK(h, hipMemcpyAsync(h->q_pcm.as<float>() + soff[i], pcm[i], n_samples[i] * 4, hipMemcpyHostToDevice, s));
+    a.pcm = h->q_pcm.as<const float>();
+    a.sample_off = h->tn_meta.as<const int64_t>();
     a.frame_off = a.sample_off + m;
     a.peak_off = a.frame_off + m;
     a.n_frames = foff[n_clips];
     a.hann = h->dt.hann; a.twiddle = h->dt.twiddle; a.edges = h->d_tuning_edges;
-    a.pitch = static_cast<float *>(h->tn_pitch.p); a.mag = static_cast<float *>(h->tn_mag.p);
-    a.n_peaks = static_cast<unsigned long long *>(h->tn_count.p);
-    a.median = static_cast<float *>(h->tn_median.p);
-    a.counts = static_cast<int32_t *>(h->tn_cells.p);
-    a.tuning = static_cast<double *>(h->tn_tuning.p);
+    a.pitch = h->tn_pitch.as<float>(); a.mag = h->tn_mag.as<float>();
+    a.n_peaks = h->tn_count.as<unsigned long long>();
+    a.median = h->tn_median.as<float>();
+    a.counts = h->tn_cells.as<int32_t>();
+    a.tuning = h->tn_tuning.as<double>();
     drop_events(h);
     begin_event(h, "tuning_peaks", s); launch_tuning_peaks(a, s); end_event(h, s);
     begin_event(h, "tuning_select", s); launch_tuning_select(a, s); end_event(h, s);
     begin_event(h, "tuning_hist", s); launch_tuning_hist(a, s); end_event(h, s);
     HIPCHK(h, hipGetLastError());
-    std::vector<unsigned long long> np_host(n_peaks_out ? (size_t)n_clips : 0);
     HIPCHK(h, hipMemcpyAsync(tuning_out, h->tn_tuning.p, (size_t)n_clips * 8, hipMemcpyDeviceToHost, s));
     if (counts_out) HIPCHK(h, hipMemcpyAsync(counts_out, h->tn_cells.p, (size_t)n_clips * kTunCells * 4, hipMemcpyDeviceToHost, s));
     if (n_peaks_out) HIPCHK(h, hipMemcpyAsync(np_host.data(), h->tn_count.p, (size_t)n_clips * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipStreamSynchronize(s));
+    if ((rc = scope.finish()) != AEGIS_OK) return rc;
     for (size_t i = 0; i < np_host.size(); ++i) n_peaks_out[i] = (int64_t)np_host[i];
     h->tn_last_peak_off.assign(poff, poff + m);
-    if (h->profiling) collect_events(h);
     return AEGIS_OK;
     } catch (...) { return abi_fail(h); }
 }

@@ -222,22 +222,22 @@ int effects_group(aegis_handle *h, const Planned &P, int32_t c0, int32_t c1, con
     ENSURE(h, fx_recs, recs.size() * sizeof(FxClip)); ENSURE(h, fx_tiles, tiles.size() * sizeof(FxTile));
     ENSURE(h, fx_peak, recs.size() * 8); ENSURE(h, fx_taps, std::max<size_t>(P.taps.size(), 1) * 8);
     if (s16 || want_i16) ENSURE(h, fx_i16, (size_t)total * 2);
-    // From here on the stream may still read the host vectors above: HIPCHK_SYNC.
-    double *buf0 = static_cast<double *>(h->fx_a.p), *buf1 = static_cast<double *>(h->fx_b.p);
-    int16_t *d_i16 = static_cast<int16_t *>(h->fx_i16.p);
-    const FxClip *d_recs = static_cast<const FxClip *>(h->fx_recs.p);
-    const FxTile *d_tiles = static_cast<const FxTile *>(h->fx_tiles.p);
-    unsigned long long *d_peak = static_cast<unsigned long long *>(h->fx_peak.p);
-    const double *d_taps = static_cast<const double *>(h->fx_taps.p);
-    HIPCHK_SYNC(h, s, hipMemcpyAsync(h->fx_recs.p, recs.data(), recs.size() * sizeof(FxClip), hipMemcpyHostToDevice, s));
-    HIPCHK_SYNC(h, s, hipMemcpyAsync(h->fx_tiles.p, tiles.data(), tiles.size() * sizeof(FxTile), hipMemcpyHostToDevice, s));
-    if (!P.taps.empty()) HIPCHK_SYNC(h, s, hipMemcpyAsync(h->fx_taps.p, P.taps.data(), P.taps.size() * 8, hipMemcpyHostToDevice, s));
-    HIPCHK_SYNC(h, s, hipMemsetAsync(h->fx_peak.p, 0, recs.size() * 8, s));
+    StreamScope scope(h);                                       // (the host vectors above are in front of it)
+    double *buf0 = h->fx_a.as<double>(), *buf1 = h->fx_b.as<double>();
+    int16_t *d_i16 = h->fx_i16.as<int16_t>();
+    const FxClip *d_recs = h->fx_recs.as<const FxClip>();
+    const FxTile *d_tiles = h->fx_tiles.as<const FxTile>();
+    unsigned long long *d_peak = h->fx_peak.as<unsigned long long>();
+    const double *d_taps = h->fx_taps.as<const double>();
+    HIPCHK(h, hipMemcpyAsync(h->fx_recs.p, recs.data(), recs.size() * sizeof(FxClip), hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(h->fx_tiles.p, tiles.data(), tiles.size() * sizeof(FxTile), hipMemcpyHostToDevice, s));
+    if (!P.taps.empty()) HIPCHK(h, hipMemcpyAsync(h->fx_taps.p, P.taps.data(), P.taps.size() * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemsetAsync(h->fx_peak.p, 0, recs.size() * 8, s));
     for (size_t c = 0; c < nc; ++c) {
         const int64_t n = off[c + 1] - off[c];
         if (n == 0) continue;
-        if (s16) HIPCHK_SYNC(h, s, hipMemcpyAsync(d_i16 + off[c], in[c0 + (int32_t)c], (size_t)n * 2, hipMemcpyHostToDevice, s));
-        else HIPCHK_SYNC(h, s, hipMemcpyAsync(buf0 + off[c], in[c0 + (int32_t)c], (size_t)n * 8, hipMemcpyHostToDevice, s));
+        if (s16) HIPCHK(h, hipMemcpyAsync(d_i16 + off[c], in[c0 + (int32_t)c], (size_t)n * 2, hipMemcpyHostToDevice, s));
+        else HIPCHK(h, hipMemcpyAsync(buf0 + off[c], in[c0 + (int32_t)c], (size_t)n * 8, hipMemcpyHostToDevice, s));
     }
     if (s16) {
         begin_event(h, "fx_load", s);
@@ -268,18 +268,16 @@ int effects_group(aegis_handle *h, const Planned &P, int32_t c0, int32_t c1, con
         fx_i16(d_recs, d_tiles + at_whole, buf0, buf1, d_i16, (int32_t)whole.size(), s);
         end_event(h, s);
     }
-    HIPCHK_SYNC(h, s, hipGetLastError());
+    HIPCHK(h, hipGetLastError());
     for (size_t c = 0; c < nc; ++c) {
         const int64_t n = off[c + 1] - off[c];
         if (n == 0) continue;
         const int32_t cc = c0 + (int32_t)c;
         if (out_f64 && out_f64[cc])
-            HIPCHK_SYNC(h, s, hipMemcpyAsync(out_f64[cc], (src[c] ? buf1 : buf0) + off[c], (size_t)n * 8, hipMemcpyDeviceToHost, s));
-        if (out_i16 && out_i16[cc]) HIPCHK_SYNC(h, s, hipMemcpyAsync(out_i16[cc], d_i16 + off[c], (size_t)n * 2, hipMemcpyDeviceToHost, s));
+            HIPCHK(h, hipMemcpyAsync(out_f64[cc], (src[c] ? buf1 : buf0) + off[c], (size_t)n * 8, hipMemcpyDeviceToHost, s));
+        if (out_i16 && out_i16[cc]) HIPCHK(h, hipMemcpyAsync(out_i16[cc], d_i16 + off[c], (size_t)n * 2, hipMemcpyDeviceToHost, s));
     }
-    HIPCHK_SYNC(h, s, hipStreamSynchronize(s));
-    if (h->profiling) collect_events(h);
-    return AEGIS_OK;
+    return scope.finish();
 }
 
 }  // namespace

@@ -105,6 +105,17 @@ void aegis::collect_events(aegis_handle *h) {
     h->last_ms["total"] = total;
 }
 
+int aegis::drain_stream(aegis_handle *h, hipStream_t s, bool collect) {
+    const hipError_t e3 = h->plan_in_flight ? hipStreamSynchronize(h->stream3) : hipSuccess, e = hipStreamSynchronize(s);
+    h->plan_in_flight = false;
+    if (!collect || e3 != hipSuccess || e != hipSuccess) drop_events(h);
+    if (!collect) return AEGIS_OK;
+    HIPCHK(h, e3);
+    HIPCHK(h, e);
+    if (h->profiling && !h->events.empty()) collect_events(h);
+    return AEGIS_OK;
+}
+
 int aegis::abi_fail(aegis_handle *h) noexcept {
     int code = AEGIS_ERR_DEVICE;
     const char *msg = "unknown C++ exception";
@@ -646,20 +657,20 @@ int aegis_debug_rake_columns(aegis_handle *h, const float *mel_power, int64_t n_
     hipStream_t s = h->stream;
     struct { int64_t frame_off[2]; uint32_t clipmax; } geo = {{0, n_rows}, 0};
     std::memcpy(&geo.clipmax, &clip_max, 4);
+    StreamScope scope(h);
     HIPCHK(h, hipMemcpyAsync(h->io_sdb.p, mel_power, bytes, hipMemcpyHostToDevice, s));
     HIPCHK(h, hipMemcpyAsync(h->io_rake.p, &geo, sizeof geo, hipMemcpyHostToDevice, s));
     PassParams p{};
     p.n_mels = n_mels; p.n_clips = 1; p.n_frames = n_rows; p.stages = AEGIS_STAGE_MEL;
-    p.frame_off = static_cast<const int64_t *>(h->io_rake.p);
-    p.clipmax = reinterpret_cast<uint32_t *>(static_cast<char *>(h->io_rake.p) + 16);
-    p.melpow = static_cast<float *>(h->io_sdb.p);
-    p.rake_raw = static_cast<uint8_t *>(h->rk_raw.p);
+    p.frame_off = h->io_rake.as<const int64_t>();
+    p.clipmax = reinterpret_cast<uint32_t *>(h->io_rake.as<char>() + 16);
+    p.melpow = h->io_sdb.as<float>();
+    p.rake_raw = h->rk_raw.as<uint8_t>();
     p.rake_ratio = ratio;
     launch_rake_columns(p, from_power != 0, s);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpyAsync(flags_out, h->rk_raw.p, n_rows, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    return AEGIS_OK;
+    return scope.finish();
     } catch (...) { return abi_fail(h); }
 }
 
@@ -674,17 +685,17 @@ int aegis_debug_pitch_bins(aegis_handle *h, const double *periods, int64_t n, in
     int rc;
     if ((rc = ensure(h, h->dbg_bins, (size_t)n * 13)) != AEGIS_OK) return rc;     // periods f64 | table i16 | exact i16 | fell u8
     hipStream_t s = h->stream;
-    double *d_per = static_cast<double *>(h->dbg_bins.p);
+    double *d_per = h->dbg_bins.as<double>();
     int16_t *d_fast = reinterpret_cast<int16_t *>(d_per + n), *d_exact = d_fast + n;
     uint8_t *d_fell = reinterpret_cast<uint8_t *>(d_exact + n);
+    StreamScope scope(h);
     HIPCHK(h, hipMemcpyAsync(d_per, periods, (size_t)n * 8, hipMemcpyHostToDevice, s));
     launch_pitch_bins(base_params(h->tab), h->dt, d_per, n, d_fast, d_exact, d_fell, s);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpyAsync(bin_table, d_fast, (size_t)n * 2, hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipMemcpyAsync(bin_exact, d_exact, (size_t)n * 2, hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipMemcpyAsync(fell_through, d_fell, (size_t)n, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    return AEGIS_OK;
+    return scope.finish();
     } catch (...) { return abi_fail(h); }
 }
 

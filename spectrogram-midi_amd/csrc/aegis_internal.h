@@ -1,7 +1,8 @@
 // What the host-side files of libaegis_hip.so share: the handle, the stream, owned device buffers and events, the error
-// macros.  Internal: not installed, not included by include/aegis_hip.h.
+// macros, the call scope (StreamScope) that drains the stream on every way out of an entry.  Internal: not installed, not
+// included by include/aegis_hip.h.
 //   aegis_api.hip     the batch pipeline (plan input, workspaces, analyze_device_locked, recovery, the analyze entries)
-//   aegis_handle.hip  create / destroy, profiling, tables, parameters, aegis_debug_plan / aegis_debug_fetch
+//   aegis_handle.hip  create / destroy, profiling, the call scope's drain, tables, parameters, aegis_debug_plan / aegis_debug_fetch
 //   aegis_stream.hip  aegis_stream_* (graph capture, commit delivery)
 //   aegis_cqt.hip     CQT, chroma, the filter-bank cache, aegis_estimate_tuning, aegis_rake_patterns
 //   aegis_trend.hip   aegis_trend, aegis_ghost_rsi
@@ -15,9 +16,10 @@
 //   aegis_salience.hip aegis_salience, aegis_cqt_salience (harmonic-sum salience and pitch candidates; kernel in
 //                     salience.hip, the CQT in front of it through aegis_cqt.hip's cqt_host_locked)
 //   aegis_onset.hip   aegis_onset_strength, aegis_onset_detect, aegis_analyze_onsets (onset envelope and onset picking;
-//                     kernels in onset.hip, the mel stage in front of them through aegis_api.hip's mel_host_locked)
+//                     kernels in onset.hip, the mel stage in front of them through aegis_api.hip's mel_host_locked); the
+//                     offsets walks every per-clip entry shares (frame_offsets, clip_frames)
 //   aegis_beat.hip    aegis_tempo, aegis_beat_track, aegis_beat_tables, aegis_analyze_beats (tempogram mean, tempo, beat
-//                     tracker; kernels in beat.hip, the mel stage and onset.hip's envelope kernel in front of them)
+//                     tracker; kernels in beat.hip, the mel stage and aegis_onset.hip's envelope stage in front of them)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -45,6 +47,7 @@ struct DevBuf {
     void *p = nullptr;
     size_t cap = 0;
     bool listed = false;
+    template <class T> T *as() const { return static_cast<T *>(p); }
 };
 
 struct aegis_handle {
@@ -202,17 +205,6 @@ struct aegis_stream {
             return AEGIS_ERR_DEVICE;                                                            \
         }                                                                                       \
     } while (0)
-// HIPCHK for code behind the first asynchronous copy of a call: stream s may still read host vectors of the caller's
-// frame, so an error return waits for it first.
-#define HIPCHK_SYNC(h, s, expr)                                                                 \
-    do {                                                                                        \
-        hipError_t e__ = (expr);                                                                \
-        if (e__ != hipSuccess) {                                                                \
-            (h)->err = std::string(#expr) + ": " + hipGetErrorString(e__);                      \
-            (void)hipStreamSynchronize(s);                                                      \
-            return AEGIS_ERR_DEVICE;                                                            \
-        }                                                                                       \
-    } while (0)
 // h->buf holds at least `bytes` afterwards, and at least 8 (an empty vector still gets a valid pointer), or the caller returns
 // what ensure() answered
 #define ENSURE(h, buf, bytes)                                                                               \
@@ -220,6 +212,8 @@ struct aegis_stream {
         const int rc__ = aegis::ensure(h, (h)->buf, std::max<size_t>((size_t)(bytes), 8));                 \
         if (rc__ != AEGIS_OK) return rc__;                                                                  \
     } while (0)
+// what this header adds to the library without adding to its dynamic symbol table
+#define AEGIS_LOCAL __attribute__((visibility("hidden")))
 #define DEVICE_ONLY(h) \
     do { if ((h)->device < 0) { (h)->err = "handle was created with device=-1 (host tables only)"; return AEGIS_ERR_DEVICE; } } while (0)
 
@@ -246,9 +240,32 @@ void end_event(aegis_handle *h, hipStream_t s);
 void drop_events(aegis_handle *h) noexcept;       // destroys the pairs not collected
 void collect_events(aegis_handle *h);
 
-// One device pass for the whole batch of n independent items (clips, notes, pairs): group(i0, i1) runs items [i0, i1).
-// When its buffers cannot be allocated (AEGIS_ERR_NOMEM) the batch is cut into passes of half as many items and the rest
-// is tried again: an item's result does not depend on the grouping.  Any other failure drops the profiling events.
+// ---- the call scope (its drain: aegis_handle.hip) ----
+// Waits for s, and for the feed stream (stream3) of a plan still in flight.  collect: a failed wait is AEGIS_ERR_DEVICE
+// with a message, and the profiling pairs are collected; otherwise errors are ignored, the pairs dropped, nothing thrown.
+AEGIS_LOCAL int drain_stream(aegis_handle *h, hipStream_t s, bool collect);
+// Asynchronous copies read and write host arrays of an entry's frame, so no way out of the entry may leave that frame before
+// the stream has drained.  THE RULE: declare every host array the stream will read or write, THEN the scope, at the point
+// where the entry (or one run_halving group) starts enqueuing; the arrays then outlive the scope, and every later return
+// (HIPCHK, ENSURE, a validation that fails half way) and every exception is safe.  The good path ends in
+// `return scope.finish();`, the call's one final synchronisation; any other way out waits too and drops the call's
+// profiling pairs.  Handle locked, device set.
+class AEGIS_LOCAL StreamScope {
+    aegis_handle *h;
+    hipStream_t s;
+    bool done = false;
+public:
+    explicit StreamScope(aegis_handle *h_, hipStream_t s_ = nullptr) : h(h_), s(s_ ? s_ : h_->stream) {}
+    StreamScope(const StreamScope &) = delete;
+    StreamScope &operator=(const StreamScope &) = delete;
+    ~StreamScope() { if (!done) (void)drain_stream(h, s, false); }
+    int finish() { done = true; return drain_stream(h, s, true); }
+    void leave_enqueued() { done = true; }        // a caller's stream with sync == 0: no host array is in flight, nothing is waited for
+};
+
+// One device pass for the whole batch of n independent items (clips, notes, pairs): group(i0, i1) runs items [i0, i1)
+// under a StreamScope of its own.  When its buffers cannot be allocated (AEGIS_ERR_NOMEM) the batch is cut into passes of
+// half as many items and the rest is tried again: an item's result does not depend on the grouping.
 template <class F>
 int run_halving(aegis_handle *h, int32_t n, F &&group) {
     int32_t size = n;
@@ -261,7 +278,7 @@ int run_halving(aegis_handle *h, int32_t n, F &&group) {
             size = (size + 1) / 2;
             continue;
         }
-        if (rc != AEGIS_OK) { drop_events(h); return rc; }
+        if (rc != AEGIS_OK) return rc;
         i0 = i1;
     }
     return AEGIS_OK;
@@ -289,10 +306,26 @@ int cqt_host_locked(aegis_handle *h, const float *const *pcm, const int64_t *n_s
 // Handle locked, device set, clips validated (n_samples[i] >= 0, pcm[i] != NULL where there are samples): the samples fed
 // as aegis_analyze_batch feeds them and the pipeline's AEGIS_STAGE_MEL pass enqueued on the handle's stream into io_sdb
 // (per clip [n_mels, F_c], clip after clip, the caller's order; a clip without samples is one frame of silence).  Not
-// synchronised: the caller enqueues behind it, synchronises the stream and clears plan_in_flight.  off / foff: sample and
-// frame offsets [n_clips + 1]; off must outlive that synchronisation.
+// synchronised: the caller enqueues behind it, and the caller's StreamScope drains the stream and the feed and clears
+// plan_in_flight.  off / foff: sample and frame offsets [n_clips + 1], declared before that scope.
 int mel_host_locked(aegis_handle *h, const float *const *pcm, const int64_t *n_samples, int32_t n_clips, std::vector<int64_t> &off,
                     std::vector<int64_t> &foff);
+
+// ---- the offsets walks and the onset stage as parts of another entry (aegis_onset.hip) ----
+// n_frames[] -> foff [n_clips + 1] and the longest clip, or AEGIS_ERR_INVALID: clip_pre + "bad clip <c>", call_pre + "too
+// many frames for one call".
+AEGIS_LOCAL int frame_offsets(aegis_handle *h, const char *clip_pre, const char *call_pre, const int64_t *n_frames, int32_t n_clips,
+                  std::vector<int64_t> &foff, int64_t &maxF);
+// The same over clips of samples, a clip of n samples being 1 + n / hop frames (pcm[c] != NULL where there are samples);
+// one prefix for both messages.
+AEGIS_LOCAL int clip_frames(aegis_handle *h, const char *pre, const float *const *pcm, const int64_t *n_samples, int32_t n_clips,
+                std::vector<int64_t> &foff, int64_t &maxF);
+struct OnsetParams;
+// the onset request with its defaults filled in, or AEGIS_ERR_INVALID with a message
+AEGIS_LOCAL int onset_request(aegis_handle *h, const aegis_onset_params *p, OnsetParams &o);
+// The envelope kernel over d_img / d_foff (device) into on_env (handle locked, device set); enqueued only.
+AEGIS_LOCAL int onset_env_locked(aegis_handle *h, const float *d_img, const int64_t *d_foff, int32_t n_clips, int64_t F, int64_t maxF, int32_t n_mels,
+                     const OnsetParams &o);
 
 // ---- kernel parameters every entry fills the same way (aegis_api.hip) ----
 struct RakeBounds { int min_frames, max_frames; };

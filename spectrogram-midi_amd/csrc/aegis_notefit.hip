@@ -82,32 +82,35 @@ int run_fit(aegis_handle *h, int32_t sr, FitBatch &B) {
     ENSURE(h, nf_notes, B.fn.size() * sizeof(FitNote)); ENSURE(h, nf_boff, B.block_off.size() * 8); ENSURE(h, nf_peak, B.oscs.size() * 8);
     ENSURE(h, nf_cnum, (size_t)B.n_feat * 8); ENSURE(h, nf_cden, (size_t)B.n_feat * 8); ENSURE(h, nf_zc, (size_t)B.n_feat * 4); ENSURE(h, nf_rms, (size_t)B.n_rms * 8);
     ENSURE(h, nf_out, B.cd.size() * 32); ENSURE(h, nf_best, B.fn.size() * 4);
-    HIPCHK_SYNC(h, s, upload(h->nf_audio, B.pcm.data(), B.pcm.size() * 8, s));
-    HIPCHK_SYNC(h, s, upload(h->nf_oscs, B.oscs.data(), B.oscs.size() * sizeof(AdsrOsc), s));
-    HIPCHK_SYNC(h, s, upload(h->nf_cands, B.cd.data(), B.cd.size() * sizeof(AdsrNote), s));
-    HIPCHK_SYNC(h, s, upload(h->nf_notes, B.fn.data(), B.fn.size() * sizeof(FitNote), s));
-    HIPCHK_SYNC(h, s, upload(h->nf_boff, B.block_off.data(), B.block_off.size() * 8, s));
+    std::vector<int64_t> sig_off;                     // (store mode's tables: host arrays, so in front of the scope)
+    std::vector<AdsrNote> stored;
+    B.out.resize(B.cd.size() * 4);
+    B.best.resize(B.fn.size());
+    StreamScope scope(h);
+    HIPCHK(h, upload(h->nf_audio, B.pcm.data(), B.pcm.size() * 8, s));
+    HIPCHK(h, upload(h->nf_oscs, B.oscs.data(), B.oscs.size() * sizeof(AdsrOsc), s));
+    HIPCHK(h, upload(h->nf_cands, B.cd.data(), B.cd.size() * sizeof(AdsrNote), s));
+    HIPCHK(h, upload(h->nf_notes, B.fn.data(), B.fn.size() * sizeof(FitNote), s));
+    HIPCHK(h, upload(h->nf_boff, B.block_off.data(), B.block_off.size() * 8, s));
     FitArgs a{};
-    a.audio = static_cast<const double *>(h->nf_audio.p);
-    a.oscs = static_cast<const AdsrOsc *>(h->nf_oscs.p);
-    a.cands = static_cast<const AdsrNote *>(h->nf_cands.p);
-    a.notes = static_cast<const FitNote *>(h->nf_notes.p);
-    a.block_off = static_cast<const int64_t *>(h->nf_boff.p);
+    a.audio = h->nf_audio.as<const double>();
+    a.oscs = h->nf_oscs.as<const AdsrOsc>();
+    a.cands = h->nf_cands.as<const AdsrNote>();
+    a.notes = h->nf_notes.as<const FitNote>();
+    a.block_off = h->nf_boff.as<const int64_t>();
     a.n_oscs = (int32_t)B.oscs.size(); a.n_cands = (int32_t)B.cd.size(); a.n_notes = (int32_t)B.fn.size();
     a.n_blocks = B.n_blocks;
     a.bin_hz = 1.0 / ((double)kFitFft * (1.0 / (double)sr));
     a.hann = h->dt.hann; a.twiddle = h->dt.twiddle;
-    a.osc_peak = static_cast<double *>(h->nf_peak.p);
-    a.cnum = static_cast<double *>(h->nf_cnum.p); a.cden = static_cast<double *>(h->nf_cden.p);
-    a.zc = static_cast<int32_t *>(h->nf_zc.p); a.rms = static_cast<double *>(h->nf_rms.p);
-    a.out = static_cast<double *>(h->nf_out.p); a.best = static_cast<int32_t *>(h->nf_best.p);
+    a.osc_peak = h->nf_peak.as<double>();
+    a.cnum = h->nf_cnum.as<double>(); a.cden = h->nf_cden.as<double>();
+    a.zc = h->nf_zc.as<int32_t>(); a.rms = h->nf_rms.as<double>();
+    a.out = h->nf_out.as<double>(); a.best = h->nf_best.as<int32_t>();
     begin_event(h, "notefit_peak", s);
     launch_adsr_peak(a.oscs, a.osc_peak, a.n_oscs, s);
     end_event(h, s);
     // Store mode (AEGIS_NOTEFIT_STORE=1, measured against the default in DESIGN.md 3.14): every synthesised candidate is
     // rendered once behind the slices, and the frames read it as they read a given signal: the same values, so the same bits.
-    std::vector<int64_t> sig_off;
-    std::vector<AdsrNote> stored;
     if (store) {
         int64_t at = (int64_t)B.pcm.size();
         stored = B.cd;
@@ -119,13 +122,13 @@ int run_fit(aegis_handle *h, int32_t sr, FitBatch &B) {
             at += B.cd[c].n_cut;
         }
         ENSURE(h, nf_sigoff, sig_off.size() * 8); ENSURE(h, nf_cands2, stored.size() * sizeof(AdsrNote));
-        HIPCHK_SYNC(h, s, upload(h->nf_sigoff, sig_off.data(), sig_off.size() * 8, s));
-        HIPCHK_SYNC(h, s, upload(h->nf_cands2, stored.data(), stored.size() * sizeof(AdsrNote), s));
+        HIPCHK(h, upload(h->nf_sigoff, sig_off.data(), sig_off.size() * 8, s));
+        HIPCHK(h, upload(h->nf_cands2, stored.data(), stored.size() * sizeof(AdsrNote), s));
         begin_event(h, "notefit_store", s);
-        launch_adsr_render(a.oscs, a.cands, a.osc_peak, static_cast<const int64_t *>(h->nf_sigoff.p), static_cast<double *>(h->nf_audio.p),
+        launch_adsr_render(a.oscs, a.cands, a.osc_peak, h->nf_sigoff.as<const int64_t>(), h->nf_audio.as<double>(),
                               a.n_cands, s);
         end_event(h, s);
-        a.cands = static_cast<const AdsrNote *>(h->nf_cands2.p);
+        a.cands = h->nf_cands2.as<const AdsrNote>();
     }
     begin_event(h, "notefit_feat", s);
     launch_notefit_feat(a, s);
@@ -133,14 +136,10 @@ int run_fit(aegis_handle *h, int32_t sr, FitBatch &B) {
     begin_event(h, "notefit_score", s);
     launch_notefit_score(a, s);
     end_event(h, s);
-    HIPCHK_SYNC(h, s, hipGetLastError());
-    B.out.resize(B.cd.size() * 4);
-    B.best.resize(B.fn.size());
-    HIPCHK_SYNC(h, s, hipMemcpyAsync(B.out.data(), a.out, B.out.size() * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK_SYNC(h, s, hipMemcpyAsync(B.best.data(), a.best, B.best.size() * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK_SYNC(h, s, hipStreamSynchronize(s));
-    if (h->profiling) collect_events(h);
-    return AEGIS_OK;
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(B.out.data(), a.out, B.out.size() * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(B.best.data(), a.best, B.best.size() * 4, hipMemcpyDeviceToHost, s));
+    return scope.finish();
 }
 
 // notes [k0, k1) as one device pass (handle locked, request validated)
@@ -294,17 +293,18 @@ int64_t aegis_synth_one_note(aegis_handle *h, int32_t sample_rate, double freq, 
     const int64_t zero = 0;
     hipStream_t s = h->stream;
     ENSURE(h, nf_oscs, sizeof o); ENSURE(h, nf_cands, sizeof c); ENSURE(h, nf_peak, 8); ENSURE(h, nf_boff, 8); ENSURE(h, nf_sig, (size_t)o.n * 8);
-    HIPCHK_SYNC(h, s, upload(h->nf_oscs, &o, sizeof o, s));
-    HIPCHK_SYNC(h, s, upload(h->nf_cands, &c, sizeof c, s));
-    HIPCHK_SYNC(h, s, upload(h->nf_boff, &zero, 8, s));
-    launch_adsr_peak(static_cast<const AdsrOsc *>(h->nf_oscs.p), static_cast<double *>(h->nf_peak.p), 1, s);
-    launch_adsr_render(static_cast<const AdsrOsc *>(h->nf_oscs.p), static_cast<const AdsrNote *>(h->nf_cands.p),
-                          static_cast<const double *>(h->nf_peak.p), static_cast<const int64_t *>(h->nf_boff.p),
-                          static_cast<double *>(h->nf_sig.p), 1, s);
-    HIPCHK_SYNC(h, s, hipGetLastError());
-    HIPCHK_SYNC(h, s, hipMemcpyAsync(out, h->nf_sig.p, (size_t)o.n * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK_SYNC(h, s, hipStreamSynchronize(s));
-    return o.n;
+    StreamScope scope(h);
+    HIPCHK(h, upload(h->nf_oscs, &o, sizeof o, s));
+    HIPCHK(h, upload(h->nf_cands, &c, sizeof c, s));
+    HIPCHK(h, upload(h->nf_boff, &zero, 8, s));
+    launch_adsr_peak(h->nf_oscs.as<const AdsrOsc>(), h->nf_peak.as<double>(), 1, s);
+    launch_adsr_render(h->nf_oscs.as<const AdsrOsc>(), h->nf_cands.as<const AdsrNote>(),
+                          h->nf_peak.as<const double>(), h->nf_boff.as<const int64_t>(),
+                          h->nf_sig.as<double>(), 1, s);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(out, h->nf_sig.p, (size_t)o.n * 8, hipMemcpyDeviceToHost, s));
+    const int rc = scope.finish();
+    return rc != AEGIS_OK ? rc : o.n;
     } catch (...) { return abi_fail(h); }
 }
 

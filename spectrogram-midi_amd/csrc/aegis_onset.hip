@@ -2,16 +2,36 @@
 // mel images and the onset frames picked from it (onset.h states the semantics; the kernels are in onset.hip).  The first
 // two take the caller's images / envelopes from host memory; the third runs the handle's own mel stage (aegis_api.hip's
 // mel_host_locked: the launches of aegis_analyze_batch(AEGIS_STAGE_MEL)) into the handle's device buffer and both kernels
-// behind it, so only the envelope and the masks cross PCIe.
+// behind it, so only the envelope and the masks cross PCIe.  Also the offsets walks of every per-clip entry.
 #include "aegis_internal.h"
 #include "onset.h"
 
 using namespace aegis;
 
-namespace {
+int aegis::frame_offsets(aegis_handle *h, const char *clip_pre, const char *call_pre, const int64_t *n_frames, int32_t n_clips,
+                         std::vector<int64_t> &foff, int64_t &maxF) {
+    foff.assign((size_t)n_clips + 1, 0);
+    maxF = 0;
+    for (int32_t c = 0; c < n_clips; ++c) {
+        if (n_frames[c] < 0) { h->err = clip_pre + ("bad clip " + std::to_string(c)); return AEGIS_ERR_INVALID; }
+        foff[(size_t)c + 1] = foff[(size_t)c] + n_frames[c];
+        maxF = std::max(maxF, n_frames[c]);
+    }
+    if (maxF > INT32_MAX) { h->err = std::string(call_pre) + "too many frames for one call"; return AEGIS_ERR_INVALID; }
+    return AEGIS_OK;
+}
 
-// the request with its defaults filled in, or AEGIS_ERR_INVALID with a message
-int ons_request(aegis_handle *h, const aegis_onset_params *p, OnsetParams &o) {
+int aegis::clip_frames(aegis_handle *h, const char *pre, const float *const *pcm, const int64_t *n_samples, int32_t n_clips,
+                       std::vector<int64_t> &foff, int64_t &maxF) {
+    std::vector<int64_t> nf((size_t)std::max(n_clips, 0));
+    for (int32_t c = 0; c < n_clips; ++c) {
+        if (n_samples[c] < 0 || (n_samples[c] > 0 && !pcm[c])) { h->err = pre + ("bad clip " + std::to_string(c)); return AEGIS_ERR_INVALID; }
+        nf[(size_t)c] = 1 + n_samples[c] / h->tab.hop;
+    }
+    return frame_offsets(h, pre, pre, nf.data(), n_clips, foff, maxF);
+}
+
+int aegis::onset_request(aegis_handle *h, const aegis_onset_params *p, OnsetParams &o) {
     const aegis_onset_params all{-1, -1, -1, -1, -1, -1, -1, -1, -1, 0, -1.0};
     if (!p) p = &all;
     const char *msg = onset_fill(h->tab.sr, h->tab.hop, h->tab.n_fft, p->lag, p->max_size, p->shift, p->pre_max, p->post_max, p->pre_avg,
@@ -20,47 +40,40 @@ int ons_request(aegis_handle *h, const aegis_onset_params *p, OnsetParams &o) {
     return AEGIS_OK;
 }
 
-// n_frames[] -> offsets and the longest clip, or AEGIS_ERR_INVALID
-int ons_frames(aegis_handle *h, const int64_t *n_frames, int32_t n_clips, std::vector<int64_t> &foff, int64_t &maxF) {
-    if (n_clips < 0 || (n_clips > 0 && !n_frames)) { h->err = "onset: null argument"; return AEGIS_ERR_INVALID; }
-    foff.assign((size_t)n_clips + 1, 0);
-    maxF = 0;
-    for (int32_t c = 0; c < n_clips; ++c) {
-        if (n_frames[c] < 0) { h->err = "onset: bad clip " + std::to_string(c); return AEGIS_ERR_INVALID; }
-        foff[(size_t)c + 1] = foff[(size_t)c] + n_frames[c];
-        maxF = std::max(maxF, n_frames[c]);
-    }
-    if (maxF > INT32_MAX) { h->err = "onset: too many frames for one call"; return AEGIS_ERR_INVALID; }
-    return AEGIS_OK;
-}
-
-// The envelope kernel over d_img / d_foff (device) into on_env (handle locked, device set); enqueued only.
-int ons_env_locked(aegis_handle *h, const float *d_img, const int64_t *d_foff, int32_t n_clips, int64_t F, int64_t maxF, int32_t n_mels,
-                   const OnsetParams &o) {
+int aegis::onset_env_locked(aegis_handle *h, const float *d_img, const int64_t *d_foff, int32_t n_clips, int64_t F, int64_t maxF,
+                            int32_t n_mels, const OnsetParams &o) {
     hipStream_t s = h->stream;
     ENSURE(h, on_env, (size_t)F * 4);
     begin_event(h, "onset_env", s);
-    launch_onset_env(d_img, d_foff, n_clips, maxF, n_mels, o, static_cast<float *>(h->on_env.p), s);
+    launch_onset_env(d_img, d_foff, n_clips, maxF, n_mels, o, h->on_env.as<float>(), s);
     end_event(h, s);
-    HIPCHK_SYNC(h, s, hipGetLastError());
+    HIPCHK(h, hipGetLastError());
     return AEGIS_OK;
 }
 
+namespace {
+
+// n_frames[] -> offsets and the longest clip, or AEGIS_ERR_INVALID
+int ons_frames(aegis_handle *h, const int64_t *n_frames, int32_t n_clips, std::vector<int64_t> &foff, int64_t &maxF) {
+    if (n_clips < 0 || (n_clips > 0 && !n_frames)) { h->err = "onset: null argument"; return AEGIS_ERR_INVALID; }
+    return frame_offsets(h, "onset: ", "onset: ", n_frames, n_clips, foff, maxF);
+}
+
 // The pick kernel over d_env / d_energy / d_foff (device) and its results back to the host (handle locked, device set);
-// the copies are enqueued, the caller synchronises.
+// the copies are enqueued, the caller's scope synchronises.
 int ons_pick_locked(aegis_handle *h, const float *d_env, const float *d_energy, const int64_t *d_foff, int32_t n_clips, int64_t F,
                     const OnsetParams &o, uint8_t *onset_mask, int32_t *onset_back, int64_t *n_onsets) {
     hipStream_t s = h->stream;
     ENSURE(h, on_x, (size_t)F * 4); ENSURE(h, on_mask, (size_t)F); ENSURE(h, on_count, (size_t)n_clips * 8);
     if (onset_back) ENSURE(h, on_back, (size_t)F * 4);
     begin_event(h, "onset_pick", s);
-    launch_onset_pick(d_env, d_energy, d_foff, n_clips, o, static_cast<float *>(h->on_x.p), static_cast<uint8_t *>(h->on_mask.p),
-                      onset_back ? static_cast<int32_t *>(h->on_back.p) : nullptr, static_cast<int64_t *>(h->on_count.p), s);
+    launch_onset_pick(d_env, d_energy, d_foff, n_clips, o, h->on_x.as<float>(), h->on_mask.as<uint8_t>(),
+                      onset_back ? h->on_back.as<int32_t>() : nullptr, h->on_count.as<int64_t>(), s);
     end_event(h, s);
-    HIPCHK_SYNC(h, s, hipGetLastError());
-    if (F) HIPCHK_SYNC(h, s, hipMemcpyAsync(onset_mask, h->on_mask.p, (size_t)F, hipMemcpyDeviceToHost, s));
-    if (F && onset_back) HIPCHK_SYNC(h, s, hipMemcpyAsync(onset_back, h->on_back.p, (size_t)F * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK_SYNC(h, s, hipMemcpyAsync(n_onsets, h->on_count.p, (size_t)n_clips * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipGetLastError());
+    if (F) HIPCHK(h, hipMemcpyAsync(onset_mask, h->on_mask.p, (size_t)F, hipMemcpyDeviceToHost, s));
+    if (F && onset_back) HIPCHK(h, hipMemcpyAsync(onset_back, h->on_back.p, (size_t)F * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(n_onsets, h->on_count.p, (size_t)n_clips * 8, hipMemcpyDeviceToHost, s));
     return AEGIS_OK;
 }
 
@@ -74,7 +87,7 @@ int aegis_onset_strength(aegis_handle *h, const float *S_dB, const int64_t *n_fr
     if (!h) return AEGIS_ERR_INVALID;
     std::lock_guard<std::mutex> lock(h->mu);
     OnsetParams o;
-    int rc = ons_request(h, p, o);
+    int rc = onset_request(h, p, o);
     if (rc != AEGIS_OK) return rc;
     if (n_mels < 1 || n_mels > kOnsMaxMels) { h->err = "onset: n_mels must be 1..256"; return AEGIS_ERR_INVALID; }
     std::vector<int64_t> foff;
@@ -88,18 +101,12 @@ int aegis_onset_strength(aegis_handle *h, const float *S_dB, const int64_t *n_fr
     hipStream_t s = h->stream;
     ENSURE(h, on_img, (size_t)F * n_mels * 4); ENSURE(h, on_foff, foff.size() * 8);
     drop_events(h);
-    HIPCHK_SYNC(h, s, upload(h->on_img, S_dB, (size_t)F * n_mels * 4, s));
-    HIPCHK_SYNC(h, s, upload(h->on_foff, foff.data(), foff.size() * 8, s));
-    rc = ons_env_locked(h, static_cast<const float *>(h->on_img.p), static_cast<const int64_t *>(h->on_foff.p), n_clips, F, maxF, n_mels, o);
-    if (rc == AEGIS_OK) {
-        const hipError_t e = hipMemcpyAsync(env_out, h->on_env.p, (size_t)F * 4, hipMemcpyDeviceToHost, s);
-        if (e != hipSuccess) { h->err = std::string("hipMemcpyAsync(env_out): ") + hipGetErrorString(e); rc = AEGIS_ERR_DEVICE; }
-    }
-    const hipError_t e = hipStreamSynchronize(s);               // foff dies with this frame, whatever happened
-    if (rc != AEGIS_OK) return rc;
-    HIPCHK(h, e);
-    if (h->profiling) collect_events(h);
-    return AEGIS_OK;
+    StreamScope scope(h);
+    HIPCHK(h, upload(h->on_img, S_dB, (size_t)F * n_mels * 4, s));
+    HIPCHK(h, upload(h->on_foff, foff.data(), foff.size() * 8, s));
+    if ((rc = onset_env_locked(h, h->on_img.as<const float>(), h->on_foff.as<const int64_t>(), n_clips, F, maxF, n_mels, o)) != AEGIS_OK) return rc;
+    HIPCHK(h, hipMemcpyAsync(env_out, h->on_env.p, (size_t)F * 4, hipMemcpyDeviceToHost, s));
+    return scope.finish();
     } catch (...) { return abi_fail(h); }
 }
 
@@ -109,7 +116,7 @@ int aegis_onset_detect(aegis_handle *h, const float *env, const float *energy, c
     if (!h) return AEGIS_ERR_INVALID;
     std::lock_guard<std::mutex> lock(h->mu);
     OnsetParams o;
-    int rc = ons_request(h, p, o);
+    int rc = onset_request(h, p, o);
     if (rc != AEGIS_OK) return rc;
     std::vector<int64_t> foff;
     int64_t maxF = 0;
@@ -123,16 +130,13 @@ int aegis_onset_detect(aegis_handle *h, const float *env, const float *energy, c
     ENSURE(h, on_env, (size_t)F * 4); ENSURE(h, on_foff, foff.size() * 8);
     if (energy) ENSURE(h, on_energy, (size_t)F * 4);
     drop_events(h);
-    HIPCHK_SYNC(h, s, upload(h->on_env, env, (size_t)F * 4, s));
-    if (energy) HIPCHK_SYNC(h, s, upload(h->on_energy, energy, (size_t)F * 4, s));
-    HIPCHK_SYNC(h, s, upload(h->on_foff, foff.data(), foff.size() * 8, s));
-    rc = ons_pick_locked(h, static_cast<const float *>(h->on_env.p), energy ? static_cast<const float *>(h->on_energy.p) : nullptr,
-                         static_cast<const int64_t *>(h->on_foff.p), n_clips, F, o, onset_mask, onset_back, n_onsets);
-    const hipError_t e = hipStreamSynchronize(s);               // foff dies with this frame, whatever happened
-    if (rc != AEGIS_OK) return rc;
-    HIPCHK(h, e);
-    if (h->profiling) collect_events(h);
-    return AEGIS_OK;
+    StreamScope scope(h);
+    HIPCHK(h, upload(h->on_env, env, (size_t)F * 4, s));
+    if (energy) HIPCHK(h, upload(h->on_energy, energy, (size_t)F * 4, s));
+    HIPCHK(h, upload(h->on_foff, foff.data(), foff.size() * 8, s));
+    rc = ons_pick_locked(h, h->on_env.as<const float>(), energy ? h->on_energy.as<const float>() : nullptr, h->on_foff.as<const int64_t>(),
+                         n_clips, F, o, onset_mask, onset_back, n_onsets);
+    return rc != AEGIS_OK ? rc : scope.finish();
     } catch (...) { return abi_fail(h); }
 }
 
@@ -142,7 +146,7 @@ int aegis_analyze_onsets(aegis_handle *h, const float *const *pcm, const int64_t
     if (!h) return AEGIS_ERR_INVALID;
     std::lock_guard<std::mutex> lock(h->mu);
     OnsetParams o;
-    int rc = ons_request(h, p, o);
+    int rc = onset_request(h, p, o);
     if (rc != AEGIS_OK) return rc;
     if (h->tab.n_mels < 1 || h->tab.n_mels > kOnsMaxMels) { h->err = "onset: n_mels must be 1..256"; return AEGIS_ERR_INVALID; }
     if (n_clips < 0 || (n_clips > 0 && (!pcm || !n_samples))) { h->err = "onset: null argument"; return AEGIS_ERR_INVALID; }
@@ -150,40 +154,24 @@ int aegis_analyze_onsets(aegis_handle *h, const float *const *pcm, const int64_t
         h->err = "onset: null argument (env_out or onset_mask is needed; onset_mask needs n_onsets, onset_back needs onset_mask)";
         return AEGIS_ERR_INVALID;
     }
+    std::vector<int64_t> off, foff;
     int64_t maxF = 0;
-    for (int32_t c = 0; c < n_clips; ++c) {
-        if (n_samples[c] < 0 || (n_samples[c] > 0 && !pcm[c])) { h->err = "onset: bad clip " + std::to_string(c); return AEGIS_ERR_INVALID; }
-        maxF = std::max<int64_t>(maxF, 1 + n_samples[c] / h->tab.hop);
-    }
-    if (maxF > INT32_MAX) { h->err = "onset: too many frames for one call"; return AEGIS_ERR_INVALID; }
+    if ((rc = clip_frames(h, "onset: ", pcm, n_samples, n_clips, foff, maxF)) != AEGIS_OK) return rc;
     DEVICE_ONLY(h);
     if (n_clips == 0) return AEGIS_OK;
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
-    std::vector<int64_t> off, foff;                            // (they outlive the synchronisation below)
-    rc = mel_host_locked(h, pcm, n_samples, n_clips, off, foff);
-    const int64_t F = foff.empty() ? 0 : foff[(size_t)n_clips];
-    if (rc == AEGIS_OK) rc = ensure(h, h->on_foff, foff.size() * 8);
-    if (rc == AEGIS_OK) {
-        const hipError_t e = upload(h->on_foff, foff.data(), foff.size() * 8, s);
-        if (e != hipSuccess) { h->err = std::string("upload of the frame offsets: ") + hipGetErrorString(e); rc = AEGIS_ERR_DEVICE; }
-    }
-    const int64_t *d_foff = static_cast<const int64_t *>(h->on_foff.p);
-    if (rc == AEGIS_OK) rc = ons_env_locked(h, static_cast<const float *>(h->io_sdb.p), d_foff, n_clips, F, maxF, h->tab.n_mels, o);
-    if (rc == AEGIS_OK && env_out) {
-        const hipError_t e = hipMemcpyAsync(env_out, h->on_env.p, (size_t)F * 4, hipMemcpyDeviceToHost, s);
-        if (e != hipSuccess) { h->err = std::string("hipMemcpyAsync(env_out): ") + hipGetErrorString(e); rc = AEGIS_ERR_DEVICE; }
-    }
-    if (rc == AEGIS_OK && onset_mask)
-        rc = ons_pick_locked(h, static_cast<const float *>(h->on_env.p), nullptr, d_foff, n_clips, F, o, onset_mask, onset_back, n_onsets);
-    // the feed's copies and the pipeline may still read pcm, off and foff: drained on every path
-    const hipError_t e3 = hipStreamSynchronize(h->stream3), e = hipStreamSynchronize(s);
-    h->plan_in_flight = false;
-    if (rc != AEGIS_OK) { drop_events(h); return rc; }
-    HIPCHK(h, e3);
-    HIPCHK(h, e);
-    if (h->profiling) collect_events(h);
-    return AEGIS_OK;
+    StreamScope scope(h);                                       // the feed's copies and the pipeline read pcm, off and foff
+    if ((rc = mel_host_locked(h, pcm, n_samples, n_clips, off, foff)) != AEGIS_OK) return rc;
+    const int64_t F = foff[(size_t)n_clips];
+    ENSURE(h, on_foff, foff.size() * 8);
+    HIPCHK(h, upload(h->on_foff, foff.data(), foff.size() * 8, s));
+    const int64_t *d_foff = h->on_foff.as<const int64_t>();
+    if ((rc = onset_env_locked(h, h->io_sdb.as<const float>(), d_foff, n_clips, F, maxF, h->tab.n_mels, o)) != AEGIS_OK) return rc;
+    if (env_out) HIPCHK(h, hipMemcpyAsync(env_out, h->on_env.p, (size_t)F * 4, hipMemcpyDeviceToHost, s));
+    if (onset_mask && (rc = ons_pick_locked(h, h->on_env.as<const float>(), nullptr, d_foff, n_clips, F, o, onset_mask, onset_back, n_onsets)) != AEGIS_OK)
+        return rc;
+    return scope.finish();
     } catch (...) { return abi_fail(h); }
 }
 

@@ -25,7 +25,7 @@ int sal_request(aegis_handle *h, int32_t n_bins, int32_t bpo, const aegis_salien
 }
 
 // The kernel over d_mag / d_foff (device) and the results back to the host (handle locked, device set); F: frames of all
-// clips, maxF: of the longest.  Blocking.
+// clips, maxF: of the longest.  The copies are enqueued, the caller's scope synchronises.
 int sal_run_locked(aegis_handle *h, const float *d_mag, const int64_t *d_foff, int32_t n_clips, int64_t F, int64_t maxF, const SalTables &T,
                    const SalFrameParams &fp, float *sal_out, int32_t *cand_bin, float *cand_sal, float *cand_shift) {
     hipStream_t s = h->stream;
@@ -33,18 +33,16 @@ int sal_run_locked(aegis_handle *h, const float *d_mag, const int64_t *d_foff, i
     if (sal_out) ENSURE(h, sl_img, img);
     ENSURE(h, sl_bin, slots); ENSURE(h, sl_sal, slots); ENSURE(h, sl_shift, slots);
     begin_event(h, "salience", s);
-    launch_salience(d_mag, d_foff, n_clips, maxF, T, fp, sal_out ? static_cast<float *>(h->sl_img.p) : nullptr,
-                    static_cast<int32_t *>(h->sl_bin.p), static_cast<float *>(h->sl_sal.p), static_cast<float *>(h->sl_shift.p), s);
+    launch_salience(d_mag, d_foff, n_clips, maxF, T, fp, sal_out ? h->sl_img.as<float>() : nullptr,
+                    h->sl_bin.as<int32_t>(), h->sl_sal.as<float>(), h->sl_shift.as<float>(), s);
     end_event(h, s);
-    HIPCHK_SYNC(h, s, hipGetLastError());
-    if (sal_out && img) HIPCHK_SYNC(h, s, hipMemcpyAsync(sal_out, h->sl_img.p, img, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipGetLastError());
+    if (sal_out && img) HIPCHK(h, hipMemcpyAsync(sal_out, h->sl_img.p, img, hipMemcpyDeviceToHost, s));
     if (slots) {
-        HIPCHK_SYNC(h, s, hipMemcpyAsync(cand_bin, h->sl_bin.p, slots, hipMemcpyDeviceToHost, s));
-        HIPCHK_SYNC(h, s, hipMemcpyAsync(cand_sal, h->sl_sal.p, slots, hipMemcpyDeviceToHost, s));
-        HIPCHK_SYNC(h, s, hipMemcpyAsync(cand_shift, h->sl_shift.p, slots, hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipMemcpyAsync(cand_bin, h->sl_bin.p, slots, hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipMemcpyAsync(cand_sal, h->sl_sal.p, slots, hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipMemcpyAsync(cand_shift, h->sl_shift.p, slots, hipMemcpyDeviceToHost, s));
     }
-    HIPCHK(h, hipStreamSynchronize(s));
-    if (h->profiling) collect_events(h);
     return AEGIS_OK;
 }
 
@@ -61,28 +59,23 @@ int aegis_salience(aegis_handle *h, const float *mag, const int64_t *n_frames, i
     SalTables T; SalFrameParams fp;
     int rc = sal_request(h, n_bins, bins_per_octave, p, cand_bin, cand_sal, cand_shift, T, fp);
     if (rc != AEGIS_OK) return rc;
-    std::vector<int64_t> foff((size_t)n_clips + 1, 0);
+    std::vector<int64_t> foff;
     int64_t maxF = 0;
-    for (int32_t c = 0; c < n_clips; ++c) {
-        if (n_frames[c] < 0) { h->err = "bad clip " + std::to_string(c); return AEGIS_ERR_INVALID; }
-        foff[(size_t)c + 1] = foff[(size_t)c] + n_frames[c];
-        maxF = std::max(maxF, n_frames[c]);
-    }
+    if ((rc = frame_offsets(h, "", "salience: ", n_frames, n_clips, foff, maxF)) != AEGIS_OK) return rc;
     const int64_t F = foff[(size_t)n_clips];
     if (F > 0 && !mag) { h->err = "null argument"; return AEGIS_ERR_INVALID; }
-    if (maxF > INT32_MAX) { h->err = "salience: too many frames for one call"; return AEGIS_ERR_INVALID; }
     DEVICE_ONLY(h);
     if (F == 0) return AEGIS_OK;
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
     ENSURE(h, sl_mag, (size_t)F * n_bins * 4); ENSURE(h, sl_foff, foff.size() * 8);
     drop_events(h);
-    HIPCHK_SYNC(h, s, upload(h->sl_mag, mag, (size_t)F * n_bins * 4, s));
-    HIPCHK_SYNC(h, s, upload(h->sl_foff, foff.data(), foff.size() * 8, s));
-    rc = sal_run_locked(h, static_cast<const float *>(h->sl_mag.p), static_cast<const int64_t *>(h->sl_foff.p), n_clips, F, maxF, T, fp,
+    StreamScope scope(h);
+    HIPCHK(h, upload(h->sl_mag, mag, (size_t)F * n_bins * 4, s));
+    HIPCHK(h, upload(h->sl_foff, foff.data(), foff.size() * 8, s));
+    rc = sal_run_locked(h, h->sl_mag.as<const float>(), h->sl_foff.as<const int64_t>(), n_clips, F, maxF, T, fp,
                         sal_out, cand_bin, cand_sal, cand_shift);
-    if (rc != AEGIS_OK) (void)hipStreamSynchronize(s);         // foff dies with this frame
-    return rc;
+    return rc != AEGIS_OK ? rc : scope.finish();
     } catch (...) { return abi_fail(h); }
 }
 
@@ -103,11 +96,14 @@ int aegis_cqt_salience(aegis_handle *h, const float *const *pcm, const int64_t *
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
     int64_t F = 0, maxF = 0;
+    std::vector<int64_t> foff;
+    StreamScope scope(h);
     if ((rc = cqt_host_locked(h, pcm, n_samples, n_clips, n_bins, bins_per_octave, fmin, filter_scale, 0, nullptr, &F)) != AEGIS_OK) return rc;
-    for (int32_t c = 0; c < n_clips; ++c) maxF = std::max<int64_t>(maxF, 1 + n_samples[c] / h->tab.hop);
-    if (mag_out) HIPCHK_SYNC(h, s, hipMemcpyAsync(mag_out, h->q_out.p, (size_t)F * n_bins * 4, hipMemcpyDeviceToHost, s));
-    return sal_run_locked(h, static_cast<const float *>(h->q_out.p), static_cast<const int64_t *>(h->q_foff.p), n_clips, F, maxF, T, fp,
-                          sal_out, cand_bin, cand_sal, cand_shift);
+    if ((rc = clip_frames(h, "", pcm, n_samples, n_clips, foff, maxF)) != AEGIS_OK) return rc;
+    if (mag_out) HIPCHK(h, hipMemcpyAsync(mag_out, h->q_out.p, (size_t)F * n_bins * 4, hipMemcpyDeviceToHost, s));
+    rc = sal_run_locked(h, h->q_out.as<const float>(), h->q_foff.as<const int64_t>(), n_clips, F, maxF, T, fp,
+                        sal_out, cand_bin, cand_sal, cand_shift);
+    return rc != AEGIS_OK ? rc : scope.finish();
     } catch (...) { return abi_fail(h); }
 }
 

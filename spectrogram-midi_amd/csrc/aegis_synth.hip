@@ -83,7 +83,8 @@ int check_note(aegis_handle *h, int32_t sr, int32_t c, int64_t k, const aegis_sy
 }  // namespace
 
 // The render half of a device pass (handle locked): upload, peaks, mix, master.  Clip c of the batch then lies as int16 at
-// sy_out + B.clip_off[c] once the stream has run; nothing is copied out and nothing is waited for.
+// sy_out + B.clip_off[c] once the stream has run; nothing is copied out and nothing is waited for: B lives in front of
+// the caller's scope.
 // labels: the profiling names of the three kernels.
 int aegis::render_into(aegis_handle *h, const AdsrBatch &B, const char *const (&labels)[3]) {
     if (B.samples == 0) return AEGIS_OK;
@@ -93,37 +94,37 @@ int aegis::render_into(aegis_handle *h, const AdsrBatch &B, const char *const (&
     ENSURE(h, sy_tiles, B.tiles.size() * sizeof(AdsrTile)); ENSURE(h, sy_tile_notes, B.tile_notes.size() * 4);
     ENSURE(h, sy_osc_peak, B.oscs.size() * 8); ENSURE(h, sy_clip_peak, nc * 8);
     ENSURE(h, sy_mix, (size_t)B.samples * 8); ENSURE(h, sy_out, (size_t)B.samples * 2);
-    HIPCHK_SYNC(h, s, upload(h->sy_oscs, B.oscs.data(), B.oscs.size() * sizeof(AdsrOsc), s));
-    HIPCHK_SYNC(h, s, upload(h->sy_notes, B.notes.data(), B.notes.size() * sizeof(AdsrNote), s));
-    HIPCHK_SYNC(h, s, upload(h->sy_tiles, B.tiles.data(), B.tiles.size() * sizeof(AdsrTile), s));
-    HIPCHK_SYNC(h, s, upload(h->sy_tile_notes, B.tile_notes.data(), B.tile_notes.size() * 4, s));
+    HIPCHK(h, upload(h->sy_oscs, B.oscs.data(), B.oscs.size() * sizeof(AdsrOsc), s));
+    HIPCHK(h, upload(h->sy_notes, B.notes.data(), B.notes.size() * sizeof(AdsrNote), s));
+    HIPCHK(h, upload(h->sy_tiles, B.tiles.data(), B.tiles.size() * sizeof(AdsrTile), s));
+    HIPCHK(h, upload(h->sy_tile_notes, B.tile_notes.data(), B.tile_notes.size() * 4, s));
     const AdsrBend *d_bends = nullptr;
     const AdsrSeg *d_segs = nullptr;
     if (!B.segs.empty()) {                                  // bent notes: their segment tables, and every oscillator's slice
         ENSURE(h, sy_bends, B.bends.size() * sizeof(AdsrBend)); ENSURE(h, sy_segs, B.segs.size() * sizeof(AdsrSeg));
-        HIPCHK_SYNC(h, s, upload(h->sy_bends, B.bends.data(), B.bends.size() * sizeof(AdsrBend), s));
-        HIPCHK_SYNC(h, s, upload(h->sy_segs, B.segs.data(), B.segs.size() * sizeof(AdsrSeg), s));
-        d_bends = static_cast<const AdsrBend *>(h->sy_bends.p);
-        d_segs = static_cast<const AdsrSeg *>(h->sy_segs.p);
+        HIPCHK(h, upload(h->sy_bends, B.bends.data(), B.bends.size() * sizeof(AdsrBend), s));
+        HIPCHK(h, upload(h->sy_segs, B.segs.data(), B.segs.size() * sizeof(AdsrSeg), s));
+        d_bends = h->sy_bends.as<const AdsrBend>();
+        d_segs = h->sy_segs.as<const AdsrSeg>();
     }
-    HIPCHK_SYNC(h, s, hipMemsetAsync(h->sy_clip_peak.p, 0, nc * 8, s));
-    const AdsrOsc *d_oscs = static_cast<const AdsrOsc *>(h->sy_oscs.p);
-    const AdsrNote *d_notes = static_cast<const AdsrNote *>(h->sy_notes.p);
-    const AdsrTile *d_tiles = static_cast<const AdsrTile *>(h->sy_tiles.p);
-    double *d_peak = static_cast<double *>(h->sy_osc_peak.p), *d_mix = static_cast<double *>(h->sy_mix.p);
-    unsigned long long *d_cpeak = static_cast<unsigned long long *>(h->sy_clip_peak.p);
-    int16_t *d_out = static_cast<int16_t *>(h->sy_out.p);
+    HIPCHK(h, hipMemsetAsync(h->sy_clip_peak.p, 0, nc * 8, s));
+    const AdsrOsc *d_oscs = h->sy_oscs.as<const AdsrOsc>();
+    const AdsrNote *d_notes = h->sy_notes.as<const AdsrNote>();
+    const AdsrTile *d_tiles = h->sy_tiles.as<const AdsrTile>();
+    double *d_peak = h->sy_osc_peak.as<double>(), *d_mix = h->sy_mix.as<double>();
+    unsigned long long *d_cpeak = h->sy_clip_peak.as<unsigned long long>();
+    int16_t *d_out = h->sy_out.as<int16_t>();
     begin_event(h, labels[0], s);
     launch_adsr_peak(d_oscs, d_peak, (int32_t)B.oscs.size(), s, d_bends, d_segs);
     end_event(h, s);
     begin_event(h, labels[1], s);
-    launch_adsr_mix(d_oscs, d_notes, d_peak, d_tiles, static_cast<const int32_t *>(h->sy_tile_notes.p), d_mix, d_cpeak, (int32_t)B.tiles.size(), s,
+    launch_adsr_mix(d_oscs, d_notes, d_peak, d_tiles, h->sy_tile_notes.as<const int32_t>(), d_mix, d_cpeak, (int32_t)B.tiles.size(), s,
                     d_bends, d_segs);
     end_event(h, s);
     begin_event(h, labels[2], s);
     launch_adsr_master(d_tiles, d_mix, d_cpeak, d_out, (int32_t)B.tiles.size(), s);
     end_event(h, s);
-    HIPCHK_SYNC(h, s, hipGetLastError());
+    HIPCHK(h, hipGetLastError());
     return AEGIS_OK;
 }
 
@@ -132,16 +133,15 @@ namespace {
 // One device pass (handle locked): render_into, then every clip's samples to out[clip of the batch].
 int render_group(aegis_handle *h, const AdsrBatch &B, int16_t *const *out, const char *const (&labels)[3]) {
     if (B.samples == 0) return AEGIS_OK;
+    StreamScope scope(h);
     const int rc = render_into(h, B, labels);
     if (rc != AEGIS_OK) return rc;
     hipStream_t s = h->stream;
     const size_t nc = B.clip_off.size();
-    const int16_t *d_out = static_cast<const int16_t *>(h->sy_out.p);
+    const int16_t *d_out = h->sy_out.as<const int16_t>();
     for (size_t c = 0; c < nc; ++c)
-        if (B.clip_total[c] > 0) HIPCHK_SYNC(h, s, hipMemcpyAsync(out[c], d_out + B.clip_off[c], (size_t)B.clip_total[c] * 2, hipMemcpyDeviceToHost, s));
-    HIPCHK_SYNC(h, s, hipStreamSynchronize(s));
-    if (h->profiling) collect_events(h);
-    return AEGIS_OK;
+        if (B.clip_total[c] > 0) HIPCHK(h, hipMemcpyAsync(out[c], d_out + B.clip_off[c], (size_t)B.clip_total[c] * 2, hipMemcpyDeviceToHost, s));
+    return scope.finish();
 }
 
 const char *const kSynthLabels[3] = {"synth_note_peak", "synth_mix", "synth_master"};

@@ -10,6 +10,7 @@ int aegis_ghost_rsi(aegis_handle *h, const int64_t *ev_a, const int64_t *ev_b, c
                     const int64_t *track_len, int32_t period, double *avg_gain, double *avg_loss) {
     try {
     if (!h) return AEGIS_ERR_INVALID;
+    std::lock_guard<std::mutex> lock(h->mu);
     if (n_series < 0 || (n_series > 0 && (!event_off || !track_len))) { h->err = "bad argument"; return AEGIS_ERR_INVALID; }
     if (period < 1 || period > 128) { h->err = "rsi period must be 1..128"; return AEGIS_ERR_INVALID; }
     DEVICE_ONLY(h);
@@ -26,25 +27,24 @@ int aegis_ghost_rsi(aegis_handle *h, const int64_t *ev_a, const int64_t *ev_b, c
         for (int64_t e = event_off[i]; e < event_off[i + 1]; ++e) sid[(size_t)(e - event_off[0])] = i;
     }
     const int64_t total = toff[(size_t)n_series];
-    std::lock_guard<std::mutex> lock(h->mu);
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
     ENSURE(h, t_x, std::max<int64_t>(total, 1) * 8); ENSURE(h, t_a, std::max<int64_t>(total, 1) * 8); ENSURE(h, t_b, std::max<int64_t>(total, 1) * 8);
     ENSURE(h, t_off, (n_series + 1) * 8); ENSURE(h, t_i64a, 2 * E * 8); ENSURE(h, t_i64b, E * 4 + 8); ENSURE(h, t_c, 2 * E * 8);
-    int64_t *d_ab = static_cast<int64_t *>(h->t_i64a.p);
-    int32_t *d_sid = static_cast<int32_t *>(h->t_i64b.p);
-    double *d_out = static_cast<double *>(h->t_c.p);
+    int64_t *d_ab = h->t_i64a.as<int64_t>();
+    int32_t *d_sid = h->t_i64b.as<int32_t>();
+    double *d_out = h->t_c.as<double>();
+    StreamScope scope(h);
     HIPCHK(h, hipMemcpyAsync(d_ab, ev_a + event_off[0], (size_t)E * 8, hipMemcpyHostToDevice, s));
     HIPCHK(h, hipMemcpyAsync(d_ab + E, ev_b + event_off[0], (size_t)E * 8, hipMemcpyHostToDevice, s));
     HIPCHK(h, hipMemcpyAsync(d_sid, sid.data(), (size_t)E * 4, hipMemcpyHostToDevice, s));
     HIPCHK(h, hipMemcpyAsync(h->t_off.p, toff.data(), ((size_t)n_series + 1) * 8, hipMemcpyHostToDevice, s));
-    trend_ghost_rsi(d_ab, d_ab + E, d_sid, E, static_cast<const int64_t *>(h->t_off.p), n_series, total, period,
-                    static_cast<double *>(h->t_x.p), static_cast<double *>(h->t_a.p), static_cast<double *>(h->t_b.p), d_out, d_out + E, s);
+    trend_ghost_rsi(d_ab, d_ab + E, d_sid, E, h->t_off.as<const int64_t>(), n_series, total, period,
+                    h->t_x.as<double>(), h->t_a.as<double>(), h->t_b.as<double>(), d_out, d_out + E, s);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpyAsync(avg_gain + event_off[0], d_out, (size_t)E * 8, hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipMemcpyAsync(avg_loss + event_off[0], d_out + E, (size_t)E * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    return AEGIS_OK;
+    return scope.finish();
     } catch (...) { return abi_fail(h); }
 }
 
@@ -52,6 +52,7 @@ int aegis_trend(aegis_handle *h, int32_t op, const double *x, const int64_t *off
                 const double *params, int32_t n_params, void *const *outs, int32_t n_outs) {
     try {
     if (!h) return AEGIS_ERR_INVALID;
+    std::lock_guard<std::mutex> lock(h->mu);
     if (n_series < 0 || (n_series > 0 && (!x || !offsets)) || !outs || n_params < 0 || (n_params > 0 && !params)) {
         h->err = "bad argument"; return AEGIS_ERR_INVALID;
     }
@@ -61,7 +62,6 @@ int aegis_trend(aegis_handle *h, int32_t op, const double *x, const int64_t *off
         for (int i = 0; i < no; ++i) if (!outs[i]) { h->err = "null output"; return false; }
         return true;
     };
-    std::lock_guard<std::mutex> lock(h->mu);
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
     int rc;
@@ -79,12 +79,13 @@ int aegis_trend(aegis_handle *h, int32_t op, const double *x, const int64_t *off
     ENSURE(h, t_x, n_in * 8); ENSURE(h, t_off, (n_series + 1) * 8);
     ENSURE(h, t_a, total * 8); ENSURE(h, t_b, total * 8); ENSURE(h, t_c, total * 8); ENSURE(h, t_d, total * 8); ENSURE(h, t_e, std::max<int64_t>(total, 256) * 8);
     ENSURE(h, t_i8, total); ENSURE(h, t_i64a, total * 8); ENSURE(h, t_i64b, (n_series + 1) * 8);
+    StreamScope scope(h);
     HIPCHK(h, hipMemcpyAsync(h->t_x.p, x, n_in * 8, hipMemcpyHostToDevice, s));
     HIPCHK(h, hipMemcpyAsync(h->t_off.p, offsets, (n_series + 1) * 8, hipMemcpyHostToDevice, s));
-    TrendArgs a{static_cast<const double *>(h->t_x.p), static_cast<const int64_t *>(h->t_off.p), n_series, total};
-    double *A = static_cast<double *>(h->t_a.p), *B = static_cast<double *>(h->t_b.p), *Cc = static_cast<double *>(h->t_c.p);
-    double *D = static_cast<double *>(h->t_d.p), *E = static_cast<double *>(h->t_e.p);
-    int8_t *I8 = static_cast<int8_t *>(h->t_i8.p);
+    TrendArgs a{h->t_x.as<const double>(), h->t_off.as<const int64_t>(), n_series, total};
+    double *A = h->t_a.as<double>(), *B = h->t_b.as<double>(), *Cc = h->t_c.as<double>();
+    double *D = h->t_d.as<double>(), *E = h->t_e.as<double>();
+    int8_t *I8 = h->t_i8.as<int8_t>();
     auto back = [&](void *dst, const void *src, size_t bytes) { return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s); };
     auto min_len = [&]() { int64_t m = INT64_MAX; for (int i = 0; i < n_series; ++i) m = std::min(m, offsets[i + 1] - offsets[i]); return m; };
     switch (op) {
@@ -151,7 +152,7 @@ int aegis_trend(aegis_handle *h, int32_t op, const double *x, const int64_t *off
         const int w = (int)params[0];
         if (w < 1 || (w & 1) == 0 || w > 255) { h->err = "savgol window must be odd, 1..255"; return AEGIS_ERR_INVALID; }
         HIPCHK(h, hipMemcpyAsync(E, params + 2, (size_t)w * 8, hipMemcpyHostToDevice, s));
-        trend_savgol(a, E, w, (int)params[1], B, static_cast<int64_t *>(h->t_i64a.p), static_cast<int64_t *>(h->t_i64b.p), A, s);
+        trend_savgol(a, E, w, (int)params[1], B, h->t_i64a.as<int64_t>(), h->t_i64b.as<int64_t>(), A, s);
         HIPCHK(h, back(outs[0], A, total * 8));
         break;
     }
@@ -182,7 +183,7 @@ int aegis_trend(aegis_handle *h, int32_t op, const double *x, const int64_t *off
         const int bw = (int)pp[4];
         if (bw < 1 || bw > 128 || min_len() < bw) { h->err = "band window must be 1..128 and not longer than any series"; return AEGIS_ERR_INVALID; }
         if ((rc = ensure(h, h->t_pa, (size_t)total * (12 * 8 + 1) + 256)) != AEGIS_OK) return rc;
-        double *R = static_cast<double *>(h->t_pa.p);
+        double *R = h->t_pa.as<double>();
         double *stack = R;                              // [3][total]: savgol, kalman, holt (the order multi_filter_consensus stacks them)
         double *ma = R + 3 * total, *up = R + 4 * total, *lo = R + 5 * total, *semi = R + 6 * total;
         double *mm = R + 7 * total, *sg = R + 8 * total, *hh = R + 9 * total, *cx = R + 10 * total, *conf = R + 11 * total;
@@ -202,7 +203,7 @@ int aegis_trend(aegis_handle *h, int32_t op, const double *x, const int64_t *off
         trend_band_confidence(a.x, up, lo, total, conf, q1);
         // q2: Holt; q3: NaN compaction + Savitzky-Golay
         trend_holt(a, pp[2], pp[3], stack + 2 * total, q2);
-        trend_savgol(a, E, w, (int)params[1], cx, static_cast<int64_t *>(h->t_i64a.p), static_cast<int64_t *>(h->t_i64b.p), stack, q3);
+        trend_savgol(a, E, w, (int)params[1], cx, h->t_i64a.as<int64_t>(), h->t_i64b.as<int64_t>(), stack, q3);
         int ei = 1;
         for (hipStream_t q : {q1, q2, q3}) {
             HIPCHK(h, hipEventRecord(h->sync_events[ei], q));
@@ -219,8 +220,7 @@ int aegis_trend(aegis_handle *h, int32_t op, const double *x, const int64_t *off
         return AEGIS_ERR_INVALID;
     }
     HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipStreamSynchronize(s));
-    return AEGIS_OK;
+    return scope.finish();
     } catch (...) { return abi_fail(h); }
 }
 

@@ -30,10 +30,10 @@ int verify_bank(aegis_handle *h, int32_t sr, aegis_handle::VerifyBank **out) {
         if (rc == AEGIS_OK) rc = ensure(h, b.off, kVerMels * 4);
         if (rc == AEGIS_OK) rc = ensure(h, b.w, std::max<size_t>(b.host.w.size() * 4, 8));
         if (rc != AEGIS_OK) return rc;
-        HIPCHK_SYNC(h, s, upload(b.start, b.host.start.data(), kVerMels * 4, s));
-        HIPCHK_SYNC(h, s, upload(b.len, b.host.len.data(), kVerMels * 4, s));
-        HIPCHK_SYNC(h, s, upload(b.off, b.host.off.data(), kVerMels * 4, s));
-        HIPCHK_SYNC(h, s, upload(b.w, b.host.w.data(), b.host.w.size() * 4, s));
+        HIPCHK(h, upload(b.start, b.host.start.data(), kVerMels * 4, s));
+        HIPCHK(h, upload(b.len, b.host.len.data(), kVerMels * 4, s));
+        HIPCHK(h, upload(b.off, b.host.off.data(), kVerMels * 4, s));
+        HIPCHK(h, upload(b.w, b.host.w.data(), b.host.w.size() * 4, s));
         b.uploaded = true;
     }
     *out = &b;
@@ -73,42 +73,41 @@ int verify_group(aegis_handle *h, int32_t sr, int32_t k0, int32_t k1, const floa
     if (n_blocks > INT32_MAX) { h->err = "batch too large"; return AEGIS_ERR_NOMEM; }       // (halved and retried)
 
     hipStream_t s = h->stream;
+    StreamScope scope(h);                                       // (B, pcm, ev and block_off are in front of it)
     aegis_handle::VerifyBank *bank = nullptr;
     if ((rc = verify_bank(h, sr, &bank)) != AEGIS_OK) return rc;
     ENSURE(h, vf_audio, pcm.size() * 4); ENSURE(h, vf_events, ev.size() * sizeof(VerifyEvent)); ENSURE(h, vf_boff, block_off.size() * 8);
     ENSURE(h, vf_mel, (size_t)n_rows * kVerMels * 8); ENSURE(h, vf_max, (size_t)n * 3 * 8);
     ENSURE(h, vf_sim, (size_t)n * 2 * 8); ENSURE(h, vf_keep, (size_t)n);
     if ((rc = render_into(h, B, kVerifyLabels)) != AEGIS_OK) return rc;
-    HIPCHK_SYNC(h, s, upload(h->vf_audio, pcm.data(), pcm.size() * 4, s));
-    HIPCHK_SYNC(h, s, upload(h->vf_events, ev.data(), ev.size() * sizeof(VerifyEvent), s));
-    HIPCHK_SYNC(h, s, upload(h->vf_boff, block_off.data(), block_off.size() * 8, s));
-    HIPCHK_SYNC(h, s, hipMemsetAsync(h->vf_max.p, 0, (size_t)n * 3 * 8, s));
+    HIPCHK(h, upload(h->vf_audio, pcm.data(), pcm.size() * 4, s));
+    HIPCHK(h, upload(h->vf_events, ev.data(), ev.size() * sizeof(VerifyEvent), s));
+    HIPCHK(h, upload(h->vf_boff, block_off.data(), block_off.size() * 8, s));
+    HIPCHK(h, hipMemsetAsync(h->vf_max.p, 0, (size_t)n * 3 * 8, s));
     VerifyArgs a{};
-    a.audio = static_cast<const float *>(h->vf_audio.p);
-    a.renders = static_cast<const int16_t *>(h->sy_out.p);
-    a.events = static_cast<const VerifyEvent *>(h->vf_events.p);
-    a.block_off = static_cast<const int64_t *>(h->vf_boff.p);
+    a.audio = h->vf_audio.as<const float>();
+    a.renders = h->sy_out.as<const int16_t>();
+    a.events = h->vf_events.as<const VerifyEvent>();
+    a.block_off = h->vf_boff.as<const int64_t>();
     a.n_events = n; a.n_blocks = n_blocks;
     a.hann = h->dt.hann; a.twiddle = h->dt.twiddle;
-    a.mel_start = static_cast<const int32_t *>(bank->start.p); a.mel_len = static_cast<const int32_t *>(bank->len.p);
-    a.mel_off = static_cast<const int32_t *>(bank->off.p); a.mel_w = static_cast<const float *>(bank->w.p);
+    a.mel_start = bank->start.as<const int32_t>(); a.mel_len = bank->len.as<const int32_t>();
+    a.mel_off = bank->off.as<const int32_t>(); a.mel_w = bank->w.as<const float>();
     a.n_used = bank->n_used;
-    a.melpow = static_cast<double *>(h->vf_mel.p);
-    a.sigmax = static_cast<unsigned long long *>(h->vf_max.p);
-    a.sim = static_cast<double *>(h->vf_sim.p);
-    a.keep = static_cast<uint8_t *>(h->vf_keep.p);
+    a.melpow = h->vf_mel.as<double>();
+    a.sigmax = h->vf_max.as<unsigned long long>();
+    a.sim = h->vf_sim.as<double>();
+    a.keep = h->vf_keep.as<uint8_t>();
     begin_event(h, "verify_mel", s);
     launch_verify_mel(a, s);
     end_event(h, s);
     begin_event(h, "verify_score", s);
     launch_verify_score(a, s);
     end_event(h, s);
-    HIPCHK_SYNC(h, s, hipGetLastError());
-    HIPCHK_SYNC(h, s, hipMemcpyAsync(sim + 2 * (int64_t)k0, a.sim, (size_t)n * 16, hipMemcpyDeviceToHost, s));
-    HIPCHK_SYNC(h, s, hipMemcpyAsync(keep + k0, a.keep, (size_t)n, hipMemcpyDeviceToHost, s));
-    HIPCHK_SYNC(h, s, hipStreamSynchronize(s));
-    if (h->profiling) collect_events(h);
-    return AEGIS_OK;
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(sim + 2 * (int64_t)k0, a.sim, (size_t)n * 16, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(keep + k0, a.keep, (size_t)n, hipMemcpyDeviceToHost, s));
+    return scope.finish();
 }
 
 }  // namespace
