@@ -854,6 +854,31 @@ int aegis_debug_set_observations(aegis_handle *h, const double *logobs, const do
  * which is the caller's to ensure: behaviour on rows whose CMND holds a NaN or an infinity is unspecified. */
 int aegis_debug_set_difference(aegis_handle *h, const double *d, int64_t F);
 
+/* aegis_debug_set_observations for ONE stream, for the tests that put the streaming Viterbi (launches that start inside a
+ * 16-step chunk, the column carried across pushes, the live_state preview, the commit walk) under adversarial rows:
+ * logobs f64[F][n_pitch_bins], logunv f64[F], rows in frame order.  From then on every launch of the observation kernel of
+ * THIS stream -- plain pushes, the captured graph of a fixed-size push, the final pass of aegis_stream_close -- is
+ * followed by a copy of the rows of the frames it covered (voiced_prob stays the observation kernel's own); the samples
+ * pushed only decide which frames are complete.  Rules:
+ *   - accepted only before the stream's first sample and while it is open (AEGIS_ERR_INVALID otherwise); arming again
+ *     before the first sample replaces the rows; the arming lasts as long as the stream and its rows live in buffers of the
+ *     stream's own, released with it;
+ *   - the same domain and the same validator as aegis_debug_set_observations: rows outside are AEGIS_ERR_INVALID with a
+ *     message naming the frame; F must be 1 .. the stream's frame capacity;
+ *   - a push that would complete a frame >= F is AEGIS_ERR_INVALID and consumes nothing, and so is an aegis_stream_close
+ *     whose frame count 1 + samples / hop is not F (the stream stays open); each message names both counts, and no row
+ *     past F is ever read;
+ *   - the handle's own arming (aegis_debug_set_observations / _set_difference) and other streams of the handle neither
+ *     see nor disturb it. */
+int aegis_debug_stream_set_observations(aegis_stream *st, const double *logobs, const double *logunv, int64_t F);
+
+/* What a stream's Viterbi left on the device, by name (the two-step protocol of aegis_debug_fetch: returns the count,
+ * writes min(count, cap) values; AEGIS_ERR_INVALID for an unknown name or one that does not exist yet):
+ * "states" i32[F]: the decoded state of every frame (voiced bin b, or n_pitch_bins + b unvoiced), after aegis_stream_close.
+ * "vstate" f64[2 n_pitch_bins]: the Viterbi column of the newest frame, as the last push that completed a frame handed it
+ * to the next launch (-inf where the band kernel declared a voiced state dead); between the first frame and close. */
+int64_t aegis_debug_stream_fetch(aegis_stream *st, const char *name, void *dst, int64_t cap);
+
 /* The pass plan an analyze call would make (CPU only: no device work, a device=-1 handle plans too).  Clips of
  * n_samples[i] samples, every stage, the handle's knobs and max_frames_per_pass, a device of n_cus compute units;
  * entry: AEGIS_PLAN_DEVICE (aegis_analyze_batch_device on the handle's stream), AEGIS_PLAN_CALLER_STREAM (on a stream of

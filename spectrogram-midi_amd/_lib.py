@@ -988,6 +988,22 @@ class Stream:
         h._check(self.lib.aegis_stream_close(self._s, float(rake_sensitivity), C.byref(out), C.byref(F)))
         return h._split(bufs, [F.value], False, False)[0]
 
+    def set_observations(self, logobs, logunv):
+        """aegis_debug_stream_set_observations: every frame of THIS stream decodes these rows (logobs [F, n_pitch_bins],
+        logunv [F], frame order) instead of its observation kernel's; before the first sample only.  AegisError(ERR_INVALID)
+        for rows outside the documented domain, and later for a push or a close() that does not fit F frames."""
+        rows = np.ascontiguousarray(logobs, dtype=np.float64)
+        unv = np.ascontiguousarray(logunv, dtype=np.float64)
+        if rows.ndim != 2 or rows.shape[1] != self.n_bins or unv.shape != (rows.shape[0],):
+            raise ValueError("logobs must be [F, n_pitch_bins] and logunv [F]")
+        self.handle._check(self.lib.aegis_debug_stream_set_observations(self._s, rows.ctypes.data, unv.ctypes.data, rows.shape[0]))
+
+    def debug_fetch(self, name):
+        """aegis_debug_stream_fetch: "states" int32 [F] (after close()), "vstate" float64 [2 n_pitch_bins] (the column the
+        last push handed over)."""
+        return _marshal.sized(lambda dst, cap: self.lib.aegis_debug_stream_fetch(self._s, name.encode(), dst, cap),
+                              _DEBUG_DTYPES.get(name, np.float64), self.handle._error)
+
     def free(self):
         # safe in either order with Handle.close(): the C handle outlives its open streams (aegis_destroy defers)
         if getattr(self, "_s", None):

@@ -129,6 +129,31 @@ int aegis::abi_fail(aegis_handle *h) noexcept {
     return code;
 }
 
+// The domain the Viterbi kernels are exact on (include/aegis_hip.h): rows pyin_obs_kernel can emit.  Host arithmetic only.
+int aegis::check_observation_rows(aegis_handle *h, const double *logobs, const double *logunv, int64_t F) {
+    const int B = h->tab.n_bins;
+    const double log_tiny = h->tab.log_tiny, easy_min = std::log(std::ldexp(1.0, -53) / B);
+    auto reject = [&](int64_t f, const char *why) {
+        h->err = "injected observations, frame " + std::to_string(f) + ": " + why;
+        return AEGIS_ERR_INVALID;
+    };
+    for (int64_t f = 0; f < F; ++f) {
+        const double u = logunv[f];
+        const bool hard = u == log_tiny;
+        if (u != u) return reject(f, "logunv is NaN");
+        if (!hard && !(u >= easy_min && u <= 0.0)) return reject(f, "logunv must be log(tiny) or within [log(2^-53 / n_pitch_bins), 0]");
+        const double *row = logobs + f * B;
+        bool observed = false;
+        for (int b = 0; b < B; ++b) {
+            if (row[b] != row[b]) return reject(f, "logobs is NaN");
+            if (!(row[b] >= log_tiny && row[b] <= 0.0)) return reject(f, "logobs must be within [log(tiny), 0]");
+            observed = observed || row[b] != log_tiny;
+        }
+        if (hard && !observed) return reject(f, "a hard frame (logunv == log(tiny)) needs a bin above log(tiny)");
+    }
+    return AEGIS_OK;
+}
+
 // the last call's plan: its last pass, and the workspace that pass used
 static const PassPlan *last_pass(const aegis_handle *h) { return h->plan.passes.empty() ? nullptr : &h->plan.passes.back(); }
 static int last_work(const aegis_handle *h) { return h->plan.passes.empty() ? 0 : (int)((h->plan.passes.size() - 1) & 1); }
@@ -707,31 +732,12 @@ int aegis_debug_set_observations(aegis_handle *h, const double *logobs, const do
     if (!logobs) return AEGIS_OK;
     if (!logunv || F <= 0) { h->err = "bad argument"; return AEGIS_ERR_INVALID; }
     if (h->inject_d.armed) { h->err = "injected observations: injected difference rows are armed already (one hook per call)"; return AEGIS_ERR_INVALID; }
-    // the domain the Viterbi kernels are exact on (include/aegis_hip.h): rows pyin_obs_kernel can emit
+    int rc;
+    if ((rc = check_observation_rows(h, logobs, logunv, F)) != AEGIS_OK) return rc;
     const int B = h->tab.n_bins;
-    const double log_tiny = h->tab.log_tiny, easy_min = std::log(std::ldexp(1.0, -53) / B);
-    auto reject = [&](int64_t f, const char *why) {
-        h->err = "injected observations, frame " + std::to_string(f) + ": " + why;
-        return AEGIS_ERR_INVALID;
-    };
-    for (int64_t f = 0; f < F; ++f) {
-        const double u = logunv[f];
-        const bool hard = u == log_tiny;
-        if (u != u) return reject(f, "logunv is NaN");
-        if (!hard && !(u >= easy_min && u <= 0.0)) return reject(f, "logunv must be log(tiny) or within [log(2^-53 / n_pitch_bins), 0]");
-        const double *row = logobs + f * B;
-        bool observed = false;
-        for (int b = 0; b < B; ++b) {
-            if (row[b] != row[b]) return reject(f, "logobs is NaN");
-            if (!(row[b] >= log_tiny && row[b] <= 0.0)) return reject(f, "logobs must be within [log(tiny), 0]");
-            observed = observed || row[b] != log_tiny;
-        }
-        if (hard && !observed) return reject(f, "a hard frame (logunv == log(tiny)) needs a bin above log(tiny)");
-    }
     DEVICE_ONLY(h);
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipDeviceSynchronize());        // (an earlier armed call that returned without a sync may still read the rows)
-    int rc;
     if ((rc = ensure(h, h->inject.obs, (size_t)F * B * 8)) != AEGIS_OK) return rc;
     if ((rc = ensure(h, h->inject.unv, (size_t)F * 8)) != AEGIS_OK) return rc;
     HIPCHK(h, hipMemcpy(h->inject.obs.p, logobs, (size_t)F * B * 8, hipMemcpyHostToDevice));

@@ -3,7 +3,7 @@
 // included by include/aegis_hip.h.
 //   aegis_api.hip     the batch pipeline (plan input, workspaces, analyze_device_locked, recovery, the analyze entries)
 //   aegis_handle.hip  create / destroy, profiling, the call scope's drain, tables, parameters, aegis_debug_plan / aegis_debug_fetch
-//   aegis_stream.hip  aegis_stream_* (graph capture, commit delivery)
+//   aegis_stream.hip  aegis_stream_* (graph capture, commit delivery), aegis_debug_stream_set_observations / _stream_fetch
 //   aegis_cqt.hip     CQT, chroma, the filter-bank cache, aegis_estimate_tuning, aegis_rake_patterns
 //   aegis_trend.hip   aegis_trend, aegis_ghost_rsi
 //   aegis_synth.hip   aegis_synth_* (the ADSR soft-synth, one envelope per clip or per note; kernels in adsr.hip, host
@@ -195,6 +195,10 @@ struct aegis_stream {
     int64_t c_newest = -1;      // newest frame the commit kernel has walked from
     int64_t c_delivered = 0;    // frames handed to the caller so far
     int64_t c_walked = 0, c_walked_wide = 0;    // frames the last commit launch walked, and how many of them as a bit mask
+    // aegis_debug_stream_set_observations: rows [F][n_bins] / [F] in frame order that every launch of the observation kernel
+    // of THIS stream is followed by a copy of (armed before the first sample, for the stream's whole life; the handle's
+    // own arming neither sees nor disturbs it)
+    struct Inject { bool armed = false; int64_t F = 0; DevBuf obs, unv; } inject;
 };
 
 #define HIPCHK(h, expr)                                                                         \
@@ -233,6 +237,9 @@ void destroy_now(aegis_handle *h) noexcept;
 // Nothing is thrown across the C boundary (include/aegis_hip.h): every exported entry runs its body inside
 // try { ... } catch (...) { return abi_fail(h); }, which maps the in-flight exception to a return code.
 int abi_fail(aegis_handle *h) noexcept;
+// The domain rules of injected observation rows (aegis_debug_set_observations and aegis_debug_stream_set_observations):
+// AEGIS_OK, or AEGIS_ERR_INVALID with a message that names the frame.  Host arithmetic only.
+AEGIS_LOCAL int check_observation_rows(aegis_handle *h, const double *logobs, const double *logunv, int64_t F);
 
 // ---- profiling event pairs (aegis_handle.hip) ----
 void begin_event(aegis_handle *h, const char *name, hipStream_t s);

@@ -39,12 +39,28 @@ static PassParams stream_params(aegis_stream *st, const int64_t *dm) {
     return p;
 }
 
-// Captures one fixed-size push as a hipGraph: H2D of the samples, advance (append + geometry), the four
-// analysis kernels reading their geometry from the device control block, result gather, D2H.
 static StreamCommitCtl *stream_commit_ctl(aegis_stream *st) {
     return reinterpret_cast<StreamCommitCtl *>(static_cast<unsigned char *>(st->ctl.p) + sizeof(StreamCtl));
 }
 
+// aegis_debug_stream_set_observations: behind every launch of the observation kernel of an armed stream, the same frames
+// take their rows from the stream's own copy (one more node of the one chain; the kernel reads its geometry as
+// pyin_obs_kernel does, so it replays under ctl).  The entries have checked that no selected frame is >= inject.F.
+static void stream_inject(aegis_stream *st, const PassParams &p, hipStream_t s) {
+    if (st->inject.armed)
+        launch_inject_obs(p, static_cast<const double *>(st->inject.obs.p), static_cast<const double *>(st->inject.unv.p), s);
+}
+// An armed stream has rows for inject.F frames: a push may complete at most that many, close() decodes exactly that many.
+// `frames`: the count the push would reach, or close()'s.  AEGIS_ERR_INVALID names both counts.
+static int stream_inject_fits(aegis_stream *st, int64_t frames, bool closing) {
+    if (!st->inject.armed || (closing ? frames == st->inject.F : frames <= st->inject.F)) return AEGIS_OK;
+    st->h->err = std::string("injected observations: ") + (closing ? "close() would decode " : "the push would complete ") +
+                 std::to_string(frames) + " frames, the stream was armed with " + std::to_string(st->inject.F);
+    return AEGIS_ERR_INVALID;
+}
+
+// Captures one fixed-size push as a hipGraph: H2D of the samples, advance (append + geometry), the four
+// analysis kernels reading their geometry from the device control block, result gather, D2H.
 static bool stream_build_graph(aegis_stream *st, int64_t n_push, hipStream_t s, int commit) {
     aegis_handle *h = st->h;
     const Tables &t = h->tab;
@@ -60,6 +76,7 @@ static bool stream_build_graph(aegis_stream *st, int64_t n_push, hipStream_t s, 
     launch_stream_advance(ctl, static_cast<const float *>(st->g_staging.p), (int)n_push, static_cast<float *>(st->pcm.p), t.hop, s);
     launch_frame(p, h->dt, s);
     launch_pyin_obs(p, h->dt, s);
+    stream_inject(st, p, s);
     ok &= launch_viterbi(p, h->dt, t.log_trans_band.data(), s) == hipSuccess;
     if (commit)
         ok &= launch_stream_commit(ctl, 0, stream_commit_ctl(st), p.ptr, p.vstate, t.n_bins, static_cast<int16_t *>(st->c_bins.p),
@@ -99,6 +116,7 @@ static int stream_run(aegis_stream *st, int64_t f_lo, int64_t f_hi, bool final_p
     if (p.n_sel > 0) {
         launch_frame(p, h->dt, s);
         launch_pyin_obs(p, h->dt, s);
+        stream_inject(st, p, s);
     }
     if (p.n_sel > 0 || final_pass) {
         hipError_t ve = launch_viterbi(p, h->dt, t.log_trans_band.data(), s);
@@ -257,6 +275,11 @@ static int stream_push_locked(aegis_stream *st, const float *samples, int64_t n,
     if (commit && (commit->cap < 0 || (commit->cap > 0 && !commit->pitch_bin))) { h->err = "bad argument"; return AEGIS_ERR_INVALID; }
     if (st->closed) { h->err = "stream is closed"; return AEGIS_ERR_INVALID; }
     if (st->n_samples + n > st->cap_samples) { h->err = "stream capacity exceeded"; return AEGIS_ERR_INVALID; }
+    if (st->inject.armed) {      // before anything is consumed: no row past inject.F is ever read
+        const int64_t after = st->n_samples + n;
+        const int rc = stream_inject_fits(st, after >= kFrameLength / 2 ? (after - kFrameLength / 2) / h->tab.hop + 1 : 0, false);
+        if (rc != AEGIS_OK) return rc;
+    }
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
     const int ci = commit ? 1 : 0;
@@ -351,7 +374,9 @@ int aegis_stream_close(aegis_stream *st, double rake_sensitivity, aegis_outputs 
     hipStream_t s = h->stream;
     const Tables &t = h->tab;
     const int64_t F = 1 + st->n_samples / t.hop;
-    int rc = stream_run(st, st->frames_done, F, true, s);       // zero-padded tail frames + back-trace
+    int rc = stream_inject_fits(st, F, true);
+    if (rc != AEGIS_OK) return rc;                              // (the stream stays open: more samples may still make it F)
+    rc = stream_run(st, st->frames_done, F, true, s);           // zero-padded tail frames + back-trace
     if (rc != AEGIS_OK) return rc;
     // clip-global stages over all F frames
     st->host_meta[5] = F;
@@ -377,6 +402,60 @@ int aegis_stream_close(aegis_stream *st, double rake_sensitivity, aegis_outputs 
     }
     HIPCHK(h, hipStreamSynchronize(s));
     return AEGIS_OK;
+    } catch (...) { return abi_fail((st ? st->h : nullptr)); }
+}
+
+int aegis_debug_stream_set_observations(aegis_stream *st, const double *logobs, const double *logunv, int64_t F) {
+    try {
+    if (!st || !st->h) return AEGIS_ERR_INVALID;
+    aegis_handle *h = st->h;
+    std::lock_guard<std::mutex> lock(h->mu);
+    if (h->destroy_requested) { h->err = "handle was destroyed"; return AEGIS_ERR_INVALID; }
+    if (st->closed) { h->err = "stream is closed"; return AEGIS_ERR_INVALID; }
+    if (st->n_samples > 0) { h->err = "injected observations: a stream is armed before its first sample (it has " + std::to_string(st->n_samples) + ")"; return AEGIS_ERR_INVALID; }
+    if (!logobs || !logunv || F <= 0) { h->err = "bad argument"; return AEGIS_ERR_INVALID; }
+    if (F > st->cap_frames) {
+        h->err = "injected observations: " + std::to_string(F) + " frames, the stream holds at most " + std::to_string(st->cap_frames);
+        return AEGIS_ERR_INVALID;
+    }
+    int rc;
+    if ((rc = check_observation_rows(h, logobs, logunv, F)) != AEGIS_OK) return rc;
+    const int B = h->tab.n_bins;
+    HIPCHK(h, hipSetDevice(h->device));
+    st->inject.armed = false;                 // (arming again replaces the rows; nothing of this stream is in flight: no sample yet)
+    if ((rc = ensure(st, st->inject.obs, (size_t)F * B * 8)) != AEGIS_OK) return rc;
+    if ((rc = ensure(st, st->inject.unv, (size_t)F * 8)) != AEGIS_OK) return rc;
+    HIPCHK(h, hipMemcpy(st->inject.obs.p, logobs, (size_t)F * B * 8, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(st->inject.unv.p, logunv, (size_t)F * 8, hipMemcpyHostToDevice));
+    st->inject.F = F;
+    st->inject.armed = true;
+    return AEGIS_OK;
+    } catch (...) { return abi_fail((st ? st->h : nullptr)); }
+}
+
+int64_t aegis_debug_stream_fetch(aegis_stream *st, const char *name, void *dst, int64_t cap) {
+    try {
+    if (!st || !st->h) return AEGIS_ERR_INVALID;
+    aegis_handle *h = st->h;
+    std::lock_guard<std::mutex> lock(h->mu);
+    if (h->destroy_requested) { h->err = "handle was destroyed"; return AEGIS_ERR_INVALID; }
+    if (!name) { h->err = "bad argument"; return AEGIS_ERR_INVALID; }
+    const std::string n(name);
+    const void *src = nullptr;
+    int64_t count = 0, esz = 0;
+    if (n == "states") {
+        if (!st->closed) { h->err = "stream fetch: \"states\" exists after close()"; return AEGIS_ERR_INVALID; }
+        src = st->states.p; count = st->frames_done; esz = 4;
+    } else if (n == "vstate") {
+        if (st->closed || st->frames_done == 0) { h->err = "stream fetch: \"vstate\" exists between the first frame and close()"; return AEGIS_ERR_INVALID; }
+        src = st->vstate.p; count = 2 * (int64_t)h->tab.n_bins; esz = 8;
+    } else { h->err = "stream fetch: unknown name " + n; return AEGIS_ERR_INVALID; }
+    if (dst && cap > 0) {
+        HIPCHK(h, hipSetDevice(h->device));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        HIPCHK(h, hipMemcpy(dst, src, (size_t)(std::min(count, cap) * esz), hipMemcpyDeviceToHost));
+    }
+    return count;
     } catch (...) { return abi_fail((st ? st->h : nullptr)); }
 }
 

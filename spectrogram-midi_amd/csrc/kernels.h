@@ -172,7 +172,7 @@ bool frame_cmnd_supported(int max_period);
 int frame_batch_fpw(int max_period);        // frames per frame_yin workgroup of a launch that selects >= 4096 frames (smaller launches: 2)
 int trough_row_doubles_host(int n_lags);    // doubles of a dfn row that holds a frame's trough list (PassParams::troughs)   // the frame kernel's LDS holds the CMND rows of a workgroup's frames (PassParams::cmnd_in_frame)
 void launch_pyin_obs(const PassParams &p, const DevTables &t, hipStream_t s);
-// in its place (aegis_debug_set_observations): the launch's selected frames take their rows from src_obs [out_total][n_bins] / src_unv
+// in its place (aegis_debug_set_observations) or behind it (aegis_debug_stream_set_observations): the launch's selected frames take their rows from src_obs [out_total][n_bins] / src_unv
 void launch_inject_obs(const PassParams &p, const double *src_obs, const double *src_unv, hipStream_t s);
 // aegis_debug_pitch_bins: bin_decide.h's bin_fast (-1 where it does not decide, fell = 1 there) and bin_exact of n periods (device arrays)
 void launch_pitch_bins(const PassParams &p, const DevTables &t, const double *periods, int64_t n, int16_t *fast, int16_t *exact, uint8_t *fell, hipStream_t s);

@@ -8,6 +8,7 @@ import pytest
 
 from spectrogram_midi_amd import _lib
 from tools import signals, stream_commit_model as M
+from tools.stream_cases import check_deliveries      # (shared with tests/test_gpu_stream_injected.py)
 
 pytestmark = pytest.mark.gpu
 
@@ -62,35 +63,6 @@ def run_commit(h, y, sizes, cap=None):
     final = st.close()
     st.free()
     return parts, final
-
-
-def check_deliveries(h, parts, final, tag):
-    """Every delivered bin against close(): consecutive from frame 0, no gaps, no repeats, frontier monotone; the
-    delivered frames never run ahead of the frames the pushes produced.  Returns the concatenated bins."""
-    freqs = h.table("freqs")
-    nxt, prev_frontier, produced = 0, -1, 0
-    bins = []
-    for k, p in enumerate(parts):
-        produced += len(p["rms"])
-        c = p["committed"]
-        assert c["first"] == nxt == prev_frontier + 1, f"{tag} push {k}: first {c['first']}, expected {nxt}"
-        assert c["pitch_bin"].dtype == np.int16
-        nxt += len(c["pitch_bin"])
-        assert p["frontier"] == nxt - 1 and p["frontier"] >= prev_frontier, f"{tag} push {k}"
-        assert p["frontier"] < produced, f"{tag} push {k}: frontier {p['frontier']} beyond the {produced} frames produced"
-        prev_frontier = p["frontier"]
-        bins.append(c["pitch_bin"])
-    bins = np.concatenate(bins) if bins else np.zeros(0, np.int16)
-    n = len(bins)
-    assert n == prev_frontier + 1 <= len(final["f0"])
-    assert ((bins >= -1) & (bins < len(freqs))).all(), tag
-    voiced = bins >= 0
-    np.testing.assert_array_equal(voiced, final["voiced_flag"][:n], err_msg=f"{tag} voiced_flag")
-    got_f0 = freqs[np.maximum(bins, 0)]
-    want_f0 = final["f0"][:n]
-    assert np.isnan(want_f0[~voiced]).all(), tag
-    np.testing.assert_array_equal(got_f0[voiced].view(np.uint64), want_f0[voiced].view(np.uint64), err_msg=f"{tag} f0 bits")
-    return bins
 
 
 @pytest.mark.parametrize("sizes", SIZES, ids=lambda s: "x".join(map(str, s[:4])))
