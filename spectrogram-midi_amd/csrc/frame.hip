@@ -220,7 +220,7 @@ __global__ __launch_bounds__(256, 2) void frame_yin_kernel(PassParams p, DevTabl
     __builtin_amdgcn_s_waitcnt(kWaitVmcnt0);
 
     for (int pr = 0; pr < nfr; pr += 2) {
-        double2 P[2][5];
+        double2 P[2][4], Pn[2];                // P = A B of the thread's four bins per frame; Pn: of the Nyquist bin (thread 255 only)
         int64_t fidx[2] = {0, 0};
         int64_t fout[2] = {0, 0};             // (INJECT only) output index of each frame: the caller's rows are in output order
         bool flive[2] = {false, false};
@@ -228,7 +228,8 @@ __global__ __launch_bounds__(256, 2) void frame_yin_kernel(PassParams p, DevTabl
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
 #pragma unroll
-            for (int r = 0; r < 5; ++r) P[h][r] = make_double2(0.0, 0.0);
+            for (int r = 0; r < 4; ++r) P[h][r] = make_double2(0.0, 0.0);
+            Pn[h] = make_double2(0.0, 0.0);
             if (pr + h >= nfr) continue;                      // odd tail: the pair's second frame does not exist (uniform)
             const bool live = geo.live;
             const int c = geo.c;
@@ -300,30 +301,24 @@ __global__ __launch_bounds__(256, 2) void frame_yin_kernel(PassParams p, DevTabl
             if (!want_fft) continue;
 
             // ---- A[k] = FFT(x)[k], B[k] = FFT(b)[k] from Z by symmetry; P = A*B; windowed power from A ----------
-            // A thread owns FIVE CONSECUTIVE bins k = 5 tid .. 5 tid + 4 (205 threads cover 0..1024): the windowed spectrum
-            // needs A[k - 1] and A[k + 1], which are then the thread's own neighbours -- seven (z[k], z[2048 - k]) pairs per
-            // thread and frame instead of fifteen with bins 256 apart.  (Lanes 80 bytes apart: 16 lanes of a ds_read_b128
-            // fall on 16 distinct bank groups.)  k is taken modulo 2048: A[-1] = conj(A[1]), A[1025] = conj(A[1023]).
-            if (tid < 205) {
+            // A thread owns FOUR CONSECUTIVE bins k = 4 tid .. 4 tid + 3 (all 256 threads; 1025 bins are four per thread plus
+            // the Nyquist bin, below): the windowed spectrum needs A[k - 1] and A[k + 1], which are then the thread's own
+            // neighbours -- six (z[k], z[2048 - k]) pairs per thread and frame instead of fifteen with bins 256 apart, and an
+            // instruction stream of four bins on every wave (five bins per thread ran the fifth on all four waves, the last
+            // wave for 13 live lanes).  Lanes 64 bytes apart; with the zsw swizzle the 16 lanes of a ds_read_b128 group meet
+            // on bank groups no more often than at 80 bytes.  k is taken modulo 2048: A[-1] = conj(A[1]).
+            {
                 auto zpair = [&](int k, double2 &zk, double2 &zn) { zk = z[zsw(k & 2047)]; zn = z[zsw((2048 - k) & 2047)]; };
                 // A2 = 2 A and B2 = 2 B: the halves are folded into the powers of two applied later (P = A B arrives as 4 P in the
                 // inverse transform, whose outputs are scaled by 1/8192 instead of 1/2048; the windowed spectrum is
                 // A/2 - (A- + A+)/4 = (2 A2 - (A2- + A2+)) / 8) -- exact scalings, every value bit-identical
                 auto Afrom = [](const double2 &zk, const double2 &zn) { return make_double2(zk.x + zn.x, zk.y - zn.y); };
-                const int k0 = 5 * tid;
-                double2 zk, zn, zk1, zn1;
-                zpair(k0 - 1, zk, zn);
-                double2 Am = Afrom(zk, zn);
-                zpair(k0, zk, zn);
-                double2 A = Afrom(zk, zn);
-#pragma unroll
-                for (int r = 0; r < 5; ++r) {
-                    const int k = k0 + r;
-                    zpair(k + 1, zk1, zn1);
-                    const double2 Ap = Afrom(zk1, zn1);
+                // one bin: its product P = A B and its windowed power
+                auto bin = [&](int k, const double2 &Am, const double2 &A, const double2 &Ap, const double2 &zk, const double2 &zn,
+                               double2 &Pk) {
                     if (want_pyin) {
                         const double2 Bv = make_double2(zk.y + zn.y, zn.x - zk.x);
-                        P[h][r] = c_mul(A, Bv);
+                        Pk = c_mul(A, Bv);
                     }
                     if (want_mel) {
                         const float re = (float)(0.125 * (2.0 * A.x - (Am.x + Ap.x)));
@@ -331,8 +326,24 @@ __global__ __launch_bounds__(256, 2) void frame_yin_kernel(PassParams p, DevTabl
                         const float mag = (float)sqrt((double)re * (double)re + (double)im * (double)im);  // npy_hypotf
                         (h == 0 ? pw : pw1)[k] = mag * mag;
                     }
+                };
+                const int k0 = 4 * tid;
+                double2 zk, zn, zk1, zn1;
+                zpair(k0 - 1, zk, zn);
+                double2 Am = Afrom(zk, zn);
+                zpair(k0, zk, zn);
+                double2 A = Afrom(zk, zn);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    zpair(k0 + r + 1, zk1, zn1);
+                    const double2 Ap = Afrom(zk1, zn1);
+                    bin(k0 + r, Am, A, Ap, zk, zn, P[h][r]);
                     Am = A; A = Ap; zk = zk1; zn = zn1;
                 }
+                // The Nyquist bin 1024 is the last thread's fifth: it holds A[1023], A[1024] and the pair of bin 1024 already,
+                // and A[1025] = conj(A[1023]) -- the sum A[1023] + A[1025] the window takes is the same to the bit
+                // (x the same two addends, y = a + (-a) = +0 as (a) + (b - c) with b - c = -a was).
+                if (tid == 255) bin(1024, Am, A, make_double2(Am.x, -Am.y), zk, zn, Pn[h]);
             }
             if (want_mel && h == 1 && tid < 15) pw1[1025 + tid] = 0.0f;      // the last chunks read (zero-weighted) bins past 1024
             __syncthreads();
@@ -392,14 +403,15 @@ __global__ __launch_bounds__(256, 2) void frame_yin_kernel(PassParams p, DevTabl
         if (!want_pyin) continue;
 
         // ---- one inverse FFT for both frames: conj(Q), Q = Hermitian extension of P0 + i*P1 ---------------------
-        if (tid < 205) {                         // the thread's own five consecutive bins (see above)
+        {                                        // the thread's own four consecutive bins (see above)
 #pragma unroll
-            for (int r = 0; r < 5; ++r) {
-                const int k = 5 * tid + r;
+            for (int r = 0; r < 4; ++r) {
+                const int k = 4 * tid + r;
                 const double2 u = P[0][r], v = P[1][r];
                 z[zsw(k)] = make_double2(u.x - v.y, -u.y - v.x);                          // conj(P0) - i conj(P1)
-                if (k > 0 && k < 1024) z[zsw(2048 - k)] = make_double2(u.x + v.y, u.y - v.x);   // P0 - i P1
+                if (k > 0) z[zsw(2048 - k)] = make_double2(u.x + v.y, u.y - v.x);         // P0 - i P1
             }
+            if (tid == 255) z[zsw(1024)] = make_double2(Pn[0].x - Pn[1].y, -Pn[0].y - Pn[1].x);      // the Nyquist bin: no mirror
         }
         __syncthreads();
         {
