@@ -216,7 +216,11 @@ __global__ __launch_bounds__(256, 2) void frame_yin_kernel(PassParams p, DevTabl
     // This rests on where the compiler's wait insertion puts its own waits: results never depend on it, the time does.
     // After a compiler upgrade, or an edit that leaves a sample load pending on some path into the loop head, look at the
     // ISA again (hipcc -O3 -ffp-contract=off --offload-arch=gfx950 --cuda-device-only -S): no `s_waitcnt vmcnt` may
-    // stand in front of the first four `ds_write2st64_b32` of the pair loop (the first frame's buffer writes).
+    // stand in front of the first four `ds_write2st64_b32` of the pair loop (the first frame's buffer writes);
+    // tools/isa_inflight.py prints what stands there and tests/test_frame_isa_inflight.py holds it.  Two pieces of work
+    // below exist only to steer that wait insertion and compute nothing: the mel section's 32 power reads and its wait
+    // stand outside `if (want_mel)` (a call without the mel stage reads 32 unused words per pair), and the quotient
+    // loop's reads carry no condition (a small launch's dead frames read a live row's entries again).
     __builtin_amdgcn_s_waitcnt(kWaitVmcnt0);
 
     for (int pr = 0; pr < nfr; pr += 2) {
@@ -252,9 +256,15 @@ __global__ __launch_bounds__(256, 2) void frame_yin_kernel(PassParams p, DevTabl
             if (want_rms && tid < 128) {
                 const int bb = tid >> 3, a = tid & 7;
                 const float *xb = xs + bb * 128 + a;
-                float r = xb[0] * xb[0];
+                // all sixteen reads requested before the first square: the adds chain in NumPy's order as before, behind
+                // counted waits instead of an LDS round trip each (waves 2 and 3 wait for this at the transform's first barrier)
+                float xv[16];
 #pragma unroll
-                for (int i = 1; i < 16; ++i) { const float v = xb[8 * i]; r = r + v * v; }
+                for (int i = 0; i < 16; ++i) xv[i] = xb[8 * i];
+                __builtin_amdgcn_sched_barrier(0);
+                float r = xv[0] * xv[0];
+#pragma unroll
+                for (int i = 1; i < 16; ++i) r = r + xv[i] * xv[i];
                 red[tid] = r;
             }
             if (!want_fft) {
@@ -267,10 +277,15 @@ __global__ __launch_bounds__(256, 2) void frame_yin_kernel(PassParams p, DevTabl
             } else {
                 // ---- packed forward FFT of (frame, reversed first half); pass 1 straight from the frame ----
                 double2 v[8];
+                {
+                    float xf[8], xr[4];                       // the thread's twelve samples in flight together
 #pragma unroll
-                for (int q = 0; q < 8; ++q) {
-                    const int i = tid + 256 * q;
-                    v[q] = make_double2((double)xs[i], i < 1024 ? (double)xs[1024 - i] : 0.0);
+                    for (int q = 0; q < 8; ++q) xf[q] = xs[tid + 256 * q];
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) xr[q] = xs[1024 - (tid + 256 * q)];
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int q = 0; q < 8; ++q) v[q] = make_double2((double)xf[q], q < 4 ? (double)xr[q] : 0.0);
                 }
                 fft8_pass1_write(z, tid, v);
                 __syncthreads();
@@ -349,29 +364,53 @@ __global__ __launch_bounds__(256, 2) void frame_yin_kernel(PassParams p, DevTabl
             __syncthreads();
             FRM_TICK(3)
         }
-        // The next pair's first frame (requested a forward transform ago) is waited for HERE, see above: what is outstanding
-        // besides it is the second frame's rms store, a power section old.  The mel section waits for its weights anyway.
-        __builtin_amdgcn_s_waitcnt(kWaitVmcnt0);
         // ---- mel projection of BOTH frames of the pair: sparse Slaney triangles.  Every <= 16-bin chunk of a triangle is
         // one thread's float32 fma chain per frame (the 16 weights requested once per pair); a band then adds its
         // chunks' sums in order (the widest band has six), threads 0..127 for the first frame and 128..255 for the
         // second.  Clip maximum.  One section per pair instead of one per frame: half the barriers, half the weight
         // traffic, all four waves busy in the band phase.
-        if (want_mel) {
-            if (has_chunk) {
-                const float4 *wp = reinterpret_cast<const float4 *>(tb.mel_chunk_w) + tid * 4;
-                const float4 w0 = wp[0], w1 = wp[1], w2 = wp[2], w3 = wp[3];
+        // The section is a few dozen fmas behind an L2 round trip (the weights) and the LDS round trips of 32 powers, so it
+        // is laid out for those to overlap: the weights are requested FIRST; under them the input of the inverse transform
+        // is written (below: z is dead since the barrier above, and the writes release the 40 registers of P for what
+        // follows) and both frames' powers are requested, all 32 before the first fma; then ONE wait takes the weights
+        // over.  That wait is also the wait for the next pair's first frame (requested a forward transform ago), see above
+        // the loop: it stands outside every condition, and what is outstanding besides samples and weights is the
+        // second frame's rms store, a power section old.
+        float4 w0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), w1 = w0, w2 = w0, w3 = w0;
+        if (has_chunk) {
+            const float4 *wp = reinterpret_cast<const float4 *>(tb.mel_chunk_w) + tid * 4;
+            w0 = wp[0]; w1 = wp[1]; w2 = wp[2]; w3 = wp[3];
+        }
+        // ---- input of the one inverse FFT for both frames: conj(Q), Q = Hermitian extension of P0 + i*P1 --------
+        if (__builtin_expect(want_pyin, 1)) {    // the thread's own four consecutive bins (see above)
 #pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const float *pp = (h == 0 ? pw : pw1) + mel_bin;
-                    float acc = 0.0f;
-                    acc = fmaf(w0.x, pp[0], acc); acc = fmaf(w0.y, pp[1], acc); acc = fmaf(w0.z, pp[2], acc); acc = fmaf(w0.w, pp[3], acc);
-                    acc = fmaf(w1.x, pp[4], acc); acc = fmaf(w1.y, pp[5], acc); acc = fmaf(w1.z, pp[6], acc); acc = fmaf(w1.w, pp[7], acc);
-                    acc = fmaf(w2.x, pp[8], acc); acc = fmaf(w2.y, pp[9], acc); acc = fmaf(w2.z, pp[10], acc); acc = fmaf(w2.w, pp[11], acc);
-                    acc = fmaf(w3.x, pp[12], acc); acc = fmaf(w3.y, pp[13], acc); acc = fmaf(w3.z, pp[14], acc); acc = fmaf(w3.w, pp[15], acc);
-                    (h == 0 ? part : part1)[tid] = acc;
-                }
+            for (int r = 0; r < 4; ++r) {
+                const int k = 4 * tid + r;
+                const double2 u = P[0][r], v = P[1][r];
+                z[zsw(k)] = make_double2(u.x - v.y, -u.y - v.x);                          // conj(P0) - i conj(P1)
+                if (k > 0) z[zsw(2048 - k)] = make_double2(u.x + v.y, u.y - v.x);         // P0 - i P1
             }
+            if (tid == 255) z[zsw(1024)] = make_double2(Pn[0].x - Pn[1].y, -Pn[0].y - Pn[1].x);      // the Nyquist bin: no mirror
+        }
+        // The reads and the wait stand outside every condition (threads without a chunk, and calls without the mel stage,
+        // read bins 0..15: in bounds, never used): a wait on one side of a branch leaves the compiler a path into the loop
+        // head on which the samples count as pending, and it then waits in front of the first frame's buffer writes.
+        float pa[16], pb[16];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) pa[k] = pw[mel_bin + k];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) pb[k] = pw1[mel_bin + k];
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_waitcnt(kWaitVmcnt0);
+        if (__builtin_expect(want_mel, 1)) {
+            const float wv[16] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w, w2.x, w2.y, w2.z, w2.w, w3.x, w3.y, w3.z, w3.w};
+            float acc0 = 0.0f, acc1 = 0.0f;
+#pragma unroll
+            for (int k = 0; k < 16; ++k) acc0 = fmaf(wv[k], pa[k], acc0);
+#pragma unroll
+            for (int k = 0; k < 16; ++k) acc1 = fmaf(wv[k], pb[k], acc1);
+            if (has_chunk) { part[tid] = acc0; part1[tid] = acc1; }
+            // this barrier publishes the chunk sums and, with them, the input of the inverse transform
             __syncthreads();
             {
                 const int h = wid >> 1, bt = tid & 127;           // waves 0, 1: first frame; waves 2, 3: second
@@ -402,18 +441,8 @@ __global__ __launch_bounds__(256, 2) void frame_yin_kernel(PassParams p, DevTabl
         FRM_TICK(4)
         if (!want_pyin) continue;
 
-        // ---- one inverse FFT for both frames: conj(Q), Q = Hermitian extension of P0 + i*P1 ---------------------
-        {                                        // the thread's own four consecutive bins (see above)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int k = 4 * tid + r;
-                const double2 u = P[0][r], v = P[1][r];
-                z[zsw(k)] = make_double2(u.x - v.y, -u.y - v.x);                          // conj(P0) - i conj(P1)
-                if (k > 0) z[zsw(2048 - k)] = make_double2(u.x + v.y, u.y - v.x);         // P0 - i P1
-            }
-            if (tid == 255) z[zsw(1024)] = make_double2(Pn[0].x - Pn[1].y, -Pn[0].y - Pn[1].x);      // the Nyquist bin: no mirror
-        }
-        __syncthreads();
+        // ---- one inverse FFT for both frames (its input was written in front of the mel section, whose barrier published it)
+        if (!want_mel) __syncthreads();
         {
             double2 v[8];
             fft8_read8(z, tid, v);
@@ -538,16 +567,34 @@ __global__ __launch_bounds__(256, 2) void frame_yin_kernel(PassParams p, DevTabl
         __syncthreads();
         FRM_TICK(8)
         const bool troughs = p.troughs != 0;
+        // A frame's three cumsum entries are requested together, in front of its three divisions: one LDS round trip per
+        // frame instead of one per quotient.  (Requesting the NEXT frame's entries under this frame's divisions as well was
+        // measured and is not kept: profiles/frame_latency_quotient_prefetch_experiment.patch.)
+        // The reads carry no condition (a choice of row by liveness became a branch per frame): frames past the workgroup's
+        // last read the last even or odd row again, lags past max_period read entry max_period -- all in bounds, none of
+        // these values used.  A clamped row is read at the thread's own lags, which only this thread writes; entry
+        // max_period read by a thread whose lag lies past it belongs to another thread, which in troughs mode may be
+        // writing its quotient over it in this same unsynchronised loop: a race on a value that is never used.
+        auto q_live = [&](int i, int u) { const int tau = tid + 256 * u; return fr[i] >= 0 && tau >= minp && tau <= mp; };
+        auto cs_read = [&](int i, double (&c)[3]) {
+            const double *src = (i & 1) ? zrows + min(i >> 1, frames_per_wg / 2 - 1) * RS
+                                        : reinterpret_cast<const double *>(en + min(i, frames_per_wg - 2) * en_stride);
+#pragma unroll
+            for (int u = 0; u < 3; ++u) c[u] = src[min(tid + 256 * u, mp)];
+        };
 #pragma unroll
         for (int i = 0; i < kFramesPerWg; ++i) {
             double *__restrict__ drow = p.dfn + (fr[i] < 0 ? 0 : fr[i]) * (int64_t)p.lag_stride;
-            double *__restrict__ cs = row_of(i);
+            double *cs = row_of(i);
+            double cv[3];
+            cs_read(i, cv);
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int u = 0; u < 3; ++u) {
                 const int tau = tid + 256 * u;
-                if (fr[i] >= 0 && tau >= minp && tau <= mp) {
-                    const double yv = dv[i][u] / (cs[tau] / (double)tau + DBL_MIN);
-                    if (troughs) cs[tau] = yv;          // the CMND stays in LDS, over the cumsum entry this thread has just read
+                if (q_live(i, u)) {
+                    const double yv = dv[i][u] / (cv[u] / (double)tau + DBL_MIN);
+                    if (troughs) cs[tau] = yv;          // the CMND stays in LDS, over the cumsum entry this thread has read (into cv)
                     else drow[tau] = yv;
                 }
             }
