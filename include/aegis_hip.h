@@ -687,6 +687,66 @@ int aegis_analyze_beats(aegis_handle *h, const float *const *pcm, const int64_t 
                         const aegis_onset_params *onset_params, const aegis_beat_params *beat_params, float *env_out /* NULL ok */,
                         uint8_t *beat_mask, int64_t *n_beats, double *bpm_out);
 
+/* --- Median-filter harmonic / percussive separation: the medians and the soft masks ---------------------------------
+ * The reference separates stems by shelling out to demucs; this is librosa 0.10's decompose.hpss(S, mask=True)
+ * and util.softmask, written from memory of upstream, in a fixed arithmetic order: csrc/hpss.h states them once and is the
+ * contract, DESIGN.md 3.19 explains them, tools/hpss_restated.py restates them in NumPy.
+ *   medians     harm[k, t] = median S[k, t - r_h .. t + r_h], perc[k, t] = median S[k - r_p .. k + r_p, t], r = (win - 1) / 2,
+ *               the edges reflected about the half sample (scipy.ndimage.median_filter's mode="reflect"), as often as an
+ *               axis shorter than the radius needs.  Selections: bit-equal to scipy's.
+ *   soft masks  float32: R = other * float(margin); Z = max(own, R); where Z < FLT_MIN the mask is 0.5 when both margins
+ *               are 1 and 0 otherwise; elsewhere a = (own / Z)^p, b = (R / Z)^p, mask = a / (a + b).  p = 2 is one
+ *               multiply, p = 1 none, p = +inf the hard mask own > R.  Subnormals are not flushed.
+ * aegis_hpss_params: win_harm / win_perc odd, 1..63 (-1: 31); an even or out-of-range window is AEGIS_ERR_INVALID.  power
+ * 1, 2 or +inf (0: 2); any other positive power is AEGIS_ERR_UNSUPPORTED (it would need powf, which no restatement can
+ * pin); negative or NaN is AEGIS_ERR_INVALID.  Margins finite and >= 1 (0: 1).  pass_frames: the output frames one device
+ * pass holds (0: automatic, what 1 GiB of workspace holds at 20 n_bins bytes per frame); a clip that does not fit is cut
+ * in time with a halo of r_h frames, and no result depends on the cuts.
+ *   aegis_hpss_masks   magnitudes from host memory, per clip float32 [n_bins, n_frames[c]] C-order, clip after clip; n_bins
+ *                      1..4096, every clip at least one frame.  Every value must be finite with its sign bit clear (checked
+ *                      on the device: AEGIS_ERR_INVALID with a message that names the clip; the outputs are then
+ *                      undefined).  harm, perc, mask_harm, mask_perc: each NULL or float32 in the layout of S.
+ *   aegis_stft         PCM as aegis_analyze_batch takes it -> the spectrogram librosa.stft(y, n_fft=2048, hop_length=hop,
+ *                      center=True, pad_mode="constant") gives: the handle's framing (n_fft / 2 zeros each side, F = 1 +
+ *                      n_samples / hop frames, a clip without samples one frame of zeros), the periodic Hann window in
+ *                      float64, the float64 DFT of w x rounded to complex64.  D (NULL ok): per clip complex64 [1025, F]
+ *                      C-order as interleaved (re, im) floats, clip after clip; S (NULL ok): float32 in the same layout,
+ *                      S = float(sqrt(double(re)^2 + double(im)^2)) of the ROUNDED D, so S is a function of D's bits.
+ *                      The handle's n_fft must be 2048 (the transform csrc/fft8.h holds) and its hop 1..2048:
+ *                      otherwise AEGIS_ERR_UNSUPPORTED.  Samples are checked as with AEGIS_OPT_CHECK_FINITE.
+ *   aegis_istft        D as aegis_stft lays it out (per clip complex64 [1025, 1 + n_samples[c] / hop]) -> y float32, the
+ *                      clips one after the other, n_samples[c] values each: librosa.istft(D, hop_length=hop, length=n).
+ *                      Frame t is w * irfft(D[:, t]) in float64 (the imaginary parts of bins 0 and 1024 are ignored); every
+ *                      output sample GATHERS its frames in ascending t into one float64 sum (no atomics: the same bits on
+ *                      every run), divided by the window sum-square where that exceeds FLT_MIN, trimmed by n_fft / 2, cut
+ *                      to n_samples[c], rounded to float32.
+ *   aegis_hpss         PCM -> y_harm, y_perc (each NULL or float32 concatenated like y): aegis_stft, the masks of its
+ *                      magnitudes (params as for aegis_hpss_masks), Y_c = mask_c * D in float32, aegis_istft's
+ *                      resynthesis.  Nothing of the complex spectrum is stored: the resynthesis kernel recomputes the
+ *                      forward transform (the same code, the same bits) and takes both stems of a frame out of ONE
+ *                      inverse transform.  A clip of 0 samples yields nothing.  Passes are whole clips here
+ *                      (pass_frames bounds their frame total; a clip is never cut).
+ * Invalid requests are rejected before the device is looked at (a device = -1 handle rejects the same ones and answers
+ * AEGIS_ERR_DEVICE to a valid one).  A clip's results depend on that clip alone.
+ * Kernel time: "hpss_stft", "hpss_check", "hpss_median_t", "hpss_median_f" and "hpss_synth" (frames and gather) of
+ * aegis_last_kernel_ms, summed over a call's passes.  Blocking; host
+ * pointers. */
+typedef struct aegis_hpss_params {
+    int32_t win_harm, win_perc;          /* -1: 31 */
+    int32_t pass_frames;                 /* 0: automatic */
+    int32_t reserved;
+    double power;                        /* 0: 2.0; 1, 2 or +inf */
+    double margin_harm, margin_perc;     /* 0: 1.0 */
+} aegis_hpss_params;
+int aegis_stft(aegis_handle *h, const float *const *pcm, const int64_t *n_samples, int32_t n_clips, float *D /* NULL ok */,
+               float *S /* NULL ok */);
+int aegis_istft(aegis_handle *h, const float *D, const int64_t *n_samples, int32_t n_clips, float *y);
+int aegis_hpss(aegis_handle *h, const float *const *pcm, const int64_t *n_samples, int32_t n_clips, const aegis_hpss_params *p,
+               float *y_harm /* NULL ok */, float *y_perc /* NULL ok */);
+int aegis_hpss_masks(aegis_handle *h, const float *S, const int64_t *n_frames, int32_t n_clips, int32_t n_bins,
+                     const aegis_hpss_params *p, float *harm /* NULL ok */, float *perc /* NULL ok */,
+                     float *mask_harm /* NULL ok */, float *mask_perc /* NULL ok */);
+
 /* --- Effect chain: distortion, reverb, delay, chorus (aegis_engine_core/effect_learning_loop.py:56-275) ----------
  * The reference's pure-NumPy effects, each ending in a whole-clip normalisation, which its learning loop
  * (effect_learning_loop.py:489-725) puts between the synthesiser and the engine.  Float64 throughout.

@@ -105,6 +105,11 @@ class BeatParams(C.Structure):
                 ("tightness", _F64), ("bpm", _F64)]
 
 
+class HpssParams(C.Structure):
+    _fields_ = [("win_harm", _I32), ("win_perc", _I32), ("pass_frames", _I32), ("reserved", _I32), ("power", _F64),
+                ("margin_harm", _F64), ("margin_perc", _F64)]
+
+
 class Effect(C.Structure):
     _fields_ = [("kind", _I32), ("n_ir", _I32), ("p0", _F64), ("p1", _F64), ("ir", _P)]
 
@@ -114,7 +119,8 @@ STRUCTS = {"aegis_config": Config, "aegis_outputs": Outputs, "aegis_pcm_clip": P
            "aegis_stream_commit": StreamCommit, "aegis_event": Event, "aegis_event_params": EventParams, "aegis_run_fit": RunFit,
            "aegis_event_batch": EventBatch, "aegis_synth_note": SynthNote, "aegis_adsr_params": AdsrParams,
            "aegis_fit_note": FitNote, "aegis_verify_event": VerifyEvent, "aegis_salience_params": SalienceParams,
-           "aegis_onset_params": OnsetParams, "aegis_beat_params": BeatParams, "aegis_effect": Effect}
+           "aegis_onset_params": OnsetParams, "aegis_beat_params": BeatParams, "aegis_hpss_params": HpssParams,
+           "aegis_effect": Effect}
 
 _OUT, _ADSR, _SAL = C.POINTER(Outputs), C.POINTER(AdsrParams), C.POINTER(SalienceParams)
 _FRAMES, _ONS, _BEAT = C.POINTER(StreamFrames), C.POINTER(OnsetParams), C.POINTER(BeatParams)
@@ -168,6 +174,10 @@ PROTOTYPES = {
     "aegis_beat_track": (C.c_int, [_P, _P, _P, _I32, _BEAT, _P, _P, _P, _P, _P, _P, _P]),
     "aegis_beat_tables": (C.c_int, [_I32, _F64, _P, _P]),
     "aegis_analyze_beats": (C.c_int, [_P, _PP, _PI64, _I32, _ONS, _BEAT, _P, _P, _P, _P]),
+    "aegis_stft": (C.c_int, [_P, _PP, _PI64, _I32, _P, _P]),
+    "aegis_istft": (C.c_int, [_P, _P, _P, _I32, _P]),
+    "aegis_hpss": (C.c_int, [_P, _PP, _PI64, _I32, C.POINTER(HpssParams), _P, _P]),
+    "aegis_hpss_masks": (C.c_int, [_P, _P, _P, _I32, _I32, C.POINTER(HpssParams), _P, _P, _P, _P]),
     "aegis_reverb_ir": (_I64, [_F64, _I32, _P, _I64]),
     "aegis_effects": (C.c_int, [_P, _I32, _I32, _PP, _I32, _P, C.POINTER(Effect), _P, _PP, _PP]),
     "aegis_get_table": (_I64, [_P, _S, _P, _I64]),

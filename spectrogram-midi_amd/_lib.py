@@ -673,6 +673,88 @@ class Handle:
         off = _marshal.offsets(frames)
         return [(env[off[c]:off[c + 1]].copy() if want_env else None, float(bpm[c]), beats[c]) for c in range(n)]
 
+    def stft(self, clips, want_D=True, want_S=False):
+        """aegis_stft: the complex spectrogram of PCM clips (librosa.stft at n_fft 2048, the handle's hop, center=True,
+        zero padding) in ONE call -> per clip (D complex64 [1025, F_c] or None, S float32 [1025, F_c] or None)."""
+        clips, ptrs, lens = _marshal.clips(clips, np.float32)
+        n = len(clips)
+        if n == 0:
+            return []
+        frames = [self.frames_for(len(c)) for c in clips]
+        F = sum(frames)
+        D = np.zeros(F * 1025, np.complex64) if want_D else None
+        S = np.zeros(F * 1025, np.float32) if want_S else None
+        self._check(self.lib.aegis_stft(self._h, ptrs, lens, n, D.ctypes.data if want_D else None, S.ctypes.data if want_S else None))
+        Ds = _marshal.per_clip(D, frames, 1025) if want_D else [None] * n
+        Ss = _marshal.per_clip(S, frames, 1025) if want_S else [None] * n
+        return list(zip(Ds, Ss))
+
+    def istft(self, spectrograms, lengths):
+        """aegis_istft: complex64 [1025, 1 + n // hop] spectrograms and their lengths n in ONE call -> list of float32 [n]."""
+        lens = [int(n) for n in lengths]
+        Ds = [np.ascontiguousarray(D, np.complex64) for D in spectrograms]
+        if len(Ds) != len(lens):
+            raise ValueError("one length per spectrogram")
+        if not Ds:
+            return []
+        for D, n in zip(Ds, lens):
+            if D.ndim != 2 or n < 0 or D.shape != (1025, self.frames_for(n)):
+                raise ValueError(f"a spectrogram of a clip of {n} samples is [1025, {self.frames_for(max(n, 0))}], not {D.shape}")
+        flat = _marshal.concat([D.ravel() for D in Ds], np.complex64)
+        ns = np.asarray(lens, np.int64)
+        y = np.zeros(max(sum(lens), 1), np.float32)
+        self._check(self.lib.aegis_istft(self._h, flat.ctypes.data, ns.ctypes.data, len(Ds), y.ctypes.data))
+        off = _marshal.offsets(lens)
+        return [y[off[c]:off[c + 1]].copy() for c in range(len(Ds))]
+
+    def hpss(self, clips, params=None, want_harm=True, want_perc=True):
+        """aegis_hpss: PCM clips in ONE call -> per clip (y_harm float32 [n] or None, y_perc float32 [n] or None)."""
+        clips, ptrs, lens = _marshal.clips(clips, np.float32)
+        n = len(clips)
+        if n == 0:
+            return []
+        sizes = [len(c) for c in clips]
+        yh = np.zeros(max(sum(sizes), 1), np.float32) if want_harm else None
+        yp = np.zeros(max(sum(sizes), 1), np.float32) if want_perc else None
+        self._check(self.lib.aegis_hpss(self._h, ptrs, lens, n, C.byref(params) if params is not None else None,
+                                        yh.ctypes.data if want_harm else None, yp.ctypes.data if want_perc else None))
+        off = _marshal.offsets(sizes)
+        return [(yh[off[c]:off[c + 1]].copy() if want_harm else None, yp[off[c]:off[c + 1]].copy() if want_perc else None)
+                for c in range(n)]
+
+    @staticmethod
+    def hpss_params(win_harm=-1, win_perc=-1, power=0.0, margin_harm=0.0, margin_perc=0.0, pass_frames=0):
+        """aegis_hpss_params; every argument left at its default (None too) takes the library's (windows of 31, power 2,
+        margins of 1, automatic passes).  The library validates."""
+        d = [0.0 if a is None else float(a) for a in (power, margin_harm, margin_perc)]
+        return HpssParams(-1 if win_harm is None else int(win_harm), -1 if win_perc is None else int(win_perc),
+                          0 if pass_frames is None else int(pass_frames), 0, *d)
+
+    def hpss_masks(self, images, params=None, want=("harm", "perc", "mask_harm", "mask_perc")):
+        """aegis_hpss_masks: the running medians along time and along bins of caller magnitudes (a list of float32
+        [n_bins, F_c] arrays, one n_bins) and the two soft masks, in ONE call -> per clip a dict of float32 [n_bins, F_c]
+        arrays under the names of `want`.  params: hpss_params(...).  AegisError with the library's code for what it
+        rejects (ERR_INVALID, ERR_UNSUPPORTED)."""
+        names = ("harm", "perc", "mask_harm", "mask_perc")
+        if any(w not in names for w in want):
+            raise ValueError(f"want holds names of {names}")
+        images = [np.ascontiguousarray(m, dtype=np.float32) for m in images]
+        if not images:
+            return []
+        n_bins = images[0].shape[0] if images[0].ndim == 2 else -1
+        if any(m.ndim != 2 or m.shape[0] != n_bins for m in images):
+            raise ValueError("images must be [n_bins, F] arrays of one n_bins")
+        frames = [m.shape[1] for m in images]
+        flat = _marshal.concat([m.ravel() for m in images], np.float32)
+        nf = np.asarray(frames, np.int64)
+        out = {w: np.zeros(sum(frames) * n_bins, np.float32) for w in names if w in want}
+        self._check(self.lib.aegis_hpss_masks(self._h, flat.ctypes.data, nf.ctypes.data, len(images), n_bins,
+                                              C.byref(params) if params is not None else None,
+                                              *[out[w].ctypes.data if w in out else None for w in names]))
+        off = _marshal.offsets(frames)
+        return [{w: a[off[c] * n_bins:off[c + 1] * n_bins].reshape(n_bins, frames[c]).copy() for w, a in out.items()}
+                for c in range(len(images))]
+
     def synth_parse_smf(self, midi_bytes, want_wheel=False):
         """aegis_synth_parse_smf: (notes in the reference's mix order as a SYNTH_NOTE_DTYPE array, mido's length in
         seconds) of a Standard MIDI File; ValueError for bytes that are not one (mido raises).  Host code.

@@ -20,6 +20,8 @@
 //                     offsets walks every per-clip entry shares (frame_offsets, clip_frames)
 //   aegis_beat.hip    aegis_tempo, aegis_beat_track, aegis_beat_tables, aegis_analyze_beats (tempogram mean, tempo, beat
 //                     tracker; kernels in beat.hip, the mel stage and aegis_onset.hip's envelope stage in front of them)
+//   aegis_hpss.hip    aegis_stft, aegis_istft, aegis_hpss (spectrogram, resynthesis, the whole separation), aegis_hpss_masks (running medians along time and bins and the soft masks of median-filter
+//                     harmonic / percussive separation; kernels in hpss.hip, the pass planner that cuts long clips here)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -147,6 +149,10 @@ struct aegis_handle {
     // aegis_tempo / aegis_beat_track / aegis_analyze_beats: caller envelopes, frame and tile offsets, window, tile sums, tempogram means,
     // moments, per-clip periods / table offsets / tables, local score, cumulative score, back links
     DevBuf bt_env, bt_foff, bt_toff, bt_win, bt_parts, bt_tg, bt_stats, bt_period, bt_taboff, bt_tabs, bt_ls, bt_cum, bt_back;
+    // aegis_hpss_masks: one pass's magnitudes, the two medians, the two masks, its segment records, the first bad element
+    // (aegis_stft: a pass's samples, its three offset tables, the complex spectrum; its magnitudes go to hp_in)
+    DevBuf hp_in, hp_harm, hp_perc, hp_mh, hp_mp, hp_segs, hp_flag, hp_pcm, hp_off, hp_D;
+    DevBuf hp_fa, hp_fb, hp_ya, hp_yb;        // aegis_istft / aegis_hpss: the float64 resynthesis frames of the two stems, their float32 audio
     bool notefit_store = false;               // AEGIS_NOTEFIT_STORE=1 at create: every candidate rendered once into nf_sig and read by the frames instead of recomputed
     int32_t lag_stride = 0, yin_stride = 0, obs_stride = 0;
     aegis::CallPlan plan;                     // the last call's plan: its host arrays stay alive until the stream drained

@@ -13,13 +13,13 @@ import multiprocessing
 
 import numpy as np
 
-from . import _lib, audio_io, beats as _beats, events_native, midi_logic, onsets as _onsets, smf
+from . import _lib, audio_io, beats as _beats, events_native, hpss as _hpss, midi_logic, onsets as _onsets, smf
 from .convert import note_to_hz
 
 _FMIN, _FMAX = note_to_hz("E2"), note_to_hz("C6")
 _ENGINE_ONLY_KWARGS = ("confidence_threshold", "start_time", "end_time", "turbo_mode", "rake_sensitivity",
                        "vibrato_rate", "vibrato_depth", "onsets", "split_on_onsets", "beats", "quantize_to_beats", "beat_subdivisions",
-                       "tempo_map")
+                       "tempo_map", "harmonic", "hpss_margin")
 
 
 class AegisEngine:
@@ -79,8 +79,23 @@ class AegisEngine:
                 f"{name} forwards to the reference's aegis_engine_core.{module} (aegis_engine.py:29-36), which is not "
                 f"importable here ({e}); it is outside the MI355X analyze path") from e
 
-    def separate_stems(self, input_wav, output_dir):
-        return self._reference_core("stems", "separate_stems")(input_wav, output_dir)
+    def separate_stems(self, input_wav, output_dir, method=None):
+        """method=None: forwarded to the reference (demucs) exactly as before.  method="hpss" (not a reference method):
+        median-filter harmonic / percussive separation on the device (hpss.py); writes
+        <output_dir>/hpss/<name>/harmonic.wav and percussive.wav (16-bit, the engine's rate) and returns the harmonic path,
+        as the reference returns other.wav."""
+        if method is None:
+            return self._reference_core("stems", "separate_stems")(input_wav, output_dir)
+        if method != "hpss":
+            raise ValueError("method must be None (the reference's demucs) or 'hpss'")
+        import os
+        y, _ = self.load_audio(input_wav)
+        yh, yp = _hpss.hpss(y, handle=self.handle)
+        out = os.path.join(output_dir, "hpss", os.path.splitext(os.path.basename(input_wav))[0])
+        os.makedirs(out, exist_ok=True)
+        audio_io.write_wav(os.path.join(out, "harmonic.wav"), yh, self.sr)
+        audio_io.write_wav(os.path.join(out, "percussive.wav"), yp, self.sr)
+        return os.path.join(out, "harmonic.wav")
 
     def generate_tabs(self, events):
         return self._reference_core("tabs", "generate_tabs")(events)
@@ -94,13 +109,15 @@ class AegisEngine:
         return self.analyze_files([input_wav], turbo_mode=kwargs.get("turbo_mode", False),
                                   rake_sensitivity=kwargs.get("rake_sensitivity", 0.6), start_time=kwargs.get("start_time", 0),
                                   end_time=kwargs.get("end_time", None), onsets=kwargs.get("onsets", False),
-                                  beats=kwargs.get("beats", False))[0]
+                                  beats=kwargs.get("beats", False), harmonic=kwargs.get("harmonic", False),
+                                  hpss_margin=kwargs.get("hpss_margin", 1.0))[0]
 
     analyze = audio_to_midi      # BASELINE.json's name for the same call
 
-    def analyze_array(self, y, turbo_mode=False, rake_sensitivity=0.6, onsets=False, beats=False):
+    def analyze_array(self, y, turbo_mode=False, rake_sensitivity=0.6, onsets=False, beats=False, harmonic=False, hpss_margin=1.0):
         """audio_to_midi from decoded PCM onward (aegis_engine.py:51-75)."""
-        res = self.analyze_arrays([y], turbo_mode=turbo_mode, rake_sensitivity=rake_sensitivity, onsets=onsets, beats=beats)
+        res = self.analyze_arrays([y], turbo_mode=turbo_mode, rake_sensitivity=rake_sensitivity, onsets=onsets, beats=beats,
+                                  harmonic=harmonic, hpss_margin=hpss_margin)
         return res[0]
 
     # ------------------------------------------------------------------ onsets (not reference methods)
@@ -180,13 +197,23 @@ class AegisEngine:
         """Do the keywords ask for a pass that the batched C++ writer does not know?  Then the bytes come from smf.render."""
         return bool(kwargs.get("split_on_onsets", False) or kwargs.get("quantize_to_beats", False) or kwargs.get("tempo_map", False))
 
-    def analyze_arrays(self, clips, turbo_mode=False, rake_sensitivity=0.6, onsets=False, beats=False, _concatenated=False):
+    def analyze_arrays(self, clips, turbo_mode=False, rake_sensitivity=0.6, onsets=False, beats=False, harmonic=False,
+                       hpss_margin=1.0, _concatenated=False):
         """Batch form: one ragged GPU batch for a folder of clips; element i is what
         audio_to_midi returns for clip i (None for an empty clip).  The arrays of a batch are slices of the batch's
         buffers (one allocation per output, not one per clip).  onsets=True adds "onset_env" and "onset_frames", beats=True
-        "tempo" and "beat_frames"."""
+        "tempo" and "beat_frames".  harmonic=True (not a reference keyword): the analysis runs on the harmonic component of
+        every clip (hpss.py, margin hpss_margin; separated whole, then chunked with turbo_mode); "y" stays the original
+        samples, "y_harmonic" is added, onsets and beats keep using the original samples."""
         clips = [np.ascontiguousarray(c, dtype=np.float32) for c in clips]
         live = [i for i, c in enumerate(clips) if len(c) > 0]
+        original = clips
+        if harmonic and live:
+            stems = self.handle.hpss([clips[i] for i in live], _lib.Handle.hpss_params(margin_harm=hpss_margin, margin_perc=hpss_margin),
+                                     want_perc=False)
+            clips = list(clips)
+            for i, (yh, _) in zip(live, stems):
+                clips[i] = yh
         results = [None] * len(clips)
         if not live:
             return (results, None, None, live) if _concatenated else results
@@ -215,26 +242,28 @@ class AegisEngine:
         for i, r in zip(live, frames):
             results[i] = {"rake_mask": r["rake_mask"], "f0": r["f0"],
                           "voiced_flag": r["voiced_flag"], "voiced_probs": r["voiced_prob"],
-                          "rms": r["rms"], "y": clips[i]}
+                          "rms": r["rms"], "y": original[i]}
+            if harmonic:
+                results[i]["y_harmonic"] = clips[i]
         if onsets:
-            self._add_onsets(results, clips)
+            self._add_onsets(results, original)
         if beats:
-            self._add_beats(results, clips)
+            self._add_beats(results, original)
         return (results, bufs, off, live) if _concatenated else results
 
     def analyze_files(self, paths, turbo_mode=False, rake_sensitivity=0.6, start_time=0, end_time=None, want_y=True,
-                      onsets=False, beats=False, _concatenated=False):
+                      onsets=False, beats=False, harmonic=False, hpss_margin=1.0, _concatenated=False):
         """A folder of WAV files -> element i is what audio_to_midi(paths[i], None, ...) returns.  The files are read
         one after the other as raw sample bytes (audio_io.load_pcm); decoding, the channel mean and the resampling to
         the engine rate run on the GPU, inside the analysis (Handle.analyze_pcm).  want_y=False: "y" is None and the
         samples never come back from the device."""
         duration = (end_time - start_time) if end_time else None
         srcs = audio_io.load_pcm_files(paths, self.sr, start_time, duration)
-        if turbo_mode:          # decode only, then the Turbo-Mode analysis of the decoded clips
+        if turbo_mode or harmonic:          # decode only, then the analysis of the decoded clips (separated first with harmonic)
             h = self.handle
             ys = [r["y"] for r in h.analyze_pcm(srcs, stages=0)] if srcs else []
-            got = self.analyze_arrays(ys, turbo_mode=True, rake_sensitivity=rake_sensitivity, onsets=onsets, beats=beats,
-                                      _concatenated=_concatenated)
+            got = self.analyze_arrays(ys, turbo_mode=turbo_mode, rake_sensitivity=rake_sensitivity, onsets=onsets, beats=beats,
+                                      harmonic=harmonic, hpss_margin=hpss_margin, _concatenated=_concatenated)
             if not want_y:
                 for r in (got[0] if _concatenated else got):
                     if r is not None:
@@ -275,7 +304,8 @@ class AegisEngine:
         got = self.analyze_files(paths, turbo_mode=kwargs.get("turbo_mode", False),
                                  rake_sensitivity=kwargs.get("rake_sensitivity", 0.6), start_time=kwargs.get("start_time", 0),
                                  end_time=kwargs.get("end_time", None), want_y=kwargs.pop("want_y", True),
-                                 onsets=kwargs.get("onsets", False), beats=kwargs.get("beats", False), _concatenated=True)
+                                 onsets=kwargs.get("onsets", False), beats=kwargs.get("beats", False),
+                                 harmonic=kwargs.get("harmonic", False), hpss_margin=kwargs.get("hpss_margin", 1.0), _concatenated=True)
         return self._events_batch(len(paths), got, want_midi, kwargs)
 
     def audio_to_midi_batch(self, clips, want_midi=True, **kwargs):
@@ -284,7 +314,8 @@ class AegisEngine:
         (C++, clips in parallel).  Empty clips give (None, [], None).  kwargs as for both reference methods."""
         turbo = kwargs.get("turbo_mode", False)
         got = self.analyze_arrays(clips, turbo_mode=turbo, rake_sensitivity=kwargs.get("rake_sensitivity", 0.6),
-                                  onsets=kwargs.get("onsets", False), beats=kwargs.get("beats", False), _concatenated=True)
+                                  onsets=kwargs.get("onsets", False), beats=kwargs.get("beats", False),
+                                  harmonic=kwargs.get("harmonic", False), hpss_margin=kwargs.get("hpss_margin", 1.0), _concatenated=True)
         return self._events_batch(len(clips), got, want_midi, kwargs)
 
     def _events_batch(self, n, got, want_midi, kwargs):
