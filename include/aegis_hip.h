@@ -175,7 +175,9 @@ int aegis_pcm_geometry(int32_t handle_rate, const aegis_pcm_clip *clip, int64_t 
 
 /* AegisEngine.detect_rake_patterns(S_dB) (aegis_engine.py:38-39 -> vision.py:3-38) on a
  * caller-supplied dB image in host memory, [n_mels, n_frames] C-order; mask_out is
- * uint8[n_frames] in host memory.  Blocking. */
+ * uint8[n_frames] in host memory.  Blocking.  A column that holds a NaN is decided as NumPy decides it: its peak is NaN
+ * (np.max hands a NaN on), `peak < -60` is false and no band compares above NaN - 20, so it has 0 active bands and is a
+ * candidate only under a negative ratio.  Infinities need nothing special (-inf is below every bound, +inf is a peak). */
 int aegis_rake_patterns(aegis_handle *h, const float *S_dB, int32_t n_mels, int64_t n_frames,
                         double broadband_threshold_ratio, uint8_t *mask_out);
 
@@ -820,7 +822,8 @@ int aegis_set_table(aegis_handle *h, const char *name, const double *data, int64
 
 /* Scalar parameters derived at create time.  name in {"min_period","max_period",
  * "n_lags","n_pitch_bins","transition_width","n_trans_classes","max_frames_per_pass",
- * "lag_stride","yin_stride","obs_stride","last_frames","pyin_init"}; of the last call (its last pass): "last_passes",
+ * "lag_stride","yin_stride","obs_stride","last_frames","pyin_init","rake_min_frames","rake_max_frames" (the run-length
+ * window of the rake mask in frames, int(10 / ms_per_frame) and int(30 / ms_per_frame): vision.py:23-25)}; of the last call (its last pass): "last_passes",
  * "last_chunks", "last_dense", "last_proportional", "last_balanced", "last_persistent", "last_split_segments"; since create:
  * "split_passes", "split_segments", "split_flagged_clips" (clips the sequential kernel decoded again), "split_unlocked_clips";
  * of the last split pass: "split_rounds" (rounds of second speculation that had work), "split_viterbi_us" (measured time of its Viterbi
@@ -913,6 +916,23 @@ int aegis_debug_set_observations(aegis_handle *h, const double *logobs, const do
  * device is looked at) AND a finite CMND d[tau] / (cumsum(d[1:])[tau] / tau + tiny) at every lag min_period .. max_period,
  * which is the caller's to ensure: behaviour on rows whose CMND holds a NaN or an infinity is unspecified. */
 int aegis_debug_set_difference(aegis_handle *h, const double *d, int64_t F);
+
+/* Replaces the column flags the rake mask's run-length filter reads, for the tests that put that filter (rake_runs_kernel:
+ * the two walks and their shared step budget, the clip's first and last frame, the window min_frames <= length <=
+ * max_frames -- aegis_get_param "rake_min_frames" / "rake_max_frames") under runs audio does not produce: flags is u8[F],
+ * one byte per output frame in the caller's clip order, clip after clip (the order of the output arrays).  Arms the handle
+ * for the NEXT aegis_analyze_batch / _batch_device / _pcm call only: that call must have the RAKE stage and exactly F
+ * frames in total (AEGIS_ERR_INVALID otherwise, the handle stays usable).  It runs the kernels and the schedule of an
+ * ordinary call on the samples it is handed, the column kernel it would take included; behind that kernel, on the same
+ * stream, one more kernel (inject_rake_kernel, one thread per workspace frame of the pass) overwrites the pass's column
+ * flags with the given ones -- what aegis_debug_fetch "rake_raw" then returns -- and the run-length filter follows
+ * unchanged.  Every other output is the unarmed call's.  The handle is disarmed when that call returns, whatever it
+ * returns; stream pushes neither consume nor disturb the arming.  flags == NULL disarms; arming again replaces the flags;
+ * arming while another injection hook is armed (aegis_debug_set_observations, aegis_debug_set_difference; or either of
+ * them while this one is) is AEGIS_ERR_INVALID: one hook per call.
+ * Domain: every byte; a frame is flagged where its byte is not 0.  A device = -1 handle has no analyze call to arm and
+ * answers AEGIS_ERR_INVALID. */
+int aegis_debug_set_rake_columns(aegis_handle *h, const uint8_t *flags, int64_t F);
 
 /* aegis_debug_set_observations for ONE stream, for the tests that put the streaming Viterbi (launches that start inside a
  * 16-step chunk, the column carried across pushes, the live_state preview, the commit walk) under adversarial rows:

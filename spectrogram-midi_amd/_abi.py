@@ -188,6 +188,7 @@ PROTOTYPES = {
     "aegis_debug_pitch_bins": (C.c_int, [_P, _P, _I64, _P, _P, _P]),
     "aegis_debug_set_observations": (C.c_int, [_P, _P, _P, _I64]),
     "aegis_debug_set_difference": (C.c_int, [_P, _P, _I64]),
+    "aegis_debug_set_rake_columns": (C.c_int, [_P, _P, _I64]),
     "aegis_debug_stream_set_observations": (C.c_int, [_P, _P, _P, _I64]),
     "aegis_debug_stream_fetch": (_I64, [_P, _S, _P, _I64]),
     "aegis_debug_plan": (_I64, [_P, _PI64, _I32, _I32, _I32, _I32, _P, _I64]),

@@ -166,6 +166,20 @@ class Handle:
             raise ValueError("d must be [F, max_period + 1]")
         self._check(fn(self._h, rows.ctypes.data, rows.shape[0]))
 
+    def set_rake_columns(self, flags):
+        """aegis_debug_set_rake_columns: the NEXT analyze call's run-length filter reads these column flags (flags [F], one
+        per output frame in the caller's clip order; a frame is flagged where its value is not 0) in place of its column
+        kernel's; None disarms.  The call needs the rake stage and exactly F frames."""
+        fn = self.lib.aegis_debug_set_rake_columns
+        if flags is None:
+            self._check(fn(self._h, None, 0))
+            return
+        v = np.asarray(flags)
+        if v.ndim != 1:
+            raise ValueError("flags must be [F]")
+        v = np.ascontiguousarray(v if v.dtype == np.uint8 else v != 0, dtype=np.uint8)      # (bytes go through as they are)
+        self._check(fn(self._h, v.ctypes.data, len(v)))
+
     # aegis_debug_plan: entry kinds, option bits and the per-pass flag bits (include/aegis_hip.h AEGIS_PLAN_*)
     PLAN_ENTRIES = {"device": 0, "caller_stream": 1, "host_fed": 2}
     PLAN_FLAGS = ("split", "split_auto", "want_hybrid", "hybrid", "hyb_part", "balanced", "may_persist", "persistent",

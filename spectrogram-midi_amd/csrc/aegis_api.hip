@@ -438,11 +438,20 @@ static int analyze_device_locked(aegis_handle *h, const float *d_pcm, const int6
             return AEGIS_ERR_INVALID;
         }
     }
-    if (h->inject_d.armed) {    // aegis_debug_set_difference: likewise (never both: each setter refuses while the other hook is armed)
+    if (h->inject_d.armed) {    // aegis_debug_set_difference: likewise (never two: each setter refuses while another hook is armed)
         int64_t F = 0;
         for (int i = 0; i < n_clips; ++i) F += 1 + (sample_offsets[i + 1] - sample_offsets[i]) / t.hop;
         if (!(stages & AEGIS_STAGE_PYIN) || F != h->inject_d.F) {
             h->err = "injected difference rows: the call needs the PYIN stage and exactly " + std::to_string(h->inject_d.F) + " frames (it has " +
+                     std::to_string(F) + ")";
+            return AEGIS_ERR_INVALID;
+        }
+    }
+    if (h->inject_r.armed) {    // aegis_debug_set_rake_columns: the flags are indexed by this call's output frames
+        int64_t F = 0;
+        for (int i = 0; i < n_clips; ++i) F += 1 + (sample_offsets[i + 1] - sample_offsets[i]) / t.hop;
+        if (!(stages & AEGIS_STAGE_RAKE) || F != h->inject_r.F) {
+            h->err = "injected rake columns: the call needs the RAKE stage and exactly " + std::to_string(h->inject_r.F) + " frames (it has " +
                      std::to_string(F) + ")";
             return AEGIS_ERR_INVALID;
         }
@@ -632,7 +641,9 @@ static int analyze_device_locked(aegis_handle *h, const float *d_pcm, const int6
         }
         // ---- finalize ---------------------------------------------------------------------------------------------------
         hipStream_t se = m.hybrid ? sd : sv;       // the stream the pass ends on
-        begin_event(h, "finalize", fa); launch_finalize_mel(p, h->dt, fa); end_event(h, fa);
+        begin_event(h, "finalize", fa);
+        launch_finalize_mel(p, h->dt, fa, h->inject_r.armed ? h->inject_r.flags.as<const uint8_t>() : nullptr);
+        end_event(h, fa);
         if (py) { begin_event(h, "finalize", se); launch_decode(p, h->dt, se); end_event(h, se); }
         // pass done = its last kernels on the frame stream and on the Viterbi stream
         if (se != fa) {
@@ -707,11 +718,11 @@ static int run_with_recovery(aegis_handle *h, const std::function<int()> &attemp
     }
 }
 
-// aegis_debug_set_observations and aegis_debug_set_difference arm ONE analyze call: every analyze entry holds one of these from its first line on, so
+// aegis_debug_set_observations, aegis_debug_set_difference and aegis_debug_set_rake_columns arm ONE analyze call: every analyze entry holds one of these from its first line on, so
 // the handle is disarmed when the entry returns, whatever it returns (declared before the entry's lock: it runs after it)
 struct DisarmInjection {
     aegis_handle *h;
-    ~DisarmInjection() { std::lock_guard<std::mutex> lock(h->mu); h->inject.armed = false; h->inject_d.armed = false; }
+    ~DisarmInjection() { std::lock_guard<std::mutex> lock(h->mu); h->inject.armed = false; h->inject_d.armed = false; h->inject_r.armed = false; }
 };
 
 int aegis_analyze_batch_device(aegis_handle *h, const float *d_pcm, const int64_t *sample_offsets,
@@ -774,7 +785,7 @@ static int host_fed_locked(aegis_handle *h, const std::vector<int64_t> &off, int
 }  // extern "C"
 int aegis::mel_host_locked(aegis_handle *h, const float *const *pcm, const int64_t *n_samples, int32_t n_clips, std::vector<int64_t> &off,
                            std::vector<int64_t> &foff) {
-    struct Disarm { aegis_handle *h; ~Disarm() { h->inject.armed = false; h->inject_d.armed = false; } } disarm{h};   // as every analyze entry
+    struct Disarm { aegis_handle *h; ~Disarm() { h->inject.armed = false; h->inject_d.armed = false; h->inject_r.armed = false; } } disarm{h};   // as every analyze entry
     off.assign((size_t)n_clips + 1, 0);
     foff.assign((size_t)n_clips + 1, 0);
     for (int i = 0; i < n_clips; ++i) {

@@ -454,6 +454,8 @@ int64_t aegis_get_param(const aegis_handle *h, const char *name) {
     if (n == "last_hybrid_step") return lp ? lp->hyb_S : 0;
     if (n == "last_persistent") return lp ? lp->persistent : 0;
     if (n == "pyin_init") return t.pyin_init;
+    if (n == "rake_min_frames") return rake_frame_bounds(t).min_frames;
+    if (n == "rake_max_frames") return rake_frame_bounds(t).max_frames;
     if (n == "cqt_bank_builds") return h->cqt_bank_builds;
     if (n == "cqt_banks") return (int64_t)h->cqt_banks.size();
     if (n == "cqt_bank_cap") return h->cqt_bank_cap;
@@ -732,6 +734,7 @@ int aegis_debug_set_observations(aegis_handle *h, const double *logobs, const do
     if (!logobs) return AEGIS_OK;
     if (!logunv || F <= 0) { h->err = "bad argument"; return AEGIS_ERR_INVALID; }
     if (h->inject_d.armed) { h->err = "injected observations: injected difference rows are armed already (one hook per call)"; return AEGIS_ERR_INVALID; }
+    if (h->inject_r.armed) { h->err = "injected observations: injected rake columns are armed already (one hook per call)"; return AEGIS_ERR_INVALID; }
     int rc;
     if ((rc = check_observation_rows(h, logobs, logunv, F)) != AEGIS_OK) return rc;
     const int B = h->tab.n_bins;
@@ -756,6 +759,7 @@ int aegis_debug_set_difference(aegis_handle *h, const double *d, int64_t F) {
     if (!d) return AEGIS_OK;
     if (F <= 0) { h->err = "bad argument"; return AEGIS_ERR_INVALID; }
     if (h->inject.armed) { h->err = "injected difference rows: injected observations are armed already (one hook per call)"; return AEGIS_ERR_INVALID; }
+    if (h->inject_r.armed) { h->err = "injected difference rows: injected rake columns are armed already (one hook per call)"; return AEGIS_ERR_INVALID; }
     const int64_t W = (int64_t)h->tab.max_period + 1;
     for (int64_t f = 0; f < F; ++f)
         for (int64_t tau = 0; tau < W; ++tau)
@@ -771,6 +775,30 @@ int aegis_debug_set_difference(aegis_handle *h, const double *d, int64_t F) {
     HIPCHK(h, hipMemcpy(h->inject_d.d.p, d, (size_t)F * W * 8, hipMemcpyHostToDevice));
     h->inject_d.F = F;
     h->inject_d.armed = true;
+    return AEGIS_OK;
+    } catch (...) { return abi_fail(h); }
+}
+
+int aegis_debug_set_rake_columns(aegis_handle *h, const uint8_t *flags, int64_t F) {
+    try {
+    if (!h) return AEGIS_ERR_INVALID;
+    std::lock_guard<std::mutex> lock(h->mu);
+    h->inject_r.armed = false;
+    if (!flags) return AEGIS_OK;
+    if (F <= 0) { h->err = "bad argument"; return AEGIS_ERR_INVALID; }
+    if (h->inject.armed || h->inject_d.armed) {
+        h->err = std::string("injected rake columns: injected ") + (h->inject.armed ? "observations" : "difference rows") + " are armed already (one hook per call)";
+        return AEGIS_ERR_INVALID;
+    }
+    // (every byte is in the domain: a flag is set where the byte is not 0; nothing to validate but the handle itself)
+    if (h->device < 0) { h->err = "injected rake columns: the handle was created with device=-1 (host tables only), no analyze call can take them"; return AEGIS_ERR_INVALID; }
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipDeviceSynchronize());        // (an earlier armed call that returned without a sync may still read the flags)
+    int rc;
+    if ((rc = ensure(h, h->inject_r.flags, (size_t)F)) != AEGIS_OK) return rc;
+    HIPCHK(h, hipMemcpy(h->inject_r.flags.p, flags, (size_t)F, hipMemcpyHostToDevice));
+    h->inject_r.F = F;
+    h->inject_r.armed = true;
     return AEGIS_OK;
     } catch (...) { return abi_fail(h); }
 }

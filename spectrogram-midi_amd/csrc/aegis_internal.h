@@ -94,6 +94,9 @@ struct aegis_handle {
     // aegis_debug_set_difference: rows [F][max_period + 1] in the caller's clip order that the next analyze call's frame kernel
     // stores in place of its own difference function (armed for one call, like `inject`; never both)
     struct InjectD { bool armed = false; int64_t F = 0; DevBuf d; } inject_d;
+    // aegis_debug_set_rake_columns: flags [F] in the caller's clip order that the next analyze call writes over each pass's
+    // column flags, in front of the run-length filter (armed for one call, like the two above; one hook per call)
+    struct InjectR { bool armed = false; int64_t F = 0; DevBuf flags; } inject_r;
     uint32_t chunk_gen = 0;                   // generation of the chunk flags of a persistent Viterbi launch
     int test_drop_signal = -1;
     // The single Viterbi launch of a balanced pass and its fall-back (run_with_recovery, aegis_api.hip)

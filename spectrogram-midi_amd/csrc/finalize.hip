@@ -181,6 +181,16 @@ __global__ __launch_bounds__(256) void rake_pow_kernel(PassParams p) {
     p.rake_raw[f] = rake_candidate(active, nm, p.rake_ratio) ? 1 : 0;
 }
 
+// Test hook (aegis_debug_set_rake_columns): behind the column kernel of an armed call, workspace row f of the pass takes
+// the flag of its output frame from src [out_total] (the caller's clip order).  One thread per workspace frame; src is an
+// argument of this launch alone, and rake_runs_kernel behind it knows nothing.
+__global__ __launch_bounds__(256) void inject_rake_kernel(PassParams p, const uint8_t *__restrict__ src) {
+    const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (f >= p.n_frames) return;
+    const int c = find_clip(p.frame_off, p.n_clips, f);
+    p.rake_raw[f] = src[out_index(p, c, f - p.frame_off[c])] != 0 ? 1 : 0;
+}
+
 // ------------------------------------------------------------------------------------------
 // Kernel 5c: run-length filter of vision.py:27-36.  A candidate frame survives when its run
 // is closed before the end of the clip and min_frames <= length <= max_frames.
@@ -213,9 +223,17 @@ __global__ __launch_bounds__(256) void rake_cols_kernel(const float *__restrict_
     const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (t >= F) return;
     float cmax = -INFINITY;
-    for (int m = 0; m < n_mels; ++m) cmax = fmaxf(cmax, sdb[(int64_t)m * F + t]);
+    bool has_nan = false;       // fmaxf skips a NaN, np.max hands it on: the flag travels beside the maximum
+    for (int m = 0; m < n_mels; ++m) {
+        const float v = sdb[(int64_t)m * F + t];
+        has_nan = has_nan || v != v;
+        cmax = fmaxf(cmax, v);
+    }
     bool cand = false;
-    if (!(cmax < -60.0f)) {
+    if (has_nan) {
+        // peak = NaN: `peak < -60` is false and no band compares above NaN - 20, so the column counts 0 active bands
+        cand = 0.0 > ratio;
+    } else if (!(cmax < -60.0f)) {
         const float thr = cmax - 20.0f;
         int active = 0;
         for (int m = 0; m < n_mels; ++m) active += sdb[(int64_t)m * F + t] > thr ? 1 : 0;
@@ -275,12 +293,13 @@ void launch_rake_columns(const PassParams &p, bool from_power, hipStream_t s) {
     if (from_power) hipLaunchKernelGGL(rake_pow_kernel, dim3((unsigned)((p.n_frames + 255) / 256)), dim3(256), 0, s, p);
     else hipLaunchKernelGGL(db_rake_kernel, dim3((unsigned)((p.n_frames + 63) / 64)), dim3(256), 0, s, p);
 }
-void launch_finalize_mel(const PassParams &p, const DevTables &, hipStream_t s) {
+void launch_finalize_mel(const PassParams &p, const DevTables &, hipStream_t s, const uint8_t *inject_rake) {
     if (p.n_frames == 0) return;
     const unsigned g256 = (unsigned)((p.n_frames + 255) / 256);
     if (p.stages & 0x3u) {
         // the dB values themselves are wanted only for the image and its column means; the flags alone come from mel power
         launch_rake_columns(p, p.out_sdb == nullptr && p.out_colmean == nullptr, s);
+        if (inject_rake && (p.stages & 0x2u)) hipLaunchKernelGGL(inject_rake_kernel, dim3(g256), dim3(256), 0, s, p, inject_rake);
         if (p.stages & 0x2u) hipLaunchKernelGGL(rake_runs_kernel, dim3(g256), dim3(256), 0, s, p);
     }
 }

@@ -199,7 +199,9 @@ void launch_chunk_signal(uint32_t *flag, uint32_t gen, hipStream_t s);
 void launch_decode(const PassParams &p, const DevTables &t, hipStream_t s);
 // first_bad (device, preset to ~0): smallest index of a sample of pcm[0..n) that is NaN or infinite
 void launch_finite_check(const float *pcm, int64_t n, unsigned long long *first_bad, hipStream_t s);
-void launch_finalize_mel(const PassParams &p, const DevTables &t, hipStream_t s);
+// inject_rake (aegis_debug_set_rake_columns): flags [out_total] in output frame order that overwrite the pass's rake_raw
+// between the column kernel and the run-length filter, by a kernel of its own; NULL: the shipping launches alone
+void launch_finalize_mel(const PassParams &p, const DevTables &t, hipStream_t s, const uint8_t *inject_rake = nullptr);
 // the column flags (rake_raw) alone: rake_pow_kernel from mel power, or db_rake_kernel through every dB value (which also
 // writes the image and its column means where p asks for them); launch_finalize_mel picks by those outputs
 void launch_rake_columns(const PassParams &p, bool from_power, hipStream_t s);
