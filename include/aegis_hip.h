@@ -853,6 +853,14 @@ int64_t aegis_get_param(const aegis_handle *h, const char *name);
  * "tuning_pitch" f32 and "tuning_mag" f32 [peak_off[n_clips]] (the piptrack peaks; of clip c only the first
  * min(n_peaks[c], room) entries behind peak_off[c] mean anything, in no particular order), "tuning_median" f32[n_clips]
  * (np.median of a clip's peak magnitudes, 0 for a clip without peaks).
+ * What the most recent device pass of a render left (aegis_synth_adsr, aegis_synth_adsr_bend, aegis_synth_adsr_notes and
+ * the renders inside aegis_verify_techniques; 0 before one has run, and of a call that was cut into several passes the
+ * last group only): "synth_mix" f64[sum of the pass's clip totals] (the float64 mix in front of the master stage, clip
+ * after clip in the order of the pass, no padding), "synth_note_peak" f64[notes of the pass that reach their file] (per
+ * note in mix order the max |sum of harmonics| over ALL samples of its oscillator, what the note is divided by; a note
+ * that starts at or past the end of its file has no entry), "synth_clip_peak" f64[clips of the pass] (max |mix| of each
+ * clip, what the master stage divides by; 0.0 for a silent clip).  The fetch waits for the handle's stream and copies;
+ * it launches nothing.
  * "viterbi_stats" i64[3] (reading resets; "viterbi_stats_peek" does not): wave-steps of the band Viterbi since the last
  * reset, how many of them took the exact observed-sources-only path, and how many were voiced waves that skipped the step
  * because all their targets were dead at an easy frame (bench.py reports the ratios).

@@ -119,6 +119,11 @@ class Handle:
                               _TABLE_DTYPES.get(name, np.float64), lambda rc: AegisError(rc, f"unknown table {name}"))
 
     def debug_fetch(self, name):
+        """aegis_debug_fetch (include/aegis_hip.h lists the names): an intermediate of the most recent pass as an array of
+        its own dtype (float64 unless _DEBUG_DTYPES says otherwise).  Of the last device pass of a render (synth_adsr,
+        synth_adsr_notes, the verifier's renders), empty before one: "synth_mix" (the float64 mix in front of the master
+        stage, clip after clip in the order of the pass), "synth_note_peak" (per note that reaches its file, in mix order,
+        the peak of its oscillator), "synth_clip_peak" (per clip its max |mix|)."""
         return _marshal.sized(lambda dst, cap: self.lib.aegis_debug_fetch(self._h, name.encode(), dst, cap),
                               _DEBUG_DTYPES.get(name, np.float64), self._error)
 

@@ -621,6 +621,24 @@ int64_t aegis_debug_fetch(aegis_handle *h, const char *name, void *dst, int64_t 
         else { src = n == "tuning_pitch" ? h->tn_pitch.p : h->tn_mag.p; count = h->tn_last_peak_off.back(); }
         esz = 4;
     }
+    else if (n == "synth_mix" || n == "synth_clip_peak") {      // the last render pass (render_into): 0 before one
+        if (h->sy_last_total.empty()) return 0;
+        if (n == "synth_clip_peak") { src = h->sy_clip_peak.p; count = (int64_t)h->sy_last_total.size(); }   // the bits of a double
+        else { src = h->sy_mix.p; for (int64_t t : h->sy_last_total) count += t; }
+    }
+    else if (n == "synth_note_peak") {    // osc_peak[notes[q].osc], gathered here: which notes share an oscillator stays inside
+        count = (int64_t)h->sy_last_osc.size();
+        if (count == 0 || !dst || cap <= 0) return count;
+        int32_t n_oscs = 0;
+        for (int32_t g : h->sy_last_osc) n_oscs = std::max(n_oscs, g + 1);
+        std::vector<double> peak((size_t)n_oscs);
+        HIPCHK(h, hipSetDevice(h->device));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        HIPCHK(h, hipMemcpy(peak.data(), h->sy_osc_peak.p, (size_t)n_oscs * 8, hipMemcpyDeviceToHost));
+        double *o = static_cast<double *>(dst);
+        for (int64_t q = 0; q < std::min(count, cap); ++q) o[q] = peak[(size_t)h->sy_last_osc[(size_t)q]];
+        return count;
+    }
     else if (n == "persistent_fallbacks") {
         if (dst && cap > 0) *static_cast<int64_t *>(dst) = h->persist.fallbacks;
         return 1;

@@ -138,6 +138,10 @@ struct aegis_handle {
     DevBuf pcm_raw, pcm_clips, pcm_ranges, pcm_taps;   // aegis_analyze_pcm: raw bytes, clip table, per-chunk range tables, filters
     DevBuf sy_oscs, sy_notes, sy_tiles, sy_tile_notes, sy_osc_peak, sy_clip_peak, sy_mix, sy_out;   // aegis_synth_adsr / aegis_synth_adsr_notes: records, peaks, float64 mix, int16 result
     DevBuf sy_bends, sy_segs;                 // aegis_synth_adsr_bend: per-oscillator slices and the segment tables of the bent notes
+    // the layout of the most recent render_into that launched (aegis_debug_fetch "synth_*"); all empty before one, and after
+    // one that failed: per clip its samples (back to back in sy_mix), per note of the mix its oscillator's index
+    std::vector<int64_t> sy_last_total;
+    std::vector<int32_t> sy_last_osc;
     DevBuf fx_a, fx_b, fx_recs, fx_tiles, fx_peak, fx_taps, fx_i16;   // aegis_effects: the two float64 batch buffers, records, clip maxima, taps, int16 in / out
     // aegis_note_fit / aegis_compare_audio / aegis_synth_one_note: slices, records, per-frame features, scores; stored note
     DevBuf nf_audio, nf_oscs, nf_cands, nf_notes, nf_boff, nf_peak, nf_cnum, nf_cden, nf_zc, nf_rms, nf_out, nf_best;

@@ -86,8 +86,11 @@ int check_note(aegis_handle *h, int32_t sr, int32_t c, int64_t k, const aegis_sy
 // sy_out + B.clip_off[c] once the stream has run; nothing is copied out and nothing is waited for: B lives in front of
 // the caller's scope.
 // labels: the profiling names of the three kernels.
+// The handle remembers the layout of the pass (sy_last_*) once everything is launched: aegis_debug_fetch "synth_mix" /
+// "synth_note_peak" / "synth_clip_peak" read the float64 mix and the peaks where the kernels left them.
 int aegis::render_into(aegis_handle *h, const AdsrBatch &B, const char *const (&labels)[3]) {
     if (B.samples == 0) return AEGIS_OK;
+    h->sy_last_total.clear(); h->sy_last_osc.clear();
     hipStream_t s = h->stream;
     const size_t nc = B.clip_off.size();
     ENSURE(h, sy_oscs, B.oscs.size() * sizeof(AdsrOsc)); ENSURE(h, sy_notes, B.notes.size() * sizeof(AdsrNote));
@@ -125,6 +128,9 @@ int aegis::render_into(aegis_handle *h, const AdsrBatch &B, const char *const (&
     launch_adsr_master(d_tiles, d_mix, d_cpeak, d_out, (int32_t)B.tiles.size(), s);
     end_event(h, s);
     HIPCHK(h, hipGetLastError());
+    h->sy_last_total = B.clip_total;
+    h->sy_last_osc.reserve(B.notes.size());
+    for (const AdsrNote &nt : B.notes) h->sy_last_osc.push_back(nt.osc);
     return AEGIS_OK;
 }
 

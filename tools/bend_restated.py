@@ -168,7 +168,13 @@ def wave(x, waveform, sin=np.sin):
     raise ValueError(f"unknown waveform {waveform}")
 
 
-def cycles(segs, n, step):
+def cycle_count(C, g, t, T):
+    """c = C_k + g_k * (t - T_k): the difference, the product and the sum each round (synth_restated states why this
+    stands alone)."""
+    return C + g * (t - T)
+
+
+def cycles(segs, n, step, sr=None):
     """c of every sample of a bent note (float64 [n])."""
     T = np.array([s[0] for s in segs])
     C = np.array([s[1] for s in segs])
@@ -176,76 +182,73 @@ def cycles(segs, n, step):
     s = np.array([s[3] for s in segs], dtype=np.int64)
     i = np.arange(n, dtype=np.int64)
     k = np.searchsorted(s, i, side="right") - 1            # the last segment with s_k <= i
-    t = i.astype(np.float64) * step
-    return C[k] + g[k] * (t - T[k])
+    t = R.sample_times(sr, n, step)
+    return cycle_count(C[k], g[k], t, T[k])
+
+
+def harmonics_kept(sr, freq, r_max):
+    """How many harmonics a bent note sums: h >= 2 while (freq * h) * r_max < sr / 2, stopping at the first failure."""
+    kept = 1
+    for h in (2, 3, 4, 5):
+        if not R.harmonic_kept((freq * h) * r_max, sr):
+            break
+        kept = h
+    return kept
 
 
 def bent_harmonics(sr, freq, segs, r_max, n, step, waveform, sin=np.sin):
     """The summed harmonics of a bent note before peak normalisation (float64 [n]).  sin: np.sin, or libm_sin to compare
     with a host program bit for bit."""
-    c = cycles(segs, n, step)
-    sig = wave(c, waveform, sin)
-    for h in (2, 3, 4, 5):
-        if not (freq * h) * r_max < sr / 2:
-            break
-        sig = sig + R.HARMONIC_AMPS[h - 1] * wave(float(h) * c, waveform, sin)
-    return sig
+    c = cycles(segs, n, step, sr)
+    terms = [wave(c, waveform, sin)]
+    for h in range(2, harmonics_kept(sr, freq, r_max) + 1):
+        terms.append(R.HARMONIC_AMPS[h - 1] * wave(float(h) * c, waveform, sin))
+    return R.sum_harmonics(terms)
 
 
 def unbent_harmonics(sr, freq, n, step, waveform, sin=np.sin):
-    """synth_restated.note_signal's summed harmonics before peak normalisation (what an unbent note keeps); sin as in
+    """synth_restated.harmonics: the summed harmonics of an unbent note before peak normalisation; sin as in
     bent_harmonics."""
-    t = np.arange(n, dtype=np.float64) * step
-
-    def osc(f):
-        if waveform in ("sine", "square"):                   # synth_restated.oscillator with the sin given
-            v = sin(((2 * np.pi) * f) * t)
-            return v if waveform == "sine" else np.sign(v)
-        return R.oscillator(f, t, waveform)
-    sig = osc(freq)
-    for h in (2, 3, 4, 5):
-        if freq * h < sr / 2:
-            sig = sig + R.HARMONIC_AMPS[h - 1] * osc(freq * h)
-    return sig
+    return R.harmonics(sr, freq, n, step, waveform, sin)
 
 
-def note_signal(sr, start, note, duration, velocity, events, bend_range, attack_ms, decay_ms, sustain_level, release_ms, waveform):
-    freq = 440.0 * (2.0 ** ((note - 69) / 12.0))
+def note_spec(sr, start, note, duration, velocity, events, bend_range, attack_ms, decay_ms, sustain_level, release_ms, waveform):
+    """The synth_restated.NoteSpec of a note under the wheel events of its track."""
+    freq = R.midi_freq(note)
     full = duration + release_ms / 1000.0
     n = int(sr * full)
     segs, r_max = segments(freq, start, full, full / n, events, bend_range)
+    env = (attack_ms, decay_ms, sustain_level, release_ms)
     if segs is None:
-        return R.note_signal(sr, note, duration, velocity, attack_ms, decay_ms, sustain_level, release_ms, waveform)
-    sig = bent_harmonics(sr, freq, segs, r_max, n, full / n, waveform)
-    peak = np.max(np.abs(sig))
-    if peak > 0:
-        sig = sig / peak
-    sig = sig * R.envelope(sr, n, attack_ms, decay_ms, sustain_level, release_ms)
-    return sig * max(0.0, min(1.0, velocity / 127.0))
+        return R.NoteSpec(int(start * sr), n, velocity, env, R.harmonics_kept(sr, freq),
+                          lambda sin: R.harmonics(sr, freq, n, full / n, waveform, sin))
+    return R.NoteSpec(int(start * sr), n, velocity, env, harmonics_kept(sr, freq, r_max),
+                      lambda sin: bent_harmonics(sr, freq, segs, r_max, n, full / n, waveform, sin))
+
+
+def note_signal(sr, start, note, duration, velocity, events, bend_range, attack_ms, decay_ms, sustain_level, release_ms, waveform,
+                sin=np.sin):
+    sp = note_spec(sr, start, note, duration, velocity, events, bend_range, attack_ms, decay_ms, sustain_level, release_ms, waveform)
+    return R.shaped_note(sp.harmonics(sin), sr, velocity, *sp.env)[0]
+
+
+def mix_notes(notes, length, note_track, wheel, sr, bend_range=2.0, attack_ms=10, decay_ms=50, sustain_level=0.7,
+              release_ms=100, waveform="sawtooth", sin=np.sin, each=None):
+    """synth_restated.mix_notes with the wheel of each note's track -> (mixed, note_peaks, clip_peak)."""
+    by_track = {}
+    for time, track, v in wheel:
+        by_track.setdefault(track, []).append((time, v))
+    specs = [note_spec(sr, start, note, duration, vel, by_track.get(track, []), bend_range, attack_ms, decay_ms, sustain_level,
+                       release_ms, waveform) for (start, duration, note, vel), track in zip(notes, note_track)]
+    return R.mix_specs(R.total_samples(sr, length, release_ms), sr, specs, sin, each)
 
 
 def render_notes(notes, length, note_track, wheel, sr, bend_range=2.0, attack_ms=10, decay_ms=50, sustain_level=0.7,
                  release_ms=100, waveform="sawtooth"):
     """synth_restated.render_notes with the wheel of each note's track."""
-    by_track = {}
-    for time, track, v in wheel:
-        by_track.setdefault(track, []).append((time, v))
-    total = R.total_samples(sr, length, release_ms)
-    mixed = np.zeros(total)
-    for (start, duration, note, vel), track in zip(notes, note_track):
-        sig = note_signal(sr, start, note, duration, vel, by_track.get(track, []), bend_range, attack_ms, decay_ms, sustain_level,
-                          release_ms, waveform)
-        a = int(start * sr)
-        b = a + len(sig)
-        if b > total:
-            sig = sig[:max(total - a, 0)]
-            b = total
-        if a < total:
-            mixed[a:b] += sig
-    peak = np.max(np.abs(mixed)) if total else 0.0
-    if peak > 0:
-        mixed = mixed / peak * 0.9
-    return np.clip(mixed * 32767, -32768, 32767).astype(np.int16)
+    mixed, _, peak = mix_notes(notes, length, note_track, wheel, sr, bend_range, attack_ms, decay_ms, sustain_level, release_ms,
+                               waveform)
+    return R.to_int16(mixed, peak)
 
 
 def render(blob, sr, bend_range=2.0, **params):

@@ -132,19 +132,13 @@ def slice_audio_for_note(audio_data, sr, start_time, end_time, padding_ms=50):
 
 
 def synthesize_note(sr, freq, duration, velocity=100, attack_ms=10, decay_ms=50, sustain_level=0.7, release_ms=100,
-                    waveform="sawtooth"):
+                    waveform="sawtooth", sin=np.sin):
     """ADSRSynthesizer.synthesize_note with harmonics=True (synthesizer.py:316-374); `duration` is the full duration."""
     n = int(sr * duration)
-    t = np.arange(n, dtype=np.float64) * (duration / n) if n else np.zeros(0)
-    sig = R.oscillator(freq, t, waveform)
-    for h in (2, 3, 4, 5):
-        if freq * h < sr / 2:
-            sig = sig + R.HARMONIC_AMPS[h - 1] * R.oscillator(freq * h, t, waveform)
-    peak = np.max(np.abs(sig))
-    if peak > 0:
-        sig = sig / peak
-    sig = sig * R.envelope(sr, n, attack_ms, decay_ms, sustain_level, release_ms)
-    return sig * max(0.0, min(1.0, velocity / 127.0))
+    sig = R.harmonics(sr, freq, n, duration / n, waveform, sin) if n else np.zeros(0)
+    if not n:
+        np.max(sig)                                          # the reference raises here
+    return R.shaped_note(sig, sr, velocity, attack_ms, decay_ms, sustain_level, release_ms)[0]
 
 
 def note_times(event, sr, hop_length=512):
@@ -204,12 +198,49 @@ def optimize_single_note(event, audio, sr=44100, quick_mode=True, analyze=None, 
     return best
 
 
+def notes_total(end_time, params, sr):
+    """Samples of a per-note render whose latest note ends at end_time seconds."""
+    max_release = max((p.get("release_ms", 100.0) for p in params), default=100.0)
+    return int(sr * (end_time + max_release / 1000.0 + 0.5))
+
+
 def per_note_total_samples(events, params, sr, hop_length=512):
     max_end = 0.0
     for e in events:
         max_end = max(max_end, e["end"] * hop_length / sr)
-    max_release = max((p.get("release_ms", 100.0) for p in params), default=100.0)
-    return int(sr * (max_end + max_release / 1000.0 + 0.5))
+    return notes_total(max_end, params, sr)
+
+
+def per_note_specs(notes, params, sr):
+    """The synth_restated.NoteSpecs of notes (start, duration, midi, velocity; seconds) that each carry their own envelope
+    and waveform (a dict as the optimiser returns it, defaults as synthesize_with_per_note_params takes them)."""
+    specs = []
+    for (start, duration, note, vel), p in zip(notes, params):
+        freq = 440.0 * (2.0 ** ((note - 69) / 12.0))
+        release_ms = p.get("release_ms", 100.0)
+        full = duration + release_ms / 1000.0
+        n = int(sr * full)
+        wf = p.get("waveform", "sawtooth")
+        specs.append(R.NoteSpec(int(start * sr), n, vel,
+                                (p.get("attack_ms", 10.0), p.get("decay_ms", 50.0), p.get("sustain_level", 0.7), release_ms),
+                                R.harmonics_kept(sr, freq),
+                                lambda sin, freq=freq, n=n, full=full, wf=wf: R.harmonics(sr, freq, n, full / n, wf, sin)))
+    return specs
+
+
+def mix_per_note(notes, end_time, params, sr, sin=np.sin, each=None):
+    """(mixed, note_peaks, clip_peak) in front of the master stage of the per-note render, from notes in seconds and the
+    latest note end: what aegis_debug_fetch "synth_mix" / "synth_note_peak" / "synth_clip_peak" hold after
+    aegis_synth_adsr_notes."""
+    return R.mix_specs(notes_total(end_time, params, sr), sr, per_note_specs(notes, params, sr), sin, each)
+
+
+def mix_with_per_note_params(events, params, sr=44100, sin=np.sin, each=None):
+    """mix_per_note of events in frames of 512 samples, as synthesize_with_per_note_params reads them."""
+    if len(events) != len(params):
+        raise ValueError("events and optimized_params differ in length")
+    notes = [(note_times(e, sr)[0], note_times(e, sr)[2], e.get("note", 60), e.get("velocity", 100)) for e in events]
+    return mix_per_note(notes, max((e["end"] * 512 / sr for e in events), default=0.0), params, sr, sin, each)
 
 
 def synthesize_with_per_note_params(events, params, sr=44100):
@@ -218,22 +249,5 @@ def synthesize_with_per_note_params(events, params, sr=44100):
         raise ValueError("events and optimized_params differ in length")
     if not events:
         return np.zeros(sr, dtype=np.int16)
-    total = per_note_total_samples(events, params, sr)
-    mixed = np.zeros(total, dtype=np.float64)
-    for e, p in zip(events, params):
-        start, _, duration = note_times(e, sr)
-        freq = 440.0 * (2.0 ** ((e.get("note", 60) - 69) / 12.0))
-        release_ms = p.get("release_ms", 100.0)
-        sig = synthesize_note(sr, freq, duration + release_ms / 1000.0, e.get("velocity", 100), p.get("attack_ms", 10.0),
-                              p.get("decay_ms", 50.0), p.get("sustain_level", 0.7), release_ms, p.get("waveform", "sawtooth"))
-        a = int(start * sr)
-        b = a + len(sig)
-        if b > total:
-            sig = sig[:max(total - a, 0)]
-            b = total
-        if 0 <= a < total:
-            mixed[a:b] += sig
-    peak = np.max(np.abs(mixed)) if total else 0.0
-    if peak > 0:
-        mixed = mixed / peak * 0.9
-    return np.clip(mixed * 32767, -32768, 32767).astype(np.int16)
+    mixed, _, peak = mix_with_per_note_params(events, params, sr)
+    return R.to_int16(mixed, peak)

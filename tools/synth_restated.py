@@ -175,11 +175,12 @@ def total_samples(sr, length, release_ms):
     return int(sr * secs)
 
 
-def oscillator(freq, t, waveform):
+def oscillator(freq, t, waveform, sin=np.sin):
+    """sin: the sine in use, float64 -> float64 (np.sin; bend_restated.libm_sin; synth_cases.long_sin for the sine truth)."""
     if waveform == "sine":
-        return np.sin(((2 * np.pi) * freq) * t)
+        return sin(((2 * np.pi) * freq) * t)
     if waveform == "square":
-        return np.sign(np.sin(((2 * np.pi) * freq) * t))
+        return np.sign(sin(((2 * np.pi) * freq) * t))
     x = freq * t
     phase = x - np.floor(x)
     if waveform == "sawtooth":
@@ -187,6 +188,48 @@ def oscillator(freq, t, waveform):
     if waveform == "triangle":
         return 2.0 * np.abs(2.0 * phase - 1.0) - 1.0
     raise ValueError(f"unknown waveform {waveform}")
+
+
+# ---- the choices of the arithmetic, one small function each --------------------------------------------------------------
+# Every float64 operation below is the device's (csrc/adsr.h) in the reference's order.  Where an implementation could
+# choose otherwise and still pass a 16-bit comparison, the choice stands in a function of its own, so that
+# tests/test_synth_cases.py can replace one at a time and show that a case of tools/synth_cases.py notices.
+def sample_times(sr, n, step):
+    """t of every sample: i * step with step = full / n (np.linspace(0, full, n, endpoint=False)), never i / sr."""
+    return np.arange(n, dtype=np.float64) * step
+
+
+def harmonic_kept(f, sr):
+    """Harmonic h >= 2 of frequency f sounds while f < sr / 2, strictly."""
+    return f < sr / 2
+
+
+def sum_harmonics(terms):
+    """((s1 + .5 s2) + .25 s3) + ..., left to right."""
+    sig = terms[0]
+    for x in terms[1:]:
+        sig = sig + x
+    return sig
+
+
+def note_peak(sig, n_cut):
+    """max |harmonics| over ALL samples of the note, not the n_cut of them that reach the file: the reference normalises a
+    note before it truncates it."""
+    return np.max(np.abs(sig))
+
+
+def decay_ramp(i, step):
+    """Two roundings: the product, then the sum."""
+    return i * step + 1.0
+
+
+def release_ramp(j, step, sustain):
+    return j * step + sustain
+
+
+def close_release(env, at):
+    """The last sample of a release of two samples or more is 0.0, whatever the ramp gives there."""
+    env[at] = 0.0
 
 
 def envelope(sr, n, attack_ms, decay_ms, sustain_level, release_ms):
@@ -203,51 +246,112 @@ def envelope(sr, n, attack_ms, decay_ms, sustain_level, release_ms):
         env[m] = i[m] * (1.0 / a)
     if d > 0:
         m = (k >= a) & (k < a + d)
-        env[m] = (i[m] - a) * ((S - 1.0) / d) + 1.0
+        env[m] = decay_ramp(i[m] - a, (S - 1.0) / d)
     m = (k >= a + d) & (k < a + d + s)
     env[m] = S
     if r > 0:
         m = (k >= a + d + s) & (k < a + d + s + r)
         j = i[m] - (a + d + s)
-        env[m] = (j * ((0.0 - S) / (r - 1)) + S) if r > 1 else S
+        env[m] = release_ramp(j, (0.0 - S) / (r - 1), S) if r > 1 else S
         if r > 1 and a + d + s + r - 1 < n:
-            env[a + d + s + r - 1] = 0.0
+            close_release(env, a + d + s + r - 1)
     return env
 
 
-def note_signal(sr, note, duration, velocity, attack_ms, decay_ms, sustain_level, release_ms, waveform):
-    freq = 440.0 * (2.0 ** ((note - 69) / 12.0))
-    full = duration + release_ms / 1000.0
-    n = int(sr * full)
-    t = np.arange(n, dtype=np.float64) * (full / n)
-    sig = oscillator(freq, t, waveform)
+def harmonics(sr, freq, n, step, waveform, sin=np.sin):
+    """The summed harmonics of an unbent note before peak normalisation (float64 [n])."""
+    t = sample_times(sr, n, step)
+    terms = [oscillator(freq, t, waveform, sin)]
     for h in (2, 3, 4, 5):
-        if freq * h < sr / 2:
-            sig = sig + HARMONIC_AMPS[h - 1] * oscillator(freq * h, t, waveform)
-    peak = np.max(np.abs(sig))
+        if harmonic_kept(freq * h, sr):
+            terms.append(HARMONIC_AMPS[h - 1] * oscillator(freq * h, t, waveform, sin))
+    return sum_harmonics(terms)
+
+
+def harmonics_kept(sr, freq):
+    """How many harmonics `harmonics` sums, the fundamental included."""
+    return 1 + sum(1 for h in (2, 3, 4, 5) if harmonic_kept(freq * h, sr))
+
+
+def shaped_note(sig, sr, velocity, attack_ms, decay_ms, sustain_level, release_ms, n_cut=None):
+    """Summed harmonics -> (the note's samples, its peak): / peak, * envelope, * velocity.  n_cut: how many of the samples
+    reach the file (all of them when None); the peak does not depend on it."""
+    peak = note_peak(sig, len(sig) if n_cut is None else n_cut)
     if peak > 0:
         sig = sig / peak
-    sig = sig * envelope(sr, n, attack_ms, decay_ms, sustain_level, release_ms)
-    return sig * max(0.0, min(1.0, velocity / 127.0))
+    sig = sig * envelope(sr, len(sig), attack_ms, decay_ms, sustain_level, release_ms)
+    return sig * max(0.0, min(1.0, velocity / 127.0)), float(peak)
+
+
+def midi_freq(note):
+    return 440.0 * (2.0 ** ((note - 69) / 12.0))
+
+
+def note_signal(sr, note, duration, velocity, attack_ms, decay_ms, sustain_level, release_ms, waveform, sin=np.sin):
+    full = duration + release_ms / 1000.0
+    n = int(sr * full)
+    sig = harmonics(sr, midi_freq(note), n, full / n, waveform, sin)
+    return shaped_note(sig, sr, velocity, attack_ms, decay_ms, sustain_level, release_ms)[0]
+
+
+class NoteSpec:
+    """One note of a mix as every render entry sees it: its first output sample, its samples, its velocity, its envelope
+    (attack_ms, decay_ms, sustain_level, release_ms), how many harmonics it sums and the function sin -> their sum."""
+    def __init__(self, start, n, velocity, env, n_harm, harmonics):
+        self.start, self.n, self.velocity, self.env, self.n_harm, self.harmonics = start, n, velocity, tuple(env), n_harm, harmonics
+
+
+def mix_specs(total, sr, specs, sin=np.sin, each=None):
+    """The float64 mix of one file in front of the master stage -> (mixed [total], note_peaks, clip_peak).  `mixed[a:b] +=
+    note` in the order of `specs`; note_peaks holds one value per note that reaches the file (a note that starts at or
+    past its end leaves nothing, on the device neither), in that order; clip_peak = max |mixed| (0.0 for an empty file).
+    each(spec, samples, peak): called per note that reaches the file with the samples that were added."""
+    mixed = np.zeros(total)
+    peaks = []
+    for sp in specs:
+        a = sp.start
+        if not a < total:
+            continue
+        sig, peak = shaped_note(sp.harmonics(sin), sr, sp.velocity, *sp.env, n_cut=min(sp.n, total - a))
+        sig = sig[:total - a]
+        mixed[a:a + len(sig)] += sig
+        peaks.append(peak)
+        if each is not None:
+            each(sp, sig, peak)
+    clip_peak = float(np.max(np.abs(mixed))) if total else 0.0
+    return mixed, np.array(peaks, dtype=np.float64), clip_peak
+
+
+def to_int16(mixed, peak):
+    """The master stage alone: / peak * 0.9 (a silent file stays as it is), * 32767, clip, truncate toward zero."""
+    if peak > 0:
+        mixed = mixed / peak * 0.9
+    return np.clip(mixed * 32767, -32768, 32767).astype(np.int16)
+
+
+def note_specs(notes, sr, attack_ms, decay_ms, sustain_level, release_ms, waveform):
+    """The NoteSpecs of closed notes (start, duration, note, velocity) under one envelope."""
+    specs = []
+    for start, duration, note, vel in notes:
+        freq, full = midi_freq(note), duration + release_ms / 1000.0
+        n = int(sr * full)
+        specs.append(NoteSpec(int(start * sr), n, vel, (attack_ms, decay_ms, sustain_level, release_ms), harmonics_kept(sr, freq),
+                              lambda sin, freq=freq, n=n, full=full: harmonics(sr, freq, n, full / n, waveform, sin)))
+    return specs
+
+
+def mix_notes(notes, length, sr, attack_ms=10, decay_ms=50, sustain_level=0.7, release_ms=100, waveform="sawtooth", sin=np.sin,
+              each=None):
+    """(mixed, note_peaks, clip_peak) of one file from its closed notes and length: what aegis_debug_fetch "synth_mix" /
+    "synth_note_peak" / "synth_clip_peak" hold after aegis_synth_adsr."""
+    total = total_samples(sr, length, release_ms)
+    return mix_specs(total, sr, note_specs(notes, sr, attack_ms, decay_ms, sustain_level, release_ms, waveform), sin, each)
 
 
 def render_notes(notes, length, sr, attack_ms=10, decay_ms=50, sustain_level=0.7, release_ms=100, waveform="sawtooth"):
     """The int16 samples of one file from its closed notes and length."""
-    total = total_samples(sr, length, release_ms)
-    mixed = np.zeros(total)
-    for start, duration, note, vel in notes:
-        sig = note_signal(sr, note, duration, vel, attack_ms, decay_ms, sustain_level, release_ms, waveform)
-        a = int(start * sr)
-        b = a + len(sig)
-        if b > total:
-            sig = sig[:max(total - a, 0)]
-            b = total
-        if a < total:
-            mixed[a:b] += sig
-    peak = np.max(np.abs(mixed)) if total else 0.0
-    if peak > 0:
-        mixed = mixed / peak * 0.9
-    return np.clip(mixed * 32767, -32768, 32767).astype(np.int16)
+    mixed, _, peak = mix_notes(notes, length, sr, attack_ms, decay_ms, sustain_level, release_ms, waveform)
+    return to_int16(mixed, peak)
 
 
 def render(blob, sr, **params):
