@@ -301,8 +301,7 @@ static int upload_pass(aegis_handle *h, aegis_handle::Work &w, const PassPlan &m
     }
     if (m.persistent) {
         if (!h->abort_flag.p) {
-            int rc;
-            if ((rc = ensure(h, h->abort_flag, 4)) != AEGIS_OK) return rc;
+            ENSURE(h, abort_flag, 4);
             HIPCHK(h, hipMemsetAsync(h->abort_flag.p, 0, 4, fa));
         }
         HIPCHK(h, up(w.chunk_lo, m.chunk_lo));
@@ -528,11 +527,11 @@ static int analyze_device_locked(aegis_handle *h, const float *d_pcm, const int6
         // A time-split launch (a plain split pass's, a hybrid pass's): an automatic call is timed from its first one to its
         // last one (split_ev), and each leaves a verdict that split_check reads once the pass is done.
         auto launch_split = [&](const PassParams &q, int n_spec, hipStream_t sq, hipStream_t aux) -> int {
-            begin_event(h, "viterbi", sq);
-            if (m.split_auto && !split_started) { HIPCHK(h, hipEventRecord(h->split_ev[0], sq)); split_started = true; }
-            const hipError_t ve = launch_viterbi_split(q, h->dt, t.log_trans_band.data(), d_seg_order, n_spec, d_lock_order, m.n_lock, sq, aux, h->fin_ev);
-            if (m.split_auto) HIPCHK(h, hipEventRecord(h->split_ev[1], sq));
-            end_event(h, sq);
+            hipError_t ve = hipSuccess;
+            TIMED(h, "viterbi", sq,
+                  if (m.split_auto && !split_started) { HIPCHK(h, hipEventRecord(h->split_ev[0], sq)); split_started = true; }
+                  ve = launch_viterbi_split(q, h->dt, t.log_trans_band.data(), d_seg_order, n_spec, d_lock_order, m.n_lock, sq, aux, h->fin_ev);
+                  if (m.split_auto) HIPCHK(h, hipEventRecord(h->split_ev[1], sq)));
             VCHK(ve);
             h->tsplit.checks.push_back({pi, q});
             ++h->tsplit.stats[0]; h->tsplit.stats[1] += m.n_seg;
@@ -576,14 +575,11 @@ static int analyze_device_locked(aegis_handle *h, const float *d_pcm, const int6
                     HIPCHK(h, hipStreamWaitEvent(fs, h->copy_event, 0));
                 }
             }
-            begin_event(h, "frame", fs);
-            launch_frame(p, h->dt, fs, h->inject_d.armed ? static_cast<const double *>(h->inject_d.d.p) : nullptr);
-            end_event(h, fs);
+            TIMED(h, "frame", fs, launch_frame(p, h->dt, fs, h->inject_d.armed ? static_cast<const double *>(h->inject_d.d.p) : nullptr));
             if (!py) continue;
-            begin_event(h, "pyin_obs", fs);
-            if (h->inject.armed) launch_inject_obs(p, static_cast<const double *>(h->inject.obs.p), static_cast<const double *>(h->inject.unv.p), fs);
-            else launch_pyin_obs(p, h->dt, fs);
-            end_event(h, fs);
+            TIMED(h, "pyin_obs", fs,
+                  if (h->inject.armed) launch_inject_obs(p, static_cast<const double *>(h->inject.obs.p), static_cast<const double *>(h->inject.unv.p), fs);
+                  else launch_pyin_obs(p, h->dt, fs));
             if (m.persistent) {
                 if (k != h->test_drop_signal)      // AEGIS_TEST_DROP_CHUNK_SIGNAL=k: the kernel's bounded wait is tested with it
                     launch_chunk_signal(static_cast<uint32_t *>(w.chunk_flag.p) + k, p.chunk_gen, fs);
@@ -592,9 +588,8 @@ static int analyze_device_locked(aegis_handle *h, const float *d_pcm, const int6
                     HIPCHK(h, hipStreamWaitEvent(sv, h->sync_events[EV_CHUNK0], 0));
                     PassParams pv = p;
                     pv.vt_begin = 0; pv.vt_end = m.hybrid ? m.hyb_S + 1 : INT64_MAX;
-                    begin_event(h, "viterbi", sv);
-                    hipError_t ve = launch_viterbi(pv, h->dt, t.log_trans_band.data(), sv);
-                    end_event(h, sv);
+                    hipError_t ve = hipSuccess;
+                    TIMED(h, "viterbi", sv, ve = launch_viterbi(pv, h->dt, t.log_trans_band.data(), sv));
                     VCHK(ve);
                 }
                 continue;
@@ -609,9 +604,8 @@ static int analyze_device_locked(aegis_handle *h, const float *d_pcm, const int6
                 if ((rc = launch_split(p, m.n_seg, sv, h->stream4 != sv ? h->stream4 : nullptr)) != AEGIS_OK) return rc;
                 continue;
             }
-            begin_event(h, "viterbi", sv);
-            hipError_t ve = launch_viterbi(p, h->dt, t.log_trans_band.data(), sv);
-            end_event(h, sv);
+            hipError_t ve = hipSuccess;
+            TIMED(h, "viterbi", sv, ve = launch_viterbi(p, h->dt, t.log_trans_band.data(), sv));
             VCHK(ve);
         }
         if (m.use_fb) {                    // the dB / rake finalisation needs every chunk's mel rows and clip maxima
@@ -641,10 +635,8 @@ static int analyze_device_locked(aegis_handle *h, const float *d_pcm, const int6
         }
         // ---- finalize ---------------------------------------------------------------------------------------------------
         hipStream_t se = m.hybrid ? sd : sv;       // the stream the pass ends on
-        begin_event(h, "finalize", fa);
-        launch_finalize_mel(p, h->dt, fa, h->inject_r.armed ? h->inject_r.flags.as<const uint8_t>() : nullptr);
-        end_event(h, fa);
-        if (py) { begin_event(h, "finalize", se); launch_decode(p, h->dt, se); end_event(h, se); }
+        TIMED(h, "finalize", fa, launch_finalize_mel(p, h->dt, fa, h->inject_r.armed ? h->inject_r.flags.as<const uint8_t>() : nullptr));
+        if (py) TIMED(h, "finalize", se, launch_decode(p, h->dt, se));
         // pass done = its last kernels on the frame stream and on the Viterbi stream
         if (se != fa) {
             HIPCHK(h, hipEventRecord(h->sync_events[EV_FA], fa));
@@ -664,8 +656,7 @@ static int analyze_device_locked(aegis_handle *h, const float *d_pcm, const int6
     for (int q = 0; q < 2; ++q)
         if (done_recorded[q]) HIPCHK(h, hipStreamWaitEvent(s, h->sync_events[EV_DONE0 + q], 0));
     if (opts & AEGIS_OPT_CHECK_FINITE) {       // behind the last sample copy of a host feed: every sample is on the device by now
-        int rc;
-        if ((rc = ensure(h, h->finite_flag, 8)) != AEGIS_OK) return rc;
+        ENSURE(h, finite_flag, 8);
         HIPCHK(h, hipMemsetAsync(h->finite_flag.p, 0xff, 8, s));
         const int64_t lo = sample_offsets[0], hi = sample_offsets[n_clips];
         launch_finite_check(d_pcm + lo, hi - lo, static_cast<unsigned long long *>(h->finite_flag.p), s);
@@ -719,7 +710,8 @@ static int run_with_recovery(aegis_handle *h, const std::function<int()> &attemp
 }
 
 // aegis_debug_set_observations, aegis_debug_set_difference and aegis_debug_set_rake_columns arm ONE analyze call: every analyze entry holds one of these from its first line on, so
-// the handle is disarmed when the entry returns, whatever it returns (declared before the entry's lock: it runs after it)
+// the handle is disarmed when the entry returns, whatever it returns (declared in front of the entry's frame, behind a null
+// check of its own: it runs after the frame has released the lock, and takes it again)
 struct DisarmInjection {
     aegis_handle *h;
     ~DisarmInjection() { std::lock_guard<std::mutex> lock(h->mu); h->inject.armed = false; h->inject_d.armed = false; h->inject_r.armed = false; }
@@ -728,13 +720,12 @@ struct DisarmInjection {
 int aegis_analyze_batch_device(aegis_handle *h, const float *d_pcm, const int64_t *sample_offsets,
                                int32_t n_clips, double rake_sensitivity, uint32_t stages,
                                aegis_outputs *dout, void *stream_v, int32_t sync) {
-    try {
     if (!h) return AEGIS_ERR_INVALID;
     DisarmInjection disarm{h};
-    std::lock_guard<std::mutex> lock(h->mu);
+    ENTRY(h)
     // (sync = 1: analyze_device_locked synchronises and reads the abort flag itself)
     return run_with_recovery(h, [&] { return analyze_device_locked(h, d_pcm, sample_offsets, n_clips, rake_sensitivity, stages, dout, stream_v, sync); });
-    } catch (...) { return abi_fail(h); }
+    ENTRY_END(h)
 }
 
 // The device half of a host-fed analysis (handle locked, io_pcm sized): the staging buffer of every output `want` names is
@@ -742,13 +733,13 @@ int aegis_analyze_batch_device(aegis_handle *h, const float *d_pcm, const int64_
 // stream.  Not synchronised, unless the single Viterbi launch had to be checked.
 static int host_fed_run_locked(aegis_handle *h, const std::vector<int64_t> &off, int64_t F, int32_t n_clips, double rake_sensitivity,
                                uint32_t stages, const aegis_outputs *want, aegis_outputs &d, const std::function<HostFeed()> &make_feed) {
-    int rc;
     hipStream_t s = h->stream;
     // the previous call's kernels may still read io_pcm only if it returned without a sync -- it never does
     const int nm = h->tab.n_mels;
     for (const OutField &f : kOutFields) {
         if (!(stages & f.stage) || !f.get(want)) continue;
-        if ((rc = ensure(h, h->*f.io, f.size(F, nm))) != AEGIS_OK) return rc;
+        const int rc = ensure(h, h->*f.io, f.size(F, nm));      // (a member pointer: not ENSURE's h->buf)
+        if (rc != AEGIS_OK) return rc;
         f.set(&d, (h->*f.io).p);
     }
     // stream_v = NULL (the handle's own stream) and sync = 2: the schedule the device-pointer entry takes with
@@ -792,8 +783,7 @@ int aegis::mel_host_locked(aegis_handle *h, const float *const *pcm, const int64
         off[(size_t)i + 1] = off[(size_t)i] + n_samples[i];
         foff[(size_t)i + 1] = foff[(size_t)i] + 1 + n_samples[i] / h->tab.hop;
     }
-    int rc;
-    if ((rc = ensure(h, h->io_pcm, (size_t)std::max<int64_t>(off[(size_t)n_clips], 1) * 4)) != AEGIS_OK) return rc;
+    ENSURE(h, io_pcm, off[(size_t)n_clips] * 4);
     aegis_outputs want{}, d{};
     want.S_dB = reinterpret_cast<float *>(h);          // any non-NULL value: the dB image is the one output wanted
     return host_fed_run_locked(h, off, foff[(size_t)n_clips], n_clips, 0.6, AEGIS_STAGE_MEL, &want, d, [&]() {
@@ -804,29 +794,24 @@ extern "C" {
 
 int aegis_analyze_batch(aegis_handle *h, const float *const *pcm, const int64_t *n_samples, int32_t n_clips,
                         double rake_sensitivity, uint32_t stages, aegis_outputs *out) {
-    try {
     if (!h) return AEGIS_ERR_INVALID;
     DisarmInjection disarm{h};
+    ENTRY(h)
     if (n_clips < 0 || (n_clips > 0 && (!pcm || !n_samples || !out))) { h->err = "null argument"; return AEGIS_ERR_INVALID; }
     if (n_clips == 0) return AEGIS_OK;
     if (stages & AEGIS_STAGE_RAKE) stages |= AEGIS_STAGE_MEL;
     DEVICE_ONLY(h);
-    std::lock_guard<std::mutex> lock(h->mu);
     HIPCHK(h, hipSetDevice(h->device));
-    std::vector<int64_t> off(n_clips + 1, 0);
+    std::vector<int64_t> off;
+    const int rc = clip_samples(h, "", pcm, n_samples, 0, n_clips, off);
+    if (rc != AEGIS_OK) return rc;
     int64_t F = 0;
-    for (int i = 0; i < n_clips; ++i) {
-        if (n_samples[i] < 0 || (n_samples[i] > 0 && !pcm[i])) { h->err = "bad clip " + std::to_string(i); return AEGIS_ERR_INVALID; }
-        // keep every clip 16-byte aligned in the packed device buffer
-        off[i + 1] = off[i] + n_samples[i];
-        F += 1 + n_samples[i] / h->tab.hop;
-    }
-    int rc;
-    if ((rc = ensure(h, h->io_pcm, (size_t)std::max<int64_t>(off[n_clips], 1) * 4)) != AEGIS_OK) return rc;
+    for (int i = 0; i < n_clips; ++i) F += 1 + n_samples[i] / h->tab.hop;
+    ENSURE(h, io_pcm, off[n_clips] * 4);
     return host_fed_locked(h, off, F, n_clips, rake_sensitivity, stages, out, [&]() {
         return HostFeed{pcm, static_cast<float *>(h->io_pcm.p), std::vector<int64_t>((size_t)n_clips, 0)};
     });
-    } catch (...) { return abi_fail(h); }
+    ENTRY_END(h)
 }
 
 // samples of a clip at rate sr (audio_io.resampled_length); negative with a message for an invalid clip
@@ -882,16 +867,15 @@ int aegis_pcm_geometry(int32_t handle_rate, const aegis_pcm_clip *clip, int64_t 
 
 int aegis_analyze_pcm(aegis_handle *h, const aegis_pcm_clip *clips, int32_t n_clips, double rake_sensitivity, uint32_t stages,
                       aegis_outputs *out, float *y_out) {
-    try {
     if (!h) return AEGIS_ERR_INVALID;
     DisarmInjection disarm{h};
+    ENTRY(h)
     if (stages & AEGIS_STAGE_RAKE) stages |= AEGIS_STAGE_MEL;
     const bool analyse = (stages & AEGIS_STAGE_ALL) != 0;
     if (n_clips < 0 || (n_clips > 0 && (!clips || (analyse && !out)))) { h->err = "null argument"; return AEGIS_ERR_INVALID; }
     if (!analyse && !y_out) { h->err = "stages == 0 decodes only and needs y_out"; return AEGIS_ERR_INVALID; }
     if (n_clips == 0) return AEGIS_OK;
     DEVICE_ONLY(h);
-    std::lock_guard<std::mutex> lock(h->mu);
     HIPCHK(h, hipSetDevice(h->device));
     const int32_t sr = h->tab.sr;
     PcmFeed pf;
@@ -935,16 +919,11 @@ int aegis_analyze_pcm(aegis_handle *h, const aegis_pcm_clip *clips, int32_t n_cl
         off[(size_t)i + 1] = off[(size_t)i] + n_out;
         F += 1 + n_out / h->tab.hop;
     }
-    int rc;
-    if ((rc = ensure(h, h->io_pcm, (size_t)std::max<int64_t>(off[(size_t)n_clips], 1) * 4)) != AEGIS_OK) return rc;
-    if ((rc = ensure(h, h->pcm_raw, (size_t)raw_bytes + 16)) != AEGIS_OK) return rc;
-    if ((rc = ensure(h, h->pcm_clips, (size_t)n_clips * sizeof(PcmClipDev))) != AEGIS_OK) return rc;
-    if ((rc = ensure(h, h->pcm_taps, std::max<size_t>(taps.size(), 1) * 4)) != AEGIS_OK) return rc;
+    ENSURE(h, io_pcm, off[(size_t)n_clips] * 4); ENSURE(h, pcm_raw, (size_t)raw_bytes + 16);
     pf.range_cap = (int64_t)n_clips * 32;
-    if ((rc = ensure(h, h->pcm_ranges, (size_t)pf.range_cap * sizeof(PcmRange))) != AEGIS_OK) return rc;
+    ENSURE(h, pcm_ranges, (size_t)pf.range_cap * sizeof(PcmRange));
     pf.range_cap = (int64_t)(h->pcm_ranges.cap / sizeof(PcmRange));
-    HIPCHK(h, hipMemcpyAsync(h->pcm_clips.p, pf.clips.data(), (size_t)n_clips * sizeof(PcmClipDev), hipMemcpyHostToDevice, h->stream3));
-    if (!taps.empty()) HIPCHK(h, hipMemcpyAsync(h->pcm_taps.p, taps.data(), taps.size() * 4, hipMemcpyHostToDevice, h->stream3));
+    PUT(h, pcm_clips, pf.clips, h->stream3); PUT(h, pcm_taps, taps, h->stream3);
     float *d_pcm = static_cast<float *>(h->io_pcm.p);
     if (!analyse) {      // decode only: every clip at once
         HostFeed feed{nullptr, d_pcm, std::vector<int64_t>((size_t)n_clips, 0), &pf};
@@ -952,9 +931,10 @@ int aegis_analyze_pcm(aegis_handle *h, const aegis_pcm_clip *clips, int32_t n_cl
         std::vector<int32_t> cis((size_t)n_clips);
         std::vector<int64_t> need((size_t)n_clips);
         for (int i = 0; i < n_clips; ++i) { cis[(size_t)i] = i; need[(size_t)i] = off[(size_t)i + 1] - off[(size_t)i]; }
-        if ((rc = pcm_feed(h, feed, cis, need)) != AEGIS_OK) return rc;
+        const int rc = pcm_feed(h, feed, cis, need);
+        if (rc != AEGIS_OK) return rc;
         if (stages & AEGIS_OPT_CHECK_FINITE) {
-            if ((rc = ensure(h, h->finite_flag, 8)) != AEGIS_OK) return rc;
+            ENSURE(h, finite_flag, 8);
             HIPCHK(h, hipMemsetAsync(h->finite_flag.p, 0xff, 8, h->stream3));
             launch_finite_check(d_pcm, off[(size_t)n_clips], static_cast<unsigned long long *>(h->finite_flag.p), h->stream3);
         }
@@ -971,7 +951,7 @@ int aegis_analyze_pcm(aegis_handle *h, const aegis_pcm_clip *clips, int32_t n_cl
         pf.range_used = 0;
         return HostFeed{nullptr, d_pcm, std::vector<int64_t>((size_t)n_clips, 0), &pf};
     });
-    } catch (...) { return abi_fail(h); }
+    ENTRY_END(h)
 }
 
 }  // extern "C"

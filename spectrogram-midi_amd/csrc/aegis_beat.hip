@@ -40,9 +40,8 @@ int beat_upload_offsets(aegis_handle *h, BeatHost &B) {
     hipStream_t s = h->stream;
     B.toff.assign(B.foff.size(), 0);
     for (size_t c = 0; c + 1 < B.foff.size(); ++c) B.toff[c + 1] = B.toff[c] + (B.foff[c + 1] - B.foff[c] + kBeatTile - 1) / kBeatTile;
-    ENSURE(h, bt_foff, B.foff.size() * 8); ENSURE(h, bt_toff, B.toff.size() * 8);
-    HIPCHK(h, upload(h->bt_foff, B.foff.data(), B.foff.size() * 8, s));
-    HIPCHK(h, upload(h->bt_toff, B.toff.data(), B.toff.size() * 8, s));
+    PUT(h, bt_foff, B.foff, s);
+    PUT(h, bt_toff, B.toff, s);
     return AEGIS_OK;
 }
 
@@ -60,16 +59,12 @@ int beat_tempogram_locked(aegis_handle *h, const float *d_env, int32_t n_clips, 
     B.win.resize((size_t)W);
     beat_window(W, B.win.data());
     B.tg.assign((size_t)n_clips * W, 0.0);
-    ENSURE(h, bt_win, (size_t)W * 4);
+    PUT(h, bt_win, B.win, s);
     ENSURE(h, bt_parts, (size_t)B.toff[(size_t)n_clips] * W * 8);
     ENSURE(h, bt_tg, (size_t)n_clips * W * 8);
-    HIPCHK(h, upload(h->bt_win, B.win.data(), (size_t)W * 4, s));
-    begin_event(h, "beat_tempogram", s);
-    launch_beat_tempogram(d_env, h->bt_foff.as<const int64_t>(), h->bt_toff.as<const int64_t>(), n_clips, maxF, W,
-                          h->bt_win.as<const float>(), h->bt_parts.as<double>(), h->bt_tg.as<double>(), s);
-    end_event(h, s);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(B.tg.data(), h->bt_tg.p, B.tg.size() * 8, hipMemcpyDeviceToHost, s));
+    TIMED(h, "beat_tempogram", s, launch_beat_tempogram(d_env, h->bt_foff.as<const int64_t>(), h->bt_toff.as<const int64_t>(), n_clips, maxF, W,
+                                                        h->bt_win.as<const float>(), h->bt_parts.as<double>(), h->bt_tg.as<double>(), s));
+    FETCH(h, B.tg.data(), h->bt_tg.p, B.tg.size(), s);
     return AEGIS_OK;
 }
 
@@ -88,11 +83,8 @@ int beat_track_locked(aegis_handle *h, const float *d_env, int32_t n_clips, int6
     const int64_t *d_foff = h->bt_foff.as<const int64_t>();
     B.stats.assign((size_t)n_clips * 3, 0.0);
     ENSURE(h, bt_stats, B.stats.size() * 8);
-    begin_event(h, "beat_score", s);
-    launch_beat_moments(d_env, d_foff, n_clips, h->bt_stats.as<double>(), s);
-    end_event(h, s);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(B.stats.data(), h->bt_stats.p, B.stats.size() * 8, hipMemcpyDeviceToHost, s));
+    TIMED(h, "beat_score", s, launch_beat_moments(d_env, d_foff, n_clips, h->bt_stats.as<double>(), s));
+    FETCH(h, B.stats.data(), h->bt_stats.p, B.stats.size(), s);
     const bool estimate = !bpm_in && o.bpm == 0.0;
     if (estimate) {
         const int rc = beat_tempogram_locked(h, d_env, n_clips, maxF, o, B);
@@ -137,29 +129,20 @@ int beat_track_locked(aegis_handle *h, const float *d_env, int32_t n_clips, int6
         B.tab_off[(size_t)c] = it->second;
     }
     // ---- device: local score and DP ----------------------------------------------------------------------------------------
-    ENSURE(h, bt_period, (size_t)n_clips * 4); ENSURE(h, bt_taboff, (size_t)n_clips * 8); ENSURE(h, bt_tabs, B.tabs.size() * 8);
+    PUT(h, bt_period, B.period, s); PUT(h, bt_taboff, B.tab_off, s); PUT(h, bt_tabs, B.tabs, s);
     ENSURE(h, bt_ls, (size_t)F * 8); ENSURE(h, bt_cum, (size_t)F * 8); ENSURE(h, bt_back, (size_t)F * 4);
-    HIPCHK(h, upload(h->bt_period, B.period.data(), (size_t)n_clips * 4, s));
-    HIPCHK(h, upload(h->bt_taboff, B.tab_off.data(), (size_t)n_clips * 8, s));
-    HIPCHK(h, upload(h->bt_tabs, B.tabs.data(), B.tabs.size() * 8, s));
     const int32_t *d_period = h->bt_period.as<const int32_t>();
     const int64_t *d_taboff = h->bt_taboff.as<const int64_t>();
     const double *d_tabs = h->bt_tabs.as<const double>();
-    begin_event(h, "beat_score", s);
-    launch_beat_score(d_env, d_foff, n_clips, maxF, d_period, d_taboff, d_tabs, h->bt_stats.as<const double>(),
-                      h->bt_ls.as<double>(), s);
-    end_event(h, s);
-    HIPCHK(h, hipGetLastError());
-    begin_event(h, "beat_dp", s);
-    launch_beat_dp(h->bt_ls.as<const double>(), d_foff, n_clips, d_period, d_taboff, d_tabs, h->bt_cum.as<double>(),
-                   h->bt_back.as<int32_t>(), s);
-    end_event(h, s);
-    HIPCHK(h, hipGetLastError());
+    TIMED(h, "beat_score", s, launch_beat_score(d_env, d_foff, n_clips, maxF, d_period, d_taboff, d_tabs, h->bt_stats.as<const double>(),
+                                                h->bt_ls.as<double>(), s));
+    TIMED(h, "beat_dp", s, launch_beat_dp(h->bt_ls.as<const double>(), d_foff, n_clips, d_period, d_taboff, d_tabs, h->bt_cum.as<double>(),
+                                          h->bt_back.as<int32_t>(), s));
     B.ls.assign((size_t)F, 0.0); B.cum.assign((size_t)F, 0.0); B.back.assign((size_t)F, -1);
     if (F) {
-        HIPCHK(h, hipMemcpyAsync(B.ls.data(), h->bt_ls.p, (size_t)F * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipMemcpyAsync(B.cum.data(), h->bt_cum.p, (size_t)F * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipMemcpyAsync(B.back.data(), h->bt_back.p, (size_t)F * 4, hipMemcpyDeviceToHost, s));
+        FETCH(h, B.ls.data(), h->bt_ls.p, F, s);
+        FETCH(h, B.cum.data(), h->bt_cum.p, F, s);
+        FETCH(h, B.back.data(), h->bt_back.p, F, s);
     }
     HIPCHK(h, hipStreamSynchronize(s));
     // ---- host: the tail ------------------------------------------------------------------------------------------------------
@@ -193,9 +176,7 @@ int aegis_beat_tables(int32_t period, double tightness, double *g_out, double *t
 
 int aegis_tempo(aegis_handle *h, const float *env, const int64_t *n_frames, int32_t n_clips, const aegis_beat_params *p, double *tg_out,
                 double *bpm_out, int32_t *period_out) {
-    try {
-    if (!h) return AEGIS_ERR_INVALID;
-    std::lock_guard<std::mutex> lock(h->mu);
+    ENTRY(h)
     BeatParams o;
     int rc = beat_request(h, p, o);
     if (rc != AEGIS_OK) return rc;
@@ -217,15 +198,13 @@ int aegis_tempo(aegis_handle *h, const float *env, const int64_t *n_frames, int3
         if ((rc = beat_pick_clip(h, B, c, o, period_out[c], bpm_out[c])) != AEGIS_OK) return rc;
     if (tg_out) std::memcpy(tg_out, B.tg.data(), B.tg.size() * 8);
     return AEGIS_OK;
-    } catch (...) { return abi_fail(h); }
+    ENTRY_END(h)
 }
 
 int aegis_beat_track(aegis_handle *h, const float *env, const int64_t *n_frames, int32_t n_clips, const aegis_beat_params *p,
                      const double *bpm_in, uint8_t *beat_mask, int64_t *n_beats, double *bpm_out, double *ls_out, double *cum_out,
                      int32_t *back_out) {
-    try {
-    if (!h) return AEGIS_ERR_INVALID;
-    std::lock_guard<std::mutex> lock(h->mu);
+    ENTRY(h)
     BeatParams o;
     int rc = beat_request(h, p, o);
     if (rc != AEGIS_OK) return rc;
@@ -243,15 +222,13 @@ int aegis_beat_track(aegis_handle *h, const float *env, const int64_t *n_frames,
     if ((rc = beat_upload_env(h, env, F, B)) != AEGIS_OK) return rc;
     rc = beat_track_locked(h, h->bt_env.as<const float>(), n_clips, maxF, o, bpm_in, B, beat_mask, n_beats, bpm_out, ls_out, cum_out, back_out);
     return rc != AEGIS_OK ? rc : scope.finish();
-    } catch (...) { return abi_fail(h); }
+    ENTRY_END(h)
 }
 
 int aegis_analyze_beats(aegis_handle *h, const float *const *pcm, const int64_t *n_samples, int32_t n_clips,
                         const aegis_onset_params *onset_params, const aegis_beat_params *beat_params, float *env_out, uint8_t *beat_mask,
                         int64_t *n_beats, double *bpm_out) {
-    try {
-    if (!h) return AEGIS_ERR_INVALID;
-    std::lock_guard<std::mutex> lock(h->mu);
+    ENTRY(h)
     BeatParams o;
     int rc = beat_request(h, beat_params, o);
     if (rc != AEGIS_OK) return rc;
@@ -272,10 +249,10 @@ int aegis_analyze_beats(aegis_handle *h, const float *const *pcm, const int64_t 
     const int64_t F = B.foff[(size_t)n_clips];
     if ((rc = beat_upload_offsets(h, B)) != AEGIS_OK) return rc;
     if ((rc = onset_env_locked(h, h->io_sdb.as<const float>(), h->bt_foff.as<const int64_t>(), n_clips, F, maxF, h->tab.n_mels, on)) != AEGIS_OK) return rc;
-    if (env_out) HIPCHK(h, hipMemcpyAsync(env_out, h->on_env.p, (size_t)F * 4, hipMemcpyDeviceToHost, h->stream));
+    if (env_out) FETCH(h, env_out, h->on_env.p, F, h->stream);
     rc = beat_track_locked(h, h->on_env.as<const float>(), n_clips, maxF, o, nullptr, B, beat_mask, n_beats, bpm_out, nullptr, nullptr, nullptr);
     return rc != AEGIS_OK ? rc : scope.finish();
-    } catch (...) { return abi_fail(h); }
+    ENTRY_END(h)
 }
 
 }  // extern "C"

@@ -9,18 +9,13 @@ extern "C" {
 
 int aegis_rake_patterns(aegis_handle *h, const float *S_dB, int32_t n_mels, int64_t n_frames,
                         double broadband_threshold_ratio, uint8_t *mask_out) {
-    try {
-    if (!h) return AEGIS_ERR_INVALID;
+    ENTRY(h)
     if (n_mels <= 0 || n_frames < 0 || (n_frames > 0 && (!S_dB || !mask_out))) { h->err = "bad argument"; return AEGIS_ERR_INVALID; }
     if (n_frames == 0) return AEGIS_OK;
     DEVICE_ONLY(h);
-    std::lock_guard<std::mutex> lock(h->mu);
     HIPCHK(h, hipSetDevice(h->device));
-    int rc;
     const size_t img = (size_t)n_mels * n_frames * 4;
-    if ((rc = ensure(h, h->io_sdb, img)) != AEGIS_OK) return rc;
-    if ((rc = ensure(h, h->rk_raw, n_frames)) != AEGIS_OK) return rc;
-    if ((rc = ensure(h, h->io_rake, n_frames)) != AEGIS_OK) return rc;
+    ENSURE(h, io_sdb, img); ENSURE(h, rk_raw, n_frames); ENSURE(h, io_rake, n_frames);
     hipStream_t s = h->stream;
     StreamScope scope(h);
     HIPCHK(h, hipMemcpyAsync(h->io_sdb.p, S_dB, img, hipMemcpyHostToDevice, s));
@@ -29,9 +24,9 @@ int aegis_rake_patterns(aegis_handle *h, const float *S_dB, int32_t n_mels, int6
                         rb.min_frames, rb.max_frames, h->rk_raw.as<uint8_t>(),
                         h->io_rake.as<uint8_t>(), s);
     HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(mask_out, h->io_rake.p, n_frames, hipMemcpyDeviceToHost, s));
+    FETCH(h, mask_out, h->io_rake.p, n_frames, s);
     return scope.finish();
-    } catch (...) { return abi_fail(h); }
+    ENTRY_END(h)
 }
 
 // Frees the least recently used banks until at most `keep` are left.  A kernel enqueued by an earlier call (on the handle's
@@ -113,22 +108,18 @@ static int cqt_launch_locked(aegis_handle *h, const float *d_pcm, const int64_t 
         foff[i + 1] = foff[i] + 1 + n / h->tab.hop;
         toff[i + 1] = toff[i] + (1 + n / h->tab.hop + kCqtSlideFrames - 1) / kCqtSlideFrames;
     }
-    int rc;
-    if ((rc = ensure(h, h->q_soff, (n_clips + 1) * 8)) != AEGIS_OK) return rc;
-    if ((rc = ensure(h, h->q_foff, (n_clips + 1) * 8)) != AEGIS_OK) return rc;
-    if ((rc = ensure(h, h->q_toff, (n_clips + 1) * 8)) != AEGIS_OK) return rc;
+    ENSURE(h, q_soff, (n_clips + 1) * 8);
     {   // foff and toff (and the caller's soff) leave with this frame: a scope of their own, drained before the launch
         StreamScope geometry(h, s);
         HIPCHK(h, hipMemcpyAsync(h->q_soff.p, soff, (n_clips + 1) * 8, hipMemcpyHostToDevice, s));
-        HIPCHK(h, hipMemcpyAsync(h->q_foff.p, foff.data(), (n_clips + 1) * 8, hipMemcpyHostToDevice, s));
-        HIPCHK(h, hipMemcpyAsync(h->q_toff.p, toff.data(), (n_clips + 1) * 8, hipMemcpyHostToDevice, s));
-        if ((rc = geometry.finish()) != AEGIS_OK) return rc;
+        PUT(h, q_foff, foff, s); PUT(h, q_toff, toff, s);
+        const int rc = geometry.finish();
+        if (rc != AEGIS_OK) return rc;
     }
     CqtArgs a{d_pcm, h->q_soff.as<const int64_t>(), h->q_foff.as<const int64_t>(), n_clips,
               foff[n_clips], h->tab.hop, d_out};
     drop_events(h);
-    begin_event(h, "cqt", s); launch_cqt(a, h->cqt_banks.front().bank, h->q_toff.as<const int64_t>(), toff[n_clips], s); end_event(h, s);
-    HIPCHK(h, hipGetLastError());
+    TIMED(h, "cqt", s, launch_cqt(a, h->cqt_banks.front().bank, h->q_toff.as<const int64_t>(), toff[n_clips], s));
     *total_frames = foff[n_clips];
     return AEGIS_OK;
 }
@@ -145,23 +136,16 @@ int aegis::cqt_host_locked(aegis_handle *h, const float *const *pcm, const int64
     if ((rc = cqt_bank_locked(h, n_bins, bins_per_octave, fmin, filter_scale, s)) != AEGIS_OK) return rc;
     for (int b = 0; bin_class && b < n_bins; ++b)
         if (bin_class[b] < 0 || bin_class[b] >= n_chroma) { h->err = "bin_class entries must lie in [0, n_chroma)"; return AEGIS_ERR_INVALID; }
-    std::vector<int64_t> soff(n_clips + 1, 0);
+    std::vector<int64_t> soff;
+    if ((rc = clip_samples(h, "", pcm, n_samples, 0, n_clips, soff)) != AEGIS_OK) return rc;
     int64_t F = 0;
-    for (int i = 0; i < n_clips; ++i) {
-        if (n_samples[i] < 0 || (n_samples[i] > 0 && !pcm[i])) { h->err = "bad clip " + std::to_string(i); return AEGIS_ERR_INVALID; }
-        soff[i + 1] = soff[i] + n_samples[i];
-        F += 1 + n_samples[i] / h->tab.hop;
-    }
-    if ((rc = ensure(h, h->q_pcm, (size_t)std::max<int64_t>(soff[n_clips], 1) * 4)) != AEGIS_OK) return rc;
-    if ((rc = ensure(h, h->q_out, (size_t)F * n_bins * 4)) != AEGIS_OK) return rc;
+    for (int i = 0; i < n_clips; ++i) F += 1 + n_samples[i] / h->tab.hop;
+    ENSURE(h, q_out, (size_t)F * n_bins * 4);
     if (bin_class) {
-        if ((rc = ensure(h, h->q_chroma, (size_t)F * n_chroma * 4)) != AEGIS_OK) return rc;
-        if ((rc = ensure(h, h->q_cls, (size_t)n_bins * 4)) != AEGIS_OK) return rc;
+        ENSURE(h, q_chroma, (size_t)F * n_chroma * 4); ENSURE(h, q_cls, (size_t)n_bins * 4);
         HIPCHK(h, hipMemcpyAsync(h->q_cls.p, bin_class, (size_t)n_bins * 4, hipMemcpyHostToDevice, s));
     }
-    for (int i = 0; i < n_clips; ++i)
-        if (n_samples[i] > 0)
-            HIPCHK(h, hipMemcpyAsync(h->q_pcm.as<float>() + soff[i], pcm[i], n_samples[i] * 4, hipMemcpyHostToDevice, s));
+    if ((rc = upload_clips(h, h->q_pcm, pcm, 0, soff, s)) != AEGIS_OK) return rc;
     int64_t Fd = 0;
     *F_out = F;
     return cqt_launch_locked(h, h->q_pcm.as<const float>(), soff.data(), n_clips, h->q_out.as<float>(), s, &Fd);
@@ -170,59 +154,49 @@ extern "C" {
 
 int aegis_cqt(aegis_handle *h, const float *const *pcm, const int64_t *n_samples, int32_t n_clips,
               int32_t n_bins, int32_t bins_per_octave, double fmin, double filter_scale, float *mag_out) {
-    try {
-    if (!h) return AEGIS_ERR_INVALID;
+    ENTRY(h)
     if (n_clips < 0 || (n_clips > 0 && (!pcm || !n_samples || !mag_out))) { h->err = "null argument"; return AEGIS_ERR_INVALID; }
     if (n_clips == 0) return AEGIS_OK;
     DEVICE_ONLY(h);
-    std::lock_guard<std::mutex> lock(h->mu);
     HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = h->stream;
-    int rc;
     int64_t F = 0;
     StreamScope scope(h);
-    if ((rc = cqt_host_locked(h, pcm, n_samples, n_clips, n_bins, bins_per_octave, fmin, filter_scale, 0, nullptr, &F)) != AEGIS_OK) return rc;
-    HIPCHK(h, hipMemcpyAsync(mag_out, h->q_out.p, (size_t)F * n_bins * 4, hipMemcpyDeviceToHost, s));
+    const int rc = cqt_host_locked(h, pcm, n_samples, n_clips, n_bins, bins_per_octave, fmin, filter_scale, 0, nullptr, &F);
+    if (rc != AEGIS_OK) return rc;
+    FETCH(h, mag_out, h->q_out.p, F * n_bins, h->stream);
     return scope.finish();
-    } catch (...) { return abi_fail(h); }
+    ENTRY_END(h)
 }
 
 int aegis_chroma_cqt(aegis_handle *h, const float *const *pcm, const int64_t *n_samples, int32_t n_clips,
                      int32_t n_bins, int32_t bins_per_octave, double fmin, double filter_scale, int32_t n_chroma,
                      const int32_t *bin_class, float *chroma_out) {
-    try {
-    if (!h) return AEGIS_ERR_INVALID;
+    ENTRY(h)
     if (n_clips < 0 || (n_clips > 0 && (!pcm || !n_samples || !chroma_out)) || !bin_class) { h->err = "null argument"; return AEGIS_ERR_INVALID; }
     if (n_clips == 0) return AEGIS_OK;
     if (n_chroma < 1 || n_chroma > 24) { h->err = "n_chroma must be 1..24"; return AEGIS_ERR_INVALID; }
     DEVICE_ONLY(h);
-    std::lock_guard<std::mutex> lock(h->mu);
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
-    int rc;
     int64_t F = 0;
     StreamScope scope(h);
-    if ((rc = cqt_host_locked(h, pcm, n_samples, n_clips, n_bins, bins_per_octave, fmin, filter_scale, n_chroma, bin_class, &F)) != AEGIS_OK) return rc;
-    begin_event(h, "chroma", s);
-    launch_chroma_fold(h->q_out.as<const float>(), h->q_foff.as<const int64_t>(), n_clips, F, n_bins, n_chroma,
-                       h->q_cls.as<const int32_t>(), h->q_chroma.as<float>(), s);
-    end_event(h, s);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(chroma_out, h->q_chroma.p, (size_t)F * n_chroma * 4, hipMemcpyDeviceToHost, s));
+    const int rc = cqt_host_locked(h, pcm, n_samples, n_clips, n_bins, bins_per_octave, fmin, filter_scale, n_chroma, bin_class, &F);
+    if (rc != AEGIS_OK) return rc;
+    TIMED(h, "chroma", s, launch_chroma_fold(h->q_out.as<const float>(), h->q_foff.as<const int64_t>(), n_clips, F, n_bins, n_chroma,
+                                             h->q_cls.as<const int32_t>(), h->q_chroma.as<float>(), s));
+    FETCH(h, chroma_out, h->q_chroma.p, F * n_chroma, s);
     return scope.finish();
-    } catch (...) { return abi_fail(h); }
+    ENTRY_END(h)
 }
 
 int aegis_cqt_device(aegis_handle *h, const float *d_pcm, const int64_t *sample_offsets, int32_t n_clips,
                      int32_t n_bins, int32_t bins_per_octave, double fmin, double filter_scale, float *d_mag_out,
                      void *stream, int32_t sync) {
-    try {
-    if (!h) return AEGIS_ERR_INVALID;
+    ENTRY(h)
     if (n_clips < 0 || (n_clips > 0 && (!sample_offsets || !d_mag_out))) { h->err = "null argument"; return AEGIS_ERR_INVALID; }
     if (n_clips == 0) return AEGIS_OK;
     DEVICE_ONLY(h);
     if (sample_offsets[n_clips] > sample_offsets[0] && !d_pcm) { h->err = "d_pcm == NULL"; return AEGIS_ERR_INVALID; }
-    std::lock_guard<std::mutex> lock(h->mu);
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
     int rc;
@@ -233,20 +207,18 @@ int aegis_cqt_device(aegis_handle *h, const float *d_pcm, const int64_t *sample_
     if (sync) return scope.finish();
     scope.leave_enqueued();
     return AEGIS_OK;
-    } catch (...) { return abi_fail(h); }
+    ENTRY_END(h)
 }
 
 /* see include/aegis_hip.h */
 int aegis_estimate_tuning(aegis_handle *h, const float *const *pcm, const int64_t *n_samples, int32_t n_clips,
                           int32_t bins_per_octave, double *tuning_out, int32_t *counts_out, int64_t *n_peaks_out) {
-    try {
-    if (!h) return AEGIS_ERR_INVALID;
+    ENTRY(h)
     if (n_clips < 0 || (n_clips > 0 && (!pcm || !n_samples || !tuning_out))) { h->err = "null argument"; return AEGIS_ERR_INVALID; }
     if (bins_per_octave < 1) { h->err = "bins_per_octave must be positive"; return AEGIS_ERR_INVALID; }
     if (h->tab.n_fft != kTunFft) { h->err = "estimate_tuning: only n_fft = 2048 is built (the twiddle and window tables are the handle's)"; return AEGIS_ERR_INVALID; }
     if (n_clips == 0) return AEGIS_OK;
     DEVICE_ONLY(h);
-    std::lock_guard<std::mutex> lock(h->mu);
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
     h->tn_last_peak_off.clear();                               // a call that fails below leaves nothing to fetch
@@ -256,33 +228,25 @@ int aegis_estimate_tuning(aegis_handle *h, const float *const *pcm, const int64_
     const int64_t per_frame = (a.k_hi - a.k_lo + 1) / 2;       // two adjacent bins cannot both be peaks
     // geometry: [sample_off | frame_off | peak_off], n_clips + 1 entries each
     const size_t m = (size_t)n_clips + 1;
-    std::vector<int64_t> geo(3 * m, 0);
-    int64_t *soff = geo.data(), *foff = soff + m, *poff = foff + m;
+    std::vector<int64_t> soff, geo(3 * m, 0);
+    int rc = clip_samples(h, "", pcm, n_samples, 0, n_clips, soff);
+    if (rc != AEGIS_OK) return rc;
+    std::copy(soff.begin(), soff.end(), geo.begin());
+    int64_t *foff = geo.data() + m, *poff = foff + m;
     for (int i = 0; i < n_clips; ++i) {
-        if (n_samples[i] < 0 || (n_samples[i] > 0 && !pcm[i])) { h->err = "bad clip " + std::to_string(i); return AEGIS_ERR_INVALID; }
         const int64_t frames = 1 + n_samples[i] / kTunHop;
-        soff[i + 1] = soff[i] + n_samples[i];
         foff[i + 1] = foff[i] + frames;
         poff[i + 1] = poff[i] + frames * per_frame;
     }
     if (foff[n_clips] >= ((int64_t)1 << 31)) { h->err = "estimate_tuning: too many frames for one call"; return AEGIS_ERR_INVALID; }
     std::vector<unsigned long long> np_host(n_peaks_out ? (size_t)n_clips : 0);
-    int rc;
     const size_t peaks = (size_t)std::max<int64_t>(poff[n_clips], 1);
-    if ((rc = ensure(h, h->q_pcm, (size_t)std::max<int64_t>(soff[n_clips], 1) * 4)) != AEGIS_OK) return rc;
-    if ((rc = ensure(h, h->tn_meta, geo.size() * 8)) != AEGIS_OK) return rc;
-    if ((rc = ensure(h, h->tn_pitch, peaks * 4)) != AEGIS_OK) return rc;
-    if ((rc = ensure(h, h->tn_mag, peaks * 4)) != AEGIS_OK) return rc;
-    if ((rc = ensure(h, h->tn_count, (size_t)n_clips * 8)) != AEGIS_OK) return rc;
-    if ((rc = ensure(h, h->tn_median, (size_t)n_clips * 4)) != AEGIS_OK) return rc;
-    if ((rc = ensure(h, h->tn_cells, (size_t)n_clips * kTunCells * 4)) != AEGIS_OK) return rc;
-    if ((rc = ensure(h, h->tn_tuning, (size_t)n_clips * 8)) != AEGIS_OK) return rc;
+    ENSURE(h, tn_pitch, peaks * 4); ENSURE(h, tn_mag, peaks * 4); ENSURE(h, tn_count, (size_t)n_clips * 8);
+    ENSURE(h, tn_median, (size_t)n_clips * 4); ENSURE(h, tn_cells, (size_t)n_clips * kTunCells * 4); ENSURE(h, tn_tuning, (size_t)n_clips * 8);
     StreamScope scope(h);
-    HIPCHK(h, hipMemcpyAsync(h->tn_meta.p, geo.data(), geo.size() * 8, hipMemcpyHostToDevice, s));
+    PUT(h, tn_meta, geo, s);
     HIPCHK(h, hipMemsetAsync(h->tn_count.p, 0, (size_t)n_clips * 8, s));
-    for (int i = 0; i < n_clips; ++i)
-        if (n_samples[i] > 0)
-            HIPCHK(h, hipMemcpyAsync(h->q_pcm.as<float>() + soff[i], pcm[i], n_samples[i] * 4, hipMemcpyHostToDevice, s));
+    if ((rc = upload_clips(h, h->q_pcm, pcm, 0, soff, s)) != AEGIS_OK) return rc;
     a.pcm = h->q_pcm.as<const float>();
     a.sample_off = h->tn_meta.as<const int64_t>();
     a.frame_off = a.sample_off + m;
@@ -295,18 +259,17 @@ int aegis_estimate_tuning(aegis_handle *h, const float *const *pcm, const int64_
     a.counts = h->tn_cells.as<int32_t>();
     a.tuning = h->tn_tuning.as<double>();
     drop_events(h);
-    begin_event(h, "tuning_peaks", s); launch_tuning_peaks(a, s); end_event(h, s);
-    begin_event(h, "tuning_select", s); launch_tuning_select(a, s); end_event(h, s);
-    begin_event(h, "tuning_hist", s); launch_tuning_hist(a, s); end_event(h, s);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(tuning_out, h->tn_tuning.p, (size_t)n_clips * 8, hipMemcpyDeviceToHost, s));
-    if (counts_out) HIPCHK(h, hipMemcpyAsync(counts_out, h->tn_cells.p, (size_t)n_clips * kTunCells * 4, hipMemcpyDeviceToHost, s));
-    if (n_peaks_out) HIPCHK(h, hipMemcpyAsync(np_host.data(), h->tn_count.p, (size_t)n_clips * 8, hipMemcpyDeviceToHost, s));
+    TIMED(h, "tuning_peaks", s, launch_tuning_peaks(a, s));
+    TIMED(h, "tuning_select", s, launch_tuning_select(a, s));
+    TIMED(h, "tuning_hist", s, launch_tuning_hist(a, s));
+    FETCH(h, tuning_out, h->tn_tuning.p, n_clips, s);
+    if (counts_out) FETCH(h, counts_out, h->tn_cells.p, (size_t)n_clips * kTunCells, s);
+    if (n_peaks_out) FETCH(h, np_host.data(), h->tn_count.p, n_clips, s);
     if ((rc = scope.finish()) != AEGIS_OK) return rc;
     for (size_t i = 0; i < np_host.size(); ++i) n_peaks_out[i] = (int64_t)np_host[i];
     h->tn_last_peak_off.assign(poff, poff + m);
     return AEGIS_OK;
-    } catch (...) { return abi_fail(h); }
+    ENTRY_END(h)
 }
 
 }  // extern "C"

@@ -219,19 +219,16 @@ int effects_group(aegis_handle *h, const Planned &P, int32_t c0, int32_t c1, con
     bool want_i16 = false;
     for (size_t c = 0; c < nc; ++c) want_i16 = want_i16 || (out_i16 && out_i16[c0 + (int32_t)c]);
     ENSURE(h, fx_a, (size_t)total * 8); ENSURE(h, fx_b, (size_t)total * 8);
-    ENSURE(h, fx_recs, recs.size() * sizeof(FxClip)); ENSURE(h, fx_tiles, tiles.size() * sizeof(FxTile));
-    ENSURE(h, fx_peak, recs.size() * 8); ENSURE(h, fx_taps, std::max<size_t>(P.taps.size(), 1) * 8);
+    ENSURE(h, fx_peak, recs.size() * 8);
     if (s16 || want_i16) ENSURE(h, fx_i16, (size_t)total * 2);
     StreamScope scope(h);                                       // (the host vectors above are in front of it)
+    PUT(h, fx_recs, recs, s); PUT(h, fx_tiles, tiles, s); PUT(h, fx_taps, P.taps, s);
     double *buf0 = h->fx_a.as<double>(), *buf1 = h->fx_b.as<double>();
     int16_t *d_i16 = h->fx_i16.as<int16_t>();
     const FxClip *d_recs = h->fx_recs.as<const FxClip>();
     const FxTile *d_tiles = h->fx_tiles.as<const FxTile>();
     unsigned long long *d_peak = h->fx_peak.as<unsigned long long>();
     const double *d_taps = h->fx_taps.as<const double>();
-    HIPCHK(h, hipMemcpyAsync(h->fx_recs.p, recs.data(), recs.size() * sizeof(FxClip), hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(h->fx_tiles.p, tiles.data(), tiles.size() * sizeof(FxTile), hipMemcpyHostToDevice, s));
-    if (!P.taps.empty()) HIPCHK(h, hipMemcpyAsync(h->fx_taps.p, P.taps.data(), P.taps.size() * 8, hipMemcpyHostToDevice, s));
     HIPCHK(h, hipMemsetAsync(h->fx_peak.p, 0, recs.size() * 8, s));
     for (size_t c = 0; c < nc; ++c) {
         const int64_t n = off[c + 1] - off[c];
@@ -239,43 +236,22 @@ int effects_group(aegis_handle *h, const Planned &P, int32_t c0, int32_t c1, con
         if (s16) HIPCHK(h, hipMemcpyAsync(d_i16 + off[c], in[c0 + (int32_t)c], (size_t)n * 2, hipMemcpyHostToDevice, s));
         else HIPCHK(h, hipMemcpyAsync(buf0 + off[c], in[c0 + (int32_t)c], (size_t)n * 8, hipMemcpyHostToDevice, s));
     }
-    if (s16) {
-        begin_event(h, "fx_load", s);
-        fx_load_s16(d_recs, d_tiles + at_whole, d_i16, buf0, (int32_t)whole.size(), s);      // (tiles hold absolute record indices)
-        end_event(h, s);
-    }
+    // (tiles hold absolute record indices)
+    if (s16) TIMED(h, "fx_load", s, fx_load_s16(d_recs, d_tiles + at_whole, d_i16, buf0, (int32_t)whole.size(), s));
     for (size_t st = 0; st < stages; ++st) {
         const int32_t np = (int32_t)(point_at[st + 1] - point_at[st]), nr = (int32_t)(reverb_at[st + 1] - reverb_at[st]);
         const int32_t na = (int32_t)(all_at[st + 1] - all_at[st]);
-        if (np > 0) {
-            begin_event(h, "fx_point", s);
-            fx_point(d_recs, d_tiles + at_point + point_at[st], buf0, buf1, d_peak, np, s);
-            end_event(h, s);
-        }
-        if (nr > 0) {
-            begin_event(h, "fx_reverb", s);
-            fx_reverb(d_recs, d_tiles + at_reverb + reverb_at[st], d_taps, buf0, buf1, d_peak, nr, s);
-            end_event(h, s);
-        }
-        if (na > 0) {
-            begin_event(h, "fx_scale", s);
-            fx_scale(d_recs, d_tiles + at_all + all_at[st], buf0, buf1, d_peak, na, s);
-            end_event(h, s);
-        }
+        if (np > 0) TIMED(h, "fx_point", s, fx_point(d_recs, d_tiles + at_point + point_at[st], buf0, buf1, d_peak, np, s));
+        if (nr > 0) TIMED(h, "fx_reverb", s, fx_reverb(d_recs, d_tiles + at_reverb + reverb_at[st], d_taps, buf0, buf1, d_peak, nr, s));
+        if (na > 0) TIMED(h, "fx_scale", s, fx_scale(d_recs, d_tiles + at_all + all_at[st], buf0, buf1, d_peak, na, s));
     }
-    if (want_i16) {
-        begin_event(h, "fx_i16", s);
-        fx_i16(d_recs, d_tiles + at_whole, buf0, buf1, d_i16, (int32_t)whole.size(), s);
-        end_event(h, s);
-    }
-    HIPCHK(h, hipGetLastError());
+    if (want_i16) TIMED(h, "fx_i16", s, fx_i16(d_recs, d_tiles + at_whole, buf0, buf1, d_i16, (int32_t)whole.size(), s));
     for (size_t c = 0; c < nc; ++c) {
         const int64_t n = off[c + 1] - off[c];
         if (n == 0) continue;
         const int32_t cc = c0 + (int32_t)c;
-        if (out_f64 && out_f64[cc])
-            HIPCHK(h, hipMemcpyAsync(out_f64[cc], (src[c] ? buf1 : buf0) + off[c], (size_t)n * 8, hipMemcpyDeviceToHost, s));
-        if (out_i16 && out_i16[cc]) HIPCHK(h, hipMemcpyAsync(out_i16[cc], d_i16 + off[c], (size_t)n * 2, hipMemcpyDeviceToHost, s));
+        if (out_f64 && out_f64[cc]) FETCH(h, out_f64[cc], (src[c] ? buf1 : buf0) + off[c], n, s);
+        if (out_i16 && out_i16[cc]) FETCH(h, out_i16[cc], d_i16 + off[c], n, s);
     }
     return scope.finish();
 }
@@ -300,9 +276,7 @@ int64_t aegis_reverb_ir(double room_size, int32_t sample_rate, double *dst, int6
 int aegis_effects(aegis_handle *h, int32_t sample_rate, int32_t n_clips, const void *const *in, int32_t in_format,
                   const int64_t *n_samples, const aegis_effect *fx, const int64_t *fx_off, double *const *out_f64,
                   int16_t *const *out_i16) {
-    try {
-    if (!h) return AEGIS_ERR_INVALID;
-    std::lock_guard<std::mutex> lock(h->mu);
+    ENTRY(h)
     if (sample_rate <= 0 || n_clips < 0 || (in_format != AEGIS_PCM_S16 && in_format != AEGIS_PCM_F64) ||
         (n_clips > 0 && (!in || !n_samples || !fx_off))) {
         h->err = "bad argument"; return AEGIS_ERR_INVALID;
@@ -315,7 +289,7 @@ int aegis_effects(aegis_handle *h, int32_t sample_rate, int32_t n_clips, const v
     return run_halving(h, n_clips, [&](int32_t c0, int32_t c1) {
         return effects_group(h, P, c0, c1, in, in_format, n_samples, out_f64, out_i16);
     });
-    } catch (...) { return abi_fail(h); }
+    ENTRY_END(h)
 }
 
 }  // extern "C"

@@ -506,9 +506,8 @@ int64_t aegis_get_table(const aegis_handle *h, const char *name, void *dst, int6
 
 int64_t aegis_debug_plan(aegis_handle *h, const int64_t *n_samples, int32_t n_clips, int32_t entry, int32_t sync,
                          int32_t n_cus, int64_t *dst, int64_t cap) {
-    try {
-    if (!h || n_clips < 0 || (n_clips > 0 && !n_samples) || cap < 0 || (cap > 0 && !dst)) return AEGIS_ERR_INVALID;
-    std::lock_guard<std::mutex> lock(h->mu);
+    ENTRY(h)
+    if (n_clips < 0 || (n_clips > 0 && !n_samples) || cap < 0 || (cap > 0 && !dst)) return AEGIS_ERR_INVALID;
     std::vector<int64_t> off((size_t)n_clips + 1, 0);
     for (int i = 0; i < n_clips; ++i) {
         if (n_samples[i] < 0 || 1 + n_samples[i] / h->tab.hop > h->max_frames_per_pass) { h->err = "bad clip " + std::to_string(i); return AEGIS_ERR_INVALID; }
@@ -540,7 +539,7 @@ int64_t aegis_debug_plan(aegis_handle *h, const int64_t *n_samples, int32_t n_cl
     }
     if (cap > 0) std::memcpy(dst, v.data(), (size_t)std::min<int64_t>(cap, (int64_t)v.size()) * 8);
     return (int64_t)v.size();
-    } catch (...) { return abi_fail(h); }
+    ENTRY_END(h)
 }
 
 // The kernels' debug counters behind aegis_debug_fetch: device-wide synchronisation, then `count` int64 through the kernel
@@ -557,8 +556,8 @@ static const Counter kCounters[] = {
 };
 
 int64_t aegis_debug_fetch(aegis_handle *h, const char *name, void *dst, int64_t cap) {
-    try {
-    if (!h || !name) return AEGIS_ERR_INVALID;
+    ENTRY(h)
+    if (!name) return AEGIS_ERR_INVALID;
     const std::string n(name);
     // test hooks of the exception barrier (tests/test_abi_and_tables.py): the body throws, the entry returns a code
     if (n == "throw_bad_alloc") throw std::bad_alloc();
@@ -647,7 +646,6 @@ int64_t aegis_debug_fetch(aegis_handle *h, const char *name, void *dst, int64_t 
         if (h->device < 0 || !h->vstats.p) return AEGIS_ERR_INVALID;
         if (dst && cap > 0) {
             long long v[3];
-            std::lock_guard<std::mutex> lock(h->mu);
             HIPCHK(h, hipSetDevice(h->device));
             HIPCHK(h, hipDeviceSynchronize());
             HIPCHK(h, hipMemcpy(v, h->vstats.p, 24, hipMemcpyDeviceToHost));
@@ -682,23 +680,18 @@ int64_t aegis_debug_fetch(aegis_handle *h, const char *name, void *dst, int64_t 
         HIPCHK(h, hipMemcpy(dst, src, (size_t)std::min(count, cap) * esz, hipMemcpyDeviceToHost));
     }
     return count;
-    } catch (...) { return abi_fail(h); }
+    ENTRY_END(h)
 }
 
 int aegis_debug_rake_columns(aegis_handle *h, const float *mel_power, int64_t n_rows, int32_t n_mels, float clip_max,
                              double ratio, int32_t from_power, uint8_t *flags_out) {
-    try {
-    if (!h) return AEGIS_ERR_INVALID;
+    ENTRY(h)
     if (n_rows < 0 || n_mels <= 0 || n_mels > 128 || (n_rows > 0 && (!mel_power || !flags_out))) { h->err = "bad argument"; return AEGIS_ERR_INVALID; }
     if (n_rows == 0) return AEGIS_OK;
     DEVICE_ONLY(h);
-    std::lock_guard<std::mutex> lock(h->mu);
     HIPCHK(h, hipSetDevice(h->device));
-    int rc;
     const size_t bytes = (size_t)n_rows * n_mels * 4;
-    if ((rc = ensure(h, h->io_sdb, bytes)) != AEGIS_OK) return rc;
-    if ((rc = ensure(h, h->rk_raw, n_rows)) != AEGIS_OK) return rc;
-    if ((rc = ensure(h, h->io_rake, 32)) != AEGIS_OK) return rc;        // frame_off[2] | clipmax
+    ENSURE(h, io_sdb, bytes); ENSURE(h, rk_raw, n_rows); ENSURE(h, io_rake, 32);        // (io_rake: frame_off[2] | clipmax)
     hipStream_t s = h->stream;
     struct { int64_t frame_off[2]; uint32_t clipmax; } geo = {{0, n_rows}, 0};
     std::memcpy(&geo.clipmax, &clip_max, 4);
@@ -714,21 +707,18 @@ int aegis_debug_rake_columns(aegis_handle *h, const float *mel_power, int64_t n_
     p.rake_ratio = ratio;
     launch_rake_columns(p, from_power != 0, s);
     HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(flags_out, h->rk_raw.p, n_rows, hipMemcpyDeviceToHost, s));
+    FETCH(h, flags_out, h->rk_raw.p, n_rows, s);
     return scope.finish();
-    } catch (...) { return abi_fail(h); }
+    ENTRY_END(h)
 }
 
 int aegis_debug_pitch_bins(aegis_handle *h, const double *periods, int64_t n, int16_t *bin_table, int16_t *bin_exact, uint8_t *fell_through) {
-    try {
-    if (!h) return AEGIS_ERR_INVALID;
+    ENTRY(h)
     if (n < 0 || (n > 0 && (!periods || !bin_table || !bin_exact || !fell_through))) { h->err = "bad argument"; return AEGIS_ERR_INVALID; }
     if (n == 0) return AEGIS_OK;
     DEVICE_ONLY(h);
-    std::lock_guard<std::mutex> lock(h->mu);
     HIPCHK(h, hipSetDevice(h->device));
-    int rc;
-    if ((rc = ensure(h, h->dbg_bins, (size_t)n * 13)) != AEGIS_OK) return rc;     // periods f64 | table i16 | exact i16 | fell u8
+    ENSURE(h, dbg_bins, (size_t)n * 13);     // periods f64 | table i16 | exact i16 | fell u8
     hipStream_t s = h->stream;
     double *d_per = h->dbg_bins.as<double>();
     int16_t *d_fast = reinterpret_cast<int16_t *>(d_per + n), *d_exact = d_fast + n;
@@ -737,17 +727,13 @@ int aegis_debug_pitch_bins(aegis_handle *h, const double *periods, int64_t n, in
     HIPCHK(h, hipMemcpyAsync(d_per, periods, (size_t)n * 8, hipMemcpyHostToDevice, s));
     launch_pitch_bins(base_params(h->tab), h->dt, d_per, n, d_fast, d_exact, d_fell, s);
     HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(bin_table, d_fast, (size_t)n * 2, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipMemcpyAsync(bin_exact, d_exact, (size_t)n * 2, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipMemcpyAsync(fell_through, d_fell, (size_t)n, hipMemcpyDeviceToHost, s));
+    FETCH(h, bin_table, d_fast, n, s); FETCH(h, bin_exact, d_exact, n, s); FETCH(h, fell_through, d_fell, n, s);
     return scope.finish();
-    } catch (...) { return abi_fail(h); }
+    ENTRY_END(h)
 }
 
 int aegis_debug_set_observations(aegis_handle *h, const double *logobs, const double *logunv, int64_t F) {
-    try {
-    if (!h) return AEGIS_ERR_INVALID;
-    std::lock_guard<std::mutex> lock(h->mu);
+    ENTRY(h)
     h->inject.armed = false;
     if (!logobs) return AEGIS_OK;
     if (!logunv || F <= 0) { h->err = "bad argument"; return AEGIS_ERR_INVALID; }
@@ -759,20 +745,17 @@ int aegis_debug_set_observations(aegis_handle *h, const double *logobs, const do
     DEVICE_ONLY(h);
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipDeviceSynchronize());        // (an earlier armed call that returned without a sync may still read the rows)
-    if ((rc = ensure(h, h->inject.obs, (size_t)F * B * 8)) != AEGIS_OK) return rc;
-    if ((rc = ensure(h, h->inject.unv, (size_t)F * 8)) != AEGIS_OK) return rc;
+    ENSURE(h, inject.obs, (size_t)F * B * 8); ENSURE(h, inject.unv, (size_t)F * 8);
     HIPCHK(h, hipMemcpy(h->inject.obs.p, logobs, (size_t)F * B * 8, hipMemcpyHostToDevice));
     HIPCHK(h, hipMemcpy(h->inject.unv.p, logunv, (size_t)F * 8, hipMemcpyHostToDevice));
     h->inject.F = F;
     h->inject.armed = true;
     return AEGIS_OK;
-    } catch (...) { return abi_fail(h); }
+    ENTRY_END(h)
 }
 
 int aegis_debug_set_difference(aegis_handle *h, const double *d, int64_t F) {
-    try {
-    if (!h) return AEGIS_ERR_INVALID;
-    std::lock_guard<std::mutex> lock(h->mu);
+    ENTRY(h)
     h->inject_d.armed = false;
     if (!d) return AEGIS_OK;
     if (F <= 0) { h->err = "bad argument"; return AEGIS_ERR_INVALID; }
@@ -788,19 +771,16 @@ int aegis_debug_set_difference(aegis_handle *h, const double *d, int64_t F) {
     DEVICE_ONLY(h);
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipDeviceSynchronize());        // (an earlier armed call that returned without a sync may still read the rows)
-    int rc;
-    if ((rc = ensure(h, h->inject_d.d, (size_t)F * W * 8)) != AEGIS_OK) return rc;
+    ENSURE(h, inject_d.d, (size_t)F * W * 8);
     HIPCHK(h, hipMemcpy(h->inject_d.d.p, d, (size_t)F * W * 8, hipMemcpyHostToDevice));
     h->inject_d.F = F;
     h->inject_d.armed = true;
     return AEGIS_OK;
-    } catch (...) { return abi_fail(h); }
+    ENTRY_END(h)
 }
 
 int aegis_debug_set_rake_columns(aegis_handle *h, const uint8_t *flags, int64_t F) {
-    try {
-    if (!h) return AEGIS_ERR_INVALID;
-    std::lock_guard<std::mutex> lock(h->mu);
+    ENTRY(h)
     h->inject_r.armed = false;
     if (!flags) return AEGIS_OK;
     if (F <= 0) { h->err = "bad argument"; return AEGIS_ERR_INVALID; }
@@ -812,13 +792,12 @@ int aegis_debug_set_rake_columns(aegis_handle *h, const uint8_t *flags, int64_t 
     if (h->device < 0) { h->err = "injected rake columns: the handle was created with device=-1 (host tables only), no analyze call can take them"; return AEGIS_ERR_INVALID; }
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipDeviceSynchronize());        // (an earlier armed call that returned without a sync may still read the flags)
-    int rc;
-    if ((rc = ensure(h, h->inject_r.flags, (size_t)F)) != AEGIS_OK) return rc;
+    ENSURE(h, inject_r.flags, (size_t)F);
     HIPCHK(h, hipMemcpy(h->inject_r.flags.p, flags, (size_t)F, hipMemcpyHostToDevice));
     h->inject_r.F = F;
     h->inject_r.armed = true;
     return AEGIS_OK;
-    } catch (...) { return abi_fail(h); }
+    ENTRY_END(h)
 }
 
 }  // extern "C"

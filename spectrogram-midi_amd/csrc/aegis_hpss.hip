@@ -72,34 +72,33 @@ hipError_t copy_rows(void *dst, size_t dpitch, const void *src, size_t spitch, s
     return hipMemcpy2DAsync(dst, dpitch * 4, src, spitch * 4, width * 4, (size_t)n_bins, kind, s);
 }
 
+// the two running medians and the masks of the n_segs segments in hp_segs over hp_in (handle locked, the images sized)
+int hpss_medians(aegis_handle *h, int n_segs, int32_t max_out, int32_t n_bins, const HpssParams &o) {
+    hipStream_t s = h->stream;
+    const HpssSeg *d_segs = h->hp_segs.as<const HpssSeg>();
+    TIMED(h, "hpss_median_t", s, launch_hpss_median_t(h->hp_in.as<const float>(), d_segs, n_segs, max_out, n_bins, o.win_harm, h->hp_harm.as<float>(), s));
+    TIMED(h, "hpss_median_f", s, launch_hpss_median_f(h->hp_in.as<const float>(), h->hp_harm.as<const float>(), d_segs, n_segs, max_out, n_bins, o,
+                                                      h->hp_perc.as<float>(), h->hp_mh.as<float>(), h->hp_mp.as<float>(), s));
+    return AEGIS_OK;
+}
+
 int hpss_run_pass(aegis_handle *h, const HpssPass &P, const float *S, const std::vector<int64_t> &foff, int32_t n_bins, const HpssParams &o,
                   float *const (&out)[4], unsigned long long *first_bad) {
     hipStream_t s = h->stream;
     const size_t bytes = (size_t)P.cols * n_bins * 4;
     const int n_segs = (int)P.segs.size();
     ENSURE(h, hp_in, bytes); ENSURE(h, hp_harm, bytes); ENSURE(h, hp_perc, bytes); ENSURE(h, hp_mh, bytes); ENSURE(h, hp_mp, bytes);
-    ENSURE(h, hp_segs, (size_t)n_segs * sizeof(HpssSeg)); ENSURE(h, hp_flag, 8);
+    PUT(h, hp_segs, P.segs, s);
+    ENSURE(h, hp_flag, 8);
     *first_bad = ~0ull;
-    HIPCHK(h, upload(h->hp_segs, P.segs.data(), (size_t)n_segs * sizeof(HpssSeg), s));
     HIPCHK(h, upload(h->hp_flag, first_bad, 8, s));
     for (const HpssSeg &g : P.segs)
         HIPCHK(h, copy_rows(h->hp_in.as<float>() + g.off, (size_t)g.W, S + foff[(size_t)g.clip] * n_bins + g.a, (size_t)g.F, (size_t)g.W, n_bins,
                             hipMemcpyHostToDevice, s));
-    const HpssSeg *d_segs = h->hp_segs.as<const HpssSeg>();
-    begin_event(h, "hpss_check", s);
-    launch_hpss_check(h->hp_in.as<const float>(), P.cols * n_bins, h->hp_flag.as<unsigned long long>(), s);
-    end_event(h, s);
-    HIPCHK(h, hipGetLastError());
-    begin_event(h, "hpss_median_t", s);
-    launch_hpss_median_t(h->hp_in.as<const float>(), d_segs, n_segs, P.max_out, n_bins, o.win_harm, h->hp_harm.as<float>(), s);
-    end_event(h, s);
-    HIPCHK(h, hipGetLastError());
-    begin_event(h, "hpss_median_f", s);
-    launch_hpss_median_f(h->hp_in.as<const float>(), h->hp_harm.as<const float>(), d_segs, n_segs, P.max_out, n_bins, o, h->hp_perc.as<float>(),
-                         h->hp_mh.as<float>(), h->hp_mp.as<float>(), s);
-    end_event(h, s);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(first_bad, h->hp_flag.p, 8, hipMemcpyDeviceToHost, s));
+    TIMED(h, "hpss_check", s, launch_hpss_check(h->hp_in.as<const float>(), P.cols * n_bins, h->hp_flag.as<unsigned long long>(), s));
+    const int rc = hpss_medians(h, n_segs, P.max_out, n_bins, o);
+    if (rc != AEGIS_OK) return rc;
+    FETCH(h, first_bad, h->hp_flag.p, 1, s);
     const DevBuf *bufs[4] = {&h->hp_harm, &h->hp_perc, &h->hp_mh, &h->hp_mp};
     for (int f = 0; f < 4; ++f) {
         if (!out[f]) continue;
@@ -110,63 +109,67 @@ int hpss_run_pass(aegis_handle *h, const HpssPass &P, const float *S, const std:
     return AEGIS_OK;
 }
 
-}  // namespace
-
-namespace {
-
-// One pass of whole clips [c0, c1): their sample, frame and frame-pair offsets on the host and (upload_pass) in hp_off.
+// One pass of pieces of clips (whole clips, but for aegis_stft, which cuts a long clip into frame ranges): per piece its clip
+// and its first sample there, the sample, frame and frame-pair offsets [n + 1] on the host and (upload_pass) in hp_off.
+// sh: aegis_stft's shift per piece, the sample its first frame is centred on counted from s_lo (empty: whole clips).
 struct ClipPass {
-    int32_t c0 = 0, n = 0;
-    std::vector<int64_t> so, fo, po;
+    int32_t n = 0;
+    std::vector<int32_t> clip;
+    std::vector<int64_t> s_lo, so{0}, fo{0}, po{0}, sh;
     unsigned long long bad = ~0ull;
-    const int64_t *d_so = nullptr, *d_fo = nullptr, *d_po = nullptr;
+    const int64_t *d_so = nullptr, *d_fo = nullptr, *d_po = nullptr, *d_sh = nullptr;
+    void add(int32_t c, int64_t lo, int64_t samples, int64_t frames) {
+        ++n; clip.push_back(c); s_lo.push_back(lo);
+        so.push_back(so.back() + samples); fo.push_back(fo.back() + frames); po.push_back(po.back() + (frames + 1) / 2);
+    }
 };
 
-// clips from c0 on while their frames stay within cap, one clip at least
+// whole clips from c0 on while their frames stay within cap, one clip at least
 void next_pass(const std::vector<int64_t> &foff, const int64_t *n_samples, int32_t n_clips, int32_t c0, int64_t cap, ClipPass &P) {
     int32_t c1 = c0 + 1;
     while (c1 < n_clips && foff[(size_t)c1 + 1] - foff[(size_t)c0] <= cap) ++c1;
-    P.c0 = c0; P.n = c1 - c0;
-    P.so.assign((size_t)P.n + 1, 0); P.fo.assign((size_t)P.n + 1, 0); P.po.assign((size_t)P.n + 1, 0);
-    for (int32_t i = 0; i < P.n; ++i) {
-        const int64_t Fc = foff[(size_t)(c0 + i) + 1] - foff[(size_t)(c0 + i)];
-        P.so[(size_t)i + 1] = P.so[(size_t)i] + n_samples[c0 + i];
-        P.fo[(size_t)i + 1] = P.fo[(size_t)i] + Fc;
-        P.po[(size_t)i + 1] = P.po[(size_t)i] + (Fc + 1) / 2;
-    }
-    P.bad = ~0ull;
+    for (int32_t c = c0; c < c1; ++c) P.add(c, 0, n_samples[c], foff[(size_t)c + 1] - foff[(size_t)c]);
 }
 
-int upload_pass(aegis_handle *h, ClipPass &P, const float *const *pcm, const int64_t *n_samples) {
+// The pass's offset tables into hp_off and, with pcm, its samples into hp_pcm behind the finite check that leaves its
+// verdict in P.bad.
+int upload_pass(aegis_handle *h, ClipPass &P, const float *const *pcm) {
     hipStream_t s = h->stream;
     const size_t n = (size_t)P.n + 1;
-    if (P.po[(size_t)P.n] > INT32_MAX) { h->err = "hpss: too many frames for one call"; return AEGIS_ERR_INVALID; }
-    ENSURE(h, hp_off, n * 24); ENSURE(h, hp_flag, 8);
+    if (P.po.back() > INT32_MAX) { h->err = "hpss: too many frames for one call"; return AEGIS_ERR_INVALID; }
+    ENSURE(h, hp_off, n * 32); ENSURE(h, hp_flag, 8);
     int64_t *d = h->hp_off.as<int64_t>();
-    HIPCHK(h, hipMemcpyAsync(d, P.so.data(), n * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(d + n, P.fo.data(), n * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(d + 2 * n, P.po.data(), n * 8, hipMemcpyHostToDevice, s));
-    P.d_so = d; P.d_fo = d + n; P.d_po = d + 2 * n;
+    const std::vector<int64_t> *tabs[4] = {&P.so, &P.fo, &P.po, &P.sh};
+    for (size_t t = 0; t < 4; ++t)
+        if (!tabs[t]->empty()) HIPCHK(h, hipMemcpyAsync(d + t * n, tabs[t]->data(), tabs[t]->size() * 8, hipMemcpyHostToDevice, s));
+    P.d_so = d; P.d_fo = d + n; P.d_po = d + 2 * n; P.d_sh = P.sh.empty() ? nullptr : d + 3 * n;
     HIPCHK(h, hipMemsetAsync(h->hp_flag.p, 0xff, 8, s));
-    if (pcm) {
-        ENSURE(h, hp_pcm, (size_t)P.so[(size_t)P.n] * 4);
-        for (int32_t i = 0; i < P.n; ++i)
-            if (n_samples[P.c0 + i] > 0)
-                HIPCHK(h, hipMemcpyAsync(h->hp_pcm.as<float>() + P.so[(size_t)i], pcm[P.c0 + i], (size_t)n_samples[P.c0 + i] * 4, hipMemcpyHostToDevice, s));
-        if (P.so[(size_t)P.n] > 0) launch_finite_check(h->hp_pcm.as<const float>(), P.so[(size_t)P.n], h->hp_flag.as<unsigned long long>(), s);
-        HIPCHK(h, hipGetLastError());
-        HIPCHK(h, hipMemcpyAsync(&P.bad, h->hp_flag.p, 8, hipMemcpyDeviceToHost, s));
-    }
+    if (!pcm) return AEGIS_OK;
+    ENSURE(h, hp_pcm, (size_t)P.so.back() * 4);
+    for (size_t i = 0; i < (size_t)P.n; ++i)      // (a piece starts s_lo into its clip: not upload_clips' whole clips)
+        if (P.so[i + 1] > P.so[i])
+            HIPCHK(h, hipMemcpyAsync(h->hp_pcm.as<float>() + P.so[i], pcm[P.clip[i]] + P.s_lo[i], (size_t)(P.so[i + 1] - P.so[i]) * 4, hipMemcpyHostToDevice, s));
+    if (P.so.back() > 0) launch_finite_check(h->hp_pcm.as<const float>(), P.so.back(), h->hp_flag.as<unsigned long long>(), s);
+    HIPCHK(h, hipGetLastError());
+    FETCH(h, &P.bad, h->hp_flag.p, 1, s);
     return AEGIS_OK;
 }
 
-// after the pass has drained: the verdict of its finite check
+// after the pass has drained: the verdict of its finite check, the sample counted in the clip's own samples
 int pass_verdict(aegis_handle *h, const ClipPass &P) {
     if (P.bad == ~0ull) return AEGIS_OK;
     int32_t i = 0;
     while (i + 1 < P.n && (int64_t)P.bad >= P.so[(size_t)i + 1]) ++i;
-    h->err = "Audio buffer is not finite everywhere (clip " + std::to_string(P.c0 + i) + ", sample " + std::to_string((int64_t)P.bad - P.so[(size_t)i]) + ")";
+    h->err = "Audio buffer is not finite everywhere (clip " + std::to_string(P.clip[(size_t)i]) + ", sample " +
+             std::to_string((int64_t)P.bad - P.so[(size_t)i] + P.s_lo[(size_t)i]) + ")";
     return AEGIS_ERR_INVALID;
+}
+
+// the end of a pass: the scope's final synchronisation, and the pass's kernel times added to the call's
+int finish_pass(aegis_handle *h, StreamScope &scope, std::map<std::string, double> &ms) {
+    const int rc = scope.finish();
+    if (rc == AEGIS_OK) for (const auto &kv : h->last_ms) ms[kv.first] += kv.second;
+    return rc;
 }
 
 int stft_geometry(aegis_handle *h, const char *pre) {
@@ -185,8 +188,8 @@ int gather_pass(aegis_handle *h, const ClipPass &P, int64_t sample0, float *ya, 
     launch_hpss_gather(h->hp_fa.as<const double>(), yb ? h->hp_fb.as<const double>() : nullptr, P.d_so, P.d_fo, P.n, (int64_t)N, h->tab.hop,
                        h->dt.hann, h->hp_ya.as<float>(), yb ? h->hp_yb.as<float>() : nullptr, s);
     HIPCHK(h, hipGetLastError());
-    if (ya) HIPCHK(h, hipMemcpyAsync(ya + sample0, h->hp_ya.p, N * 4, hipMemcpyDeviceToHost, s));
-    if (yb) HIPCHK(h, hipMemcpyAsync(yb + sample0, h->hp_yb.p, N * 4, hipMemcpyDeviceToHost, s));
+    if (ya) FETCH(h, ya + sample0, h->hp_ya.p, N, s);
+    if (yb) FETCH(h, yb + sample0, h->hp_yb.p, N, s);
     return AEGIS_OK;
 }
 
@@ -195,9 +198,7 @@ int gather_pass(aegis_handle *h, const ClipPass &P, int64_t sample0, float *ya, 
 extern "C" {
 
 int aegis_stft(aegis_handle *h, const float *const *pcm, const int64_t *n_samples, int32_t n_clips, float *D, float *S) {
-    try {
-    if (!h) return AEGIS_ERR_INVALID;
-    std::lock_guard<std::mutex> lock(h->mu);
+    ENTRY(h)
     int rc = stft_geometry(h, "stft: ");
     if (rc != AEGIS_OK) return rc;
     if (n_clips < 0 || (n_clips > 0 && (!pcm || !n_samples))) { h->err = "stft: null argument"; return AEGIS_ERR_INVALID; }
@@ -227,66 +228,38 @@ int aegis_stft(aegis_handle *h, const float *const *pcm, const int64_t *n_sample
     }
     std::map<std::string, double> ms;                             // kernel times summed over the passes
     for (size_t p0 = 0; p0 < pieces.size();) {
-        size_t p1 = p0 + 1;
-        int64_t frames = pieces[p0].tb - pieces[p0].ta;
-        while (p1 < pieces.size() && frames + (pieces[p1].tb - pieces[p1].ta) <= cap) { frames += pieces[p1].tb - pieces[p1].ta; ++p1; }
-        const size_t n = p1 - p0;
-        std::vector<int64_t> off(4 * (n + 1), 0);                // sample, frame and pair offsets [n + 1] each, then the shifts
-        int64_t *so = off.data(), *fo = so + (n + 1), *po = fo + (n + 1), *sh = po + (n + 1);
-        for (size_t i = 0; i < n; ++i) {
-            const Piece &q = pieces[p0 + i];
-            so[i + 1] = so[i] + q.s_n;
-            fo[i + 1] = fo[i] + (q.tb - q.ta);
-            po[i + 1] = po[i] + (q.tb - q.ta + 1) / 2;
-            sh[i] = q.shift;
-        }
-        unsigned long long bad = ~0ull;
+        ClipPass P;
+        size_t p1 = p0;
+        do {
+            const Piece &q = pieces[p1++];
+            P.add(q.clip, q.s_lo, q.s_n, q.tb - q.ta);
+            P.sh.push_back(q.shift);
+        } while (p1 < pieces.size() && P.fo.back() + (pieces[p1].tb - pieces[p1].ta) <= cap);
+        const size_t Fg = (size_t)P.fo.back();
         StreamScope scope(h);
-        ENSURE(h, hp_off, off.size() * 8); ENSURE(h, hp_flag, 8); ENSURE(h, hp_pcm, (size_t)so[n] * 4);
-        if (D) ENSURE(h, hp_D, (size_t)fo[n] * 1025 * 8);
-        if (S) ENSURE(h, hp_in, (size_t)fo[n] * 1025 * 4);
-        HIPCHK(h, upload(h->hp_off, off.data(), off.size() * 8, s));
-        const int64_t *d = h->hp_off.as<const int64_t>();
-        for (size_t i = 0; i < n; ++i) {
-            const Piece &q = pieces[p0 + i];
-            if (q.s_n > 0) HIPCHK(h, hipMemcpyAsync(h->hp_pcm.as<float>() + so[i], pcm[q.clip] + q.s_lo, (size_t)q.s_n * 4, hipMemcpyHostToDevice, s));
-        }
-        HIPCHK(h, hipMemsetAsync(h->hp_flag.p, 0xff, 8, s));
-        if (so[n] > 0) launch_finite_check(h->hp_pcm.as<const float>(), so[n], h->hp_flag.as<unsigned long long>(), s);
-        HIPCHK(h, hipGetLastError());
-        HIPCHK(h, hipMemcpyAsync(&bad, h->hp_flag.p, 8, hipMemcpyDeviceToHost, s));
-        begin_event(h, "hpss_stft", s);
-        launch_hpss_stft(h->hp_pcm.as<const float>(), d, d + (n + 1), d + 2 * (n + 1), d + 3 * (n + 1), (int)n, po[n], h->tab.hop, h->dt.hann,
-                         h->dt.twiddle, D ? h->hp_D.as<float>() : nullptr, S ? h->hp_in.as<float>() : nullptr, s);
-        end_event(h, s);
-        HIPCHK(h, hipGetLastError());
-        for (size_t i = 0; i < n; ++i) {                          // a piece's [1025, W] image into its columns of the clip's [1025, F]
+        if ((rc = upload_pass(h, P, pcm)) != AEGIS_OK) return rc;
+        if (D) ENSURE(h, hp_D, Fg * 1025 * 8);
+        if (S) ENSURE(h, hp_in, Fg * 1025 * 4);
+        TIMED(h, "hpss_stft", s, launch_hpss_stft(h->hp_pcm.as<const float>(), P.d_so, P.d_fo, P.d_po, P.d_sh, P.n, P.po.back(), h->tab.hop, h->dt.hann,
+                                                  h->dt.twiddle, D ? h->hp_D.as<float>() : nullptr, S ? h->hp_in.as<float>() : nullptr, s));
+        for (size_t i = 0; i < p1 - p0; ++i) {                    // a piece's [1025, W] image into its columns of the clip's [1025, F]
             const Piece &q = pieces[p0 + i];
             const size_t F = (size_t)(foff[(size_t)q.clip + 1] - foff[(size_t)q.clip]), W = (size_t)(q.tb - q.ta);
             const size_t at = (size_t)foff[(size_t)q.clip] * 1025 + (size_t)q.ta;
-            if (D) HIPCHK(h, copy_rows(D + 2 * at, 2 * F, h->hp_D.as<const float>() + 2 * (size_t)fo[i] * 1025, 2 * W, 2 * W, 1025, hipMemcpyDeviceToHost, s));
-            if (S) HIPCHK(h, copy_rows(S + at, F, h->hp_in.as<const float>() + (size_t)fo[i] * 1025, W, W, 1025, hipMemcpyDeviceToHost, s));
+            if (D) HIPCHK(h, copy_rows(D + 2 * at, 2 * F, h->hp_D.as<const float>() + 2 * (size_t)P.fo[i] * 1025, 2 * W, 2 * W, 1025, hipMemcpyDeviceToHost, s));
+            if (S) HIPCHK(h, copy_rows(S + at, F, h->hp_in.as<const float>() + (size_t)P.fo[i] * 1025, W, W, 1025, hipMemcpyDeviceToHost, s));
         }
-        if ((rc = scope.finish()) != AEGIS_OK) return rc;
-        for (const auto &kv : h->last_ms) ms[kv.first] += kv.second;
-        if (bad != ~0ull) {
-            size_t i = 0;
-            while (i + 1 < n && (int64_t)bad >= so[i + 1]) ++i;
-            const Piece &q = pieces[p0 + i];
-            h->err = "Audio buffer is not finite everywhere (clip " + std::to_string(q.clip) + ", sample " + std::to_string((int64_t)bad - so[i] + q.s_lo) + ")";
-            return AEGIS_ERR_INVALID;
-        }
+        if ((rc = finish_pass(h, scope, ms)) != AEGIS_OK) return rc;
+        if ((rc = pass_verdict(h, P)) != AEGIS_OK) return rc;
         p0 = p1;
     }
     h->last_ms = ms;
     return AEGIS_OK;
-    } catch (...) { return abi_fail(h); }
+    ENTRY_END(h)
 }
 
 int aegis_istft(aegis_handle *h, const float *D, const int64_t *n_samples, int32_t n_clips, float *y) {
-    try {
-    if (!h) return AEGIS_ERR_INVALID;
-    std::lock_guard<std::mutex> lock(h->mu);
+    ENTRY(h)
     int rc = stft_geometry(h, "istft: ");
     if (rc != AEGIS_OK) return rc;
     if (n_clips < 0 || (n_clips > 0 && (!D || !n_samples))) { h->err = "istft: null argument"; return AEGIS_ERR_INVALID; }
@@ -312,31 +285,26 @@ int aegis_istft(aegis_handle *h, const float *D, const int64_t *n_samples, int32
         next_pass(foff, n_samples, n_clips, c0, cap, P);
         const size_t Fg = (size_t)P.fo[(size_t)P.n];
         StreamScope scope(h);
-        if ((rc = upload_pass(h, P, nullptr, n_samples)) != AEGIS_OK) return rc;
+        if ((rc = upload_pass(h, P, nullptr)) != AEGIS_OK) return rc;
         ENSURE(h, hp_D, Fg * 1025 * 8); ENSURE(h, hp_fa, Fg * 2048 * 8);
         HIPCHK(h, hipMemcpyAsync(h->hp_D.p, D + (size_t)foff[(size_t)c0] * 1025 * 2, Fg * 1025 * 8, hipMemcpyHostToDevice, s));
-        begin_event(h, "hpss_synth", s);
-        launch_hpss_synth(true, nullptr, P.d_so, P.d_fo, P.d_po, P.n, P.po[(size_t)P.n], h->tab.hop, h->dt.hann, h->dt.twiddle,
-                          h->hp_D.as<const float>(), nullptr, nullptr, h->hp_fa.as<double>(), nullptr, s);
-        HIPCHK(h, hipGetLastError());
-        rc = gather_pass(h, P, sample0, y, nullptr);
-        end_event(h, s);
+        TIMED(h, "hpss_synth", s,                                  // one name over the synthesis and the gather
+              launch_hpss_synth(true, nullptr, P.d_so, P.d_fo, P.d_po, P.n, P.po.back(), h->tab.hop, h->dt.hann, h->dt.twiddle,
+                                h->hp_D.as<const float>(), nullptr, nullptr, h->hp_fa.as<double>(), nullptr, s);
+              rc = gather_pass(h, P, sample0, y, nullptr));
         if (rc != AEGIS_OK) return rc;
-        if ((rc = scope.finish()) != AEGIS_OK) return rc;
-        for (const auto &kv : h->last_ms) ms[kv.first] += kv.second;
+        if ((rc = finish_pass(h, scope, ms)) != AEGIS_OK) return rc;
         sample0 += P.so[(size_t)P.n];
         c0 += P.n;
     }
     h->last_ms = ms;
     return AEGIS_OK;
-    } catch (...) { return abi_fail(h); }
+    ENTRY_END(h)
 }
 
 int aegis_hpss(aegis_handle *h, const float *const *pcm, const int64_t *n_samples, int32_t n_clips, const aegis_hpss_params *p,
                float *y_harm, float *y_perc) {
-    try {
-    if (!h) return AEGIS_ERR_INVALID;
-    std::lock_guard<std::mutex> lock(h->mu);
+    ENTRY(h)
     HpssParams o;
     int rc = hpss_request(h, p, o);
     if (rc != AEGIS_OK) return rc;
@@ -364,53 +332,35 @@ int aegis_hpss(aegis_handle *h, const float *const *pcm, const int64_t *n_sample
         int32_t max_out = 0;
         for (int32_t i = 0; i < P.n; ++i) {
             const int32_t Fc = (int32_t)(P.fo[(size_t)i + 1] - P.fo[(size_t)i]);
-            segs[(size_t)i] = HpssSeg{P.fo[(size_t)i] * 1025, Fc, 0, Fc, 0, Fc, P.c0 + i};
+            segs[(size_t)i] = HpssSeg{P.fo[(size_t)i] * 1025, Fc, 0, Fc, 0, Fc, P.clip[(size_t)i]};
             max_out = std::max(max_out, Fc);
         }
         StreamScope scope(h);
-        if ((rc = upload_pass(h, P, pcm, n_samples)) != AEGIS_OK) return rc;
+        if ((rc = upload_pass(h, P, pcm)) != AEGIS_OK) return rc;
         ENSURE(h, hp_in, img); ENSURE(h, hp_harm, img); ENSURE(h, hp_perc, img); ENSURE(h, hp_mh, img); ENSURE(h, hp_mp, img);
-        ENSURE(h, hp_fa, Fg * 2048 * 8); ENSURE(h, hp_fb, Fg * 2048 * 8); ENSURE(h, hp_segs, segs.size() * sizeof(HpssSeg));
-        HIPCHK(h, upload(h->hp_segs, segs.data(), segs.size() * sizeof(HpssSeg), s));
-        const HpssSeg *d_segs = h->hp_segs.as<const HpssSeg>();
-        begin_event(h, "hpss_stft", s);
-        launch_hpss_stft(h->hp_pcm.as<const float>(), P.d_so, P.d_fo, P.d_po, nullptr, P.n, P.po[(size_t)P.n], h->tab.hop, h->dt.hann,
-                         h->dt.twiddle, nullptr, h->hp_in.as<float>(), s);
-        end_event(h, s);
-        HIPCHK(h, hipGetLastError());
-        begin_event(h, "hpss_median_t", s);
-        launch_hpss_median_t(h->hp_in.as<const float>(), d_segs, P.n, max_out, 1025, o.win_harm, h->hp_harm.as<float>(), s);
-        end_event(h, s);
-        HIPCHK(h, hipGetLastError());
-        begin_event(h, "hpss_median_f", s);
-        launch_hpss_median_f(h->hp_in.as<const float>(), h->hp_harm.as<const float>(), d_segs, P.n, max_out, 1025, o, h->hp_perc.as<float>(),
-                             h->hp_mh.as<float>(), h->hp_mp.as<float>(), s);
-        end_event(h, s);
-        HIPCHK(h, hipGetLastError());
-        begin_event(h, "hpss_synth", s);
-        launch_hpss_synth(false, h->hp_pcm.as<const float>(), P.d_so, P.d_fo, P.d_po, P.n, P.po[(size_t)P.n], h->tab.hop, h->dt.hann,
-                          h->dt.twiddle, nullptr, h->hp_mh.as<const float>(), h->hp_mp.as<const float>(), h->hp_fa.as<double>(),
-                          h->hp_fb.as<double>(), s);
-        HIPCHK(h, hipGetLastError());
-        rc = gather_pass(h, P, sample0, y_harm, y_perc ? y_perc : nullptr);
-        end_event(h, s);
+        ENSURE(h, hp_fa, Fg * 2048 * 8); ENSURE(h, hp_fb, Fg * 2048 * 8);
+        PUT(h, hp_segs, segs, s);
+        TIMED(h, "hpss_stft", s, launch_hpss_stft(h->hp_pcm.as<const float>(), P.d_so, P.d_fo, P.d_po, nullptr, P.n, P.po.back(), h->tab.hop, h->dt.hann,
+                                                  h->dt.twiddle, nullptr, h->hp_in.as<float>(), s));
+        if ((rc = hpss_medians(h, P.n, max_out, 1025, o)) != AEGIS_OK) return rc;
+        TIMED(h, "hpss_synth", s,                                  // one name over the synthesis and the gather
+              launch_hpss_synth(false, h->hp_pcm.as<const float>(), P.d_so, P.d_fo, P.d_po, P.n, P.po.back(), h->tab.hop, h->dt.hann, h->dt.twiddle,
+                                nullptr, h->hp_mh.as<const float>(), h->hp_mp.as<const float>(), h->hp_fa.as<double>(), h->hp_fb.as<double>(), s);
+              rc = gather_pass(h, P, sample0, y_harm, y_perc));
         if (rc != AEGIS_OK) return rc;
-        if ((rc = scope.finish()) != AEGIS_OK) return rc;
-        for (const auto &kv : h->last_ms) ms[kv.first] += kv.second;
+        if ((rc = finish_pass(h, scope, ms)) != AEGIS_OK) return rc;
         if ((rc = pass_verdict(h, P)) != AEGIS_OK) return rc;
         sample0 += P.so[(size_t)P.n];
         c0 += P.n;
     }
     h->last_ms = ms;
     return AEGIS_OK;
-    } catch (...) { return abi_fail(h); }
+    ENTRY_END(h)
 }
 
 int aegis_hpss_masks(aegis_handle *h, const float *S, const int64_t *n_frames, int32_t n_clips, int32_t n_bins, const aegis_hpss_params *p,
                      float *harm, float *perc, float *mask_harm, float *mask_perc) {
-    try {
-    if (!h) return AEGIS_ERR_INVALID;
-    std::lock_guard<std::mutex> lock(h->mu);
+    ENTRY(h)
     HpssParams o;
     int rc = hpss_request(h, p, o);
     if (rc != AEGIS_OK) return rc;
@@ -442,7 +392,7 @@ int aegis_hpss_masks(aegis_handle *h, const float *S, const int64_t *n_frames, i
         return AEGIS_ERR_INVALID;
     }
     return AEGIS_OK;
-    } catch (...) { return abi_fail(h); }
+    ENTRY_END(h)
 }
 
 }  // extern "C"

@@ -1,6 +1,11 @@
 // What the host-side files of libaegis_hip.so share: the handle, the stream, owned device buffers and events, the error
 // macros, the call scope (StreamScope) that drains the stream on every way out of an entry.  Internal: not installed, not
 // included by include/aegis_hip.h.
+// An exported entry that locks its handle is ENTRY(h) ... ENTRY_END(h): the frame answers a null handle, takes the lock
+// in front of the body's first write to h->err and maps an exception to a code.  A launch that is timed under a
+// profiling name is TIMED(h, "name", s, launch): the event pair, the launch, the error check.  A host vector goes to
+// its buffer with PUT, n elements come back with FETCH.  Clips of samples are walked by clip_samples and uploaded by
+// upload_clips (aegis_onset.hip, next to the frame walks).
 //   aegis_api.hip     the batch pipeline (plan input, workspaces, analyze_device_locked, recovery, the analyze entries)
 //   aegis_handle.hip  create / destroy, profiling, the call scope's drain, tables, parameters, aegis_debug_plan / aegis_debug_fetch
 //   aegis_stream.hip  aegis_stream_* (graph capture, commit delivery), aegis_debug_stream_set_observations / _stream_fetch
@@ -17,7 +22,7 @@
 //                     salience.hip, the CQT in front of it through aegis_cqt.hip's cqt_host_locked)
 //   aegis_onset.hip   aegis_onset_strength, aegis_onset_detect, aegis_analyze_onsets (onset envelope and onset picking;
 //                     kernels in onset.hip, the mel stage in front of them through aegis_api.hip's mel_host_locked); the
-//                     offsets walks every per-clip entry shares (frame_offsets, clip_frames)
+//                     offsets walks every per-clip entry shares (frame_offsets, clip_frames, clip_samples) and upload_clips
 //   aegis_beat.hip    aegis_tempo, aegis_beat_track, aegis_beat_tables, aegis_analyze_beats (tempogram mean, tempo, beat
 //                     tracker; kernels in beat.hip, the mel stage and aegis_onset.hip's envelope stage in front of them)
 //   aegis_hpss.hip    aegis_stft, aegis_istft, aegis_hpss (spectrogram, resynthesis, the whole separation), aegis_hpss_masks (running medians along time and bins and the soft masks of median-filter
@@ -229,6 +234,22 @@ struct aegis_stream {
         const int rc__ = aegis::ensure(h, (h)->buf, std::max<size_t>((size_t)(bytes), 8));                 \
         if (rc__ != AEGIS_OK) return rc__;                                                                  \
     } while (0)
+// the whole host vector v into h->buf (sized for it) on stream s; v outlives the caller's StreamScope
+#define PUT(h, buf, v, s)                                                                                   \
+    do {                                                                                                    \
+        ENSURE(h, buf, (v).size() * sizeof((v)[0]));                                                        \
+        HIPCHK(h, aegis::upload((h)->buf, (v).data(), (v).size() * sizeof((v)[0]), s));                     \
+    } while (0)
+// n elements of the device array src into the host array dst (whose element type counts the bytes) on stream s
+#define FETCH(h, dst, src, n, s) HIPCHK(h, hipMemcpyAsync(dst, src, (size_t)(n) * sizeof(*(dst)), hipMemcpyDeviceToHost, s))
+// A launch under a profiling name: the event pair around it on stream s, then the launch's error check.
+#define TIMED(h, name, s, ...)                                                                              \
+    do {                                                                                                    \
+        aegis::begin_event(h, name, s);                                                                     \
+        __VA_ARGS__;                                                                                        \
+        aegis::end_event(h, s);                                                                             \
+        HIPCHK(h, hipGetLastError());                                                                       \
+    } while (0)
 // what this header adds to the library without adding to its dynamic symbol table
 #define AEGIS_LOCAL __attribute__((visibility("hidden")))
 #define DEVICE_ONLY(h) \
@@ -250,6 +271,14 @@ void destroy_now(aegis_handle *h) noexcept;
 // Nothing is thrown across the C boundary (include/aegis_hip.h): every exported entry runs its body inside
 // try { ... } catch (...) { return abi_fail(h); }, which maps the in-flight exception to a return code.
 int abi_fail(aegis_handle *h) noexcept;
+// The frame of every exported entry that locks its handle, ENTRY(h) ... ENTRY_END(h) around its body: a null handle is
+// AEGIS_ERR_INVALID, the body runs with h->mu held (a handle is shared between threads: nothing writes h->err in front
+// of the lock) and what it throws becomes abi_fail's code.  Every path of the body returns.
+#define ENTRY(h)                                                                                            \
+    if (!(h)) return AEGIS_ERR_INVALID;                                                                     \
+    try {                                                                                                   \
+        std::lock_guard<std::mutex> entry_lock__((h)->mu);
+#define ENTRY_END(h) } catch (...) { return aegis::abi_fail(h); }
 // The domain rules of injected observation rows (aegis_debug_set_observations and aegis_debug_stream_set_observations):
 // AEGIS_OK, or AEGIS_ERR_INVALID with a message that names the frame.  Host arithmetic only.
 AEGIS_LOCAL int check_observation_rows(aegis_handle *h, const double *logobs, const double *logunv, int64_t F);
@@ -340,6 +369,12 @@ AEGIS_LOCAL int frame_offsets(aegis_handle *h, const char *clip_pre, const char 
 // one prefix for both messages.
 AEGIS_LOCAL int clip_frames(aegis_handle *h, const char *pre, const float *const *pcm, const int64_t *n_samples, int32_t n_clips,
                 std::vector<int64_t> &foff, int64_t &maxF);
+// The sample walk: clips [c0, c1) of pcm[] / n_samples[] -> soff [c1 - c0 + 1], or AEGIS_ERR_INVALID with pre + "bad clip
+// <c>" (a negative length, samples without a pointer).
+AEGIS_LOCAL int clip_samples(aegis_handle *h, const char *pre, const float *const *pcm, const int64_t *n_samples, int32_t c0, int32_t c1,
+                 std::vector<int64_t> &soff);
+// ... and the clips that have samples into b (sized here, for one sample at least) at those offsets, on stream s
+AEGIS_LOCAL int upload_clips(aegis_handle *h, DevBuf &b, const float *const *pcm, int32_t c0, const std::vector<int64_t> &soff, hipStream_t s);
 struct OnsetParams;
 // the onset request with its defaults filled in, or AEGIS_ERR_INVALID with a message
 AEGIS_LOCAL int onset_request(aegis_handle *h, const aegis_onset_params *p, OnsetParams &o);

@@ -17,8 +17,8 @@ bool params_ok(const aegis_adsr_params &p) { return adsr_params_ok(p, 86400e3); 
 // ---- aegis_note_fit ---------------------------------------------------------------------------------------------------
 bool validate_fit(aegis_handle *h, int32_t sr, int32_t n_clips, const float *const *audio, const int64_t *n_samples, int32_t n_notes,
                   const aegis_fit_note *notes, const aegis_adsr_params *cands, const int64_t *cand_off) {
-    for (int32_t c = 0; c < n_clips; ++c)
-        if (n_samples[c] < 0 || (n_samples[c] > 0 && !audio[c])) { h->err = "bad clip " + std::to_string(c); return false; }
+    std::vector<int64_t> soff;
+    if (clip_samples(h, "", audio, n_samples, 0, n_clips, soff) != AEGIS_OK) return false;
     if (n_notes > 0 && cand_off[0] != 0) { h->err = "cand_off must start at 0"; return false; }
     for (int32_t k = 0; k < n_notes; ++k) {
         const aegis_fit_note &nt = notes[k];
@@ -78,8 +78,7 @@ int run_fit(aegis_handle *h, int32_t sr, FitBatch &B) {
     const bool store = h->notefit_store && !B.oscs.empty();
     size_t audio_elems = B.pcm.size();
     if (store) for (const AdsrNote &c : B.cd) audio_elems += c.osc < 0 ? 0 : (size_t)c.n_cut;
-    ENSURE(h, nf_audio, audio_elems * 8); ENSURE(h, nf_oscs, B.oscs.size() * sizeof(AdsrOsc)); ENSURE(h, nf_cands, B.cd.size() * sizeof(AdsrNote));
-    ENSURE(h, nf_notes, B.fn.size() * sizeof(FitNote)); ENSURE(h, nf_boff, B.block_off.size() * 8); ENSURE(h, nf_peak, B.oscs.size() * 8);
+    ENSURE(h, nf_audio, audio_elems * 8); ENSURE(h, nf_peak, B.oscs.size() * 8);
     ENSURE(h, nf_cnum, (size_t)B.n_feat * 8); ENSURE(h, nf_cden, (size_t)B.n_feat * 8); ENSURE(h, nf_zc, (size_t)B.n_feat * 4); ENSURE(h, nf_rms, (size_t)B.n_rms * 8);
     ENSURE(h, nf_out, B.cd.size() * 32); ENSURE(h, nf_best, B.fn.size() * 4);
     std::vector<int64_t> sig_off;                     // (store mode's tables: host arrays, so in front of the scope)
@@ -88,10 +87,7 @@ int run_fit(aegis_handle *h, int32_t sr, FitBatch &B) {
     B.best.resize(B.fn.size());
     StreamScope scope(h);
     HIPCHK(h, upload(h->nf_audio, B.pcm.data(), B.pcm.size() * 8, s));
-    HIPCHK(h, upload(h->nf_oscs, B.oscs.data(), B.oscs.size() * sizeof(AdsrOsc), s));
-    HIPCHK(h, upload(h->nf_cands, B.cd.data(), B.cd.size() * sizeof(AdsrNote), s));
-    HIPCHK(h, upload(h->nf_notes, B.fn.data(), B.fn.size() * sizeof(FitNote), s));
-    HIPCHK(h, upload(h->nf_boff, B.block_off.data(), B.block_off.size() * 8, s));
+    PUT(h, nf_oscs, B.oscs, s); PUT(h, nf_cands, B.cd, s); PUT(h, nf_notes, B.fn, s); PUT(h, nf_boff, B.block_off, s);
     FitArgs a{};
     a.audio = h->nf_audio.as<const double>();
     a.oscs = h->nf_oscs.as<const AdsrOsc>();
@@ -106,9 +102,7 @@ int run_fit(aegis_handle *h, int32_t sr, FitBatch &B) {
     a.cnum = h->nf_cnum.as<double>(); a.cden = h->nf_cden.as<double>();
     a.zc = h->nf_zc.as<int32_t>(); a.rms = h->nf_rms.as<double>();
     a.out = h->nf_out.as<double>(); a.best = h->nf_best.as<int32_t>();
-    begin_event(h, "notefit_peak", s);
-    launch_adsr_peak(a.oscs, a.osc_peak, a.n_oscs, s);
-    end_event(h, s);
+    TIMED(h, "notefit_peak", s, launch_adsr_peak(a.oscs, a.osc_peak, a.n_oscs, s));
     // Store mode (AEGIS_NOTEFIT_STORE=1, measured against the default in DESIGN.md 3.14): every synthesised candidate is
     // rendered once behind the slices, and the frames read it as they read a given signal: the same values, so the same bits.
     if (store) {
@@ -121,24 +115,15 @@ int run_fit(aegis_handle *h, int32_t sr, FitBatch &B) {
             stored[c].start = at;
             at += B.cd[c].n_cut;
         }
-        ENSURE(h, nf_sigoff, sig_off.size() * 8); ENSURE(h, nf_cands2, stored.size() * sizeof(AdsrNote));
-        HIPCHK(h, upload(h->nf_sigoff, sig_off.data(), sig_off.size() * 8, s));
-        HIPCHK(h, upload(h->nf_cands2, stored.data(), stored.size() * sizeof(AdsrNote), s));
-        begin_event(h, "notefit_store", s);
-        launch_adsr_render(a.oscs, a.cands, a.osc_peak, h->nf_sigoff.as<const int64_t>(), h->nf_audio.as<double>(),
-                              a.n_cands, s);
-        end_event(h, s);
+        PUT(h, nf_sigoff, sig_off, s); PUT(h, nf_cands2, stored, s);
+        TIMED(h, "notefit_store", s, launch_adsr_render(a.oscs, a.cands, a.osc_peak, h->nf_sigoff.as<const int64_t>(), h->nf_audio.as<double>(),
+                                                        a.n_cands, s));
         a.cands = h->nf_cands2.as<const AdsrNote>();
     }
-    begin_event(h, "notefit_feat", s);
-    launch_notefit_feat(a, s);
-    end_event(h, s);
-    begin_event(h, "notefit_score", s);
-    launch_notefit_score(a, s);
-    end_event(h, s);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(B.out.data(), a.out, B.out.size() * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipMemcpyAsync(B.best.data(), a.best, B.best.size() * 4, hipMemcpyDeviceToHost, s));
+    TIMED(h, "notefit_feat", s, launch_notefit_feat(a, s));
+    TIMED(h, "notefit_score", s, launch_notefit_score(a, s));
+    FETCH(h, B.out.data(), a.out, B.out.size(), s);
+    FETCH(h, B.best.data(), a.best, B.best.size(), s);
     return scope.finish();
 }
 
@@ -228,9 +213,7 @@ extern "C" {
 int aegis_note_fit(aegis_handle *h, int32_t sample_rate, int32_t n_clips, const float *const *audio, const int64_t *n_samples,
                    int32_t n_notes, const aegis_fit_note *notes, const aegis_adsr_params *cands, const int64_t *cand_off,
                    double *score, double *env, double *centroid, double *zcr, int32_t *best) {
-    try {
-    if (!h) return AEGIS_ERR_INVALID;
-    std::lock_guard<std::mutex> lock(h->mu);
+    ENTRY(h)
     if (sample_rate <= 0 || n_clips < 0 || n_notes < 0 || (n_clips > 0 && (!audio || !n_samples)) ||
         (n_notes > 0 && (!notes || !cand_off || !best))) {
         h->err = "bad argument"; return AEGIS_ERR_INVALID;
@@ -246,14 +229,12 @@ int aegis_note_fit(aegis_handle *h, int32_t sample_rate, int32_t n_clips, const 
     return run_halving(h, n_notes, [&](int32_t k0, int32_t k1) {
         return fit_group(h, sample_rate, k0, k1, audio, notes, cands, cand_off, score, env, centroid, zcr, best);
     });
-    } catch (...) { return abi_fail(h); }
+    ENTRY_END(h)
 }
 
 int aegis_compare_audio(aegis_handle *h, int32_t sample_rate, int32_t n_pairs, const double *const *orig, const int64_t *n_orig,
                         const double *const *synth, const int64_t *n_synth, double *out) {
-    try {
-    if (!h) return AEGIS_ERR_INVALID;
-    std::lock_guard<std::mutex> lock(h->mu);
+    ENTRY(h)
     if (sample_rate <= 0 || n_pairs < 0 || (n_pairs > 0 && (!orig || !n_orig || !synth || !n_synth || !out))) {
         h->err = "bad argument"; return AEGIS_ERR_INVALID;
     }
@@ -271,14 +252,12 @@ int aegis_compare_audio(aegis_handle *h, int32_t sample_rate, int32_t n_pairs, c
     return run_halving(h, n_pairs, [&](int32_t k0, int32_t k1) {
         return compare_group(h, sample_rate, k0, k1, orig, n_orig, synth, n_synth, out);
     });
-    } catch (...) { return abi_fail(h); }
+    ENTRY_END(h)
 }
 
 int64_t aegis_synth_one_note(aegis_handle *h, int32_t sample_rate, double freq, double duration, int32_t velocity,
                          const aegis_adsr_params *params, double *out, int64_t cap) {
-    try {
-    if (!h) return AEGIS_ERR_INVALID;
-    std::lock_guard<std::mutex> lock(h->mu);
+    ENTRY(h)
     if (sample_rate <= 0 || !params || cap < 0) { h->err = "bad argument"; return AEGIS_ERR_INVALID; }
     if (!params_ok(*params) || !adsr_finite_nonneg(freq) || freq > 1e9 || !adsr_finite_nonneg(duration) || duration > 86400.0) {
         h->err = "bad ADSR parameters, frequency or duration"; return AEGIS_ERR_INVALID;
@@ -302,10 +281,10 @@ int64_t aegis_synth_one_note(aegis_handle *h, int32_t sample_rate, double freq, 
                           h->nf_peak.as<const double>(), h->nf_boff.as<const int64_t>(),
                           h->nf_sig.as<double>(), 1, s);
     HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(out, h->nf_sig.p, (size_t)o.n * 8, hipMemcpyDeviceToHost, s));
+    FETCH(h, out, h->nf_sig.p, o.n, s);
     const int rc = scope.finish();
     return rc != AEGIS_OK ? rc : o.n;
-    } catch (...) { return abi_fail(h); }
+    ENTRY_END(h)
 }
 
 }  // extern "C"

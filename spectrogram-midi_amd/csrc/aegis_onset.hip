@@ -23,12 +23,29 @@ int aegis::frame_offsets(aegis_handle *h, const char *clip_pre, const char *call
 
 int aegis::clip_frames(aegis_handle *h, const char *pre, const float *const *pcm, const int64_t *n_samples, int32_t n_clips,
                        std::vector<int64_t> &foff, int64_t &maxF) {
-    std::vector<int64_t> nf((size_t)std::max(n_clips, 0));
-    for (int32_t c = 0; c < n_clips; ++c) {
-        if (n_samples[c] < 0 || (n_samples[c] > 0 && !pcm[c])) { h->err = pre + ("bad clip " + std::to_string(c)); return AEGIS_ERR_INVALID; }
-        nf[(size_t)c] = 1 + n_samples[c] / h->tab.hop;
-    }
+    std::vector<int64_t> nf;
+    const int rc = clip_samples(h, pre, pcm, n_samples, 0, n_clips, nf);
+    if (rc != AEGIS_OK) return rc;
+    for (int32_t c = 0; c < n_clips; ++c) nf[(size_t)c] = 1 + n_samples[c] / h->tab.hop;
     return frame_offsets(h, pre, pre, nf.data(), n_clips, foff, maxF);
+}
+
+int aegis::clip_samples(aegis_handle *h, const char *pre, const float *const *pcm, const int64_t *n_samples, int32_t c0, int32_t c1,
+                        std::vector<int64_t> &soff) {
+    soff.assign((size_t)std::max(c1 - c0, 0) + 1, 0);
+    for (int32_t c = c0; c < c1; ++c) {
+        if (n_samples[c] < 0 || (n_samples[c] > 0 && !pcm[c])) { h->err = pre + ("bad clip " + std::to_string(c)); return AEGIS_ERR_INVALID; }
+        soff[(size_t)(c - c0) + 1] = soff[(size_t)(c - c0)] + n_samples[c];
+    }
+    return AEGIS_OK;
+}
+
+int aegis::upload_clips(aegis_handle *h, DevBuf &b, const float *const *pcm, int32_t c0, const std::vector<int64_t> &soff, hipStream_t s) {
+    const int rc = ensure(h, b, std::max<size_t>((size_t)soff.back() * 4, 8));
+    if (rc != AEGIS_OK) return rc;
+    for (size_t i = 0; i + 1 < soff.size(); ++i)
+        if (soff[i + 1] > soff[i]) HIPCHK(h, hipMemcpyAsync(b.as<float>() + soff[i], pcm[c0 + (int32_t)i], (size_t)(soff[i + 1] - soff[i]) * 4, hipMemcpyHostToDevice, s));
+    return AEGIS_OK;
 }
 
 int aegis::onset_request(aegis_handle *h, const aegis_onset_params *p, OnsetParams &o) {
@@ -44,10 +61,7 @@ int aegis::onset_env_locked(aegis_handle *h, const float *d_img, const int64_t *
                             int32_t n_mels, const OnsetParams &o) {
     hipStream_t s = h->stream;
     ENSURE(h, on_env, (size_t)F * 4);
-    begin_event(h, "onset_env", s);
-    launch_onset_env(d_img, d_foff, n_clips, maxF, n_mels, o, h->on_env.as<float>(), s);
-    end_event(h, s);
-    HIPCHK(h, hipGetLastError());
+    TIMED(h, "onset_env", s, launch_onset_env(d_img, d_foff, n_clips, maxF, n_mels, o, h->on_env.as<float>(), s));
     return AEGIS_OK;
 }
 
@@ -66,14 +80,11 @@ int ons_pick_locked(aegis_handle *h, const float *d_env, const float *d_energy, 
     hipStream_t s = h->stream;
     ENSURE(h, on_x, (size_t)F * 4); ENSURE(h, on_mask, (size_t)F); ENSURE(h, on_count, (size_t)n_clips * 8);
     if (onset_back) ENSURE(h, on_back, (size_t)F * 4);
-    begin_event(h, "onset_pick", s);
-    launch_onset_pick(d_env, d_energy, d_foff, n_clips, o, h->on_x.as<float>(), h->on_mask.as<uint8_t>(),
-                      onset_back ? h->on_back.as<int32_t>() : nullptr, h->on_count.as<int64_t>(), s);
-    end_event(h, s);
-    HIPCHK(h, hipGetLastError());
-    if (F) HIPCHK(h, hipMemcpyAsync(onset_mask, h->on_mask.p, (size_t)F, hipMemcpyDeviceToHost, s));
-    if (F && onset_back) HIPCHK(h, hipMemcpyAsync(onset_back, h->on_back.p, (size_t)F * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipMemcpyAsync(n_onsets, h->on_count.p, (size_t)n_clips * 8, hipMemcpyDeviceToHost, s));
+    TIMED(h, "onset_pick", s, launch_onset_pick(d_env, d_energy, d_foff, n_clips, o, h->on_x.as<float>(), h->on_mask.as<uint8_t>(),
+                                                onset_back ? h->on_back.as<int32_t>() : nullptr, h->on_count.as<int64_t>(), s));
+    if (F) FETCH(h, onset_mask, h->on_mask.p, F, s);
+    if (F && onset_back) FETCH(h, onset_back, h->on_back.p, F, s);
+    FETCH(h, n_onsets, h->on_count.p, n_clips, s);
     return AEGIS_OK;
 }
 
@@ -83,9 +94,7 @@ extern "C" {
 
 int aegis_onset_strength(aegis_handle *h, const float *S_dB, const int64_t *n_frames, int32_t n_clips, int32_t n_mels,
                          const aegis_onset_params *p, float *env_out) {
-    try {
-    if (!h) return AEGIS_ERR_INVALID;
-    std::lock_guard<std::mutex> lock(h->mu);
+    ENTRY(h)
     OnsetParams o;
     int rc = onset_request(h, p, o);
     if (rc != AEGIS_OK) return rc;
@@ -99,22 +108,20 @@ int aegis_onset_strength(aegis_handle *h, const float *S_dB, const int64_t *n_fr
     if (F == 0) return AEGIS_OK;
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
-    ENSURE(h, on_img, (size_t)F * n_mels * 4); ENSURE(h, on_foff, foff.size() * 8);
+    ENSURE(h, on_img, (size_t)F * n_mels * 4);
     drop_events(h);
     StreamScope scope(h);
     HIPCHK(h, upload(h->on_img, S_dB, (size_t)F * n_mels * 4, s));
-    HIPCHK(h, upload(h->on_foff, foff.data(), foff.size() * 8, s));
+    PUT(h, on_foff, foff, s);
     if ((rc = onset_env_locked(h, h->on_img.as<const float>(), h->on_foff.as<const int64_t>(), n_clips, F, maxF, n_mels, o)) != AEGIS_OK) return rc;
-    HIPCHK(h, hipMemcpyAsync(env_out, h->on_env.p, (size_t)F * 4, hipMemcpyDeviceToHost, s));
+    FETCH(h, env_out, h->on_env.p, F, s);
     return scope.finish();
-    } catch (...) { return abi_fail(h); }
+    ENTRY_END(h)
 }
 
 int aegis_onset_detect(aegis_handle *h, const float *env, const float *energy, const int64_t *n_frames, int32_t n_clips,
                        const aegis_onset_params *p, uint8_t *onset_mask, int32_t *onset_back, int64_t *n_onsets) {
-    try {
-    if (!h) return AEGIS_ERR_INVALID;
-    std::lock_guard<std::mutex> lock(h->mu);
+    ENTRY(h)
     OnsetParams o;
     int rc = onset_request(h, p, o);
     if (rc != AEGIS_OK) return rc;
@@ -127,24 +134,22 @@ int aegis_onset_detect(aegis_handle *h, const float *env, const float *energy, c
     if (n_clips == 0) return AEGIS_OK;
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
-    ENSURE(h, on_env, (size_t)F * 4); ENSURE(h, on_foff, foff.size() * 8);
+    ENSURE(h, on_env, (size_t)F * 4);
     if (energy) ENSURE(h, on_energy, (size_t)F * 4);
     drop_events(h);
     StreamScope scope(h);
     HIPCHK(h, upload(h->on_env, env, (size_t)F * 4, s));
     if (energy) HIPCHK(h, upload(h->on_energy, energy, (size_t)F * 4, s));
-    HIPCHK(h, upload(h->on_foff, foff.data(), foff.size() * 8, s));
+    PUT(h, on_foff, foff, s);
     rc = ons_pick_locked(h, h->on_env.as<const float>(), energy ? h->on_energy.as<const float>() : nullptr, h->on_foff.as<const int64_t>(),
                          n_clips, F, o, onset_mask, onset_back, n_onsets);
     return rc != AEGIS_OK ? rc : scope.finish();
-    } catch (...) { return abi_fail(h); }
+    ENTRY_END(h)
 }
 
 int aegis_analyze_onsets(aegis_handle *h, const float *const *pcm, const int64_t *n_samples, int32_t n_clips,
                          const aegis_onset_params *p, float *env_out, uint8_t *onset_mask, int32_t *onset_back, int64_t *n_onsets) {
-    try {
-    if (!h) return AEGIS_ERR_INVALID;
-    std::lock_guard<std::mutex> lock(h->mu);
+    ENTRY(h)
     OnsetParams o;
     int rc = onset_request(h, p, o);
     if (rc != AEGIS_OK) return rc;
@@ -164,15 +169,14 @@ int aegis_analyze_onsets(aegis_handle *h, const float *const *pcm, const int64_t
     StreamScope scope(h);                                       // the feed's copies and the pipeline read pcm, off and foff
     if ((rc = mel_host_locked(h, pcm, n_samples, n_clips, off, foff)) != AEGIS_OK) return rc;
     const int64_t F = foff[(size_t)n_clips];
-    ENSURE(h, on_foff, foff.size() * 8);
-    HIPCHK(h, upload(h->on_foff, foff.data(), foff.size() * 8, s));
+    PUT(h, on_foff, foff, s);
     const int64_t *d_foff = h->on_foff.as<const int64_t>();
     if ((rc = onset_env_locked(h, h->io_sdb.as<const float>(), d_foff, n_clips, F, maxF, h->tab.n_mels, o)) != AEGIS_OK) return rc;
-    if (env_out) HIPCHK(h, hipMemcpyAsync(env_out, h->on_env.p, (size_t)F * 4, hipMemcpyDeviceToHost, s));
+    if (env_out) FETCH(h, env_out, h->on_env.p, F, s);
     if (onset_mask && (rc = ons_pick_locked(h, h->on_env.as<const float>(), nullptr, d_foff, n_clips, F, o, onset_mask, onset_back, n_onsets)) != AEGIS_OK)
         return rc;
     return scope.finish();
-    } catch (...) { return abi_fail(h); }
+    ENTRY_END(h)
 }
 
 }  // extern "C"

@@ -32,16 +32,13 @@ int sal_run_locked(aegis_handle *h, const float *d_mag, const int64_t *d_foff, i
     const size_t img = (size_t)F * fp.n_bins * 4, slots = (size_t)F * fp.top_k * 4;
     if (sal_out) ENSURE(h, sl_img, img);
     ENSURE(h, sl_bin, slots); ENSURE(h, sl_sal, slots); ENSURE(h, sl_shift, slots);
-    begin_event(h, "salience", s);
-    launch_salience(d_mag, d_foff, n_clips, maxF, T, fp, sal_out ? h->sl_img.as<float>() : nullptr,
-                    h->sl_bin.as<int32_t>(), h->sl_sal.as<float>(), h->sl_shift.as<float>(), s);
-    end_event(h, s);
-    HIPCHK(h, hipGetLastError());
-    if (sal_out && img) HIPCHK(h, hipMemcpyAsync(sal_out, h->sl_img.p, img, hipMemcpyDeviceToHost, s));
+    TIMED(h, "salience", s, launch_salience(d_mag, d_foff, n_clips, maxF, T, fp, sal_out ? h->sl_img.as<float>() : nullptr,
+                                            h->sl_bin.as<int32_t>(), h->sl_sal.as<float>(), h->sl_shift.as<float>(), s));
+    if (sal_out && img) FETCH(h, sal_out, h->sl_img.p, img / 4, s);
     if (slots) {
-        HIPCHK(h, hipMemcpyAsync(cand_bin, h->sl_bin.p, slots, hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipMemcpyAsync(cand_sal, h->sl_sal.p, slots, hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipMemcpyAsync(cand_shift, h->sl_shift.p, slots, hipMemcpyDeviceToHost, s));
+        FETCH(h, cand_bin, h->sl_bin.p, slots / 4, s);
+        FETCH(h, cand_sal, h->sl_sal.p, slots / 4, s);
+        FETCH(h, cand_shift, h->sl_shift.p, slots / 4, s);
     }
     return AEGIS_OK;
 }
@@ -52,9 +49,7 @@ extern "C" {
 
 int aegis_salience(aegis_handle *h, const float *mag, const int64_t *n_frames, int32_t n_clips, int32_t n_bins, int32_t bins_per_octave,
                    const aegis_salience_params *p, float *sal_out, int32_t *cand_bin, float *cand_sal, float *cand_shift) {
-    try {
-    if (!h) return AEGIS_ERR_INVALID;
-    std::lock_guard<std::mutex> lock(h->mu);
+    ENTRY(h)
     if (n_clips < 0 || (n_clips > 0 && !n_frames)) { h->err = "null argument"; return AEGIS_ERR_INVALID; }
     SalTables T; SalFrameParams fp;
     int rc = sal_request(h, n_bins, bins_per_octave, p, cand_bin, cand_sal, cand_shift, T, fp);
@@ -68,23 +63,21 @@ int aegis_salience(aegis_handle *h, const float *mag, const int64_t *n_frames, i
     if (F == 0) return AEGIS_OK;
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
-    ENSURE(h, sl_mag, (size_t)F * n_bins * 4); ENSURE(h, sl_foff, foff.size() * 8);
+    ENSURE(h, sl_mag, (size_t)F * n_bins * 4);
     drop_events(h);
     StreamScope scope(h);
     HIPCHK(h, upload(h->sl_mag, mag, (size_t)F * n_bins * 4, s));
-    HIPCHK(h, upload(h->sl_foff, foff.data(), foff.size() * 8, s));
+    PUT(h, sl_foff, foff, s);
     rc = sal_run_locked(h, h->sl_mag.as<const float>(), h->sl_foff.as<const int64_t>(), n_clips, F, maxF, T, fp,
                         sal_out, cand_bin, cand_sal, cand_shift);
     return rc != AEGIS_OK ? rc : scope.finish();
-    } catch (...) { return abi_fail(h); }
+    ENTRY_END(h)
 }
 
 int aegis_cqt_salience(aegis_handle *h, const float *const *pcm, const int64_t *n_samples, int32_t n_clips, int32_t n_bins,
                        int32_t bins_per_octave, double fmin, double filter_scale, const aegis_salience_params *p, float *mag_out,
                        float *sal_out, int32_t *cand_bin, float *cand_sal, float *cand_shift) {
-    try {
-    if (!h) return AEGIS_ERR_INVALID;
-    std::lock_guard<std::mutex> lock(h->mu);
+    ENTRY(h)
     if (n_clips < 0 || (n_clips > 0 && (!pcm || !n_samples))) { h->err = "null argument"; return AEGIS_ERR_INVALID; }
     if (n_bins == 0) n_bins = 84;                               // aegis_cqt's defaults
     if (bins_per_octave == 0) bins_per_octave = 12;
@@ -100,11 +93,11 @@ int aegis_cqt_salience(aegis_handle *h, const float *const *pcm, const int64_t *
     StreamScope scope(h);
     if ((rc = cqt_host_locked(h, pcm, n_samples, n_clips, n_bins, bins_per_octave, fmin, filter_scale, 0, nullptr, &F)) != AEGIS_OK) return rc;
     if ((rc = clip_frames(h, "", pcm, n_samples, n_clips, foff, maxF)) != AEGIS_OK) return rc;
-    if (mag_out) HIPCHK(h, hipMemcpyAsync(mag_out, h->q_out.p, (size_t)F * n_bins * 4, hipMemcpyDeviceToHost, s));
+    if (mag_out) FETCH(h, mag_out, h->q_out.p, F * n_bins, s);
     rc = sal_run_locked(h, h->q_out.as<const float>(), h->q_foff.as<const int64_t>(), n_clips, F, maxF, T, fp,
                         sal_out, cand_bin, cand_sal, cand_shift);
     return rc != AEGIS_OK ? rc : scope.finish();
-    } catch (...) { return abi_fail(h); }
+    ENTRY_END(h)
 }
 
 }  // extern "C"

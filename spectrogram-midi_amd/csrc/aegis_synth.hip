@@ -93,20 +93,13 @@ int aegis::render_into(aegis_handle *h, const AdsrBatch &B, const char *const (&
     h->sy_last_total.clear(); h->sy_last_osc.clear();
     hipStream_t s = h->stream;
     const size_t nc = B.clip_off.size();
-    ENSURE(h, sy_oscs, B.oscs.size() * sizeof(AdsrOsc)); ENSURE(h, sy_notes, B.notes.size() * sizeof(AdsrNote));
-    ENSURE(h, sy_tiles, B.tiles.size() * sizeof(AdsrTile)); ENSURE(h, sy_tile_notes, B.tile_notes.size() * 4);
     ENSURE(h, sy_osc_peak, B.oscs.size() * 8); ENSURE(h, sy_clip_peak, nc * 8);
     ENSURE(h, sy_mix, (size_t)B.samples * 8); ENSURE(h, sy_out, (size_t)B.samples * 2);
-    HIPCHK(h, upload(h->sy_oscs, B.oscs.data(), B.oscs.size() * sizeof(AdsrOsc), s));
-    HIPCHK(h, upload(h->sy_notes, B.notes.data(), B.notes.size() * sizeof(AdsrNote), s));
-    HIPCHK(h, upload(h->sy_tiles, B.tiles.data(), B.tiles.size() * sizeof(AdsrTile), s));
-    HIPCHK(h, upload(h->sy_tile_notes, B.tile_notes.data(), B.tile_notes.size() * 4, s));
+    PUT(h, sy_oscs, B.oscs, s); PUT(h, sy_notes, B.notes, s); PUT(h, sy_tiles, B.tiles, s); PUT(h, sy_tile_notes, B.tile_notes, s);
     const AdsrBend *d_bends = nullptr;
     const AdsrSeg *d_segs = nullptr;
     if (!B.segs.empty()) {                                  // bent notes: their segment tables, and every oscillator's slice
-        ENSURE(h, sy_bends, B.bends.size() * sizeof(AdsrBend)); ENSURE(h, sy_segs, B.segs.size() * sizeof(AdsrSeg));
-        HIPCHK(h, upload(h->sy_bends, B.bends.data(), B.bends.size() * sizeof(AdsrBend), s));
-        HIPCHK(h, upload(h->sy_segs, B.segs.data(), B.segs.size() * sizeof(AdsrSeg), s));
+        PUT(h, sy_bends, B.bends, s); PUT(h, sy_segs, B.segs, s);
         d_bends = h->sy_bends.as<const AdsrBend>();
         d_segs = h->sy_segs.as<const AdsrSeg>();
     }
@@ -117,17 +110,10 @@ int aegis::render_into(aegis_handle *h, const AdsrBatch &B, const char *const (&
     double *d_peak = h->sy_osc_peak.as<double>(), *d_mix = h->sy_mix.as<double>();
     unsigned long long *d_cpeak = h->sy_clip_peak.as<unsigned long long>();
     int16_t *d_out = h->sy_out.as<int16_t>();
-    begin_event(h, labels[0], s);
-    launch_adsr_peak(d_oscs, d_peak, (int32_t)B.oscs.size(), s, d_bends, d_segs);
-    end_event(h, s);
-    begin_event(h, labels[1], s);
-    launch_adsr_mix(d_oscs, d_notes, d_peak, d_tiles, h->sy_tile_notes.as<const int32_t>(), d_mix, d_cpeak, (int32_t)B.tiles.size(), s,
-                    d_bends, d_segs);
-    end_event(h, s);
-    begin_event(h, labels[2], s);
-    launch_adsr_master(d_tiles, d_mix, d_cpeak, d_out, (int32_t)B.tiles.size(), s);
-    end_event(h, s);
-    HIPCHK(h, hipGetLastError());
+    TIMED(h, labels[0], s, launch_adsr_peak(d_oscs, d_peak, (int32_t)B.oscs.size(), s, d_bends, d_segs));
+    TIMED(h, labels[1], s, launch_adsr_mix(d_oscs, d_notes, d_peak, d_tiles, h->sy_tile_notes.as<const int32_t>(), d_mix, d_cpeak,
+                                           (int32_t)B.tiles.size(), s, d_bends, d_segs));
+    TIMED(h, labels[2], s, launch_adsr_master(d_tiles, d_mix, d_cpeak, d_out, (int32_t)B.tiles.size(), s));
     h->sy_last_total = B.clip_total;
     h->sy_last_osc.reserve(B.notes.size());
     for (const AdsrNote &nt : B.notes) h->sy_last_osc.push_back(nt.osc);
@@ -146,7 +132,7 @@ int render_group(aegis_handle *h, const AdsrBatch &B, int16_t *const *out, const
     const size_t nc = B.clip_off.size();
     const int16_t *d_out = h->sy_out.as<const int16_t>();
     for (size_t c = 0; c < nc; ++c)
-        if (B.clip_total[c] > 0) HIPCHK(h, hipMemcpyAsync(out[c], d_out + B.clip_off[c], (size_t)B.clip_total[c] * 2, hipMemcpyDeviceToHost, s));
+        if (B.clip_total[c] > 0) FETCH(h, out[c], d_out + B.clip_off[c], B.clip_total[c], s);
     return scope.finish();
 }
 
@@ -249,9 +235,7 @@ extern "C" {
 
 int64_t aegis_synth_parse_smf(aegis_handle *h, const uint8_t *smf, int64_t n_bytes, aegis_synth_note *notes, int64_t cap,
                               double *length_seconds) {
-    try {
-    if (!h) return AEGIS_ERR_INVALID;
-    std::lock_guard<std::mutex> lock(h->mu);
+    ENTRY(h)
     if (!smf || n_bytes < 0 || cap < 0 || (cap > 0 && !notes)) { h->err = "bad argument"; return AEGIS_ERR_INVALID; }
     SmfNotes got;
     std::string why;
@@ -260,14 +244,12 @@ int64_t aegis_synth_parse_smf(aegis_handle *h, const uint8_t *smf, int64_t n_byt
     for (int64_t i = 0; i < std::min(n, cap); ++i) notes[i] = got.notes[(size_t)i];
     if (length_seconds) *length_seconds = got.length;
     return n;
-    } catch (...) { return abi_fail(h); }
+    ENTRY_END(h)
 }
 
 int64_t aegis_synth_parse_smf_wheel(aegis_handle *h, const uint8_t *smf, int64_t n_bytes, aegis_synth_note *notes, int32_t *note_track,
                                     int64_t cap, aegis_synth_wheel *wheel, int64_t wheel_cap, int64_t *n_wheel, double *length_seconds) {
-    try {
-    if (!h) return AEGIS_ERR_INVALID;
-    std::lock_guard<std::mutex> lock(h->mu);
+    ENTRY(h)
     if (!smf || n_bytes < 0 || cap < 0 || (cap > 0 && !notes) || wheel_cap < 0 || (wheel_cap > 0 && !wheel)) { h->err = "bad argument"; return AEGIS_ERR_INVALID; }
     SmfNotes got;
     std::string why;
@@ -281,7 +263,7 @@ int64_t aegis_synth_parse_smf_wheel(aegis_handle *h, const uint8_t *smf, int64_t
     if (n_wheel) *n_wheel = nw;
     if (length_seconds) *length_seconds = got.length;
     return n;
-    } catch (...) { return abi_fail(h); }
+    ENTRY_END(h)
 }
 
 int64_t aegis_synth_samples_for(int32_t sample_rate, double length_seconds, const aegis_adsr_params *params) {
@@ -292,9 +274,7 @@ int64_t aegis_synth_samples_for(int32_t sample_rate, double length_seconds, cons
 
 int aegis_synth_adsr(aegis_handle *h, int32_t sample_rate, int32_t n_clips, const aegis_synth_note *notes, const int64_t *note_off,
                      const double *length_seconds, const aegis_adsr_params *params, int16_t *const *out, const int64_t *out_cap) {
-    try {
-    if (!h) return AEGIS_ERR_INVALID;
-    std::lock_guard<std::mutex> lock(h->mu);
+    ENTRY(h)
     if (sample_rate <= 0 || n_clips < 0 || (n_clips > 0 && (!note_off || !length_seconds || !params || !out || !out_cap))) {
         h->err = "bad argument"; return AEGIS_ERR_INVALID;
     }
@@ -308,16 +288,14 @@ int aegis_synth_adsr(aegis_handle *h, int32_t sample_rate, int32_t n_clips, cons
     return run_halving(h, n_clips, [&](int32_t c0, int32_t c1) {
         return synth_group(h, sample_rate, c0, c1, notes, note_off, length_seconds, params, out);
     });
-    } catch (...) { return abi_fail(h); }
+    ENTRY_END(h)
 }
 
 int aegis_synth_adsr_bend(aegis_handle *h, int32_t sample_rate, int32_t n_clips, const aegis_synth_note *notes, const int64_t *note_off,
                           const double *length_seconds, const aegis_adsr_params *params, const int32_t *note_track,
                           const aegis_synth_wheel *wheel, const int64_t *wheel_off, const double *bend_range, int16_t *const *out,
                           const int64_t *out_cap) {
-    try {
-    if (!h) return AEGIS_ERR_INVALID;
-    std::lock_guard<std::mutex> lock(h->mu);
+    ENTRY(h)
     if (sample_rate <= 0 || n_clips < 0 ||
         (n_clips > 0 && (!note_off || !length_seconds || !params || !out || !out_cap || !wheel_off || !bend_range))) {
         h->err = "bad argument"; return AEGIS_ERR_INVALID;
@@ -332,7 +310,7 @@ int aegis_synth_adsr_bend(aegis_handle *h, int32_t sample_rate, int32_t n_clips,
     return run_halving(h, n_clips, [&](int32_t c0, int32_t c1) {
         return synth_group(h, sample_rate, c0, c1, notes, note_off, length_seconds, params, out, &bend);
     });
-    } catch (...) { return abi_fail(h); }
+    ENTRY_END(h)
 }
 
 int64_t aegis_synth_notes_samples_for(int32_t sample_rate, double length_seconds, const aegis_adsr_params *params, int64_t n_notes) {
@@ -345,9 +323,7 @@ int64_t aegis_synth_notes_samples_for(int32_t sample_rate, double length_seconds
 
 int aegis_synth_adsr_notes(aegis_handle *h, int32_t sample_rate, int32_t n_clips, const aegis_synth_note *notes, const int64_t *note_off,
                            const double *length_seconds, const aegis_adsr_params *params, int16_t *const *out, const int64_t *out_cap) {
-    try {
-    if (!h) return AEGIS_ERR_INVALID;
-    std::lock_guard<std::mutex> lock(h->mu);
+    ENTRY(h)
     if (sample_rate <= 0 || n_clips < 0 || (n_clips > 0 && (!note_off || !length_seconds || !out || !out_cap))) {
         h->err = "bad argument"; return AEGIS_ERR_INVALID;
     }
@@ -368,7 +344,7 @@ int aegis_synth_adsr_notes(aegis_handle *h, int32_t sample_rate, int32_t n_clips
     return run_halving(h, n_clips, [&](int32_t c0, int32_t c1) {
         return notes_group(h, sample_rate, c0, c1, notes, note_off, length_seconds, params, out);
     });
-    } catch (...) { return abi_fail(h); }
+    ENTRY_END(h)
 }
 
 }  // extern "C"

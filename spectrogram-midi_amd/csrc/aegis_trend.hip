@@ -8,9 +8,7 @@ extern "C" {
 
 int aegis_ghost_rsi(aegis_handle *h, const int64_t *ev_a, const int64_t *ev_b, const int64_t *event_off, int32_t n_series,
                     const int64_t *track_len, int32_t period, double *avg_gain, double *avg_loss) {
-    try {
-    if (!h) return AEGIS_ERR_INVALID;
-    std::lock_guard<std::mutex> lock(h->mu);
+    ENTRY(h)
     if (n_series < 0 || (n_series > 0 && (!event_off || !track_len))) { h->err = "bad argument"; return AEGIS_ERR_INVALID; }
     if (period < 1 || period > 128) { h->err = "rsi period must be 1..128"; return AEGIS_ERR_INVALID; }
     DEVICE_ONLY(h);
@@ -45,14 +43,12 @@ int aegis_ghost_rsi(aegis_handle *h, const int64_t *ev_a, const int64_t *ev_b, c
     HIPCHK(h, hipMemcpyAsync(avg_gain + event_off[0], d_out, (size_t)E * 8, hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipMemcpyAsync(avg_loss + event_off[0], d_out + E, (size_t)E * 8, hipMemcpyDeviceToHost, s));
     return scope.finish();
-    } catch (...) { return abi_fail(h); }
+    ENTRY_END(h)
 }
 
 int aegis_trend(aegis_handle *h, int32_t op, const double *x, const int64_t *offsets, int32_t n_series,
                 const double *params, int32_t n_params, void *const *outs, int32_t n_outs) {
-    try {
-    if (!h) return AEGIS_ERR_INVALID;
-    std::lock_guard<std::mutex> lock(h->mu);
+    ENTRY(h)
     if (n_series < 0 || (n_series > 0 && (!x || !offsets)) || !outs || n_params < 0 || (n_params > 0 && !params)) {
         h->err = "bad argument"; return AEGIS_ERR_INVALID;
     }
@@ -64,7 +60,6 @@ int aegis_trend(aegis_handle *h, int32_t op, const double *x, const int64_t *off
     };
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
-    int rc;
     int64_t total = n_series > 0 ? offsets[n_series] : 0;
     int64_t n_in = total;
     if (op == AEGIS_TREND_CONSENSUS) {       // x = k stacked rows of one series
@@ -182,7 +177,7 @@ int aegis_trend(aegis_handle *h, int32_t op, const double *x, const int64_t *off
         const double *pp = params + 2 + w;
         const int bw = (int)pp[4];
         if (bw < 1 || bw > 128 || min_len() < bw) { h->err = "band window must be 1..128 and not longer than any series"; return AEGIS_ERR_INVALID; }
-        if ((rc = ensure(h, h->t_pa, (size_t)total * (12 * 8 + 1) + 256)) != AEGIS_OK) return rc;
+        ENSURE(h, t_pa, (size_t)total * (12 * 8 + 1) + 256);
         double *R = h->t_pa.as<double>();
         double *stack = R;                              // [3][total]: savgol, kalman, holt (the order multi_filter_consensus stacks them)
         double *ma = R + 3 * total, *up = R + 4 * total, *lo = R + 5 * total, *semi = R + 6 * total;
@@ -221,7 +216,7 @@ int aegis_trend(aegis_handle *h, int32_t op, const double *x, const int64_t *off
     }
     HIPCHK(h, hipGetLastError());
     return scope.finish();
-    } catch (...) { return abi_fail(h); }
+    ENTRY_END(h)
 }
 
 }  // extern "C"

@@ -76,13 +76,10 @@ int verify_group(aegis_handle *h, int32_t sr, int32_t k0, int32_t k1, const floa
     StreamScope scope(h);                                       // (B, pcm, ev and block_off are in front of it)
     aegis_handle::VerifyBank *bank = nullptr;
     if ((rc = verify_bank(h, sr, &bank)) != AEGIS_OK) return rc;
-    ENSURE(h, vf_audio, pcm.size() * 4); ENSURE(h, vf_events, ev.size() * sizeof(VerifyEvent)); ENSURE(h, vf_boff, block_off.size() * 8);
     ENSURE(h, vf_mel, (size_t)n_rows * kVerMels * 8); ENSURE(h, vf_max, (size_t)n * 3 * 8);
     ENSURE(h, vf_sim, (size_t)n * 2 * 8); ENSURE(h, vf_keep, (size_t)n);
     if ((rc = render_into(h, B, kVerifyLabels)) != AEGIS_OK) return rc;
-    HIPCHK(h, upload(h->vf_audio, pcm.data(), pcm.size() * 4, s));
-    HIPCHK(h, upload(h->vf_events, ev.data(), ev.size() * sizeof(VerifyEvent), s));
-    HIPCHK(h, upload(h->vf_boff, block_off.data(), block_off.size() * 8, s));
+    PUT(h, vf_audio, pcm, s); PUT(h, vf_events, ev, s); PUT(h, vf_boff, block_off, s);
     HIPCHK(h, hipMemsetAsync(h->vf_max.p, 0, (size_t)n * 3 * 8, s));
     VerifyArgs a{};
     a.audio = h->vf_audio.as<const float>();
@@ -98,15 +95,10 @@ int verify_group(aegis_handle *h, int32_t sr, int32_t k0, int32_t k1, const floa
     a.sigmax = h->vf_max.as<unsigned long long>();
     a.sim = h->vf_sim.as<double>();
     a.keep = h->vf_keep.as<uint8_t>();
-    begin_event(h, "verify_mel", s);
-    launch_verify_mel(a, s);
-    end_event(h, s);
-    begin_event(h, "verify_score", s);
-    launch_verify_score(a, s);
-    end_event(h, s);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(sim + 2 * (int64_t)k0, a.sim, (size_t)n * 16, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipMemcpyAsync(keep + k0, a.keep, (size_t)n, hipMemcpyDeviceToHost, s));
+    TIMED(h, "verify_mel", s, launch_verify_mel(a, s));
+    TIMED(h, "verify_score", s, launch_verify_score(a, s));
+    FETCH(h, sim + 2 * (int64_t)k0, a.sim, 2 * n, s);
+    FETCH(h, keep + k0, a.keep, n, s);
     return scope.finish();
 }
 
@@ -118,17 +110,16 @@ int aegis_verify_techniques(aegis_handle *h, int32_t sample_rate, int32_t n_clip
                             int32_t n_events, const aegis_verify_event *events, const aegis_synth_note *notes, const int64_t *note_off,
                             const double *length_seconds, const aegis_adsr_params *params, const int32_t *note_track,
                             const aegis_synth_wheel *wheel, const int64_t *wheel_off, const double *bend_range, double *sim, uint8_t *keep) {
-    try {
-    if (!h) return AEGIS_ERR_INVALID;
-    std::lock_guard<std::mutex> lock(h->mu);
+    ENTRY(h)
     if (sample_rate <= 0 || n_clips < 0 || n_events < 0 || n_events > INT32_MAX / 2 || (n_clips > 0 && (!audio || !n_samples)) ||
         (n_events > 0 && (!events || !note_off || !length_seconds || !params || !wheel_off || !bend_range || !sim || !keep))) {
         h->err = "bad argument"; return AEGIS_ERR_INVALID;
     }
     if (sample_rate < 16000) { h->err = "technique verifier: sample rates below 16 kHz are not built (the mel bank ends at 8000 Hz)"; return AEGIS_ERR_INVALID; }
     if (h->tab.n_fft != kVerFft) { h->err = "technique verifier: only n_fft = 2048 is built (the twiddle and window tables are the handle's)"; return AEGIS_ERR_INVALID; }
-    for (int32_t c = 0; c < n_clips; ++c)
-        if (n_samples[c] < 0 || (n_samples[c] > 0 && !audio[c])) { h->err = "bad clip " + std::to_string(c); return AEGIS_ERR_INVALID; }
+    std::vector<int64_t> soff;
+    int rc = clip_samples(h, "", audio, n_samples, 0, n_clips, soff);
+    if (rc != AEGIS_OK) return rc;
     for (int32_t k = 0; k < n_events; ++k) {
         const aegis_verify_event &e = events[k];
         const std::string who = "event " + std::to_string(k);
@@ -138,8 +129,8 @@ int aegis_verify_techniques(aegis_handle *h, int32_t sample_rate, int32_t n_clip
         if (e.hi - e.lo > (int64_t)1 << 30) { h->err = who + ": slice too long"; return AEGIS_ERR_INVALID; }
         if ((double)(e.hi - e.lo) < (double)sample_rate * 0.05) { h->err = who + ": shorter than 50 ms (the caller passes such events through)"; return AEGIS_ERR_INVALID; }
     }
-    const int rc = check_bend_request(h, sample_rate, 2 * n_events, notes, note_off, length_seconds, params, note_track, wheel, wheel_off,
-                                      bend_range, nullptr, nullptr);
+    rc = check_bend_request(h, sample_rate, 2 * n_events, notes, note_off, length_seconds, params, note_track, wheel, wheel_off, bend_range,
+                            nullptr, nullptr);
     if (rc != AEGIS_OK) return rc;
     for (int32_t k = 0; k < n_events; ++k)
         for (int j = 0; j < 2; ++j)
@@ -153,7 +144,7 @@ int aegis_verify_techniques(aegis_handle *h, int32_t sample_rate, int32_t n_clip
         return verify_group(h, sample_rate, k0, k1, audio, events, notes, note_off, length_seconds, params, note_track, wheel, wheel_off,
                             bend_range, sim, keep);
     });
-    } catch (...) { return abi_fail(h); }
+    ENTRY_END(h)
 }
 
 }  // extern "C"
