@@ -39,6 +39,16 @@ int aegis::cmnd_in_frame(const aegis_handle *h) {
 // finds them, the round-3 path; tests compare the two)
 int aegis::troughs_in_frame(const aegis_handle *h) { return (cmnd_in_frame(h) && !h->troughs_off) ? 1 : 0; }
 
+void aegis::bind_core(PassParams &p, const aegis_handle *h, const PassBufs &w) {
+    p.dfn = w.dfn.as<double>(); p.logobs = w.logobs.as<double>(); p.logunv = w.logunv.as<double>();
+    p.obs_seg = w.obs_seg.as<int32_t>();
+    p.ptr = w.ptr.as<uint16_t>(); p.cmap = w.cmap.as<uint16_t>(); p.bnd = w.bnd.as<int32_t>();
+    p.states = w.states.as<int32_t>(); p.vstate = w.vstate.as<double>();
+    p.melpow = w.melpow.as<float>(); p.clipmax = w.clipmax.as<uint32_t>(); p.rake_raw = w.rake_raw.as<uint8_t>();
+    p.lag_stride = h->lag_stride; p.yin_stride = h->yin_stride; p.obs_stride = h->obs_stride;
+    p.cmnd_in_frame = cmnd_in_frame(h); p.troughs = troughs_in_frame(h); p.bin_table = h->bin_table_off ? 0 : 1;
+}
+
 // (in the order the host-fed entries size, bind and copy them back)
 const OutField aegis::kOutFields[8] = {
     {AEGIS_STAGE_PYIN, 8, false, offsetof(aegis_outputs, f0), &aegis_handle::io_f0, &aegis_stream::o_f0},
@@ -257,28 +267,23 @@ static aegis_handle::SplitSet *split_streams(aegis_handle *h, int n_clips) {
 }
 
 static int ensure_pass(aegis_handle *h, aegis_handle::Work &w, const PassPlan &m, uint32_t stages) {
-    const int64_t nc = m.nc(), nk = m.nk(), fp = m.fp, S = 2 * h->tab.n_bins, nchunks = m.chunk_off[nc];
+    PassGeometry g;
+    g.F = m.fp; g.S = 2 * h->tab.n_bins; g.cmap_rows = m.chunk_off[m.nc()] + 1; g.clips = m.nc(); g.nk = m.nk();
+    g.lag_stride = h->lag_stride; g.yin_stride = h->yin_stride; g.obs_stride = h->obs_stride; g.n_mels = h->tab.n_mels;
+    g.pyin = stages & AEGIS_STAGE_PYIN; g.mel = stages & AEGIS_STAGE_MEL;
+    g.debug_stages = h->debug_stages; g.proportional = m.proportional; g.tsplit = m.tsplit;
+    g.n_seg = m.n_seg; g.tube_cap = m.tube_cap; g.tube_record_ints = viterbi_tube_record_ints();
+    g.seg64_size = (int64_t)m.seg64.size(); g.seg32_size = (int64_t)m.seg32.size();
+    const PassBytes b = pass_bytes(g);
     int rc;
-#define ENS(buf, bytes) if ((rc = ensure(h, w.buf, (size_t)(bytes))) != AEGIS_OK) return rc
-    ENS(sample_off, nc * 8); ENS(sample_len, nc * 8); ENS(out_off, nc * 8); ENS(frame_off, (nc + 1) * 8);
-    ENS(order, nc * 4); ENS(chunk_off, (nc + 1) * 8); ENS(sel_off, (size_t)nk * (nc + 1) * 8);
-    if (stages & AEGIS_STAGE_PYIN) {
-        ENS(dfn, fp * h->lag_stride * 8); if (h->debug_stages) ENS(yin, fp * h->yin_stride * 8);
-        ENS(logobs, fp * h->obs_stride * 8); ENS(logunv, fp * 8); ENS(obs_seg, fp * 4);
-        ENS(ptr, fp * S * 2); ENS(cmap, (nchunks + 1) * S * 2); ENS(bnd, (nchunks + 1) * 4);
-        ENS(states, fp * 4); ENS(vstate, (size_t)nc * S * 8);
-        ENS(chunk_lo, (size_t)nk * 8); ENS(chunk_flag, (size_t)nk * 4);
-        if (m.proportional) ENS(clip_tb, (size_t)(nk + 1) * nc * 8);
-        if (m.tsplit) {
-            const int64_t n_seg = m.n_seg;
-            ENS(seg64, m.seg64.size() * 8); ENS(seg32, m.seg32.size() * 4);
-            ENS(seg_col, (size_t)2 * n_seg * S * 8); ENS(seg_map, (size_t)n_seg * S * 2); ENS(seg_i32, ((size_t)n_seg * 3 + 2 * nc) * 4);
-            ENS(colhist, (size_t)fp * S * 8); ENS(colG, (size_t)fp * 8); ENS(colkg, (size_t)fp * 4); ENS(clip_flag, (size_t)nc * 4);
-            ENS(flag_order, (size_t)nc * 4);
-            ENS(tube_buf, (size_t)m.tube_cap * viterbi_tube_record_ints() * 4); ENS(tube_at, (size_t)fp * 4); ENS(tube_count, 8);
-        }
-    }
-    if (stages & AEGIS_STAGE_MEL) { ENS(melpow, fp * h->tab.n_mels * 4); ENS(clipmax, nc * 4); ENS(rake_raw, fp); }
+    // (a buffer the pass does not use asks for 0 bytes, which never grows anything)
+#define ENS(buf) if ((rc = ensure(h, w.buf, b.buf)) != AEGIS_OK) return rc
+    ENS(sample_off); ENS(sample_len); ENS(out_off); ENS(frame_off); ENS(order); ENS(chunk_off); ENS(sel_off);
+    ENS(dfn); ENS(yin); ENS(logobs); ENS(logunv); ENS(obs_seg); ENS(ptr); ENS(cmap); ENS(bnd); ENS(states); ENS(vstate);
+    ENS(chunk_lo); ENS(chunk_flag); ENS(clip_tb);
+    ENS(seg64); ENS(seg32); ENS(seg_col); ENS(seg_map); ENS(seg_i32); ENS(colhist); ENS(colG); ENS(colkg); ENS(clip_flag);
+    ENS(flag_order); ENS(tube_buf); ENS(tube_at); ENS(tube_count);
+    ENS(melpow); ENS(clipmax); ENS(rake_raw);
 #undef ENS
     return AEGIS_OK;
 }
@@ -294,7 +299,7 @@ static int upload_pass(aegis_handle *h, aegis_handle::Work &w, const PassPlan &m
     if (stages & AEGIS_STAGE_MEL) HIPCHK(h, hipMemsetAsync(w.clipmax.p, 0, nc * 4, fa));
     if (m.tsplit) {
         HIPCHK(h, up(w.seg64, m.seg64)); HIPCHK(h, up(w.seg32, m.seg32));
-        HIPCHK(h, hipMemsetAsync(w.seg_i32.p, 0, ((size_t)m.n_seg * 3 + 2 * nc) * 4, fa));       // seg_lock = 0 for the segments without a lock-on run
+        HIPCHK(h, hipMemsetAsync(w.seg_i32.p, 0, SegLayout(m.n_seg, nc, m.n_lock).n_i32 * 4, fa));       // seg_lock = 0 for the segments without a lock-on run
         HIPCHK(h, hipMemsetAsync(w.clip_flag.p, 0, nc * 4, fa));
         HIPCHK(h, hipMemsetAsync(w.tube_at.p, 0, (size_t)m.fp * 4, fa));
         HIPCHK(h, hipMemsetAsync(w.tube_count.p, 0, 8, fa));       // tubes recorded, rounds of second speculation that had work
@@ -319,28 +324,13 @@ static PassParams bind_pass(const aegis_handle *h, const PassPlan &m, const aegi
     PassParams p = base_params(t);
     p.stages = stages;
     p.pcm = d_pcm;
-    p.sample_off = static_cast<const int64_t *>(w.sample_off.p);
-    p.sample_len = static_cast<const int64_t *>(w.sample_len.p);
-    p.frame_off = static_cast<const int64_t *>(w.frame_off.p);
-    p.out_off = static_cast<const int64_t *>(w.out_off.p);
-    p.order = static_cast<const int32_t *>(w.order.p);
+    p.sample_off = w.sample_off.as<const int64_t>(); p.sample_len = w.sample_len.as<const int64_t>();
+    p.frame_off = w.frame_off.as<const int64_t>(); p.out_off = w.out_off.as<const int64_t>();
+    p.order = w.order.as<const int32_t>(); p.chunk_off = w.chunk_off.as<int64_t>();
     p.n_clips = nc; p.n_frames = m.fp;
-    p.dfn = static_cast<double *>(w.dfn.p); p.lag_stride = h->lag_stride;
-    p.yin = (py && h->debug_stages) ? static_cast<double *>(w.yin.p) : nullptr; p.yin_stride = h->yin_stride;
-    p.cmnd_in_frame = cmnd_in_frame(h); p.troughs = troughs_in_frame(h); p.bin_table = h->bin_table_off ? 0 : 1;
-    p.logobs = static_cast<double *>(w.logobs.p); p.obs_stride = h->obs_stride;
-    p.logunv = static_cast<double *>(w.logunv.p);
-    p.obs_seg = static_cast<int32_t *>(w.obs_seg.p);
-    p.ptr = static_cast<uint16_t *>(w.ptr.p);
-    p.cmap = static_cast<uint16_t *>(w.cmap.p);
-    p.chunk_off = static_cast<int64_t *>(w.chunk_off.p);
-    p.bnd = static_cast<int32_t *>(w.bnd.p);
-    p.states = static_cast<int32_t *>(w.states.p);
-    p.melpow = static_cast<float *>(w.melpow.p);
-    p.clipmax = static_cast<uint32_t *>(w.clipmax.p);
-    p.rake_raw = static_cast<uint8_t *>(w.rake_raw.p);
-    p.vstate = static_cast<double *>(w.vstate.p);
-    p.vstats = static_cast<unsigned long long *>(h->vstats.p);
+    bind_core(p, h, w);
+    p.yin = (py && h->debug_stages) ? w.yin.as<double>() : nullptr;
+    p.vstats = h->vstats.as<unsigned long long>();
     p.out_f0 = py ? dout->f0 : nullptr;
     p.out_voiced = py ? dout->voiced_flag : nullptr;
     p.out_vprob = py ? dout->voiced_prob : nullptr;
@@ -354,27 +344,28 @@ static PassParams bind_pass(const aegis_handle *h, const PassPlan &m, const aegi
     if (opts & AEGIS_OPT_F0_ZERO) p.f0_unvoiced = 0.0;
     p.dense = m.dense ? 1 : 0;
     if (m.tsplit) {
-        const int64_t *g64 = static_cast<const int64_t *>(w.seg64.p);
-        const int32_t *g32 = static_cast<const int32_t *>(w.seg32.p);
-        p.seg_f0 = g64; p.seg_ch0 = g64 + n_seg;
-        p.vf_off = g64 + 2 * n_seg; p.vf_total = m.seg64.back();
-        p.seg_T = g32; p.seg_store = g32 + n_seg; p.seg_prev = g32 + 2 * n_seg; p.seg_clip = g32 + 3 * n_seg;
-        p.clip_seg0 = g32 + 4 * n_seg;
-        p.seg_col = static_cast<double *>(w.seg_col.p); p.seg_col2 = p.seg_col + (size_t)n_seg * S;
-        p.seg_map = static_cast<uint16_t *>(w.seg_map.p);
-        p.seg_kg = static_cast<int32_t *>(w.seg_i32.p); p.seg_lock = p.seg_kg + n_seg; p.seg_end = p.seg_kg + 2 * n_seg; p.clip_first = p.seg_kg + 3 * n_seg; p.clip_dirty = p.clip_first + nc;
-        p.colhist = static_cast<double *>(w.colhist.p); p.colG = static_cast<double *>(w.colG.p); p.colkg = static_cast<int32_t *>(w.colkg.p);
-        p.clip_flag = static_cast<uint32_t *>(w.clip_flag.p);
-        p.tube_buf = static_cast<int32_t *>(w.tube_buf.p); p.tube_cap = m.tube_cap; p.tube_count = static_cast<uint32_t *>(w.tube_count.p);
-        p.tube_at = static_cast<int32_t *>(w.tube_at.p);
+        const SegLayout L(n_seg, nc, m.n_lock);
+        const int64_t *g64 = w.seg64.as<const int64_t>();
+        const int32_t *g32 = w.seg32.as<const int32_t>();
+        p.seg_f0 = g64 + L.f0; p.seg_ch0 = g64 + L.ch0; p.vf_off = g64 + L.vf_off; p.vf_total = m.seg64.back();
+        p.seg_T = g32 + L.T; p.seg_store = g32 + L.store; p.seg_prev = g32 + L.prev; p.seg_clip = g32 + L.clip;
+        p.clip_seg0 = g32 + L.clip_seg0;
+        p.seg_col = w.seg_col.as<double>(); p.seg_col2 = p.seg_col + (size_t)n_seg * S;
+        p.seg_map = w.seg_map.as<uint16_t>();
+        int32_t *i32 = w.seg_i32.as<int32_t>();
+        p.seg_kg = i32 + L.kg; p.seg_lock = i32 + L.lock; p.seg_end = i32 + L.end; p.clip_first = i32 + L.clip_first; p.clip_dirty = i32 + L.clip_dirty;
+        p.colhist = w.colhist.as<double>(); p.colG = w.colG.as<double>(); p.colkg = w.colkg.as<int32_t>();
+        p.clip_flag = w.clip_flag.as<uint32_t>();
+        p.tube_buf = w.tube_buf.as<int32_t>(); p.tube_cap = m.tube_cap; p.tube_count = w.tube_count.as<uint32_t>();
+        p.tube_at = w.tube_at.as<int32_t>();
         p.n_seg = n_seg;
     }
     if (m.persistent) {
-        p.chunk_flag = static_cast<const uint32_t *>(w.chunk_flag.p);
-        p.chunk_lo = static_cast<const int64_t *>(w.chunk_lo.p);
+        p.chunk_flag = w.chunk_flag.as<const uint32_t>();
+        p.chunk_lo = w.chunk_lo.as<const int64_t>();
         p.n_chunks = m.nk();
         if (m.hybrid) { int ks = 0; while (ks < m.nk() && m.cb[ks] <= m.hyb_S) ++ks; p.n_chunks = ks; }      // (the launch ends at step S: chunks 0 .. ks - 1)
-        p.abort_flag = static_cast<uint32_t *>(h->abort_flag.p);
+        p.abort_flag = h->abort_flag.as<uint32_t>();
         // bound of one chunk wait: a chunk's frame stage takes well under a millisecond per 10 k frames, so 0.1 s plus
         // 0.1 s per million frames of the pass is two orders of magnitude of slack, and a pass that cannot overlap
         // (kernels serialised) costs that much once instead of 1.5 s
@@ -428,30 +419,19 @@ static int analyze_device_locked(aegis_handle *h, const float *d_pcm, const int6
             return AEGIS_ERR_INVALID;
         }
     }
-    if (h->inject.armed) {      // aegis_debug_set_observations: the rows are indexed by this call's output frames
+    {   // An armed injection hook (at most one: each setter refuses while another is armed) holds rows indexed by this call's
+        // output frames: aegis_debug_set_observations, aegis_debug_set_difference, aegis_debug_set_rake_columns.
+        const struct { bool armed; int64_t F; uint32_t stage; const char *what, *stage_name; } hooks[] = {
+            {h->inject.armed, h->inject.F, AEGIS_STAGE_PYIN, "injected observations", "PYIN"},
+            {h->inject_d.armed, h->inject_d.F, AEGIS_STAGE_PYIN, "injected difference rows", "PYIN"},
+            {h->inject_r.armed, h->inject_r.F, AEGIS_STAGE_RAKE, "injected rake columns", "RAKE"},
+        };
         int64_t F = 0;
         for (int i = 0; i < n_clips; ++i) F += 1 + (sample_offsets[i + 1] - sample_offsets[i]) / t.hop;
-        if (!(stages & AEGIS_STAGE_PYIN) || F != h->inject.F) {
-            h->err = "injected observations: the call needs the PYIN stage and exactly " + std::to_string(h->inject.F) + " frames (it has " +
-                     std::to_string(F) + ")";
-            return AEGIS_ERR_INVALID;
-        }
-    }
-    if (h->inject_d.armed) {    // aegis_debug_set_difference: likewise (never two: each setter refuses while another hook is armed)
-        int64_t F = 0;
-        for (int i = 0; i < n_clips; ++i) F += 1 + (sample_offsets[i + 1] - sample_offsets[i]) / t.hop;
-        if (!(stages & AEGIS_STAGE_PYIN) || F != h->inject_d.F) {
-            h->err = "injected difference rows: the call needs the PYIN stage and exactly " + std::to_string(h->inject_d.F) + " frames (it has " +
-                     std::to_string(F) + ")";
-            return AEGIS_ERR_INVALID;
-        }
-    }
-    if (h->inject_r.armed) {    // aegis_debug_set_rake_columns: the flags are indexed by this call's output frames
-        int64_t F = 0;
-        for (int i = 0; i < n_clips; ++i) F += 1 + (sample_offsets[i + 1] - sample_offsets[i]) / t.hop;
-        if (!(stages & AEGIS_STAGE_RAKE) || F != h->inject_r.F) {
-            h->err = "injected rake columns: the call needs the RAKE stage and exactly " + std::to_string(h->inject_r.F) + " frames (it has " +
-                     std::to_string(F) + ")";
+        for (const auto &k : hooks) {
+            if (!k.armed || ((stages & k.stage) && F == k.F)) continue;
+            h->err = std::string(k.what) + ": the call needs the " + k.stage_name + " stage and exactly " + std::to_string(k.F) +
+                     " frames (it has " + std::to_string(F) + ")";
             return AEGIS_ERR_INVALID;
         }
     }
@@ -517,7 +497,9 @@ static int analyze_device_locked(aegis_handle *h, const float *d_pcm, const int6
             if (m.persistent) HIPCHK(h, hipStreamWaitEvent(sv, h->sync_events[EV_META], 0));
         }
         PassParams p = bind_pass(h, m, w, d_pcm, stages, opts, dout, rake_sensitivity);
-        const int32_t *d_seg_order = m.tsplit ? p.clip_seg0 + nc + 1 : nullptr, *d_lock_order = d_seg_order ? d_seg_order + m.n_seg : nullptr;
+        const SegLayout L(m.n_seg, nc, m.n_lock);
+        const int32_t *d_seg_order = m.tsplit ? w.seg32.as<const int32_t>() + L.seg_order : nullptr;
+        const int32_t *d_lock_order = m.tsplit ? w.seg32.as<const int32_t>() + L.lock_order : nullptr;
         if (m.persistent) {
             p.chunk_gen = ++h->chunk_gen;
             if (p.chunk_gen == 0) p.chunk_gen = ++h->chunk_gen;

@@ -661,8 +661,9 @@ int64_t aegis_debug_fetch(aegis_handle *h, const char *name, void *dst, int64_t 
             std::vector<int32_t> v((size_t)ns), st((size_t)ns);
             HIPCHK(h, hipSetDevice(h->device));
             HIPCHK(h, hipDeviceSynchronize());
-            HIPCHK(h, hipMemcpy(v.data(), static_cast<const int32_t *>(lw.seg_i32.p) + ns, (size_t)ns * 4, hipMemcpyDeviceToHost));
-            HIPCHK(h, hipMemcpy(st.data(), static_cast<const int32_t *>(lw.seg32.p) + ns, (size_t)ns * 4, hipMemcpyDeviceToHost));
+            const SegLayout L(ns, lp->nc(), lp->n_lock);
+            HIPCHK(h, hipMemcpy(v.data(), lw.seg_i32.as<const int32_t>() + L.lock, (size_t)ns * 4, hipMemcpyDeviceToHost));
+            HIPCHK(h, hipMemcpy(st.data(), lw.seg32.as<const int32_t>() + L.store, (size_t)ns * 4, hipMemcpyDeviceToHost));
             int64_t *o = static_cast<int64_t *>(dst);
             for (int i = 0; i < std::min<int64_t>(cap, ns); ++i) o[i] = v[i] > 0 ? v[i] - st[i] : v[i];
         }

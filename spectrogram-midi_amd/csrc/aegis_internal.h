@@ -5,7 +5,9 @@
 // in front of the body's first write to h->err and maps an exception to a code.  A launch that is timed under a
 // profiling name is TIMED(h, "name", s, launch): the event pair, the launch, the error check.  A host vector goes to
 // its buffer with PUT, n elements come back with FETCH.  Clips of samples are walked by clip_samples and uploaded by
-// upload_clips (aegis_onset.hip, next to the frame walks).
+// upload_clips (aegis_onset.hip, next to the frame walks).  aegis_stream.hip follows the same rules: its entries are
+// STREAM_ENTRY(st) ... STREAM_ENTRY_END(st), its plain push and its close hold a StreamScope, and the workspace it shares
+// with a batch pass is PassBufs, sized by pass_bytes (plan.h) and bound by bind_core.
 //   aegis_api.hip     the batch pipeline (plan input, workspaces, analyze_device_locked, recovery, the analyze entries)
 //   aegis_handle.hip  create / destroy, profiling, the call scope's drain, tables, parameters, aegis_debug_plan / aegis_debug_fetch
 //   aegis_stream.hip  aegis_stream_* (graph capture, commit delivery), aegis_debug_stream_set_observations / _stream_fetch
@@ -57,6 +59,12 @@ struct DevBuf {
     template <class T> T *as() const { return static_cast<T *>(p); }
 };
 
+// The pYIN / mel workspace of one pass, which a batch workspace (aegis_handle::Work) and a stream both own: sized from
+// pass_bytes (plan.h), bound into PassParams by bind_core.
+struct PassBufs {
+    DevBuf dfn, logobs, logunv, obs_seg, ptr, cmap, bnd, states, melpow, clipmax, rake_raw, vstate;
+};
+
 struct aegis_handle {
     aegis::Tables tab;
     aegis::DevTables dt{};
@@ -87,9 +95,9 @@ struct aegis_handle {
     std::vector<DevBuf *> bufs;               // every DevBuf of the handle that holds memory (ensure)
     // workspaces (grow-only): passes alternate between the two, so that the frame stage of one pass runs under the
     // Viterbi of the previous one
-    struct Work {
-        DevBuf dfn, yin, logobs, logunv, obs_seg, ptr, cmap, chunk_off, bnd, states, melpow, clipmax, rake_raw;
-        DevBuf sample_off, sample_len, out_off, frame_off, order, sel_off, vstate, chunk_lo, chunk_flag, clip_tb;
+    struct Work : PassBufs {
+        DevBuf yin, chunk_off;
+        DevBuf sample_off, sample_len, out_off, frame_off, order, sel_off, chunk_lo, chunk_flag, clip_tb;
         DevBuf seg64, seg32, seg_col, seg_map, seg_i32, colhist, colG, colkg, clip_flag, flag_order, tube_buf, tube_at, tube_count;    // time-split passes
     } work[2];
     DevBuf vstats, rk_raw, abort_flag, finite_flag, dbg_bins;
@@ -185,14 +193,14 @@ struct aegis_handle {
 // the same handle may interleave.  Frames are analysed as soon as their 2048-sample window is
 // complete; the Viterbi column is carried across pushes exactly as the offline pipeline carries it
 // across time chunks, so aegis_stream_close() returns what aegis_analyze_batch() returns.
-struct aegis_stream {
+struct aegis_stream : PassBufs {
     aegis_handle *h = nullptr;
     int64_t cap_samples = 0, cap_frames = 0;
     int64_t n_samples = 0;      // samples received
     int64_t frames_done = 0;    // frames analysed (= Viterbi columns produced)
     bool closed = false;
     std::vector<DevBuf *> bufs; // every DevBuf of the stream that holds memory (sized through the handle's ensure, owned here)
-    DevBuf pcm, dfn, logobs, logunv, obs_seg, ptr, cmap, bnd, states, live, melpow, clipmax, rake_raw, vstate, meta;
+    DevBuf pcm, live, meta;     // the stream's own: its samples, the arg-max state of every column, the one-clip geometry (kernels.h StreamMeta)
     DevBuf o_f0, o_voiced, o_vprob, o_rms, o_rake, o_sdb;
     std::vector<int64_t> host_meta;
     // captured hipGraph of one fixed-size push (built lazily for the first push size that is a multiple of hop)
@@ -279,6 +287,15 @@ int abi_fail(aegis_handle *h) noexcept;
     try {                                                                                                   \
         std::lock_guard<std::mutex> entry_lock__((h)->mu);
 #define ENTRY_END(h) } catch (...) { return aegis::abi_fail(h); }
+// The same frame for an entry that takes a stream: a null stream, or one without a handle, is AEGIS_ERR_INVALID and
+// nothing is written; the lock is the handle's; a stream whose handle aegis_destroy() has marked answers "handle was
+// destroyed" before the body looks at an argument.
+#define STREAM_ENTRY(st)                                                                                    \
+    if (!(st) || !(st)->h) return AEGIS_ERR_INVALID;                                                        \
+    try {                                                                                                   \
+        std::lock_guard<std::mutex> entry_lock__((st)->h->mu);                                              \
+        if ((st)->h->destroy_requested) { (st)->h->err = "handle was destroyed"; return AEGIS_ERR_INVALID; }
+#define STREAM_ENTRY_END(st) } catch (...) { return aegis::abi_fail((st)->h); }
 // The domain rules of injected observation rows (aegis_debug_set_observations and aegis_debug_stream_set_observations):
 // AEGIS_OK, or AEGIS_ERR_INVALID with a message that names the frame.  Host arithmetic only.
 AEGIS_LOCAL int check_observation_rows(aegis_handle *h, const double *logobs, const double *logunv, int64_t F);
@@ -388,6 +405,9 @@ RakeBounds rake_frame_bounds(const Tables &t);    // a rake lasts 10 .. 30 ms: i
 PassParams base_params(const Tables &t);          // (rake_frame_bounds included)
 int cmnd_in_frame(const aegis_handle *h);
 int troughs_in_frame(const aegis_handle *h);
+// The workspace half of PassParams, for a batch pass and a stream alike: the PassBufs pointers, the handle's three row
+// strides, and which form of the frame / observation kernels the handle runs (cmnd_in_frame, troughs, bin_table).
+AEGIS_LOCAL void bind_core(PassParams &p, const aegis_handle *h, const PassBufs &w);
 DevTables rule_tables(const aegis_handle *h);     // h->dt as the Viterbi launch rules read it, also on a host-only handle
 PlanInput plan_input(aegis_handle *h, const int64_t *sample_offsets, int32_t n_clips, uint32_t stages, bool feed,
                      bool caller_stream, int32_t sync, int n_cus, std::function<bool(int)> masked);

@@ -9,35 +9,28 @@ using namespace aegis;
 
 extern "C" {
 
+// The kernels' view of the stream: a pass of one clip whose offset tables are the meta block at dm (device: the stream's
+// own copy, or the one inside the graph's control block).
 static PassParams stream_params(aegis_stream *st, const int64_t *dm) {
     aegis_handle *h = st->h;
-    const Tables &t = h->tab;
-    PassParams p = base_params(t);
+    PassParams p = base_params(h->tab);
     p.stages = AEGIS_STAGE_ALL;
-    p.pcm = static_cast<const float *>(st->pcm.p);
-    p.sample_off = dm; p.sample_len = dm + 1; p.frame_off = dm + 2; p.out_off = dm + 2; p.sel_off = dm + 4;
-    p.chunk_off = const_cast<int64_t *>(dm + 6);
-    p.order = reinterpret_cast<const int32_t *>(dm + 8);
+    p.pcm = st->pcm.as<const float>();
+    p.sample_off = dm + kMetaSampleOff; p.sample_len = dm + kMetaSampleOff + 1;
+    p.frame_off = dm + kMetaFrameOff; p.out_off = dm + kMetaFrameOff; p.sel_off = dm + kMetaSelOff;
+    p.chunk_off = const_cast<int64_t *>(dm + kMetaChunkOff);
+    p.order = reinterpret_cast<const int32_t *>(dm + kMetaOrder);
     p.n_clips = 1;
-    p.dfn = static_cast<double *>(st->dfn.p); p.lag_stride = h->lag_stride;
-    p.yin = nullptr; p.yin_stride = h->yin_stride;
-    p.cmnd_in_frame = cmnd_in_frame(h); p.troughs = troughs_in_frame(h); p.bin_table = h->bin_table_off ? 0 : 1;
-    p.logobs = static_cast<double *>(st->logobs.p); p.obs_stride = h->obs_stride;
-    p.logunv = static_cast<double *>(st->logunv.p);
-    p.obs_seg = static_cast<int32_t *>(st->obs_seg.p);
-    p.ptr = static_cast<uint16_t *>(st->ptr.p); p.cmap = static_cast<uint16_t *>(st->cmap.p);
-    p.bnd = static_cast<int32_t *>(st->bnd.p); p.states = static_cast<int32_t *>(st->states.p);
-    p.live_states = static_cast<int32_t *>(st->live.p);
-    p.melpow = static_cast<float *>(st->melpow.p); p.clipmax = static_cast<uint32_t *>(st->clipmax.p);
-    p.rake_raw = static_cast<uint8_t *>(st->rake_raw.p);
-    p.vstate = static_cast<double *>(st->vstate.p);
-    p.out_vprob = static_cast<double *>(st->o_vprob.p);
-    p.out_rms = static_cast<float *>(st->o_rms.p);
-    p.out_f0 = static_cast<double *>(st->o_f0.p); p.out_voiced = static_cast<uint8_t *>(st->o_voiced.p);
-    p.out_rake = static_cast<uint8_t *>(st->o_rake.p); p.out_sdb = static_cast<float *>(st->o_sdb.p);
+    bind_core(p, h, *st);
+    p.live_states = st->live.as<int32_t>();
+    p.out_vprob = st->o_vprob.as<double>(); p.out_rms = st->o_rms.as<float>();
+    p.out_f0 = st->o_f0.as<double>(); p.out_voiced = st->o_voiced.as<uint8_t>();
+    p.out_rake = st->o_rake.as<uint8_t>(); p.out_sdb = st->o_sdb.as<float>();
     p.rake_ratio = 0.6;
     return p;
 }
+// Chunk maps a clip of F frames composes (its F - 1 steps, kViterbiChunk to a map).
+static int64_t stream_chunks(int64_t F) { return (F - 1 + kViterbiChunk - 1) / kViterbiChunk; }
 
 static StreamCommitCtl *stream_commit_ctl(aegis_stream *st) {
     return reinterpret_cast<StreamCommitCtl *>(static_cast<unsigned char *>(st->ctl.p) + sizeof(StreamCtl));
@@ -64,7 +57,7 @@ static int stream_inject_fits(aegis_stream *st, int64_t frames, bool closing) {
 static bool stream_build_graph(aegis_stream *st, int64_t n_push, hipStream_t s, int commit) {
     aegis_handle *h = st->h;
     const Tables &t = h->tab;
-    if (!st->pin_samples || !st->pin_result || (commit && !st->pin_commit) || n_push > 8192 || n_push % t.hop != 0 || n_push / t.hop + 1 > 8) return false;
+    if (!st->pin_samples || !st->pin_result || (commit && !st->pin_commit) || !stream_push_replays(n_push, t.hop)) return false;
     StreamCtl *ctl = static_cast<StreamCtl *>(st->ctl.p);
     PassParams p = stream_params(st, ctl->meta);      // device address arithmetic only
     p.ctl = ctl;
@@ -82,7 +75,7 @@ static bool stream_build_graph(aegis_stream *st, int64_t n_push, hipStream_t s, 
         ok &= launch_stream_commit(ctl, 0, stream_commit_ctl(st), p.ptr, p.vstate, t.n_bins, static_cast<int16_t *>(st->c_bins.p),
                                    st->c_result.p, s) == hipSuccess;
     launch_stream_gather(ctl, p.out_rms, p.out_vprob, p.live_states, st->g_result.p, s);
-    ok &= hipMemcpyAsync(st->pin_result, st->g_result.p, 256, hipMemcpyDeviceToHost, s) == hipSuccess;
+    ok &= hipMemcpyAsync(st->pin_result, st->g_result.p, kGatherBytes, hipMemcpyDeviceToHost, s) == hipSuccess;
     if (commit) ok &= hipMemcpyAsync(st->pin_commit, st->c_result.p, kCommitResultBytes, hipMemcpyDeviceToHost, s) == hipSuccess;
     hipGraph_t g = nullptr;
     ok &= hipStreamEndCapture(s, &g) == hipSuccess && g != nullptr;
@@ -98,21 +91,17 @@ static int stream_run(aegis_stream *st, int64_t f_lo, int64_t f_hi, bool final_p
     // back-trace and the clip-global stages
     aegis_handle *h = st->h;
     const Tables &t = h->tab;
-    const int S = 2 * t.n_bins;
     const int64_t Ftot = final_pass ? f_hi : st->cap_frames;     // clip length as far as the kernels know
-    // meta layout (int64): sample_off[2] | frame_off[2] | sel_off[2] | chunk_off[2] | order (int32 in one slot)
-    st->host_meta.assign(9, 0);
-    st->host_meta[1] = st->n_samples;
-    st->host_meta[3] = Ftot;
-    st->host_meta[5] = f_hi - f_lo;
-    st->host_meta[7] = (Ftot - 1 + kViterbiChunk - 1) / kViterbiChunk;
-    HIPCHK(h, hipMemcpyAsync(st->meta.p, st->host_meta.data(), 9 * 8, hipMemcpyHostToDevice, s));
-    const int64_t *dm = static_cast<const int64_t *>(st->meta.p);
-    PassParams p = stream_params(st, dm);
+    st->host_meta.assign(kMetaSlots, 0);
+    st->host_meta[kMetaSampleOff + 1] = st->n_samples;
+    st->host_meta[kMetaFrameOff + 1] = Ftot;
+    st->host_meta[kMetaSelOff + 1] = f_hi - f_lo;
+    st->host_meta[kMetaChunkOff + 1] = stream_chunks(Ftot);
+    HIPCHK(h, hipMemcpyAsync(st->meta.p, st->host_meta.data(), kMetaSlots * 8, hipMemcpyHostToDevice, s));
+    PassParams p = stream_params(st, st->meta.as<const int64_t>());
     p.n_frames = Ftot;
     p.t_begin = f_lo; p.n_sel = f_hi - f_lo;
     p.vt_begin = f_lo; p.vt_end = final_pass ? INT64_MAX : f_hi;
-    (void)S;
     if (p.n_sel > 0) {
         launch_frame(p, h->dt, s);
         launch_pyin_obs(p, h->dt, s);
@@ -146,38 +135,42 @@ static int stream_open_locked(aegis_handle *h, int64_t max_samples, aegis_stream
     const Tables &t = h->tab;
     st->cap_samples = max_samples;
     st->cap_frames = 1 + max_samples / t.hop;
-    const int64_t F = st->cap_frames, S = 2 * t.n_bins;
-    const int64_t nch = (F - 1 + kViterbiChunk - 1) / kViterbiChunk + 1;
+    const int64_t F = st->cap_frames;
+    PassGeometry g;                           // one clip of the stream's capacity, every stage
+    g.F = F; g.S = 2 * t.n_bins; g.cmap_rows = stream_chunks(F) + 1;
+    g.lag_stride = h->lag_stride; g.yin_stride = h->yin_stride; g.obs_stride = h->obs_stride; g.n_mels = t.n_mels;
+    const PassBytes b = pass_bytes(g);
+    const size_t clipmax_bytes = std::max<size_t>(b.clipmax, 16);      // (16: what a stream has always asked for its one maximum)
     int rc = AEGIS_OK;
-    auto need = [&](DevBuf &b, size_t bytes) { if (rc == AEGIS_OK) rc = ensure(st, b, bytes); };      // (the handle's fail_allocs hook, the stream's list)
-    need(st->pcm, max_samples * 4); need(st->dfn, F * h->lag_stride * 8);
-    need(st->logobs, F * h->obs_stride * 8); need(st->logunv, F * 8); need(st->obs_seg, F * 4); need(st->ptr, F * S * 2);
-    need(st->cmap, nch * S * 2); need(st->bnd, nch * 4); need(st->states, F * 4); need(st->live, F * 4);
-    need(st->melpow, F * t.n_mels * 4); need(st->clipmax, 16); need(st->rake_raw, F); need(st->vstate, S * 8);
-    need(st->meta, 9 * 8); need(st->ctl, sizeof(StreamCtl) + sizeof(StreamCommitCtl)); need(st->g_staging, 8192 * 4); need(st->g_result, 256);
+    auto need = [&](DevBuf &buf, size_t bytes) { if (rc == AEGIS_OK) rc = ensure(st, buf, bytes); };      // (the handle's fail_allocs hook, the stream's list)
+    need(st->pcm, max_samples * 4); need(st->dfn, b.dfn);
+    need(st->logobs, b.logobs); need(st->logunv, b.logunv); need(st->obs_seg, b.obs_seg); need(st->ptr, b.ptr);
+    need(st->cmap, b.cmap); need(st->bnd, b.bnd); need(st->states, b.states); need(st->live, F * 4);
+    need(st->melpow, b.melpow); need(st->clipmax, clipmax_bytes); need(st->rake_raw, b.rake_raw); need(st->vstate, b.vstate);
+    need(st->meta, kMetaSlots * 8); need(st->ctl, sizeof(StreamCtl) + sizeof(StreamCommitCtl)); need(st->g_staging, kStreamStaging * 4); need(st->g_result, kGatherBytes);
     need(st->c_bins, F * 2); need(st->c_result, kCommitResultBytes);
     need(st->o_f0, F * 8); need(st->o_voiced, F); need(st->o_vprob, F * 8); need(st->o_rms, F * 4); need(st->o_rake, F);
     need(st->o_sdb, F * t.n_mels * 4);
     if (rc != AEGIS_OK) return rc;
-    HIPCHK(h, hipMemsetAsync(st->clipmax.p, 0, 16, h->stream));
+    HIPCHK(h, hipMemsetAsync(st->clipmax.p, 0, clipmax_bytes, h->stream));
     // The band Viterbi leaves the back-pointer of a dead voiced state unwritten, and a launch that starts inside a 16-step
     // chunk (any push that is not a whole number of chunks) walks the rows of the chunk's earlier steps for EVERY state to
     // rebuild its chunk map (viterbi_band.inc, "rebuilds org from the HBM pointers").  What it reads for a dead state is
     // never used, but it is used as the next index: with recycled memory behind the rows an index up to 65535 reaches
     // 128 KB past a short stream's last row (an illegal access on a 0.5 s stream, met in the test suite).  Zeroed rows keep
     // every such index at state 0.
-    HIPCHK(h, hipMemsetAsync(st->ptr.p, 0, (size_t)F * S * 2, h->stream));
+    HIPCHK(h, hipMemsetAsync(st->ptr.p, 0, b.ptr, h->stream));
     {
         struct { StreamCtl ctl; StreamCommitCtl commit; } c0{};
         static_assert(sizeof(c0) == sizeof(StreamCtl) + sizeof(StreamCommitCtl), "the commit block sits right behind the control block");
-        c0.ctl.meta[3] = st->cap_frames;
-        c0.ctl.meta[7] = (st->cap_frames - 1 + kViterbiChunk - 1) / kViterbiChunk;
+        c0.ctl.meta[kMetaFrameOff + 1] = F;
+        c0.ctl.meta[kMetaChunkOff + 1] = stream_chunks(F);
         c0.commit.frontier = -1; c0.commit.newest = -1;
         HIPCHK(h, hipMemcpyAsync(st->ctl.p, &c0, sizeof(c0), hipMemcpyHostToDevice, h->stream));
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (hipHostMalloc(reinterpret_cast<void **>(&st->pin_samples), 8192 * 4, hipHostMallocDefault) != hipSuccess) st->pin_samples = nullptr;
-    if (hipHostMalloc(reinterpret_cast<void **>(&st->pin_result), 256, hipHostMallocDefault) != hipSuccess) st->pin_result = nullptr;
+    if (hipHostMalloc(reinterpret_cast<void **>(&st->pin_samples), kStreamStaging * 4, hipHostMallocDefault) != hipSuccess) st->pin_samples = nullptr;
+    if (hipHostMalloc(reinterpret_cast<void **>(&st->pin_result), kGatherBytes, hipHostMallocDefault) != hipSuccess) st->pin_result = nullptr;
     if (hipHostMalloc(reinterpret_cast<void **>(&st->pin_commit), kCommitResultBytes, hipHostMallocDefault) != hipSuccess) st->pin_commit = nullptr;
     // AEGIS_STREAM_GRAPH=0 keeps every push on the plain-launch path, =1 allows the hipGraph replay.  Unset: the replay,
     // except under an injected rocprofiler tool -- round 1's SIGSEGV in aegis_stream_push (profiles/
@@ -193,25 +186,21 @@ static int stream_open_locked(aegis_handle *h, int64_t max_samples, aegis_stream
 }
 
 int aegis_stream_open(aegis_handle *h, int64_t max_samples, aegis_stream **out) {
-    aegis_stream *st = nullptr;
-    try {
-    if (!h || !out || max_samples <= 0) { if (h) h->err = "bad argument"; return AEGIS_ERR_INVALID; }
+    ENTRY(h)
+    if (!out || max_samples <= 0) { h->err = "bad argument"; return AEGIS_ERR_INVALID; }
     *out = nullptr;
     DEVICE_ONLY(h);
-    std::lock_guard<std::mutex> lock(h->mu);
     if (h->destroy_requested) { h->err = "handle was destroyed"; return AEGIS_ERR_INVALID; }
-    st = new (std::nothrow) aegis_stream();
-    if (!st) { h->err = "out of host memory"; return AEGIS_ERR_NOMEM; }
-    const int rc = stream_open_locked(h, max_samples, st);
-    if (rc != AEGIS_OK) { stream_release(st); st = nullptr; return rc; }     // nothing leaks on a failed open
+    // nothing leaks on a failed open: a stream not handed out is released on the way out, by a return or an exception
+    struct HalfBuilt { aegis_stream *st; ~HalfBuilt() { if (st) stream_release(st); } } half{new (std::nothrow) aegis_stream()};
+    if (!half.st) { h->err = "out of host memory"; return AEGIS_ERR_NOMEM; }
+    const int rc = stream_open_locked(h, max_samples, half.st);
+    if (rc != AEGIS_OK) return rc;
     ++h->open_streams;
-    *out = st;
+    *out = half.st;
+    half.st = nullptr;
     return AEGIS_OK;
-    } catch (...) {
-        const int code = abi_fail(h);
-        if (st) stream_release(st);
-        return code;
-    }
+    ENTRY_END(h)
 }
 
 void aegis_stream_free(aegis_stream *st) {
@@ -270,50 +259,48 @@ static int stream_deliver(aegis_stream *st, const unsigned char *res, aegis_stre
 static int stream_push_locked(aegis_stream *st, const float *samples, int64_t n, aegis_stream_frames *out, int64_t *n_frames,
                               aegis_stream_commit *commit) {
     aegis_handle *h = st->h;
-    if (h->destroy_requested) { h->err = "handle was destroyed"; return AEGIS_ERR_INVALID; }
     if (n < 0 || (n > 0 && !samples) || !n_frames) { h->err = "bad argument"; return AEGIS_ERR_INVALID; }
     if (commit && (commit->cap < 0 || (commit->cap > 0 && !commit->pitch_bin))) { h->err = "bad argument"; return AEGIS_ERR_INVALID; }
     if (st->closed) { h->err = "stream is closed"; return AEGIS_ERR_INVALID; }
     if (st->n_samples + n > st->cap_samples) { h->err = "stream capacity exceeded"; return AEGIS_ERR_INVALID; }
     if (st->inject.armed) {      // before anything is consumed: no row past inject.F is ever read
-        const int64_t after = st->n_samples + n;
-        const int rc = stream_inject_fits(st, after >= kFrameLength / 2 ? (after - kFrameLength / 2) / h->tab.hop + 1 : 0, false);
+        const int rc = stream_inject_fits(st, stream_frames_ready(st->n_samples + n, h->tab.hop), false);
         if (rc != AEGIS_OK) return rc;
     }
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
     const int ci = commit ? 1 : 0;
     // ---- fixed-size pushes replay a captured hipGraph ---------------------------------------------
-    const bool eligible = n > 0 && n <= 8192 && n % h->tab.hop == 0 && n / h->tab.hop + 1 <= 8;
-    if (eligible && !st->graph_failed && (st->graph_exec[ci] == nullptr || st->graph_push[ci] == n)) {
+    if (stream_push_replays(n, h->tab.hop) && !st->graph_failed && (st->graph_exec[ci] == nullptr || st->graph_push[ci] == n)) {
         if (st->graph_exec[ci] == nullptr && !stream_build_graph(st, n, s, ci)) st->graph_failed = true;
         if (st->graph_exec[ci] != nullptr && st->graph_push[ci] == n) {
             std::memcpy(st->pin_samples, samples, (size_t)n * 4);
             HIPCHK(h, hipGraphLaunch(st->graph_exec[ci], s));
             HIPCHK(h, hipStreamSynchronize(s));
             st->n_samples += n;
-            const int64_t ready = st->n_samples >= kFrameLength / 2 ? (st->n_samples - kFrameLength / 2) / h->tab.hop + 1 : 0;
-            const int64_t lo = st->frames_done, hi = std::max(lo, ready);
+            const int64_t lo = st->frames_done, hi = std::max(lo, stream_frames_ready(st->n_samples, h->tab.hop));
             int64_t got = 0;
-            std::memcpy(&got, st->pin_result, 8);
+            std::memcpy(&got, st->pin_result + kGatherCount, 8);
             if (got != hi - lo) { h->err = "stream graph and host disagree on the frame count"; return AEGIS_ERR_DEVICE; }
             st->frames_done = hi;
             *n_frames = got;
             if (out) {
-                if (out->rms) std::memcpy(out->rms, st->pin_result + 8, (size_t)got * 4);
-                if (out->voiced_prob) std::memcpy(out->voiced_prob, st->pin_result + 8 + 32, (size_t)got * 8);
-                if (out->live_state) std::memcpy(out->live_state, st->pin_result + 8 + 32 + 64, (size_t)got * 4);
+                if (out->rms) std::memcpy(out->rms, st->pin_result + kGatherRms, (size_t)got * 4);
+                if (out->voiced_prob) std::memcpy(out->voiced_prob, st->pin_result + kGatherVprob, (size_t)got * 8);
+                if (out->live_state) std::memcpy(out->live_state, st->pin_result + kGatherLive, (size_t)got * 4);
             }
             return commit ? stream_deliver(st, st->pin_commit, commit) : AEGIS_OK;
         }
     }
+    // ---- plain launches.  The stream reads `samples`, st->host_meta (stream_run) and `counters`, and writes the caller's
+    // out->rms / voiced_prob / live_state and the commit result block (pinned, or st->commit_host): all of them outlive
+    // the scope
+    int64_t counters[2];
+    StreamScope scope(h);
     if (n > 0)
         HIPCHK(h, hipMemcpyAsync(static_cast<float *>(st->pcm.p) + st->n_samples, samples, n * 4, hipMemcpyHostToDevice, s));
     st->n_samples += n;
-    // frames whose centred window [t*hop - 1024, t*hop + 1024) is complete
-    const int hop = h->tab.hop;
-    const int64_t ready = st->n_samples >= kFrameLength / 2 ? (st->n_samples - kFrameLength / 2) / hop + 1 : 0;
-    const int64_t lo = st->frames_done, hi = std::max(lo, ready);
+    const int64_t lo = st->frames_done, hi = std::max(lo, stream_frames_ready(st->n_samples, h->tab.hop));
     *n_frames = hi - lo;
     if (hi > lo) {
         int rc = stream_run(st, lo, hi, false, s);
@@ -326,48 +313,40 @@ static int stream_push_locked(aegis_stream *st, const float *samples, int64_t n,
             if (out->live_state) HIPCHK(h, hipMemcpyAsync(out->live_state, static_cast<int32_t *>(st->live.p) + lo, k * 4, hipMemcpyDeviceToHost, s));
         }
     }
-    {   // the device control block of the graph path mirrors the host counters
-        const int64_t counters[2] = {st->n_samples, st->frames_done};
-        HIPCHK(h, hipMemcpyAsync(st->ctl.p, counters, 16, hipMemcpyHostToDevice, s));
-    }
+    // the device control block of the graph path mirrors the host counters
+    counters[0] = st->n_samples; counters[1] = st->frames_done;
+    HIPCHK(h, hipMemcpyAsync(st->ctl.p, counters, 16, hipMemcpyHostToDevice, s));
     // commit: one more launch behind the Viterbi, when there is a frame the last walk has not seen (also the frames of
     // earlier plain pushes: the walk goes from the newest frame back to the frontier, however far that is)
     unsigned char *cres = nullptr;
     if (commit && st->frames_done > 0 && st->frames_done - 1 != st->c_newest) {
         cres = st->pin_commit ? st->pin_commit : st->commit_host;
-        hipError_t ce = launch_stream_commit(nullptr, st->frames_done, stream_commit_ctl(st), static_cast<const uint16_t *>(st->ptr.p),
-                                             static_cast<const double *>(st->vstate.p), h->tab.n_bins, static_cast<int16_t *>(st->c_bins.p),
-                                             st->c_result.p, s);
+        hipError_t ce = launch_stream_commit(nullptr, st->frames_done, stream_commit_ctl(st), st->ptr.as<const uint16_t>(),
+                                             st->vstate.as<const double>(), h->tab.n_bins, st->c_bins.as<int16_t>(), st->c_result.p, s);
         if (ce != hipSuccess) { h->err = std::string("stream commit launch: ") + hipGetErrorString(ce); return AEGIS_ERR_DEVICE; }
         HIPCHK(h, hipMemcpyAsync(cres, st->c_result.p, kCommitResultBytes, hipMemcpyDeviceToHost, s));
     }
-    HIPCHK(h, hipStreamSynchronize(s));
-    return commit ? stream_deliver(st, cres, commit) : AEGIS_OK;
+    const int rc = scope.finish();
+    if (rc != AEGIS_OK) return rc;
+    return commit ? stream_deliver(st, cres, commit) : AEGIS_OK;      // (after the drain: it may end in a synchronous copy)
 }
 
 int aegis_stream_push(aegis_stream *st, const float *samples, int64_t n, aegis_stream_frames *out, int64_t *n_frames) {
-    try {
-    if (!st || !st->h) return AEGIS_ERR_INVALID;
-    std::lock_guard<std::mutex> lock(st->h->mu);
+    STREAM_ENTRY(st)
     return stream_push_locked(st, samples, n, out, n_frames, nullptr);
-    } catch (...) { return abi_fail((st ? st->h : nullptr)); }
+    STREAM_ENTRY_END(st)
 }
 
 int aegis_stream_push_commit(aegis_stream *st, const float *samples, int64_t n, aegis_stream_frames *out, int64_t *n_frames,
                              aegis_stream_commit *commit) {
-    try {
-    if (!st || !st->h) return AEGIS_ERR_INVALID;
-    std::lock_guard<std::mutex> lock(st->h->mu);
+    STREAM_ENTRY(st)
     return stream_push_locked(st, samples, n, out, n_frames, commit);
-    } catch (...) { return abi_fail((st ? st->h : nullptr)); }
+    STREAM_ENTRY_END(st)
 }
 
 int aegis_stream_close(aegis_stream *st, double rake_sensitivity, aegis_outputs *out, int64_t *n_frames) {
-    try {
-    if (!st || !st->h) return AEGIS_ERR_INVALID;
+    STREAM_ENTRY(st)
     aegis_handle *h = st->h;
-    std::lock_guard<std::mutex> lock(h->mu);
-    if (h->destroy_requested) { h->err = "handle was destroyed"; return AEGIS_ERR_INVALID; }
     if (!n_frames) { h->err = "bad argument"; return AEGIS_ERR_INVALID; }
     if (st->closed) { h->err = "stream is closed"; return AEGIS_ERR_INVALID; }
     HIPCHK(h, hipSetDevice(h->device));
@@ -376,19 +355,14 @@ int aegis_stream_close(aegis_stream *st, double rake_sensitivity, aegis_outputs 
     const int64_t F = 1 + st->n_samples / t.hop;
     int rc = stream_inject_fits(st, F, true);
     if (rc != AEGIS_OK) return rc;                              // (the stream stays open: more samples may still make it F)
+    // The stream reads st->host_meta (stream_run) and writes the caller's arrays behind `out`: they outlive the scope.
+    StreamScope scope(h);
     rc = stream_run(st, st->frames_done, F, true, s);           // zero-padded tail frames + back-trace
     if (rc != AEGIS_OK) return rc;
-    // clip-global stages over all F frames
-    st->host_meta[5] = F;
-    PassParams p = base_params(t);
-    p.stages = AEGIS_STAGE_ALL;
-    const int64_t *dm = static_cast<const int64_t *>(st->meta.p);
-    p.sample_off = dm; p.sample_len = dm + 1; p.frame_off = dm + 2; p.out_off = dm + 2; p.sel_off = dm + 2; p.n_clips = 1; p.n_frames = F; p.n_sel = F;
-    p.states = static_cast<int32_t *>(st->states.p);
-    p.melpow = static_cast<float *>(st->melpow.p); p.clipmax = static_cast<uint32_t *>(st->clipmax.p);
-    p.rake_raw = static_cast<uint8_t *>(st->rake_raw.p);
-    p.out_f0 = static_cast<double *>(st->o_f0.p); p.out_voiced = static_cast<uint8_t *>(st->o_voiced.p);
-    p.out_rake = static_cast<uint8_t *>(st->o_rake.p); p.out_sdb = static_cast<float *>(st->o_sdb.p);
+    // clip-global stages over all F frames: the selection is the whole clip (the frame offsets; the meta block's own
+    // selection still counts the frames of the last launch)
+    PassParams p = stream_params(st, st->meta.as<const int64_t>());
+    p.sel_off = p.frame_off; p.n_frames = F; p.n_sel = F;
     p.rake_ratio = rake_sensitivity;
     launch_finalize_mel(p, h->dt, s);
     launch_decode(p, h->dt, s);
@@ -400,17 +374,13 @@ int aegis_stream_close(aegis_stream *st, double rake_sensitivity, aegis_outputs 
         for (const OutField &f : kOutFields)
             if (f.st && f.get(out)) HIPCHK(h, hipMemcpyAsync(f.get(out), (st->*f.st).p, f.size(F, t.n_mels), hipMemcpyDeviceToHost, s));
     }
-    HIPCHK(h, hipStreamSynchronize(s));
-    return AEGIS_OK;
-    } catch (...) { return abi_fail((st ? st->h : nullptr)); }
+    return scope.finish();
+    STREAM_ENTRY_END(st)
 }
 
 int aegis_debug_stream_set_observations(aegis_stream *st, const double *logobs, const double *logunv, int64_t F) {
-    try {
-    if (!st || !st->h) return AEGIS_ERR_INVALID;
+    STREAM_ENTRY(st)
     aegis_handle *h = st->h;
-    std::lock_guard<std::mutex> lock(h->mu);
-    if (h->destroy_requested) { h->err = "handle was destroyed"; return AEGIS_ERR_INVALID; }
     if (st->closed) { h->err = "stream is closed"; return AEGIS_ERR_INVALID; }
     if (st->n_samples > 0) { h->err = "injected observations: a stream is armed before its first sample (it has " + std::to_string(st->n_samples) + ")"; return AEGIS_ERR_INVALID; }
     if (!logobs || !logunv || F <= 0) { h->err = "bad argument"; return AEGIS_ERR_INVALID; }
@@ -430,15 +400,12 @@ int aegis_debug_stream_set_observations(aegis_stream *st, const double *logobs, 
     st->inject.F = F;
     st->inject.armed = true;
     return AEGIS_OK;
-    } catch (...) { return abi_fail((st ? st->h : nullptr)); }
+    STREAM_ENTRY_END(st)
 }
 
 int64_t aegis_debug_stream_fetch(aegis_stream *st, const char *name, void *dst, int64_t cap) {
-    try {
-    if (!st || !st->h) return AEGIS_ERR_INVALID;
+    STREAM_ENTRY(st)
     aegis_handle *h = st->h;
-    std::lock_guard<std::mutex> lock(h->mu);
-    if (h->destroy_requested) { h->err = "handle was destroyed"; return AEGIS_ERR_INVALID; }
     if (!name) { h->err = "bad argument"; return AEGIS_ERR_INVALID; }
     const std::string n(name);
     const void *src = nullptr;
@@ -456,7 +423,7 @@ int64_t aegis_debug_stream_fetch(aegis_stream *st, const char *name, void *dst, 
         HIPCHK(h, hipMemcpy(dst, src, (size_t)(std::min(count, cap) * esz), hipMemcpyDeviceToHost));
     }
     return count;
-    } catch (...) { return abi_fail((st ? st->h : nullptr)); }
+    STREAM_ENTRY_END(st)
 }
 
 }  // extern "C"

@@ -5,6 +5,7 @@
 #include <cstdint>
 
 #include "plan.h"      // kViterbiChunk
+#include "tables.h"    // kFrameLength
 
 namespace aegis {
 
@@ -40,8 +41,22 @@ struct StreamCtl {
     int64_t frames_done;      // frames analysed
     int64_t t_begin, n_sel;   // frames of the current push
     int64_t vt_begin, vt_end; // Viterbi steps of the current push
-    int64_t meta[9];          // sample_off[2] | frame_off[2] | sel_off[2] | chunk_off[2] | order
+    int64_t meta[9];          // the one-clip geometry below
 };
+// The meta block of a stream (int64 slots): the offset tables of a pass of one clip, [0, count] each, and the clip order
+// (one int32 0 in a slot of its own).  The host's copy (aegis_stream::host_meta) and StreamCtl::meta share it.
+enum StreamMeta { kMetaSampleOff = 0, kMetaFrameOff = 2, kMetaSelOff = 4, kMetaChunkOff = 6, kMetaOrder = 8, kMetaSlots = 9 };
+// The result block of a graph push (stream_gather_kernel writes it, the push reads its pinned copy): the frame count
+// (int64), then rms float32 | voiced_prob float64 | live_state int32 of up to kGatherFrames frames.
+constexpr int kGatherFrames = 8;
+constexpr int kGatherCount = 0, kGatherRms = 8, kGatherVprob = kGatherRms + 4 * kGatherFrames, kGatherLive = kGatherVprob + 8 * kGatherFrames;
+constexpr int kGatherBytes = 256;
+static_assert(kGatherLive + 4 * kGatherFrames <= kGatherBytes, "the gather block holds its three rows");
+constexpr int kStreamStaging = 8192;       // samples of the graph's staging buffer: the longest push it replays
+// Frames whose centred window [t*hop - 1024, t*hop + 1024) is complete after n samples.
+constexpr int64_t stream_frames_ready(int64_t n, int hop) { return n >= kFrameLength / 2 ? (n - kFrameLength / 2) / hop + 1 : 0; }
+// A push of n samples replays the captured graph: whole hops that fit the staging buffer and the gather block.
+constexpr bool stream_push_replays(int64_t n, int hop) { return n > 0 && n <= kStreamStaging && n % hop == 0 && n / hop + 1 <= kGatherFrames; }
 
 // Device state of the streaming commit (aegis_stream_push_commit; stream_commit.hip), kept behind the stream's StreamCtl
 // so that a graph replay needs no new kernel arguments.

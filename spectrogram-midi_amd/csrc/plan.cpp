@@ -4,6 +4,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <numeric>
+#include <stdexcept>
 
 namespace aegis {
 
@@ -330,6 +331,11 @@ void Planner::plan_pass(PassPlan &m, const int *pc, int nc, int64_t fp, const st
         for (int k = 0; k < n_seg; ++k) if (!hybrid || sprev[k] >= 0) m.seg32.push_back(k);
         if (hybrid) for (int k = 0; k < n_seg; ++k) if (sprev[k] < 0) m.seg32.push_back(k);       // (padding: keeps the layout)
         for (int k = 0; k < n_seg; ++k) if (sprev[k] >= 0) { m.seg32.push_back(k); ++n_lock; }      // lock_order
+        // what the executor sizes, clears and binds by: a table packed in another shape must never reach it (the entry's
+        // frame turns this into an error code and a message, in every build)
+        const SegLayout lay(n_seg, nc, n_lock);
+        if (m.seg64.size() != lay.n64 || m.seg32.size() != lay.n32)
+            throw std::logic_error("plan: the packed time-split tables (seg64, seg32) do not have SegLayout's totals");
         m.tube_cap = (int)std::max<int64_t>(4096, fp / 128);
     }
     const bool balanced = !tsplit && py && !in.caller_stream && kn.balanced_chunk > 0 && nc >= kn.balanced_min && in.n_cus == 256 &&

@@ -100,6 +100,64 @@ struct CallPlan {
     double t_seq = 0.0, t_front = 0.0;
 };
 
+// The packed tables of a time-split pass, in elements: where each array starts and how many there are.  plan.cpp packs
+// seg64 and seg32 in this order, the executor sizes, clears and binds by it.
+struct SegLayout {
+    // seg64 (int64, from the plan): seg_f0 [n_seg] | seg_ch0 [n_seg] | vf_off [nc + 1]
+    size_t f0, ch0, vf_off, n64;
+    // seg32 (int32, from the plan): seg_T | seg_store | seg_prev | seg_clip [n_seg each] | clip_seg0 [nc + 1] | seg_order [n_seg] | lock_order [n_lock]
+    size_t T, store, prev, clip, clip_seg0, seg_order, lock_order, n32;
+    // seg_i32 (int32, device state): seg_kg | seg_lock | seg_end [n_seg each] | clip_first | clip_dirty [nc each]
+    size_t kg, lock, end, clip_first, clip_dirty, n_i32;
+    SegLayout(size_t n_seg, size_t nc, size_t n_lock)
+        : f0(0), ch0(n_seg), vf_off(2 * n_seg), n64(2 * n_seg + nc + 1),
+          T(0), store(n_seg), prev(2 * n_seg), clip(3 * n_seg), clip_seg0(4 * n_seg), seg_order(4 * n_seg + nc + 1),
+          lock_order(5 * n_seg + nc + 1), n32(5 * n_seg + nc + 1 + n_lock),
+          kg(0), lock(n_seg), end(2 * n_seg), clip_first(3 * n_seg), clip_dirty(3 * n_seg + nc), n_i32(3 * n_seg + 2 * nc) {}
+};
+
+// What sizes the workspace of one pass: a batch pass (ensure_pass) or a stream, which is one clip of its capacity.
+struct PassGeometry {
+    int64_t F = 0, S = 0;                   // frames, Viterbi states (2 n_bins)
+    int64_t cmap_rows = 0, clips = 1;       // composed chunk maps (the pass's chunks + 1)
+    int64_t lag_stride = 0, yin_stride = 0, obs_stride = 0, n_mels = 0;
+    bool pyin = true, mel = true;           // the stages that run
+    bool debug_stages = false, proportional = false, tsplit = false;
+    int64_t nk = 1;                         // time chunks
+    int64_t n_seg = 0, tube_cap = 0, tube_record_ints = 0, seg64_size = 0, seg32_size = 0;   // a time-split pass
+};
+// Bytes of every workspace buffer (0: the pass does not use it).  Growth goes by the request, so these ARE the requests.
+struct PassBytes {
+    size_t dfn = 0, logobs = 0, logunv = 0, obs_seg = 0, ptr = 0, cmap = 0, bnd = 0, states = 0, melpow = 0, clipmax = 0, rake_raw = 0, vstate = 0;
+    size_t sample_off = 0, sample_len = 0, out_off = 0, frame_off = 0, order = 0, chunk_off = 0, sel_off = 0;   // batch geometry
+    size_t yin = 0, chunk_lo = 0, chunk_flag = 0, clip_tb = 0;
+    size_t seg64 = 0, seg32 = 0, seg_col = 0, seg_map = 0, seg_i32 = 0, colhist = 0, colG = 0, colkg = 0, clip_flag = 0, flag_order = 0,
+           tube_buf = 0, tube_at = 0, tube_count = 0;
+};
+inline PassBytes pass_bytes(const PassGeometry &g) {
+    const size_t F = (size_t)g.F, S = (size_t)g.S, nc = (size_t)g.clips, nk = (size_t)g.nk;
+    PassBytes b;
+    b.sample_off = nc * 8; b.sample_len = nc * 8; b.out_off = nc * 8; b.frame_off = (nc + 1) * 8;
+    b.order = nc * 4; b.chunk_off = (nc + 1) * 8; b.sel_off = nk * (nc + 1) * 8;
+    if (g.pyin) {
+        b.dfn = F * g.lag_stride * 8; if (g.debug_stages) b.yin = F * g.yin_stride * 8;
+        b.logobs = F * g.obs_stride * 8; b.logunv = F * 8; b.obs_seg = F * 4;
+        b.ptr = F * S * 2; b.cmap = (size_t)g.cmap_rows * S * 2; b.bnd = (size_t)g.cmap_rows * 4;
+        b.states = F * 4; b.vstate = nc * S * 8;
+        b.chunk_lo = nk * 8; b.chunk_flag = nk * 4;
+        if (g.proportional) b.clip_tb = (nk + 1) * nc * 8;
+        if (g.tsplit) {
+            const size_t n_seg = (size_t)g.n_seg;
+            b.seg64 = (size_t)g.seg64_size * 8; b.seg32 = (size_t)g.seg32_size * 4;
+            b.seg_col = 2 * n_seg * S * 8; b.seg_map = n_seg * S * 2; b.seg_i32 = SegLayout(n_seg, nc, 0).n_i32 * 4;
+            b.colhist = F * S * 8; b.colG = F * 8; b.colkg = F * 4; b.clip_flag = nc * 4; b.flag_order = nc * 4;
+            b.tube_buf = (size_t)g.tube_cap * g.tube_record_ints * 4; b.tube_at = F * 4; b.tube_count = 8;
+        }
+    }
+    if (g.mel) { b.melpow = F * g.n_mels * 4; b.clipmax = nc * 4; b.rake_raw = F; }
+    return b;
+}
+
 bool split_allowed(const PlanInput &in);              // time-split passes may be planned for this call at all
 bool masked_streams_fit(const PlanKnobs &k, int n_cus, int n_clips);   // split_streams' conditions on the pass
 CallPlan plan_call(const PlanInput &in);

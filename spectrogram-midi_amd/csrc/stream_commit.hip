@@ -169,8 +169,8 @@ __global__ void stream_advance_kernel(StreamCtl *ctl, const float *__restrict__ 
         ctl->t_begin = lo; ctl->n_sel = hi - lo;
         ctl->vt_begin = lo; ctl->vt_end = hi;
         ctl->frames_done = hi;
-        ctl->meta[1] = n;            // sample_off[1]
-        ctl->meta[5] = hi - lo;      // sel_off[1]
+        ctl->meta[kMetaSampleOff + 1] = n;
+        ctl->meta[kMetaSelOff + 1] = hi - lo;
     }
 }
 
@@ -178,9 +178,9 @@ __global__ void stream_gather_kernel(const StreamCtl *ctl, const float *__restri
                                      const int32_t *__restrict__ live, unsigned char *__restrict__ result) {
     const int i = threadIdx.x;
     int64_t *cnt = reinterpret_cast<int64_t *>(result);
-    float *r = reinterpret_cast<float *>(result + 8);
-    double *v = reinterpret_cast<double *>(result + 8 + 32);
-    int32_t *l = reinterpret_cast<int32_t *>(result + 8 + 32 + 64);
+    float *r = reinterpret_cast<float *>(result + kGatherRms);
+    double *v = reinterpret_cast<double *>(result + kGatherVprob);
+    int32_t *l = reinterpret_cast<int32_t *>(result + kGatherLive);
     const int64_t n = ctl->n_sel, t0 = ctl->t_begin;
     if (i == 0) *cnt = n;
     if (i < 8 && i < n) { r[i] = rms[t0 + i]; v[i] = vprob[t0 + i]; l[i] = live[t0 + i]; }
