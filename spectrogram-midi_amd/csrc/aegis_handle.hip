@@ -52,10 +52,10 @@ int aegis::new_event(aegis_handle *h, hipEvent_t *e, unsigned flags) {
     return AEGIS_OK;
 }
 
-// The fixed events of a device handle (sync_events' slots: analyze_device_locked; split_ev times kernels, the others only order)
+// The fixed events of a device handle (sync_events' slots: EV_* in aegis_internal.h; split_ev times kernels, the others only order)
 static int create_events(aegis_handle *h) {
     int rc = new_event(h, &h->copy_event, hipEventDisableTiming);
-    h->sync_events.assign(8, nullptr);
+    h->sync_events.assign(EV_FIXED, nullptr);
     for (hipEvent_t &e : h->sync_events) if (rc == AEGIS_OK) rc = new_event(h, &e, hipEventDisableTiming);
     for (hipEvent_t &e : h->split_ev) if (rc == AEGIS_OK) rc = new_event(h, &e, hipEventDefault);
     for (hipEvent_t &e : h->hyb_ev) if (rc == AEGIS_OK) rc = new_event(h, &e, hipEventDisableTiming);

@@ -8,7 +8,9 @@
 // upload_clips (aegis_onset.hip, next to the frame walks).  aegis_stream.hip follows the same rules: its entries are
 // STREAM_ENTRY(st) ... STREAM_ENTRY_END(st), its plain push and its close hold a StreamScope, and the workspace it shares
 // with a batch pass is PassBufs, sized by pass_bytes (plan.h) and bound by bind_core.
-//   aegis_api.hip     the batch pipeline (plan input, workspaces, analyze_device_locked, recovery, the analyze entries)
+//   aegis_api.hip     the batch entries (plan input, the host and raw-byte feeds, recovery, the three analyze entries, PCM helpers)
+//   aegis_exec.hip    the batch executor: analyze_device_locked runs the passes plan.cpp plans, step by step (check_call,
+//                     open_pass, the pass workspace, the chunks, hybrid_segments, close_pass, join_call, the split verdicts)
 //   aegis_handle.hip  create / destroy, profiling, the call scope's drain, tables, parameters, aegis_debug_plan / aegis_debug_fetch
 //   aegis_stream.hip  aegis_stream_* (graph capture, commit delivery), aegis_debug_stream_set_observations / _stream_fetch
 //   aegis_cqt.hip     CQT, chroma, the filter-bank cache, aegis_estimate_tuning, aegis_rake_patterns
@@ -45,6 +47,7 @@
 #include "../../include/aegis_hip.h"
 #include "kernels.h"
 #include "plan.h"
+#include "pcm.h"
 #include "cqt.h"
 #include "tables.h"
 #include "tuning.h"
@@ -65,6 +68,11 @@ struct PassBufs {
     DevBuf dfn, logobs, logunv, obs_seg, ptr, cmap, bnd, states, melpow, clipmax, rake_raw, vstate;
 };
 
+// The slots of aegis_handle::sync_events as a batch call uses them: call start, pass done (by workspace parity), frame_b
+// joined, frame_a final, pass metadata uploaded, then one per time chunk (reserve_chunk_events grows the list; EV_FIXED
+// exist from aegis_create on).  Between batch calls aegis_trend.hip forks and joins its streams on the first four.
+enum { EV_START = 0, EV_DONE0 = 1, EV_DONE1 = 2, EV_FB = 3, EV_FA = 4, EV_META = 5, EV_CHUNK0 = 6, EV_FIXED = 8 };
+
 struct aegis_handle {
     aegis::Tables tab;
     aegis::DevTables dt{};
@@ -84,7 +92,7 @@ struct aegis_handle {
     // from aegis_create on; sync_events grows by one per time chunk beyond its fixed slots.
     std::vector<hipEvent_t> owned_events;
     hipEvent_t copy_event = nullptr;
-    std::vector<hipEvent_t> sync_events;      // cross-stream dependencies (no timing)
+    std::vector<hipEvent_t> sync_events;      // cross-stream dependencies (no timing): the slots EV_* above
     hipEvent_t split_ev[2] = {nullptr, nullptr};   // around an automatic split call's Viterbi kernels: the planning rule checks its estimate against them
     hipEvent_t hyb_ev[3] = {nullptr, nullptr, nullptr};
     hipEvent_t fin_ev[2] = {nullptr, nullptr};       // fork / join of a split pass's two finishing streams (launch_viterbi_split)
@@ -120,7 +128,7 @@ struct aegis_handle {
         int cooldown = 0;                     // calls left on the one-launch-per-chunk schedule after a give-up; then the single launch is tried again
         int64_t fallbacks = 0;                // calls repeated with one launch per chunk (aegis_debug_fetch "persistent_fallbacks")
     } persist;
-    // Time-split passes: the verdicts still to read, and the rule that stops planning them when they do not pay (split_check)
+    // Time-split passes: the verdicts still to read, and the rule that stops planning them when they do not pay (split_verdict, aegis_exec.hip)
     struct SplitCheck { int pass; aegis::PassParams p; };
     struct TimeSplit {
         std::vector<SplitCheck> checks;       // split passes of the call in flight whose clip flags have not been read
@@ -398,6 +406,40 @@ AEGIS_LOCAL int onset_request(aegis_handle *h, const aegis_onset_params *p, Onse
 // The envelope kernel over d_img / d_foff (device) into on_env (handle locked, device set); enqueued only.
 AEGIS_LOCAL int onset_env_locked(aegis_handle *h, const float *d_img, const int64_t *d_foff, int32_t n_clips, int64_t F, int64_t maxF, int32_t n_mels,
                      const OnsetParams &o);
+
+// ---- the batch executor and what feeds it (aegis_exec.hip, aegis_api.hip) ----
+// Raw WAV bytes of aegis_analyze_pcm: per time chunk, the bytes of the input frames the chunk's new output samples read
+// are copied on stream3 and one pcm_decode_resample_kernel writes those samples into the PCM buffer.
+struct PcmFeed {
+    const aegis_pcm_clip *src;            // [n_clips] the caller's clips
+    std::vector<PcmClipDev> clips;        // host copy of the device clip table
+    std::vector<int64_t> done_in;         // input frames of each clip already enqueued
+    std::vector<std::vector<PcmRange>> tables;   // every launch's range table (host memory of in-flight copies)
+    int64_t range_cap = 0, range_used = 0;       // entries of h->pcm_ranges
+    float *y_out = nullptr;               // the decoded samples back to the host, pass after pass (optional)
+};
+// Host-resident input of aegis_analyze_batch: the samples each time chunk needs are copied on stream3 right
+// before that chunk's frame stage is enqueued, so the transfer hides behind the pipeline instead of preceding it.
+struct HostFeed {
+    const float *const *pcm;      // [n_clips] host pointers
+    float *dst;                   // packed device buffer (== d_pcm)
+    std::vector<int64_t> copied;  // samples of each clip already enqueued (output samples for a raw-byte feed)
+    PcmFeed *raw = nullptr;       // raw WAV bytes instead of float32 samples
+    std::vector<int32_t> cis;
+    std::vector<int64_t> need;    // (bring: samples of each clip the chunk at hand needs)
+    // the samples chunk k of pass m reads, enqueued on stream3; frame stream fs waits for them (aegis_api.hip)
+    int bring(aegis_handle *h, const PassPlan &m, int k, hipStream_t fs);
+};
+// sync: 0 = return with the work enqueued, 1 = synchronise and report (give-up of the single Viterbi launch, non-finite
+// samples), 2 = the caller synchronises and makes those checks itself right away (aegis_analyze_batch: the single Viterbi
+// launch is allowed, as with 1)
+AEGIS_LOCAL int analyze_device_locked(aegis_handle *h, const float *d_pcm, const int64_t *sample_offsets, int32_t n_clips,
+                                      double rake_sensitivity, uint32_t stages, aegis_outputs *dout, void *stream_v, int32_t sync,
+                                      HostFeed *feed = nullptr);
+// After a synchronisation: a persistent Viterbi launch that gave up waiting for its chunk flags says so here.
+AEGIS_LOCAL int persistent_check(aegis_handle *h);
+// After a synchronisation: the verdict of AEGIS_OPT_CHECK_FINITE (librosa.util.valid_audio's ParameterError).
+AEGIS_LOCAL int finite_result(aegis_handle *h, uint32_t opts, const int64_t *sample_offsets, int32_t n_clips);
 
 // ---- kernel parameters every entry fills the same way (aegis_api.hip) ----
 struct RakeBounds { int min_frames, max_frames; };

@@ -92,7 +92,7 @@ struct PassParams {
     const int64_t *sel_off;      // [n_clips+1]
     int64_t t_begin;
     // Ragged passes cut every clip into the SAME number of time chunks, each proportional to the clip's length (see
-    // aegis_api.hip): clip c then contributes its frames clip_t0[c] .. clip_t0[c] + (sel_off[c+1]-sel_off[c]) - 1 and its
+    // aegis_exec.hip chunk_params): clip c then contributes its frames clip_t0[c] .. clip_t0[c] + (sel_off[c+1]-sel_off[c]) - 1 and its
     // Viterbi steps [max(1, clip_t0[c]), min(T, clip_t1[c])).  NULL: t_begin / vt_begin / vt_end for every clip.
     const int64_t *clip_t0, *clip_t1;
     int32_t dense;               // throughput pass (a Viterbi workgroup on every CU): the 96-register Viterbi build and four-wave
@@ -142,7 +142,7 @@ struct PassParams {
     uint32_t *clip_flag;         // [n_clips] != 0: the clip's decode could not be certified, the sequential kernel must redo it
     int32_t split_phase;         // 1: speculative runs, 2: lock-on runs
     int32_t n_seg;
-    // Hybrid split pass (aegis_api.hip): the sequential kernel has run every clip's steps 1 .. hybrid_step under the frame
+    // Hybrid split pass (aegis_exec.hip hybrid_segments): the sequential kernel has run every clip's steps 1 .. hybrid_step under the frame
     // stage (a clip's first segment is that run; vstate holds its last column), only the segments behind it are speculative
     int32_t split_hybrid;
     int32_t hybrid_step;

@@ -1,6 +1,6 @@
 // Pass planner of the batch entries (aegis_analyze_batch / _device): which clips share a pass, how each pass is cut into
 // time chunks or time-split segments, which kernels run and on which stream.  Plain C++: no HIP, testable on the CPU
-// (aegis_debug_plan, tests/test_plan.py).  aegis_api.hip enqueues what it plans.
+// (aegis_debug_plan, tests/test_plan.py).  aegis_exec.hip enqueues what it plans.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -66,6 +66,11 @@ struct PlanInput {
     bool persistent = true;                 // single Viterbi launches allowed (false for a while after a give-up)
 };
 
+// The Viterbi launch that follows chunk k's observations (PassPlan::viterbi_behind).  The sequential kernel: none, the one
+// persistent launch (behind chunk 0), one launch for this chunk.  segments: a plain split pass's one launch, behind its
+// last chunk.
+enum class ViterbiBehind : uint8_t { none, single_launch, per_chunk, segments };
+
 struct PassPlan {
     std::vector<int> clips;                 // indices into the caller's arrays, longest first
     int64_t fp = 0, maxF = 0;               // frames of the pass, of its longest clip
@@ -90,6 +95,19 @@ struct PassPlan {
     // first frame of chunk k of the pass's clip i, and one past its last
     int64_t clip_lo(int k, int i) const { return proportional ? clip_tb[(size_t)k * nc() + i] : std::min(frames(i), cb[k]); }
     int64_t clip_hi(int k, int i) const { return proportional ? clip_tb[(size_t)(k + 1) * nc() + i] : std::min(frames(i), cb[k + 1]); }
+    // The chunks the sequential kernel runs: every one, or in a hybrid pass those that begin at or before step S (behind S
+    // the segments take over).
+    int sequential_chunks() const {
+        if (!hybrid) return nk();
+        int ks = 0;
+        while (ks < nk() && cb[ks] <= hyb_S) ++ks;
+        return ks;
+    }
+    ViterbiBehind viterbi_behind(int k) const {
+        if (persistent) return k == 0 ? ViterbiBehind::single_launch : ViterbiBehind::none;      // its first column reads frame 0
+        if (tsplit && !hybrid) return k == nk() - 1 ? ViterbiBehind::segments : ViterbiBehind::none;   // they need every frame's observations
+        return (!hybrid || cb[k] <= hyb_S) ? ViterbiBehind::per_chunk : ViterbiBehind::none;   // (behind step S the segments take over)
+    }
 };
 
 struct CallPlan {

@@ -9,6 +9,12 @@ and run directly.  Geometries: F of 1, 2, 16, 17, 18, 33 frames per clip (both s
 clips, 1 and 4 time chunks, the PYIN stage alone, the MEL stage alone and both, debug_stages / proportional on and off,
 no time split and time splits of 1 and 5 segments per clip, and the stream's row for each F.
 
+The launch rule: which Viterbi launch follows chunk k's observations (PassPlan::viterbi_behind) and how many chunks the
+sequential kernel runs (PassPlan::sequential_chunks) are the plan's statements, which the executor's chunk loop and
+bind_pass read.  The same program answers them for hand-written plans -- persistent with 3 chunks, per chunk with 2, a
+plain split pass of 1 chunk, a host-fed split pass of 2, a hybrid pass with cb = {0, 465, 945, 4785, 7000, 9000} and
+S = 4784, persistent and not -- and the answers are held to the literals below, which restate the parent's chunk loop.
+
 The packed tables themselves: plan.cpp refuses, in every build, a pass whose seg64 / seg32 do not have SegLayout's
 totals; the plans of tests/test_plan.py that force split passes (plain and hybrid) are planned once more here.  CPU only."""
 import importlib.util
@@ -53,7 +59,7 @@ ORDER = ("F", "S", "cmap_rows", "clips", "lag", "yin", "obs", "n_mels", "pyin", 
 
 # ---- the parent's expressions --------------------------------------------------------------------------------------------
 def parent_ensure_pass(g):
-    """aegis_api.hip ensure_pass, ENS by ENS (a buffer it did not size: 0)."""
+    """ensure_pass as the parent's aegis_api.hip spelled it out (now aegis_exec.hip, from pass_bytes), ENS by ENS (a buffer it did not size: 0)."""
     nc, nk, fp, nchunks = g["clips"], g["nk"], g["F"], g["cmap_rows"] - 1
     b = dict.fromkeys(("dfn logobs logunv obs_seg ptr cmap bnd states melpow clipmax rake_raw vstate sample_off sample_len out_off frame_off "
                        "order chunk_off sel_off yin chunk_lo chunk_flag clip_tb seg64 seg32 seg_col seg_map seg_i32 colhist colG colkg "
@@ -97,12 +103,18 @@ def parent_layout(g):
 
 
 @pytest.fixture(scope="module")
-def report(tmp_path_factory):
+def program(tmp_path_factory):
     cxx = shutil.which("g++") or shutil.which("c++")
     assert cxx, "a host C++ compiler is needed to compile csrc/plan.h"
     exe = str(tmp_path_factory.mktemp("workspace") / "workspace_host_check")
     subprocess.run([cxx, "-O1", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
                     os.path.join(ROOT, "tools", "workspace_host_check.cpp"), "-o", exe], check=True)
+    return exe
+
+
+@pytest.fixture(scope="module")
+def report(program):
+    exe = program
     rows = batch_rows() + stream_rows()
     r = subprocess.run([exe] + [",".join(str(g[k]) for k in ORDER) for g in rows], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
@@ -136,6 +148,19 @@ def test_layout_offsets_equal_the_parents_pointer_arithmetic(report):
         if g["tsplit"]:
             assert out["layout"] == parent_layout(g), g
             assert out["bytes"]["seg_i32"] == (4 * out["layout"]["n_i32"] if g["pyin"] else 0)     # (upload_pass's memset)
+
+
+def test_the_launch_rule_of_hand_written_plans(program):
+    """n: no launch behind the chunk, s: the one persistent launch, c: one launch for this chunk, g: the segments.  The
+    parent's loop: a persistent pass launches behind chunk 0 alone; a plain split pass behind its last chunk alone; a
+    hybrid pass runs the sequential kernel for the chunks that begin at or before step S (cb[k] <= S: 0, 465, 945 of the
+    six boundaries for S = 4784, and 4785 as well for S = 4785) and nothing behind the others."""
+    r = subprocess.run([program, "launch_rule"], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    got = {c["name"]: (c["behind"], c["sequential_chunks"]) for c in json.loads(r.stdout)}
+    assert got == {"persistent_nk3": ("snn", 3), "per_chunk_nk2": ("cc", 2), "plain_split_nk1": ("g", 1),
+                   "host_fed_split_nk2": ("ng", 2), "hybrid_persistent": ("snnnn", 3), "hybrid_per_chunk": ("cccnn", 3),
+                   "hybrid_step_on_a_boundary": ("ccccn", 4)}
 
 
 def test_planned_split_passes_have_the_layouts_totals():

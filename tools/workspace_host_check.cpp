@@ -5,16 +5,59 @@
 //   workspace_host_check  F,S,cmap_rows,clips,lag,yin,obs,n_mels,pyin,mel,debug,prop,tsplit,nk,n_seg,tube_cap,tube_rec,seg64,seg32,n_lock ...
 //
 // One JSON object per argument, in a list.
+//
+//   workspace_host_check launch_rule
+//
+// Which Viterbi launch follows chunk k's observations (PassPlan::viterbi_behind) and how many chunks the sequential kernel
+// runs (PassPlan::sequential_chunks), for hand-written plans of every pass kind, against the answers written out below:
+// one JSON object per plan, exit status 1 when an answer differs.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "../spectrogram-midi_amd/csrc/plan.h"
 
 using namespace aegis;
 
+struct RuleCase {
+    const char *name;
+    bool persistent, tsplit, hybrid;
+    std::vector<int64_t> cb;
+    int64_t hyb_S;
+    const char *behind;      // per chunk: n(one), s(ingle launch), c (per chunk), g (segments)
+    int sequential_chunks;
+};
+
+static int launch_rule() {
+    const std::vector<int64_t> hyb_cb = {0, 465, 945, 4785, 7000, 9000};
+    const RuleCase cases[] = {
+        {"persistent_nk3", true, false, false, {0, 64, 128, 200}, 0, "snn", 3},
+        {"per_chunk_nk2", false, false, false, {0, 64, 100}, 0, "cc", 2},
+        {"plain_split_nk1", false, true, false, {0, 1600}, 0, "g", 1},
+        {"host_fed_split_nk2", false, true, false, {0, 96, 2200}, 0, "ng", 2},
+        {"hybrid_persistent", true, true, true, hyb_cb, 4784, "snnnn", 3},
+        {"hybrid_per_chunk", false, true, true, hyb_cb, 4784, "cccnn", 3},
+        {"hybrid_step_on_a_boundary", false, true, true, hyb_cb, 4785, "ccccn", 4},
+    };
+    int bad = 0;
+    std::printf("[");
+    for (const RuleCase &c : cases) {
+        PassPlan m;
+        m.persistent = c.persistent; m.tsplit = c.tsplit; m.hybrid = c.hybrid; m.cb = c.cb; m.hyb_S = c.hyb_S;
+        std::string got;
+        for (int k = 0; k < m.nk(); ++k) got += "nscg"[(int)m.viterbi_behind(k)];
+        if (got != c.behind || m.sequential_chunks() != c.sequential_chunks) ++bad;
+        std::printf("%s\n{\"name\": \"%s\", \"behind\": \"%s\", \"sequential_chunks\": %d}", &c == cases ? "" : ",", c.name, got.c_str(),
+                    m.sequential_chunks());
+    }
+    std::printf("\n]\n");
+    return bad ? 1 : 0;
+}
+
 int main(int argc, char **argv) {
+    if (argc == 2 && !std::strcmp(argv[1], "launch_rule")) return launch_rule();
     std::printf("[");
     for (int a = 1; a < argc; ++a) {
         std::vector<long long> v;
