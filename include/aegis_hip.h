@@ -749,6 +749,51 @@ int aegis_hpss_masks(aegis_handle *h, const float *S, const int64_t *n_frames, i
                      const aegis_hpss_params *p, float *harm /* NULL ok */, float *perc /* NULL ok */,
                      float *mask_harm /* NULL ok */, float *mask_perc /* NULL ok */);
 
+/* --- Dynamic time warping: where one feature sequence lies in time against another ----------------------------------
+ * The reference has no alignment.  This is librosa 0.10's sequence.dtw with its default step set (diagonal,
+ * left, up; no weights), written from memory of upstream, in a fixed arithmetic order: csrc/dtw.h states it once and is the
+ * contract, DESIGN.md 3.20 explains it, tools/dtw_restated.py restates it in NumPy.
+ *   cost        cosine (metric 0 or 1: the default here) c = max(0, 1 - <u, v>) of the float32 unit columns, a zero column
+ *               costing exactly 1; euclidean (metric 2, librosa's own default) c = sqrtf(sum (x_k - y_k)^2).  Float32, k
+ *               ascending, product or square rounded, then the add.
+ *   recurrence  float64: D[i][j] = c[i][j] + the smallest of D[i-1][j-1], D[i][j-1], D[i-1][j], taken in that order, a later
+ *               one winning only when strictly smaller.  Step codes 0 diagonal, 1 left, 2 up, 3 "starts here".
+ *   subsequence every cell of row 0 starts; the path ends at the first arg-min of the last row.  Otherwise (N-1, M-1).
+ *   band        frames, 0 = none: cells with |i (M-1) - j (N-1)| > band max(N-1, M-1) have D = +inf.  Not with subsequence.
+ *   aegis_dtw           seq: float32 sequences in host memory one after another, sequence s as [K][n_frames[s]] (row k =
+ *                       feature k of every frame: what aegis_chroma_cqt writes), K = 1..24.  Pair p aligns sequence
+ *                       pair_a[p] (rows, N frames) with pair_b[p] (columns, M frames): indices, so many pairs may share a
+ *                       sequence; N, M >= 1, N M <= 2^28.  path_out: int32 [.][2], the ascending path of pair p at cell
+ *                       offset sum over q < p of (N_q + M_q - 1), path_len[p] cells of it written; cost_out[p] = D at the
+ *                       path's end.  D_out (float64) and steps_out (uint8, one code per cell; undefined where D is +inf):
+ *                       [N][M] per pair, pair after pair -- probes for the tests: with either one the kernel also stores D,
+ *                       and a call of more than 2^22 cells in all is refused.  Without them no N x M array of D exists:
+ *                       two bits per cell are kept on the device and walked there.
+ *   aegis_align_chroma  PCM as aegis_analyze_batch takes it -> the chroma of aegis_chroma_cqt (same bank arguments), which
+ *                       stays on the device -> the same alignment over clips (a clip has 1 + n_samples / hop frames, K =
+ *                       n_chroma).  Only paths and costs come back.
+ * A batch whose step codes exceed the pass workspace (512 MiB, or AEGIS_DTW_PASS_BYTES at aegis_create) runs in passes of
+ * whole pairs; no result depends on the cut.  A pair's results depend on that pair alone.
+ * AEGIS_ERR_INVALID with a message, before the device is looked at: K outside 1..24, a pair index outside the sequences, an
+ * empty sequence in a pair, a pair above 2^28 cells, a negative band, an unknown metric, band with subsequence, a value
+ * that is not finite (the message names the sequence and the frame).  A device = -1 handle rejects the same requests and
+ * answers AEGIS_ERR_DEVICE to a valid one.
+ * Kernel time: "dtw_cost", "dtw_forward" and "dtw_walk" of aegis_last_kernel_ms, summed over a call's passes.  Blocking;
+ * host pointers. */
+typedef struct aegis_dtw_params {
+    int32_t metric;                      /* 0 or 1: cosine; 2: euclidean */
+    int32_t subsequence;                 /* 0 or 1 */
+    int32_t band;                        /* frames; 0: none */
+    int32_t reserved;
+} aegis_dtw_params;
+int aegis_dtw(aegis_handle *h, const float *seq, const int64_t *n_frames, int32_t n_seq, int32_t K, const int32_t *pair_a,
+              const int32_t *pair_b, int32_t n_pairs, const aegis_dtw_params *params, int32_t *path_out, int64_t *path_len,
+              double *cost_out, double *D_out /* NULL ok */, uint8_t *steps_out /* NULL ok */);
+int aegis_align_chroma(aegis_handle *h, const float *const *pcm, const int64_t *n_samples, int32_t n_clips, int32_t n_bins,
+                       int32_t bins_per_octave, double fmin, double filter_scale, int32_t n_chroma, const int32_t *bin_class,
+                       const int32_t *pair_a, const int32_t *pair_b, int32_t n_pairs, const aegis_dtw_params *params,
+                       int32_t *path_out, int64_t *path_len, double *cost_out);
+
 /* --- Effect chain: distortion, reverb, delay, chorus (aegis_engine_core/effect_learning_loop.py:56-275) ----------
  * The reference's pure-NumPy effects, each ending in a whole-clip normalisation, which its learning loop
  * (effect_learning_loop.py:489-725) puts between the synthesiser and the engine.  Float64 throughout.

@@ -21,6 +21,7 @@ FX_DISTORTION, FX_REVERB, FX_DELAY, FX_CHORUS = 1, 2, 3, 4                # AEGI
 # effect name -> (kind, (parameter, the reference's default) for p0 and p1): effect_learning_loop.py:56, :84, :137, :185
 EFFECT_KINDS = {"distortion": (FX_DISTORTION, (("drive", 0.5),)), "reverb": (FX_REVERB, (("room_size", 0.5),)),
                 "delay": (FX_DELAY, (("delay_ms", 300), ("feedback", 0.3))), "chorus": (FX_CHORUS, (("depth", 0.003), ("rate", 1.5)))}
+DTW_METRICS = {"cosine": 1, "euclidean": 2}                                # aegis_dtw_params.metric (0: cosine too)
 WAVEFORMS = {"sine": 0, "sawtooth": 1, "square": 2, "triangle": 3}          # AEGIS_WAVE_*
 SYNTH_NOTE_DTYPE = np.dtype([("start", "<f8"), ("duration", "<f8"), ("note", "<i4"), ("velocity", "<i4")])
 SYNTH_WHEEL_DTYPE = np.dtype([("time", "<f8"), ("track", "<i4"), ("value", "<i4")])      # aegis_synth_wheel
@@ -110,6 +111,10 @@ class HpssParams(C.Structure):
                 ("margin_harm", _F64), ("margin_perc", _F64)]
 
 
+class DtwParams(C.Structure):
+    _fields_ = [("metric", _I32), ("subsequence", _I32), ("band", _I32), ("reserved", _I32)]
+
+
 class Effect(C.Structure):
     _fields_ = [("kind", _I32), ("n_ir", _I32), ("p0", _F64), ("p1", _F64), ("ir", _P)]
 
@@ -119,7 +124,7 @@ STRUCTS = {"aegis_config": Config, "aegis_outputs": Outputs, "aegis_pcm_clip": P
            "aegis_stream_commit": StreamCommit, "aegis_event": Event, "aegis_event_params": EventParams, "aegis_run_fit": RunFit,
            "aegis_event_batch": EventBatch, "aegis_synth_note": SynthNote, "aegis_adsr_params": AdsrParams,
            "aegis_fit_note": FitNote, "aegis_verify_event": VerifyEvent, "aegis_salience_params": SalienceParams,
-           "aegis_onset_params": OnsetParams, "aegis_beat_params": BeatParams, "aegis_hpss_params": HpssParams,
+           "aegis_onset_params": OnsetParams, "aegis_beat_params": BeatParams, "aegis_hpss_params": HpssParams, "aegis_dtw_params": DtwParams,
            "aegis_effect": Effect}
 
 _OUT, _ADSR, _SAL = C.POINTER(Outputs), C.POINTER(AdsrParams), C.POINTER(SalienceParams)
@@ -178,6 +183,8 @@ PROTOTYPES = {
     "aegis_istft": (C.c_int, [_P, _P, _P, _I32, _P]),
     "aegis_hpss": (C.c_int, [_P, _PP, _PI64, _I32, C.POINTER(HpssParams), _P, _P]),
     "aegis_hpss_masks": (C.c_int, [_P, _P, _P, _I32, _I32, C.POINTER(HpssParams), _P, _P, _P, _P]),
+    "aegis_dtw": (C.c_int, [_P, _P, _P, _I32, _I32, _P, _P, _I32, C.POINTER(DtwParams), _P, _P, _P, _P, _P]),
+    "aegis_align_chroma": (C.c_int, [_P, _PP, _PI64, _I32, _I32, _I32, _F64, _F64, _I32, _P, _P, _P, _I32, C.POINTER(DtwParams), _P, _P, _P]),
     "aegis_reverb_ir": (_I64, [_F64, _I32, _P, _I64]),
     "aegis_effects": (C.c_int, [_P, _I32, _I32, _PP, _I32, _P, C.POINTER(Effect), _P, _PP, _PP]),
     "aegis_get_table": (_I64, [_P, _S, _P, _I64]),

@@ -774,6 +774,76 @@ class Handle:
         return [{w: a[off[c] * n_bins:off[c + 1] * n_bins].reshape(n_bins, frames[c]).copy() for w, a in out.items()}
                 for c in range(len(images))]
 
+    @staticmethod
+    def dtw_params(metric="cosine", subsequence=False, band=0):
+        """aegis_dtw_params.  The library validates the combination (AegisError from the calls below)."""
+        if metric not in DTW_METRICS:
+            raise ValueError("metric is 'cosine' or 'euclidean'")
+        return DtwParams(DTW_METRICS[metric], int(bool(subsequence)), int(band), 0)
+
+    @staticmethod
+    def _dtw_pairs(lengths, pairs):
+        """(pair_a, pair_b as int32 arrays, per pair its (N, M)); with an index outside the sequences every pair gets
+        (1, 1): the library refuses the call and names the pair"""
+        pa, pb = (np.ascontiguousarray([p[i] for p in pairs], dtype=np.int32) for i in (0, 1))
+        if min(pa.min(), pb.min()) < 0 or max(pa.max(), pb.max()) >= len(lengths):
+            return pa, pb, [(1, 1)] * len(pairs)
+        return pa, pb, [(lengths[a], lengths[b]) for a, b in zip(pa, pb)]
+
+    @staticmethod
+    def _dtw_split(shapes, path, length, cost):
+        """The batch buffers of an alignment call -> per pair (path int32 [L, 2], cost)."""
+        off = _marshal.offsets([n + m - 1 for n, m in shapes])
+        return [(path[off[p]:off[p] + int(length[p])].copy(), float(cost[p])) for p in range(len(shapes))]
+
+    def dtw(self, seqs, pairs, params=None, want_D=False):
+        """aegis_dtw: sequences (float32 [K, n_s] arrays, one K) and pairs ((a, b) indices: a gives the rows) in ONE device
+        call -> per pair (path int32 [L, 2], cost), or (path, cost, D float64 [N, M], steps uint8 [N, M]) with want_D (the
+        probes: at most 2^22 cells per call).  params: dtw_params(...)."""
+        seqs = [np.ascontiguousarray(s, dtype=np.float32) for s in seqs]
+        if not seqs or not len(pairs):
+            return []
+        K = seqs[0].shape[0] if seqs[0].ndim == 2 else -1
+        if any(s.ndim != 2 or s.shape[0] != K for s in seqs):
+            raise ValueError("sequences must be [K, n] arrays of one K")
+        pa, pb, shapes = self._dtw_pairs([s.shape[1] for s in seqs], pairs)
+        flat = _marshal.concat([s.ravel() for s in seqs], np.float32)
+        nf = np.asarray([s.shape[1] for s in seqs], np.int64)
+        cells = sum(n * m for n, m in shapes)
+        path = np.zeros((max(sum(n + m - 1 for n, m in shapes), 1), 2), np.int32)
+        length, cost = np.zeros(len(pairs), np.int64), np.zeros(len(pairs), np.float64)
+        D = np.zeros(max(cells, 1), np.float64) if want_D else None
+        steps = np.zeros(max(cells, 1), np.uint8) if want_D else None
+        self._check(self.lib.aegis_dtw(self._h, flat.ctypes.data, nf.ctypes.data, len(seqs), K, pa.ctypes.data, pb.ctypes.data, len(pairs),
+                                       C.byref(params) if params is not None else None, path.ctypes.data, length.ctypes.data,
+                                       cost.ctypes.data, D.ctypes.data if want_D else None, steps.ctypes.data if want_D else None))
+        out = self._dtw_split(shapes, path, length, cost)
+        if want_D:
+            coff = _marshal.offsets([n * m for n, m in shapes])
+            out = [o + (D[coff[p]:coff[p + 1]].reshape(shapes[p]).copy(), steps[coff[p]:coff[p + 1]].reshape(shapes[p]).copy())
+                   for p, o in enumerate(out)]
+        return out
+
+    def align_chroma(self, clips, pairs, bin_class, params=None, n_chroma=12, n_bins=252, bins_per_octave=36, fmin=32.70319566257483,
+                     filter_scale=1.0):
+        """aegis_align_chroma: the chroma of chroma_cqt(clips, ...) kept on the device and aligned pair by pair ((a, b) clip
+        indices: a gives the rows) in ONE call -> per pair (path int32 [L, 2], cost)."""
+        clips, ptrs, lens = _marshal.clips(clips, np.float32)
+        if not len(clips) or not len(pairs):
+            return []
+        cls = np.ascontiguousarray(bin_class, dtype=np.int32)
+        if len(cls) != n_bins:
+            raise ValueError("bin_class needs one entry per CQT bin")
+        frames = [self.frames_for(len(c)) for c in clips]
+        pa, pb, shapes = self._dtw_pairs(frames, pairs)
+        path = np.zeros((max(sum(n + m - 1 for n, m in shapes), 1), 2), np.int32)
+        length, cost = np.zeros(len(pairs), np.int64), np.zeros(len(pairs), np.float64)
+        self._check(self.lib.aegis_align_chroma(self._h, ptrs, lens, len(clips), int(n_bins), int(bins_per_octave), float(fmin),
+                                                float(filter_scale), int(n_chroma), cls.ctypes.data, pa.ctypes.data, pb.ctypes.data,
+                                                len(pairs), C.byref(params) if params is not None else None, path.ctypes.data,
+                                                length.ctypes.data, cost.ctypes.data))
+        return self._dtw_split(shapes, path, length, cost)
+
     def synth_parse_smf(self, midi_bytes, want_wheel=False):
         """aegis_synth_parse_smf: (notes in the reference's mix order as a SYNTH_NOTE_DTYPE array, mido's length in
         seconds) of a Standard MIDI File; ValueError for bytes that are not one (mido raises).  Host code.

@@ -201,6 +201,7 @@ int aegis_create(const aegis_config *cfg, aegis_handle **out) {
     if (const char *e = std::getenv("AEGIS_TROUGHS_IN_FRAME")) h->troughs_off = (e[0] == '0');
     if (const char *e = std::getenv("AEGIS_OBS_BIN_TABLE")) h->bin_table_off = (e[0] == '0');
     if (const char *e = std::getenv("AEGIS_CQT_BANKS")) { const int v = std::atoi(e); if (v >= 1 && v <= 32) h->cqt_bank_cap = v; }
+    if (const char *e = std::getenv("AEGIS_DTW_PASS_BYTES")) { const long long v = std::atoll(e); if (v >= 1) h->dtw_pass_bytes = v; }
     h->tuning_edges.resize(kTunCells + 1);
     tuning_edges(h->tuning_edges.data());
     if (c.device == -1) { *out = h; return AEGIS_OK; }   // host tables only

@@ -31,6 +31,8 @@
 //                     tracker; kernels in beat.hip, the mel stage and aegis_onset.hip's envelope stage in front of them)
 //   aegis_hpss.hip    aegis_stft, aegis_istft, aegis_hpss (spectrogram, resynthesis, the whole separation), aegis_hpss_masks (running medians along time and bins and the soft masks of median-filter
 //                     harmonic / percussive separation; kernels in hpss.hip, the pass planner that cuts long clips here)
+//   aegis_dtw.hip     aegis_dtw, aegis_align_chroma (dynamic time warping of feature sequences, and of clips through the
+//                     chroma of aegis_cqt.hip's cqt_host_locked; kernels in dtw.hip)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -181,6 +183,10 @@ struct aegis_handle {
     // (aegis_stft: a pass's samples, its three offset tables, the complex spectrum; its magnitudes go to hp_in)
     DevBuf hp_in, hp_harm, hp_perc, hp_mh, hp_mp, hp_segs, hp_flag, hp_pcm, hp_off, hp_D;
     DevBuf hp_fa, hp_fb, hp_ya, hp_yb;        // aegis_istft / aegis_hpss: the float64 resynthesis frames of the two stems, their float32 audio
+    // aegis_dtw / aegis_align_chroma: caller sequences, their unit columns, frame offsets, pair records, one pass's step codes
+    // and boundary rows, the call's paths, path lengths and costs, the probe of D
+    DevBuf dw_seq, dw_unit, dw_foff, dw_pairs, dw_codes, dw_bnd, dw_paths, dw_len, dw_cost, dw_probe;
+    int64_t dtw_pass_bytes = (int64_t)512 << 20;   // codes and boundary rows of one pass (AEGIS_DTW_PASS_BYTES at create; a pair that needs more runs alone)
     bool notefit_store = false;               // AEGIS_NOTEFIT_STORE=1 at create: every candidate rendered once into nf_sig and read by the frames instead of recomputed
     int32_t lag_stride = 0, yin_stride = 0, obs_stride = 0;
     aegis::CallPlan plan;                     // the last call's plan: its host arrays stay alive until the stream drained

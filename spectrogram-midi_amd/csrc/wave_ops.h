@@ -42,6 +42,21 @@ __device__ __forceinline__ int wave_incl_scan(int v, int lane) {
     return v;
 }
 
+// A double moved one lane up the wave: lane l receives lane l - 1's v, lane 0 keeps `first`.  The two halves go through one
+// DPP move each (wave_shr:1, which gfx9 still has: the shift crosses the rows of 16 lanes).
+__device__ __forceinline__ double wave_shr1_f64(double v, double first) {
+    const long long b = __double_as_longlong(v), f = __double_as_longlong(first);
+    const int lo = __builtin_amdgcn_update_dpp((int)f, (int)b, 0x138, 0xf, 0xf, false);
+    const int hi = __builtin_amdgcn_update_dpp((int)(f >> 32), (int)(b >> 32), 0x138, 0xf, 0xf, false);
+    return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
+}
+// lane `src`'s double in every lane; src is the same in all of them
+__device__ __forceinline__ double wave_readlane_f64(double v, int src) {
+    const long long b = __double_as_longlong(v);
+    const int lo = __builtin_amdgcn_readlane((int)b, src), hi = __builtin_amdgcn_readlane((int)(b >> 32), src);
+    return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
+}
+
 // orders a wave's own LDS traffic where its lanes hand data to each other; the other waves are not involved
 __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");

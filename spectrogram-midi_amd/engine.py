@@ -161,6 +161,19 @@ class AegisEngine:
             return 0.0, np.zeros(0, np.float64 if kw.get("units") == "time" else np.int64)
         return _beats.beat_track(self.handle, [y], **kw)[0]
 
+    # ------------------------------------------------------------------ alignment (not a reference method)
+    def align_midi(self, midi_data, path_or_array, **kw):
+        """A Standard MIDI File re-timed to a take (a WAV path or decoded samples): alignment.align_midi_to_audio's dict
+        {"path", "cost", "warp", "events", "midi"} (preset, metric, band by keyword; start_time / end_time for a path)."""
+        from . import alignment
+        if isinstance(path_or_array, (str, bytes)) or hasattr(path_or_array, "__fspath__"):
+            end, start = kw.pop("end_time", None), kw.pop("start_time", 0)
+            srcs = audio_io.load_pcm_files([path_or_array], self.sr, start, (end - start) if end else None)
+            take = self.handle.analyze_pcm(srcs, stages=0, check_finite=True)[0]["y"]
+        else:
+            take = np.ascontiguousarray(path_or_array, dtype=np.float32)
+        return alignment.align_midi_to_audio(midi_data, take, self, **kw)
+
     def _add_beats(self, raws, clips):
         """raw["tempo"] / raw["beat_frames"] of every analysed clip, from ONE aegis_analyze_beats call for the batch."""
         live = [i for i, r in enumerate(raws) if r is not None]
