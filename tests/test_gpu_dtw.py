@@ -11,7 +11,9 @@ alone, reversed, regrouped, and under a pass workspace that forces three passes 
 probes.  aegis_align_chroma: the path is the restated path on the chroma aegis_chroma_cqt returns for the same clips.
 Music: eight notes and the same notes under a known piecewise-linear time map, both rendered by the device synth and
 aligned: every onset lands within T frames (profiles/dtw.json: the CPU composition's worst error plus 2).  Engine:
-align_midi, and reverse_analysis with and without align."""
+align_midi, and reverse_analysis with and without align.
+(More than one round of strips with the probes on -- 513 rows and up, every K, bands, subsequence and ordinary floats there --
+is tests/test_gpu_dtw_rounds.py.)"""
 import json
 import os
 

@@ -39,9 +39,17 @@ def ragged_shapes():
     return out
 
 
-def special_columns(rng, K, n):
+def dyadic_at_once(rng, K, n):
+    """the columns of dyadic, drawn for all n frames at once (other draws from the same distribution: the long sequences)"""
+    nnz = rng.choice([m for m in (1, 4, 16) if m <= K], n)
+    rank = np.argsort(np.argsort(rng.random((K, n)), axis=0), axis=0)           # a random order of the K rows per column
+    x = np.where(rank < nnz[None, :], rng.choice([-1.0, 1.0], (K, n)) * 2.0 ** rng.integers(-3, 4, n)[None, :], 0.0)
+    return x.astype(F32)
+
+
+def special_columns(rng, K, n, base=dyadic):
     """dyadic columns with zero columns, repeated columns (exact three-way ties), FLT_MIN and the two tiny values"""
-    x = dyadic(rng, K, n)
+    x = base(rng, K, n)
     for f in range(n):
         r = f % 11
         if r == 2:
@@ -116,6 +124,174 @@ def property_cases():
 
 def core_cases():
     return shape_cases() + band_cases() + subsequence_cases() + property_cases()
+
+
+# ---- past one round of strips -----------------------------------------------------------------------------------------------
+# The forward kernel gives a pair's 64-row strips to NW waves, NW strips at a time (a round): 8 waves for K <= 12, 4 above.
+# A second round starts at row 64 NW: 513 rows for K <= 12, 257 for K > 12.
+ROUND_NS = {8: (511, 512, 513, 576, 577, 1024, 1025, 1089, 1151), 4: (255, 256, 319, 320, 321, 512, 513, 577)}
+ROUND_KS = {8: (3, 4, 7, 12), 4: (13, 24)}
+ROUND_MS = (1, 2, 63, 64, 65, 130)
+EXTREMES = ((5, 2000), (64, 1100), (65, 1100), (2000, 5), (1100, 2))
+
+
+def waves_of(K):
+    return 8 if K <= 12 else 4
+
+
+def strips_of(N, K):
+    """(rounds, strips, the last strip's last lane with a row) of N rows under K features"""
+    S = (N + 63) // 64
+    return -(-S // waves_of(K)), S, N - 1 - 64 * (S - 1)
+
+
+def round_shapes(NW):
+    """every N of the group against two of ROUND_MS, chosen raggedly: every M occurs in the group"""
+    out = []
+    for k, n in enumerate(ROUND_NS[NW]):
+        at = (5 * k + 3) % len(ROUND_MS)
+        out += [(n, ROUND_MS[at]), (n, ROUND_MS[(at + 3) % len(ROUND_MS)])]
+    return out
+
+
+def _pairs_of(rng, K, shapes, columns=None):
+    columns = columns or (lambda r, k, n: special_columns(r, k, n, dyadic_at_once))
+    seqs, pairs = [], []
+    for n, m in shapes:
+        seqs += [columns(rng, K, n), columns(rng, K, m)]
+        pairs.append((len(seqs) - 2, len(seqs) - 1))
+    return seqs, pairs
+
+
+def round_cases():
+    """rounds_*: rows either side of the first and the second round edge (the first two N of a group are the last sizes of
+    ONE round, the others have two or three), one call per (K, metric).  extremes_*: one strip of 32 phases, two of 18, and
+    32 and 18 strips of one short phase.  square_1025: three rounds of 17 phases, a call of its own."""
+    rng = np.random.default_rng(40)
+    cases = []
+    for NW in (8, 4):
+        for K in ROUND_KS[NW]:
+            for metric in ("cosine", "euclidean"):
+                cases.append(_case(f"rounds_K{K}_{metric}", *_pairs_of(rng, K, round_shapes(NW)), metric))
+    for K in (4, 12, 24):
+        for metric in ("cosine", "euclidean"):
+            cases.append(_case(f"extremes_K{K}_{metric}", *_pairs_of(rng, K, EXTREMES), metric))
+    cases.append(_case("square_1025", *_pairs_of(rng, 12, [(1025, 1025)])))
+    return cases
+
+
+def k_sweep_cases():
+    """every K the entry accepts: the zero padding of a lane's column to 4, 12 or 24 values, the dispatch edges 4|5, 12|13"""
+    rng = np.random.default_rng(41)
+    return [_case(f"sweep_K{K}_{metric}", *_pairs_of(rng, K, [(65, 130), (130, 65)]), metric)
+            for K in range(1, 25) for metric in ("cosine", "euclidean")]
+
+
+def band_round_cases():
+    """a band's per-lane counter past one round: it is set anew from the row and the lane at every round"""
+    rng = np.random.default_rng(42)
+    cases = []
+    for k, band in enumerate((1, 7, 40)):
+        metric = "euclidean" if k == 1 else "cosine"
+        other = "cosine" if k == 1 else "euclidean"
+        cases.append(_case(f"band_rounds_{band}_K12", *_pairs_of(rng, 12, [(1025, 600), (600, 1025), (577, 64), (64, 577)]), metric, band=band))
+        cases.append(_case(f"band_rounds_{band}_K24", *_pairs_of(rng, 24, [(513, 300), (300, 513)]), other, band=band))
+    return cases
+
+
+def distinct_columns(rng, K, n, first_not=-1):
+    """one-hot columns, neighbours different (the first differs from class first_not): a run of them matches only itself"""
+    idx = rng.integers(0, K, n)
+    while idx[0] == first_not:
+        idx[0] = rng.integers(0, K)
+    for f in range(1, n):
+        while idx[f] == idx[f - 1]:
+            idx[f] = rng.integers(0, K)
+    x = np.zeros((K, n), F32)
+    x[idx, np.arange(n)] = 1
+    return x
+
+
+def subsequence_round_cases():
+    """queries of more than one round of rows, cut out of a longer reference: rows 512, 1024 (256, 512 at K = 24) are the
+    first of a round and must NOT start a path; the arg-min of the last row runs over 700 to 1237 columns.
+    Pairs (query, reference) of the K = 12 calls: 600 rows found at 50 .. 649 of 700; the same query in [query | 37 other
+    frames | query], found twice at cost 0 (the first wins, 637 columns before the tied one); 1025 rows found at 100 .. 1124
+    of 1200.  K = 24: 513 rows found at 90 .. 602 of 700."""
+    rng = np.random.default_rng(43)
+    ref, long = distinct_columns(rng, 12, 700), distinct_columns(rng, 12, 1200)
+    query = ref[:, 50:650]
+    other = distinct_columns(rng, 12, 37, first_not=int(np.argmax(query[:, -1])))
+    while np.argmax(other[:, -1]) == np.argmax(query[:, 0]):
+        other = distinct_columns(rng, 12, 37, first_not=int(np.argmax(query[:, -1])))
+    twice = np.concatenate([query, other, query], axis=1)
+    seqs12 = [ref, query, twice, long, long[:, 100:1125]]
+    ref24 = distinct_columns(rng, 24, 700)
+    seqs24 = [ref24, ref24[:, 90:603]]
+    cases = []
+    for metric in ("cosine", "euclidean"):
+        cases.append(_case(f"subsequence_rounds_K12_{metric}", seqs12, [(1, 0), (1, 2), (4, 3)], metric, subsequence=True))
+        cases.append(_case(f"subsequence_rounds_K24_{metric}", seqs24, [(1, 0)], metric, subsequence=True))
+    return cases
+
+
+FLOAT_SEED = 44
+
+
+def float_cases():
+    """ordinary float32 features with the probes on: products and quotients that round.  normal (signed) and uniform [0, 1);
+    the normal calls end with 200 frames against themselves, where a unit column's own dot product rounds to more than 1 on
+    some frames: 1 - dot < 0 before the clamp (tests/test_dtw_restated.py asserts it for FLOAT_SEED)."""
+    rng = np.random.default_rng(FLOAT_SEED)
+    draws = {"normal": lambda r, K, n: r.standard_normal((K, n), F32), "uniform": lambda r, K, n: r.random((K, n), F32)}
+    cases = []
+    for K in (3, 12, 24):
+        for metric in ("cosine", "euclidean"):
+            for kind, draw in draws.items():
+                seqs, pairs = _pairs_of(rng, K, [(130, 65), (577, 130)], draw)
+                if kind == "normal":
+                    seqs.append(draw(rng, K, 200))
+                    pairs.append((len(seqs) - 1, len(seqs) - 1))
+                cases.append(_case(f"float_{kind}_K{K}_{metric}", seqs, pairs, metric))
+    return cases
+
+
+_beyond = []
+
+
+def beyond_cases():
+    """what tests/test_gpu_dtw_rounds.py runs on top of core_cases, built once per process"""
+    if not _beyond:
+        _beyond.extend(round_cases() + k_sweep_cases() + band_round_cases() + subsequence_round_cases() + float_cases())
+    return list(_beyond)
+
+
+def beyond_names():
+    """the names of beyond_cases in its order, without building one (test ids at collection)"""
+    both = ("cosine", "euclidean")
+    names = [f"rounds_K{K}_{m}" for NW in (8, 4) for K in ROUND_KS[NW] for m in both]
+    names += [f"extremes_K{K}_{m}" for K in (4, 12, 24) for m in both] + ["square_1025"]
+    names += [f"sweep_K{K}_{m}" for K in range(1, 25) for m in both]
+    names += [f"band_rounds_{band}_K{K}" for band in (1, 7, 40) for K in (12, 24)]
+    names += [f"subsequence_rounds_K{K}_{m}" for m in both for K in (12, 24)]
+    names += [f"float_{kind}_K{K}_{m}" for K in (3, 12, 24) for m in both for kind in ("normal", "uniform")]
+    return names
+
+
+def beyond_case(name):
+    return {c["name"]: c for c in beyond_cases()}[name]
+
+
+def host_round_cases():
+    """the host program's share of beyond_cases: tools/dtw_host_check.cpp walks every cell of every pair of it"""
+    return beyond_cases()
+
+
+def three_way_ties(D):
+    """cells whose three predecessors are equal and finite"""
+    if D.shape[0] < 2 or D.shape[1] < 2:
+        return 0
+    return int(np.count_nonzero((D[:-1, :-1] == D[1:, :-1]) & (D[:-1, :-1] == D[:-1, 1:]) & np.isfinite(D[:-1, :-1])))
 
 
 def host_cases():

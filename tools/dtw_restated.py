@@ -4,7 +4,7 @@ default step set, from memory of upstream, in a fixed arithmetic order).
   unit(x)            float32 unit columns of x [K, n]: n = sqrt(sum_k x_k x_k) with a float32 accumulator from 0, k ascending,
                      the product rounded, then the add; u = x / n where n > 0, else 0
   cost(a, b, metric) float32 [N, M]: cosine 1 - sum_k u_k v_k (the same accumulator), negative values to 0; euclidean
-                     sqrt(sum_k (x_k - y_k)^2)
+                     sqrt(sum_k (x_k - y_k)^2); cosine_before_clamp(a, b) is the cosine cost with its negative values kept
   inside(N, M, band) bool [N, M]: |i (M-1) - j (N-1)| <= band max(N-1, M-1) in int64 (all True for band 0, N == 1 or M == 1)
   forward(c, ...)    float64 D [N, M] and uint8 codes [N, M] by anti-diagonals: D = c + the smallest of diagonal, left, up in
                      that order (a later one only when strictly smaller); codes 0 / 1 / 2, 3 where a path starts
@@ -29,19 +29,27 @@ def unit(x):
         return np.where(n > 0, x / n, F32(0)).astype(F32)
 
 
+def cosine_before_clamp(a, b):
+    """float32 [N, M]: 1 - the dot product of the unit columns, before negative values go to 0 (for the tests: where it is
+    negative the clamp has something to do)"""
+    a, b = np.ascontiguousarray(a, F32), np.ascontiguousarray(b, F32)
+    u, v = unit(a), unit(b)
+    acc = np.zeros((a.shape[1], b.shape[1]), F32)
+    for k in range(a.shape[0]):
+        acc = acc + u[k][:, None] * v[k][None, :]
+    return (F32(1) - acc).astype(F32)
+
+
 def cost(a, b, metric="cosine"):
     a, b = np.ascontiguousarray(a, F32), np.ascontiguousarray(b, F32)
     if a.ndim != 2 or b.ndim != 2 or a.shape[0] != b.shape[0]:
         raise ValueError("a is [K, N] and b [K, M]")
-    acc = np.zeros((a.shape[1], b.shape[1]), F32)
     if metric == "cosine":
-        u, v = unit(a), unit(b)
-        for k in range(a.shape[0]):
-            acc = acc + u[k][:, None] * v[k][None, :]
-        c = F32(1) - acc
+        c = cosine_before_clamp(a, b)
         return np.where(c < 0, F32(0), c).astype(F32)
     if metric != "euclidean":
         raise ValueError("metric is 'cosine' or 'euclidean'")
+    acc = np.zeros((a.shape[1], b.shape[1]), F32)
     for k in range(a.shape[0]):
         d = a[k][:, None] - b[k][None, :]
         acc = acc + d * d
