@@ -587,6 +587,46 @@ int aegis_cqt_salience(aegis_handle *h, const float *const *pcm, const int64_t *
                        int32_t bins_per_octave, double fmin, double filter_scale, const aegis_salience_params *p,
                        float *mag_out /* NULL ok */, float *sal_out /* NULL ok */, int32_t *cand_bin, float *cand_sal, float *cand_shift);
 
+/* --- Non-negative note-template fit of the constant-Q magnitudes ------------------------------------------------------
+ * Every column of the magnitudes is explained as a non-negative combination of note templates, so that a partial a lower
+ * note accounts for stops counting for its octave.  The reference has no polyphonic path; the semantics are
+ * this project's, stated once in csrc/nnls.h and DESIGN.md 3.21 and pinned to tools/nnls_restated.py: Lee and Seung's
+ * multiplicative update in IEEE float32 with a fixed order, so the same bits come out of the host and of the device.
+ *   W             the dictionary, float32 [n_notes, n_bins] C-order in host memory, row p the template of note p; entries
+ *                 finite and >= 0, every row with a positive entry.  G = W W^T is formed once per call on the host in double.
+ *   frame         mx = max_b M[b]; num[p] = max(sum_b W[p, b] M[b], 0); h[p] = mx; iters times, every den from the old h:
+ *                 den[p] = sum_q G[p, q] h[q]; h[p] = h[p] num[p] / (den[p] + eps_rel mx); h[p] = 0 where h[p] < zero_rel mx.
+ *                 A frame with mx == 0 gives zeros.  Sums ascending, product then sum, no fused operation.
+ *   act_out       NULL, or per clip [n_notes, F_clip]: the activations h.
+ *   candidates    per clip [F_clip, top_k], frame-major, clip after clip: the rows with h > 0 and h >= act_floor * max_p h
+ *                 (one float32 product), activation descending, then row ascending.  Unused slots: row -1, activation 0.
+ *                 cand_* may be NULL when top_k == 0.
+ * A frame scaled by a power of two gives the same result scaled by that power, bit for bit, while nothing underflows or
+ * overflows.  Non-finite magnitudes are handled as aegis_salience handles them: not looked for, nothing rejected; such a
+ * frame's activations are unspecified and no other frame sees it.
+ * aegis_activations takes magnitudes from host memory (per clip [n_bins, n_frames[c]] C-order, clip after clip).
+ * aegis_cqt_activations takes PCM as aegis_cqt does, runs the same CQT (the cached filter bank) into the handle's device
+ * buffer and the fit behind it; mag_out (NULL, or as aegis_cqt's) is the only way the magnitudes cross to the host.  A
+ * frame's results depend on that frame alone: the same bits alone, batched, reversed, regrouped.  When the workspace cannot
+ * be allocated the batch is cut into passes of half as many clips and retried.
+ * AEGIS_ERR_INVALID with a message: n_bins outside 1..256, n_notes outside 1..64, iters outside 0..256 (-1: 30), top_k
+ * outside 0..8, eps_rel zero or non-finite (negative: 2^-20), zero_rel non-finite (negative: 2^-30), act_floor negative or
+ * non-finite, a dictionary entry negative or non-finite, a dictionary row without a positive entry.
+ * Kernel time: "nnls" of aegis_last_kernel_ms (and "cqt").  Blocking; host pointers. */
+typedef struct aegis_nnls_params {
+    int32_t n_notes;                /* P, rows of W: 1..64 */
+    int32_t iters;                  /* 0..256; -1: 30 */
+    float eps_rel;                  /* > 0; negative: 2^-20 */
+    float zero_rel;                 /* >= 0; negative: 2^-30 */
+    float act_floor;                /* >= 0 */
+    int32_t top_k;                  /* 0..8 */
+} aegis_nnls_params;
+int aegis_activations(aegis_handle *h, const float *mag, const int64_t *n_frames, int32_t n_clips, int32_t n_bins, const float *W,
+                      const aegis_nnls_params *p, float *act_out /* NULL ok */, int32_t *cand_row, float *cand_act);
+int aegis_cqt_activations(aegis_handle *h, const float *const *pcm, const int64_t *n_samples, int32_t n_clips, int32_t n_bins,
+                          int32_t bins_per_octave, double fmin, double filter_scale, const float *W, const aegis_nnls_params *p,
+                          float *mag_out /* NULL ok */, float *act_out /* NULL ok */, int32_t *cand_row, float *cand_act);
+
 /* --- Onset strength and onset picking behind the dB mel image ---------------------------------------------------------
  * The reference calls no onset detector; the semantics are librosa 0.10's onset_strength / onset_detect /
  * util.peak_pick / onset_backtrack in a fixed arithmetic order, stated once in csrc/onset.h and DESIGN.md 3.17 and pinned

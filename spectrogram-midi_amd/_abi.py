@@ -96,6 +96,10 @@ class SalienceParams(C.Structure):
                 ("bin_lo", _I32), ("bin_hi", _I32), ("top_k", _I32)]
 
 
+class NnlsParams(C.Structure):
+    _fields_ = [("n_notes", _I32), ("iters", _I32), ("eps_rel", _F32), ("zero_rel", _F32), ("act_floor", _F32), ("top_k", _I32)]
+
+
 class OnsetParams(C.Structure):
     _fields_ = [("lag", _I32), ("max_size", _I32), ("shift", _I32), ("pre_max", _I32), ("post_max", _I32), ("pre_avg", _I32),
                 ("post_avg", _I32), ("wait", _I32), ("normalize", _I32), ("reserved", _I32), ("delta", _F64)]
@@ -123,7 +127,7 @@ class Effect(C.Structure):
 STRUCTS = {"aegis_config": Config, "aegis_outputs": Outputs, "aegis_pcm_clip": PcmClip, "aegis_stream_frames": StreamFrames,
            "aegis_stream_commit": StreamCommit, "aegis_event": Event, "aegis_event_params": EventParams, "aegis_run_fit": RunFit,
            "aegis_event_batch": EventBatch, "aegis_synth_note": SynthNote, "aegis_adsr_params": AdsrParams,
-           "aegis_fit_note": FitNote, "aegis_verify_event": VerifyEvent, "aegis_salience_params": SalienceParams,
+           "aegis_fit_note": FitNote, "aegis_verify_event": VerifyEvent, "aegis_salience_params": SalienceParams, "aegis_nnls_params": NnlsParams,
            "aegis_onset_params": OnsetParams, "aegis_beat_params": BeatParams, "aegis_hpss_params": HpssParams, "aegis_dtw_params": DtwParams,
            "aegis_effect": Effect}
 
@@ -172,6 +176,8 @@ PROTOTYPES = {
     "aegis_verify_techniques": (C.c_int, [_P, _I32, _I32, _PP, _P, _I32, C.POINTER(VerifyEvent), _P, _P, _P, _ADSR, _P, _P, _P, _P, _P, _P]),
     "aegis_salience": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _SAL, _P, _P, _P, _P]),
     "aegis_cqt_salience": (C.c_int, [_P, _PP, _PI64, _I32, _I32, _I32, _F64, _F64, _SAL, _P, _P, _P, _P, _P]),
+    "aegis_activations": (C.c_int, [_P, _P, _P, _I32, _I32, _P, C.POINTER(NnlsParams), _P, _P, _P]),
+    "aegis_cqt_activations": (C.c_int, [_P, _PP, _PI64, _I32, _I32, _I32, _F64, _F64, _P, C.POINTER(NnlsParams), _P, _P, _P, _P]),
     "aegis_onset_strength": (C.c_int, [_P, _P, _P, _I32, _I32, _ONS, _P]),
     "aegis_onset_detect": (C.c_int, [_P, _P, _P, _P, _I32, _ONS, _P, _P, _P]),
     "aegis_analyze_onsets": (C.c_int, [_P, _PP, _PI64, _I32, _ONS, _P, _P, _P, _P]),

@@ -535,6 +535,71 @@ class Handle:
         return self._salience_split(frames, n_bins, K, img, cb, cs, csh), (_marshal.per_clip(mag, frames, n_bins) if want_mag else None)
 
     @staticmethod
+    def nnls_params(n_notes, iters=-1, eps_rel=-1.0, zero_rel=-1.0, act_floor=0.0, top_k=8):
+        """aegis_nnls_params; -1 / a negative value take the library's defaults (30 iterations, eps_rel 2^-20, zero_rel
+        2^-30).  The library validates (AegisError from the calls below)."""
+        p = NnlsParams()
+        p.n_notes, p.iters, p.eps_rel, p.zero_rel, p.act_floor, p.top_k = int(n_notes), int(iters), float(eps_rel), float(zero_rel), float(act_floor), int(top_k)
+        return p
+
+    @staticmethod
+    def _nnls_dictionary(W, params, n_bins):
+        W = np.ascontiguousarray(W, dtype=np.float32)
+        if W.ndim != 2 or W.shape != (int(params.n_notes), n_bins):
+            raise ValueError("the dictionary must be [params.n_notes, n_bins]")
+        return W
+
+    @staticmethod
+    def _nnls_split(frames, n_notes, top_k, act, rows, vals):
+        """The batch buffers of an activations call -> per clip (image or None, rows, activations)."""
+        imgs = _marshal.per_clip(act, frames, n_notes) if act is not None else [None] * len(frames)
+        return list(zip(imgs, *(_marshal.per_clip(a, frames, top_k, frame_major=True) for a in (rows, vals))))
+
+    def activations(self, mags, W, params, want_image=True):
+        """aegis_activations: the non-negative fit of caller magnitudes (a list of float32 [n_bins, F_c] arrays, one n_bins)
+        to the dictionary W float32 [n_notes, n_bins] in ONE device call -> per clip (activations float32 [n_notes, F_c] or
+        None, rows int32 [F_c, top_k] (-1: unused), their activations float32 [F_c, top_k]).  params: nnls_params(...).
+        AegisError with code ERR_INVALID for what the library rejects."""
+        mags = [np.ascontiguousarray(m, dtype=np.float32) for m in mags]
+        if not mags:
+            return []
+        n_bins = mags[0].shape[0]
+        if any(m.ndim != 2 or m.shape[0] != n_bins for m in mags):
+            raise ValueError("magnitudes must be [n_bins, F] arrays of one n_bins")
+        W = self._nnls_dictionary(W, params, n_bins)
+        frames = [m.shape[1] for m in mags]
+        F, K, P = sum(frames), max(int(params.top_k), 0), max(int(params.n_notes), 0)
+        flat = _marshal.concat([m.ravel() for m in mags], np.float32)
+        nf = np.asarray(frames, np.int64)
+        act = np.zeros(F * P, np.float32) if want_image else None
+        rows, vals = np.full(F * K, -1, np.int32), np.zeros(F * K, np.float32)
+        rc = self.lib.aegis_activations(self._h, flat.ctypes.data, nf.ctypes.data, len(mags), n_bins, W.ctypes.data, C.byref(params),
+                                        act.ctypes.data if want_image else None, rows.ctypes.data, vals.ctypes.data)
+        self._check(rc)
+        return self._nnls_split(frames, P, K, act, rows, vals)
+
+    def cqt_activations(self, clips, W, params, n_bins=252, bins_per_octave=36, fmin=32.70319566257483, filter_scale=1.0,
+                        want_mag=False, want_image=False):
+        """aegis_cqt_activations: the CQT of aegis_cqt and the fit behind it on the device -> (per clip tuples as
+        activations() returns them, per clip magnitudes float32 [n_bins, F_c] or None).  The magnitudes leave the device
+        only with want_mag."""
+        clips, ptrs, lens = _marshal.clips(clips, np.float32)
+        n = len(clips)
+        if n == 0:
+            return [], ([] if want_mag else None)
+        W = self._nnls_dictionary(W, params, int(n_bins))
+        frames = [self.frames_for(len(c)) for c in clips]
+        F, K, P = sum(frames), max(int(params.top_k), 0), max(int(params.n_notes), 0)
+        mag = np.zeros(F * n_bins, np.float32) if want_mag else None
+        act = np.zeros(F * P, np.float32) if want_image else None
+        rows, vals = np.full(F * K, -1, np.int32), np.zeros(F * K, np.float32)
+        rc = self.lib.aegis_cqt_activations(self._h, ptrs, lens, n, int(n_bins), int(bins_per_octave), float(fmin), float(filter_scale),
+                                            W.ctypes.data, C.byref(params), mag.ctypes.data if want_mag else None,
+                                            act.ctypes.data if want_image else None, rows.ctypes.data, vals.ctypes.data)
+        self._check(rc)
+        return self._nnls_split(frames, P, K, act, rows, vals), (_marshal.per_clip(mag, frames, n_bins) if want_mag else None)
+
+    @staticmethod
     def onset_params(lag=-1, max_size=-1, shift=-1, pre_max=-1, post_max=-1, pre_avg=-1, post_avg=-1, wait=-1, normalize=-1,
                      delta=-1.0):
         """aegis_onset_params; every argument left at -1 (None too) takes the library's default.  The library validates."""

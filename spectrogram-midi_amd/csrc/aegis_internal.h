@@ -33,6 +33,8 @@
 //                     harmonic / percussive separation; kernels in hpss.hip, the pass planner that cuts long clips here)
 //   aegis_dtw.hip     aegis_dtw, aegis_align_chroma (dynamic time warping of feature sequences, and of clips through the
 //                     chroma of aegis_cqt.hip's cqt_host_locked; kernels in dtw.hip)
+//   aegis_nnls.hip    aegis_activations, aegis_cqt_activations (the non-negative note-template fit of the CQT columns and
+//                     the most active notes per frame; kernel in nnls.hip, the CQT in front of it through cqt_host_locked)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -186,6 +188,9 @@ struct aegis_handle {
     // aegis_dtw / aegis_align_chroma: caller sequences, their unit columns, frame offsets, pair records, one pass's step codes
     // and boundary rows, the call's paths, path lengths and costs, the probe of D
     DevBuf dw_seq, dw_unit, dw_foff, dw_pairs, dw_codes, dw_bnd, dw_paths, dw_len, dw_cost, dw_probe;
+    // aegis_activations / aegis_cqt_activations: caller magnitudes, frame offsets, the transposed dictionary, the Gram matrix,
+    // the activation image, candidate rows and activations
+    DevBuf nn_mag, nn_foff, nn_w, nn_g, nn_act, nn_row, nn_val;
     int64_t dtw_pass_bytes = (int64_t)512 << 20;   // codes and boundary rows of one pass (AEGIS_DTW_PASS_BYTES at create; a pair that needs more runs alone)
     bool notefit_store = false;               // AEGIS_NOTEFIT_STORE=1 at create: every candidate rendered once into nf_sig and read by the frames instead of recomputed
     int32_t lag_stride = 0, yin_stride = 0, obs_stride = 0;

@@ -407,11 +407,26 @@ class AegisEngine:
     # ------------------------------------------------------------------ polyphonic entry (not a reference method)
     _POLY_DEVICE_KW = ("n_bins", "bins_per_octave", "fmin", "filter_scale", "harmonics", "weights", "filter_peaks", "peak_floor",
                        "bin_lo", "bin_hi", "top_k")
+    _NNLS_DEVICE_KW = ("dictionary", "n_bins", "bins_per_octave", "fmin", "filter_scale", "iters", "eps_rel", "zero_rel", "act_floor",
+                       "top_k")
+
+    @staticmethod
+    def _poly_method(kw):
+        """kw without "method", and with the event rule's frame_ratio of the note-template fit filled in; the method."""
+        method = kw.get("method", "salience")
+        if method not in ("salience", "nnls"):
+            raise ValueError("method must be 'salience' or 'nnls'")
+        kw = {k: v for k, v in kw.items() if k != "method"}
+        if method == "nnls":
+            from . import polyphonic
+            kw.setdefault("frame_ratio", polyphonic.NNLS_FRAME_RATIO)
+        return method, kw
 
     def audio_to_midi_polyphonic(self, input_wav_or_array, **kw):
-        """A WAV path or decoded samples -> {"cands": multi-pitch candidates (polyphonic.multipitch_candidates), "rms", "y"},
-        or None for empty audio.  kw: the device defaults of polyphonic.py by name (harmonics, top_k, ...), start_time /
-        end_time for a path."""
+        """A WAV path or decoded samples -> {"cands": multi-pitch candidates (polyphonic.multipitch_candidates, or
+        polyphonic.note_activations with method="nnls"), "rms", "y", "method"}, or None for empty audio.  kw: the device
+        defaults of polyphonic.py by name (harmonics, top_k, ...; with method="nnls": dictionary, iters, act_floor, top_k,
+        ...), start_time / end_time for a path."""
         if isinstance(input_wav_or_array, (str, bytes)) or hasattr(input_wav_or_array, "__fspath__"):
             end, start = kw.get("end_time", None), kw.get("start_time", 0)
             srcs = audio_io.load_pcm_files([input_wav_or_array], self.sr, start, (end - start) if end else None)
@@ -422,8 +437,12 @@ class AegisEngine:
 
     def audio_to_midi_polyphonic_batch(self, clips, want_midi=True, want_events=True, **kw):
         """A folder of decoded clips -> (raw dicts, event lists, SMF bytes per clip): ONE CQT + salience call and ONE rms
-        call on the device for the whole batch, the piano-roll per clip on the host.  Empty clips give (None, [], None)."""
+        call on the device for the whole batch, the piano-roll per clip on the host.  Empty clips give (None, [], None).
+        method="nnls": the candidates are the most active notes of the non-negative note-template fit (DESIGN.md 3.21;
+        dictionary=(W, bins) for templates of the caller's own), frame_ratio defaults to 0.2 and top_k to 8;
+        method="salience" (the default) is harmonic summation."""
         from . import polyphonic
+        method, kw = self._poly_method(kw)
         clips = [np.ascontiguousarray(c, dtype=np.float32) for c in clips]
         live = [i for i, c in enumerate(clips) if len(c) > 0]
         raws, events, blobs = [None] * len(clips), [[] for _ in clips], [None] * len(clips)
@@ -431,10 +450,15 @@ class AegisEngine:
             return raws, events, blobs
         h = self.handle
         batch = [clips[i] for i in live]
-        cands = polyphonic.multipitch_candidates(h, batch, **{k: kw[k] for k in self._POLY_DEVICE_KW if k in kw})
+        if method == "nnls":
+            cands = polyphonic.note_activations(h, batch, **{k: kw[k] for k in self._NNLS_DEVICE_KW if k in kw})
+        else:
+            cands = polyphonic.multipitch_candidates(h, batch, **{k: kw[k] for k in self._POLY_DEVICE_KW if k in kw})
         rms = h.analyze_batch(batch, stages=_lib.STAGE_RMS, check_finite=True)
         for i, c, r in zip(live, cands, rms):
             raws[i] = {"cands": c, "rms": r["rms"], "y": clips[i]}
+            if method == "nnls":
+                raws[i]["method"] = method
         if kw.get("onsets", False):
             self._add_onsets(raws, clips)
         if kw.get("beats", False):
@@ -451,8 +475,10 @@ class AegisEngine:
 
     def extract_events_polyphonic(self, raw, output_mid, **kw):
         """raw of audio_to_midi_polyphonic -> note events (polyphonic.get_midi_events_polyphonic), optional SMF to a path
-        or a file-like object through the engine's writer."""
+        or a file-like object through the engine's writer.  A raw dict of method="nnls" carries its method: frame_ratio
+        defaults to 0.2 for it."""
         from . import polyphonic
+        _, kw = self._poly_method(dict(kw, method=kw.get("method", raw.get("method", "salience"))))
         events = polyphonic.get_midi_events_polyphonic(raw["cands"], raw["rms"], self.sr, self.hop_length, **kw)
         events = self._post_passes(events, raw, kw, monophonic=False)
         if output_mid:

@@ -5,6 +5,9 @@ reference's schema (midi_logic.get_midi_events), written by the existing SMF wri
 The reference has no polyphonic path: the semantics are the project's own, pinned to
 tools/salience_restated.py.  This is a threshold piano-roll over plain harmonic summation, not a transcription model:
 DESIGN.md 3.16 records where it stops (an open E chord's G#3 reaches 0.38 of the frame maximum, below the default 0.5).
+The second method (harmonic_dictionary, note_activations; csrc/nnls.h) explains every CQT column as a
+non-negative combination of harmonic note templates on the device (aegis_cqt_activations), so that a partial a lower note
+accounts for stops counting for its octave; its candidates go through the same event rule.
 
 Event rule (quirk-compatible with midi_logic.py: `end` inclusive, frame counts int(ms / 1000 * sr / hop), a note kept when
 end - start >= min frames):
@@ -28,6 +31,11 @@ HARMONICS = (1, 2, 3, 4, 5)                   # weights 1 / h
 PEAK_FLOOR = 0.02
 TOP_K = 6
 _RANGE = ("E2", "C6")                         # the engine's own pitch range
+# the note-template fit (method "nnls": csrc/nnls.h)
+NNLS_NOTES = tuple(range(40, 85))             # E2..C6 as MIDI numbers
+NNLS_HARMONICS = (1, 2, 3, 4, 5, 6)           # weights 1 / h
+NNLS_TOP_K = 8
+NNLS_FRAME_RATIO = 0.2
 
 
 def bin_of(freq, fmin=FMIN, bins_per_octave=BINS_PER_OCTAVE):
@@ -65,6 +73,68 @@ def candidate_dict(bins, sal, shift, fmin=FMIN, bins_per_octave=BINS_PER_OCTAVE)
     used = bins >= 0
     freqs = np.where(used, float(fmin) * 2.0 ** ((bins.astype(np.float64) + shift.astype(np.float64)) / bins_per_octave), 0.0)
     return {"bins": bins, "freqs": freqs, "sal": sal, "shift": shift}
+
+
+def harmonic_dictionary(notes=NNLS_NOTES, n_bins=N_BINS, bins_per_octave=BINS_PER_OCTAVE, fmin=FMIN, harmonics=NNLS_HARMONICS,
+                        weights=None, filter_scale=1.0, sr=44100):
+    """The note templates of the fit: (W float32 [P, n_bins], bins int32 [P]), row p the magnitudes the bank shows for
+    note notes[p] (MIDI numbers) with partials `harmonics` at amplitudes `weights` (1 / h), bins[p] its fundamental bin.
+    Harmonic h of a note at bin b0 lands at b0 + k_h, split towards b0 + k_h + 1 with the a_h of csrc/salience.h (1 - a_h
+    and a_h); each of the two entries is scaled by sqrt(N_b), the bank's scale=True factor, N_b = filter_scale sr /
+    (f_b alpha) as the bank forms its lengths; entries outside the grid are dropped.  Built in float64, rows normalised to
+    unit L2, rounded once.  Templates matched to an instrument are the point: this is the default, not the only one."""
+    harmonics = [float(h) for h in harmonics]
+    weights = [1.0 / h for h in harmonics] if weights is None else [float(w) for w in weights]
+    if len(weights) != len(harmonics) or min(harmonics) <= 0 or min(weights) < 0:
+        raise ValueError("one non-negative weight per positive harmonic")
+    r = 2.0 ** (1.0 / bins_per_octave)
+    alpha = (r ** 2 - 1) / (r ** 2 + 1)
+    lengths = (filter_scale / alpha) * sr / (float(fmin) * 2.0 ** (np.arange(n_bins) / bins_per_octave))
+    root = np.sqrt(lengths)
+    W = np.zeros((len(notes), n_bins), np.float64)
+    bins = np.zeros(len(notes), np.int32)
+    for p, note in enumerate(notes):
+        b0 = bin_of(440.0 * 2.0 ** ((note - 69) / 12.0), fmin, bins_per_octave)
+        bins[p] = b0
+        for h, w in zip(harmonics, weights):
+            q = bins_per_octave * np.log2(h)
+            if abs(q - np.rint(q)) <= 1e-9:
+                k, a = int(np.rint(q)), 0.0
+            else:
+                k = int(np.floor(q))
+                a = (np.exp2((q - k) / bins_per_octave) - 1.0) / (np.exp2(1.0 / bins_per_octave) - 1.0)
+            j = b0 + k
+            if 0 <= j < n_bins:
+                W[p, j] += w * (1.0 - a) * root[j]
+            if a != 0.0 and 0 <= j + 1 < n_bins:
+                W[p, j + 1] += w * a * root[j + 1]
+        norm = np.sqrt((W[p] * W[p]).sum())
+        if not norm > 0:
+            raise ValueError(f"note {note} has no partial on the grid")
+        W[p] /= norm
+    return W.astype(np.float32), bins
+
+
+def note_activations(handle, clips, dictionary=None, n_bins=N_BINS, bins_per_octave=BINS_PER_OCTAVE, fmin=FMIN, filter_scale=1.0,
+                     iters=-1, eps_rel=-1.0, zero_rel=-1.0, act_floor=0.0, top_k=NNLS_TOP_K):
+    """The top_k most active notes of every frame of every clip, CQT and fit in one device call (aegis_cqt_activations):
+    per clip a dict in the shape of multipitch_candidates -- bins int32 [F, top_k] the notes' fundamental bins (-1:
+    unused), freqs float64 [F, top_k], sal float32 [F, top_k] the activations (descending along a frame), shift zeros --
+    so get_midi_events_polyphonic and the SMF writer take it as it is.  dictionary: (W, bins) as harmonic_dictionary
+    returns them (the default: its defaults on this grid)."""
+    W, bins = harmonic_dictionary(n_bins=n_bins, bins_per_octave=bins_per_octave, fmin=fmin, filter_scale=filter_scale) \
+        if dictionary is None else dictionary
+    W = np.ascontiguousarray(W, np.float32)
+    bins = np.ascontiguousarray(bins, np.int32)
+    if W.ndim != 2 or bins.shape != (W.shape[0],):
+        raise ValueError("dictionary: (W [P, n_bins], bins [P])")
+    p = _lib.Handle.nnls_params(W.shape[0], iters, eps_rel, zero_rel, act_floor, top_k)
+    res, _ = handle.cqt_activations(clips, W, p, n_bins, bins_per_octave, fmin, filter_scale)
+    out = []
+    for _, rows, act in res:
+        b = np.where(rows >= 0, bins[np.maximum(rows, 0)], -1).astype(np.int32)
+        out.append(candidate_dict(b, act, np.zeros(act.shape, np.float32), fmin, bins_per_octave))
+    return out
 
 
 def get_midi_events_polyphonic(cands, rms, sr, hop, **kw):
