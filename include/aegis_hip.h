@@ -1081,6 +1081,55 @@ int64_t aegis_debug_stream_fetch(aegis_stream *st, const char *name, void *dst, 
 int64_t aegis_debug_plan(aegis_handle *h, const int64_t *n_samples, int32_t n_clips, int32_t entry, int32_t sync,
                          int32_t n_cus, int64_t *dst, int64_t cap);
 
+/* ---- time-stretch, time warp, resampling at any ratio, pitch shift (csrc/pvoc.h is the contract; tools/pvoc_restated.py
+ * restates it) ----
+ * The phase vocoder is librosa 0.10's phase_vocoder generalised to an arbitrary time map and restated without angle, sin or
+ * cos: the phase of a bin is kept as a unit complex number in float64, advanced by the rotor
+ * r_t = w / |w|, w = unit(D[k, i + 1]) * conj(unit(D[k, i])), i = int(steps[t]) (unit: widened, an exactly zero value
+ * replaced by 1), the magnitude is (1 - alpha) |D[k, i]| + alpha |D[k, i + 1]| in float64 over the float32 magnitudes of
+ * aegis_stft, alpha = steps[t] - i, and columns F and F + 1 of D read as zero.  The product P_t of the rotors is taken in a
+ * fixed order (blocks of 64 frames, a Kogge-Stone scan inside a block, a serial carry over the blocks), so the result
+ * repeats bit for bit and equals the host restatement.  IEEE basic operations and sqrt only.
+ *   aegis_pvoc_steps     (host only, no handle) steps[i] = fl(i * rate) for every i >= 0 with fl(i * rate) < n_frames: the
+ *                        map of a constant rate.  Returns the count and copies min(count, cap) of them; -1 for a rate that
+ *                        is not finite and > 0, n_frames < 1 or more than 2^31 steps.
+ *   aegis_phase_vocoder  D from host memory as aegis_stft lays it out (per clip complex64 [1025, n_frames[c]], clip after
+ *                        clip), steps float64, n_steps[c] per clip one after the other, every value finite with
+ *                        0 <= step < n_frames[c] (they need not be monotone) -> D_out per clip complex64 [1025, n_steps[c]].
+ *                        Every clip has at least one frame and one step.
+ *   aegis_time_warp      PCM as aegis_analyze_batch takes it -> aegis_stft, the phase vocoder along steps (against the clip's
+ *                        1 + n_samples / hop frames), aegis_istft's resynthesis of the n_steps[c] frames, cut to n_out[c]
+ *                        samples (a sample no frame reaches is 0); y_out float32, the clips one after the other.  Nothing
+ *                        of either spectrogram leaves the device.  time_stretch(y, rate) is steps = aegis_pvoc_steps(F, rate)
+ *                        with n_out = round-half-even(n / rate).
+ *   aegis_resample       band-limited interpolation at ratio[c] (any finite ratio > 0): n_out = ceil(n_samples[c] * ratio[c])
+ *                        samples per clip into y_out.  win: the 32 769 float64 entries of the interpolation table (64 zero
+ *                        crossings, 512 per crossing; resampy's kaiser_best shape, built by the caller: sinc and i0 are not
+ *                        IEEE basic operations).  Output t sums, over the input samples m in ascending order with
+ *                        p = |t / ratio - m| * min(1, ratio) * 512 <= 32768, the linearly interpolated table value at p
+ *                        times x[m] into one float64 accumulator, times min(1, ratio), rounded to float32.  Independent of
+ *                        the handle's framing.
+ *   aegis_pitch_shift    librosa.effects.pitch_shift: rate[c] = 2^(-n_steps / bins_per_octave), evaluated by the caller;
+ *                        the time warp at that constant rate, resampled by ratio = rate, cut or zero-padded to
+ *                        n_samples[c].  The stretched audio stays on the device between the two stages.
+ * The handle's n_fft must be 2048 and its hop 1..2048 (aegis_phase_vocoder, aegis_time_warp, aegis_pitch_shift): otherwise
+ * AEGIS_ERR_UNSUPPORTED.  Samples are checked as with AEGIS_OPT_CHECK_FINITE (the message names clip and sample).  Invalid
+ * requests -- a null argument, a clip without steps, a step that is negative, >= n_frames[c] or not finite, a rate or ratio
+ * that is not finite and > 0, a table of another length -- are rejected before the device is looked at (a device = -1
+ * handle rejects the same ones and answers AEGIS_ERR_DEVICE to a valid one).  Passes are whole clips (the handle's
+ * max_frames_per_pass bounds the input and output frames of one); a clip's results depend on that clip alone.
+ * Kernel time: "hpss_stft", "pvoc", "hpss_synth" and "resample" of aegis_last_kernel_ms, summed over a call's passes.
+ * Blocking; host pointers. */
+int64_t aegis_pvoc_steps(int64_t n_frames, double rate, double *dst, int64_t cap);
+int aegis_phase_vocoder(aegis_handle *h, const float *D, const int64_t *n_frames, const double *steps, const int64_t *n_steps,
+                        int32_t n_clips, float *D_out);
+int aegis_time_warp(aegis_handle *h, const float *const *pcm, const int64_t *n_samples, const double *steps,
+                    const int64_t *n_steps, const int64_t *n_out, int32_t n_clips, float *y_out);
+int aegis_resample(aegis_handle *h, const float *const *pcm, const int64_t *n_samples, int32_t n_clips, const double *ratio,
+                   const double *win, int64_t n_win, float *y_out);
+int aegis_pitch_shift(aegis_handle *h, const float *const *pcm, const int64_t *n_samples, int32_t n_clips, const double *rate,
+                      const double *win, int64_t n_win, float *y_out);
+
 /* Kernel timing of the most recent aegis_analyze_batch_device() with sync != 0,
  * measured with hipEvents on the stream the kernels ran on.  name in
  * {"frame","pyin_obs","viterbi","finalize","total"}; milliseconds,

@@ -191,6 +191,11 @@ PROTOTYPES = {
     "aegis_hpss_masks": (C.c_int, [_P, _P, _P, _I32, _I32, C.POINTER(HpssParams), _P, _P, _P, _P]),
     "aegis_dtw": (C.c_int, [_P, _P, _P, _I32, _I32, _P, _P, _I32, C.POINTER(DtwParams), _P, _P, _P, _P, _P]),
     "aegis_align_chroma": (C.c_int, [_P, _PP, _PI64, _I32, _I32, _I32, _F64, _F64, _I32, _P, _P, _P, _I32, C.POINTER(DtwParams), _P, _P, _P]),
+    "aegis_pvoc_steps": (_I64, [_I64, _F64, _P, _I64]),
+    "aegis_phase_vocoder": (C.c_int, [_P, _P, _P, _P, _P, _I32, _P]),
+    "aegis_time_warp": (C.c_int, [_P, _PP, _PI64, _P, _P, _P, _I32, _P]),
+    "aegis_resample": (C.c_int, [_P, _PP, _PI64, _I32, _P, _P, _I64, _P]),
+    "aegis_pitch_shift": (C.c_int, [_P, _PP, _PI64, _I32, _P, _P, _I64, _P]),
     "aegis_reverb_ir": (_I64, [_F64, _I32, _P, _I64]),
     "aegis_effects": (C.c_int, [_P, _I32, _I32, _PP, _I32, _P, C.POINTER(Effect), _P, _PP, _PP]),
     "aegis_get_table": (_I64, [_P, _S, _P, _I64]),

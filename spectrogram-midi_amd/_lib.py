@@ -806,6 +806,83 @@ class Handle:
         return [(yh[off[c]:off[c + 1]].copy() if want_harm else None, yp[off[c]:off[c + 1]].copy() if want_perc else None)
                 for c in range(n)]
 
+    def phase_vocoder(self, spectrograms, steps):
+        """aegis_phase_vocoder: complex64 [1025, F_c] spectrograms and one float64 time map per clip (0 <= step < F_c) in ONE
+        call -> list of complex64 [1025, len(steps_c)]."""
+        Ds = [np.ascontiguousarray(D, np.complex64) for D in spectrograms]
+        maps = [np.ascontiguousarray(s, np.float64) for s in steps]
+        if len(Ds) != len(maps):
+            raise ValueError("one time map per spectrogram")
+        if not Ds:
+            return []
+        for D, s in zip(Ds, maps):
+            if D.ndim != 2 or D.shape[0] != 1025 or s.ndim != 1:
+                raise ValueError(f"a spectrogram is [1025, F] and its time map one-dimensional, not {D.shape} and {s.shape}")
+        flat = _marshal.concat([D.ravel() for D in Ds] + [np.zeros(1, np.complex64)], np.complex64)
+        st = _marshal.concat(maps + [np.zeros(1)], np.float64)
+        F, T = np.asarray([D.shape[1] for D in Ds], np.int64), np.asarray([len(s) for s in maps], np.int64)
+        out = np.zeros(max(int(T.sum()), 1) * 1025, np.complex64)
+        self._check(self.lib.aegis_phase_vocoder(self._h, flat.ctypes.data, F.ctypes.data, st.ctypes.data, T.ctypes.data, len(Ds), out.ctypes.data))
+        return _marshal.per_clip(out, [int(t) for t in T], 1025)
+
+    def time_warp(self, clips, steps, lengths):
+        """aegis_time_warp: PCM clips, one float64 time map per clip (in frames of the clip's own spectrogram) and the output
+        lengths in ONE call -> list of float32 [lengths[c]].  Nothing of either spectrogram leaves the device."""
+        clips, ptrs, lens = _marshal.clips(clips, np.float32)
+        maps = [np.ascontiguousarray(s, np.float64) for s in steps]
+        n_out = [int(n) for n in lengths]
+        if not len(clips) == len(maps) == len(n_out):
+            raise ValueError("one time map and one output length per clip")
+        if not clips:
+            return []
+        if any(s.ndim != 1 for s in maps) or any(n < 0 for n in n_out):
+            raise ValueError("a time map is one-dimensional and an output length >= 0")
+        st = _marshal.concat(maps + [np.zeros(1)], np.float64)
+        T, no = np.asarray([len(s) for s in maps], np.int64), np.asarray(n_out, np.int64)
+        y = np.zeros(max(sum(n_out), 1), np.float32)
+        self._check(self.lib.aegis_time_warp(self._h, ptrs, lens, st.ctypes.data, T.ctypes.data, no.ctypes.data, len(clips), y.ctypes.data))
+        off = _marshal.offsets(n_out)
+        return [y[off[c]:off[c + 1]].copy() for c in range(len(clips))]
+
+    def _per_clip_value(self, value, n, what):
+        v = np.ascontiguousarray(np.broadcast_to(np.asarray(value, np.float64), (n,)) if np.ndim(value) == 0 else value, np.float64)
+        if v.shape != (n,):
+            raise ValueError(f"one {what} for the batch or one per clip")
+        return v
+
+    def resample(self, clips, ratio, win):
+        """aegis_resample: band-limited interpolation of PCM clips at `ratio` (one for the batch or one per clip; any finite
+        ratio > 0) in ONE call -> list of float32 [ceil(n * ratio)].  win: timescale.interp_table()."""
+        clips, ptrs, lens = _marshal.clips(clips, np.float32)
+        n = len(clips)
+        if n == 0:
+            return []
+        r = self._per_clip_value(ratio, n, "ratio")
+        win = np.ascontiguousarray(win, np.float64)
+        sizes = []
+        for c, q in zip(clips, r):
+            v = len(c) * float(q) if np.isfinite(q) and q > 0 else 0.0
+            sizes.append(int(v) + (int(v) < v) if v <= 2.0 ** 31 else 0)       # (the entry refuses the call in either case)
+        y = np.zeros(max(sum(sizes), 1), np.float32)
+        self._check(self.lib.aegis_resample(self._h, ptrs, lens, n, r.ctypes.data, win.ctypes.data, len(win), y.ctypes.data))
+        off = _marshal.offsets(sizes)
+        return [y[off[c]:off[c + 1]].copy() for c in range(n)]
+
+    def pitch_shift(self, clips, rate, win):
+        """aegis_pitch_shift: the time stretch of PCM clips at `rate` (one for the batch or one per clip) resampled by the
+        same ratio, cut or padded to each clip's own length, in ONE call -> list of float32 [n]."""
+        clips, ptrs, lens = _marshal.clips(clips, np.float32)
+        n = len(clips)
+        if n == 0:
+            return []
+        r = self._per_clip_value(rate, n, "rate")
+        win = np.ascontiguousarray(win, np.float64)
+        sizes = [len(c) for c in clips]
+        y = np.zeros(max(sum(sizes), 1), np.float32)
+        self._check(self.lib.aegis_pitch_shift(self._h, ptrs, lens, n, r.ctypes.data, win.ctypes.data, len(win), y.ctypes.data))
+        off = _marshal.offsets(sizes)
+        return [y[off[c]:off[c + 1]].copy() for c in range(n)]
+
     @staticmethod
     def hpss_params(win_harm=-1, win_perc=-1, power=0.0, margin_harm=0.0, margin_perc=0.0, pass_frames=0):
         """aegis_hpss_params; every argument left at its default (None too) takes the library's (windows of 31, power 2,
@@ -1137,6 +1214,13 @@ def resample_taps(up, down):
     """aegis_resample_taps: the library's built-in low-pass for a rate pair (host code, no handle, no GPU)."""
     return _marshal.sized(lambda dst, cap: load().aegis_resample_taps(int(up), int(down), dst, cap), np.float32,
                           lambda rc: AegisError(rc, "bad rate pair"))
+
+
+def pvoc_steps(n_frames, rate):
+    """aegis_pvoc_steps: the time map of a constant rate, float64 fl(i * rate) while below n_frames (host code, no handle,
+    no GPU)."""
+    return _marshal.sized(lambda dst, cap: load().aegis_pvoc_steps(int(n_frames), float(rate), dst, cap), np.float64,
+                          lambda rc: AegisError(rc, "a rate that is finite and > 0 and at least one frame are needed (at most 2^31 steps)"))
 
 
 def reverb_ir(room_size, sr):

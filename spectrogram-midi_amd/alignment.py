@@ -10,6 +10,9 @@ synth, aligns the render (rows) to a take (columns) and re-times every note thro
   * warp[i] is the smallest take frame paired with render frame i;
   * a note's frames are rint(seconds * sr / hop), kept inside the render; start' = warp[start], end' = max(warp[end], start');
   * every other field of the note is kept; the re-timed notes are written by the package's SMF writer (smf.render).
+
+conform_audio goes the other way: it brings the take onto the render's frames with the device time warp (timescale.time_warp)
+along the smoothed warp (steps_of_warp), so that the take and the render can be crossfaded without drifting.
 """
 import numpy as np
 
@@ -96,3 +99,27 @@ def align_midi_to_audio(midi_data, take, engine, preset="electric_clean", **kw):
     events = retime_notes(notes, warp, engine.sr, engine.hop_length)
     return {"path": res["path"], "cost": res["cost"], "warp": warp, "events": events,
             "midi": smf.render(events, engine.sr, engine.hop_length)}
+
+
+def steps_of_warp(warp, F_take, smooth=43):
+    """float64 [len(warp)]: the time map of the device time warp from an integer warp -- its running mean over a centred
+    window of `smooth` frames (clipped at the ends), clipped to [0, F_take - 1].  The staircase DTW returns would repeat and
+    skip frames of the take; the mean turns it into a slope.  Host NumPy."""
+    w = np.asarray(warp, np.float64).ravel()
+    smooth = int(smooth)
+    if smooth < 1 or F_take < 1 or not len(w):
+        raise ValueError("a warp of at least one frame, smooth >= 1 and F_take >= 1 are needed")
+    r0, r1 = (smooth - 1) // 2, smooth // 2
+    cs = np.concatenate([[0.0], np.cumsum(w)])
+    i = np.arange(len(w))
+    lo, hi = np.maximum(i - r0, 0), np.minimum(i + r1 + 1, len(w))
+    return np.clip((cs[hi] - cs[lo]) / (hi - lo), 0.0, float(F_take - 1))
+
+
+def conform_audio(take, warp, engine, smooth=43):
+    """The take on the render's frames: float32 of len(warp) frames (len(warp) * hop samples), frame i of it taken from
+    the take's frame steps_of_warp(warp)[i], in one device call."""
+    from . import timescale
+    take = np.ascontiguousarray(take, dtype=np.float32)
+    steps = steps_of_warp(warp, engine.handle.frames_for(len(take)), smooth)
+    return timescale.time_warp(engine.handle, [take], [steps], [len(steps) * engine.hop_length])[0]

@@ -35,6 +35,9 @@
 //                     chroma of aegis_cqt.hip's cqt_host_locked; kernels in dtw.hip)
 //   aegis_nnls.hip    aegis_activations, aegis_cqt_activations (the non-negative note-template fit of the CQT columns and
 //                     the most active notes per frame; kernel in nnls.hip, the CQT in front of it through cqt_host_locked)
+//   aegis_pvoc.hip    aegis_pvoc_steps, aegis_phase_vocoder, aegis_time_warp, aegis_resample, aegis_pitch_shift (phase vocoder
+//                     along a time map, band-limited resampling; kernels in pvoc.hip, the STFT and the resynthesis
+//                     around them hpss.hip's, the pass of whole clips clip_pass.h's, which aegis_hpss.hip shares)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -191,7 +194,10 @@ struct aegis_handle {
     // aegis_activations / aegis_cqt_activations: caller magnitudes, frame offsets, the transposed dictionary, the Gram matrix,
     // the activation image, candidate rows and activations
     DevBuf nn_mag, nn_foff, nn_w, nn_g, nn_act, nn_row, nn_val;
-    int64_t dtw_pass_bytes = (int64_t)512 << 20;   // codes and boundary rows of one pass (AEGIS_DTW_PASS_BYTES at create; a pair that needs more runs alone)
+    // aegis_phase_vocoder / aegis_time_warp / aegis_resample / aegis_pitch_shift: a pass's steps, clip records, the output
+    // side's offset tables, the vocoder's spectrum D', the interpolation table, resampling records, resampled audio
+    DevBuf pv_steps, pv_clips, pv_off, pv_D2, pv_win, pv_res, pv_y;
+    int64_t dtw_pass_bytes =(int64_t)512 << 20;   // codes and boundary rows of one pass (AEGIS_DTW_PASS_BYTES at create; a pair that needs more runs alone)
     bool notefit_store = false;               // AEGIS_NOTEFIT_STORE=1 at create: every candidate rendered once into nf_sig and read by the frames instead of recomputed
     int32_t lag_stride = 0, yin_stride = 0, obs_stride = 0;
     aegis::CallPlan plan;                     // the last call's plan: its host arrays stay alive until the stream drained

@@ -174,6 +174,44 @@ class AegisEngine:
             take = np.ascontiguousarray(path_or_array, dtype=np.float32)
         return alignment.align_midi_to_audio(midi_data, take, self, **kw)
 
+    # ------------------------------------------------------------------ time and pitch (not reference methods)
+    def _samples_of(self, path_or_array, start_time=0, end_time=None):
+        """decoded samples at the engine's rate of a WAV path, or the array itself as float32"""
+        if isinstance(path_or_array, (str, bytes)) or hasattr(path_or_array, "__fspath__"):
+            srcs = audio_io.load_pcm_files([path_or_array], self.sr, start_time, (end_time - start_time) if end_time else None)
+            return self.handle.analyze_pcm(srcs, stages=0, check_finite=True)[0]["y"]
+        return np.ascontiguousarray(path_or_array, dtype=np.float32)
+
+    def time_stretch(self, path_or_array, rate):
+        """librosa.effects.time_stretch on the device: the take `rate` times as fast, float32 [round(n / rate)]."""
+        from . import timescale
+        return timescale.time_stretch(self.handle, [self._samples_of(path_or_array)], rate)[0]
+
+    def pitch_shift(self, path_or_array, n_steps, bins_per_octave=12):
+        """librosa.effects.pitch_shift on the device: the take n_steps (fractions allowed) higher, float32 [n]."""
+        from . import timescale
+        return timescale.pitch_shift(self.handle, [self._samples_of(path_or_array)], n_steps, bins_per_octave)[0]
+
+    def retune(self, path_or_array):
+        """The take shifted back onto the equal-tempered grid: (audio float32 [n], the device tuning estimate in
+        fractions of a semitone that it was shifted by the negative of).  A second estimate on the result is the check."""
+        from . import timescale
+        y = self._samples_of(path_or_array)
+        if len(y) == 0:
+            return y, 0.0
+        tuning = self.handle.estimate_tuning([y], bins_per_octave=12)[0]
+        if tuning == 0.0:
+            return y.copy(), 0.0
+        return timescale.pitch_shift(self.handle, [y], -tuning, 12)[0], tuning
+
+    def conform_take(self, midi_data, path_or_array, smooth=43, **align_kw):
+        """The take brought onto the timeline of its MIDI file's render: align_midi, then alignment.conform_audio along
+        the smoothed warp -> (audio float32 of len(warp) frames, warp, the re-timed events)."""
+        from . import alignment
+        take = self._samples_of(path_or_array, align_kw.pop("start_time", 0), align_kw.pop("end_time", None))
+        res = alignment.align_midi_to_audio(midi_data, take, self, **align_kw)
+        return alignment.conform_audio(take, res["warp"], self, smooth), res["warp"], res["events"]
+
     def _add_beats(self, raws, clips):
         """raw["tempo"] / raw["beat_frames"] of every analysed clip, from ONE aegis_analyze_beats call for the batch."""
         live = [i for i, r in enumerate(raws) if r is not None]
